@@ -16,6 +16,9 @@ Rank 0 prints ONE JSON line: the contract fields plus
                    launch duration measured live with events on the launch stream, vs 8 TB/s HBM
   "cpu_baseline" — the CPU oracle (a port of the reference's op order) timed on this host's cores
                    on a bounded sample of the same workload (rank 0, N=1 only).
+
+`--dump-outputs DIR` writes what the last timed step computed (outputs, loss, updated parameters) as DIR/<name>.npy; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -67,10 +70,36 @@ def parse():
     ap.add_argument('--cpu-batch', type=int, default=512)
     ap.add_argument('--cpu-threads', type=int, default=16)
     ap.add_argument('--hop-order', type=int, default=9, help='syn_hop: order of the high-order factors (train_syn_hop_factor.py --hop_order)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (model outputs, loss, updated parameters) '
+                         'as DIR/<name>.npy in float32 / float64 (rank 0; at most 64 MB in all), to compare two builds output for output')
     a = ap.parse_args()
     if a.batch is None:
         a.batch = {'ldpc': 4096, 'syn_pw': 256, 'syn_hop': 1024}[a.workload]
     return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """`arrays` (name -> tensor) as `path/<name>.npy`: floating tensors keep float64 or become float32, integer ones become float64.
+    Past DUMP_LIMIT_BYTES in all, an array larger than an equal share of the budget is cut to that share by a fixed, seeded sample
+    of its flattened elements (in index order), so two runs stay comparable element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 or not torch.is_floating_point(t) else t.float()
+        host[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    share = DUMP_LIMIT_BYTES // max(len(host), 1)
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES and a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
+    return sorted(host)
 
 
 def loss_fn(logits, snr_pred, label, sigma_b):
@@ -423,14 +452,19 @@ def main_syn(args):
         pred, _ = model(nf, [pws, hi], [[rep_i(idx_pw), rep_e(et_pw)], [rep_i(idx_hi), rep_e(et_hi)]])
         return pred
 
+    keep = {} if args.dump_outputs else None     # --dump-outputs: as in main()
+
     def compute():
         if train:
             bucket.zero()
             pred = forward()
-            torch.nn.functional.cross_entropy(pred.squeeze(-1).permute(0, 2, 1).reshape(-1, 2), label.reshape(-1)).backward()
+            loss = torch.nn.functional.cross_entropy(pred.squeeze(-1).permute(0, 2, 1).reshape(-1, 2), label.reshape(-1))
+            loss.backward()
         else:
             with torch.no_grad():
-                forward()
+                pred = forward()
+        if keep is not None:
+            keep.update({'pred': pred}, **({'loss': loss} if train else {}))
 
     graphed = None
     if not args.no_graph:
@@ -483,6 +517,10 @@ def main_syn(args):
             print('rank %d step %.3f ms' % (rank, (time.perf_counter() - t1) * 1e3), file=sys.stderr)
     fence()
     elapsed = time.perf_counter() - t0
+    if keep is not None and rank == 0:
+        if train:
+            keep['parameters'] = torch.cat([p.detach().reshape(-1) for p in everything.parameters()])
+        dump_outputs(args.dump_outputs, keep)
     dist_info = dist_report(world, dev, elapsed, args.steps)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -645,16 +683,21 @@ def main():
     # bf16: activations / messages are stored in bf16 (the message kernels then use bf16 matrix cores for
     # the forward), parameters, gradients and optimizer state stay f32 (autocast for the node-wise GEMMs)
     amp = torch.autocast(device_type='cuda', dtype=torch.bfloat16, enabled=(args.dtype == 'bf16'))
+    # --dump-outputs: the step's outputs held by reference (a replayed graph rewrites the tensors of its capture in place)
+    keep = {} if args.dump_outputs else None
 
     def compute():                      # everything but the collective and the optimizer: graph-capturable
         if train:
             bucket.zero()
             with amp:
                 logits, snr = model(*inputs)
-            loss_fn(logits, snr, label, sigma_b).backward()
+            loss = loss_fn(logits, snr, label, sigma_b)
+            loss.backward()
         else:
             with torch.no_grad(), amp:
-                model(*inputs)
+                logits, snr = model(*inputs)
+        if keep is not None:
+            keep.update({'logits': logits, 'snr_pred': snr}, **({'loss': loss} if train else {}))
 
     def update():
         bucket.all_reduce_sum()                     # one RCCL all-reduce of the flat gradient; the mean is folded into Adam
@@ -729,6 +772,10 @@ def main():
     host_enqueue = time.perf_counter() - t0      # the host's share: when it is close to `elapsed` the replay is launch-bound
     fence()
     elapsed = time.perf_counter() - t0
+    if keep is not None and rank == 0:           # before the instrumented eager passes below run the model again
+        if train:
+            keep['parameters'] = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+        dump_outputs(args.dump_outputs, keep)
     _trace('timed steps done')
     if host_times:
         print('rank %d: host enqueue %.3f ms per step, wall %.3f ms per step' % (rank, host_enqueue / args.steps * 1e3, elapsed / args.steps * 1e3),

@@ -607,9 +607,11 @@ int fgnn_mpconv_forward_ext(const fgnn_mpconv_desc* d, const void* x, const int6
     int off_b = 0;
     auto take = [&](int bytes) { const int o = off_b; off_b = fgnn_round_up(off_b + bytes, 16); return o; };
     const bool piped = (d->idx_sb == 0 && d->et_sb == 0) || d->B == 1;
-    static const bool exact = getenv("FGNN_EXT_F32MFMA") != nullptr;      // projections on the f32 matrix cores (bitwise an fmaf chain)
-    // default: three-term bf16 split on the bf16 matrix cores, when its larger x images still fit next to the edge types
-    const bool split = piped && !exact && (2 * 3 * 64 * FQ_XS * 2 + 2 * 64 * FP_PROW * 4 + d->N * d->k * (FX_NET * 4 + 4) + 3 * 64 * 4 + 64 <= 160 * 1024);
+    // default: projections on the f32 matrix cores (bitwise an fmaf chain, the reference's f32 accuracy).  FGNN_EXT_BF16_SPLIT=1
+    // opts in to the three-term bf16 split on the bf16 matrix cores (when its larger x images fit next to the edge types): faster,
+    // but on an ill-conditioned stack its result drifts several times further from f64 than an f32 evaluation does
+    static const bool opt_split = getenv("FGNN_EXT_BF16_SPLIT") != nullptr;
+    const bool split = piped && opt_split && (2 * 3 * 64 * FQ_XS * 2 + 2 * 64 * FP_PROW * 4 + d->N * d->k * (FX_NET * 4 + 4) + 3 * 64 * 4 + 64 <= 160 * 1024);
     p.off_xs = take(split ? 2 * 3 * 64 * FQ_XS * 2 : (piped ? 2 : 1) * 64 * FX_XS * 4);
     p.off_ps = take(piped ? 2 * 64 * FP_PROW * 4 : 64 * FX_PS * 4);
     p.off_et = take(d->N * d->k * FX_NET * 4);
