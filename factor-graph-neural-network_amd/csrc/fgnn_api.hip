@@ -20,6 +20,37 @@ void fgnn_note_kernel(const char* fmt, ...) {
     va_end(ap);
 }
 
+int fgnn_reject(const char* family, int rule) {
+    static const bool trace = getenv("FGNN_TRACE") != nullptr;
+    if (trace) fprintf(stderr, "[fgnn] %s rejects shape: rule %d\n", family, rule);
+    return 0;
+}
+
+#ifdef FGNN_ENABLE_PROF
+long long* fgnn_prof_begin() {
+    static const bool on = getenv("FGNN_PROF") != nullptr;
+    static long long* buf = nullptr;
+    if (!on) return nullptr;
+    if (!buf) (void)hipMalloc(&buf, 256 * 8);
+    (void)hipMemset(buf, 0, 256 * 8);
+    return buf;
+}
+void fgnn_prof_print(const long long* prof, const char* tag, int first, int rows, int cols, int stride) {
+    if (!prof) return;
+    long long h[256];
+    (void)hipDeviceSynchronize();
+    (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
+    for (int r = 0; r < rows; ++r) {
+        fprintf(stderr, "[fgnn prof %s] row %d:", tag, r);
+        for (int i = 0; i < cols; ++i) {
+            const long long v = h[first + r * stride + i];
+            fprintf(stderr, " %lld", v ? v - h[first] : -1);
+        }
+        fprintf(stderr, "\n");
+    }
+}
+#endif
+
 extern "C" const char* fgnn_last_error(void) { return g_err; }
 extern "C" const char* fgnn_last_kernel(void) { return g_kernel; }
 extern "C" int fgnn_abi_version(void) { return FGNN_ABI_VERSION; }

@@ -45,5 +45,19 @@ __device__ __forceinline__ f32x4 fgnn_ld4(const bf16_t* p) {
 void fgnn_set_error(const char* fmt, ...);
 void fgnn_note_kernel(const char* fmt, ...);   // records which kernel a dispatch chose (fgnn_last_kernel)
 #define FGNN_FAIL(code, ...) do { fgnn_set_error(__VA_ARGS__); return (code); } while (0)
+// a kernel family's plan turns a call down (returns 0); FGNN_TRACE=1 prints which rule
+int fgnn_reject(const char* family, int rule);
+#define FGNN_REJECT(family, rule) return fgnn_reject(family, rule)
+
+// phase-timeline stamps (tuning aid, -DFGNN_ENABLE_PROF builds, read with FGNN_PROF=1): fgnn_prof_begin gives the launch a zeroed
+// device buffer of 256 stamps (NULL when off), fgnn_prof_print waits for the launch and prints rows x cols stamps from slot `first`
+// on (row stride `stride`) relative to that slot.  The product build has neither.
+#ifdef FGNN_ENABLE_PROF
+long long* fgnn_prof_begin();
+void fgnn_prof_print(const long long* prof, const char* tag, int first, int rows, int cols, int stride);
+#else
+static inline long long* fgnn_prof_begin() { return nullptr; }
+static inline void fgnn_prof_print(const long long*, const char*, int, int, int, int) {}
+#endif
 
 static inline int fgnn_round_up(int v, int m) { return (v + m - 1) / m * m; }

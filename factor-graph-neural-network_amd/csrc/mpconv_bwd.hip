@@ -28,6 +28,7 @@
 // DIFF / NEIGHBOR, max and softmax, 2..64 output channels) to mpconv_bwd_ext.hip.  Like those, this kernel is free of
 // atomics (tests/test_mpconv_gpu.py::test_generic_backward_is_bitwise_reproducible).
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include <stdlib.h>
 
 #define BWD_MAXT 8   // 16x16 dW tiles a wave can own within one channel tile
@@ -416,28 +417,6 @@ __global__ __launch_bounds__(FGNN_THREADS) void mpconv_bwd_kernel(const BwdParam
 // ----------------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------------
-int fgnn_check_desc(const fgnn_mpconv_desc* d);
-void fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias, hipStream_t st);
-int fgnn_mpconv_backward_resident(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
-                                  const void* etype, const float* filters, const void* gz,
-                                  const uint8_t* argmax, void* gx, void* getype, float* gfilters,
-                                  float* gbias, void* workspace, int64_t workspace_bytes,
-                                  fgnn_stream_t stream);
-
-int fgnn_mpconv_backward_hyper(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                               const float* filters, const void* gz, const uint8_t* argmax, void* gx, void* getype,
-                               float* gfilters, float* gbias, void* workspace, int64_t workspace_bytes,
-                               fgnn_stream_t stream);
-
-int fgnn_mpconv_backward_b16(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                             const float* filters, const void* gz, const uint8_t* argmax, void* gx, void* getype,
-                             float* gfilters, float* gbias, void* workspace, int64_t workspace_bytes,
-                             fgnn_stream_t stream);
-int fgnn_mpconv_backward_sg(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                            const float* filters, const void* gz, const uint8_t* argmax, void* gx, void* getype,
-                            float* gfilters, float* gbias, void* workspace, int64_t workspace_bytes,
-                            fgnn_stream_t stream);
-
 static int plan_backward(const fgnn_mpconv_desc* d, BwdParams* p) {
     const int nproj = d->ext == FGNN_EXT_NONE ? 1 : 2;
     p->nproj = nproj;
@@ -502,36 +481,98 @@ static void* pick_net_b(int net, int agg) {
     }
 }
 
-int fgnn_mpconv_backward_ext(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                             const float* filters, const void* gz, const uint8_t* argmax, void* gx, void* getype,
-                             float* gfilters, float* gbias, void* workspace, int64_t workspace_bytes,
-                             fgnn_stream_t stream);
-int fgnn_mpconv_backward_ext_accepts(const fgnn_mpconv_desc* d);
-
 extern "C" int fgnn_mpconv_backward_reduces_getype(const fgnn_mpconv_desc* d) {
     if (!d || fgnn_check_desc(d)) return 0;
-    return fgnn_mpconv_backward_ext_accepts(d);
+    return fgnn_bwd_ext_accepts(d, fgnn_switches());
 }
 
-void fgnn_bw_set_pending_tables(const void* t);
+// the generic kernel: any shape but the batch-reduced edge-type gradient
+static int generic_plan(const FgnnBwdCall& c, const FgnnSwitches&, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    if (d->reserved & FGNN_DESC_GETYPE_REDUCED)
+        FGNN_FAIL(FGNN_EUNSUPPORTED, "batch-reduced edge-type gradient asked of a shape without that kernel");
+    BwdParams p;
+    pl->lds = plan_backward(d, &p);
+    if (pl->lds < 0) return pl->lds;
+    // one slab per workgroup (<= 256: the workspace every backward kernel of this library sizes), folded in a fixed order
+    const int64_t R_rows = d->ext == FGNN_EXT_NONE ? d->nin : 2 * d->nin;
+    const int64_t slab_len = R_rows * d->nou * d->net + d->nou;
+    if (!c.workspace || c.workspace_bytes < 256 * slab_len * 4)
+        FGNN_FAIL(FGNN_EINVAL, "mpconv backward: workspace of fgnn_mpconv_backward_workspace_bytes(d) bytes needed");
+    const int chunk = (d->B + 255) / 256 < 1 ? 1 : (d->B + 255) / 256;
+    pl->aux = chunk;
+    pl->grid = (d->B + chunk - 1) / chunk;
+    pl->block = FGNN_THREADS;
+    pl->fn = d->dtype == FGNN_F32 ? pick_net_b<float>(d->net, d->agg) : pick_net_b<bf16_t>(d->net, d->agg);
+    return 1;
+}
+
+static int generic_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    BwdParams p;
+    p.d = *d;
+    p.x = c.x; p.idx = c.idx; p.et = c.et; p.W = c.W; p.gz = c.gz; p.z = c.z; p.argmax = c.argmax;
+    p.gx = c.gx; p.get = c.getype; p.bias = nullptr; p.has_gbias = c.gbias != nullptr;
+    plan_backward(d, &p);
+    const int64_t R_rows = d->ext == FGNN_EXT_NONE ? d->nin : 2 * d->nin;
+    const int64_t nw = R_rows * d->nou * d->net, slab_len = nw + d->nou;
+    p.slab = (float*)c.workspace;
+    p.chunk = pl.aux;
+    if (pl.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
+    }
+    fgnn_note_kernel("mpconv_bwd_kernel<%s, %d, %d>", d->dtype ? "bf16_t" : "float",
+                     (d->net == 1 || d->net == 4 || d->net == 16) ? d->net : 0, d->agg);
+    void* args[] = {(void*)&p};
+    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward launch: %s", hipGetErrorString(e));
+    fgnn_launch_slab_reduce(p.slab, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
+    e = hipGetLastError();
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward fold launch: %s", hipGetErrorString(e));
+    return FGNN_OK;
+}
+
+// The backward's families, most specialised first; the first whose plan takes the call runs it.
+static const struct { FgnnBwdPlanFn plan; FgnnBwdLaunchFn launch; } kBwdFamilies[] = {
+    {fgnn_bwd_ext_plan, fgnn_bwd_ext_launch},         // f32 synthetic-PGM calls
+    {fgnn_bwd_hyper_plan, fgnn_bwd_hyper_launch},     // hyper-edge calls: fan-in / fan-out
+    {fgnn_bwd_ws_plan, fgnn_bwd_ws_launch},           // bf16 LDPC parity calls: third generation
+    {fgnn_bwd_sg_plan, fgnn_bwd_sg_launch},           //   second generation
+    {fgnn_bwd_b16_plan, fgnn_bwd_b16_launch},         //   first generation
+    {fgnn_bwd_res_plan, fgnn_bwd_res_launch},         // W resident in LDS
+    {generic_plan, generic_launch},
+};
+static const int kBwdGeneric = sizeof(kBwdFamilies) / sizeof(kBwdFamilies[0]) - 1;
+
+static int bwd_run(const FgnnBwdCall& c) {
+    const FgnnSwitches& sw = fgnn_switches();
+    for (int f = sw.force_generic ? kBwdGeneric : 0; f <= kBwdGeneric; ++f) {
+        FgnnPlan pl = {};
+        pl.family = f;
+        const int rc = kBwdFamilies[f].plan(c, sw, &pl);
+        if (rc < 0) return rc;
+        if (rc > 0) return kBwdFamilies[f].launch(c, pl);
+    }
+    return FGNN_EUNSUPPORTED;        // (not reached: the generic kernel takes every call or fails it)
+}
 
 // fgnn_mpconv_backward with the per-graph tables of fgnn_mpconv_backward_tables (NULL = none): the table-driven kernel then
 // copies them instead of rebuilding the transposed incidence in every workgroup of every launch.
-extern "C" int fgnn_mpconv_backward(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
-                                    const void* etype, const float* filters, const void* gz,
-                                    const void* z, const uint8_t* argmax, void* gx, void* getype,
-                                    float* gfilters, float* gbias, void* workspace,
-                                    int64_t workspace_bytes, fgnn_stream_t stream);
 extern "C" int fgnn_mpconv_backward_with_tables(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
                                                 const void* etype, const float* filters, const void* gz,
                                                 const void* z, const uint8_t* argmax, void* gx, void* getype,
                                                 float* gfilters, float* gbias, void* workspace,
                                                 int64_t workspace_bytes, const void* tables, fgnn_stream_t stream) {
-    fgnn_bw_set_pending_tables(tables);
-    const int rc = fgnn_mpconv_backward(d, x, nn_idx, etype, filters, gz, z, argmax, gx, getype, gfilters, gbias, workspace,
-                                        workspace_bytes, stream);
-    fgnn_bw_set_pending_tables(nullptr);
-    return rc;
+    int rc = fgnn_check_desc(d);
+    if (rc) return rc;
+    if (!x || !nn_idx || !etype || !filters || !gz || !gx || !gfilters)
+        FGNN_FAIL(FGNN_EINVAL, "null tensor pointer");
+    if (d->agg == FGNN_AGG_MAX && !argmax) FGNN_FAIL(FGNN_EINVAL, "max aggregator needs the forward's argmax");
+    if (d->B == 0) return FGNN_OK;
+    const FgnnBwdCall c = {d, x, nn_idx, etype, filters, gz, z, argmax, gx, getype, gfilters, gbias, workspace, workspace_bytes,
+                           tables, (hipStream_t)stream};
+    return bwd_run(c);
 }
 
 extern "C" int fgnn_mpconv_backward(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
@@ -539,62 +580,6 @@ extern "C" int fgnn_mpconv_backward(const fgnn_mpconv_desc* d, const void* x, co
                                     const void* z, const uint8_t* argmax, void* gx, void* getype,
                                     float* gfilters, float* gbias, void* workspace,
                                     int64_t workspace_bytes, fgnn_stream_t stream) {
-    int rc = fgnn_check_desc(d);
-    if (rc) return rc;
-    if (!x || !nn_idx || !etype || !filters || !gz || !gx || !gfilters)
-        FGNN_FAIL(FGNN_EINVAL, "null tensor pointer");
-    if (d->agg == FGNN_AGG_MAX && !argmax) FGNN_FAIL(FGNN_EINVAL, "max aggregator needs the forward's argmax");
-    if (d->B == 0) return FGNN_OK;
-    {   // LDPC shape family: W-stationary persistent kernel (mpconv_bwd_res.hip)
-        static const bool force_generic = getenv("FGNN_FORCE_GENERIC") != nullptr;
-        if (!force_generic) {
-            rc = fgnn_mpconv_backward_ext(d, x, nn_idx, etype, filters, gz, argmax, gx, getype, gfilters, gbias,
-                                          workspace, workspace_bytes, stream);
-            if (rc != 0) return rc < 0 ? rc : FGNN_OK;
-            rc = fgnn_mpconv_backward_hyper(d, x, nn_idx, etype, filters, gz, argmax, gx, getype, gfilters, gbias,
-                                            workspace, workspace_bytes, stream);
-            if (rc != 0) return rc < 0 ? rc : FGNN_OK;
-            rc = fgnn_mpconv_backward_sg(d, x, nn_idx, etype, filters, gz, argmax, gx, getype, gfilters, gbias,
-                                         workspace, workspace_bytes, stream);
-            if (rc != 0) return rc < 0 ? rc : FGNN_OK;
-            rc = fgnn_mpconv_backward_b16(d, x, nn_idx, etype, filters, gz, argmax, gx, getype, gfilters, gbias,
-                                          workspace, workspace_bytes, stream);
-            if (rc != 0) return rc < 0 ? rc : FGNN_OK;
-            rc = fgnn_mpconv_backward_resident(d, x, nn_idx, etype, filters, gz, argmax, gx, getype,
-                                               gfilters, gbias, workspace, workspace_bytes, stream);
-            if (rc != 0) return rc < 0 ? rc : FGNN_OK;
-        }
-    }
-    if (d->reserved & FGNN_DESC_GETYPE_REDUCED)
-        FGNN_FAIL(FGNN_EUNSUPPORTED, "batch-reduced edge-type gradient asked of a shape without that kernel");
-    BwdParams p;
-    p.d = *d;
-    p.x = x; p.idx = nn_idx; p.et = etype; p.W = filters; p.gz = gz; p.z = z; p.argmax = argmax;
-    p.gx = gx; p.get = getype; p.bias = nullptr; p.has_gbias = gbias != nullptr;
-    const int lds = plan_backward(d, &p);
-    if (lds < 0) return lds;
-    // one slab per workgroup (<= 256: the workspace every backward kernel of this library sizes), folded in a fixed order
-    const int64_t R_rows = d->ext == FGNN_EXT_NONE ? d->nin : 2 * d->nin;
-    const int64_t nw = R_rows * d->nou * d->net, slab_len = nw + d->nou;
-    if (!workspace || workspace_bytes < 256 * slab_len * 4)
-        FGNN_FAIL(FGNN_EINVAL, "mpconv backward: workspace of fgnn_mpconv_backward_workspace_bytes(d) bytes needed");
-    p.slab = (float*)workspace;
-    int chunk = (d->B + 255) / 256;
-    if (chunk < 1) chunk = 1;
-    p.chunk = chunk;
-    const int grid = (d->B + chunk - 1) / chunk;
-    void* fn = d->dtype == FGNN_F32 ? pick_net_b<float>(d->net, d->agg) : pick_net_b<bf16_t>(d->net, d->agg);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
-    fgnn_note_kernel("mpconv_bwd_kernel<%s, %d, %d>", d->dtype ? "bf16_t" : "float",
-                     (d->net == 1 || d->net == 4 || d->net == 16) ? d->net : 0, d->agg);
-    void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(FGNN_THREADS), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward launch: %s", hipGetErrorString(e));
-    fgnn_launch_slab_reduce(p.slab, grid, slab_len, nw, gfilters, gbias, (hipStream_t)stream);
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward fold launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_mpconv_backward_with_tables(d, x, nn_idx, etype, filters, gz, z, argmax, gx, getype, gfilters, gbias, workspace,
+                                            workspace_bytes, nullptr, stream);
 }

@@ -19,6 +19,7 @@
 // Rounding: x and gz arrive as bf16; P and dP are rounded to bf16 (2^-9 relative) before they feed the matrix
 // cores, which is what a bf16 autocast backward does everywhere else in the model.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include <stdlib.h>
 
 #define BB_THREADS 512
@@ -520,8 +521,6 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
 // ----------------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------------
-#define BB_REJECT(code) do { if (getenv("FGNN_TRACE")) fprintf(stderr, "[fgnn] bf16-MFMA backward rejects shape: rule %d\n", code); return 0; } while (0)
-
 static void* bb_pick(int KS2, int NPASS) {
 #define BB_CASE(ks, np) if (KS2 == ks && NPASS == np) return (void*)mpconv_bwd_b16_kernel<ks, np>;
     BB_CASE(2, 2) BB_CASE(2, 4) BB_CASE(4, 2)
@@ -529,84 +528,78 @@ static void* bb_pick(int KS2, int NPASS) {
     return nullptr;
 }
 
-// Returns 1 if launched, 0 if the call is outside this kernel's family, <0 on error.
-int fgnn_mpconv_backward_b16(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                             const float* filters, const void* gz, const uint8_t* argmax, void* gx, void* getype,
-                             float* gfilters, float* gbias, void* workspace, int64_t workspace_bytes,
-                             fgnn_stream_t stream) {
-    static const bool off = getenv("FGNN_NO_BWD_B16") != nullptr;
-    if (off) return 0;
-    if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->agg != FGNN_AGG_MAX || d->net != 4) BB_REJECT(1);
-    if ((d->nin != 64 && d->nin != 128) || (d->nou != 64 && d->nou != 128)) BB_REJECT(2);
-    const int KS2 = d->nin / 32, NPASS = d->nou / 32;
-    void* fn = bb_pick(KS2, NPASS);
-    if (!fn) BB_REJECT(3);
-    if (!(d->x_sc == 1 && d->x_sn == d->nin && d->x_sb % 8 == 0)) BB_REJECT(4);
-    if (!(d->y_sc == 1 && d->y_sm == d->nou && d->y_sb % 8 == 0)) BB_REJECT(5);
+// LDS offsets and the shape constants of one launch; returns the bytes
+static int bb_layout(const fgnn_mpconv_desc* d, Bb16Params* p) {
     const int mk = d->M * d->k;
-    if (!(d->et_se == 1 && d->et_sk == 4 && (d->et_sm == 4 * d->k || d->M == 1) && d->et_sb % 4 == 0)) BB_REJECT(6);
-    if (d->N > 96 || d->N < 9 || mk > BB_THREADS || d->k > 255 || d->M > 128) BB_REJECT(7);
-    if (((uintptr_t)x & 15) || ((uintptr_t)gz & 15) || ((uintptr_t)etype & 7) || ((uintptr_t)argmax & 3) ||
-        ((uintptr_t)gx & 7)) BB_REJECT(8);
-    const int64_t nw = (int64_t)d->nin * d->nou * 4, slab_len = nw + d->nou;
-    if (!workspace || workspace_bytes < (256 * slab_len + nw) * 4) BB_REJECT(9);
-
-    Bb16Params p;
-    p.d = *d;
-    p.x = (const uint16_t*)x; p.idx = nn_idx; p.et = (const uint16_t*)etype; p.W = filters;
-    p.gz = (const uint16_t*)gz; p.argmax = argmax; p.gx = (uint16_t*)gx; p.get = (uint16_t*)getype;
-    p.ws = (float*)workspace;
-    p.Wt = p.ws + 256 * slab_len;
-    p.Npad16 = fgnn_round_up(d->N, 16);
-    p.Npad32 = fgnn_round_up(d->N, 32);
-    { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
-    p.prof = nullptr;
-    static long long* prof_buf = nullptr;
-    if (getenv("FGNN_PROF")) {
-        if (!prof_buf) { (void)hipMalloc(&prof_buf, 64 * 8); }
-        (void)hipMemset(prof_buf, 0, 64 * 8);
-        p.prof = prof_buf;
-    }
-    p.kmagic = d->k == 1 ? 0u : (unsigned)((0x100000000ULL + d->k - 1) / d->k);
-    if (d->k == 1) BB_REJECT(10);
+    p->d = *d;
+    p->Npad16 = fgnn_round_up(d->N, 16);
+    p->Npad32 = fgnn_round_up(d->N, 32);
+    p->kmagic = d->k == 1 ? 0u : (unsigned)((0x100000000ULL + d->k - 1) / d->k);
     int off_b = 0;
     auto take = [&](int bytes) { const int o = off_b; off_b = fgnn_round_up(off_b + bytes, 16); return o; };
-    p.off_xb = take(p.Npad32 * (d->nin + BB_XPAD) * 2);
-    p.off_pb = take(p.Npad32 * BB_PSB * 2);
-    p.off_db = take(p.Npad32 * BB_PSB * 2);
-    p.off_gz = take((d->M * BB_GS > BB_THREADS ? d->M * BB_GS : BB_THREADS) * 4);
-    p.off_am = take(d->M * BB_GS);
-    p.off_et = take(mk * 16);
-    p.off_det = take(mk * 16);
-    p.off_idx = take(mk * 4);
-    p.off_cs = take((2 * BB_MAXN + 4) * 4);
-    p.off_cl = take(mk * 4);
-    p.off_ce = take(mk * 4);
-    const int lds = off_b;
-    if (lds > 160 * 1024) BB_REJECT(11);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
-    int grid = 256;
-    if (grid > d->B) grid = d->B;
+    p->off_xb = take(p->Npad32 * (d->nin + BB_XPAD) * 2);
+    p->off_pb = take(p->Npad32 * BB_PSB * 2);
+    p->off_db = take(p->Npad32 * BB_PSB * 2);
+    p->off_gz = take((d->M * BB_GS > BB_THREADS ? d->M * BB_GS : BB_THREADS) * 4);
+    p->off_am = take(d->M * BB_GS);
+    p->off_et = take(mk * 16);
+    p->off_det = take(mk * 16);
+    p->off_idx = take(mk * 4);
+    p->off_cs = take((2 * BB_MAXN + 4) * 4);
+    p->off_cl = take(mk * 4);
+    p->off_ce = take(mk * 4);
+    return off_b;
+}
+
+int fgnn_bwd_b16_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    if (sw.no_bwd_b16) return 0;
+    if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->agg != FGNN_AGG_MAX || d->net != 4) FGNN_REJECT("bf16-MFMA backward", 1);
+    if ((d->nin != 64 && d->nin != 128) || (d->nou != 64 && d->nou != 128)) FGNN_REJECT("bf16-MFMA backward", 2);
+    pl->fn = bb_pick(d->nin / 32, d->nou / 32);
+    if (!pl->fn) FGNN_REJECT("bf16-MFMA backward", 3);
+    if (!(d->x_sc == 1 && d->x_sn == d->nin && d->x_sb % 8 == 0)) FGNN_REJECT("bf16-MFMA backward", 4);
+    if (!(d->y_sc == 1 && d->y_sm == d->nou && d->y_sb % 8 == 0)) FGNN_REJECT("bf16-MFMA backward", 5);
+    const int mk = d->M * d->k;
+    if (!(d->et_se == 1 && d->et_sk == 4 && (d->et_sm == 4 * d->k || d->M == 1) && d->et_sb % 4 == 0)) FGNN_REJECT("bf16-MFMA backward", 6);
+    if (d->N > 96 || d->N < 9 || mk > BB_THREADS || d->k > 255 || d->M > 128) FGNN_REJECT("bf16-MFMA backward", 7);
+    if (((uintptr_t)c.x & 15) || ((uintptr_t)c.gz & 15) || ((uintptr_t)c.et & 7) || ((uintptr_t)c.argmax & 3) ||
+        ((uintptr_t)c.gx & 7)) FGNN_REJECT("bf16-MFMA backward", 8);
+    const int64_t nw = (int64_t)d->nin * d->nou * 4, slab_len = nw + d->nou;
+    if (!c.workspace || c.workspace_bytes < (256 * slab_len + nw) * 4) FGNN_REJECT("bf16-MFMA backward", 9);
+    if (d->k == 1) FGNN_REJECT("bf16-MFMA backward", 10);
+    Bb16Params p;
+    pl->lds = bb_layout(d, &p);
+    if (pl->lds > 160 * 1024) FGNN_REJECT("bf16-MFMA backward", 11);
+    int grid = d->B < 256 ? d->B : 256;
     const int chunk = (d->B + grid - 1) / grid;
-    grid = (d->B + chunk - 1) / chunk;
-    hipStream_t st = (hipStream_t)stream;
-    fgnn_note_kernel("mpconv_bwd_b16_kernel<%d, %d>", KS2, NPASS);
+    pl->grid = (d->B + chunk - 1) / chunk;
+    pl->block = BB_THREADS;
+    return 1;
+}
+
+int fgnn_bwd_b16_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    const int64_t nw = (int64_t)d->nin * d->nou * 4, slab_len = nw + d->nou;
+    Bb16Params p;
+    bb_layout(d, &p);
+    p.x = (const uint16_t*)c.x; p.idx = c.idx; p.et = (const uint16_t*)c.et; p.W = c.W;
+    p.gz = (const uint16_t*)c.gz; p.argmax = c.argmax; p.gx = (uint16_t*)c.gx; p.get = (uint16_t*)c.getype;
+    p.ws = (float*)c.workspace;
+    p.Wt = p.ws + 256 * slab_len;
+    { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
+    if (pl.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
+    }
+    fgnn_note_kernel("mpconv_bwd_b16_kernel<%d, %d>", d->nin / 32, d->nou / 32);
+    p.prof = fgnn_prof_begin();
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(BB_THREADS), args, lds, st);
+    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv bf16 backward launch: %s", hipGetErrorString(e));
-    fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, gfilters, gbias, st);
+    fgnn_launch_slab_reduce(p.ws, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
     e = hipGetLastError();
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward helper launch: %s", hipGetErrorString(e));
-    if (p.prof) {                                     // tuning aid: phase timeline of one sample (cycles at 100 MHz s_memtime)
-        long long h[64];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, p.prof, sizeof(h), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[fgnn prof]");
-        for (int i = 0; i < 41; ++i) if (h[i]) fprintf(stderr, " %d:%lld", i, h[i] - h[0]);
-        fprintf(stderr, "\n");
-    }
-    return 1;
+    fgnn_prof_print(p.prof, "b16 bwd", 0, 1, 41, 0);             // phase timeline of one sample (cycles at 100 MHz s_memtime)
+    return FGNN_OK;
 }

@@ -25,6 +25,7 @@
 // LDS rows: x image stride 68 floats, P / dP stride 132: every access pattern above is bank-conflict-free (the k index of
 // the gW product runs over nodes in the order 4 lk + (kk & 3) + 16 (kk >> 2) for that reason).
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include <stdlib.h>
 
 #define BX_THREADS 512
@@ -1024,9 +1025,6 @@ __global__ __launch_bounds__(BX_THREADS, 1) void mpconv_bwd_extq_kernel(const Bx
     }
 }
 
-void fgnn_launch_slab_store(const float* ws, int nslab, int64_t slab_len, float* out, hipStream_t st);
-void fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias,
-                             hipStream_t st);
 
 // which arithmetic the backward of this family runs in (process-wide; FGNN_EXT_BWD_PIECES gives the initial value)
 static int g_bq_pieces = -1;
@@ -1048,9 +1046,8 @@ int64_t fgnn_mpconv_backward_ext_extra_bytes(const fgnn_mpconv_desc* d) {
 
 // 1 when this descriptor's backward sums the edge-type gradient over the batch itself (getype = [net, M, k]); the caller
 // asks for that form with FGNN_DESC_GETYPE_REDUCED in d->reserved.
-int fgnn_mpconv_backward_ext_accepts(const fgnn_mpconv_desc* d) {
-    static const bool off = getenv("FGNN_NO_EXT") != nullptr;
-    if (off) return 0;
+int fgnn_bwd_ext_accepts(const fgnn_mpconv_desc* d, const FgnnSwitches& sw) {
+    if (sw.no_ext) return 0;
     if (d->dtype != FGNN_F32 || (d->ext != FGNN_EXT_NEIGHBOR && d->ext != FGNN_EXT_DIFF)) return 0;
     if (d->agg != FGNN_AGG_MAX && d->agg != FGNN_AGG_LSE) return 0;
     if (d->net != BX_NET || d->nin != BX_NIN || d->nou < 2 || d->nou > BX_NOU || (d->nou & 1)) return 0;
@@ -1062,169 +1059,133 @@ int fgnn_mpconv_backward_ext_accepts(const fgnn_mpconv_desc* d) {
     return 1;
 }
 
-// Returns 1 if launched, 0 if the call is outside this kernel's family, < 0 on error.
-int fgnn_mpconv_backward_ext(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                             const float* filters, const void* gz, const uint8_t* argmax, void* gx, void* getype,
-                             float* gfilters, float* gbias, void* workspace, int64_t workspace_bytes,
-                             fgnn_stream_t stream) {
+// LDS offsets of one launch: np = 0 the exact-f32 kernel, else the split form with np bf16 pieces (sep: dP in its own image).
+// Returns the bytes.
+static int bx_layout(const fgnn_mpconv_desc* d, int np, int sep, BxParams* p) {
+    const int mk = d->N * d->k;
+    int ob = 0;
+    auto take = [&](int bytes) { const int o = ob; ob = fgnn_round_up(ob + bytes, 16); return o; };
+    if (np) {
+        p->off_xs = 0;
+        p->off_xq = take(np * BQ_XPIECE);
+        p->off_ps = take(sep ? 64 * BX_PS * 4 : (np * BQ_DPIECE > 64 * BX_PS * 4 ? np * BQ_DPIECE : 64 * BX_PS * 4));
+        p->off_dq = p->off_dp = sep ? take(np * BQ_DPIECE) : p->off_ps;
+        p->off_et = take((mk + 1) * BX_NET * 4); p->off_get = take(mk * BX_NET * 4); p->off_idx = take(mk * 4);
+        p->off_w = take((mk + 1) * 16);
+        p->off_csr = take(((mk * 2 + 15) & ~15) + 65 * 4); p->off_e16 = take(64 * 16 * 2); p->off_gz = take(64 * 4 * 4);
+        p->off_am = take(64 * 4);
+        return ob;
+    }
+    p->off_xs = take(64 * BX_XS * 4);
+    p->off_ps = take(64 * BX_PS * 4);
+    p->off_dp = p->off_ps;
+    p->off_et = take(mk * BX_NET * 4);
+    p->off_get = take(mk * BX_NET * 4);
+    p->off_idx = take(mk * 4);
+    p->off_csr = take(((mk * 2 + 15) & ~15) + 65 * 4);
+    p->off_e16 = take(64 * 16 * 2);
+    p->off_gz = take(64 * 4 * 4);
+    p->off_am = take(64 * 4);
+    p->off_w = take(d->agg == FGNN_AGG_LSE ? mk * 4 * 4 : 16);
+    if (ob + 64 * BX_PS * 4 <= 160 * 1024) p->off_dp = take(64 * BX_PS * 4);      // room for dP's own image
+    return ob;
+}
+
+// f32 synthetic-PGM calls.  pl->mode: bf16 pieces of the split form (0: the exact-f32 kernel), pl->split: its separate dP image.
+int fgnn_bwd_ext_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
     const bool reduced = (d->reserved & FGNN_DESC_GETYPE_REDUCED) != 0;
-    if (!fgnn_mpconv_backward_ext_accepts(d)) {
+    if (!fgnn_bwd_ext_accepts(d, sw)) {
         if (reduced) FGNN_FAIL(FGNN_EUNSUPPORTED, "batch-reduced edge-type gradient asked of a shape without that kernel");
         return 0;
     }
-    if (getype && !reduced && d->B != 1) return 0;                   // per-sample edge-type gradient: the generic kernel
-    if (((uintptr_t)x & 15) || ((d->nou & 3) == 0 && (((uintptr_t)gz & 15) || ((uintptr_t)argmax & 3)))) {
+    if (c.getype && !reduced && d->B != 1) return 0;                 // per-sample edge-type gradient: the generic kernel
+    if (((uintptr_t)c.x & 15) || ((d->nou & 3) == 0 && (((uintptr_t)c.gz & 15) || ((uintptr_t)c.argmax & 3)))) {
         if (reduced) FGNN_FAIL(FGNN_EINVAL, "mpconv ext backward needs 16-byte aligned x / gz");
         return 0;
     }
-    const int mk = d->N * d->k;
-    const int ncols = d->nou * BX_NET;
-    const int64_t nw = (int64_t)2 * BX_NIN * ncols, slab_len = nw + d->nou, get_len = (int64_t)BX_NET * mk;
-    int grid = 256;
-    if (grid > d->B) grid = d->B;
+    const int64_t slab_len = (int64_t)2 * BX_NIN * d->nou * BX_NET + d->nou, get_len = (int64_t)BX_NET * d->N * d->k;
+    int grid = d->B < 256 ? d->B : 256;
     const int chunk = (d->B + grid - 1) / grid;
-    grid = (d->B + chunk - 1) / chunk;
-    const int64_t pieces_bytes = (int64_t)2 * 3 * BQ_WPIECE * 2;
-    const int64_t need = (grid * slab_len + (getype ? grid * get_len : 0)) * 4 + pieces_bytes;
-    if (!workspace || workspace_bytes < need)
+    pl->grid = grid = (d->B + chunk - 1) / chunk;
+    pl->block = BX_THREADS;
+    const int64_t need = (grid * slab_len + (c.getype ? grid * get_len : 0)) * 4 + (int64_t)2 * 3 * BQ_WPIECE * 2;
+    if (!c.workspace || c.workspace_bytes < need)
         FGNN_FAIL(FGNN_EINVAL, "mpconv ext backward needs %lld bytes of workspace (fgnn_mpconv_backward_workspace_bytes)", (long long)need);
     BxParams p;
-    p.x = (const float*)x; p.idx = nn_idx; p.et = (const float*)etype; p.W = filters; p.gz = (const float*)gz;
-    p.am = argmax; p.gx = (float*)gx; p.ws = (float*)workspace;
-    p.get_ws = getype ? (float*)workspace + grid * slab_len : nullptr;
-    p.B = d->B; p.N = d->N; p.k = d->k; p.ext = d->ext; p.nou = d->nou; p.ncols = ncols; p.wvec = ((uintptr_t)filters & 15) == 0; p.npass = (d->nou + BX_PCH - 1) / BX_PCH;
-    p.x_sb = d->x_sb; p.y_sb = d->y_sb; p.idx_sm = d->idx_sm; p.idx_sk = d->idx_sk;
-    p.et_se = d->et_se; p.et_sm = d->et_sm; p.et_sk = d->et_sk;
-    p.slab_len = slab_len; p.get_len = get_len;
-    int off_b = 0;
-    auto take = [&](int bytes) { const int o = off_b; off_b = fgnn_round_up(off_b + bytes, 16); return o; };
-    p.off_xs = take(64 * BX_XS * 4);
-    p.off_ps = take(64 * BX_PS * 4);
-    p.off_dp = p.off_ps;
-    p.off_et = take(mk * BX_NET * 4);
-    p.off_get = take(mk * BX_NET * 4);
-    p.off_idx = take(mk * 4);
-    p.off_csr = take(((mk * 2 + 15) & ~15) + 65 * 4);
-    p.off_e16 = take(64 * 16 * 2);
-    p.off_gz = take(64 * 4 * 4);
-    p.off_am = take(64 * 4);
-    p.off_w = take(d->agg == FGNN_AGG_LSE ? mk * 4 * 4 : 16);
-    if (off_b + 64 * BX_PS * 4 <= 160 * 1024) p.off_dp = take(64 * BX_PS * 4);      // room for dP's own image
-    const int lds = off_b;
-    if (lds > 160 * 1024) {
-        if (reduced) FGNN_FAIL(FGNN_EUNSUPPORTED, "mpconv ext backward: %d bytes of LDS", lds);
+    pl->lds = bx_layout(d, 0, 0, &p);
+    if (pl->lds > 160 * 1024) {
+        if (reduced) FGNN_FAIL(FGNN_EUNSUPPORTED, "mpconv ext backward: %d bytes of LDS", pl->lds);
         return 0;
     }
-    const bool narrow = d->nou != BX_NOU, wvec = p.wvec != 0;
-    void* fn;
+    const bool narrow = d->nou != BX_NOU, wvec = ((uintptr_t)c.W & 15) == 0;
     // ---- split form (bf16 pieces on the bf16 matrix cores): max aggregation, 64 output channels, when its images fit ----
     // FGNN_EXT_BWD_PIECES: 2 (default: h + l pieces, three bf16 MFMAs per fragment product; gradients within 5e-6 of the exact kernel's,
     // tools/xbench.py), 3 (h + m + l, six MFMAs: within 4e-7, 1.35 x the time), 0 (the exact-f32 kernel above: 2 x the time)
     const int want_np = bq_pieces();
     if (want_np >= 2 && d->agg == FGNN_AGG_MAX && !narrow && (d->y_sb % 4) == 0) {
-        int np = 0, sep = 0, lds_q = 0;
-        for (int cand = want_np >= 3 ? 3 : 2; cand >= 2 && !np; --cand)
-            for (int sp = 1; sp >= 0 && !np; --sp) {
-                int ob = 0;
-                auto tk = [&](int bytes) { const int o = ob; ob = fgnn_round_up(ob + bytes, 16); return o; };
-                const int oxq = tk(cand * BQ_XPIECE);
-                const int ops_ = tk(sp ? 64 * BX_PS * 4 : (cand * BQ_DPIECE > 64 * BX_PS * 4 ? cand * BQ_DPIECE : 64 * BX_PS * 4));
-                const int odq = sp ? tk(cand * BQ_DPIECE) : ops_;
-                const int oet = tk((mk + 1) * BX_NET * 4), oget = tk(mk * BX_NET * 4), oidx = tk(mk * 4), osel = tk((mk + 1) * 16);
-                const int ocsr = tk(((mk * 2 + 15) & ~15) + 65 * 4), oe16 = tk(64 * 16 * 2), ogz = tk(64 * 4 * 4), oam = tk(64 * 4);
-                if (ob <= 160 * 1024) {
-                    np = cand; sep = sp; lds_q = ob;
-                    p.off_xq = oxq; p.off_ps = ops_; p.off_dq = odq; p.off_dp = odq; p.off_et = oet; p.off_get = oget; p.off_idx = oidx;
-                    p.off_csr = ocsr; p.off_e16 = oe16; p.off_gz = ogz; p.off_am = oam; p.off_w = osel; p.off_xs = 0;
-                }
+        for (int cand = want_np >= 3 ? 3 : 2; cand >= 2; --cand)
+            for (int sp = 1; sp >= 0; --sp) {
+                const int lds = bx_layout(d, cand, sp, &p);
+                if (lds > 160 * 1024) continue;
+                pl->mode = cand; pl->split = sp; pl->lds = lds;
+                pl->fn = cand == 3 ? (sp ? (void*)mpconv_bwd_extq_kernel<3, true> : (void*)mpconv_bwd_extq_kernel<3, false>)
+                                   : (sp ? (void*)mpconv_bwd_extq_kernel<2, true> : (void*)mpconv_bwd_extq_kernel<2, false>);
+                return 1;
             }
-        if (np) {
-            uint16_t* wq = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(workspace) + (grid * slab_len + (getype ? grid * get_len : 0)) * 4);
-            p.wq1 = wq;
-            p.wq2 = wq + (int64_t)3 * BQ_WPIECE;
-            void* prep = np == 3 ? (void*)bq_prep_kernel<3> : (void*)bq_prep_kernel<2>;
-            const float* Wf = filters;
-            uint16_t* a1 = wq;
-            uint16_t* a2 = wq + (int64_t)3 * BQ_WPIECE;
-            int is_diff = d->ext == FGNN_EXT_DIFF;
-            void* pargs[] = {(void*)&Wf, (void*)&a1, (void*)&a2, (void*)&is_diff};
-            hipError_t e = hipLaunchKernel(prep, dim3(BX_NCOLS / 256, BX_NIN), dim3(256), pargs, 0, (hipStream_t)stream);
-            if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ext backward (filter pieces) launch: %s", hipGetErrorString(e));
-            fn = np == 3 ? (sep ? (void*)mpconv_bwd_extq_kernel<3, true> : (void*)mpconv_bwd_extq_kernel<3, false>)
-                         : (sep ? (void*)mpconv_bwd_extq_kernel<2, true> : (void*)mpconv_bwd_extq_kernel<2, false>);
-            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_q);
-            if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds_q, hipGetErrorString(e));
-            fgnn_note_kernel("mpconv_bwd_extq_kernel<%d, %s>", np, sep ? "true" : "false");
-            p.prof = nullptr;
-            p.dbg = 0;
-#ifdef FGNN_ENABLE_PROF
-            static long long* prof_q = nullptr;
-            if (getenv("FGNN_PROF")) {
-                if (!prof_q) (void)hipMalloc(&prof_q, 64 * 8);
-                (void)hipMemset(prof_q, 0, 64 * 8);
-                p.prof = prof_q;
-            }
-#endif
-            void* qargs[] = {(void*)&p};
-            e = hipLaunchKernel(fn, dim3(grid), dim3(BX_THREADS), qargs, lds_q, (hipStream_t)stream);
-            if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ext backward (split form) launch: %s", hipGetErrorString(e));
-#ifdef FGNN_ENABLE_PROF
-            if (p.prof) {
-                long long h[64];
-                (void)hipDeviceSynchronize();
-                (void)hipMemcpy(h, p.prof, sizeof(h), hipMemcpyDeviceToHost);
-                for (int w = 0; w < 8; ++w) {
-                    fprintf(stderr, "[fgnn prof extq bwd] wave %d:", w);
-                    for (int i = 0; i < 8; ++i) fprintf(stderr, " %lld", h[w * 8 + i] - h[0]);
-                    fprintf(stderr, "\n");
-                }
-            }
-#endif
-            fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, gfilters, gbias, (hipStream_t)stream);
-            if (getype) fgnn_launch_slab_store(p.get_ws, grid, get_len, (float*)getype, (hipStream_t)stream);
-            e = hipGetLastError();
-            if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ext backward helper launch: %s", hipGetErrorString(e));
-            return 1;
-        }
     }
 #define BX_PICK(A) (narrow ? (wvec ? (void*)mpconv_bwd_ext_kernel<A, true, true> : (void*)mpconv_bwd_ext_kernel<A, true, false>) \
                            : (wvec ? (void*)mpconv_bwd_ext_kernel<A, false, true> : (void*)mpconv_bwd_ext_kernel<A, false, false>))
-    fn = d->agg == FGNN_AGG_MAX ? BX_PICK(FGNN_AGG_MAX) : BX_PICK(FGNN_AGG_LSE);
+    pl->fn = d->agg == FGNN_AGG_MAX ? BX_PICK(FGNN_AGG_MAX) : BX_PICK(FGNN_AGG_LSE);
 #undef BX_PICK
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    fgnn_note_kernel("mpconv_bwd_ext_kernel<%d, %s, %s>", d->agg, narrow ? "true" : "false", wvec ? "true" : "false");
-    p.prof = nullptr;
+    pl->mode = 0;
+    return 1;
+}
+
+int fgnn_bwd_ext_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    const int mk = d->N * d->k, ncols = d->nou * BX_NET, grid = pl.grid;
+    const int64_t nw = (int64_t)2 * BX_NIN * ncols, slab_len = nw + d->nou, get_len = (int64_t)BX_NET * mk;
+    BxParams p;
+    p.x = (const float*)c.x; p.idx = c.idx; p.et = (const float*)c.et; p.W = c.W; p.gz = (const float*)c.gz;
+    p.am = c.argmax; p.gx = (float*)c.gx; p.ws = (float*)c.workspace;
+    p.get_ws = c.getype ? (float*)c.workspace + grid * slab_len : nullptr;
+    p.B = d->B; p.N = d->N; p.k = d->k; p.ext = d->ext; p.nou = d->nou; p.ncols = ncols; p.wvec = ((uintptr_t)c.W & 15) == 0; p.npass = (d->nou + BX_PCH - 1) / BX_PCH;
+    p.x_sb = d->x_sb; p.y_sb = d->y_sb; p.idx_sm = d->idx_sm; p.idx_sk = d->idx_sk;
+    p.et_se = d->et_se; p.et_sm = d->et_sm; p.et_sk = d->et_sk;
+    p.slab_len = slab_len; p.get_len = get_len;
+    bx_layout(d, pl.mode, pl.split, &p);
+    hipError_t e;
+    if (pl.mode) {                                    // the filters' bf16 pieces, behind the slabs in the workspace
+        uint16_t* wq = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(c.workspace) + (grid * slab_len + (c.getype ? grid * get_len : 0)) * 4);
+        p.wq1 = wq;
+        p.wq2 = wq + (int64_t)3 * BQ_WPIECE;
+        void* prep = pl.mode == 3 ? (void*)bq_prep_kernel<3> : (void*)bq_prep_kernel<2>;
+        const float* Wf = c.W;
+        uint16_t* a1 = wq;
+        uint16_t* a2 = wq + (int64_t)3 * BQ_WPIECE;
+        int is_diff = d->ext == FGNN_EXT_DIFF;
+        void* pargs[] = {(void*)&Wf, (void*)&a1, (void*)&a2, (void*)&is_diff};
+        e = hipLaunchKernel(prep, dim3(BX_NCOLS / 256, BX_NIN), dim3(256), pargs, 0, c.stream);
+        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ext backward (filter pieces) launch: %s", hipGetErrorString(e));
+    }
+    e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
+    if (pl.mode) fgnn_note_kernel("mpconv_bwd_extq_kernel<%d, %s>", pl.mode, pl.split ? "true" : "false");
+    else fgnn_note_kernel("mpconv_bwd_ext_kernel<%d, %s, %s>", d->agg, d->nou != BX_NOU ? "true" : "false", p.wvec ? "true" : "false");
+    p.prof = fgnn_prof_begin();
     p.dbg = 0;
 #ifdef FGNN_ENABLE_PROF
-    if (getenv("FGNN_EXT_DBG")) p.dbg = atoi(getenv("FGNN_EXT_DBG"));
-    static long long* prof_buf = nullptr;
-    if (getenv("FGNN_PROF")) {
-        if (!prof_buf) (void)hipMalloc(&prof_buf, 64 * 8);
-        (void)hipMemset(prof_buf, 0, 64 * 8);
-        p.prof = prof_buf;
-    }
+    if (!pl.mode && getenv("FGNN_EXT_DBG")) p.dbg = atoi(getenv("FGNN_EXT_DBG"));
 #endif
     void* args[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(BX_THREADS), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ext backward launch: %s", hipGetErrorString(e));
-#ifdef FGNN_ENABLE_PROF
-    if (p.prof) {              // tuning aid: one stage of workgroup 0 (shader clocks): A start, A end, B1 start, B1 end, B2 end, C start, C end
-        long long h[64];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, p.prof, sizeof(h), hipMemcpyDeviceToHost);
-        for (int w = 0; w < 8; ++w) {
-            fprintf(stderr, "[fgnn prof ext bwd] wave %d:", w);
-            for (int i = 0; i < 8; ++i) fprintf(stderr, " %lld", h[w * 8 + i] - h[0]);
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
-    fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, gfilters, gbias, (hipStream_t)stream);
-    if (getype) {
-        fgnn_launch_slab_store(p.get_ws, grid, get_len, (float*)getype, (hipStream_t)stream);
-    }
+    e = hipLaunchKernel(pl.fn, dim3(grid), dim3(pl.block), args, pl.lds, c.stream);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, pl.mode ? "mpconv ext backward (split form) launch: %s" : "mpconv ext backward launch: %s", hipGetErrorString(e));
+    // (exact kernel: one stage of workgroup 0: A start, A end, B1 start, B1 end, B2 end, C start, C end; shader clocks)
+    fgnn_prof_print(p.prof, pl.mode ? "extq bwd" : "ext bwd", 0, 8, 8, 8);
+    fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW, c.gbias, c.stream);
+    if (c.getype) fgnn_launch_slab_store(p.get_ws, grid, get_len, (float*)c.getype, c.stream);
     e = hipGetLastError();
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ext backward helper launch: %s", hipGetErrorString(e));
-    return 1;
+    return FGNN_OK;
 }

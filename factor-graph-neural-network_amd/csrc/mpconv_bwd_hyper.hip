@@ -22,6 +22,7 @@
 // workgroup's slab of the caller's workspace (summed by the slab reduce of mpconv_bwd_res.hip).
 // Both kernels are HBM-bound: fan-in writes the (mostly zero) gx, fan-out reads gz.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include <stdlib.h>
 
 #define BH_THREADS 512
@@ -261,8 +262,6 @@ __global__ __launch_bounds__(BH_THREADS) void mpconv_bwd_fanout_kernel(const BhP
 // ----------------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------------
-#define BH_REJECT(code) do { if (getenv("FGNN_TRACE")) fprintf(stderr, "[fgnn] hyper-edge backward rejects shape: rule %d\n", code); return 0; } while (0)
-
 template <typename T>
 static void* bh_pick(bool fanin, int NI, int NO) {
 #define BH_CASE(ni, no) if (NI == ni && NO == no) return fanin ? (void*)mpconv_bwd_fanin_kernel<T, ni, no> : (void*)mpconv_bwd_fanout_kernel<T, ni, no>;
@@ -271,41 +270,45 @@ static void* bh_pick(bool fanin, int NI, int NO) {
     return nullptr;
 }
 
-// Returns 1 if launched, 0 if the call is not a constant-etype hyper-edge call, <0 on error.
-int fgnn_mpconv_backward_hyper(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                               const float* filters, const void* gz, const uint8_t* argmax, void* gx, void* getype,
-                               float* gfilters, float* gbias, void* workspace, int64_t workspace_bytes,
-                               fgnn_stream_t stream) {
-    if (getype) BH_REJECT(1);                                    // edge-weight gradient: the resident kernel has it
-    if (d->ext != FGNN_EXT_NONE || d->agg != FGNN_AGG_MAX || d->net != 1) BH_REJECT(2);
-    if (d->nin % 64 || d->nou % 64 || d->nin > 128 || d->nou > 128 || d->nin * d->nou > 64 * 128) BH_REJECT(3);
+// Constant-etype hyper-edge calls: one destination of degree N (fan-in, pl->mode 1) or one source (fan-out).
+int fgnn_bwd_hyper_plan(const FgnnBwdCall& c, const FgnnSwitches&, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    if (c.getype) FGNN_REJECT("hyper-edge backward", 1);                 // edge-weight gradient: the resident kernel has it
+    if (d->ext != FGNN_EXT_NONE || d->agg != FGNN_AGG_MAX || d->net != 1) FGNN_REJECT("hyper-edge backward", 2);
+    if (d->nin % 64 || d->nou % 64 || d->nin > 128 || d->nou > 128 || d->nin * d->nou > 64 * 128) FGNN_REJECT("hyper-edge backward", 3);
     const bool fanin = d->M == 1 && d->k >= 1 && d->k <= 256 && d->N >= 1;
     const bool fanout = !fanin && d->N == 1 && d->k == 1;
-    if (!fanin && !fanout) BH_REJECT(4);
-    if (fanout && !(d->y_sc == 1 && d->y_sm % 4 == 0 && d->y_sb % 4 == 0 && d->y_sm >= d->nou)) BH_REJECT(5);
-    const int64_t nw = (int64_t)d->nin * d->nou, slab_len = nw + d->nou;
-    if (!workspace || workspace_bytes < 256 * slab_len * 4) BH_REJECT(6);
+    if (!fanin && !fanout) FGNN_REJECT("hyper-edge backward", 4);
+    if (fanout && !(d->y_sc == 1 && d->y_sm % 4 == 0 && d->y_sb % 4 == 0 && d->y_sm >= d->nou)) FGNN_REJECT("hyper-edge backward", 5);
+    const int64_t slab_len = (int64_t)d->nin * d->nou + d->nou;
+    if (!c.workspace || c.workspace_bytes < 256 * slab_len * 4) FGNN_REJECT("hyper-edge backward", 6);
     const int NI = d->nin / 64, NO = d->nou / 64;
-    void* fn = d->dtype == FGNN_F32 ? bh_pick<float>(fanin, NI, NO) : bh_pick<bf16_t>(fanin, NI, NO);
-    if (!fn) BH_REJECT(7);
-    const int lds = (int)(slab_len * 4);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
+    pl->fn = d->dtype == FGNN_F32 ? bh_pick<float>(fanin, NI, NO) : bh_pick<bf16_t>(fanin, NI, NO);
+    if (!pl->fn) FGNN_REJECT("hyper-edge backward", 7);
+    pl->mode = fanin;
+    pl->lds = (int)(slab_len * 4);
+    pl->grid = (d->B + BH_WAVES - 1) / BH_WAVES < 256 ? (d->B + BH_WAVES - 1) / BH_WAVES : 256;
+    pl->block = BH_THREADS;
+    return 1;
+}
+
+int fgnn_bwd_hyper_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    const int64_t nw = (int64_t)d->nin * d->nou, slab_len = nw + d->nou;
+    if (pl.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
     }
-    int grid = (d->B + BH_WAVES - 1) / BH_WAVES;
-    if (grid > 256) grid = 256;
     BhParams p;
     p.d = *d;
-    p.x = x; p.idx = nn_idx; p.et = etype; p.W = filters; p.gz = gz; p.argmax = argmax; p.gx = gx;
-    p.ws = (float*)workspace; p.has_bias = gbias != nullptr;
-    fgnn_note_kernel("mpconv_bwd_%s_kernel<%s, %d, %d>", fanin ? "fanin" : "fanout", d->dtype ? "bf16_t" : "float", NI, NO);
+    p.x = c.x; p.idx = c.idx; p.et = c.et; p.W = c.W; p.gz = c.gz; p.argmax = c.argmax; p.gx = c.gx;
+    p.ws = (float*)c.workspace; p.has_bias = c.gbias != nullptr;
+    fgnn_note_kernel("mpconv_bwd_%s_kernel<%s, %d, %d>", pl.mode ? "fanin" : "fanout", d->dtype ? "bf16_t" : "float", d->nin / 64, d->nou / 64);
     void* args[] = {(void*)&p};
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(BH_THREADS), args, lds, st);
+    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv hyper-edge backward launch: %s", hipGetErrorString(e));
-    fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, gfilters, gbias, st);
+    fgnn_launch_slab_reduce(p.ws, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
     e = hipGetLastError();
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward helper launch: %s", hipGetErrorString(e));
-    return 1;
+    return FGNN_OK;
 }

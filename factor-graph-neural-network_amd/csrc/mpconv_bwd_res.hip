@@ -22,6 +22,7 @@
 // than the whole kernel: profiles/r01 notes).  A transposed copy of W in the workspace makes the
 // dx-projection fragments coalesced loads.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include <stdlib.h>
 
 #define BR_THREADS 512
@@ -641,7 +642,6 @@ static void* bres_pick(int KS, int NPASS) {
     return nullptr;
 }
 
-int64_t fgnn_mpconv_backward_ext_extra_bytes(const fgnn_mpconv_desc* d);
 extern "C" int64_t fgnn_mpconv_backward_workspace_bytes(const fgnn_mpconv_desc* d) {
     if (!d) return 0;
     const int64_t R = d->ext == FGNN_EXT_NONE ? d->nin : 2 * d->nin;
@@ -649,129 +649,137 @@ extern "C" int64_t fgnn_mpconv_backward_workspace_bytes(const fgnn_mpconv_desc* 
     return (256 * (nw + d->nou) + nw) * 4 + fgnn_mpconv_backward_ext_extra_bytes(d);   // 256 slabs + the transposed filter copy (+ edge-type slabs)
 }
 
-#define BR_REJECT(code) do { if (getenv("FGNN_TRACE")) fprintf(stderr, "[fgnn] resident backward rejects shape: rule %d (line %d)\n", code, __LINE__); return 0; } while (0)
-
-// Returns 1 if launched, 0 if the shape is outside this kernel's family, <0 on error.
-int fgnn_mpconv_backward_resident(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
-                                  const void* etype, const float* filters, const void* gz,
-                                  const uint8_t* argmax, void* gx, void* getype, float* gfilters,
-                                  float* gbias, void* workspace, int64_t workspace_bytes,
-                                  fgnn_stream_t stream) {
-    if (d->ext != FGNN_EXT_NONE || d->agg != FGNN_AGG_MAX) BR_REJECT(1);
-    if (d->net != 1 && d->net != 4) BR_REJECT(2);
+// The checks and geometry of one launch, pointers aside: the LDS bytes, or 0 when the call is outside this kernel's family.
+static int bres_shape(const FgnnBwdCall& c, BresParams* p) {
+    const fgnn_mpconv_desc* d = c.d;
+    if (d->ext != FGNN_EXT_NONE || d->agg != FGNN_AGG_MAX) FGNN_REJECT("resident backward", 1);
+    if (d->net != 1 && d->net != 4) FGNN_REJECT("resident backward", 2);
     const int ncols = d->nou * d->net;
-    if (ncols % 16 != 0 || ncols > 4 * BR_PASS_COLS) BR_REJECT(3);
-    if (d->nin != 64 && d->nin != 128) BR_REJECT(4);
-    if (!workspace || workspace_bytes < fgnn_mpconv_backward_workspace_bytes(d)) BR_REJECT(5);
+    if (ncols % 16 != 0 || ncols > 4 * BR_PASS_COLS) FGNN_REJECT("resident backward", 3);
+    if (d->nin != 64 && d->nin != 128) FGNN_REJECT("resident backward", 4);
+    if (!c.workspace || c.workspace_bytes < fgnn_mpconv_backward_workspace_bytes(d)) FGNN_REJECT("resident backward", 5);
     const int Kpad = d->nin;
     const int Npad = fgnn_round_up(d->N, 16);
-    if (Npad > 96 || d->N > BR_MAXN) BR_REJECT(6);
-    if (d->nou % 4 != 0 || d->nou > BR_THREADS) BR_REJECT(7);
+    if (Npad > 96 || d->N > BR_MAXN) FGNN_REJECT("resident backward", 6);
+    if (d->nou % 4 != 0 || d->nou > BR_THREADS) FGNN_REJECT("resident backward", 7);
     const bool nchw = (d->x_sn == 1 && d->x_sc == d->N);
     const bool cl = d->x_sc == 1 && (d->x_sn == d->nin || d->N == 1);   // N == 1: the node stride is moot
-    if (!nchw && !cl) BR_REJECT(8);
+    if (!nchw && !cl) FGNN_REJECT("resident backward", 8);
     const int cl_in = cl ? 1 : 0;
-    if (!cl_in && d->N == 1) BR_REJECT(9);
+    if (!cl_in && d->N == 1) FGNN_REJECT("resident backward", 9);
     // gz / argmax: dense per sample, channel-fastest [M][nou] or node-fastest [nou][M]
     const bool y_cl = d->y_sc == 1 && (d->y_sm == d->nou || d->M == 1);
     const bool y_nchw = (d->y_sm == 1 || d->M == 1) && d->y_sc == d->M;
-    if (!y_cl && !y_nchw) BR_REJECT(10);
+    if (!y_cl && !y_nchw) FGNN_REJECT("resident backward", 10);
     const int cl_y = y_cl ? 1 : 0;
-    if (!cl_y && d->M == 1) BR_REJECT(11);
+    if (!cl_y && d->M == 1) FGNN_REJECT("resident backward", 11);
     const int mk = d->M * d->k;
     const int NPASS = (ncols + BR_PASS_COLS - 1) / BR_PASS_COLS;
     const int KS = Kpad / 4;
     const int PT = KS == 32 ? 30 : 18;
     const int otp = BR_PASS_COLS / d->net;
     const int otcP = otp < d->nou ? otp : d->nou;                      // channels per pass slice
-    if (NPASS > 1 && d->nou % otp != 0) BR_REJECT(21);
+    if (NPASS > 1 && d->nou % otp != 0) FGNN_REJECT("resident backward", 21);
     const int XQ = (d->nin * d->N + BR_THREADS - 1) / BR_THREADS;
     const int GQ = (d->M * otcP + BR_THREADS - 1) / BR_THREADS;
-    if (XQ + GQ > PT) BR_REJECT(12);
-    if (mk * d->net > BR_THREADS * BR_EPT || mk > BR_THREADS) BR_REJECT(13);
-    if (d->M * otcP > BR_THREADS * BR_APT * 4 || otcP % 4 != 0 || d->nou % 4 != 0) BR_REJECT(14);
+    if (XQ + GQ > PT) FGNN_REJECT("resident backward", 12);
+    if (mk * d->net > BR_THREADS * BR_EPT || mk > BR_THREADS) FGNN_REJECT("resident backward", 13);
+    if (d->M * otcP > BR_THREADS * BR_APT * 4 || otcP % 4 != 0 || d->nou % 4 != 0) FGNN_REJECT("resident backward", 14);
     int et_mode;
     if (d->net == 1) {
-        if (!((d->et_sk == 1 || d->k == 1) && (d->et_sm == d->k || d->M == 1))) BR_REJECT(15);
+        if (!((d->et_sk == 1 || d->k == 1) && (d->et_sm == d->k || d->M == 1))) FGNN_REJECT("resident backward", 15);
         et_mode = 1;
     } else if (mk == 1) {
-        if (d->et_se != 1) BR_REJECT(16);
+        if (d->et_se != 1) FGNN_REJECT("resident backward", 16);
         et_mode = 1;
     } else if ((d->et_sk == 1 || d->k == 1) && (d->et_sm == d->k || d->M == 1) && d->et_se == mk) {
         et_mode = 0;
     } else if (d->et_se == 1 && d->et_sk == d->net && (d->et_sm == d->k * d->net || d->M == 1)) {
         et_mode = 1;
     } else {
-        BR_REJECT(99);
+        FGNN_REJECT("resident backward", 99);
     }
 
-    BresParams p;
-    p.d = *d;
-    p.x = x; p.idx = nn_idx; p.et = etype; p.W = filters; p.gz = gz; p.argmax = argmax;
-    p.gx = gx; p.get = getype; p.has_bias = gbias != nullptr;
-    p.Npad = Npad; p.Kpad = Kpad;
-    p.XS = (Kpad + 29) / 32 * 32 + 2;
-    p.PS = BR_PASS_COLS + 4;
-    p.GS = otcP + 4;
-    p.otcP = otcP;
-    if ((int64_t)d->M * p.GS >= (1 << 23)) BR_REJECT(17);
-    p.cl_in = cl_in; p.cl_y = cl_y; p.et_mode = et_mode; p.XQ = XQ;
-    p.fast_bias = (cl_y && BR_THREADS % otcP == 0) ? 1 : 0;
-    { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
-    p.xdiv = cl_in ? d->nin : d->N;
-    p.ydiv = cl_y ? otcP : d->M;
-    if (p.xdiv == 1 || p.ydiv == 1) BR_REJECT(18);
-    p.xmagic = (unsigned)((0x100000000ULL + p.xdiv - 1) / p.xdiv);
-    p.mkmagic = mk == 1 ? 0u : (unsigned)((0x100000000ULL + mk - 1) / mk);
-    p.ymagic = (unsigned)((0x100000000ULL + p.ydiv - 1) / p.ydiv);
-    p.y4magic = otcP / 4 == 1 ? 0u : (unsigned)((0x100000000ULL + otcP / 4 - 1) / (otcP / 4));
-    if (cl_y && otcP / 4 == 1) BR_REJECT(22);
+    p->d = *d;
+    p->Npad = Npad; p->Kpad = Kpad;
+    p->XS = (Kpad + 29) / 32 * 32 + 2;
+    p->PS = BR_PASS_COLS + 4;
+    p->GS = otcP + 4;
+    p->otcP = otcP;
+    if ((int64_t)d->M * p->GS >= (1 << 23)) FGNN_REJECT("resident backward", 17);
+    p->cl_in = cl_in; p->cl_y = cl_y; p->et_mode = et_mode; p->XQ = XQ;
+    p->fast_bias = (cl_y && BR_THREADS % otcP == 0) ? 1 : 0;
+    p->xdiv = cl_in ? d->nin : d->N;
+    p->ydiv = cl_y ? otcP : d->M;
+    if (p->xdiv == 1 || p->ydiv == 1) FGNN_REJECT("resident backward", 18);
+    p->xmagic = (unsigned)((0x100000000ULL + p->xdiv - 1) / p->xdiv);
+    p->mkmagic = mk == 1 ? 0u : (unsigned)((0x100000000ULL + mk - 1) / mk);
+    p->ymagic = (unsigned)((0x100000000ULL + p->ydiv - 1) / p->ydiv);
+    p->y4magic = otcP / 4 == 1 ? 0u : (unsigned)((0x100000000ULL + otcP / 4 - 1) / (otcP / 4));
+    if (cl_y && otcP / 4 == 1) FGNN_REJECT("resident backward", 22);
     int off = 0;
-    p.off_xs = off;  off += Npad * p.XS;                    off = fgnn_round_up(off, 4);
-    p.off_pb = off;  off += Npad * p.PS;                    off = fgnn_round_up(off, 4);
-    p.off_idx = off; off += fgnn_round_up(mk, 4);
-    p.off_et = off;  off += fgnn_round_up(mk * d->net, 4);
-    p.off_gz = off;  off += d->M * p.GS;                    off = fgnn_round_up(off, 4);
-    p.off_am = off;  off += (d->M * p.GS + 3) / 4;          off = fgnn_round_up(off, 4);
-    p.off_cs = off;  off += 2 * BR_MAXN + 4;
-    p.off_cl = off;  off += fgnn_round_up(mk, 4);
-    p.off_ce = off;  off += fgnn_round_up(mk, 4);
+    p->off_xs = off;  off += Npad * p->XS;                    off = fgnn_round_up(off, 4);
+    p->off_pb = off;  off += Npad * p->PS;                    off = fgnn_round_up(off, 4);
+    p->off_idx = off; off += fgnn_round_up(mk, 4);
+    p->off_et = off;  off += fgnn_round_up(mk * d->net, 4);
+    p->off_gz = off;  off += d->M * p->GS;                    off = fgnn_round_up(off, 4);
+    p->off_am = off;  off += (d->M * p->GS + 3) / 4;          off = fgnn_round_up(off, 4);
+    p->off_cs = off;  off += 2 * BR_MAXN + 4;
+    p->off_cl = off;  off += fgnn_round_up(mk, 4);
+    p->off_ce = off;  off += fgnn_round_up(mk, 4);
     {   // few owners (N * channel groups <= 64): split their in-edge lists over up to 32 thread groups
         const int ogv = (otcP + 3) / 4, owners = d->N * ogv;
-        p.JS = 1;
-        if (owners <= 64 && mk >= 4 * owners) { p.JS = BR_THREADS / owners; if (p.JS > 32) p.JS = 32; }
-        p.off_red = off;
-        if (p.JS > 1) off += p.JS * owners * 4 * d->net;
+        p->JS = 1;
+        if (owners <= 64 && mk >= 4 * owners) { p->JS = BR_THREADS / owners; if (p->JS > 32) p->JS = 32; }
+        p->off_red = off;
+        if (p->JS > 1) off += p->JS * owners * 4 * d->net;
     }
-    const int lds = off * 4;
-    if (lds > 160 * 1024) BR_REJECT(19);
-    void* fn = nullptr;
-    if (d->dtype == FGNN_F32) fn = d->net == 1 ? bres_pick<float, 1>(KS, NPASS) : bres_pick<float, 4>(KS, NPASS);
-    else fn = d->net == 1 ? bres_pick<bf16_t, 1>(KS, NPASS) : bres_pick<bf16_t, 4>(KS, NPASS);
-    if (!fn) BR_REJECT(20);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
-    int grid = 256;
-    if (grid > d->B) grid = d->B;
+    if (off * 4 > 160 * 1024) FGNN_REJECT("resident backward", 19);
+    return off * 4;
+}
+
+int fgnn_bwd_res_plan(const FgnnBwdCall& c, const FgnnSwitches&, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    BresParams p;
+    pl->lds = bres_shape(c, &p);
+    if (!pl->lds) return 0;
+    const int KS = d->nin / 4, NPASS = (d->nou * d->net + BR_PASS_COLS - 1) / BR_PASS_COLS;
+    if (d->dtype == FGNN_F32) pl->fn = d->net == 1 ? bres_pick<float, 1>(KS, NPASS) : bres_pick<float, 4>(KS, NPASS);
+    else pl->fn = d->net == 1 ? bres_pick<bf16_t, 1>(KS, NPASS) : bres_pick<bf16_t, 4>(KS, NPASS);
+    if (!pl->fn) FGNN_REJECT("resident backward", 20);
+    int grid = d->B < 256 ? d->B : 256;
     const int chunk = (d->B + grid - 1) / grid;
-    grid = (d->B + chunk - 1) / chunk;                // every workgroup owns >= 1 sample (writes its slab)
+    pl->grid = (d->B + chunk - 1) / chunk;            // every workgroup owns >= 1 sample (writes its slab)
+    pl->block = BR_THREADS;
+    return 1;
+}
+
+int fgnn_bwd_res_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    BresParams p;
+    bres_shape(c, &p);
+    p.x = c.x; p.idx = c.idx; p.et = c.et; p.W = c.W; p.gz = c.gz; p.argmax = c.argmax;
+    p.gx = c.gx; p.get = c.getype; p.has_bias = c.gbias != nullptr;
+    { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
+    if (pl.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
+    }
+    const int ncols = d->nou * d->net, KS = d->nin / 4, NPASS = (ncols + BR_PASS_COLS - 1) / BR_PASS_COLS;
     const int64_t nw = (int64_t)d->nin * ncols;
     const int64_t slab_len = nw + d->nou;
-    p.ws = (float*)workspace;
+    p.ws = (float*)c.workspace;
     float* Wt = p.ws + 256 * slab_len;
     p.Wt = Wt;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bres_transpose_kernel, dim3((ncols + 31) / 32, (d->nin + 31) / 32), dim3(256), 0, st,
-                       filters, Wt, d->nin, ncols);
+    hipLaunchKernelGGL(bres_transpose_kernel, dim3((ncols + 31) / 32, (d->nin + 31) / 32), dim3(256), 0, c.stream,
+                       c.W, Wt, d->nin, ncols);
     fgnn_note_kernel("mpconv_bwd_res_kernel<%s, %d, %d, %d, %s>", d->dtype ? "bf16_t" : "float", d->net, KS, NPASS,
                      (KS == 16 && NPASS <= 2) ? "true" : "false");
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(BR_THREADS), args, lds, st);
+    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv resident backward launch: %s", hipGetErrorString(e));
-    fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, gfilters, gbias, st);
+    fgnn_launch_slab_reduce(p.ws, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
     e = hipGetLastError();
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward helper launch: %s", hipGetErrorString(e));
-    return 1;
+    return FGNN_OK;
 }

@@ -24,6 +24,7 @@
 // One 1024-thread workgroup (16 waves) per CU: the LDS images of a sample (x double-buffered 2 x 14 KB, P / dP 50 KB —
 // one buffer, used in turn —, gz+argmax 12..25 KB, the per-wave detype images 55 KB) do not leave room for two.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include <stdlib.h>
 
 #define BS_THREADS 1024
@@ -581,125 +582,108 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
 // ----------------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------------
-int fgnn_mpconv_backward_ws(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                            const float* filters, const void* gz, const uint8_t* argmax, void* gx, void* getype,
-                            float* gfilters, float* gbias, void* workspace, int64_t workspace_bytes,
-                            fgnn_stream_t stream);
-
-#define BS_REJECT(code) do { if (getenv("FGNN_TRACE")) fprintf(stderr, "[fgnn] sg backward rejects shape: rule %d\n", code); return 0; } while (0)
-
-// Returns 1 if launched, 0 if the call is outside this kernel's family, <0 on error.  d->reserved carries the largest
-// in-degree of the (batch-shared) neighbour table as the caller measured it (0 = unknown: not this kernel).
-int fgnn_mpconv_backward_sg(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                            const float* filters, const void* gz, const uint8_t* argmax, void* gx, void* getype,
-                            float* gfilters, float* gbias, void* workspace, int64_t workspace_bytes,
-                            fgnn_stream_t stream) {
-    static const bool off = getenv("FGNN_NO_SG") != nullptr;
-    if (off) BS_REJECT(0);
-    if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->agg != FGNN_AGG_MAX || d->net != 4) BS_REJECT(1);
+// The shared-graph rules (mpconv_dispatch.h).  d->reserved carries the largest in-degree of the (batch-shared) neighbour table as
+// the caller measured it (0 = unknown: not these kernels).
+int fgnn_bwd_sg_rules(const FgnnBwdCall& c, const FgnnSwitches& sw, bool layout_only, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    if (sw.no_sg) FGNN_REJECT("sg backward", 0);
+    if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->agg != FGNN_AGG_MAX || d->net != 4) FGNN_REJECT("sg backward", 1);
+    if (d->k != 3 && d->k != 6) FGNN_REJECT("sg backward", 3);
+    if (d->idx_sb != 0 && d->B > 1) FGNN_REJECT("sg backward", 4);
+    if (!(d->idx_sk == 1 && d->idx_sm == d->k)) FGNN_REJECT("sg backward", 5);
+    if (!c.getype || !c.argmax || !c.gbias) FGNN_REJECT("sg backward", 6);
+    if (!(d->x_sc == 1 && d->x_sn == d->nin && d->x_sb % 8 == 0)) FGNN_REJECT("sg backward", 9);
+    if (!(d->y_sc == 1 && (d->y_sm == d->nou || d->M == 1) && d->y_sb % 8 == 0)) FGNN_REJECT("sg backward", 10);
+    if (!(d->et_se == 1 && d->et_sk == 4 && (d->et_sm == 4 * d->k || d->M == 1) && d->et_sb % 4 == 0)) FGNN_REJECT("sg backward", 11);
+    if (layout_only) return 1;
     // 64 -> 128: the output channels are independent and every gradient is a sum over them, so the call runs as TWO launches
     // of this 64 -> 64 kernel over the halves of gz / argmax / W's columns; the second one ADDS to gx and getype (one more bf16
     // rounding of those two) and its dW / dbias land in the upper halves of gfilters' columns / gbias.
-    static const bool no_split = getenv("FGNN_SG_NOSPLIT") != nullptr;
-    const bool split = d->nin == 64 && d->nou == 128 && !no_split;
-    if (d->nin == 128 && d->nou == 64) {              // third generation, two launches over the input-channel halves (mpconv_bwd_ws.hip); 0 = not its shape
-        const int r = fgnn_mpconv_backward_ws(d, x, nn_idx, etype, filters, gz, argmax, gx, getype, gfilters, gbias, workspace,
-                                              workspace_bytes, stream);
-        if (r != 0) return r;
-    }
-    if (d->nin != 64 || (d->nou != 64 && !split)) BS_REJECT(2);
-    if (d->k != 3 && d->k != 6) BS_REJECT(3);
-    if (d->idx_sb != 0 && d->B > 1) BS_REJECT(4);
-    if (!(d->idx_sk == 1 && d->idx_sm == d->k)) BS_REJECT(5);
-    if (!getype || !argmax || !gbias) BS_REJECT(6);
-    if (d->N < 1 || d->N > BS_MAXN || d->M < 1 || d->M > 96) BS_REJECT(7);
+    const bool split = d->nin == 64 && d->nou == 128 && !sw.sg_nosplit;
+    if (d->nin != 64 || (d->nou != 64 && !split)) FGNN_REJECT("sg backward", 2);
+    if (d->N < 1 || d->N > BS_MAXN || d->M < 1 || d->M > 96) FGNN_REJECT("sg backward", 7);
     const int indeg = d->reserved & 0xffff;
     const int KC = d->k, DEG = KC == 6 ? 3 : 6;        // LDPC: degree-6 checks <-> degree-3 variables
-    if (indeg < 1 || indeg > DEG) BS_REJECT(8);
-    if (!(d->x_sc == 1 && d->x_sn == d->nin && d->x_sb % 8 == 0)) BS_REJECT(9);
-    if (!(d->y_sc == 1 && (d->y_sm == d->nou || d->M == 1) && d->y_sb % 8 == 0)) BS_REJECT(10);
-    if (!(d->et_se == 1 && d->et_sk == 4 && (d->et_sm == 4 * d->k || d->M == 1) && d->et_sb % 4 == 0)) BS_REJECT(11);
-    if (((uintptr_t)x & 15) || ((uintptr_t)gz & 15) || ((uintptr_t)etype & 7) || ((uintptr_t)argmax & 7) ||
-        ((uintptr_t)gx & 7)) BS_REJECT(12);
-    const int64_t nw = (int64_t)d->nin * 64 * 4, slab_len = nw + 64;                  // of ONE launch (64 output channels)
-    if (!workspace || workspace_bytes < (split ? 2 : 1) * 256 * slab_len * 4) BS_REJECT(13);
+    if (indeg < 1 || indeg > DEG) FGNN_REJECT("sg backward", 8);
+    if (((uintptr_t)c.x & 15) || ((uintptr_t)c.gz & 15) || ((uintptr_t)c.et & 7) || ((uintptr_t)c.argmax & 7) ||
+        ((uintptr_t)c.gx & 7)) FGNN_REJECT("sg backward", 12);
+    const int64_t slab_len = (int64_t)d->nin * 64 * 4 + 64;                          // of ONE launch (64 output channels)
+    if (!c.workspace || c.workspace_bytes < (split ? 2 : 1) * 256 * slab_len * 4) FGNN_REJECT("sg backward", 13);
     const int NPW = (d->N + BS_WAVES - 1) / BS_WAVES, DPW = (d->M + BS_WAVES - 1) / BS_WAVES;
-    void* fn = nullptr;
     const int GSL = (d->M * 16 + BS_THREADS - 1) / BS_THREADS;
-    if (KC == 6 && NPW <= 6 && DPW <= 3 && GSL == 1) fn = (void*)mpconv_bwd_sg_kernel<6, 3, 6, 3, 1>;
-    else if (KC == 3 && NPW <= 3 && DPW <= 6) fn = GSL == 1 ? (void*)mpconv_bwd_sg_kernel<3, 6, 3, 6, 1> : (void*)mpconv_bwd_sg_kernel<3, 6, 3, 6, 2>;
-    if (!fn) BS_REJECT(14);
+    pl->fn = nullptr;
+    if (KC == 6 && NPW <= 6 && DPW <= 3 && GSL == 1) pl->fn = (void*)mpconv_bwd_sg_kernel<6, 3, 6, 3, 1>;
+    else if (KC == 3 && NPW <= 3 && DPW <= 6) pl->fn = GSL == 1 ? (void*)mpconv_bwd_sg_kernel<3, 6, 3, 6, 1> : (void*)mpconv_bwd_sg_kernel<3, 6, 3, 6, 2>;
+    if (!pl->fn) FGNN_REJECT("sg backward", 14);
+    pl->mode = GSL;
+    pl->split = split ? 1 : 0;
+    return 1;
+}
 
-    {                                                 // third generation first (mpconv_bwd_ws.hip; also splits 64 -> 128); 0 = not its shape
-        const int r = fgnn_mpconv_backward_ws(d, x, nn_idx, etype, filters, gz, argmax, gx, getype, gfilters, gbias, workspace,
-                                              workspace_bytes, stream);
-        if (r != 0) return r;
-    }
-    BsParams p;
-    p.x = (const uint16_t*)x; p.idx = nn_idx; p.et = (const uint16_t*)etype; p.W = filters;
-    p.gz = (const uint16_t*)gz; p.argmax = argmax; p.gx = (uint16_t*)gx; p.get = (uint16_t*)getype;
-    p.ws = (float*)workspace;
-    p.B = d->B; p.N = d->N; p.M = d->M; p.Npad = fgnn_round_up(d->N, 32);
-    p.NPW = KC == 6 ? 6 : 3; p.DPW = KC == 6 ? 3 : 6;
-    p.x_sb = d->x_sb; p.et_sb = d->et_sb; p.y_sb = d->y_sb;
-    p.y_ld = d->nou; p.w_ld = d->nou * 4; p.accum = 0;
+// LDS offsets of one launch; returns the bytes
+static int bs_layout(const fgnn_mpconv_desc* d, BsParams* p) {
+    const int KC = d->k, DEG = KC == 6 ? 3 : 6;
+    p->Npad = fgnn_round_up(d->N, 32);
+    p->NPW = KC == 6 ? 6 : 3; p->DPW = KC == 6 ? 3 : 6;
     int off_b = 0;
     auto take = [&](int bytes) { const int o = off_b; off_b = fgnn_round_up(off_b + bytes, 16); return o; };
-    p.off_xs = take(2 * p.Npad * BS_XSB);
-    p.off_pd = take(p.Npad * BS_PSB);
-    p.off_ga = take(d->M * BS_GSB);
-    p.zbytes = (KC == 3 ? 2 : 1) * KC * 2 * BS_ZCS;                      // 3 slots: two destinations per image
-    p.off_z = take(BS_WAVES * p.zbytes + 16 * BS_ZCS);                  // + slack: the 16-column tile reads past column 2 KC
-    p.off_es = take(BS_WAVES * 4 * p.NPW * (DEG > 4 ? 16 : 8));         // per-wave [4 e][NPW][8 | 4 slots] bf16 edge-type images
-    p.off_tab = take(d->N * DEG * 4);
-    p.off_idx = take(d->M * KC * 4);
-    p.off_gst = take(8 * d->M * KC);
-    p.off_red = p.off_xs;                                               // dbias partials: after the last sample (16 KB)
-    const int lds = off_b > 16384 ? off_b : 16384;
-    if (lds > 160 * 1024) BS_REJECT(15);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    int grid = 256;
-    if (grid > d->B) grid = d->B;
-    const int chunk = (d->B + grid - 1) / grid;
-    grid = (d->B + chunk - 1) / chunk;
-    hipStream_t st = (hipStream_t)stream;
-    fgnn_note_kernel(split ? "mpconv_bwd_sg_kernel<%d, %d, %d, %d, %d> x2" : "mpconv_bwd_sg_kernel<%d, %d, %d, %d, %d>", KC, DEG, p.NPW, p.DPW, GSL);
-    p.prof = nullptr;
-#ifdef FGNN_ENABLE_PROF
-    static long long* prof_buf = nullptr;
-    if (getenv("FGNN_PROF")) {
-        if (!prof_buf) (void)hipMalloc(&prof_buf, 64 * 8);
-        (void)hipMemset(prof_buf, 0, 64 * 8);
-        p.prof = prof_buf;
-    }
-#endif
+    p->off_xs = take(2 * p->Npad * BS_XSB);
+    p->off_pd = take(p->Npad * BS_PSB);
+    p->off_ga = take(d->M * BS_GSB);
+    p->zbytes = (KC == 3 ? 2 : 1) * KC * 2 * BS_ZCS;                    // 3 slots: two destinations per image
+    p->off_z = take(BS_WAVES * p->zbytes + 16 * BS_ZCS);                // + slack: the 16-column tile reads past column 2 KC
+    p->off_es = take(BS_WAVES * 4 * p->NPW * (DEG > 4 ? 16 : 8));       // per-wave [4 e][NPW][8 | 4 slots] bf16 edge-type images
+    p->off_tab = take(d->N * DEG * 4);
+    p->off_idx = take(d->M * KC * 4);
+    p->off_gst = take(8 * d->M * KC);
+    p->off_red = p->off_xs;                                             // dbias partials: after the last sample (16 KB)
+    return off_b > 16384 ? off_b : 16384;
+}
+
+int fgnn_bwd_sg_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
+    const int r = fgnn_bwd_sg_rules(c, sw, false, pl);
+    if (r <= 0) return r;
+    BsParams p;
+    pl->lds = bs_layout(c.d, &p);
+    if (pl->lds > 160 * 1024) FGNN_REJECT("sg backward", 15);
+    int grid = c.d->B < 256 ? c.d->B : 256;
+    const int chunk = (c.d->B + grid - 1) / grid;
+    pl->grid = (c.d->B + chunk - 1) / chunk;
+    pl->block = BS_THREADS;
+    return 1;
+}
+
+int fgnn_bwd_sg_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    BsParams p;
+    bs_layout(d, &p);
+    p.x = (const uint16_t*)c.x; p.idx = c.idx; p.et = (const uint16_t*)c.et; p.W = c.W;
+    p.gz = (const uint16_t*)c.gz; p.argmax = c.argmax; p.gx = (uint16_t*)c.gx; p.get = (uint16_t*)c.getype;
+    p.ws = (float*)c.workspace;
+    p.B = d->B; p.N = d->N; p.M = d->M;
+    p.x_sb = d->x_sb; p.et_sb = d->et_sb; p.y_sb = d->y_sb;
+    p.y_ld = d->nou; p.w_ld = d->nou * 4; p.accum = 0;
+    const int64_t nw = (int64_t)d->nin * 64 * 4, slab_len = nw + 64;
+    hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
+    const int KC = d->k, DEG = KC == 6 ? 3 : 6;
+    fgnn_note_kernel(pl.split ? "mpconv_bwd_sg_kernel<%d, %d, %d, %d, %d> x2" : "mpconv_bwd_sg_kernel<%d, %d, %d, %d, %d>", KC, DEG, p.NPW, p.DPW, pl.mode);
+    p.prof = fgnn_prof_begin();
     void* args[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(BS_THREADS), args, lds, st);
+    e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv sg backward launch: %s", hipGetErrorString(e));
-#ifdef FGNN_ENABLE_PROF
-    if (p.prof) {                                     // tuning aid: phase timeline of one sample, waves 0 / 4 / 8 / 12 (shader clocks)
-        long long h[64];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, p.prof, sizeof(h), hipMemcpyDeviceToHost);
-        for (int w = 0; w < 4; ++w) {
-            fprintf(stderr, "[fgnn prof sg bwd] wave %d:", 4 * w);
-            for (int i = 0; i < 11; ++i) fprintf(stderr, " %lld", h[w * 16 + i] - h[0]);
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
-    if (!split) fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, gfilters, gbias, st);
+    fgnn_prof_print(p.prof, "sg bwd", 0, 4, 11, 16);             // phase timeline of one sample, waves 0 / 4 / 8 / 12 (shader clocks)
+    if (!pl.split) fgnn_launch_slab_reduce(p.ws, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
     else {
         // slab rows are 256 columns of gfilters' 512: lower half, then the second launch on the upper 64 output channels
-        fgnn_launch_slab_reduce_ld(p.ws, grid, slab_len, nw, 256, 512, gfilters, gbias, st);
-        p.ws += (int64_t)grid * slab_len;            // (its own slabs: the first launch's fold may be a recorded one, fold_batch.hip)
+        fgnn_launch_slab_reduce_ld(p.ws, pl.grid, slab_len, nw, 256, 512, c.gW, c.gbias, c.stream);
+        p.ws += (int64_t)pl.grid * slab_len;         // (its own slabs: the first launch's fold may be a recorded one, fold_batch.hip)
         p.W += 256; p.gz += 64; p.argmax += 64; p.accum = 1;
-        e = hipLaunchKernel(fn, dim3(grid), dim3(BS_THREADS), args, lds, st);
+        e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
         if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv sg backward launch (upper half): %s", hipGetErrorString(e));
-        fgnn_launch_slab_reduce_ld(p.ws, grid, slab_len, nw, 256, 512, gfilters + 256, gbias + 64, st);
+        fgnn_launch_slab_reduce_ld(p.ws, pl.grid, slab_len, nw, 256, 512, c.gW + 256, c.gbias + 64, c.stream);
     }
     e = hipGetLastError();
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward helper launch: %s", hipGetErrorString(e));
-    return 1;
+    return FGNN_OK;
 }

@@ -32,6 +32,7 @@
 //   3  waves 0-1 dx, waves 2,3,6,7 dW (48 MFMAs per SIMD), waves 4-5 build G / etT of sample s+1 from registers prefetched in
 //      phase 1 and wait for its x (LDS-DMA)
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include <stdlib.h>
 
 #define BW_THREADS 512       // 8 waves x 256 VGPRs: the roles' resident state (64 MFMA registers, 16 + 48 of the projection, ~60 of the staging) spills at 128
@@ -803,17 +804,10 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
 // ----------------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------------
-#define BW_REJECT(code) do { if (getenv("FGNN_TRACE")) fprintf(stderr, "[fgnn] ws backward rejects shape: rule %d\n", code); return 0; } while (0)
-
-// Called first by fgnn_mpconv_backward_sg (mpconv_bwd_sg.hip) for the 64 -> 64 calls: 1 = launched, 0 = not this kernel's
-// shape (the second-generation kernel takes it), < 0 = error.
-int fgnn_check_desc(const fgnn_mpconv_desc* d);
-
-// Does this descriptor go to the kernel above, and with how many table entries?  (The shape rules of fgnn_mpconv_backward_ws that do
+// Does this descriptor go to the kernel above, and with how many table entries?  (The shape rules of fgnn_bwd_ws_plan that do
 // not depend on pointers.)
 static int bw_tables_count(const fgnn_mpconv_desc* d) {
-    static const bool off = getenv("FGNN_NO_WS") != nullptr;
-    if (off || d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->net != 4 || d->agg != FGNN_AGG_MAX) return 0;
+    if (fgnn_switches().no_ws || d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->net != 4 || d->agg != FGNN_AGG_MAX) return 0;
     if (d->nin != 64 || (d->nou != 64 && d->nou != 128) || (d->k != 3 && d->k != 6)) return 0;
     if (d->idx_sb != 0 && d->B > 1) return 0;
     if (!(d->idx_sk == 1 && d->idx_sm == d->k)) return 0;
@@ -844,110 +838,91 @@ extern "C" int fgnn_mpconv_backward_tables(const fgnn_mpconv_desc* d, const int6
     return FGNN_OK;
 }
 
-// The tables of the NEXT backward launch on this thread (fgnn_mpconv_backward_with_tables sets them around its call).
-static thread_local const void* bw_pending_tables = nullptr;
-void fgnn_bw_set_pending_tables(const void* t) { bw_pending_tables = t; }
-
-int fgnn_mpconv_backward_ws(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                            const float* filters, const void* gz, const uint8_t* argmax, void* gx, void* getype,
-                            float* gfilters, float* gbias, void* workspace, int64_t workspace_bytes,
-                            fgnn_stream_t stream) {
-    static const bool off = getenv("FGNN_NO_WS") != nullptr;       // (tests: the second-generation kernels on the same shapes)
-    if (off) BW_REJECT(0);
-    const bool split = d->nin == 64 && d->nou == 128;                    // 64 -> 128: two launches over the halves of the output channels
+// Asked before the second-generation kernel, behind its rules (fgnn_bwd_sg_rules): 64 -> 64, 64 -> 128 as two launches over the
+// output-channel halves (pl->split), 128 -> 64 as two launches over the input-channel halves (pl->mode).  pl->aux: the call's
+// per-graph tables fit this descriptor.
+int fgnn_bwd_ws_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
     // 128 -> 64 (round 5): two launches over the halves of the INPUT channels.  Everything the kernel computes is linear in the
     // input-channel block it is given — P = P_lo + P_hi, so detype = sum_o G P splits into two addends (the second launch ADDS to
     // getype); dP depends on G and etype only; dx and dW are per input channel — so the 64-channel kernel runs twice on x / W / gx /
     // gfilters offset by 64 channels / rows (x and gx rows stay 128 apart in memory: x_ld), dbias counted once.  Replaces the
     // first-generation mpconv_bwd_b16_kernel<4,2> for these calls (245 us at 4096 codewords, profiles/r04).
     const bool ksplit = d->nin == 128 && d->nou == 64;
-    if (ksplit) {      // (the layout rules fgnn_mpconv_backward_sg checks for its callers)
-        if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->agg != FGNN_AGG_MAX || d->net != 4 || (d->k != 3 && d->k != 6)) BW_REJECT(10);
-        if ((d->idx_sb != 0 && d->B > 1) || !(d->idx_sk == 1 && d->idx_sm == d->k) || !getype || !argmax || !gbias) BW_REJECT(11);
-        if (!(d->x_sc == 1 && d->x_sn == d->nin) || !(d->y_sc == 1 && (d->y_sm == d->nou || d->M == 1))) BW_REJECT(12);
-        if (!(d->et_se == 1 && d->et_sk == 4 && (d->et_sm == 4 * d->k || d->M == 1))) BW_REJECT(13);
-    }
-    if (!ksplit && (d->nin != 64 || (d->nou != 64 && !split))) BW_REJECT(1);
+    const int r = fgnn_bwd_sg_rules(c, sw, ksplit, pl);     // (128 -> 64: the layout rules only; the sg kernel has no such form)
+    if (r <= 0) return r;
+    if (sw.no_ws) FGNN_REJECT("ws backward", 0);            // (tests: the second-generation kernels on the same shapes)
+    const bool split = !ksplit && pl->split;                 // 64 -> 128: two launches over the halves of the output channels
     const int KC = d->k, DEG = KC == 6 ? 3 : 6;
     const int indeg = d->reserved & 0xffff;
-    if (indeg < 1 || indeg > DEG) BW_REJECT(2);
-    if (KC == 6 ? (d->N > 96 || d->M > 48) : (d->N > 64 || d->M > 96)) BW_REJECT(3);
-    if ((d->M * KC) & 1) BW_REJECT(4);                                  // getype leaves as whole 16-byte lanes
-    if (((uintptr_t)getype & 15) || ((uintptr_t)x & 15) || ((uintptr_t)gz & 15) || ((uintptr_t)argmax & 7) || ((uintptr_t)gx & 7) ||
-        ((uintptr_t)etype & 7)) BW_REJECT(5);
-    if ((d->x_sb % 8) != 0 || (d->y_sb % 8) != 0 || (d->et_sb % 4) != 0) BW_REJECT(6);
-    const int64_t nw = 64 * 256, slab_len = nw + 64;
-    if (!workspace || workspace_bytes < ((split || ksplit) ? 2 : 1) * 256 * slab_len * 4) BW_REJECT(7);
+    if (indeg < 1 || indeg > DEG) FGNN_REJECT("ws backward", 2);
+    if (KC == 6 ? (d->N > 96 || d->M > 48) : (d->N > 64 || d->M > 96)) FGNN_REJECT("ws backward", 3);
+    if ((d->M * KC) & 1) FGNN_REJECT("ws backward", 4);                  // getype leaves as whole 16-byte lanes
+    if (((uintptr_t)c.getype & 15) || ((uintptr_t)c.x & 15) || ((uintptr_t)c.gz & 15) || ((uintptr_t)c.argmax & 7) || ((uintptr_t)c.gx & 7) ||
+        ((uintptr_t)c.et & 7)) FGNN_REJECT("ws backward", 5);
+    if ((d->x_sb % 8) != 0 || (d->y_sb % 8) != 0 || (d->et_sb % 4) != 0) FGNN_REJECT("ws backward", 6);
+    const int64_t slab_len = 64 * 256 + 64;
+    if (!c.workspace || c.workspace_bytes < ((split || ksplit) ? 2 : 1) * 256 * slab_len * 4) FGNN_REJECT("ws backward", 7);
+    const bool nl48 = KC == 3 && d->N <= 48;                   // the LDPC F -> V call: 48 factor nodes
+    pl->fn = ksplit ? (KC == 6 ? (void*)mpconv_bwd_ws_kernel<6, 3, 128> : nl48 ? (void*)mpconv_bwd_ws_kernel<3, 6, 128, 48> : (void*)mpconv_bwd_ws_kernel<3, 6, 128>)
+                    : (KC == 6 ? (void*)mpconv_bwd_ws_kernel<6, 3> : nl48 ? (void*)mpconv_bwd_ws_kernel<3, 6, 64, 48> : (void*)mpconv_bwd_ws_kernel<3, 6>);
+    static_assert(BwLayout<6>::BYTES <= 160 * 1024 && BwLayout<3>::BYTES <= 160 * 1024, "LDS");
+    pl->lds = KC == 6 ? BwLayout<6>::BYTES : BwLayout<3>::BYTES;
+    int grid = d->B < 256 ? d->B : 256;      // one workgroup per CU (caps of 248 / 240 / 224 to leave CUs to the other stream: no effect, profiles/r05/README.md)
+    const int chunk = (d->B + grid - 1) / grid;
+    pl->grid = (d->B + chunk - 1) / chunk;
+    pl->block = BW_THREADS;
+    pl->split = split ? 1 : 0;
+    pl->mode = ksplit ? 1 : 0;
+    pl->aux = c.tables && bw_tables_count(d) > 0;
+    return 1;
+}
 
+int fgnn_bwd_ws_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    const bool split = pl.split, ksplit = pl.mode;
+    const int KC = d->k, DEG = KC == 6 ? 3 : 6;
+    const int64_t nw = 64 * 256, slab_len = nw + 64;
     BwParams p;
-    p.x = (const uint16_t*)x; p.idx = nn_idx; p.et = (const uint16_t*)etype; p.W = filters;
-    p.gz = (const uint16_t*)gz; p.argmax = argmax; p.gx = (uint16_t*)gx; p.get = (uint16_t*)getype;
-    p.ws = (float*)workspace;
+    p.x = (const uint16_t*)c.x; p.idx = c.idx; p.et = (const uint16_t*)c.et; p.W = c.W;
+    p.gz = (const uint16_t*)c.gz; p.argmax = c.argmax; p.gx = (uint16_t*)c.gx; p.get = (uint16_t*)c.getype;
+    p.ws = (float*)c.workspace;
     p.B = d->B; p.N = d->N; p.M = d->M;
     p.y_ld = d->nou; p.w_ld = d->nou * 4; p.x_ld = d->nin; p.accum = 0;
     p.x_sb = d->x_sb; p.et_sb = d->et_sb; p.y_sb = d->y_sb;
-    p.tables = (bw_pending_tables && bw_tables_count(d) > 0) ? (const int*)bw_pending_tables : nullptr;
-    const int off_b = KC == 6 ? BwLayout<6>::BYTES : BwLayout<3>::BYTES;
-    static_assert(BwLayout<6>::BYTES <= 160 * 1024 && BwLayout<3>::BYTES <= 160 * 1024, "LDS");
-    const bool nl48 = KC == 3 && d->N <= 48;                   // the LDPC F -> V call: 48 factor nodes
-    void* fn = ksplit ? (KC == 6 ? (void*)mpconv_bwd_ws_kernel<6, 3, 128> : nl48 ? (void*)mpconv_bwd_ws_kernel<3, 6, 128, 48> : (void*)mpconv_bwd_ws_kernel<3, 6, 128>)
-                      : (KC == 6 ? (void*)mpconv_bwd_ws_kernel<6, 3> : nl48 ? (void*)mpconv_bwd_ws_kernel<3, 6, 64, 48> : (void*)mpconv_bwd_ws_kernel<3, 6>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, off_b);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", off_b, hipGetErrorString(e));
-    int grid = 256;      // one workgroup per CU (caps of 248 / 240 / 224 to leave CUs to the other stream: no effect, profiles/r05/README.md)
-    if (grid > d->B) grid = d->B;
-    const int chunk = (d->B + grid - 1) / grid;
-    grid = (d->B + chunk - 1) / chunk;
-    hipStream_t st = (hipStream_t)stream;
+    p.tables = pl.aux ? (const int*)c.tables : nullptr;
+    hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
+    const int grid = pl.grid;
+    hipStream_t st = c.stream;
     fgnn_note_kernel(split ? "mpconv_bwd_ws_kernel<%d, %d> x2" : (ksplit ? "mpconv_bwd_ws_kernel<%d, %d> k2" : "mpconv_bwd_ws_kernel<%d, %d>"), KC, DEG);
-    p.prof = nullptr;
-#ifdef FGNN_ENABLE_PROF
-    static long long* prof_buf = nullptr;
-    if (getenv("FGNN_PROF")) {
-        if (!prof_buf) (void)hipMalloc(&prof_buf, 256 * 8);
-        (void)hipMemset(prof_buf, 0, 256 * 8);
-        p.prof = prof_buf;
-    }
-#endif
+    p.prof = fgnn_prof_begin();
     void* args[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(BW_THREADS), args, off_b, st);
+    e = hipLaunchKernel(pl.fn, dim3(grid), dim3(pl.block), args, pl.lds, st);
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ws backward launch: %s", hipGetErrorString(e));
-#ifdef FGNN_ENABLE_PROF
-    if (p.prof) {      // slots: 0 sample start, 1/2 projection done / released, 3/4 detype, 5/6 dP, 7/8 dx | dW | staging
-        long long h[256];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, p.prof, sizeof(h), hipMemcpyDeviceToHost);
-        for (int w = 0; w < 8; ++w) {
-            fprintf(stderr, "[fgnn prof ws bwd] wave %d:", w);
-            for (int i = 0; i < 11; ++i) fprintf(stderr, " %6lld", h[w * 16 + i] - h[0]);
-            fprintf(stderr, "\n");
-        }
-        fprintf(stderr, "[fgnn prof ws bwd] kernel: early-dma %lld zero+idx %lld rank %lld gtab %lld consts %lld loop-end %lld end %lld; samples:", h[129] - h[128],
-                h[130] - h[128], h[134] - h[128], h[135] - h[128], h[131] - h[128], h[132] - h[128], h[133] - h[128]);
-        for (int i = 0; i < 20 && h[136 + i]; ++i) fprintf(stderr, " %lld", h[136 + i] - h[128]);
-        fprintf(stderr, "\n[fgnn prof ws bwd] setup (thread 0): W-proj frags %lld, dx frags %lld, prefetch issued %lld, zeroed %lld, barrier %lld\n",
-                h[128 + 40] - h[128], h[128 + 41] - h[128], h[128 + 42] - h[128], h[128 + 43] - h[128], h[128 + 44] - h[128]);
-    }
-#endif
+    // per-wave slots: 0 sample start, 1/2 projection done / released, 3/4 detype, 5/6 dP, 7/8 dx | dW | staging; from 128 on the
+    // kernel-wide stamps: 1 early-dma, 2 zero+idx, 6 rank, 7 gtab, 3 consts, 4 loop-end, 5 end, 8.. sample starts, 40..44 setup
+    fgnn_prof_print(p.prof, "ws bwd", 0, 8, 11, 16);
+    fgnn_prof_print(p.prof, "ws bwd kernel", 128, 1, 45, 0);
     if (ksplit) {
-        fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, gfilters, gbias, st);                  // rows 0..63 of gfilters, dbias
+        fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW, c.gbias, st);                    // rows 0..63 of gfilters, dbias
         p.ws += (int64_t)grid * slab_len;                                                         // (its own slabs: the first launch's fold may be a recorded one)
         p.x += 64; p.W += 64 * (int64_t)p.w_ld; p.gx += 64; p.accum = 2;                          // input channels 64..127: getype accumulates
-        e = hipLaunchKernel(fn, dim3(grid), dim3(BW_THREADS), args, off_b, st);
+        e = hipLaunchKernel(pl.fn, dim3(grid), dim3(pl.block), args, pl.lds, st);
         if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ws backward launch (upper input channels): %s", hipGetErrorString(e));
-        fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, gfilters + nw, nullptr, st);           // rows 64..127 (dbias was counted by the first launch)
-    } else if (!split) fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, gfilters, gbias, st);
+        fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW + nw, nullptr, st);               // rows 64..127 (dbias was counted by the first launch)
+    } else if (!split) fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW, c.gbias, st);
     else {
         // slab rows are 256 columns of gfilters' 512: lower half, then the second launch on the upper 64 output channels, which ADDS
         // to gx / getype (one more bf16 rounding of those two) and folds its dW / dbias into the upper column / channel blocks
-        fgnn_launch_slab_reduce_ld(p.ws, grid, slab_len, nw, 256, 512, gfilters, gbias, st);
+        fgnn_launch_slab_reduce_ld(p.ws, grid, slab_len, nw, 256, 512, c.gW, c.gbias, st);
         p.ws += (int64_t)grid * slab_len;
         p.W += 256; p.gz += 64; p.argmax += 64; p.accum = 3;
-        e = hipLaunchKernel(fn, dim3(grid), dim3(BW_THREADS), args, off_b, st);
+        e = hipLaunchKernel(pl.fn, dim3(grid), dim3(pl.block), args, pl.lds, st);
         if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ws backward launch (upper half): %s", hipGetErrorString(e));
-        fgnn_launch_slab_reduce_ld(p.ws, grid, slab_len, nw, 256, 512, gfilters + 256, gbias + 64, st);
+        fgnn_launch_slab_reduce_ld(p.ws, grid, slab_len, nw, 256, 512, c.gW + 256, c.gbias + 64, st);
     }
     e = hipGetLastError();
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward helper launch: %s", hipGetErrorString(e));
-    return 1;
+    return FGNN_OK;
 }

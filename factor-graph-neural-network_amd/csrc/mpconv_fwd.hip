@@ -22,6 +22,7 @@
 // HBM traffic per call = x + etype + nn_idx read once, y written once, filters from L2:
 // the algorithmic bytes of SURVEY §8d.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include "fgnn_gridfold.h"
 #include <stdlib.h>
 
@@ -305,23 +306,6 @@ static int plan_forward(const fgnn_mpconv_desc* d, FwdParams* p) {
     return off * 4;
 }
 
-int fgnn_mpconv_forward_resident(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
-                                 const void* etype, const float* filters, const float* bias,
-                                 const float* post_scale, const float* post_shift, void* y,
-                                 uint8_t* argmax, fgnn_stream_t stream);
-
-int fgnn_mpconv_forward_hyper(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                              const float* filters, const float* bias, const float* post_scale,
-                              const float* post_shift, void* y, uint8_t* argmax, fgnn_stream_t stream);
-int fgnn_mpconv_forward_b16(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
-                            const void* etype, const float* filters, const float* bias,
-                            const float* post_scale, const float* post_shift, void* y,
-                            uint8_t* argmax, fgnn_stream_t stream, float* stats, int* plan_grid);
-
-int fgnn_mpconv_forward_ext(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                            const float* filters, const float* bias, const float* post_scale, const float* post_shift,
-                            void* y, uint8_t* argmax, fgnn_stream_t stream);
-
 int fgnn_check_desc(const fgnn_mpconv_desc* d) {
     if (!d) FGNN_FAIL(FGNN_EINVAL, "null descriptor");
     if (d->B < 0 || d->nin < 1 || d->nou < 1 || d->net < 1 || d->N < 1 || d->M < 1 || d->k < 1)
@@ -360,50 +344,105 @@ extern "C" int64_t fgnn_mpconv_forward_lds_bytes(const fgnn_mpconv_desc* d) {
     return plan_forward(d, &p);
 }
 
-extern "C" int fgnn_mpconv_forward(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
-                                   const void* etype, const float* filters, const float* bias,
-                                   const float* post_scale, const float* post_shift, void* y,
-                                   uint8_t* argmax, fgnn_stream_t stream) {
+const FgnnSwitches& fgnn_switches() {
+    static const FgnnSwitches sw = [] {
+        FgnnSwitches s;
+        s.force_generic = getenv("FGNN_FORCE_GENERIC") != nullptr;
+        s.no_ws = getenv("FGNN_NO_WS") != nullptr;
+        s.no_sg = getenv("FGNN_NO_SG") != nullptr;
+        s.sg_nosplit = getenv("FGNN_SG_NOSPLIT") != nullptr;
+        s.no_bwd_b16 = getenv("FGNN_NO_BWD_B16") != nullptr;
+        s.no_fwd_hyper = getenv("FGNN_NO_FWD_HYPER") != nullptr;
+        s.no_fanin_id = getenv("FGNN_NO_FANIN_ID") != nullptr;
+        s.no_ext = getenv("FGNN_NO_EXT") != nullptr;
+        s.ext_bf16_split = getenv("FGNN_EXT_BF16_SPLIT") != nullptr;
+        return s;
+    }();
+    return sw;
+}
+
+// the generic kernel: any shape (no statistics epilogue)
+static int generic_plan(const FgnnFwdCall& c, const FgnnSwitches&, FgnnPlan* pl) {
+    if (c.stats_epilogue) return 0;
+    FwdParams p;
+    pl->lds = plan_forward(c.d, &p);
+    if (pl->lds < 0) return pl->lds;
+    pl->fn = c.d->dtype == FGNN_F32 ? pick_net<float>(c.d->net, c.d->agg) : pick_net<bf16_t>(c.d->net, c.d->agg);
+    pl->grid = c.d->B < 4096 ? c.d->B : 4096;
+    pl->block = FGNN_THREADS;
+    return 1;
+}
+
+static int generic_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    FwdParams p;
+    p.d = *d;
+    p.x = c.x; p.idx = c.idx; p.et = c.et; p.W = c.W; p.bias = c.bias;
+    p.pscale = c.pscale; p.pshift = c.pshift; p.y = c.y; p.argmax = c.argmax;
+    plan_forward(d, &p);
+    if (pl.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
+    }
+    fgnn_note_kernel("mpconv_fwd_kernel<%s, %d, %d>", d->dtype ? "bf16_t" : "float",
+                     (d->net == 1 || d->net == 4 || d->net == 16) ? d->net : 0, d->agg);
+    void* args[] = {(void*)&p};
+    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv forward launch: %s", hipGetErrorString(e));
+    return FGNN_OK;
+}
+
+// The forward's families, most specialised first; the first whose plan takes the call runs it.
+static const struct { FgnnFwdPlanFn plan; FgnnFwdLaunchFn launch; } kFwdFamilies[] = {
+    {fgnn_fwd_hyper_plan, fgnn_fwd_hyper_launch},     // bf16 hyper-edge calls: fan-in (identity list) / fan-in / fan-out
+    {fgnn_fwd_ws_plan, fgnn_fwd_ws_launch},           // bf16 LDPC parity calls: third generation
+    {fgnn_fwd_sg_plan, fgnn_fwd_sg_launch},           //   second generation
+    {fgnn_fwd_b16_plan, fgnn_fwd_b16_launch},         //   first generation (per-sample tables too)
+    {fgnn_fwd_ext_plan, fgnn_fwd_ext_launch},         // f32 synthetic-PGM calls
+    {fgnn_fwd_res_plan, fgnn_fwd_res_launch},         // f32 LDPC shapes: W resident in LDS
+    {generic_plan, generic_launch},
+};
+static const int kFwdGeneric = sizeof(kFwdFamilies) / sizeof(kFwdFamilies[0]) - 1;
+
+// 1 with *pl the first family that takes the call, 0 = none does (a statistics call without that epilogue), < 0 = error.
+// FGNN_FORCE_GENERIC leaves only the generic kernel to the calls without statistics.
+static int fwd_plan(const FgnnFwdCall& c, FgnnPlan* pl) {
+    const FgnnSwitches& sw = fgnn_switches();
+    for (int f = (sw.force_generic && !c.stats_epilogue) ? kFwdGeneric : 0; f <= kFwdGeneric; ++f) {
+        *pl = FgnnPlan{};
+        pl->family = f;
+        const int rc = kFwdFamilies[f].plan(c, sw, pl);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
+// plan, then launch the winner (the generic kernel takes every call without statistics)
+static int fwd_run(const FgnnFwdCall& c, FgnnPlan* pl) {
+    const int rc = fwd_plan(c, pl);
+    return rc == 1 ? kFwdFamilies[pl->family].launch(c, *pl) : rc;
+}
+
+static int fwd_check(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype, const float* filters,
+                     const float* post_scale, const float* post_shift, void* y) {
     int rc = fgnn_check_desc(d);
     if (rc) return rc;
     if (!x || !nn_idx || !etype || !filters || !y) FGNN_FAIL(FGNN_EINVAL, "null tensor pointer");
     if ((post_scale == nullptr) != (post_shift == nullptr))
         FGNN_FAIL(FGNN_EINVAL, "post_scale and post_shift must be given together");
-    if (d->B == 0) return FGNN_OK;
-    {   // LDPC shape family: W-stationary persistent kernel (mpconv_fwd_res.hip)
-        static const bool force_generic = getenv("FGNN_FORCE_GENERIC") != nullptr;
-        if (!force_generic) {
-            rc = fgnn_mpconv_forward_hyper(d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y, argmax,
-                                           stream);
-            if (rc != 0) return rc < 0 ? rc : FGNN_OK;
-            rc = fgnn_mpconv_forward_b16(d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y, argmax,
-                                         stream, nullptr, nullptr);
-            if (rc != 0) return rc < 0 ? rc : FGNN_OK;
-            rc = fgnn_mpconv_forward_ext(d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y, argmax, stream);
-            if (rc != 0) return rc < 0 ? rc : FGNN_OK;
-            rc = fgnn_mpconv_forward_resident(d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y,
-                                              argmax, stream);
-            if (rc != 0) return rc < 0 ? rc : FGNN_OK;
-        }
-    }
-    FwdParams p;
-    p.d = *d;
-    p.x = x; p.idx = nn_idx; p.et = etype; p.W = filters; p.bias = bias;
-    p.pscale = post_scale; p.pshift = post_shift; p.y = y; p.argmax = argmax;
-    const int lds = plan_forward(d, &p);
-    if (lds < 0) return lds;
-    void* fn = d->dtype == FGNN_F32 ? pick_net<float>(d->net, d->agg) : pick_net<bf16_t>(d->net, d->agg);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
-    fgnn_note_kernel("mpconv_fwd_kernel<%s, %d, %d>", d->dtype ? "bf16_t" : "float",
-                     (d->net == 1 || d->net == 4 || d->net == 16) ? d->net : 0, d->agg);
-    const int grid = d->B < 4096 ? d->B : 4096;
-    void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(FGNN_THREADS), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv forward launch: %s", hipGetErrorString(e));
     return FGNN_OK;
+}
+
+extern "C" int fgnn_mpconv_forward(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
+                                   const void* etype, const float* filters, const float* bias,
+                                   const float* post_scale, const float* post_shift, void* y,
+                                   uint8_t* argmax, fgnn_stream_t stream) {
+    int rc = fwd_check(d, x, nn_idx, etype, filters, post_scale, post_shift, y);
+    if (rc || d->B == 0) return rc;
+    FgnnFwdCall c = {d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y, argmax};
+    c.stream = (hipStream_t)stream;
+    FgnnPlan pl;
+    return fwd_run(c, &pl);
 }
 
 // Training form of fgnn_mpconv_forward whose epilogue also leaves the BatchNorm batch statistics of the stored output:
@@ -412,17 +451,12 @@ extern "C" int fgnn_mpconv_forward(const fgnn_mpconv_desc* d, const void* x, con
 // this descriptor's launch writes, or 0 when the shape has no statistics epilogue (use fgnn_mpconv_forward + fgnn_bn_stats).
 extern "C" int fgnn_mpconv_forward_stats_partials(const fgnn_mpconv_desc* d) {
     if (fgnn_check_desc(d) || d->B == 0) return 0;
-    if (d->net == 1 && (d->M == 1 || (d->N == 1 && d->k == 1))) return 0;       // the hyper-edge kernels take these
-    int grid = 0;
-    return fgnn_mpconv_forward_b16(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                   nullptr, nullptr, &grid) == 1 ? grid : 0;
+    FgnnFwdCall c = {d};
+    c.stats_epilogue = true;
+    FgnnPlan pl;
+    return fwd_plan(c, &pl) == 1 ? pl.grid : 0;
 }
 
-// The BatchNorm finalisation of the NEXT statistics launch on this thread: fgnn_mpconv_forward_stats sets it around its call of
-// the kernel families' host entry points (b16 -> sg -> ws), whichever launches picks it up (as the inference addends travel).
-static thread_local const fgnn_bn_final* stats_pending_fin = nullptr;
-static thread_local void* stats_pending_scratch = nullptr;
-void fgnn_stats_pending(const fgnn_bn_final** fin, void** scratch) { *fin = stats_pending_fin; *scratch = stats_pending_scratch; }
 // second launch of a 64 -> 128 call: the upper 64 channels of every per-channel vector (num_batches_tracked was counted by the first)
 void fgnn_stats_upper_half(FgnnFold* fold, fgnn_bn_final* fin) {
     if (!fold->tickets) return;
@@ -436,6 +470,7 @@ void fgnn_stats_upper_half(FgnnFold* fold, fgnn_bn_final* fin) {
 }
 int fgnn_bn_finalize_launch(const float* partials, int npartials, int C, const fgnn_bn_final* fin, hipStream_t st);
 
+// The call is planned once, with its pointers: the launch and the stand-alone finaliser's row count come from that one plan.
 extern "C" int fgnn_mpconv_forward_stats(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
                                          const void* etype, const float* filters, const float* bias, void* y,
                                          uint8_t* argmax, float* stats_partials, const fgnn_bn_final* fin, void* fold_scratch,
@@ -443,41 +478,39 @@ extern "C" int fgnn_mpconv_forward_stats(const fgnn_mpconv_desc* d, const void* 
     int rc = fgnn_check_desc(d);
     if (rc) return rc;
     if (!x || !nn_idx || !etype || !filters || !y || !stats_partials) FGNN_FAIL(FGNN_EINVAL, "null tensor pointer");
-    const int rows = fgnn_mpconv_forward_stats_partials(d);
-    if (rows == 0)
-        FGNN_FAIL(FGNN_EUNSUPPORTED, "mpconv_forward_stats: this shape has no statistics epilogue");
+    const bool inkernel = fin && fold_scratch && !fgnn_separate_finalisers();
+    FgnnFwdCall c = {d, x, nn_idx, etype, filters, bias, nullptr, nullptr, y, argmax, true, stats_partials,
+                     inkernel ? fin : nullptr, inkernel ? fold_scratch : nullptr};
+    c.stream = (hipStream_t)stream;
+    FgnnPlan pl;
+    rc = d->B == 0 ? 0 : fwd_plan(c, &pl);
+    if (rc < 0) return rc;
+    if (rc == 0) FGNN_FAIL(FGNN_EUNSUPPORTED, "mpconv_forward_stats: this shape has no statistics epilogue");
     if (fin && (!fin->mean || !fin->invstd || !fin->scale || !fin->shift || fin->shift_k || fin->count != (int64_t)d->B * d->M))
         FGNN_FAIL(FGNN_EINVAL, "mpconv_forward_stats: fgnn_bn_final needs its outputs, count == B * M and no shift_k");
-    const bool inkernel = fin && fold_scratch && !fgnn_separate_finalisers();
-    stats_pending_fin = inkernel ? fin : nullptr;
-    stats_pending_scratch = inkernel ? fold_scratch : nullptr;
-    rc = fgnn_mpconv_forward_b16(d, x, nn_idx, etype, filters, bias, nullptr, nullptr, y, argmax, stream, stats_partials,
-                                 nullptr);
-    stats_pending_fin = nullptr;
-    stats_pending_scratch = nullptr;
-    if (rc == 0) FGNN_FAIL(FGNN_EUNSUPPORTED, "mpconv_forward_stats: this shape has no statistics epilogue");
-    if (rc != 1) return rc;
-    if (fin && !inkernel && fgnn_bn_finalize_launch(stats_partials, rows, d->nou, fin, (hipStream_t)stream))
+    rc = kFwdFamilies[pl.family].launch(c, pl);
+    if (rc) return rc;
+    if (fin && !inkernel && fgnn_bn_finalize_launch(stats_partials, pl.grid, d->nou, fin, c.stream))
         FGNN_FAIL(FGNN_ELAUNCH, "mpconv_forward_stats finaliser launch: %s", hipGetErrorString(hipGetLastError()));
     return FGNN_OK;
 }
-
 
 // fgnn_mpconv_forward with up to three ADDENDS of y's layout (the caller's running sum, residual, skip term: factor_mpnn_sp.py:139-168
 // adds them to the operator's activated output) folded into the kernel's epilogue where the kernel family supports it — the
 // third-generation bf16 parity kernel in its inference mode (post_scale / post_shift + ReLU).  Returns 1 when the addends were
 // added by the kernel, 0 when y was computed WITHOUT them (the caller adds them: one more pass), < 0 on error.
-void fgnn_ws_set_pending_addends(const void* a0, const void* a1, const void* a2);
-int fgnn_ws_pending_addends_taken(void);
 extern "C" int fgnn_mpconv_forward_addends(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
                                            const float* filters, const float* bias, const float* post_scale,
                                            const float* post_shift, const void* addend0, const void* addend1, const void* addend2,
                                            void* y, fgnn_stream_t stream) {
     if (!addend0 && (addend1 || addend2)) FGNN_FAIL(FGNN_EINVAL, "mpconv_forward_addends: addend0 first");
-    fgnn_ws_set_pending_addends(addend0, addend1, addend2);
-    const int rc = fgnn_mpconv_forward(d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y, nullptr, stream);
-    const int taken = fgnn_ws_pending_addends_taken();
-    fgnn_ws_set_pending_addends(nullptr, nullptr, nullptr);
-    if (rc != FGNN_OK) return rc;
-    return (addend0 && taken) ? 1 : 0;
+    int rc = fwd_check(d, x, nn_idx, etype, filters, post_scale, post_shift, y);
+    if (rc || d->B == 0) return rc;
+    FgnnFwdCall c = {d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y, nullptr};
+    c.add[0] = addend0; c.add[1] = addend1; c.add[2] = addend2;
+    c.stream = (hipStream_t)stream;
+    FgnnPlan pl;
+    rc = fwd_run(c, &pl);
+    if (rc) return rc;
+    return (addend0 && kFwdFamilies[pl.family].plan == fgnn_fwd_ws_plan && pl.aux) ? 1 : 0;
 }

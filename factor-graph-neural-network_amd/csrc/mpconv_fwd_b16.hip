@@ -15,6 +15,7 @@
 //     per (edge, channel), lanes = channels, destinations walk across the 4 waves;
 //   * next sample's x / etype / nn_idx are prefetched into registers during the current sample.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include "fgnn_gridfold.h"
 #ifndef B16_XPAD
 #define B16_XPAD 16
@@ -486,24 +487,12 @@ static void* b16_pick_agg(int agg, int k, int KSB, int SWP, int NPASS) {
     }
 }
 
-int fgnn_mpconv_forward_sg(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                           const float* filters, const float* bias, const float* post_scale, const float* post_shift,
-                           void* y, uint8_t* argmax, fgnn_stream_t stream, float* stats, int* plan_grid);
-
-// Returns 1 if launched, 0 if the shape is outside this kernel's family, <0 on error.
-// stats != NULL: also write per-workgroup BatchNorm partials (only one-pass shapes with <= 64 output channels: returns 0
-// otherwise).  plan_grid != NULL: no launch, *plan_grid = the grid (= number of partial rows) the launch would use.
-int fgnn_mpconv_forward_b16(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
-                            const void* etype, const float* filters, const float* bias,
-                            const float* post_scale, const float* post_shift, void* y,
-                            uint8_t* argmax, fgnn_stream_t stream, float* stats, int* plan_grid) {
+// The checks and geometry of one launch, pointers aside: the LDS bytes, or 0 when the shape is outside this kernel's family.
+// stats: with the statistics epilogue (one-pass shapes with <= 64 output channels only).
+static int b16_shape(const fgnn_mpconv_desc* d, bool stats, B16Params* p) {
     if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE) return 0;
     if (d->net != 1 && d->net != 4) return 0;
-    {   // batch-shared graph, fixed degree, max aggregation: the second-generation kernel (mpconv_fwd_sg.hip)
-        const int rc = fgnn_mpconv_forward_sg(d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y, argmax, stream,
-                                              stats, plan_grid);
-        if (rc != 0) return rc;
-    }
+    if (stats && d->net == 1 && (d->M == 1 || (d->N == 1 && d->k == 1))) return 0;     // the hyper-edge kernels take these
     const int ncols = d->nou * d->net;
     if (ncols % 16 != 0 || ncols > 512) return 0;
     if (d->nin != 64 && d->nin != 128) return 0;
@@ -514,93 +503,93 @@ int fgnn_mpconv_forward_b16(const fgnn_mpconv_desc* d, const void* x, const int6
     const int mk = d->M * d->k;
     if ((d->nin * d->N) / 8 > B16_THREADS * B16_XPT) return 0;
     if (mk * d->net > B16_THREADS * B16_EPT || mk > B16_THREADS * B16_IPT) return 0;
-    int et_mode;
     if (d->net == 1) {
         if (!((d->et_sk == 1 || d->k == 1) && (d->et_sm == d->k || d->M == 1))) return 0;
-        et_mode = 1;
+        p->et_mode = 1;
     } else if (mk == 1) {
         if (d->et_se != 1) return 0;
-        et_mode = 1;
+        p->et_mode = 1;
     } else if ((d->et_sk == 1 || d->k == 1) && (d->et_sm == d->k || d->M == 1) && d->et_se == mk) {
-        et_mode = 0;
+        p->et_mode = 0;
     } else if (d->et_se == 1 && d->et_sk == d->net && (d->et_sm == d->k * d->net || d->M == 1)) {
-        et_mode = 1;
+        p->et_mode = 1;
     } else {
         return 0;
     }
-    B16Params p = {};
-    p.d = *d;
-    p.x = x; p.idx = nn_idx; p.et = etype; p.W = filters; p.bias = bias;
-    p.pscale = post_scale; p.pshift = post_shift; p.y = y; p.argmax = argmax; p.stats = stats;
-    p.Npad = Npad;
+    p->d = *d;
+    p->Npad = Npad;
     const int NPASS = (ncols + B16_PASS_COLS - 1) / B16_PASS_COLS;
-    p.pass_cols = NPASS == 1 ? ncols : B16_PASS_COLS;
+    p->pass_cols = NPASS == 1 ? ncols : B16_PASS_COLS;
     if (NPASS > 1 && ncols % B16_PASS_COLS != 0) return 0;
-    if ((stats || plan_grid) && (NPASS != 1 || d->nou > 64 || d->M * ((d->nou + 63) / 64) * 2 <= B16_WAVES)) return 0;
-    const int slabs_per_pass = p.pass_cols / 16;
-    const int SWP = (slabs_per_pass + B16_WAVES - 1) / B16_WAVES;
-    const int KSB = d->nin / 32;
-    p.XSB = d->nin * 2 + B16_XPAD;                       // + padding: rows land on distinct 16-byte bank groups
-    p.PSB = p.pass_cols * 2 + B16_PPAD;
-    p.c8shift = d->nin == 64 ? 3 : 4;
-    p.et_mode = et_mode;
-    { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
-    p.prof = nullptr;
-    static long long* prof_buf = nullptr;
-    if (getenv("FGNN_PROF")) {
-        if (!prof_buf) (void)hipMalloc(&prof_buf, 64 * 8);
-        (void)hipMemset(prof_buf, 0, 64 * 8);
-        p.prof = prof_buf;
-    }
-    p.mkmagic = mk == 1 ? 0u : (unsigned)((0x100000000ULL + mk - 1) / mk);
+    if (stats && (NPASS != 1 || d->nou > 64 || d->M * ((d->nou + 63) / 64) * 2 <= B16_WAVES)) return 0;
+    p->XSB = d->nin * 2 + B16_XPAD;                      // + padding: rows land on distinct 16-byte bank groups
+    p->PSB = p->pass_cols * 2 + B16_PPAD;
+    p->c8shift = d->nin == 64 ? 3 : 4;
+    p->mkmagic = mk == 1 ? 0u : (unsigned)((0x100000000ULL + mk - 1) / mk);
     int off = 0;
-    p.off_xs = off;  off += Npad * p.XSB;                off = fgnn_round_up(off, 16);
-    p.off_ps = off;  off += Npad * p.PSB;                off = fgnn_round_up(off, 16);
-    p.off_idx = off; off += fgnn_round_up(mk, 4) * 4;
-    p.off_et = off;  off += fgnn_round_up(mk * d->net * 2, 16);
+    p->off_xs = off;  off += Npad * p->XSB;              off = fgnn_round_up(off, 16);
+    p->off_ps = off;  off += Npad * p->PSB;              off = fgnn_round_up(off, 16);
+    p->off_idx = off; off += fgnn_round_up(mk, 4) * 4;
+    p->off_et = off;  off += fgnn_round_up(mk * d->net * 2, 16);
     // few high-degree destinations: split each neighbour list over JP waves
     {
-        const int otp = p.pass_cols / d->net;
+        const int otp = p->pass_cols / d->net;
         const int units = d->M * ((otp < d->nou ? otp : d->nou) + 63) / 64;
-        p.JP = 1;
-        if (d->k >= 16 && units * 2 <= B16_WAVES) p.JP = B16_WAVES / units;
-        p.off_red = off;
-        if (p.JP > 1) off += units * p.JP * 64 * 3 * 4;
+        p->JP = 1;
+        if (d->k >= 16 && units * 2 <= B16_WAVES) p->JP = B16_WAVES / units;
+        p->off_red = off;
+        if (p->JP > 1) off += units * p->JP * 64 * 3 * 4;
     }
-    const int lds = off;
-    if (lds > 160 * 1024) return 0;
-    void* fn = d->net == 1 ? b16_pick_agg<1>(d->agg, d->k, KSB, SWP, NPASS)
-                           : b16_pick_agg<4>(d->agg, d->k, KSB, SWP, NPASS);
-    if (!fn) return 0;
-    int wg_per_cu = (160 * 1024) / lds;
+    return off <= 160 * 1024 ? off : 0;
+}
+
+// template arguments of the kernel b16_shape laid out: KSB, SWP, NPASS
+static void b16_widths(const fgnn_mpconv_desc* d, const B16Params& p, int* KSB, int* SWP, int* NPASS) {
+    *KSB = d->nin / 32;
+    *SWP = (p.pass_cols / 16 + B16_WAVES - 1) / B16_WAVES;
+    *NPASS = (d->nou * d->net + B16_PASS_COLS - 1) / B16_PASS_COLS;
+}
+
+int fgnn_fwd_b16_plan(const FgnnFwdCall& c, const FgnnSwitches&, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    B16Params p = {};
+    pl->lds = b16_shape(d, c.stats_epilogue, &p);
+    if (!pl->lds) return 0;
+    int KSB, SWP, NPASS;
+    b16_widths(d, p, &KSB, &SWP, &NPASS);
+    pl->fn = d->net == 1 ? b16_pick_agg<1>(d->agg, d->k, KSB, SWP, NPASS) : b16_pick_agg<4>(d->agg, d->k, KSB, SWP, NPASS);
+    if (!pl->fn) return 0;
+    int wg_per_cu = (160 * 1024) / pl->lds;
     if (wg_per_cu > 4) wg_per_cu = 4;
     if (wg_per_cu < 1) wg_per_cu = 1;
-    int grid = 256 * wg_per_cu;
-    if (grid > d->B) grid = d->B;
-    if (plan_grid) { *plan_grid = grid; return 1; }
-    {   // the BatchNorm behind the operator, finalised by this launch (fgnn_mpconv_forward_stats set it for this call)
-        const fgnn_bn_final* fin = nullptr;
-        void* scratch = nullptr;
-        fgnn_stats_pending(&fin, &scratch);
-        p.fold = fgnn_fold_make(stats, (stats && fin) ? scratch : nullptr, grid, d->nou);
-        if (fin) p.fin = *fin;
+    pl->grid = 256 * wg_per_cu;
+    if (pl->grid > d->B) pl->grid = d->B;
+    pl->block = B16_THREADS;
+    return 1;
+}
+
+int fgnn_fwd_b16_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    B16Params p = {};
+    b16_shape(d, c.stats_epilogue, &p);
+    p.x = c.x; p.idx = c.idx; p.et = c.et; p.W = c.W; p.bias = c.bias;
+    p.pscale = c.pscale; p.pshift = c.pshift; p.y = c.y; p.argmax = c.argmax; p.stats = c.stats;
+    { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
+    // the BatchNorm behind the operator, finalised by this launch (fgnn_mpconv_forward_stats)
+    p.fold = fgnn_fold_make(c.stats, (c.stats && c.fin) ? c.fold_scratch : nullptr, pl.grid, d->nou);
+    if (c.fin) p.fin = *c.fin;
+    if (pl.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
+    int KSB, SWP, NPASS;
+    b16_widths(d, p, &KSB, &SWP, &NPASS);
     fgnn_note_kernel("mpconv_fwd_b16_kernel<%d, %d, %d, %d, %d, %d>", d->net, d->agg, KSB, SWP, NPASS,
                      (d->agg == FGNN_AGG_MAX && d->net == 4 && (d->k == 3 || d->k == 6)) ? d->k : 0);
+    p.prof = fgnn_prof_begin();
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(B16_THREADS), args, lds, (hipStream_t)stream);
+    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv bf16 forward launch: %s", hipGetErrorString(e));
-    if (p.prof) {                                     // tuning aid: phase timeline of one sample (shader clocks)
-        long long h[64];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, p.prof, sizeof(h), hipMemcpyDeviceToHost);
-        fprintf(stderr, "[fgnn prof fwd]");
-        for (int i = 0; i < 20; ++i) if (h[i]) fprintf(stderr, " %d:%lld", i, h[i] - h[0]);
-        fprintf(stderr, "\n");
-    }
-    return 1;
+    fgnn_prof_print(p.prof, "b16 fwd", 0, 1, 20, 0);             // phase timeline of one sample (shader clocks)
+    return FGNN_OK;
 }

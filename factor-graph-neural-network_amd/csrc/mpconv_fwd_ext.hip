@@ -18,6 +18,7 @@
 //   * gather: thread = (destination, channel of the pass); per neighbour 8 LDS reads of 16 B and 16 packed FMAs.
 // One 512-thread workgroup per CU (P 65 KB + edge types <= 40 KB + x 17 KB of LDS), up to 256 VGPRs per lane.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include <stdlib.h>
 
 #define FX_THREADS 512
@@ -586,80 +587,72 @@ __global__ __launch_bounds__(FX_THREADS, 2) void mpconv_fwd_extp_kernel(const Fx
     }
 }
 
-// Returns 1 if launched, 0 if the call is outside this kernel's family, < 0 on error.
-int fgnn_mpconv_forward_ext(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                            const float* filters, const float* bias, const float* post_scale, const float* post_shift,
-                            void* y, uint8_t* argmax, fgnn_stream_t stream) {
-    static const bool off = getenv("FGNN_NO_EXT") != nullptr;
-    if (off) return 0;
+// LDS offsets of one launch (piped: the batch-shared pipelined kernel; split: its three-term bf16 form); returns the bytes.
+static int fx_layout(const fgnn_mpconv_desc* d, bool piped, bool split, FxParams* p) {
+    int off_b = 0;
+    auto take = [&](int bytes) { const int o = off_b; off_b = fgnn_round_up(off_b + bytes, 16); return o; };
+    p->off_xs = take(split ? 2 * 3 * 64 * FQ_XS * 2 : (piped ? 2 : 1) * 64 * FX_XS * 4);
+    p->off_ps = take(piped ? 2 * 64 * FP_PROW * 4 : 64 * FX_PS * 4);
+    p->off_et = take(d->N * d->k * FX_NET * 4);
+    p->off_idx = take(d->N * d->k * 4);
+    p->off_par = take(3 * 64 * 4);
+    return off_b;
+}
+
+// f32 synthetic-PGM calls: 16 edge types, ORIG_WITH_DIFF / NEIGHBOR, 64 -> 64.  pl->mode: piped, pl->split: the bf16 split.
+int fgnn_fwd_ext_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    if (sw.no_ext || c.stats_epilogue) return 0;
     if (d->dtype != FGNN_F32 || (d->ext != FGNN_EXT_NEIGHBOR && d->ext != FGNN_EXT_DIFF)) return 0;
     if (d->net != FX_NET || d->nin != FX_NIN || d->nou != FX_NOU) return 0;
     if (d->N != d->M || d->N < 1 || d->N > 64 || d->k < 1 || d->k > 16 || d->N * d->k > FX_MAX_MK) return 0;
     // x / y: dense channel-fastest per-sample blocks, 16-byte aligned
-    if (!(d->x_sc == 1 && d->x_sn == FX_NIN && d->x_sb % 4 == 0) || ((uintptr_t)x & 15)) return 0;
+    if (!(d->x_sc == 1 && d->x_sn == FX_NIN && d->x_sb % 4 == 0) || ((uintptr_t)c.x & 15)) return 0;
     if (!(d->y_sc == 1 && d->y_sm == FX_NOU)) return 0;
-    FxParams p;
-    p.x = (const float*)x; p.idx = nn_idx; p.et = (const float*)etype; p.W = filters; p.bias = bias;
-    p.pscale = post_scale; p.pshift = post_shift; p.y = (float*)y; p.argmax = argmax;
-    p.B = d->B; p.N = d->N; p.k = d->k; p.ext = d->ext; p.agg = d->agg; p.relu = d->relu;
-    p.x_sb = d->x_sb; p.y_sb = d->y_sb; p.idx_sb = d->idx_sb; p.idx_sm = d->idx_sm; p.idx_sk = d->idx_sk;
-    p.et_sb = d->et_sb; p.et_se = d->et_se; p.et_sm = d->et_sm; p.et_sk = d->et_sk;
-    int off_b = 0;
-    auto take = [&](int bytes) { const int o = off_b; off_b = fgnn_round_up(off_b + bytes, 16); return o; };
     const bool piped = (d->idx_sb == 0 && d->et_sb == 0) || d->B == 1;
     // default: projections on the f32 matrix cores (bitwise an fmaf chain, the reference's f32 accuracy).  FGNN_EXT_BF16_SPLIT=1
     // opts in to the three-term bf16 split on the bf16 matrix cores (when its larger x images fit next to the edge types): faster,
     // but on an ill-conditioned stack its result drifts several times further from f64 than an f32 evaluation does
-    static const bool opt_split = getenv("FGNN_EXT_BF16_SPLIT") != nullptr;
-    const bool split = piped && opt_split && (2 * 3 * 64 * FQ_XS * 2 + 2 * 64 * FP_PROW * 4 + d->N * d->k * (FX_NET * 4 + 4) + 3 * 64 * 4 + 64 <= 160 * 1024);
-    p.off_xs = take(split ? 2 * 3 * 64 * FQ_XS * 2 : (piped ? 2 : 1) * 64 * FX_XS * 4);
-    p.off_ps = take(piped ? 2 * 64 * FP_PROW * 4 : 64 * FX_PS * 4);
-    p.off_et = take(d->N * d->k * FX_NET * 4);
-    p.off_idx = take(d->N * d->k * 4);
-    p.off_par = take(3 * 64 * 4);
-    const int lds = off_b;
-    if (lds > 160 * 1024) return 0;
-    void* fn = d->agg == FGNN_AGG_MAX ? (void*)mpconv_fwd_ext_kernel<FGNN_AGG_MAX>
-             : d->agg == FGNN_AGG_LSE ? (void*)mpconv_fwd_ext_kernel<FGNN_AGG_LSE> : (void*)mpconv_fwd_ext_kernel<FGNN_AGG_MEAN>;
+    const bool split = piped && sw.ext_bf16_split && (2 * 3 * 64 * FQ_XS * 2 + 2 * 64 * FP_PROW * 4 + d->N * d->k * (FX_NET * 4 + 4) + 3 * 64 * 4 + 64 <= 160 * 1024);
+    FxParams p;
+    pl->lds = fx_layout(d, piped, split, &p);
+    if (pl->lds > 160 * 1024) return 0;
+    pl->mode = piped; pl->split = split;
+    pl->fn = d->agg == FGNN_AGG_MAX ? (void*)mpconv_fwd_ext_kernel<FGNN_AGG_MAX>
+           : d->agg == FGNN_AGG_LSE ? (void*)mpconv_fwd_ext_kernel<FGNN_AGG_LSE> : (void*)mpconv_fwd_ext_kernel<FGNN_AGG_MEAN>;
     if (piped && split)
-        fn = d->agg == FGNN_AGG_MAX ? (void*)mpconv_fwd_extp_kernel<FGNN_AGG_MAX, true>
-           : d->agg == FGNN_AGG_LSE ? (void*)mpconv_fwd_extp_kernel<FGNN_AGG_LSE, true> : (void*)mpconv_fwd_extp_kernel<FGNN_AGG_MEAN, true>;
+        pl->fn = d->agg == FGNN_AGG_MAX ? (void*)mpconv_fwd_extp_kernel<FGNN_AGG_MAX, true>
+               : d->agg == FGNN_AGG_LSE ? (void*)mpconv_fwd_extp_kernel<FGNN_AGG_LSE, true> : (void*)mpconv_fwd_extp_kernel<FGNN_AGG_MEAN, true>;
     else if (piped)
-        fn = d->agg == FGNN_AGG_MAX ? (void*)mpconv_fwd_extp_kernel<FGNN_AGG_MAX, false>
-           : d->agg == FGNN_AGG_LSE ? (void*)mpconv_fwd_extp_kernel<FGNN_AGG_LSE, false> : (void*)mpconv_fwd_extp_kernel<FGNN_AGG_MEAN, false>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    int grid = 256;
-    if (grid > d->B) grid = d->B;
+        pl->fn = d->agg == FGNN_AGG_MAX ? (void*)mpconv_fwd_extp_kernel<FGNN_AGG_MAX, false>
+               : d->agg == FGNN_AGG_LSE ? (void*)mpconv_fwd_extp_kernel<FGNN_AGG_LSE, false> : (void*)mpconv_fwd_extp_kernel<FGNN_AGG_MEAN, false>;
+    int grid = d->B < 256 ? d->B : 256;
     const int chunk = (d->B + grid - 1) / grid;
-    grid = (d->B + chunk - 1) / chunk;
-    fgnn_note_kernel(piped ? (split ? "mpconv_fwd_extp_kernel<%d, true>" : "mpconv_fwd_extp_kernel<%d, false>") : "mpconv_fwd_ext_kernel<%d>", d->agg);
-    p.prof = nullptr;
+    pl->grid = (d->B + chunk - 1) / chunk;
+    pl->block = FX_THREADS;
+    return 1;
+}
+
+int fgnn_fwd_ext_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    FxParams p;
+    p.x = (const float*)c.x; p.idx = c.idx; p.et = (const float*)c.et; p.W = c.W; p.bias = c.bias;
+    p.pscale = c.pscale; p.pshift = c.pshift; p.y = (float*)c.y; p.argmax = c.argmax;
+    p.B = d->B; p.N = d->N; p.k = d->k; p.ext = d->ext; p.agg = d->agg; p.relu = d->relu;
+    p.x_sb = d->x_sb; p.y_sb = d->y_sb; p.idx_sb = d->idx_sb; p.idx_sm = d->idx_sm; p.idx_sk = d->idx_sk;
+    p.et_sb = d->et_sb; p.et_se = d->et_se; p.et_sm = d->et_sm; p.et_sk = d->et_sk;
+    fx_layout(d, pl.mode, pl.split, &p);
+    hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
+    fgnn_note_kernel(pl.mode ? (pl.split ? "mpconv_fwd_extp_kernel<%d, true>" : "mpconv_fwd_extp_kernel<%d, false>") : "mpconv_fwd_ext_kernel<%d>", d->agg);
+    p.prof = fgnn_prof_begin();
     p.dbg = 0;
 #ifdef FGNN_ENABLE_PROF
     if (getenv("FGNN_EXT_DBG")) p.dbg = atoi(getenv("FGNN_EXT_DBG"));
-    static long long* prof_buf = nullptr;
-    if (getenv("FGNN_PROF")) {
-        if (!prof_buf) (void)hipMalloc(&prof_buf, 128 * 8);
-        (void)hipMemset(prof_buf, 0, 128 * 8);
-        p.prof = prof_buf;
-    }
 #endif
     void* args[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(FX_THREADS), args, lds, (hipStream_t)stream);
+    e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ext forward launch: %s", hipGetErrorString(e));
-#ifdef FGNN_ENABLE_PROF
-    if (p.prof && piped) {                            // tuning aid: stages 8..11 of workgroup 0 (shader clocks): start, x written, end
-        long long h[128];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, p.prof, sizeof(h), hipMemcpyDeviceToHost);
-        for (int w = 0; w < 8; ++w) {
-            fprintf(stderr, "[fgnn prof ext fwd] wave %d:", w);
-            for (int t = 0; t < 4; ++t)
-                fprintf(stderr, "  | %lld %lld %lld", h[(w * 4 + t) * 4] - h[0], h[(w * 4 + t) * 4 + 2] - h[0], h[(w * 4 + t) * 4 + 1] - h[0]);
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
-    return 1;
+    if (pl.mode) fgnn_prof_print(p.prof, "ext fwd", 0, 8, 16, 16);     // stages 8..11 of workgroup 0, 4 stamps each (shader clocks)
+    return FGNN_OK;
 }

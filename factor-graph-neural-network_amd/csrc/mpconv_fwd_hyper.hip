@@ -15,6 +15,7 @@
 // fan-out: P is 64..128 numbers per sample (lane <-> 4..8 channels, W from LDS), the output rows are streamed
 // with 8..16-byte stores.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include <stdlib.h>
 
 typedef __bf16 fh_bf16x8 __attribute__((ext_vector_type(8)));
@@ -382,8 +383,6 @@ __global__ __launch_bounds__(512) void mpconv_fwd_fanout_kernel(const FhParams p
 // ----------------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------------
-#define FH_REJECT(code) do { if (getenv("FGNN_TRACE")) fprintf(stderr, "[fgnn] hyper-edge forward rejects shape: rule %d\n", code); return 0; } while (0)
-
 template <int AGG>
 static void* fh_pick_fanin(int KS2, int OT) {
 #define FH_CASE(ks, ot) if (KS2 == ks && OT == ot) return (void*)mpconv_fwd_fanin_kernel<AGG, ks, ot>;
@@ -392,70 +391,76 @@ static void* fh_pick_fanin(int KS2, int OT) {
     return nullptr;
 }
 
-// Returns 1 if launched, 0 if the call is not a bf16 hyper-edge call, <0 on error.
-int fgnn_mpconv_forward_hyper(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                              const float* filters, const float* bias, const float* post_scale,
-                              const float* post_shift, void* y, uint8_t* argmax, fgnn_stream_t stream) {
-    static const bool off = getenv("FGNN_NO_FWD_HYPER") != nullptr;
-    if (off) return 0;
-    if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->net != 1) FH_REJECT(1);
-    if ((d->nin != 64 && d->nin != 128) || (d->nou != 64 && d->nou != 128) || d->nin * d->nou > 64 * 128) FH_REJECT(2);
+enum { FH_FANIN = 0, FH_FANIN_ID = 1, FH_FANOUT = 2 };
+
+// bf16 hyper-edge calls: one destination of degree N (fan-in, with the identity-list variant) or one source (fan-out).
+int fgnn_fwd_hyper_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    if (sw.no_fwd_hyper || c.stats_epilogue) return 0;
+    if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->net != 1) FGNN_REJECT("hyper-edge forward", 1);
+    if ((d->nin != 64 && d->nin != 128) || (d->nou != 64 && d->nou != 128) || d->nin * d->nou > 64 * 128) FGNN_REJECT("hyper-edge forward", 2);
     const bool fanin = d->M == 1 && d->k >= 1 && d->k <= 255 && d->N >= 1 && d->N <= 128;
     const bool fanout = !fanin && d->N == 1 && d->k == 1;
-    if (!fanin && !fanout) FH_REJECT(3);
-    FhParams p;
-    p.d = *d;
-    p.x = (const uint16_t*)x; p.idx = nn_idx; p.et = (const uint16_t*)etype; p.W = filters; p.bias = bias;
-    p.pscale = post_scale; p.pshift = post_shift; p.y = (uint16_t*)y; p.argmax = argmax;
-    p.Npad16 = fgnn_round_up(d->N, 16);
-    void* fn = nullptr;
-    int lds = 0, waves = 8;
+    if (!fanin && !fanout) FGNN_REJECT("hyper-edge forward", 3);
+    int waves = 8;
     if (fanin) {
-        if (!(d->x_sc == 1 && d->x_sn == d->nin && d->x_sb % 8 == 0) || ((uintptr_t)x & 15)) FH_REJECT(4);
+        if (!(d->x_sc == 1 && d->x_sn == d->nin && d->x_sb % 8 == 0) || ((uintptr_t)c.x & 15)) FGNN_REJECT("hyper-edge forward", 4);
         const int KS2 = d->nin / 32, OT = d->nou / 16;
-        static const bool no_id = getenv("FGNN_NO_FANIN_ID") != nullptr;
         // the caller vouches for an identity neighbour list (FGNN_DESC_IDENTITY_LIST): the reduction stays in the MFMA accumulators
-        if (!no_id && (d->reserved & FGNN_DESC_IDENTITY_LIST) && d->agg == FGNN_AGG_MAX && d->k == d->N && d->N <= 128 && d->N >= 2) {
+        if (!sw.no_fanin_id && (d->reserved & FGNN_DESC_IDENTITY_LIST) && d->agg == FGNN_AGG_MAX && d->k == d->N && d->N <= 128 && d->N >= 2) {
             void* idfn = nullptr;
-#define FI_CASE(ks, ot) if (KS2 == ks && OT == ot) idfn = argmax ? (void*)mpconv_fwd_fanin_id_kernel<ks, ot, true> : (void*)mpconv_fwd_fanin_id_kernel<ks, ot, false>;
+#define FI_CASE(ks, ot) if (KS2 == ks && OT == ot) idfn = c.argmax ? (void*)mpconv_fwd_fanin_id_kernel<ks, ot, true> : (void*)mpconv_fwd_fanin_id_kernel<ks, ot, false>;
             FI_CASE(2, 4) FI_CASE(2, 8) FI_CASE(4, 4)
 #undef FI_CASE
             if (idfn) {
-                int g = (d->B + 3) / 4;
-                if (g > 1024) g = 1024;
-                const int idlds = 4 * 16 * (d->nou + FI_ROWPAD) * 4 + 4 * 16 * d->nou;
-                fgnn_note_kernel("mpconv_fwd_fanin_id_kernel<%d, %d>", KS2, OT);
-                void* args[] = {(void*)&p};
-                hipError_t e = hipLaunchKernel(idfn, dim3(g), dim3(256), args, idlds, (hipStream_t)stream);
-                if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv hyper-edge forward launch: %s", hipGetErrorString(e));
+                pl->mode = FH_FANIN_ID; pl->fn = idfn;
+                pl->grid = (d->B + 3) / 4 < 1024 ? (d->B + 3) / 4 : 1024;
+                pl->block = 256;
+                pl->lds = 4 * 16 * (d->nou + FI_ROWPAD) * 4 + 4 * 16 * d->nou;
                 return 1;
             }
         }
-        fn = d->agg == FGNN_AGG_MAX ? fh_pick_fanin<FGNN_AGG_MAX>(KS2, OT)
-           : d->agg == FGNN_AGG_LSE ? fh_pick_fanin<FGNN_AGG_LSE>(KS2, OT) : fh_pick_fanin<FGNN_AGG_MEAN>(KS2, OT);
-        const int per_wave = p.Npad16 * d->nou * 2;
+        pl->mode = FH_FANIN;
+        pl->fn = d->agg == FGNN_AGG_MAX ? fh_pick_fanin<FGNN_AGG_MAX>(KS2, OT)
+               : d->agg == FGNN_AGG_LSE ? fh_pick_fanin<FGNN_AGG_LSE>(KS2, OT) : fh_pick_fanin<FGNN_AGG_MEAN>(KS2, OT);
+        const int per_wave = fgnn_round_up(d->N, 16) * d->nou * 2;
         while (waves > 1 && waves * per_wave > 64 * 1024) waves /= 2;      // keep >= 2 workgroups per CU
-        lds = waves * per_wave;
+        pl->lds = waves * per_wave;
     } else {
-        if (!(d->y_sc == 1 && d->y_sm % 4 == 0 && d->y_sb % 4 == 0 && d->y_sm >= d->nou) || ((uintptr_t)y & 7) ||
-            (argmax && ((uintptr_t)argmax & 3))) FH_REJECT(5);
+        if (!(d->y_sc == 1 && d->y_sm % 4 == 0 && d->y_sb % 4 == 0 && d->y_sm >= d->nou) || ((uintptr_t)c.y & 7) ||
+            (c.argmax && ((uintptr_t)c.argmax & 3))) FGNN_REJECT("hyper-edge forward", 5);
         const int NI = d->nin / 64, CH = d->nou / 16;
-        fn = NI == 1 ? (CH == 4 ? (void*)mpconv_fwd_fanout_kernel<1, 4> : (void*)mpconv_fwd_fanout_kernel<1, 8>)
-                     : (CH == 4 ? (void*)mpconv_fwd_fanout_kernel<2, 4> : nullptr);
-        lds = d->nin * d->nou * 4;
+        pl->mode = FH_FANOUT;
+        pl->fn = NI == 1 ? (CH == 4 ? (void*)mpconv_fwd_fanout_kernel<1, 4> : (void*)mpconv_fwd_fanout_kernel<1, 8>)
+                         : (CH == 4 ? (void*)mpconv_fwd_fanout_kernel<2, 4> : nullptr);
+        pl->lds = d->nin * d->nou * 4;
     }
-    if (!fn) FH_REJECT(6);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
-    p.waves = waves;
-    int grid = (d->B + waves - 1) / waves;
-    if (grid > 1024) grid = 1024;
-    if (fanin) fgnn_note_kernel("mpconv_fwd_fanin_kernel<%d, %d, %d>", d->agg, d->nin / 32, d->nou / 16);
-    else fgnn_note_kernel("mpconv_fwd_fanout_kernel<%d, %d>", d->nin / 64, d->nou / 16);
-    void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(64 * waves), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv hyper-edge forward launch: %s", hipGetErrorString(e));
+    if (!pl->fn) FGNN_REJECT("hyper-edge forward", 6);
+    pl->aux = waves;
+    pl->grid = (d->B + waves - 1) / waves < 1024 ? (d->B + waves - 1) / waves : 1024;
+    pl->block = 64 * waves;
     return 1;
+}
+
+int fgnn_fwd_hyper_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    FhParams p;
+    p.d = *d;
+    p.x = (const uint16_t*)c.x; p.idx = c.idx; p.et = (const uint16_t*)c.et; p.W = c.W; p.bias = c.bias;
+    p.pscale = c.pscale; p.pshift = c.pshift; p.y = (uint16_t*)c.y; p.argmax = c.argmax;
+    p.Npad16 = fgnn_round_up(d->N, 16);
+    if (pl.mode == FH_FANIN_ID) fgnn_note_kernel("mpconv_fwd_fanin_id_kernel<%d, %d>", d->nin / 32, d->nou / 16);
+    else {
+        if (pl.lds > 48 * 1024) {
+            hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+            if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
+        }
+        p.waves = pl.aux;
+        if (pl.mode == FH_FANIN) fgnn_note_kernel("mpconv_fwd_fanin_kernel<%d, %d, %d>", d->agg, d->nin / 32, d->nou / 16);
+        else fgnn_note_kernel("mpconv_fwd_fanout_kernel<%d, %d>", d->nin / 64, d->nou / 16);
+    }
+    void* args[] = {(void*)&p};
+    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv hyper-edge forward launch: %s", hipGetErrorString(e));
+    return FGNN_OK;
 }

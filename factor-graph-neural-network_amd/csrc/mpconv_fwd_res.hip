@@ -15,6 +15,7 @@
 //     high-degree destinations (the degree-96 LDPC hyper-factor: M*nou < threads) splits the
 //     neighbour list over up to 8 waves and combines the partial max / log-sum-exp / sum in LDS.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include <stdlib.h>
 
 #define RES_THREADS 512
@@ -356,11 +357,8 @@ static void* res_pick(int net, int agg, int KS, int SWP, int NPASS) {
     return nullptr;
 }
 
-// Returns 1 if launched, 0 if the shape is outside this kernel's family, <0 on error.
-int fgnn_mpconv_forward_resident(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,
-                                 const void* etype, const float* filters, const float* bias,
-                                 const float* post_scale, const float* post_shift, void* y,
-                                 uint8_t* argmax, fgnn_stream_t stream) {
+// The checks and geometry of one launch, pointers aside: the LDS bytes, or 0 when the shape is outside this kernel's family.
+static int res_shape(const fgnn_mpconv_desc* d, ResParams* p) {
     if (d->ext != FGNN_EXT_NONE) return 0;
     if (d->net != 1 && d->net != 4) return 0;
     const int ncols = d->nou * d->net;
@@ -396,58 +394,78 @@ int fgnn_mpconv_forward_resident(const fgnn_mpconv_desc* d, const void* x, const
         return 0;
     }
 
-    ResParams p;
-    p.d = *d;
-    p.x = x; p.idx = nn_idx; p.et = etype; p.W = filters; p.bias = bias;
-    p.pscale = post_scale; p.pshift = post_shift; p.y = y; p.argmax = argmax;
-    p.Npad = Npad; p.Kpad = Kpad;
+    p->d = *d;
+    p->Npad = Npad; p->Kpad = Kpad;
     const int NPASS = (ncols + RES_PASS_COLS - 1) / RES_PASS_COLS;
-    p.pass_cols = NPASS == 1 ? ncols : RES_PASS_COLS;
+    p->pass_cols = NPASS == 1 ? ncols : RES_PASS_COLS;
     if (NPASS > 1 && ncols % RES_PASS_COLS != 0) return 0;
-    const int slabs_per_pass = p.pass_cols / 16;
-    const int SWP = (slabs_per_pass + RES_WAVES - 1) / RES_WAVES;
-    const int KS = Kpad / 4;
-    p.cl_in = cl_in; p.cl_out = cl_out; p.et_mode = et_mode;
-    { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
-    p.xdiv = cl_in ? d->nin : d->N;
-    p.xmagic = (unsigned)((0x100000000ULL + p.xdiv - 1) / p.xdiv);
-    p.mkmagic = (unsigned)((0x100000000ULL + mk - 1) / mk);
-    if (cl_in) { p.xs_sn = (Kpad + 29) / 32 * 32 + 2; p.xs_sk = 1; }            // xs[n][c], row == 2 (mod 32)
-    else { p.xs_sk = (Npad % 32 == 0) ? Npad + 16 : Npad; p.xs_sn = 1; }         // xs[c][n], row == 16 (mod 32)
-    p.PS = p.pass_cols + 4;
-    p.YS = d->M + 1;
-    const int otp = p.pass_cols / d->net;
+    p->cl_in = cl_in; p->cl_out = cl_out; p->et_mode = et_mode;
+    p->xdiv = cl_in ? d->nin : d->N;
+    p->xmagic = (unsigned)((0x100000000ULL + p->xdiv - 1) / p->xdiv);
+    p->mkmagic = (unsigned)((0x100000000ULL + mk - 1) / mk);
+    if (cl_in) { p->xs_sn = (Kpad + 29) / 32 * 32 + 2; p->xs_sk = 1; }            // xs[n][c], row == 2 (mod 32)
+    else { p->xs_sk = (Npad % 32 == 0) ? Npad + 16 : Npad; p->xs_sn = 1; }         // xs[c][n], row == 16 (mod 32)
+    p->PS = p->pass_cols + 4;
+    p->YS = d->M + 1;
+    const int otp = p->pass_cols / d->net;
     // neighbour-list split for few, high-degree destinations
     const int items = d->M * (otp < d->nou ? otp : d->nou);
-    p.items_pad = fgnn_round_up(items, 64);
-    p.JP = 1;
-    if (d->k >= 16 && p.items_pad * 2 <= RES_THREADS) {
-        p.JP = RES_THREADS / p.items_pad;
-        if (p.JP > RES_JP_MAX) p.JP = RES_JP_MAX;
+    p->items_pad = fgnn_round_up(items, 64);
+    p->JP = 1;
+    if (d->k >= 16 && p->items_pad * 2 <= RES_THREADS) {
+        p->JP = RES_THREADS / p->items_pad;
+        if (p->JP > RES_JP_MAX) p->JP = RES_JP_MAX;
     }
     int off = 0;
-    p.off_xs = off;  off += cl_in ? Npad * p.xs_sn : Kpad * p.xs_sk;  off = fgnn_round_up(off, 4);
-    p.off_ps = off;  off += Npad * p.PS;                                off = fgnn_round_up(off, 4);
-    p.off_idx = off; off += fgnn_round_up(mk, 4);
-    p.off_et = off;  off += fgnn_round_up(mk * d->net, 4);
-    p.off_ys = off;  off += cl_out ? 0 : fgnn_round_up(otp * p.YS, 4);
-    p.off_ya = off;  off += cl_out ? 0 : fgnn_round_up((otp * p.YS + 3) / 4, 4);
-    p.off_red = off; off += p.JP > 1 ? p.JP * p.items_pad * 2 : 0;
-    const int lds = off * 4;
-    if (lds > 160 * 1024) return 0;
-    void* fn = d->dtype == FGNN_F32 ? res_pick<float>(d->net, d->agg, KS, SWP, NPASS)
-                                    : res_pick<bf16_t>(d->net, d->agg, KS, SWP, NPASS);
-    if (!fn) return 0;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
+    p->off_xs = off;  off += cl_in ? Npad * p->xs_sn : Kpad * p->xs_sk;  off = fgnn_round_up(off, 4);
+    p->off_ps = off;  off += Npad * p->PS;                                off = fgnn_round_up(off, 4);
+    p->off_idx = off; off += fgnn_round_up(mk, 4);
+    p->off_et = off;  off += fgnn_round_up(mk * d->net, 4);
+    p->off_ys = off;  off += cl_out ? 0 : fgnn_round_up(otp * p->YS, 4);
+    p->off_ya = off;  off += cl_out ? 0 : fgnn_round_up((otp * p->YS + 3) / 4, 4);
+    p->off_red = off; off += p->JP > 1 ? p->JP * p->items_pad * 2 : 0;
+    return off * 4 <= 160 * 1024 ? off * 4 : 0;
+}
+
+// template arguments of the kernel res_shape laid out: KS, SWP, NPASS
+static void res_widths(const fgnn_mpconv_desc* d, const ResParams& p, int* KS, int* SWP, int* NPASS) {
+    *KS = p.Kpad / 4;
+    *SWP = (p.pass_cols / 16 + RES_WAVES - 1) / RES_WAVES;
+    *NPASS = (d->nou * d->net + RES_PASS_COLS - 1) / RES_PASS_COLS;
+}
+
+int fgnn_fwd_res_plan(const FgnnFwdCall& c, const FgnnSwitches&, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    if (c.stats_epilogue) return 0;
+    ResParams p;
+    pl->lds = res_shape(d, &p);
+    if (!pl->lds) return 0;
+    int KS, SWP, NPASS;
+    res_widths(d, p, &KS, &SWP, &NPASS);
+    pl->fn = d->dtype == FGNN_F32 ? res_pick<float>(d->net, d->agg, KS, SWP, NPASS) : res_pick<bf16_t>(d->net, d->agg, KS, SWP, NPASS);
+    if (!pl->fn) return 0;
+    pl->grid = 256 * (pl->lds <= 76 * 1024 ? 2 : 1);
+    if (pl->grid > d->B) pl->grid = d->B;
+    pl->block = RES_THREADS;
+    return 1;
+}
+
+int fgnn_fwd_res_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    ResParams p;
+    res_shape(d, &p);
+    p.x = c.x; p.idx = c.idx; p.et = c.et; p.W = c.W; p.bias = c.bias;
+    p.pscale = c.pscale; p.pshift = c.pshift; p.y = c.y; p.argmax = c.argmax;
+    { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
+    if (pl.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
     }
-    const int wg_per_cu = lds <= 76 * 1024 ? 2 : 1;
-    int grid = 256 * wg_per_cu;
-    if (grid > d->B) grid = d->B;
+    int KS, SWP, NPASS;
+    res_widths(d, p, &KS, &SWP, &NPASS);
     fgnn_note_kernel("mpconv_fwd_res_kernel<%s, %d, %d, %d, %d, %d>", d->dtype ? "bf16_t" : "float", d->net, d->agg, KS, SWP, NPASS);
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(RES_THREADS), args, lds, (hipStream_t)stream);
+    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv resident forward launch: %s", hipGetErrorString(e));
-    return 1;
+    return FGNN_OK;
 }

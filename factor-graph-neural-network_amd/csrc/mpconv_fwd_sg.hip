@@ -26,6 +26,7 @@
 // [w*DPW, (w+1)*DPW).  Per sample: x (prefetched into registers one sample ahead) -> LDS image; MFMA projection ->
 // P[N][64 ch][4 et] bf16 in LDS; barrier; gather with lane = channel; barrier.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include "fgnn_gridfold.h"
 #include <stdlib.h>
 
@@ -402,121 +403,91 @@ static void* sg_pick_mode(int mode) {
 template <int KC, int MAXD>
 static void* sg_pick_width(int nin, int nou, int mode) {
     if (nin == 64 && nou == 64) return sg_pick_mode<64, 64, KC, MAXD>(mode);
-    if (nin == 64 && nou == 128) return sg_pick_mode<64, 128, KC, MAXD>(mode);
     if (nin == 128 && nou == 64) return sg_pick_mode<128, 64, KC, MAXD>(mode);
     return nullptr;
 }
 
-int fgnn_mpconv_forward_ws(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                           const float* filters, const float* bias, const float* post_scale, const float* post_shift,
-                           void* y, uint8_t* argmax, fgnn_stream_t stream, float* stats, int* plan_grid, int mode, int split);
-void fgnn_stats_pending(const fgnn_bn_final** fin, void** scratch);
-void fgnn_stats_upper_half(FgnnFold* fold, fgnn_bn_final* fin);
-
-// Same contract as fgnn_mpconv_forward_b16 (mpconv_fwd_b16.hip): 1 = launched, 0 = shape outside this kernel's family,
-// < 0 = error; stats / plan_grid as there.
-int fgnn_mpconv_forward_sg(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                           const float* filters, const float* bias, const float* post_scale, const float* post_shift,
-                           void* y, uint8_t* argmax, fgnn_stream_t stream, float* stats, int* plan_grid) {
-    static const bool off = getenv("FGNN_NO_SG") != nullptr;
-    if (off) return 0;
+// The shared-graph layout (batch-shared graph, fixed degree, max aggregation) that this kernel and the third-generation one
+// (mpconv_fwd_ws.hip) both need; sets pl->mode (the epilogue) and pl->split.
+int fgnn_fwd_sg_layout(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
+    const fgnn_mpconv_desc* d = c.d;
+    if (sw.no_sg) return 0;
     if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->net != 4 || d->agg != FGNN_AGG_MAX) return 0;
     if (d->k != 3 && d->k != 6) return 0;
     // 64 -> 128 as ONE launch (two column passes: 32 more resident fragment registers) spills under the 128-VGPR budget of 2
-    // workgroups per CU and measured slower than the first-generation kernel (200 vs 150 us; FGNN_SG_WIDE=1 selects it).  The
-    // output channels are independent, so the call runs as TWO launches of the 64 -> 64 kernel over the halves of W's columns
-    // and of the 128-wide y / argmax / statistics rows (x and etype are read twice: +60 MB at 4 096 codewords).
-    static const bool wide = getenv("FGNN_SG_WIDE") != nullptr;
-    static const bool no_split = getenv("FGNN_SG_NOSPLIT") != nullptr;
-    const bool split = d->nin == 64 && d->nou == 128 && !wide && !no_split;
-    if (!((d->nin == 64 && (d->nou == 64 || d->nou == 128) && !(d->nou == 128 && no_split && !wide)) || (d->nin == 128 && d->nou == 64))) return 0;
+    // workgroups per CU and measured slower than the first-generation kernel (200 vs 150 us).  The output channels are
+    // independent, so the call runs as TWO launches of the 64 -> 64 kernel over the halves of W's columns and of the 128-wide
+    // y / argmax / statistics rows (x and etype are read twice: +60 MB at 4 096 codewords).
+    const bool split = d->nin == 64 && d->nou == 128 && !sw.sg_nosplit;
+    if (!((d->nin == 64 && (d->nou == 64 || split)) || (d->nin == 128 && d->nou == 64))) return 0;
     if (d->N < 1 || d->N > 96 || d->M < 1) return 0;
-    const int DPW = (d->M + SG_WAVES - 1) / SG_WAVES;
-    const int MAXD = d->k == 6 ? 6 : 12;
-    if (DPW > MAXD) return 0;
+    if ((d->M + SG_WAVES - 1) / SG_WAVES > (d->k == 6 ? 6 : 12)) return 0;
     // x: dense channel-fastest sample block, 16-byte aligned rows; y / argmax: channel-fastest, dense per sample
     if (!(d->x_sc == 1 && d->x_sn == d->nin) || (d->x_sb % 8) != 0) return 0;
     if (!(d->y_sc == 1 && (d->M == 1 || d->y_sm == d->nou))) return 0;
     // nn_idx: dense [M][k] per sample (or shared); etype: edge-type fastest [M][k][4], per sample, 4-byte aligned rows
     if (!(d->idx_sk == 1 && d->idx_sm == d->k)) return 0;
     if (!(d->et_se == 1 && d->et_sk == 4 && d->et_sm == 4 * d->k) || (d->et_sb % 2) != 0) return 0;
-    if (x && ((((uintptr_t)x) & 15) || (((uintptr_t)etype) & 3))) {
-        // The plan call (x == NULL) announced THIS kernel's grid, and the caller sized / will finalise that many statistics rows:
-        // falling through to the first-generation kernel (another grid) would leave rows unwritten or overrun them, silently.
-        if (stats) FGNN_FAIL(FGNN_EINVAL, "mpconv forward with statistics: x must be 16-byte and etype 4-byte aligned (the partial rows were planned for the shared-graph kernel)");
+    if (c.x && ((((uintptr_t)c.x) & 15) || (((uintptr_t)c.et) & 3))) {
+        // the pointerless plan (fgnn_mpconv_forward_stats_partials) announced a shared-graph grid, and the caller sized that many
+        // statistics rows: another family (another grid) would leave rows unwritten or overrun them, silently
+        if (c.stats_epilogue) FGNN_FAIL(FGNN_EINVAL, "mpconv forward with statistics: x must be 16-byte and etype 4-byte aligned (the partial rows were planned for the shared-graph kernel)");
         return 0;
     }
-    int mode;
-    if (stats || plan_grid) mode = SG_MODE_TRAIN_STATS;
-    else if (!post_scale && !d->relu) mode = SG_MODE_TRAIN;
-    else if (post_scale && d->relu && !argmax && bias) mode = SG_MODE_AFFINE_RELU;
-    else mode = SG_MODE_GENERIC;
+    if (c.stats_epilogue) pl->mode = SG_MODE_TRAIN_STATS;
+    else if (!c.pscale && !d->relu) pl->mode = SG_MODE_TRAIN;
+    else if (c.pscale && d->relu && !c.argmax && c.bias) pl->mode = SG_MODE_AFFINE_RELU;
+    else pl->mode = SG_MODE_GENERIC;
     if (d->idx_sb != 0 && d->B > 1) return 0;                     // per-sample graphs: first-generation kernel
-    const int knou = split ? 64 : d->nou;                         // output channels of one launch
-    if (knou == 64) {                                             // third generation first (mpconv_fwd_ws.hip); 0 = not its shape
-        const int r = fgnn_mpconv_forward_ws(d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y, argmax, stream, stats,
-                                             plan_grid, mode, split ? 1 : 0);
-        if (r != 0) return r;
-    }
-    void* fn = d->k == 6 ? sg_pick_width<6, 6>(d->nin, knou, mode) : sg_pick_width<3, 12>(d->nin, knou, mode);
-    if (!fn) return 0;
+    pl->split = split ? 1 : 0;
+    return 1;
+}
+
+int fgnn_fwd_sg_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
+    const int r = fgnn_fwd_sg_layout(c, sw, pl);
+    if (r <= 0) return r;
+    const fgnn_mpconv_desc* d = c.d;
+    pl->fn = d->k == 6 ? sg_pick_width<6, 6>(d->nin, 64, pl->mode) : sg_pick_width<3, 12>(d->nin, 64, pl->mode);
+    if (!pl->fn) return 0;
     const int Npad = fgnn_round_up(d->N, 32);
-    const int lds = Npad * (d->nin * 2 + 16) + Npad * SG_PSB + SG_WAVES * 2 * SG_ESLOT;
-    int grid = 256 * 2;
-    if (grid > d->B) grid = d->B;
-    if (plan_grid) { *plan_grid = grid; return 1; }
+    pl->lds = Npad * (d->nin * 2 + 16) + Npad * SG_PSB + SG_WAVES * 2 * SG_ESLOT;
+    pl->grid = d->B < 256 * 2 ? d->B : 256 * 2;
+    pl->block = SG_THREADS;
+    return 1;
+}
+
+int fgnn_fwd_sg_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
     SgParams p = {};
-    p.x = static_cast<const unsigned short*>(x); p.idx = nn_idx; p.et = static_cast<const unsigned short*>(etype);
-    p.W = filters; p.bias = bias; p.pscale = post_scale; p.pshift = post_shift;
-    p.y = static_cast<unsigned short*>(y); p.argmax = argmax; p.stats = stats;
-    p.B = d->B; p.N = d->N; p.M = d->M; p.Npad = Npad; p.DPW = DPW; p.relu = d->relu;
+    p.x = static_cast<const unsigned short*>(c.x); p.idx = c.idx; p.et = static_cast<const unsigned short*>(c.et);
+    p.W = c.W; p.bias = c.bias; p.pscale = c.pscale; p.pshift = c.pshift;
+    p.y = static_cast<unsigned short*>(c.y); p.argmax = c.argmax; p.stats = c.stats;
+    p.B = d->B; p.N = d->N; p.M = d->M; p.Npad = fgnn_round_up(d->N, 32); p.DPW = (d->M + SG_WAVES - 1) / SG_WAVES; p.relu = d->relu;
     p.x_sb = d->x_sb; p.et_sb = d->et_sb; p.y_sb = d->y_sb;
     p.y_ld = d->nou; p.w_ld = d->nou * 4; p.st_ld = d->nou;
-    {   // the BatchNorm behind the operator, finalised by this launch (fgnn_mpconv_forward_stats set it for this call)
-        const fgnn_bn_final* fin = nullptr;
-        void* scratch = nullptr;
-        fgnn_stats_pending(&fin, &scratch);
-        p.fold = fgnn_fold_make(stats, (stats && fin) ? scratch : nullptr, grid, knou, 2 * d->nou, d->nou);
-        if (fin) p.fin = *fin;
+    // the BatchNorm behind the operator, finalised by this launch (fgnn_mpconv_forward_stats)
+    p.fold = fgnn_fold_make(c.stats, (c.stats && c.fin) ? c.fold_scratch : nullptr, pl.grid, 64, 2 * d->nou, d->nou);
+    if (c.fin) p.fin = *c.fin;
+    if (pl.lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
-    fgnn_note_kernel(split ? "mpconv_fwd_sg_kernel<%d, %d, %d, %d, %d> x2" : "mpconv_fwd_sg_kernel<%d, %d, %d, %d, %d>", d->nin, knou, d->k, MAXD, mode);
-    p.prof = nullptr;
-#ifdef FGNN_ENABLE_PROF
-    static long long* prof_buf = nullptr;
-    if (getenv("FGNN_PROF")) {
-        if (!prof_buf) (void)hipMalloc(&prof_buf, 64 * 8);
-        (void)hipMemset(prof_buf, 0, 64 * 8);
-        p.prof = prof_buf;
-    }
-#endif
+    fgnn_note_kernel(pl.split ? "mpconv_fwd_sg_kernel<%d, %d, %d, %d, %d> x2" : "mpconv_fwd_sg_kernel<%d, %d, %d, %d, %d>", d->nin, 64, d->k,
+                     d->k == 6 ? 6 : 12, pl.mode);
+    p.prof = fgnn_prof_begin();
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(SG_THREADS), args, lds, (hipStream_t)stream);
+    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv sg forward launch: %s", hipGetErrorString(e));
-    if (split) {                                                  // the upper 64 output channels
+    fgnn_prof_print(p.prof, "sg fwd", 0, 8, 6, 8);              // per-wave phase timeline of one sample (shader clocks)
+    if (pl.split) {                                               // the upper 64 output channels
         p.W += 256; p.y += 64;
         if (p.bias) p.bias += 64;
         if (p.pscale) { p.pscale += 64; p.pshift += 64; }
         if (p.argmax) p.argmax += 64;
         if (p.stats) p.stats += 64;
         fgnn_stats_upper_half(&p.fold, &p.fin);
-        e = hipLaunchKernel(fn, dim3(grid), dim3(SG_THREADS), args, lds, (hipStream_t)stream);
+        e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
         if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv sg forward launch (upper half): %s", hipGetErrorString(e));
     }
-#ifdef FGNN_ENABLE_PROF
-    if (p.prof) {                                     // tuning aid: per-wave phase timeline of one sample (shader clocks)
-        long long h[64];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, p.prof, sizeof(h), hipMemcpyDeviceToHost);
-        for (int w = 0; w < 8; ++w) {
-            fprintf(stderr, "[fgnn prof sg fwd] wave %d:", w);
-            for (int i = 0; i < 6; ++i) fprintf(stderr, " %lld", h[w * 8 + i] - h[0]);
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
-    return 1;
+    return FGNN_OK;
 }

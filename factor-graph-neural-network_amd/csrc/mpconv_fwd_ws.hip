@@ -26,6 +26,7 @@
 //     32 nodes on 2 bank groups, so the DMA's per-lane SOURCE addresses apply the XOR swizzle (chunk ^ (node >> 1 & 7))
 //     instead and the readers undo it.
 #include "fgnn_common.h"
+#include "mpconv_dispatch.h"
 #include "fgnn_gridfold.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -528,95 +529,69 @@ static void* ws_pick_mode(int mode) {
     return nullptr;
 }
 
-// Same contract as fgnn_mpconv_forward_sg (mpconv_fwd_sg.hip), which calls this first: 1 = launched, 0 = shape outside this
-// kernel's family (the second-generation kernel takes it), < 0 = error.  grid_out: the number of statistics partial rows.
-// Addends of the NEXT inference-mode launch on this thread (fgnn_mpconv_forward_addends sets them around its call of the ordinary
-// entry point; `taken` tells it whether this kernel consumed them or the caller has to add them itself).
-static thread_local const void* ws_pending_add[3] = {nullptr, nullptr, nullptr};
-static thread_local int ws_pending_taken = 0;
-void fgnn_ws_set_pending_addends(const void* a0, const void* a1, const void* a2) {
-    ws_pending_add[0] = a0; ws_pending_add[1] = a1; ws_pending_add[2] = a2; ws_pending_taken = 0;
-}
-int fgnn_ws_pending_addends_taken(void) { return ws_pending_taken; }
-
-void fgnn_stats_pending(const fgnn_bn_final** fin, void** scratch);
-void fgnn_stats_upper_half(FgnnFold* fold, fgnn_bn_final* fin);
-
-int fgnn_mpconv_forward_ws(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx, const void* etype,
-                           const float* filters, const float* bias, const float* post_scale, const float* post_shift,
-                           void* y, uint8_t* argmax, fgnn_stream_t stream, float* stats, int* plan_grid, int mode, int split) {
-    static const bool off = getenv("FGNN_NO_WS") != nullptr;
-    if (off) return 0;
+// Asked before the second-generation kernel, behind the same shared-graph layout (fgnn_fwd_sg_layout: mode, split) with 64 output
+// channels per launch.  pl->aux = 1: the inference addends of the call go into this launch's epilogue.
+int fgnn_fwd_ws_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
+    const int r = fgnn_fwd_sg_layout(c, sw, pl);
+    if (r <= 0) return r;
+    const fgnn_mpconv_desc* d = c.d;
+    if (sw.no_ws) return 0;
+    if (d->nou != 64 && !pl->split) return 0;
     const int KC = d->k;
     if (d->N > WS_MAXN || d->M > (KC == 6 ? 48 : 96)) return 0;
     if ((d->M * KC) & 1) return 0;                                    // a sample's edge types: whole 16-byte DMA lanes
     if (d->M * KC * 8 > WS_ESZ || d->M * KC * 8 < 16) return 0;
     if ((d->et_sb % 8) != 0 || (d->y_sb % 4) != 0) return 0;
-    if (x && ((((uintptr_t)etype) & 15) || (((uintptr_t)y) & 7) || (argmax && (((uintptr_t)argmax) & 3)))) return 0;
+    if (c.x && ((((uintptr_t)c.et) & 15) || (((uintptr_t)c.y) & 7) || (c.argmax && (((uintptr_t)c.argmax) & 3)))) {
+        // (as in fgnn_fwd_sg_layout: the statistics rows were planned for this kernel's grid)
+        if (c.stats_epilogue) FGNN_FAIL(FGNN_EINVAL, "mpconv forward with statistics: etype must be 16-byte, y 8-byte and argmax 4-byte aligned (the partial rows were planned for the table-driven kernel)");
+        return 0;
+    }
     const int Npad = fgnn_round_up(d->N, 32);
     const int xbuf = d->nin == 64 ? 3 : 2;
-    const int lds = xbuf * WS_MAXN * d->nin * 2 + 2 * Npad * WS_PROW + (xbuf + 1) * WS_ESZ + 64;      // + the dataflow flags
-    if (lds > 160 * 1024) return 0;
-    void* fn = nullptr;
-    if (d->nin == 64) fn = KC == 6 ? ws_pick_mode<64, 6, 3>(mode) : ws_pick_mode<64, 3, 3>(mode);
+    pl->lds = xbuf * WS_MAXN * d->nin * 2 + 2 * Npad * WS_PROW + (xbuf + 1) * WS_ESZ + 64;      // + the dataflow flags
+    if (pl->lds > 160 * 1024) return 0;
+    pl->fn = nullptr;
+    if (d->nin == 64) pl->fn = KC == 6 ? ws_pick_mode<64, 6, 3>(pl->mode) : ws_pick_mode<64, 3, 3>(pl->mode);
     // (nin = 128: 64 resident A registers per producer; what spills under 128 VGPRs is the fragment-loading prologue only — none in the sample loops)
-    else if (d->nin == 128) fn = KC == 6 ? ws_pick_mode<128, 6, 2>(mode) : ws_pick_mode<128, 3, 2>(mode);
-    if (!fn) return 0;
-    int grid = 256;      // one workgroup per CU
-    if (grid > d->B) grid = d->B;
-    if (plan_grid) { *plan_grid = grid; return 1; }
+    else if (d->nin == 128) pl->fn = KC == 6 ? ws_pick_mode<128, 6, 2>(pl->mode) : ws_pick_mode<128, 3, 2>(pl->mode);
+    if (!pl->fn) return 0;
+    pl->grid = d->B < 256 ? d->B : 256;      // one workgroup per CU
+    pl->block = WS_THREADS;
+    pl->aux = 0;
+    if (pl->mode == WS_MODE_AFFINE_RELU && c.add[0]) {
+        bool ok = true;
+        for (int a = 0; a < 3; ++a) ok = ok && !(((uintptr_t)c.add[a]) & 7);
+        pl->aux = ok ? 1 : 0;
+    }
+    return 1;
+}
+
+int fgnn_fwd_ws_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
+    const fgnn_mpconv_desc* d = c.d;
     WsParams p = {};
-    p.x = static_cast<const unsigned short*>(x); p.idx = nn_idx; p.et = static_cast<const unsigned short*>(etype);
-    p.W = filters; p.bias = bias; p.pscale = post_scale; p.pshift = post_shift;
-    p.y = static_cast<unsigned short*>(y); p.argmax = argmax; p.stats = stats;
-    p.B = d->B; p.N = d->N; p.M = d->M; p.Npad = Npad; p.relu = d->relu;
+    p.x = static_cast<const unsigned short*>(c.x); p.idx = c.idx; p.et = static_cast<const unsigned short*>(c.et);
+    p.W = c.W; p.bias = c.bias; p.pscale = c.pscale; p.pshift = c.pshift;
+    p.y = static_cast<unsigned short*>(c.y); p.argmax = c.argmax; p.stats = c.stats;
+    p.B = d->B; p.N = d->N; p.M = d->M; p.Npad = fgnn_round_up(d->N, 32); p.relu = d->relu;
     p.x_sb = d->x_sb; p.et_sb = d->et_sb; p.y_sb = d->y_sb;
     p.y_ld = d->nou; p.w_ld = d->nou * 4; p.st_ld = d->nou;
-    {   // the BatchNorm behind the operator, finalised by this launch (fgnn_mpconv_forward_stats set it for this call)
-        const fgnn_bn_final* fin = nullptr;
-        void* scratch = nullptr;
-        fgnn_stats_pending(&fin, &scratch);
-        p.fold = fgnn_fold_make(stats, (stats && fin) ? scratch : nullptr, grid, 64, 2 * d->nou, d->nou);
-        if (fin) p.fin = *fin;
-    }
-    for (int a = 0; a < 3; ++a) p.add[a] = nullptr;
-    if (mode == WS_MODE_AFFINE_RELU && ws_pending_add[0]) {
-        bool ok = true;
-        for (int a = 0; a < 3; ++a) ok = ok && !(((uintptr_t)ws_pending_add[a]) & 7);
-        if (ok) {
-            for (int a = 0; a < 3; ++a) p.add[a] = static_cast<const unsigned short*>(ws_pending_add[a]);
-            ws_pending_taken = 1;
-        }
-    }
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    fgnn_note_kernel(split ? "mpconv_fwd_ws_kernel<%d, %d, %d, %d> x2" : "mpconv_fwd_ws_kernel<%d, %d, %d, %d>", d->nin, KC, mode, xbuf);
-    p.prof = nullptr;
-#ifdef FGNN_ENABLE_PROF
-    static long long* prof_buf = nullptr;
-    if (getenv("FGNN_PROF")) {
-        if (!prof_buf) (void)hipMalloc(&prof_buf, 128 * 8);
-        (void)hipMemset(prof_buf, 0, 128 * 8);
-        p.prof = prof_buf;
-    }
-#endif
+    // the BatchNorm behind the operator, finalised by this launch (fgnn_mpconv_forward_stats)
+    p.fold = fgnn_fold_make(c.stats, (c.stats && c.fin) ? c.fold_scratch : nullptr, pl.grid, 64, 2 * d->nou, d->nou);
+    if (c.fin) p.fin = *c.fin;
+    for (int a = 0; a < 3; ++a) p.add[a] = pl.aux ? static_cast<const unsigned short*>(c.add[a]) : nullptr;
+    hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
+    fgnn_note_kernel(pl.split ? "mpconv_fwd_ws_kernel<%d, %d, %d, %d> x2" : "mpconv_fwd_ws_kernel<%d, %d, %d, %d>", d->nin, d->k, pl.mode,
+                     d->nin == 64 ? 3 : 2);
+    p.prof = fgnn_prof_begin();
     void* args[] = {(void*)&p};
-    e = hipLaunchKernel(fn, dim3(grid), dim3(WS_THREADS), args, lds, (hipStream_t)stream);
+    e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ws forward launch: %s", hipGetErrorString(e));
-#ifdef FGNN_ENABLE_PROF
-    if (p.prof) {                                     // tuning aid: per-stage timeline of workgroup 0 (shader clocks)
-        long long h[128];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpy(h, p.prof, sizeof(h), hipMemcpyDeviceToHost);
-        for (int w = 0; w < 16; ++w) {                 // slots: 0 / 1 = sample 8 started / finished, 3 / 4 = sample 9, 6 / 7 = sample 10
-            fprintf(stderr, "[fgnn prof ws fwd] wave %2d:", w);
-            for (int i = 0; i < 8; ++i) fprintf(stderr, " %6lld", h[w * 8 + i] ? h[w * 8 + i] - h[0] : -1);
-            fprintf(stderr, "\n");
-        }
-        p.prof = nullptr;
-    }
-#endif
-    if (split) {                                                      // the upper 64 output channels of a 64 -> 128 call
+    // per-stage timeline of workgroup 0 (shader clocks); slots: 0 / 1 = sample 8 started / finished, 3 / 4 = sample 9, 6 / 7 = sample 10
+    fgnn_prof_print(p.prof, "ws fwd", 0, 16, 8, 8);
+    p.prof = nullptr;
+    if (pl.split) {                                                   // the upper 64 output channels of a 64 -> 128 call
         p.W += 256; p.y += 64;
         for (int a = 0; a < 3; ++a)
             if (p.add[a]) p.add[a] += 64;
@@ -625,8 +600,8 @@ int fgnn_mpconv_forward_ws(const fgnn_mpconv_desc* d, const void* x, const int64
         if (p.argmax) p.argmax += 64;
         if (p.stats) p.stats += 64;
         fgnn_stats_upper_half(&p.fold, &p.fin);
-        e = hipLaunchKernel(fn, dim3(grid), dim3(WS_THREADS), args, lds, (hipStream_t)stream);
+        e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
         if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ws forward launch (upper half): %s", hipGetErrorString(e));
     }
-    return 1;
+    return FGNN_OK;
 }

@@ -105,6 +105,31 @@ def test_descriptor_checks_without_a_gpu():
     assert L.fgnn_mpconv_forward_lds_bytes(ctypes.byref(d)) == -1
 
 
+def test_forward_planner_picks_the_statistics_grid_without_a_gpu():
+    """fgnn_mpconv_forward_stats_partials runs the forward's dispatch table without pointers: the number of statistics rows
+    is the grid of the family that takes the call.  bf16 LDPC-shaped calls, descriptors as the operator builds them."""
+    from fgnn_amd import _hip, ops
+    L = _hip.lib()
+    B = 4096
+
+    def rows(nin, nou, net, N, M, k, shared=True):
+        x = torch.zeros(B, N, nin, dtype=torch.bfloat16).permute(0, 2, 1).unsqueeze(-1)       # channel-fastest
+        idx = torch.zeros(1 if shared else B, M, k, dtype=torch.int64).expand(B, -1, -1)
+        idx = ops.shared_graph_view(idx if shared else idx.contiguous())
+        et = torch.zeros(B, M, k, net, dtype=torch.bfloat16).permute(0, 3, 1, 2)               # edge-type fastest
+        y = torch.zeros(B, M, nou, dtype=torch.bfloat16).permute(0, 2, 1).unsqueeze(-1)
+        d = _hip.make_desc(x, idx, et, nou, net, 0, _hip.AGG_MAX, False, y)
+        return L.fgnn_mpconv_forward_stats_partials(ctypes.byref(d))
+
+    assert rows(64, 64, 4, 96, 48, 6) == 256                 # V->F: the table-driven (ws) kernel, one workgroup per CU
+    assert rows(64, 64, 4, 48, 96, 3) == 256                 # F->V
+    assert rows(64, 128, 4, 96, 48, 6) == 256                # 64 -> 128: two ws launches
+    assert rows(128, 64, 4, 96, 48, 6) == 256
+    assert rows(64, 64, 4, 95, 47, 3) == 512                 # odd M * k: the shared-graph (sg) kernel
+    assert rows(64, 64, 4, 96, 48, 6, shared=False) == 512   # per-sample table: the first-generation bf16 kernel
+    assert rows(64, 64, 1, 48, 1, 48) == 0                   # hyper-factor fan-in: no statistics epilogue
+
+
 def test_side_entry_points_validate_their_arguments_without_a_gpu():
     """Size / pointer checks of the entry points either side of the operator run before any device work: unsupported
     shapes come back as FGNN_EUNSUPPORTED (-3), missing buffers as FGNN_EINVAL (-1), with a message."""
