@@ -697,10 +697,6 @@ static int bt_check(const char* who, const void* e, const float* s2, const float
     return FGNN_OK;
 }
 
-int fgnn_bn_finalize_launch(const float* partials, int npartials, int C, const fgnn_bn_final* fin, hipStream_t st);
-int fgnn_bn_bwd_final_raw_launch(const float* partials, int npartials, int C, const float* mean, const float* invstd, float* dsum,
-                                 float* gweight, float* gbias, hipStream_t st);
-
 extern "C" int fgnn_block_tail_stats(const void* e, const float* scale2, const float* shift2, float slope2, const float* W2,
                                      const float* b2, int64_t R, int Cout, float* partials, const fgnn_bn_final* fin,
                                      void* fold_scratch, fgnn_stream_t stream) {
@@ -1027,10 +1023,6 @@ __global__ __launch_bounds__(BT_THREADS, 3) void block_head_bwd_kernel(const BhP
       }
     }
 }
-
-int fgnn_bn_backward_sums_bf16(const void* x, const void* gy, int64_t R, int C, const float* mean, const float* invstd,
-                               const float* gamma, const float* beta, float slope, float* gweight, float* gbias,
-                               void* workspace, void* fold_scratch, hipStream_t st, const float** dsum_out);
 
 // BatchNorm1 + activation backward and conv1's input gradient (see above).  z1 / ga1 [R][64] bf16, W1 [64][Cin] f32 (Cin in
 // {64, 128, 256}), gz1 [R][64] and gx [R][Cin] bf16 out (gx NULL: only gz1 — the caller multiplies it by W1 together with the state's

@@ -61,3 +61,19 @@ static inline void fgnn_prof_print(const long long*, const char*, int, int, int,
 #endif
 
 static inline int fgnn_round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// ---- host helpers shared by the translation units (not C ABI) ---------------------------
+// mpconv_bwd_res.hip: fold nslab slabs (slab_len apart) of [nw weights + bias] floats into gW / gbias in a fixed order; _ld: the
+// slab's [nw / ncols][ncols] weight block lands in rows `ld` apart (a column block of a wider gW)
+void fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias, hipStream_t st);
+void fgnn_launch_slab_reduce_ld(const float* ws, int nslab, int64_t slab_len, int64_t nw, int ncols, int ld, float* gW,
+                                float* gbias, hipStream_t st);
+// fold_batch.hip: called instead of launching a slab fold: true = recorded (deferral is on), false = launch it yourself
+bool fgnn_fold_push(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gb, int kind, int a, int b, int c, int d);
+// bnact.hip: the stand-alone BatchNorm finalisers and the bf16 backward sums
+int fgnn_bn_finalize_launch(const float* partials, int npartials, int C, const fgnn_bn_final* fin, hipStream_t st);
+int fgnn_bn_bwd_final_raw_launch(const float* partials, int npartials, int C, const float* mean, const float* invstd, float* dsum,
+                                 float* gweight, float* gbias, hipStream_t st);
+int fgnn_bn_backward_sums_bf16(const void* x, const void* gy, int64_t R, int C, const float* mean, const float* invstd,
+                               const float* gamma, const float* beta, float slope, float* gweight, float* gbias,
+                               void* workspace, void* fold_scratch, hipStream_t st, const float** dsum_out);

@@ -60,9 +60,6 @@ int fgnn_separate_finalisers(void);
 // host-side plumbing shared by the translation units (not C ABI)
 void fgnn_stats_pending(const fgnn_bn_final** fin, void** scratch);          // mpconv_fwd.hip: the finalisation the NEXT operator-forward launch carries
 void fgnn_stats_upper_half(FgnnFold* fold, fgnn_bn_final* fin);               // second launch of a 64 -> 128 call
-int fgnn_bn_finalize_launch(const float* partials, int npartials, int C, const fgnn_bn_final* fin, hipStream_t st);     // bnact.hip (stand-alone finalisers)
-int fgnn_bn_bwd_final_raw_launch(const float* partials, int npartials, int C, const float* mean, const float* invstd, float* dsum,
-                                 float* gweight, float* gbias, hipStream_t st);
 
 #ifdef __HIPCC__
 // A partial-row element: written through to the memory side (agent scope), whichever XCD the writer runs on.

@@ -378,7 +378,6 @@ extern "C" int fgnn_linear_forward_partials(int64_t R, int Cin, int Cout) {
 // fgnn_linear_forward_partials(..) * 2 * Cout floats receiving per-workgroup (sum y, sum y^2) per channel —
 // feed it to fgnn_bn_finalize.  w_transposed: W is [Cin][Cout] in memory (y = x W; the grad-input product of a
 // map whose weight is [Cin][Cout] = [cout'][cin']).  Returns FGNN_EUNSUPPORTED for other shapes (callers fall back to a library GEMM).
-int fgnn_bn_finalize_launch(const float* partials, int npartials, int C, const fgnn_bn_final* fin, hipStream_t st);
 
 extern "C" int fgnn_linear_forward(const void* x, const float* W, const float* bias, void* y, int64_t R, int Cin,
                                    int Cout, float* stats_partials, const fgnn_bn_final* fin, void* fold_scratch,

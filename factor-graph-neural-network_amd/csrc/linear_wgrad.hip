@@ -9,8 +9,7 @@
 // (100 MB ~ 15 us).  Here the rows are split over ~1000 workgroups; each stages 32-row tiles of gy
 // and x in LDS (row-major, as in memory) and accumulates its partial gW with exact-f32 MFMA; partials go
 // to a workspace slab per workgroup and a second kernel sums them (no contended atomics).
-#include "fgnn_common.h"
-#include <stdlib.h>
+#include "linear_wgrad.h"
 
 #define WG_THREADS 256
 #define WG_WAVES 4
@@ -291,49 +290,88 @@ __global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(const float* _
     }
 }
 
-static int wgrad_plan(int R, int Cin, int Cout, WgradParams* p, int* gx, int* gy_) {
-    p->Cip = fgnn_round_up(Cin, 16);
-    // channel slice: <= 64 output tiles per workgroup (4 waves x WG_TMAX), power-of-two channels so that
-    // WG_THREADS % oc == 0 (per-thread bias column sums)
+// The general family: any width up to the register tiling, f32 or bf16.  Channel slice: <= 64 output tiles per workgroup (4 waves
+// x WG_TMAX), power-of-two channels so that WG_THREADS % oc == 0 (per-thread bias column sums).  16-byte rows whose chunks fit the
+// registers take the vectorised kernel (mode 1).
+static int wgrad_plan(const FgnnWgradCall& c, FgnnWgradPlan* pl) {
+    const int R = (int)c.R, Cin = c.Cin, Cout = c.cout[0], Cip = fgnn_round_up(Cin, 16);
     int oc = 1;
     while (oc < Cout && oc < 256) oc *= 2;
-    while (oc > 16 && (fgnn_round_up(oc, 16) / 16) * (p->Cip / 16) > WG_WAVES * WG_TMAX) oc /= 2;
-    if ((fgnn_round_up(oc, 16) / 16) * (p->Cip / 16) > WG_WAVES * WG_TMAX) return -1;
-    p->oc = oc;
-    p->Cop = fgnn_round_up(oc, 16);
-    p->XS = (p->Cip % 32 == 0) ? p->Cip + 16 : p->Cip;
-    p->GS = (p->Cop % 32 == 0) ? p->Cop + 16 : p->Cop;
-    *gy_ = (Cout + oc - 1) / oc;
-    int g = 512 / *gy_;
-    if (g < 1) g = 1;
-    int rows = (R + g - 1) / g;
-    rows = fgnn_round_up(rows < 64 ? 64 : rows, 64);      // multiple of both kernels' row tiles
-    p->rows_per_wg = rows;
-    *gx = (R + rows - 1) / rows;
-    return 0;
+    while (oc > 16 && (fgnn_round_up(oc, 16) / 16) * (Cip / 16) > WG_WAVES * WG_TMAX) oc /= 2;
+    if ((fgnn_round_up(oc, 16) / 16) * (Cip / 16) > WG_WAVES * WG_TMAX) FGNN_REJECT("wgrad general", 1);
+    const int Cop = fgnn_round_up(oc, 16);
+    pl->aux = oc;
+    pl->gy = (Cout + oc - 1) / oc;
+    const int g = pl->gy > 512 ? 1 : 512 / pl->gy;
+    const int rows = (R + g - 1) / g;
+    pl->rows = fgnn_round_up(rows < 64 ? 64 : rows, 64);      // multiple of both kernels' row tiles
+    pl->gx = (R + pl->rows - 1) / pl->rows;
+    pl->ws_bytes = (int64_t)pl->gx * pl->gy * ((int64_t)Cop * Cip + Cop) * 4;
+    const int epc = c.dtype == FGNN_F32 ? 4 : 8;
+    pl->mode = Cin % epc == 0 && Cout % epc == 0 && oc % epc == 0 && Cout % oc == 0 && (WV_ROWS * (Cin + oc) / epc) <= WG_THREADS * WV_MAXCH &&
+               ((uintptr_t)c.x % 16 == 0) && ((uintptr_t)c.gy[0] % 16 == 0);
+    return 1;
 }
 
-// bf16, channel counts in multiples of 64: the LDS-free kernel of linear_wgrad_b16.hip
-int64_t fgnn_linear_wgrad_b16_workspace_bytes(int64_t R, int Cin, int Cout);
-int fgnn_linear_wgrad_b16(const void* x, const void* gy, int64_t R, int Cin, int Cout, float* gW, float* gb,
-                          void* workspace, int64_t workspace_bytes, fgnn_stream_t stream);
-
-// f32, rows >= 2048, channel counts in multiples of 4: the output-blocked kernel of linear_wgrad_f32.hip
-int64_t fgnn_linear_wgrad_f32_workspace_bytes(int64_t R, int Cin, int Cout);
-int fgnn_linear_wgrad_f32(const void* x, const void* gy, int64_t R, int Cin, int Cout, float* gW, float* gb, void* workspace,
-                          int64_t workspace_bytes, fgnn_stream_t stream);
-
-extern "C" int64_t fgnn_linear_wgrad_workspace_bytes(int64_t R, int Cin, int Cout) {
+static int wgrad_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
+    const int Cin = c.Cin, Cout = c.cout[0], dtype = c.dtype, epc = dtype == FGNN_F32 ? 4 : 8;
     WgradParams p;
-    int gx, gy;
+    p.x = c.x; p.gy = c.gy[0]; p.ws = (float*)c.workspace; p.R = (int)c.R; p.Cin = Cin; p.Cout = Cout; p.dtype = dtype;
+    p.rows_per_wg = pl.rows; p.oc = pl.aux; p.nslab = pl.gx;           // one slab per workgroup: plain stores, no atomics
+    p.Cip = fgnn_round_up(Cin, 16);
+    p.Cop = fgnn_round_up(p.oc, 16);
+    p.XS = (p.Cip % 32 == 0) ? p.Cip + 16 : p.Cip;
+    p.GS = (p.Cop % 32 == 0) ? p.Cop + 16 : p.Cop;
+    const unsigned gpr = p.oc / epc > 0 ? p.oc / epc : 1, xpr = Cin / epc > 0 ? Cin / epc : 1;
+    p.gmagic = gpr == 1 ? 0u : (unsigned)((0x100000000ULL + gpr - 1) / gpr);
+    p.xmagic = xpr == 1 ? 0u : (unsigned)((0x100000000ULL + xpr - 1) / xpr);
+    p.omagic = p.oc == 1 ? 0u : (unsigned)((0x100000000ULL + p.oc - 1) / p.oc);
+    const int lds = (pl.mode ? WV_ROWS : WG_ROWS) * (p.XS + p.GS) * 4;
+    void* fn;
+    if (pl.mode) {
+        const int tm = ((p.Cop / 16) * (p.Cip / 16) + WG_WAVES - 1) / WG_WAVES;
+        const int nchunks = (WV_ROWS * (Cin + p.oc) / epc + WG_THREADS - 1) / WG_THREADS;
+#define WV_PICK(T) (tm <= 4 && nchunks <= 4 ? (void*)linear_wgrad_vec_kernel<T, 4, 4> : \
+                                              (void*)linear_wgrad_vec_kernel<T, 16, 10>)
+        fn = dtype == FGNN_F32 ? WV_PICK(float) : WV_PICK(bf16_t);
+#undef WV_PICK
+    } else {
+        fn = dtype == FGNN_F32 ? (void*)linear_wgrad_kernel<float> : (void*)linear_wgrad_kernel<bf16_t>;
+    }
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    }
+    void* args[] = {(void*)&p};
+    hipError_t e = hipLaunchKernel(fn, dim3(pl.gx, pl.gy), dim3(WG_THREADS), args, lds, c.stream);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad launch: %s", hipGetErrorString(e));
+    const int64_t slab_len = (int64_t)p.Cop * p.Cip + p.Cop;
+    hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((unsigned)((slab_len + 15) / 16), pl.gy), dim3(256), 0,
+                       c.stream, p.ws, pl.gx, Cin, Cout, p.Cip, p.Cop, p.oc, c.gW[0], c.gb[0]);
+    e = hipGetLastError();
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad reduce launch: %s", hipGetErrorString(e));
+    return FGNN_OK;
+}
+
+// The families, most specialised first, each for one storage type (-1: both); the first whose plan takes the call
+// runs it.  fgnn_linear_wgrad_multi asks the b16 family alone, in its merged form.
+static const struct { int dtype; FgnnWgradPlanFn plan; FgnnWgradLaunchFn launch; } kWgradFamilies[] = {
+    {FGNN_BF16, fgnn_wgrad_narrow_plan, fgnn_wgrad_narrow_launch},   // linear_wgrad_b16.hip: one operand <= 16 channels
+    {FGNN_BF16, fgnn_wgrad_b16_plan, fgnn_wgrad_b16_launch},         //   multiples of 64: register-direct or LDS-staged
+    {FGNN_F32, fgnn_wgrad_f32_plan, fgnn_wgrad_f32_launch},          // linear_wgrad_f32.hip: output-blocked
+    {-1, wgrad_plan, wgrad_launch},
+};
+
+// The largest workspace of the families that take the shape, whatever their storage type; -1 if none does.
+extern "C" int64_t fgnn_linear_wgrad_workspace_bytes(int64_t R, int Cin, int Cout) {
     if (R <= 0 || Cin <= 0 || Cout <= 0) return -1;
-    const bool general = wgrad_plan((int)R, Cin, Cout, &p, &gx, &gy) == 0;
-    if (!general && fgnn_linear_wgrad_f32_workspace_bytes(R, Cin, Cout) == 0) return -1;
-    const int64_t a = general ? (int64_t)gx * gy * ((int64_t)p.Cop * p.Cip + p.Cop) * 4 : 0;
-    const int64_t b = fgnn_linear_wgrad_b16_workspace_bytes(R, Cin, Cout);
-    const int64_t c = fgnn_linear_wgrad_f32_workspace_bytes(R, Cin, Cout);
-    const int64_t m = a > b ? a : b;
-    return m > c ? m : c;
+    const FgnnWgradCall c = {nullptr, R, Cin, FGNN_F32, 1, false, {}, {Cout}};
+    int64_t need = -1;
+    for (const auto& f : kWgradFamilies) {
+        FgnnWgradPlan pl = {};
+        if (f.plan(c, &pl) == 1 && pl.ws_bytes > need) need = pl.ws_bytes;
+    }
+    return need;
 }
 
 // gW [Cout][Cin] f32 and gb [Cout] f32 (or NULL) are ACCUMULATED into.  x [R][Cin], gy [R][Cout] dense
@@ -344,60 +382,56 @@ extern "C" int fgnn_linear_wgrad(const void* x, const void* gy, int64_t R, int C
     if (!x || !gy || !gW || !workspace) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: null pointer");
     if (R <= 0 || R > 0x7fffffff || Cin <= 0 || Cout <= 0) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: bad sizes");
     if (dtype != FGNN_F32 && dtype != FGNN_BF16) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: unknown dtype %d", dtype);
-    if (dtype == FGNN_BF16) {
-        const int rc = fgnn_linear_wgrad_b16(x, gy, R, Cin, Cout, gW, gb, workspace, workspace_bytes, stream);
-        if (rc != 0) return rc < 0 ? rc : FGNN_OK;
+    const FgnnWgradCall c = {x, R, Cin, dtype, 1, false, {gy}, {Cout}, {gW}, {gb}, workspace, workspace_bytes, (hipStream_t)stream};
+    for (const auto& f : kWgradFamilies) {
+        FgnnWgradPlan pl = {};
+        if ((f.dtype >= 0 && f.dtype != dtype) || f.plan(c, &pl) != 1) continue;
+        if (workspace_bytes < pl.ws_bytes) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: workspace %lld < %lld bytes",
+                                                     (long long)workspace_bytes, (long long)pl.ws_bytes);
+        return f.launch(c, pl);
     }
-    if (dtype == FGNN_F32) {
-        const int rc = fgnn_linear_wgrad_f32(x, gy, R, Cin, Cout, gW, gb, workspace, workspace_bytes, stream);
-        if (rc != 0) return rc < 0 ? rc : FGNN_OK;
+    FGNN_FAIL(FGNN_EUNSUPPORTED, "linear_wgrad: Cin=%d too wide for the register tiling", Cin);
+}
+
+// The merged form's call; nsrc outside 1..WB_MAXSRC leaves it without sources (no plan takes it).  gy == NULL: a query.
+static FgnnWgradCall multi_call(const void* x, int64_t R, int Cin, int nsrc, const void* const* gy, const int32_t* couts,
+                                float* const* gW, float* const* gb) {
+    FgnnWgradCall c = {x, R, Cin, FGNN_BF16, 0, true};
+    if (nsrc < 1 || nsrc > WB_MAXSRC) return c;
+    c.nsrc = nsrc;
+    for (int s = 0; s < nsrc; ++s) {
+        c.cout[s] = couts[s];
+        if (gy) c.gy[s] = gy[s], c.gW[s] = gW[s], c.gb[s] = gb ? gb[s] : nullptr;
     }
-    WgradParams p;
-    int gx, gyn;
-    if (wgrad_plan((int)R, Cin, Cout, &p, &gx, &gyn))
-        FGNN_FAIL(FGNN_EUNSUPPORTED, "linear_wgrad: Cin=%d too wide for the register tiling", Cin);
-    const int64_t need = (int64_t)gx * gyn * ((int64_t)p.Cop * p.Cip + p.Cop) * 4;
-    if (workspace_bytes < need) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: workspace %lld < %lld bytes",
-                                          (long long)workspace_bytes, (long long)need);
-    p.x = x; p.gy = gy; p.ws = (float*)workspace; p.R = (int)R; p.Cin = Cin; p.Cout = Cout; p.dtype = dtype;
-    const int epc = dtype == FGNN_F32 ? 4 : 8;
-    const bool vec = Cin % epc == 0 && Cout % epc == 0 && p.oc % epc == 0 && Cout % p.oc == 0 &&
-                     (WV_ROWS * (Cin + p.oc) / epc) <= WG_THREADS * WV_MAXCH &&
-                     ((uintptr_t)x % 16 == 0) && ((uintptr_t)gy % 16 == 0);
-    const int rows_tile = vec ? WV_ROWS : WG_ROWS;
-    {
-        const unsigned gpr = p.oc / epc > 0 ? p.oc / epc : 1, xpr = Cin / epc > 0 ? Cin / epc : 1;
-        p.gmagic = gpr == 1 ? 0u : (unsigned)((0x100000000ULL + gpr - 1) / gpr);
-        p.xmagic = xpr == 1 ? 0u : (unsigned)((0x100000000ULL + xpr - 1) / xpr);
-        p.omagic = p.oc == 1 ? 0u : (unsigned)((0x100000000ULL + p.oc - 1) / p.oc);
+    return c;
+}
+
+// The weight / bias gradients of nsrc <= 3 node-wise maps that read the SAME rows x [R][Cin] (the maps consuming one layer state:
+// conv1 of the blocks' heads, the state's own v2v / f2f map — /root/reference/lib/model/mpnn/factor_mpnn_sp.py:136-168) in ONE
+// pass: gW_s [couts[s]][Cin] += gy_s^T x, gb_s [couts[s]] += column sums of gy_s (gb_s may be NULL).  bf16, channel counts in
+// multiples of 64 up to 256, sum_s (couts[s] / 64) (Cin / 64) <= 16.  x is read once instead of nsrc times.
+extern "C" int64_t fgnn_linear_wgrad_multi_workspace_bytes(int64_t R, int32_t Cin, int32_t nsrc, const int32_t* couts) {
+    FgnnWgradPlan pl = {};
+    if (R <= 0 || R > 0x7fffffff || !couts || fgnn_wgrad_b16_plan(multi_call(nullptr, R, Cin, nsrc, nullptr, couts, nullptr, nullptr), &pl) != 1)
+        return -1;
+    return pl.ws_bytes;
+}
+
+extern "C" int fgnn_linear_wgrad_multi(const void* x, int64_t R, int32_t Cin, int32_t nsrc, const void* const* gy, const int32_t* couts,
+                                       float* const* gW, float* const* gb, void* workspace, int64_t workspace_bytes,
+                                       fgnn_stream_t stream) {
+    if (!x || !gy || !couts || !gW || !workspace) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: null pointer");
+    if (R <= 0 || R > 0x7fffffff) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: bad sizes");
+    FgnnWgradCall c = multi_call(x, R, Cin, nsrc, gy, couts, gW, gb);
+    FgnnWgradPlan pl = {};
+    if (fgnn_wgrad_b16_plan(c, &pl) != 1)
+        FGNN_FAIL(FGNN_EUNSUPPORTED, "linear_wgrad_multi: Cin=%d with %d sources is outside the kernel's family", Cin, nsrc);
+    for (int s = 0; s < nsrc; ++s) {
+        if (!gy[s] || !gW[s]) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: null pointer (source %d)", s);
+        if ((uintptr_t)gy[s] & 7) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: gy[%d] not 8-byte aligned", s);
     }
-    const int lds = rows_tile * (p.XS + p.GS) * 4;
-    void* fn;
-    const int ntiles = (p.Cop / 16) * (p.Cip / 16);
-    const int nchunks = (WV_ROWS * (Cin + p.oc) / epc + WG_THREADS - 1) / WG_THREADS;
-    int nslab_x = gx;
-    if (vec) {
-        const int tm = (ntiles + WG_WAVES - 1) / WG_WAVES;
-#define WV_PICK(T) (tm <= 4 && nchunks <= 4 ? (void*)linear_wgrad_vec_kernel<T, 4, 4> : \
-                                              (void*)linear_wgrad_vec_kernel<T, 16, 10>)
-        fn = dtype == FGNN_F32 ? WV_PICK(float) : WV_PICK(bf16_t);
-#undef WV_PICK
-        p.nslab = gx;                                  // one slab per workgroup: plain stores, no atomics
-    } else {
-        p.nslab = gx;
-        fn = dtype == FGNN_F32 ? (void*)linear_wgrad_kernel<float> : (void*)linear_wgrad_kernel<bf16_t>;
-    }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(gx, gyn), dim3(WG_THREADS), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad launch: %s", hipGetErrorString(e));
-    const int64_t slab_len = (int64_t)p.Cop * p.Cip + p.Cop;
-    hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((unsigned)((slab_len + 15) / 16), gyn), dim3(256), 0,
-                       (hipStream_t)stream, p.ws, nslab_x, Cin, Cout, p.Cip, p.Cop, p.oc, gW, gb);
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad reduce launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    if ((uintptr_t)x & 7) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: x not 8-byte aligned");
+    if (workspace_bytes < pl.ws_bytes) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: workspace too small");
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+    return fgnn_wgrad_b16_launch(c, pl);
 }

@@ -18,10 +18,7 @@
 // each fragment dword against (1, 1).  Partials: the row-waves of a slice fold through LDS as a binary tree
 // (fixed order), the workgroup writes its slab in REGISTER order (coalesced), and wgb_reduce_kernel sums the
 // slabs and undoes the permutation: deterministic, no atomics.
-#include "fgnn_common.h"
-#include <stdlib.h>
-
-bool fgnn_fold_push(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gb, int kind, int a, int b, int c, int d);   // fold_batch.hip
+#include "linear_wgrad.h"
 
 #define WB_THREADS 1024
 #define WB_WAVES 16
@@ -30,7 +27,6 @@ bool fgnn_fold_push(const float* ws, int nslab, int64_t slab_len, int64_t nw, fl
 typedef __bf16 wb_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 wb_bf16x2 __attribute__((ext_vector_type(2)));
 
-#define WB_MAXSRC 3
 struct WgbParams {
     const uint16_t* x;   // [R][Cin]  bf16
     const uint16_t* gy;  // [R][Cout] bf16 (source 0)
@@ -562,198 +558,141 @@ __global__ __launch_bounds__(1024) void wgn_reduce_kernel(const float* __restric
     }
 }
 
-static bool wn_plan(int64_t R, int Cin, int Cout, bool* narrow_x, int* gx) {
-    if (Cin <= 16 && Cout % 64 == 0 && Cout <= 256) *narrow_x = true;          // wide side: 64-channel groups, one launch each
-    else if (Cout <= 16 && Cin % 64 == 0 && Cin <= 256) *narrow_x = false;
-    else return false;
-    const int64_t nblk = (R + 31) / 32;
-    int64_t g = (nblk + 2 * WB_WAVES - 1) / (2 * WB_WAVES);
-    if (g > 256) g = 256;
-    if (g < 1) g = 1;
-    *gx = (int)g;
-    return true;
+
+// ---- host: the narrow and the b16 families of the dispatch (linear_wgrad.h) ----
+
+// workgroups: >= 2 32-row blocks per row-wave, at most one per CU (128: no effect, profiles/r05/README.md)
+static int wb_grid(int64_t R, int row_waves) {
+    const int64_t g = ((R + 31) / 32 + 2 * row_waves - 1) / (2 * row_waves);
+    return (int)(g > 256 ? 256 : g < 1 ? 1 : g);
 }
 
-static bool wb_plan(int64_t R, int Cin, int Cout, int* nso, int* S, int* RW, int* gx) {
-    if (Cin % 64 || Cout % 64) return false;
-    *nso = Cout / 64;
-    *S = *nso * (Cin / 64);
-    if (*S > 16 || (*S & (*S - 1))) return false;
-    *RW = 16 / *S;
-    const int wgs = 256;      // one workgroup per CU (128: no effect, profiles/r05/README.md)
-    const int64_t nblk = (R + 31) / 32;
-    int64_t g = (nblk + 2 * *RW - 1) / (2 * *RW);                      // >= 2 blocks per row-wave
-    if (g > wgs) g = wgs;
-    if (g < 1) g = 1;
-    *gx = (int)g;
-    return true;
+// one operand <= 16 channels against 64..256 in 64-channel groups (one launch each)
+int fgnn_wgrad_narrow_plan(const FgnnWgradCall& c, FgnnWgradPlan* pl) {
+    const int Cin = c.Cin, Cout = c.cout[0];
+    if (Cin <= 16 && Cout % 64 == 0 && Cout <= 256) pl->mode = 1;
+    else if (Cout <= 16 && Cin % 64 == 0 && Cin <= 256) pl->mode = 0;
+    else FGNN_REJECT("wgrad b16 narrow", 1);
+    const uintptr_t wide = (uintptr_t)(pl->mode ? c.gy[0] : c.x), narrow = (uintptr_t)(pl->mode ? c.x : c.gy[0]);
+    if (c.x && ((wide & 7) || (narrow & 1))) FGNN_REJECT("wgrad b16 narrow", 2);
+    pl->gx = wb_grid(c.R, WB_WAVES);
+    pl->ws_bytes = (int64_t)pl->gx * WN_NACC * 64 * 4;
+    return 1;
 }
 
-int64_t fgnn_linear_wgrad_b16_workspace_bytes(int64_t R, int Cin, int Cout) {
-    int nso, S, RW, gx;
-    bool nx;
-    if (wn_plan(R, Cin, Cout, &nx, &gx)) return (int64_t)gx * WN_NACC * 64 * 4;
-    if (!wb_plan(R, Cin, Cout, &nso, &S, &RW, &gx)) return 0;
-    return (int64_t)gx * S * WB_NACC * 64 * 4;
-}
-
-// nsrc gradient tensors against one x: live slices, S padded to a power of two <= 16, row-waves, grid
-static bool wb_plan_multi(int64_t R, int Cin, int nsrc, const int32_t* couts, int* sb, int* S, int* RW, int* gx) {
-    if (nsrc < 1 || nsrc > WB_MAXSRC || Cin % 64 || Cin < 64 || Cin > 256) return false;
-    int live = 0;
-    for (int s = 0; s < WB_MAXSRC; ++s) {
-        sb[s] = live;
-        if (s < nsrc) {
-            if (couts[s] % 64 || couts[s] < 64 || couts[s] > 256) return false;
-            live += (couts[s] / 64) * (Cin / 64);
+int fgnn_wgrad_narrow_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
+    WgbParams p = {};
+    p.x = (const uint16_t*)c.x; p.gy = (const uint16_t*)c.gy[0]; p.ws = (float*)c.workspace;
+    p.R = (int)c.R; p.Cin = c.Cin; p.Cout = c.cout[0]; p.nso = 1; p.S = 1; p.RW = WB_WAVES;
+    const int lds = (WB_WAVES / 2) * WN_NACC * 64 * 4;
+    for (int woff = 0; woff < (pl.mode ? p.Cout : p.Cin); woff += 64) {     // the kernel reads 64 channels from the pointer, rows at the full stride
+        if (pl.mode) {
+            p.gy = (const uint16_t*)c.gy[0] + woff;
+            hipLaunchKernelGGL(linear_wgrad_b16_narrow_kernel<true>, dim3(pl.gx), dim3(WB_THREADS), lds, c.stream, p);
+            hipLaunchKernelGGL(wgn_reduce_kernel<true>, dim3(WN_NACC), dim3(1024), 0, c.stream, p.ws, pl.gx, p.Cin, p.Cout, woff, c.gW[0], c.gb[0]);
+        } else {
+            p.x = (const uint16_t*)c.x + woff;
+            hipLaunchKernelGGL(linear_wgrad_b16_narrow_kernel<false>, dim3(pl.gx), dim3(WB_THREADS), lds, c.stream, p);
+            hipLaunchKernelGGL(wgn_reduce_kernel<false>, dim3(WN_NACC), dim3(1024), 0, c.stream, p.ws, pl.gx, p.Cin, p.Cout, woff, c.gW[0], c.gb[0]);
         }
     }
-    sb[WB_MAXSRC] = live;
-    if (live > 16) return false;
-    int sp = 1;
-    while (sp < live) sp *= 2;
-    *S = sp;
-    *RW = 16 / sp;
-    const int wgs = 256;      // one workgroup per CU (128: no effect, profiles/r05/README.md)
-    const int64_t nblk = (R + 31) / 32;
-    int64_t g = (nblk + 2 * *RW - 1) / (2 * *RW);                      // >= 2 blocks per row-wave
-    if (g > wgs) g = wgs;
-    if (g < 1) g = 1;
-    *gx = (int)g;
-    return true;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad_b16 narrow launch: %s", hipGetErrorString(e));
+    return FGNN_OK;
 }
 
-static int wb_launch(const void* x, int64_t R, int Cin, int nsrc, const void* const* gys, const int32_t* couts, float* const* gWs,
-                     float* const* gbs, const int* sb, int S, int RW, int gx, void* workspace, hipStream_t st) {
-    WgbParams p = {};
-    p.x = (const uint16_t*)x; p.gy = (const uint16_t*)gys[0]; p.ws = (float*)workspace;
-    p.R = (int)R; p.Cin = Cin; p.Cout = couts[0]; p.nso = couts[0] / 64; p.S = S; p.RW = RW;
+// The LDS-staged form's stages: 32 RW rows of x and of every gy, three or four stages deep.  True when they fit the kernel (whole
+// 1 KB DMA pieces, one to three per wave, <= 150 KB) and hold the row-waves' fold.
+static bool wl_stages(const FgnnWgradCall& c, int S, WglParams* q) {
+    const int RW = 16 / S;
+    int ctot = c.Cin;
+    for (int s = 0; s < c.nsrc; ++s) ctot += c.cout[s];
+    q->nsrc = c.nsrc;
+    q->rows_stage = 32 * RW;
+    q->stage_bytes = q->rows_stage * ctot * 2;
+    q->nst = q->stage_bytes <= 32 * 1024 ? 4 : 3;
+    q->off[0] = 0;
+    q->off[1] = q->rows_stage * c.Cin * 2;
+    for (int s = 1; s < WB_MAXSRC; ++s) q->off[s + 1] = q->off[s] + (s - 1 < c.nsrc ? q->rows_stage * c.cout[s - 1] * 2 : 0);
+    return q->stage_bytes % 1024 == 0 && q->stage_bytes >= 1024 * WB_WAVES && q->stage_bytes <= 3 * 1024 * WB_WAVES &&
+           q->nst * q->stage_bytes <= 150 * 1024 && q->nst * q->stage_bytes >= S * (RW / 2) * WB_NACC * 64 * 4;
+}
+
+// Channel counts in multiples of 64.  One map: S = (Cout / 64) (Cin / 64) slices, a power of two <= 16.  The merged form (multi):
+// Cin and every cout 64..256, at most 16 live slices, S padded to a power of two.  The wide maps (8 / 16 slices, >= 2048 rows,
+// 16-byte rows) take the LDS-staged form (mode 1), the rest the register-direct kernel.
+int fgnn_wgrad_b16_plan(const FgnnWgradCall& c, FgnnWgradPlan* pl) {
+    const bool m = c.multi;
+    if (c.nsrc < 1 || c.Cin % 64 || (m && (c.Cin < 64 || c.Cin > 256))) FGNN_REJECT("wgrad b16", 1);
+    int live = 0;
     for (int s = 0; s < WB_MAXSRC; ++s) {
-        p.gys[s] = (const uint16_t*)gys[s < nsrc ? s : 0];
-        p.couts[s] = couts[s < nsrc ? s : 0];
-        p.sb[s] = sb[s];
+        pl->sb[s] = live;
+        if (s >= c.nsrc) continue;
+        if (c.cout[s] % 64 || (m && (c.cout[s] < 64 || c.cout[s] > 256))) FGNN_REJECT("wgrad b16", 1);
+        live += (c.cout[s] / 64) * (c.Cin / 64);
     }
-    p.sb[WB_MAXSRC] = sb[WB_MAXSRC];
-    const int lds = S * (RW / 2) * WB_NACC * 64 * 4;                   // 0 when every slice has one row-wave
-    // wide maps (8 / 16 slices): rows staged ONCE per workgroup through LDS (linear_wgrad_lds_kernel)
-    WglParams q = {};
-    bool staged = false;
-    static const bool no_lds = getenv("FGNN_WG_NOLDS") != nullptr;      // A/B switch: the register-direct kernel for every shape
-    if (S >= 8 && !no_lds && R >= 2048) {
-        int ctot = Cin;
-        for (int s = 0; s < nsrc; ++s) ctot += couts[s];
-        q.b = p; q.nsrc = nsrc;
-        q.rows_stage = 32 * RW;
-        q.stage_bytes = q.rows_stage * ctot * 2;
-        q.nst = q.stage_bytes <= 32 * 1024 ? 4 : 3;
-        q.off[0] = 0;
-        q.off[1] = q.rows_stage * Cin * 2;
-        for (int s = 1; s <= WB_MAXSRC; ++s) if (s < WB_MAXSRC) q.off[s + 1] = q.off[s] + (s - 1 < nsrc ? q.rows_stage * couts[s - 1] * 2 : 0);
-        const bool aligned = ((uintptr_t)x & 15) == 0 && ((uintptr_t)gys[0] & 15) == 0 && (nsrc < 2 || ((uintptr_t)gys[1] & 15) == 0) &&
-                             (nsrc < 3 || ((uintptr_t)gys[2] & 15) == 0);
-        staged = aligned && q.stage_bytes % 1024 == 0 && q.stage_bytes >= 1024 * WB_WAVES && q.stage_bytes <= 3 * 1024 * WB_WAVES &&
-                 q.nst * q.stage_bytes <= 150 * 1024 && q.nst * q.stage_bytes >= lds;
+    pl->sb[WB_MAXSRC] = live;
+    if (live > 16 || (!m && (live & (live - 1)))) FGNN_REJECT("wgrad b16", 2);
+    int S = 1;
+    while (S < live) S *= 2;
+    pl->aux = S;
+    pl->gx = wb_grid(c.R, 16 / S);
+    pl->ws_bytes = (int64_t)pl->gx * S * WB_NACC * 64 * 4;
+    // (fgnn_linear_wgrad_multi refuses misaligned rows as errors before it launches)
+    if (!m && c.x && (((uintptr_t)c.x & 7) || ((uintptr_t)c.gy[0] & 7))) FGNN_REJECT("wgrad b16", 3);
+    bool aligned = ((uintptr_t)c.x & 15) == 0;
+    for (int s = 0; s < c.nsrc; ++s) aligned = aligned && ((uintptr_t)c.gy[s] & 15) == 0;
+    WglParams q;
+    pl->mode = S >= 8 && c.R >= 2048 && aligned && wl_stages(c, S, &q);
+    return 1;
+}
+
+int fgnn_wgrad_b16_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
+    const int S = pl.aux, RW = 16 / S, gx = pl.gx;
+    WgbParams p = {};
+    p.x = (const uint16_t*)c.x; p.gy = (const uint16_t*)c.gy[0]; p.ws = (float*)c.workspace;
+    p.R = (int)c.R; p.Cin = c.Cin; p.Cout = c.cout[0]; p.nso = c.cout[0] / 64; p.S = S; p.RW = RW;
+    for (int s = 0; s < WB_MAXSRC; ++s) {
+        p.gys[s] = (const uint16_t*)c.gy[s < c.nsrc ? s : 0];
+        p.couts[s] = c.cout[s < c.nsrc ? s : 0];
     }
+    for (int s = 0; s <= WB_MAXSRC; ++s) p.sb[s] = pl.sb[s];
     hipError_t e;
-    if (staged) {
+    if (pl.mode) {
+        WglParams q = {};
+        wl_stages(c, S, &q);
+        q.b = p;
         void* fn = (void*)linear_wgrad_lds_kernel;
         const int bytes = q.nst * q.stage_bytes;
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
         void* args[] = {(void*)&q};
-        e = hipLaunchKernel(fn, dim3(gx), dim3(WB_THREADS), args, bytes, st);
+        e = hipLaunchKernel(fn, dim3(gx), dim3(WB_THREADS), args, bytes, c.stream);
     } else {
         void* fn = (void*)linear_wgrad_b16_kernel;
+        const int lds = S * (RW / 2) * WB_NACC * 64 * 4;                   // 0 when every slice has one row-wave
         if (lds > 48 * 1024) {
             e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
         }
         void* args[] = {(void*)&p};
-        e = hipLaunchKernel(fn, dim3(gx), dim3(WB_THREADS), args, lds, st);
+        e = hipLaunchKernel(fn, dim3(gx), dim3(WB_THREADS), args, lds, c.stream);
     }
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad_b16 launch: %s", hipGetErrorString(e));
     const int64_t stride = (int64_t)S * WB_NACC * 64;                  // distance between the workgroups' slabs
-    for (int s = 0; s < nsrc; ++s) {
-        const int Ss = sb[s + 1] - sb[s], nso = couts[s] / 64;
+    for (int s = 0; s < c.nsrc; ++s) {
+        const int Ss = pl.sb[s + 1] - pl.sb[s], nso = c.cout[s] / 64;
         const int64_t len = (int64_t)Ss * WB_NACC * 64;
-        const float* ws_s = p.ws + (int64_t)sb[s] * WB_NACC * 64;
-        if (fgnn_fold_push(ws_s, gx, stride, len, gWs[s], gbs ? gbs[s] : nullptr, staged ? 2 : 1, Ss, nso, Cin, couts[s])) continue;      // recorded (fold_batch.hip)
-        if (staged)
-            hipLaunchKernelGGL(wgb_reduce_kernel<true>, dim3((unsigned)(len / 64)), dim3(1024), 0, st, ws_s, gx, stride, nso, Cin, couts[s], gWs[s],
-                               gbs ? gbs[s] : nullptr);
+        const float* ws_s = p.ws + (int64_t)pl.sb[s] * WB_NACC * 64;
+        if (fgnn_fold_push(ws_s, gx, stride, len, c.gW[s], c.gb[s], pl.mode ? 2 : 1, Ss, nso, c.Cin, c.cout[s])) continue;      // recorded (fold_batch.hip)
+        if (pl.mode)
+            hipLaunchKernelGGL(wgb_reduce_kernel<true>, dim3((unsigned)(len / 64)), dim3(1024), 0, c.stream, ws_s, gx, stride, nso, c.Cin, c.cout[s],
+                               c.gW[s], c.gb[s]);
         else
-            hipLaunchKernelGGL(wgb_reduce_kernel<false>, dim3((unsigned)(len / 64)), dim3(1024), 0, st, ws_s, gx, stride, nso, Cin, couts[s], gWs[s],
-                               gbs ? gbs[s] : nullptr);
+            hipLaunchKernelGGL(wgb_reduce_kernel<false>, dim3((unsigned)(len / 64)), dim3(1024), 0, c.stream, ws_s, gx, stride, nso, c.Cin, c.cout[s],
+                               c.gW[s], c.gb[s]);
     }
     e = hipGetLastError();
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad_b16 reduce launch: %s", hipGetErrorString(e));
-    return 1;
-}
-
-// The weight / bias gradients of nsrc <= 3 node-wise maps that read the SAME rows x [R][Cin] (the maps consuming one layer state:
-// conv1 of the blocks' heads, the state's own v2v / f2f map — /root/reference/lib/model/mpnn/factor_mpnn_sp.py:136-168) in ONE
-// pass: gW_s [couts[s]][Cin] += gy_s^T x, gb_s [couts[s]] += column sums of gy_s (gb_s may be NULL).  bf16, channel counts in
-// multiples of 64 up to 256, sum_s (couts[s] / 64) (Cin / 64) <= 16.  x is read once instead of nsrc times.
-extern "C" int64_t fgnn_linear_wgrad_multi_workspace_bytes(int64_t R, int32_t Cin, int32_t nsrc, const int32_t* couts) {
-    int sb[WB_MAXSRC + 1], S, RW, gx;
-    if (R <= 0 || R > 0x7fffffff || !couts || !wb_plan_multi(R, Cin, nsrc, couts, sb, &S, &RW, &gx)) return -1;
-    return (int64_t)gx * S * WB_NACC * 64 * 4;
-}
-
-extern "C" int fgnn_linear_wgrad_multi(const void* x, int64_t R, int32_t Cin, int32_t nsrc, const void* const* gy, const int32_t* couts,
-                                       float* const* gW, float* const* gb, void* workspace, int64_t workspace_bytes,
-                                       fgnn_stream_t stream) {
-    int sb[WB_MAXSRC + 1], S, RW, gx;
-    if (!x || !gy || !couts || !gW || !workspace) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: null pointer");
-    if (R <= 0 || R > 0x7fffffff) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: bad sizes");
-    if (!wb_plan_multi(R, Cin, nsrc, couts, sb, &S, &RW, &gx))
-        FGNN_FAIL(FGNN_EUNSUPPORTED, "linear_wgrad_multi: Cin=%d with %d sources is outside the kernel's family", Cin, nsrc);
-    for (int s = 0; s < nsrc; ++s) {
-        if (!gy[s] || !gW[s]) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: null pointer (source %d)", s);
-        if ((uintptr_t)gy[s] & 7) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: gy[%d] not 8-byte aligned", s);
-    }
-    if ((uintptr_t)x & 7) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: x not 8-byte aligned");
-    if (workspace_bytes < (int64_t)gx * S * WB_NACC * 64 * 4) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: workspace too small");
-    const int rc = wb_launch(x, R, Cin, nsrc, gy, couts, gW, gb, sb, S, RW, gx, workspace, (hipStream_t)stream);
-    return rc < 0 ? rc : FGNN_OK;
-}
-
-// Returns 1 if launched, 0 if the shape is outside this kernel's family, <0 on error.
-int fgnn_linear_wgrad_b16(const void* x, const void* gy, int64_t R, int Cin, int Cout, float* gW, float* gb,
-                          void* workspace, int64_t workspace_bytes, fgnn_stream_t stream) {
-    int nso, S, RW, gx;
-    bool nx;
-    if (wn_plan(R, Cin, Cout, &nx, &gx)) {
-        if (((uintptr_t)(nx ? gy : x) & 7) || ((uintptr_t)(nx ? x : gy) & 1)) return 0;
-        if (workspace_bytes < (int64_t)gx * WN_NACC * 64 * 4) return 0;
-        WgbParams p;
-        p.x = (const uint16_t*)x; p.gy = (const uint16_t*)gy; p.ws = (float*)workspace;
-        p.R = (int)R; p.Cin = Cin; p.Cout = Cout; p.nso = 1; p.S = 1; p.RW = WB_WAVES;
-        const int lds = (WB_WAVES / 2) * WN_NACC * 64 * 4;
-        hipStream_t st = (hipStream_t)stream;
-        const int wide_c = nx ? Cout : Cin;
-        for (int woff = 0; woff < wide_c; woff += 64) {     // the kernel reads 64 channels from the pointer, rows at the full stride
-            if (nx) {
-                p.gy = (const uint16_t*)gy + woff;
-                hipLaunchKernelGGL(linear_wgrad_b16_narrow_kernel<true>, dim3(gx), dim3(WB_THREADS), lds, st, p);
-                hipLaunchKernelGGL(wgn_reduce_kernel<true>, dim3(WN_NACC), dim3(1024), 0, st, p.ws, gx, Cin, Cout, woff, gW, gb);
-            } else {
-                p.x = (const uint16_t*)x + woff;
-                hipLaunchKernelGGL(linear_wgrad_b16_narrow_kernel<false>, dim3(gx), dim3(WB_THREADS), lds, st, p);
-                hipLaunchKernelGGL(wgn_reduce_kernel<false>, dim3(WN_NACC), dim3(1024), 0, st, p.ws, gx, Cin, Cout, woff, gW, gb);
-            }
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad_b16 narrow launch: %s", hipGetErrorString(e));
-        return 1;
-    }
-    if (!wb_plan(R, Cin, Cout, &nso, &S, &RW, &gx)) return 0;
-    if (((uintptr_t)x & 7) || ((uintptr_t)gy & 7)) return 0;
-    if (workspace_bytes < (int64_t)gx * S * WB_NACC * 64 * 4) return 0;
-    const int sb[WB_MAXSRC + 1] = {0, S, S, S};
-    const void* gys[1] = {gy};
-    const int32_t couts[1] = {Cout};
-    float* gWs[1] = {gW};
-    float* gbs[1] = {gb};
-    return wb_launch(x, R, Cin, 1, gys, couts, gWs, gbs, sb, S, RW, gx, workspace, (hipStream_t)stream);
+    return FGNN_OK;
 }

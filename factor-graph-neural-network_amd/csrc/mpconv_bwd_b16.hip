@@ -57,8 +57,6 @@ struct Bb16Params {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fgnn_lds_bb[];
 
-void fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias,
-                             hipStream_t st);
 void fgnn_launch_w_transpose(const float* W, float* Wt, int nin, int ncols, hipStream_t st);
 
 __device__ __forceinline__ float bb_lo(unsigned u) { return __uint_as_float(u << 16); }

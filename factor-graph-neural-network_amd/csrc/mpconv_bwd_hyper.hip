@@ -43,9 +43,6 @@ struct BhParams {
 
 extern __shared__ __attribute__((aligned(16))) float fgnn_lds_bh[];
 
-void fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias,
-                             hipStream_t st);
-
 __device__ __forceinline__ float bh_bcast(float v, int l) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }

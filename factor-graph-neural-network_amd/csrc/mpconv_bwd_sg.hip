@@ -73,11 +73,6 @@ extern __shared__ __attribute__((aligned(16))) unsigned char bs_lds[];
 #define BS_STAMP(slot) do { } while (0)
 #endif
 
-void fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias,
-                             hipStream_t st);
-void fgnn_launch_slab_reduce_ld(const float* ws, int nslab, int64_t slab_len, int64_t nw, int ncols, int ld, float* gW,
-                                float* gbias, hipStream_t st);
-
 // uniform 64-bit base + UNSIGNED 32-bit per-lane byte offset: the form the compiler turns into `global_load v, v_off, s[base]`
 // (a signed or 64-bit per-lane offset becomes a per-lane 64-bit pointer: two VGPRs each, hoisted out of the sample loop)
 template <typename T> __device__ __forceinline__ const T* bs_at(const void* base, unsigned byte_off) {

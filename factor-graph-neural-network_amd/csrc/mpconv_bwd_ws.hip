@@ -79,11 +79,6 @@ struct BwParams {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char bw_lds[];
 
-void fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias,
-                             hipStream_t st);
-void fgnn_launch_slab_reduce_ld(const float* ws, int nslab, int64_t slab_len, int64_t nw, int ncols, int ld, float* gW,
-                                float* gbias, hipStream_t st);
-
 __device__ __forceinline__ unsigned bw_pack2(float a, float b) {
     typedef __bf16 v2 __attribute__((ext_vector_type(2)));
     const v2 h = {(__bf16)a, (__bf16)b};

@@ -96,6 +96,5 @@ int fgnn_bwd_sg_rules(const FgnnBwdCall& c, const FgnnSwitches& sw, bool layout_
 // ---- shared helpers ----
 int fgnn_check_desc(const fgnn_mpconv_desc* d);
 void fgnn_stats_upper_half(FgnnFold* fold, fgnn_bn_final* fin);
-void fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias, hipStream_t st);
 void fgnn_launch_slab_store(const float* ws, int nslab, int64_t slab_len, float* out, hipStream_t st);
 int64_t fgnn_mpconv_backward_ext_extra_bytes(const fgnn_mpconv_desc* d);

@@ -468,7 +468,6 @@ void fgnn_stats_upper_half(FgnnFold* fold, fgnn_bn_final* fin) {
     if (fin->shift_k) fin->shift_k += 64;
     fin->num_batches_tracked = nullptr;
 }
-int fgnn_bn_finalize_launch(const float* partials, int npartials, int C, const fgnn_bn_final* fin, hipStream_t st);
 
 // The call is planned once, with its pointers: the launch and the stand-alone finaliser's row count come from that one plan.
 extern "C" int fgnn_mpconv_forward_stats(const fgnn_mpconv_desc* d, const void* x, const int64_t* nn_idx,

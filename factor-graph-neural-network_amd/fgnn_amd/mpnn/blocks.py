@@ -209,11 +209,7 @@ class _BlockHead(torch.autograd.Function):
             record = s_W and s_bias and ops.folds_deferrable()
 
             def launch(rows=rows, gz1=gz1, gW=gW, gbias=gbias):
-                with ops.fold_scope(record) as scope:
-                    wsw = scope.slabs(dev, int(L.fgnn_linear_wgrad_workspace_bytes(R, cin, 64)))
-                    ops.timed('linear_wgrad_b16_kernel', 2 * R * (cin + 64), lambda: _hip.check(L.fgnn_linear_wgrad(
-                        P(rows), P(gz1), R, cin, 64, _hip.BF16, P(gW.view(64, cin)), P(gbias), P(wsw), wsw.numel() * 4, _hip.stream_ptr())),
-                        nflops=2 * R * cin * 64)
+                ops.linear_wgrad(rows, [(gz1, gW.view(64, cin), gbias)], record)
             if s_W and s_bias:
                 ops.defer_wgrad(launch, (rows, gz1))
             else:
@@ -401,11 +397,7 @@ class _BlockTail(torch.autograd.Function):
             operands = (mom, scale3)
         else:
             def launch(a2=a2, gz3=gz3, gW2=gW2, gbias2=gbias2):
-                with ops.fold_scope(record) as scope:
-                    wsw = scope.slabs(dev, int(L.fgnn_linear_wgrad_workspace_bytes(R, 64, Cout)))
-                    ops.timed('linear_wgrad_b16_kernel', 2 * R * (64 + Cout), lambda: _hip.check(L.fgnn_linear_wgrad(
-                        P(a2), P(gz3), R, 64, Cout, _hip.BF16, P(gW2.view(Cout, 64)), P(gbias2), P(wsw), wsw.numel() * 4, _hip.stream_ptr())),
-                        nflops=2 * R * 64 * Cout)
+                ops.linear_wgrad(a2, [(gz3, gW2.view(Cout, 64), gbias2)], record)
             operands = (a2, gz3)
         if s_W2 and s_bias2:
             ops.defer_wgrad(launch, operands)

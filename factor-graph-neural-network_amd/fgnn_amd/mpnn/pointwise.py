@@ -327,7 +327,6 @@ class _RowLinear(torch.autograd.Function):
             gw = (gy.t() @ rows).float()                # f32 square 256-wide maps: rocBLAS is ahead there
             gb = gy.float().sum(0) if ctx.has_bias else None
             return grows, gw.to(weight.dtype), (gb.to(weight.dtype) if gb is not None else None), None, None, None
-        L = _hip.lib()
         gw = gw_sink if gw_sink is not None else torch.zeros((cout, cin), device=rows.device, dtype=torch.float32)
         gb = None
         if ctx.has_bias:
@@ -335,14 +334,7 @@ class _RowLinear(torch.autograd.Function):
         record = sinks and ops.folds_deferrable()        # (decided here, inside the pass: a parked launch may go out from its end-of-pass callback)
 
         def launch(rows=rows, gy=gy, gw=gw, gb=gb):      # (the closure keeps rows / gy alive until the kernel is issued)
-            with ops.fold_scope(record) as scope:
-                ws = scope.slabs(rows.device, int(L.fgnn_linear_wgrad_workspace_bytes(R, cin, cout)))
-                ops.timed('linear_wgrad_b16_kernel' if rows.dtype == torch.bfloat16 else 'linear_wgrad_kernel',
-                          rows.element_size() * R * (cin + cout),
-                          lambda: _hip.check(L.fgnn_linear_wgrad(_hip._ptr(rows), _hip._ptr(gy), R, cin, cout,
-                                                                 _hip.dtype_code(rows), _hip._ptr(gw), _hip._ptr(gb),
-                                                                 _hip._ptr(ws), ws.numel() * 4, _hip.stream_ptr())),
-                          nflops=2 * R * cin * cout)
+            ops.linear_wgrad(rows, [(gy, gw, gb)], record)
         # nothing in the backward reads a weight gradient: with both gradients going to the flat bucket the kernel is parked
         # and issued where its stream would otherwise wait for the other one (ops.defer_wgrad)
         if sinks:

@@ -176,6 +176,34 @@ class fold_scope:
         return False
 
 
+def linear_wgrad(rows, jobs, record):
+    """gW += gy^T rows and gb += the column sums of gy (gb may be None) for every job (gy [R, K], gW [K, C] f32, gb [K] f32) of
+    node-wise maps that read the same rows [R, C]: ONE csrc/linear_wgrad_b16.hip launch over several jobs when its merged form takes
+    them (``fgnn_linear_wgrad_multi``: the rows are read once), else one ``fgnn_linear_wgrad`` launch per job.  ``record``: the
+    slab folds are recorded (fold_scope)."""
+    L = _hip.lib()
+    P = _hip._ptr
+    R, C = rows.shape
+    symbol = 'linear_wgrad_b16_kernel' if rows.dtype == torch.bfloat16 else 'linear_wgrad_kernel'
+    couts = (ctypes.c_int32 * len(jobs))(*[gy.shape[1] for gy, _, _ in jobs])
+    with fold_scope(record) as scope:
+        nb = int(L.fgnn_linear_wgrad_multi_workspace_bytes(R, C, len(jobs), couts)) if len(jobs) > 1 else -1
+        if nb > 0:
+            ws = scope.slabs(rows.device, nb)
+            ptrs = lambda i: (ctypes.c_void_p * len(jobs))(*[P(j[i]) for j in jobs])
+            K = sum(couts)
+            timed(symbol, rows.element_size() * R * (C + K),
+                  lambda: _hip.check(L.fgnn_linear_wgrad_multi(P(rows), R, C, len(jobs), ptrs(0), couts, ptrs(1), ptrs(2), P(ws), ws.numel() * 4,
+                                                               _hip.stream_ptr())), nflops=2 * R * C * K)
+            return
+        for gy, gW, gb in jobs:
+            K = gy.shape[1]
+            ws = scope.slabs(rows.device, int(L.fgnn_linear_wgrad_workspace_bytes(R, C, K)))
+            timed(symbol, rows.element_size() * R * (C + K),
+                  lambda: _hip.check(L.fgnn_linear_wgrad(P(rows), P(gy), R, C, K, _hip.dtype_code(rows), P(gW), P(gb), P(ws), ws.numel() * 4,
+                                                         _hip.stream_ptr())), nflops=2 * R * C * K)
+
+
 def flush_folds():
     """Fold everything recorded, on the current stream (the caller has ordered it behind every producer)."""
     L = _hip.lib()
@@ -997,34 +1025,10 @@ class FanBox:
         self._park_wgrad_group(jobs)
 
     def _park_wgrad_group(self, jobs):
-        L = _hip.lib()
-        P = _hip._ptr
         rows = jobs[0][1][0]
-        R, C = self.R, self.C
-        gzs = [j[0] for j in jobs]
+        wjobs = [(gz, gW, gb) for gz, (_, gW, gb) in jobs]
         record = folds_deferrable()          # (decided inside the pass: the parked launch may go out from its end-of-pass callback)
-        couts = (ctypes.c_int32 * len(jobs))(*[g.shape[1] for g in gzs])
-        multi = len(jobs) > 1 and int(L.fgnn_linear_wgrad_multi_workspace_bytes(R, C, len(jobs), couts)) > 0
-
-        def launch(rows=rows, jobs=jobs):
-            with fold_scope(record) as scope:
-                if multi:
-                    nb = int(L.fgnn_linear_wgrad_multi_workspace_bytes(R, C, len(jobs), couts))
-                    ws = scope.slabs(rows.device, nb)
-                    gy = (ctypes.c_void_p * len(jobs))(*[P(j[0]) for j in jobs])
-                    gW = (ctypes.c_void_p * len(jobs))(*[P(j[1][1]) for j in jobs])
-                    gb = (ctypes.c_void_p * len(jobs))(*[P(j[1][2]) for j in jobs])
-                    timed('linear_wgrad_b16_kernel', 2 * R * (C + sum(couts)),
-                          lambda: _hip.check(L.fgnn_linear_wgrad_multi(P(rows), R, C, len(jobs), gy, couts, gW, gb, P(ws), ws.numel() * 4,
-                                                                       _hip.stream_ptr())), nflops=2 * R * C * sum(couts))
-                    return
-                for gz, (_, gW1, gb1) in jobs:       # (outside the merged kernel's family: one launch per map, as their owners would have)
-                    K = gz.shape[1]
-                    ws = scope.slabs(rows.device, int(L.fgnn_linear_wgrad_workspace_bytes(R, C, K)))
-                    timed('linear_wgrad_b16_kernel', 2 * R * (C + K),
-                          lambda: _hip.check(L.fgnn_linear_wgrad(P(rows), P(gz), R, C, K, _hip.BF16, P(gW1), P(gb1), P(ws), ws.numel() * 4,
-                                                                 _hip.stream_ptr())), nflops=2 * R * C * K)
-        defer_wgrad(launch, (rows,) + tuple(gzs))
+        defer_wgrad(lambda: linear_wgrad(rows, wjobs, record), (rows,) + tuple(j[0] for j in wjobs))
 
     def merge(self, grads):
         """The state's gradient from the deposits + the gradients that arrived as tensors."""

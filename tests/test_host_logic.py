@@ -130,6 +130,24 @@ def test_forward_planner_picks_the_statistics_grid_without_a_gpu():
     assert rows(64, 64, 1, 48, 1, 48) == 0                   # hyper-factor fan-in: no statistics epilogue
 
 
+def test_weight_gradient_planner_sizes_the_workspace_without_a_gpu():
+    """fgnn_linear_wgrad_workspace_bytes / fgnn_linear_wgrad_multi_workspace_bytes run the weight-gradient families' plans without
+    pointers: the single-map answer is the largest need of the families that take the shape whatever its dtype, -1
+    if none does."""
+    from fgnn_amd import _hip
+    L = _hip.lib()
+    q = lambda R, cin, cout: int(L.fgnn_linear_wgrad_workspace_bytes(R, cin, cout))
+    m = lambda R, cin, couts: int(L.fgnn_linear_wgrad_multi_workspace_bytes(R, cin, len(couts), (ctypes.c_int32 * len(couts))(*couts)))
+    R = 393216                                          # LDPC rows: the b16 family (one slice per 64 x 64 block), or the general kernel
+    assert q(R, 64, 64) == 8519680 and q(R, 64, 128) == 17039360 and q(R, 256, 256) == 71303168
+    assert q(R, 192, 64) == 25296896                    # S = 3 slices: not a power of two, the general kernel
+    assert q(R, 2, 64) == 2228224 and q(R, 64, 4) == 2129920          # one narrow operand
+    assert q(61440, 64, 64) == 7987200 and q(61440, 256, 256) == 71303168 and q(61440, 512, 512) == 33619968     # f32 blocked maps
+    assert q(61440, 1025, 64) == -1                     # wider than the register tiling
+    assert m(R, 64, (64, 128, 64)) == 17825792 and m(R, 64, (192,)) == 17825792   # 3 live slices padded to 4
+    assert m(R, 256, (64, 256, 64)) == -1 and m(R, 64, (64,) * 4) == -1
+
+
 def test_side_entry_points_validate_their_arguments_without_a_gpu():
     """Size / pointer checks of the entry points either side of the operator run before any device work: unsupported
     shapes come back as FGNN_EUNSUPPORTED (-3), missing buffers as FGNN_EINVAL (-1), with a message."""

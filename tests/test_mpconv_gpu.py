@@ -786,6 +786,11 @@ def test_weight_gradients_of_several_maps_refuses_what_it_cannot_tile(dev):
     rc = L.fgnn_linear_wgrad_multi(P(x), 4096, 256, 3, (ctypes.c_void_p * 3)(P(gy), P(gy), P(gy)), (ctypes.c_int32 * 3)(64, 256, 64),
                                    (ctypes.c_void_p * 3)(P(gw), P(gw), P(gw)), None, P(ws), ws.numel() * 4, _hip.stream_ptr())
     assert rc == _hip.EUNSUPPORTED
+    # a map the b16 family takes, handed less workspace than its plan needs (more than the general kernel's): an error, no other kernel
+    need = int(L.fgnn_linear_wgrad_workspace_bytes(4096, 256, 256))
+    ws = torch.zeros(need // 4, device=dev)
+    rc = L.fgnn_linear_wgrad(P(x), P(gy), 4096, 256, 256, _hip.BF16, P(gw), None, P(ws), need - 1024, _hip.stream_ptr())
+    assert rc == -1 and b'workspace' in L.fgnn_last_error()
 
 
 @pytest.mark.parametrize('cin,cout', [(64, 64), (64, 128), (128, 256), (256, 256), (256, 128), (128, 64)])
