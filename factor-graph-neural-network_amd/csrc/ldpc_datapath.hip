@@ -13,6 +13,7 @@
 // inputs (the transform is deterministic and is checked bit-for-bit (encode) / to f32 rounding (channel) against
 // the oracle) or come from a counter-based generator inside the kernel (fgnn_ldpc_channel_features_rng).
 #include "fgnn_common.h"
+#include "fgnn_philox.h"
 #include <stdint.h>
 
 #define LD_THREADS 256
@@ -59,19 +60,6 @@ struct LdFeatParams {
     unsigned long long seed, offset;     // RNG variant: Philox key and stream offset (z1 / u / z2 are not read)
 };
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter-based, so the draws of
-// codeword bit i of the batch depend on (seed, offset, i) only — not on the grid, the launch order or earlier calls.
-// oracle/fgnn_oracle.py::philox4x32 restates it in numpy; tests compare the two streams through the channel output.
-__device__ __forceinline__ void ld_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&r)[4]) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
 // standard normal from two 32-bit words (Box-Muller, cosine branch): u1 in (0, 1], u2 in [0, 1)
 __device__ __forceinline__ float ld_normal(unsigned a, unsigned b) {
     const float u1 = ((float)(a >> 8) + 1.0f) * 5.9604644775390625e-08f, u2 = (float)(b >> 8) * 5.9604644775390625e-08f;

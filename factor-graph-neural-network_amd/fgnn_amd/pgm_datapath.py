@@ -1,0 +1,148 @@
+"""The synthetic-PGM data path, per batch on the GPU: the reference's random chain models and their exact MAP labels.
+
+The reference makes the datasets of train_syn_pw_factor.py / train_syn_hop_factor.py on the host, one item at a time
+(/root/reference/lib/data/random_pgm.py, random_pgm_pw.py, random_pgm_hop.py and the NoHop variants; written to a pickle stream
+by data_generate/generate_random_pgm.py), and labels every item with AD3's branch-and-bound.  Those models are chains of binary
+variables with 2x2 link factors and a budget factor on every window of h consecutive variables, so the exact MAP is a Viterbi
+recursion over the last h-1 bits.  ``PgmDataPath`` runs that recursion (csrc/pgm_datapath.hip, one wave64 per sample) on
+potentials the caller has (``solve_map``) or on models it draws itself (``sample``).  No CPU fallback.
+"""
+import ctypes
+import pickle
+
+import numpy as np
+import torch
+
+from . import _hip
+
+FAMILIES = {'raw': 0, 'pws': 1, 'hops': 2}
+
+
+def check_chain(N, h):
+    """ValueError unless the solver takes chains of N variables with windows of h (2 <= h <= 13, N >= h, the per-sample LDS
+    footprint within the workgroup limit).  Asks the library (fgnn_chain_budget_map_lds_bytes), no device needed."""
+    N, h = int(N), int(h)
+    L = _hip.lib()
+    if L.fgnn_chain_budget_map_lds_bytes(N, h) < 0:
+        raise ValueError(L.fgnn_last_error().decode())
+    return N, h
+
+
+def _batched(t, name, per_sample, B=None):
+    """t of shape per_sample (shared: batch stride 0) or [B] + per_sample -> (tensor with a batch axis, batch size or None)."""
+    per_sample = tuple(per_sample)
+    if tuple(t.shape) == per_sample:
+        return t.unsqueeze(0), None
+    if t.dim() == len(per_sample) + 1 and tuple(t.shape[1:]) == per_sample and (B is None or t.shape[0] == B):
+        return t, t.shape[0]
+    raise ValueError('%s must be %s or [B, %s]%s, got %s' % (name, list(per_sample), ', '.join(map(str, per_sample)),
+                                                            '' if B is None else ' with B = %d' % B, tuple(t.shape)))
+
+
+def check_solve_args(unary, pair, caps, N, h):
+    """Shapes of a ``solve_map`` call, checked before anything reaches the device.  unary [B,N,2]; pair [N-1,4] / [N-1,2,2] or with
+    a leading [B]; caps an int, [N-h+1] or [B,N-h+1].  Returns (B, unary, pair [*,N-1,4], caps [*,N-h+1]) as tensors."""
+    N, h = check_chain(N, h)
+    unary = torch.as_tensor(unary)
+    if unary.dim() != 3 or tuple(unary.shape[1:]) != (N, 2):
+        raise ValueError('unary must be [B, %d, 2], got %s' % (N, tuple(unary.shape)))
+    B = unary.shape[0]
+    pair = torch.as_tensor(pair)
+    if pair.shape[-2:] == (2, 2):
+        pair = pair.reshape(tuple(pair.shape[:-2]) + (4,))
+    pair, _ = _batched(pair, 'pair', (N - 1, 4), B)
+    if isinstance(caps, (int, np.integer)):
+        caps = torch.full((N - h + 1,), int(caps), dtype=torch.int32)
+    caps = torch.as_tensor(caps)
+    if caps.is_floating_point() or caps.is_complex() or caps.dtype == torch.bool:
+        raise ValueError('caps must be integers, got %s' % caps.dtype)
+    caps, _ = _batched(caps, 'caps', (N - h + 1,), B)
+    return B, unary, pair, caps
+
+
+class PgmDataPath:
+    """Chains of ``chain_length`` binary variables with budget windows of ``hop_order`` (the reference's 30 and 9).
+
+    ``solve_map`` labels potentials the caller has; ``sample`` draws a training batch of the reference's models (families
+    ``raw`` = RandomPGM, ``pws`` = RandomPGMPw, ``hops`` = RandomPGMHop) and labels it; ``write_reference_dataset`` writes the
+    reference's pickle stream for an unchanged ``train_syn_*.py --train_path``."""
+
+    def __init__(self, device, chain_length=30, hop_order=9):
+        self.N, self.h = check_chain(chain_length, hop_order)
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('PgmDataPath runs on a ROCm device (no CPU fallback)')
+
+    def solve_map(self, unary, pair, caps, want_objective=False):
+        """Exact MAP of B chains: unary [B,N,2] log-potentials; pair [N-1,4] (row-major [x_i][x_{i+1}], or [N-1,2,2]) or
+        [B,N-1,4]; caps: an int, [N-h+1] or [B,N-h+1] — window w = x_w .. x_{w+h-1} holds at most caps[w] ones (cap >= h: no
+        constraint, the NoHop models).  Potentials are read as f32 and summed in f64.  Ties: the lowest state (csrc/pgm_datapath.hip).
+        Returns labels [B,N] int64 (and the objective [B] f64 with want_objective)."""
+        B, unary, pair, caps = check_solve_args(unary, pair, caps, self.N, self.h)
+        dev = self.device
+        if B == 0:
+            labels = torch.empty((0, self.N), device=dev, dtype=torch.int64)
+            return (labels, torch.empty((0,), device=dev, dtype=torch.float64)) if want_objective else labels
+        u = unary.to(dev, torch.float32).contiguous()
+        p = pair.to(dev, torch.float32).contiguous()
+        c = caps.to(dev, torch.int32).contiguous()
+        sb = lambda t: 0 if t.shape[0] == 1 and B != 1 else t[0].numel()
+        labels = torch.empty((B, self.N), device=dev, dtype=torch.int64)
+        obj = torch.empty((B,), device=dev, dtype=torch.float64) if want_objective else None
+        P = _hip._ptr
+        _hip.check(_hip.lib().fgnn_chain_budget_map(P(u), u[0].numel(), P(p), sb(p), P(c), sb(c), B, self.N, self.h,
+                                                    P(labels), P(obj), _hip.stream_ptr()))
+        return (labels, obj) if want_objective else labels
+
+    def sample(self, B, family='hops', seed=0, step=0, cap=5, transition=(0, .1, .2, 1), want_objective=False):
+        """One training batch of B random models, drawn in the kernel from (seed, step) (Philox4x32-10; a training loop passes its
+        step), in the tuple order the reference's ``RandomPGMData`` yields for ``family``:
+          hops: (node_feature [B,2,N,1], pws [B,4,N,1], hops [B,h,N,1], label [B,N])   RandomPGMHop (per-position caps)
+          pws:  (node_feature, pws, label)                                             RandomPGMPw (every window ``cap``)
+          raw:  (node_feature, label)                                                  RandomPGM (link table ``transition``)
+        Features f32, labels int64 = the exact MAP.  ``cap`` >= h gives the NoHop variants.  With want_objective the MAP
+        objective [B] f64 is appended."""
+        if family not in FAMILIES:
+            raise ValueError('family must be one of %s, got %r' % (sorted(FAMILIES), family))
+        B = int(B)
+        if B < 0:
+            raise ValueError('batch must be >= 0')
+        if len(tuple(transition)) != 4:
+            raise ValueError('transition must hold 4 values (row-major [x_i][x_{i+1}])')
+        N, h, dev = self.N, self.h, self.device
+        fam = FAMILIES[family]
+        node = torch.empty((B, 2, N, 1), device=dev, dtype=torch.float32)
+        pws = torch.empty((B, 4, N, 1), device=dev, dtype=torch.float32) if fam != 0 else None
+        hops = torch.empty((B, h, N, 1), device=dev, dtype=torch.float32) if fam == 2 else None
+        label = torch.empty((B, N), device=dev, dtype=torch.int64)
+        obj = torch.empty((B,), device=dev, dtype=torch.float64) if want_objective else None
+        trans = (ctypes.c_float * 4)(*[float(v) for v in transition])          # host memory, copied into the launch
+        P = _hip._ptr
+        _hip.check(_hip.lib().fgnn_pgm_sample_rng(fam, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, B, N, h,
+                                                  int(cap), ctypes.cast(trans, ctypes.c_void_p), P(node), P(pws), P(hops),
+                                                  P(label), P(obj), _hip.stream_ptr()))
+        out = (node, pws, hops, label) if fam == 2 else (node, pws, label) if fam == 1 else (node, label)
+        return out + (obj,) if want_objective else out
+
+    def write_reference_dataset(self, path, family, size, seed, step=0, batch=4096, cap=5, transition=(0, .1, .2, 1)):
+        """Write ``size`` items of ``family`` as the reference's pickle stream (data_generate/generate_random_pgm.py: one
+        ``pickle.dump`` per item), readable by ``RandomPGMData(path, family, size)`` and so by an unchanged
+        ``train_syn_*.py --train_path``.  Items come from ``sample(batch, family, seed, step + k)`` for k = 0, 1, ..., so item i of
+        the first chunk is item i of ``sample(..., seed, step)``.  Per item, as random_pgm*.py returns them with the features
+        unexpanded: hops (node_feature [2,N], pws [4,N,1], hop feature [h,N,1] f32, assign [N], assign1 [N] int64), pws
+        (node_feature, pws, assign, assign1), raw (node_feature, assign, assign1).
+
+        ``assign`` is the exact MAP.  ``assign1``, the reference's label from AD3's LP relaxation (``solve(branch_and_bound=False)``),
+        is NOT produced: it is -1 everywhere, so the scripts' ``lp_acc`` reads 0."""
+        size, batch = int(size), max(1, int(batch))
+        with open(path, 'wb') as f:
+            k = 0
+            while k * batch < size:
+                n = min(batch, size - k * batch)
+                out = [t.cpu().numpy() for t in self.sample(n, family, seed, step + k, cap, transition)]
+                label = out[-1]
+                feats = [np.ascontiguousarray(out[0][:, :, :, 0])] + out[1:-1]                  # node_feature [2,N]; pws / hops keep their [.., N, 1]
+                lp = np.full((self.N,), -1, np.int64)
+                for i in range(n):
+                    pickle.dump(tuple(a[i] for a in feats) + (label[i], lp.copy()), f)
+                k += 1

@@ -574,6 +574,38 @@ int fgnn_ldpc_decode(const double* bias, const int32_t* col_ptr, const int32_t* 
                      const int32_t* row_var, int64_t B, int32_t N, int32_t M, int32_t E, int32_t loops, uint8_t* x,
                      double* q1, int32_t* viol, int32_t* iters, fgnn_stream_t stream);
 
+/*
+ * The synthetic-PGM data path (csrc/pgm_datapath.hip).  The reference labels every item of its synthetic datasets with AD3's
+ * branch-and-bound (`g.solve(tol=1e-6, branch_and_bound=True)`, /root/reference/lib/data/random_pgm.py:20-48,
+ * random_pgm_pw.py:28-45,75-85, random_pgm_hop.py:28-45,111-125 and the NoHop variants); its models are chains of N binary
+ * variables with 2x2 link factors and budget factors on every window of h consecutive variables, so the exact MAP is a Viterbi
+ * recursion over the last h-1 bits (2^(h-1) states) instead.
+ *
+ * fgnn_chain_budget_map     labels [B][N] int64 = the MAP assignment, objective [B] f64 (or NULL) = its log-potential sum, for
+ *                           unary [B][N][2], pair [B][N-1][4] (row-major [x_i][x_{i+1}]), caps [B][N-h+1] int32 (window w =
+ *                           x_w .. x_{w+h-1} holds at most caps[w] ones; cap >= h: no constraint).  Each input is dense per
+ *                           sample; a batch stride of 0 shares it.  Scores in f64, candidate (V + pair) + unary, ties to the
+ *                           dropped bit 0 and to the lowest final state.  2 <= h <= 13, N >= h, LDS footprint within 160 KiB
+ *                           (FGNN_EUNSUPPORTED otherwise).
+ * fgnn_chain_budget_map_lds_bytes  the per-sample LDS footprint of (N, h), -1 outside the family (message in fgnn_last_error):
+ *                           the host validates shapes with it without launching.
+ * fgnn_pgm_sample_rng       B random models of `family` 0 = raw (RandomPGM: unary U(0,1), fixed `transition` [4] (host memory),
+ *                           fixed `cap`), 1 = pws (RandomPGMPw, random_pgm_pw.py:48-73: unary U(0,1), pair[i][1][1] = U(0,2),
+ *                           fixed `cap`), 2 = hops (RandomPGMHop, random_pgm_hop.py:47-93: as pws, per-position caps
+ *                           U{1..h-1}, window w uses cap[w + h/2]), drawn by Philox4x32-10: word w of sample b =
+ *                           philox(counter (b, w/4, offset lo, offset hi), key seed)[w % 4], draw order lops, link bonus, caps.
+ *                           Writes node [B][2][N] (lops^T), pws [B][4][N] (to-right link, zero at N-1; pws/hops), hops [B][h][N]
+ *                           (one-hot cap, h-1 at the h/2 border positions; hops), f32, and the labels / objective of
+ *                           fgnn_chain_budget_map for those models.
+ */
+int fgnn_chain_budget_map(const float* unary, int64_t unary_sb, const float* pair, int64_t pair_sb, const int32_t* caps,
+                          int64_t caps_sb, int64_t B, int32_t N, int32_t h, int64_t* labels, double* objective,
+                          fgnn_stream_t stream);
+int64_t fgnn_chain_budget_map_lds_bytes(int32_t N, int32_t h);
+int fgnn_pgm_sample_rng(int32_t family, uint64_t seed, uint64_t offset, int64_t B, int32_t N, int32_t h, int32_t cap,
+                        const float* transition, float* node, float* pws, float* hops, int64_t* labels, double* objective,
+                        fgnn_stream_t stream);
+
 const char* fgnn_last_error(void);
 /* Name (as rocprofv3 prints it) of the kernel the calling thread's last forward/backward dispatched to. */
 const char* fgnn_last_kernel(void);
@@ -582,8 +614,9 @@ const char* fgnn_last_kernel(void);
  * mismatch and not as a missing symbol or a misread field.  4: round-2 additions (flat_adam, factor_layer_*,
  * ldpc_channel_features_rng, backward_reduces_getype, desc.reserved = in-degree | GETYPE_REDUCED); 5: fgnn_block_tail_*;
  * 6: fgnn_block_head_backward.  11: fgnn_mpconv_block_forward_rows.  12: fgnn_block_tail_backward_moments,
- * fgnn_block_tail_wgrad_finish, fgnn_block_tail_moments_bytes. */
-#define FGNN_ABI_VERSION 13
+ * fgnn_block_tail_wgrad_finish, fgnn_block_tail_moments_bytes.  14: fgnn_chain_budget_map, fgnn_chain_budget_map_lds_bytes,
+ * fgnn_pgm_sample_rng. */
+#define FGNN_ABI_VERSION 14
 /* Arithmetic of the f32 synthetic-PGM operator's BACKWARD (16 edge types, ORIG_WITH_NEIGHBOR / ORIG_WITH_DIFF, 64 -> 64, max: the
  * autograd of /root/reference/lib/model/mpnn/mp_nn.py:136-175 as train_syn_*.py reaches it): 2 (default) = every f32 operand of the three
  * GEMMs as two bf16 pieces on the bf16 matrix cores (gradients within 5e-6 of the exact kernel's), 3 = three pieces (4e-7), 0 = f32 matrix
