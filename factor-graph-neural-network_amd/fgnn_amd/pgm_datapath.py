@@ -5,7 +5,12 @@ The reference makes the datasets of train_syn_pw_factor.py / train_syn_hop_facto
 by data_generate/generate_random_pgm.py), and labels every item with AD3's branch-and-bound.  Those models are chains of binary
 variables with 2x2 link factors and a budget factor on every window of h consecutive variables, so the exact MAP is a Viterbi
 recursion over the last h-1 bits.  ``PgmDataPath`` runs that recursion (csrc/pgm_datapath.hip, one wave64 per sample) on
-potentials the caller has (``solve_map``) or on models it draws itself (``sample``).  No CPU fallback.
+potentials the caller has (``solve_map``) or on models it draws itself (``sample``).
+
+The reference labels every item a second time, with the argmax of AD3's LP-relaxation posteriors (``assign1``, the ``lp_acc``
+baseline of train_syn_*.py).  ``solve_lp`` solves that LP the way AD3 does, by ADMM over the local polytope (csrc/pgm_lp.hip, one
+wave64 per sample, f64), from AD3's start with its default step, tolerance and iteration cap; ``sample(..., lp_label=True)`` and
+``write_reference_dataset(..., lp_label=True)`` add that label.  No CPU fallback.
 """
 import ctypes
 import pickle
@@ -94,14 +99,65 @@ class PgmDataPath:
                                                     P(labels), P(obj), _hip.stream_ptr()))
         return (labels, obj) if want_objective else labels
 
-    def sample(self, B, family='hops', seed=0, step=0, cap=5, transition=(0, .1, .2, 1), want_objective=False):
+    def solve_lp(self, unary, pair, caps, max_iter=1000, tol=1e-6, eta=0.1, adapt=True, want_details=False):
+        """The LP relaxation of the same B chains (inputs as ``solve_map``), by AD3-style ADMM (csrc/pgm_lp.hip): start z = 1/2,
+        step ``eta`` with residual balancing every 50th iteration when ``adapt``, stop when both RMS residuals are below ``tol`` or
+        after ``max_iter`` iterations (the defaults are the reference's call, AD3's ``solve()`` defaults).  Returns labels [B,N]
+        int64 (z_i > 0.5; ties to 0), and with want_details also a dict of marginals [B,N] f64 (z), value [B] f64 (the LP
+        objective at z), status [B] int32 (0 integral, 1 fractional, 2 infeasible: a negative cap, 3 iteration cap reached) and
+        iters [B] int32."""
+        B, unary, pair, caps = check_solve_args(unary, pair, caps, self.N, self.h)
+        max_iter, tol, eta = int(max_iter), float(tol), float(eta)
+        if max_iter < 0:
+            raise ValueError('max_iter must be >= 0, got %d' % max_iter)
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError('tol must be a finite value >= 0, got %r' % tol)
+        if not (np.isfinite(eta) and eta > 0):
+            raise ValueError('eta must be a finite value > 0, got %r' % eta)
+        dev, N = self.device, self.N
+        labels = torch.empty((B, N), device=dev, dtype=torch.int64)
+        det = dict(marginals=torch.empty((B, N), device=dev, dtype=torch.float64),
+                   value=torch.empty((B,), device=dev, dtype=torch.float64),
+                   status=torch.empty((B,), device=dev, dtype=torch.int32),
+                   iters=torch.empty((B,), device=dev, dtype=torch.int32)) if want_details else None
+        if B > 0:
+            u = unary.to(dev, torch.float32).contiguous()
+            p = pair.to(dev, torch.float32).contiguous()
+            c = caps.to(dev, torch.int32).contiguous()
+            sb = lambda t: 0 if t.shape[0] == 1 and B != 1 else t[0].numel()
+            P = _hip._ptr
+            d = det or {}
+            _hip.check(_hip.lib().fgnn_chain_budget_lp(P(u), u[0].numel(), P(p), sb(p), P(c), sb(c), B, N, self.h, max_iter, tol,
+                                                       eta, 1 if adapt else 0, P(labels), P(d.get('marginals')),
+                                                       P(d.get('value')), P(d.get('status')), P(d.get('iters')),
+                                                       _hip.stream_ptr()))
+        return (labels, det) if want_details else labels
+
+    def lp_inputs(self, family, sampled, cap=5, transition=(0, .1, .2, 1)):
+        """The (unary [B,N,2], pair, caps) of models ``sample(..., family)`` drew, rebuilt on the device from its output tuple:
+        unary = node feature transposed; pair = the pws feature's to-right link ([B,N-1,4]) or the shared ``transition``; caps = the
+        hop feature's one-hot at position w + h/2 ([B,N-h+1]) or ``cap``."""
+        N, h, dev = self.N, self.h, self.device
+        unary = sampled[0][:, :, :, 0].transpose(1, 2)
+        if family == 'raw':
+            pair = torch.tensor([float(v) for v in transition], dtype=torch.float32, device=dev).expand(N - 1, 4)
+        else:
+            pair = sampled[1][:, :, :N - 1, 0].transpose(1, 2)
+        if family == 'hops':
+            caps = sampled[2][:, :, h // 2:h // 2 + N - h + 1, 0].argmax(1).to(torch.int32)
+        else:
+            caps = int(cap)
+        return unary, pair, caps
+
+    def sample(self, B, family='hops', seed=0, step=0, cap=5, transition=(0, .1, .2, 1), want_objective=False, lp_label=False):
         """One training batch of B random models, drawn in the kernel from (seed, step) (Philox4x32-10; a training loop passes its
         step), in the tuple order the reference's ``RandomPGMData`` yields for ``family``:
           hops: (node_feature [B,2,N,1], pws [B,4,N,1], hops [B,h,N,1], label [B,N])   RandomPGMHop (per-position caps)
           pws:  (node_feature, pws, label)                                             RandomPGMPw (every window ``cap``)
           raw:  (node_feature, label)                                                  RandomPGM (link table ``transition``)
-        Features f32, labels int64 = the exact MAP.  ``cap`` >= h gives the NoHop variants.  With want_objective the MAP
-        objective [B] f64 is appended."""
+        Features f32, labels int64 = the exact MAP.  ``cap`` >= h gives the NoHop variants.  With lp_label the LP-relaxation label
+        [B,N] int64 of ``solve_lp`` at its defaults follows the MAP label (the reference's (..., assign, assign1)); with
+        want_objective the MAP objective [B] f64 is appended last."""
         if family not in FAMILIES:
             raise ValueError('family must be one of %s, got %r' % (sorted(FAMILIES), family))
         B = int(B)
@@ -122,9 +178,12 @@ class PgmDataPath:
                                                   int(cap), ctypes.cast(trans, ctypes.c_void_p), P(node), P(pws), P(hops),
                                                   P(label), P(obj), _hip.stream_ptr()))
         out = (node, pws, hops, label) if fam == 2 else (node, pws, label) if fam == 1 else (node, label)
+        if lp_label:
+            out = out + (self.solve_lp(*self.lp_inputs(family, out, cap, transition)),)
         return out + (obj,) if want_objective else out
 
-    def write_reference_dataset(self, path, family, size, seed, step=0, batch=4096, cap=5, transition=(0, .1, .2, 1)):
+    def write_reference_dataset(self, path, family, size, seed, step=0, batch=4096, cap=5, transition=(0, .1, .2, 1),
+                                lp_label=False):
         """Write ``size`` items of ``family`` as the reference's pickle stream (data_generate/generate_random_pgm.py: one
         ``pickle.dump`` per item), readable by ``RandomPGMData(path, family, size)`` and so by an unchanged
         ``train_syn_*.py --train_path``.  Items come from ``sample(batch, family, seed, step + k)`` for k = 0, 1, ..., so item i of
@@ -132,17 +191,22 @@ class PgmDataPath:
         unexpanded: hops (node_feature [2,N], pws [4,N,1], hop feature [h,N,1] f32, assign [N], assign1 [N] int64), pws
         (node_feature, pws, assign, assign1), raw (node_feature, assign, assign1).
 
-        ``assign`` is the exact MAP.  ``assign1``, the reference's label from AD3's LP relaxation (``solve(branch_and_bound=False)``),
-        is NOT produced: it is -1 everywhere, so the scripts' ``lp_acc`` reads 0."""
+        ``assign`` is the exact MAP.  ``assign1`` is the reference's label from AD3's LP relaxation (``solve(branch_and_bound=False)``):
+        with lp_label, ``solve_lp``'s label at its defaults (the same LP, solved from AD3's start with its defaults; where the LP
+        optimum is not unique or the iteration cap is reached it may differ from what AD3 would return); without, it is -1
+        everywhere and the scripts' ``lp_acc`` reads 0."""
         size, batch = int(size), max(1, int(batch))
         with open(path, 'wb') as f:
             k = 0
             while k * batch < size:
                 n = min(batch, size - k * batch)
-                out = [t.cpu().numpy() for t in self.sample(n, family, seed, step + k, cap, transition)]
+                out = [t.cpu().numpy() for t in self.sample(n, family, seed, step + k, cap, transition, lp_label=lp_label)]
+                if lp_label:
+                    lp = out.pop()
+                else:
+                    lp = np.full((n, self.N), -1, np.int64)
                 label = out[-1]
                 feats = [np.ascontiguousarray(out[0][:, :, :, 0])] + out[1:-1]                  # node_feature [2,N]; pws / hops keep their [.., N, 1]
-                lp = np.full((self.N,), -1, np.int64)
                 for i in range(n):
-                    pickle.dump(tuple(a[i] for a in feats) + (label[i], lp.copy()), f)
+                    pickle.dump(tuple(a[i] for a in feats) + (label[i], lp[i].copy()), f)
                 k += 1

@@ -605,6 +605,26 @@ int64_t fgnn_chain_budget_map_lds_bytes(int32_t N, int32_t h);
 int fgnn_pgm_sample_rng(int32_t family, uint64_t seed, uint64_t offset, int64_t B, int32_t N, int32_t h, int32_t cap,
                         const float* transition, float* node, float* pws, float* hops, int64_t* labels, double* objective,
                         fgnn_stream_t stream);
+/* The LP relaxation of the same models (csrc/pgm_lp.hip): the reference's second label, `assign1` = argmax of AD3's LP posteriors
+ * (`g.solve(branch_and_bound=False)`, random_pgm_hop.py:119-125 and the other random_pgm*.py).
+ *
+ * fgnn_chain_budget_lp      same inputs and layouts as fgnn_chain_budget_map.  AD3-style ADMM over the local polytope (one link
+ *                           factor per link, one budget factor per window with cap < h), one wave64 per sample, f64: start z = 1/2,
+ *                           multipliers 0, step `eta` (> 0, finite), residual balancing every 50th iteration when `adapt` != 0,
+ *                           stop when the primal and dual RMS residuals are both below `tol` (>= 0, finite) or after `max_iter`
+ *                           (>= 0) iterations; the reference's call is max_iter 1000, tol 1e-6, eta 0.1, adapt 1.  Writes labels
+ *                           [B][N] int64 (z_i > 0.5, ties to 0) and, each where not NULL, marginals [B][N] f64 (z), value [B] f64
+ *                           (the LP objective at z), status [B] int32 (0 integral, 1 fractional, 2 infeasible: a cap < 0, labels 0,
+ *                           value -inf; 3 iteration cap reached) and iters [B] int32.  Shapes outside the family:
+ *                           FGNN_EUNSUPPORTED; null pointers, negative strides, bad max_iter / tol / eta: FGNN_EINVAL, all before any
+ *                           launch.  B = 0 is a no-op.
+ * fgnn_chain_budget_lp_lds_bytes  its per-sample LDS footprint, -1 outside 2 <= h <= 13, N >= h, 160 KiB (message in
+ *                           fgnn_last_error).
+ */
+int fgnn_chain_budget_lp(const float* unary, int64_t unary_sb, const float* pair, int64_t pair_sb, const int32_t* caps,
+                         int64_t caps_sb, int64_t B, int32_t N, int32_t h, int32_t max_iter, double tol, double eta, int32_t adapt,
+                         int64_t* labels, double* marginals, double* value, int32_t* status, int32_t* iters, fgnn_stream_t stream);
+int64_t fgnn_chain_budget_lp_lds_bytes(int32_t N, int32_t h);
 
 const char* fgnn_last_error(void);
 /* Name (as rocprofv3 prints it) of the kernel the calling thread's last forward/backward dispatched to. */
@@ -615,8 +635,8 @@ const char* fgnn_last_kernel(void);
  * ldpc_channel_features_rng, backward_reduces_getype, desc.reserved = in-degree | GETYPE_REDUCED); 5: fgnn_block_tail_*;
  * 6: fgnn_block_head_backward.  11: fgnn_mpconv_block_forward_rows.  12: fgnn_block_tail_backward_moments,
  * fgnn_block_tail_wgrad_finish, fgnn_block_tail_moments_bytes.  14: fgnn_chain_budget_map, fgnn_chain_budget_map_lds_bytes,
- * fgnn_pgm_sample_rng. */
-#define FGNN_ABI_VERSION 14
+ * fgnn_pgm_sample_rng.  15: fgnn_chain_budget_lp, fgnn_chain_budget_lp_lds_bytes. */
+#define FGNN_ABI_VERSION 15
 /* Arithmetic of the f32 synthetic-PGM operator's BACKWARD (16 edge types, ORIG_WITH_NEIGHBOR / ORIG_WITH_DIFF, 64 -> 64, max: the
  * autograd of /root/reference/lib/model/mpnn/mp_nn.py:136-175 as train_syn_*.py reaches it): 2 (default) = every f32 operand of the three
  * GEMMs as two bf16 pieces on the bf16 matrix cores (gradients within 5e-6 of the exact kernel's), 3 = three pieces (4e-7), 0 = f32 matrix
