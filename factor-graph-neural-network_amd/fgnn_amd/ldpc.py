@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from .mpnn.assemblies import FactorNN
-from .mpnn.pointwise import cast_cached, bn_spec, _RowLinear, _BatchNormAct
+from .mpnn.pointwise import cast_cached, BnHandoff, _RowLinear, _BatchNormAct
 from .edge_mlp import EdgeMLP
 from .tables import LdpcGraph
 
@@ -50,14 +50,12 @@ class LDPCModel(torch.nn.Module):
         modules, all of them alone on the GPU at the step's turn-around (profiles/r05/train_step_sequence.csv; round 5 also tried
         them on the side stream: slower, the joins cost more than the overlap buys)."""
         reg = self.nhop_regressor
-        spec = bn_spec(reg[1]) if (_FAST_REGRESSOR and hop.is_cuda and hop.dtype == torch.bfloat16 and self.training
-                                   and torch.is_grad_enabled() and hop.shape[0] > 1) else None
-        if spec is None:
+        handoff = BnHandoff.of(reg[1]) if (_FAST_REGRESSOR and hop.is_cuda and hop.dtype == torch.bfloat16 and self.training
+                                           and torch.is_grad_enabled() and hop.shape[0] > 1) else None
+        if handoff is None:
             return reg(hop.float())
-        bn = reg[1]
-        z = _RowLinear.apply(hop.contiguous(), reg[0].weight, reg[0].bias, spec)
-        a = _BatchNormAct.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, 0.0, None,
-                                bn.num_batches_tracked, None, None, (1, 1, 1), 0)
+        z = _RowLinear.apply(hop.contiguous(), reg[0].weight, reg[0].bias, handoff)
+        a = _BatchNormAct.apply(z, reg[1].weight, reg[1].bias, handoff, 0.0)
         a = torch.relu(_RowLinear.apply(a, reg[3].weight, reg[3].bias))
         return torch.relu(_RowLinear.apply(a, reg[5].weight, reg[5].bias)).float()
 

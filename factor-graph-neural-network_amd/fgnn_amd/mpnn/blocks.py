@@ -10,7 +10,7 @@ import torch
 
 from .message_op import base_mp_nn, mp_conv_type, mp_conv_v2
 from .. import ops
-from .pointwise import BatchNormAct2d, NodeInstanceNorm, PointwiseConv2d, as_addends, refresh_in_place
+from .pointwise import BatchNormAct2d, BnHandoff, NodeInstanceNorm, PointwiseConv2d, as_addends, refresh_in_place
 from .pointwise import state_epoch as pointwise_state_epoch
 
 
@@ -41,7 +41,8 @@ class iid_mapping_bn(torch.nn.Module):
         self.main = _conv_norm_act(nin, nout, BatchNormAct2d(nout, slope=0.0), torch.nn.Identity(), bias)
 
     def forward(self, x):
-        return self.main[1](self.main[0](x, bn=self.main[1]))
+        handoff = BnHandoff.of(self.main[1])
+        return self.main[1](self.main[0](x, bn=handoff), handoff=handoff)
 
 
 class iid_mapping_in(torch.nn.Module):
@@ -150,18 +151,18 @@ class _BlockHead(torch.autograd.Function):
     in the input-gradient GEMM.  gz1 is still stored once for conv1's weight-gradient kernel, which is parked like every other."""
 
     @staticmethod
-    def forward(ctx, rows, weight, bias, bn_w, bn_b, rm, rv, nbt, momentum, eps, slope, box=None):
+    def forward(ctx, rows, weight, bias, bn_w, bn_b, handoff, slope, box=None):
+        """``handoff``: BatchNorm1's ``BnHandoff``; ``bn_w`` / ``bn_b`` are its gamma / beta as arguments of their own, for autograd."""
         ctx.box = box                   # the ops.FanBox of the state `rows` views: the backward deposits (gz1, W1) there instead of forming gx
         from .. import _hip
         from . import pointwise
         L = _hip.lib()
         P = _hip._ptr
-        spec = (bn_w, bn_b, rm, rv, nbt, momentum, eps)
-        z1 = pointwise.hip_linear(rows, weight, bias, bn=spec)          # the map's last workgroup finalises BatchNorm1's statistics
+        z1 = pointwise.hip_linear(rows, weight, bias, bn=handoff)       # the map's last workgroup finalises BatchNorm1's statistics
         if z1 is None:
             raise _hip.FgnnHipError('fused block head: the 1x1 map is outside csrc/linear_fwd_b16.hip (checked by the caller)')
         R = rows.shape[0]
-        stats = pointwise.batch_stats(z1, spec)                       # [4, 64] mean, invstd, scale, shift
+        stats = handoff.batch_stats(z1)                               # [4, 64] mean, invstd, scale, shift
         a1 = torch.empty_like(z1)
         ops.timed('bn_apply (forward)', 2 * z1.numel() * 2, lambda: _hip.check(L.fgnn_bn_apply(
             P(z1), P(a1), R, 64, _hip.BF16, P(stats[2]), P(stats[3]), slope, None, None, None, None, _hip.stream_ptr())))
@@ -223,8 +224,7 @@ class _BlockHead(torch.autograd.Function):
                 if gx is None:
                     gx = gz1 @ pointwise.cast_cached(pW._base if pW._base is not None else pW, gz1.dtype).view(weight.shape)
         return (gx if ctx.needs_input_grad[0] else None, None if s_W else gW.view(pW.shape).to(pW.dtype),
-                None if (s_bias or gbias is None) else gbias, None if s_w1 else gw1, None if s_b1 else gb1,
-                None, None, None, None, None, None, None)
+                None if (s_bias or gbias is None) else gbias, None if s_w1 else gw1, None if s_b1 else gb1, None, None, None)
 
 
 LATE_JOIN = True     # the tail asks for addends of another stream behind its statistics pass
@@ -286,10 +286,12 @@ class _BlockTail(torch.autograd.Function):
     operator's epilogue did not bring them), backward = reduce + grad + the 64-channel BatchNorm's apply."""
 
     @staticmethod
-    def forward(ctx, e, w2, b2, slope2, slope3, momentum2, eps2, momentum3, eps3, W2, bias2, w3, b3, rm2, rv2, nbt2, rm3, rv3,
-                nbt3, population, add0=None, add1=None, add2=None, periods=(1, 1, 1)):
-        """``population``: rows the batch statistics stand for in the running variances (0 = R; R * m for a per-sample vector the
-        reference broadcasts over m nodes).  ``periods``: see ``_AddendRoute``."""
+    def forward(ctx, e, w2, b2, slope2, slope3, bn2, bn3, W2, bias2, w3, b3, population, add0=None, add1=None, add2=None,
+                periods=(1, 1, 1)):
+        """``bn2`` / ``bn3``: the ``BnHandoff`` of BatchNorm2 (the operator's epilogue may have finalised it) and of BatchNorm3;
+        their gamma / beta are ``w2``, ``b2`` / ``w3``, ``b3``, arguments of their own for autograd.  ``population``: rows the batch
+        statistics stand for in the running variances (0 = R; R * m for a per-sample vector the reference broadcasts over m nodes).
+        ``periods``: see ``_AddendRoute``."""
         import ctypes
         from .. import _hip
         from . import pointwise
@@ -297,8 +299,8 @@ class _BlockTail(torch.autograd.Function):
         P = _hip._ptr
         R, Cout = e.shape[0], W2.shape[0]
         dev = e.device
-        # BatchNorm2: the operator's epilogue finalised it (pending), else one reducing launch
-        st2 = pointwise.batch_stats(e, (w2, b2, rm2, rv2, nbt2, momentum2, eps2), population)         # mean, invstd, scale, shift
+        # BatchNorm2: the operator's epilogue finalised it, else one reducing launch
+        st2 = bn2.batch_stats(e, population)                          # mean, invstd, scale, shift
         ws = ops._workspace(dev, int(L.fgnn_bn_workspace_bytes(R, Cout)))
         fold = ops._fold_scratch(dev)
         # a2 is stored only for a weight-gradient KERNEL; with the moments form (TAIL_WGRAD_MOMENTS) the backward recomputes it
@@ -306,7 +308,7 @@ class _BlockTail(torch.autograd.Function):
         W2c = W2.detach()
         bias2c = None if bias2 is None else bias2.detach()
         flops = 2 * R * 64 * Cout
-        st3, fin3 = pointwise.make_final((w3, b3, rm3, rv3, nbt3, momentum3, eps3), Cout, dev, R, population)
+        st3, fin3 = bn3.final(Cout, dev, R, population)
         ops.timed('block_tail_stats_kernel', 2 * R * 64, lambda: _hip.check(L.fgnn_block_tail_stats(
             P(e), P(st2[2]), P(st2[3]), slope2, P(W2c), P(bias2c), R, Cout, P(ws), fin3, P(fold), _hip.stream_ptr())), nflops=flops)
         out = torch.empty((R, Cout), device=dev, dtype=e.dtype)
@@ -408,10 +410,9 @@ class _BlockTail(torch.autograd.Function):
         for i in range(3):
             if ha[i]:
                 gadd[i] = gout if ctx.periods[i] == 1 else pointwise.node_sum(gout, ctx.periods[i])
-        return (ge, None if s_w2 else gw2, None if s_b2 else gb2, None, None, None, None, None, None,
+        return (ge, None if s_w2 else gw2, None if s_b2 else gb2, None, None, None, None,
                 None if s_W2 else gW2.view(pW2.shape).to(pW2.dtype), None if (s_bias2 or gbias2 is None) else gbias2,
-                None if s_w3 else gw3, None if s_b3 else gb3, None, None, None, None, None, None, None,
-                gadd[0], gadd[1], gadd[2], None)
+                None if s_w3 else gw3, None if s_b3 else gb3, None, *gadd, None)
 
 
 class mp_conv_residual(base_mp_nn):
@@ -587,15 +588,17 @@ class mp_conv_residual(base_mp_nn):
         fuse = self.training            # BatchNorm statistics ride in the 1x1 map's epilogue when training
         h = self._fused_train_head(node_feature)
         if h is None:
-            h = self.conv1[1](self.conv1[0](node_feature, bn=self.conv1[1] if fuse else None))
+            handoff = BnHandoff.of(self.conv1[1]) if fuse else None
+            h = self.conv1[1](self.conv1[0](node_feature, bn=handoff), handoff=handoff)
         y = self._fused_train_tail(h, nn_idx, etype, addend, mult)
         if y is not None:
             return y + node_feature if self.with_residual else y
         h = self.mp_conv(h, nn_idx, etype, population_mult=mult)
-        h = self.conv2[0](h, bn=self.conv2[1] if (fuse and mult == 1) else None)
+        handoff = BnHandoff.of(self.conv2[1]) if (fuse and mult == 1) else None
+        h = self.conv2[0](h, bn=handoff)
         if callable(addend):            # produced on another stream: asked for (and waited on) only where it is consumed
             addend = addend()
-        h = self.conv2[1](h, addend=addend, population_mult=mult)
+        h = self.conv2[1](h, addend=addend, population_mult=mult, handoff=handoff)
         return h + node_feature if self.with_residual else h
 
     def _fused_train_head(self, x):
@@ -603,10 +606,10 @@ class mp_conv_residual(base_mp_nn):
         backward).  None = not this family."""
         from .. import _hip
         conv, bn = self.conv1[0], self.conv1[1]
+        handoff = BnHandoff.of(bn) if isinstance(bn, BatchNormAct2d) else None
         if not (FUSE_TRAIN_HEAD and self.training and torch.is_grad_enabled() and x.is_cuda and isinstance(conv, PointwiseConv2d)
-                and isinstance(bn, BatchNormAct2d) and bn.training and conv.out_channels == 64 and conv.in_channels in _HEAD_WIDTHS
-                and bn.track_running_stats and bn.affine and bn.momentum is not None and conv.weight.dtype == torch.float32
-                and bn.weight.dtype == torch.float32 and (x.requires_grad or conv.weight.requires_grad)):
+                and handoff is not None and conv.out_channels == 64 and conv.in_channels in _HEAD_WIDTHS
+                and conv.weight.dtype == torch.float32 and (x.requires_grad or conv.weight.requires_grad)):
             return None
         B, C, H, W = x.shape
         rows = x.permute(0, 2, 3, 1)
@@ -619,8 +622,7 @@ class mp_conv_residual(base_mp_nn):
         R = B * H * W
         if rows.dtype != torch.bfloat16 or R < 2 or not L.fgnn_block_tail_partials(R, C) or not L.fgnn_linear_forward_partials(R, C, 64):
             return None
-        a1 = _BlockHead.apply(rows, conv.weight.view(64, C), conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                              bn.num_batches_tracked, bn.momentum, bn.eps, float(bn.slope), ops.fan_box(x))
+        a1 = _BlockHead.apply(rows, conv.weight.view(64, C), conv.bias, bn.weight, bn.bias, handoff, float(bn.slope), ops.fan_box(x))
         return a1.view(B, H, W, 64).permute(0, 3, 1, 2)
 
     def _fused_train_tail(self, h, nn_idx, etype, addend, mult=1):
@@ -631,24 +633,23 @@ class mp_conv_residual(base_mp_nn):
         from .message_op import _EXT_CODE
         mp = self.mp_conv
         bn2, conv2, bn3 = mp.bn, self.conv2[0], self.conv2[1]
+        hand2, hand3 = (BnHandoff.of(b) if isinstance(b, BatchNormAct2d) else None for b in (bn2, bn3))
         if not (FUSE_TRAIN_TAIL and self.training and torch.is_grad_enabled() and h.is_cuda and h.dtype == torch.bfloat16
                 and mp.nou == 64 and mp.extension == mp_conv_type.NO_EXTENSION      # (the operand preparation of the extension branches lives in mp_conv_v2.forward)
                 and isinstance(mp.aggregtor, str) and isinstance(mp.activation_fn, torch.nn.ReLU)
-                and isinstance(bn2, BatchNormAct2d) and bn2.training and isinstance(bn3, BatchNormAct2d) and bn3.training
+                and hand2 is not None and hand3 is not None
                 and isinstance(conv2, PointwiseConv2d) and conv2.in_channels == 64 and conv2.out_channels in (64, 128, 256)
-                and all(b.track_running_stats and b.affine and b.momentum is not None for b in (bn2, bn3))
-                and conv2.weight.dtype == torch.float32 and bn2.weight.dtype == torch.float32):
+                and conv2.weight.dtype == torch.float32):
             return None
         B, M = h.shape[0], nn_idx.shape[1]
         if B * M < 2 or not _hip.lib().fgnn_block_tail_partials(B * M, conv2.out_channels):
             return None
         from . import pointwise
         z = ops.mpconv(h, nn_idx, etype, mp.filters, mp.bias, mp.nou, mp.nedge_types, _EXT_CODE[mp.extension],
-                       _hip.AGG_CODES[mp.aggregtor], bn=pointwise.bn_spec(bn2) if mult == 1 else None)
+                       _hip.AGG_CODES[mp.aggregtor], bn=hand2 if mult == 1 else None)
         rows = z.permute(0, 2, 3, 1)
         if not rows.is_contiguous():
-            pointwise.take_pending_stats(rows)                        # (drop them: they describe another buffer)
-            rows = rows.contiguous()
+            rows = rows.contiguous()                                  # (BatchNorm2's statistics pass then forms scale / shift only)
         rows = rows.view(B * M, 64)
         Cout = conv2.out_channels
         got = {}
@@ -683,10 +684,8 @@ class mp_conv_residual(base_mp_nn):
             tail_adds = [detached, None, None]
         else:
             tail_adds = [(a.detach() if (route and a is not None) else a) for a in arows]
-        y = _BlockTail.apply(rows, bn2.weight, bn2.bias, 0.0, float(bn3.slope), bn2.momentum, bn2.eps, bn3.momentum, bn3.eps,
-                             conv2.weight.view(Cout, 64), conv2.bias, bn3.weight, bn3.bias, bn2.running_mean, bn2.running_var,
-                             bn2.num_batches_tracked, bn3.running_mean, bn3.running_var, bn3.num_batches_tracked,
-                             0 if mult == 1 else B * M * mult, *tail_adds, periods)
+        y = _BlockTail.apply(rows, bn2.weight, bn2.bias, 0.0, float(bn3.slope), hand2, hand3, conv2.weight.view(Cout, 64), conv2.bias,
+                             bn3.weight, bn3.bias, 0 if mult == 1 else B * M * mult, *tail_adds, periods)
         if route:
             pairs = [(a, q, st) for a, q, st in zip(got['arows'], got['periods'], got['streams']) if a is not None]
             y = _AddendRoute.apply(y, tuple(q for _, q, _ in pairs), tuple(st for _, _, st in pairs), *[a for a, _, _ in pairs])

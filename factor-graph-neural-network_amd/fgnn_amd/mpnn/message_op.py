@@ -128,7 +128,7 @@ class mp_conv_v2(base_mp_nn):
         # ONE source node feeding every destination through identical edges (the LDPC hyper-factor -> variables call of the plain
         # layers, factor_mpnn_sp.py:88-91): every destination receives the same message, so the operator, its BatchNorm and its ReLU
         # run on one row per sample and the result travels as a broadcast (see mp_conv_residual.forward)
-        from .pointwise import BatchNormAct2d, bn_spec
+        from .pointwise import BatchNormAct2d, BnHandoff
         M = 0
         if (population_mult == 1 and ext == _hip.EXT_NONE and addend is None and needs_grad and bn_batch_stats and plain_relu
                 and isinstance(self.bn, BatchNormAct2d) and x.shape[0] > 1):
@@ -138,14 +138,14 @@ class mp_conv_v2(base_mp_nn):
             one = x.reshape(B, 1, 1, C).permute(0, 3, 1, 2)
             return ops.broadcast_nodes(self.forward(one, nn_idx[:, :1, :], etype[:, :, :1, :], None, M), M)
         # a training-mode BatchNorm right behind the operator is finalised by the operator's own launch where it has the epilogue
-        spec = bn_spec(self.bn) if (self.bn is not None and isinstance(self.bn, BatchNormAct2d) and population_mult == 1) else None
-        z = ops.mpconv(x, nn_idx, etype, self.filters, self.bias, self.nou, self.nedge_types, ext, agg, bn=spec)
+        handoff = BnHandoff.of(self.bn) if (isinstance(self.bn, BatchNormAct2d) and population_mult == 1) else None
+        z = ops.mpconv(x, nn_idx, etype, self.filters, self.bias, self.nou, self.nedge_types, ext, agg, bn=handoff)
         if callable(addend):
             addend = addend()
         if self.bn is not None:
             if plain_relu:                      # BatchNorm + ReLU (+ addend) in one fused kernel pair
-                return self.bn(z, addend=addend, slope=0.0, population_mult=population_mult)
-            z = self.bn(z, population_mult=population_mult)
+                return self.bn(z, addend=addend, slope=0.0, population_mult=population_mult, handoff=handoff)
+            z = self.bn(z, population_mult=population_mult, handoff=handoff)
         if self.activation_fn is not None:
             z = self.activation_fn(z)
         return add_all(z, addend)

@@ -9,6 +9,7 @@ dominate the step).  ``PointwiseConv2d`` keeps Conv2d's parameters / state_dict 
 kernel reads and writes without a transpose.  Outputs are logical [B,C,N,W] with
 channels-last strides; every consumer in this package is stride-agnostic.
 """
+import dataclasses
 import weakref
 
 import torch
@@ -112,61 +113,76 @@ def cast_cached(t, dtype):
     return out
 
 
-_PENDING_STATS = None     # (rows tensor, stats [4, C], running_mean) finalised batch statistics of the last statistics-producing launch
-# A producer that takes ``bn=`` finalises the BatchNorm ITSELF: momentum applied to the running statistics, num_batches_tracked + 1.
-# When the consumer then never sees the pending statistics (they describe another buffer: a non-contiguous copy; another map ran
-# in between; the BatchNorm fell back to torch), whoever re-derives the batch statistics must NOT finalise a second time — the
-# momentum would be applied twice and the counter advance by 2 for one forward.  The running_mean buffers of such dropped
-# finalisations are remembered here until that BatchNorm's own statistics pass (or its torch fallback) has run without them.
-_ALREADY_FINAL = set()    # data_ptr() of running_mean buffers whose BatchNorm a producer finalised for the forward in flight
+@dataclasses.dataclass(eq=False)
+class BnHandoff:
+    """A training-mode BatchNorm's batch statistics on their way from the launch that produces them to the BatchNorm that uses them.
+    The caller makes one per forward and hands it to both.  A producer (``hip_linear``, ``ops.mpconv_forward_raw``) given ``bn=``
+    forms the statistics of its output and FINALISES the BatchNorm itself (momentum applied to the running statistics,
+    num_batches_tracked + 1), then records the rows it wrote and the statistics here; the consumer asks ``batch_stats``."""
+    gamma: torch.Tensor
+    beta: torch.Tensor
+    running_mean: torch.Tensor
+    running_var: torch.Tensor
+    num_batches_tracked: torch.Tensor
+    momentum: float
+    eps: float
+    rows: torch.Tensor = dataclasses.field(default=None, init=False)      # [R, C] the producer wrote ...
+    stats: torch.Tensor = dataclasses.field(default=None, init=False)     # ... and their [4, C] mean, invstd, scale, shift
 
+    @classmethod
+    def of(cls, bn):
+        """The handle of a training-mode BatchNorm module the hand-written kernels can finalise themselves, else None (eval mode, no
+        running statistics, cumulative momentum, ...)."""
+        if bn is None or not bn.training or not bn.track_running_stats or not bn.affine or bn.momentum is None:
+            return None
+        if bn.weight.dtype != torch.float32 or not bn.weight.is_cuda:
+            return None
+        return cls(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, float(bn.momentum), float(bn.eps))
 
-def _drop_pending():
-    global _PENDING_STATS
-    pend, _PENDING_STATS = _PENDING_STATS, None
-    if pend is not None and pend[2] is not None:
-        _ALREADY_FINAL.add(pend[2].data_ptr())
+    def final(self, C, device, count, population=0, running=True):
+        """(stats [4, C] f32, the fgnn_bn_final that finalises into it) for statistics over ``count`` rows standing for ``population``
+        rows of the reference's tensor (0 = count).  ``running=False``: scale / shift only, the running buffers and the counter stay."""
+        stats = torch.empty((4, C), device=device, dtype=torch.float32)
+        rm, rv, nbt = (self.running_mean, self.running_var, self.num_batches_tracked) if running else (None, None, None)
+        return stats, _hip.bn_final(stats, self.gamma.detach(), self.beta.detach(), rm, rv, nbt, self.momentum, self.eps, count,
+                                    population)
 
+    def record(self, rows, stats):
+        """A producer's launch just finalised the BatchNorm with ``stats`` [4, C], the batch statistics of ``rows`` [R, C]."""
+        note_state_change()                 # running statistics / num_batches_tracked were just updated in place
+        self.rows, self.stats = rows, stats
 
-def finalised_by_producer(running_mean):
-    """True ONCE when a producer launch already finalised the BatchNorm that owns ``running_mean`` for this forward and its
-    pending statistics were dropped: the caller forms the batch statistics again but leaves the running buffers alone."""
-    if running_mean is None or not _ALREADY_FINAL:
-        return False
-    key = running_mean.data_ptr()
-    if key in _ALREADY_FINAL:
-        _ALREADY_FINAL.discard(key)
-        return True
-    return False
-
-
-def bn_spec(bn):
-    """(gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps) of a training-mode BatchNorm module the
-    hand-written kernels can finalise themselves, else None (eval mode, no running statistics, cumulative momentum, ...)."""
-    if bn is None or not bn.training or not bn.track_running_stats or not bn.affine or bn.momentum is None:
+    def stats_for(self, rows):
+        """The producer's statistics if they describe exactly ``rows``, else None."""
+        if self.stats is not None and self.rows.data_ptr() == rows.data_ptr() and self.rows.shape == rows.shape:
+            return self.stats
         return None
-    if bn.weight.dtype != torch.float32 or not bn.weight.is_cuda:
-        return None
-    return (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, float(bn.momentum), float(bn.eps))
 
-
-def make_final(spec, C, device, count, population=0):
-    """(stats [4, C] f32 — rows mean, invstd, scale, shift —, the fgnn_bn_final describing it) for a BatchNorm ``spec`` (bn_spec) whose
-    statistics run over ``count`` rows standing for ``population`` rows of the reference's tensor (0 = count)."""
-    gamma, beta, rm, rv, nbt, momentum, eps = spec
-    stats = torch.empty((4, C), device=device, dtype=torch.float32)
-    fin = _hip.bn_final(stats, gamma.detach(), beta.detach(), rm, rv, nbt, momentum, eps, count, population)
-    return stats, fin
+    def batch_stats(self, rows, population=0):
+        """stats [4, C] of the BatchNorm over ``rows`` [R, C]: the producer's when they describe these rows, else one reducing launch
+        of csrc/bnact.hip (its last workgroup finalises).  When the producer finalised but wrote other rows (the consumer normalises
+        a contiguous copy) that launch forms scale / shift only: the batch is already counted."""
+        from .. import ops
+        stats = self.stats_for(rows)
+        if stats is not None:
+            return stats
+        L = _hip.lib()
+        R, C = rows.shape
+        stats, fin = self.final(C, rows.device, R, population, running=self.stats is None)
+        ws = ops._workspace(rows.device, int(L.fgnn_bn_workspace_bytes(R, C)))
+        fold = ops._fold_scratch(rows.device)
+        ops.timed('bn_stats (reduce + finalise)', rows.numel() * rows.element_size(), lambda: _hip.check(L.fgnn_bn_stats(
+            _hip._ptr(rows), R, C, _hip.dtype_code(rows), fin, _hip._ptr(ws), ws.numel() * 4, _hip._ptr(fold), _hip.stream_ptr())))
+        note_state_change()
+        return stats
 
 
 def hip_linear(rows, weight, bias, bn=None, transposed=False):
     """``rows @ weight.T + bias`` through csrc/linear_fwd_b16.hip (bf16 rows, f32 parameters, channel counts in
-    multiples of 64): one pass over rows and the output at HBM rate, no cast of the weights.  With ``bn`` (a ``bn_spec``
-    tuple) the launch also forms the per-channel batch statistics of the output and FINALISES that BatchNorm itself (its last
-    workgroup: csrc/fgnn_gridfold.h) — running statistics, num_batches_tracked, scale / shift; the result waits for the
-    BatchNorm that follows (``take_pending_stats``).  None = shape not handled."""
-    global _PENDING_STATS
-    _drop_pending()
+    multiples of 64): one pass over rows and the output at HBM rate, no cast of the weights.  With ``bn`` (a ``BnHandoff``) the
+    launch also forms the per-channel batch statistics of the output and FINALISES that BatchNorm itself (its last workgroup:
+    csrc/fgnn_gridfold.h) — running statistics, num_batches_tracked, scale / shift — and records them on the handle for the
+    BatchNorm that follows.  None = shape not handled."""
     if not (rows.is_cuda and rows.dtype == torch.bfloat16 and weight.dtype == torch.float32 and rows.is_contiguous()):
         return None
     R, cin = rows.shape
@@ -191,59 +207,14 @@ def hip_linear(rows, weight, bias, bn=None, transposed=False):
     if bn is not None:
         ws = ops._workspace(rows.device, int(L.fgnn_bn_workspace_bytes(R, cout)))
         fold = ops._fold_scratch(rows.device)
-        stats, fin = make_final(bn, cout, rows.device, R)
+        stats, fin = bn.final(cout, rows.device, R)
     ops.timed('linear_fwd_b16_kernel', 2 * R * (cin + cout),
               lambda: _hip.check(L.fgnn_linear_forward(_hip._ptr(rows), _hip._ptr(w), _hip._ptr(b), _hip._ptr(y), R, cin,
                                                        cout, _hip._ptr(ws), fin, _hip._ptr(fold), int(transposed), _hip.stream_ptr())),
               nflops=2 * R * cin * cout)
     if bn is not None:
-        note_state_change()                 # running statistics / num_batches_tracked were just updated in place
-        _ALREADY_FINAL.discard(bn[2].data_ptr())
-        _PENDING_STATS = (y, stats, bn[2])
+        bn.record(y, stats)
     return y
-
-
-def set_pending_stats(rows, stats, running_mean=None):
-    """A kernel just finalised the batch statistics ``stats`` [4, C] of ``rows`` ([R, C]) for the BatchNorm that follows (the one
-    that owns ``running_mean``)."""
-    global _PENDING_STATS
-    _drop_pending()
-    if running_mean is not None:
-        _ALREADY_FINAL.discard(running_mean.data_ptr())
-    _PENDING_STATS = (rows, stats, running_mean)
-
-
-def take_pending_stats(rows):
-    """The finalised statistics [4, C] waiting for exactly this tensor, else None."""
-    global _PENDING_STATS
-    pend = _PENDING_STATS
-    if pend is not None and pend[0].data_ptr() == rows.data_ptr() and pend[0].shape == rows.shape:
-        _PENDING_STATS = None
-        return pend[1]
-    _drop_pending()             # (missed: the producer's finalisation is remembered, see _ALREADY_FINAL)
-    return None
-
-
-def batch_stats(rows, spec, population=0):
-    """stats [4, C] of a training-mode BatchNorm over ``rows`` [R, C]: the producer's (take_pending_stats) when it finalised them,
-    else one reducing launch of csrc/bnact.hip (its last workgroup finalises)."""
-    from .. import ops
-    stats = take_pending_stats(rows)
-    if stats is not None:
-        return stats
-    L = _hip.lib()
-    R, C = rows.shape
-    if finalised_by_producer(spec[2]):
-        # the producing launch already applied this forward's momentum update and counted the batch, but its statistics did not
-        # reach us (they described another buffer): scale / shift only, the running buffers and the counter stay as they are
-        spec = (spec[0], spec[1], None, None, None) + tuple(spec[5:])
-    stats, fin = make_final(spec, C, rows.device, R, population)
-    ws = ops._workspace(rows.device, int(L.fgnn_bn_workspace_bytes(R, C)))
-    fold = ops._fold_scratch(rows.device)
-    ops.timed('bn_stats (reduce + finalise)', rows.numel() * rows.element_size(), lambda: _hip.check(L.fgnn_bn_stats(
-        _hip._ptr(rows), R, C, _hip.dtype_code(rows), fin, _hip._ptr(ws), ws.numel() * 4, _hip._ptr(fold), _hip.stream_ptr())))
-    note_state_change()
-    return stats
 
 
 def node_sum(g, M):
@@ -273,7 +244,7 @@ class _RowLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rows, weight, bias, bn=None, precomputed=None, box=None):
-        """``bn``: a ``bn_spec`` tuple — the training-mode BatchNorm behind the map, finalised by the map's own launch.
+        """``bn``: a ``BnHandoff`` — the training-mode BatchNorm behind the map, finalised by the map's own launch.
         ``precomputed``: the output, already formed by a fused kernel (blocks.iid_mapping_in): only the graph node is made.
         ``box``: the ``ops.FanBox`` of the state ``rows`` views — the backward deposits (gy, weight) there instead of forming
         ``gy @ weight`` (the fan-out's backward multiplies all its consumers' pairs in one launch)."""
@@ -351,10 +322,9 @@ class PointwiseConv2d(torch.nn.Conv2d):
         super().__init__(in_channels, out_channels, 1, bias=bias)
 
     def forward(self, x, bn=None):
-        """``bn``: the BatchNormAct2d module the caller hands the result straight to.  In training mode the map's launch then forms
-        that BatchNorm's batch statistics in its epilogue and finalises them (running statistics included): the BatchNorm neither
-        re-reads the tensor for them nor launches a finaliser."""
-        bn = bn_spec(bn)
+        """``bn``: the ``BnHandoff`` of the training-mode BatchNorm the caller hands the result straight to (with the same handle).
+        The map's launch then forms that BatchNorm's batch statistics in its epilogue and finalises them (running statistics
+        included): the BatchNorm neither re-reads the tensor for them nor launches a finaliser."""
         B, C, H, W = x.shape
         rows = x.permute(0, 2, 3, 1)                    # [B,H,W,C] view; free when channels-last
         if not rows.is_contiguous():
@@ -563,15 +533,16 @@ class _BatchNormAct(torch.autograd.Function):
     """Train-mode BatchNorm + LeakyReLU(slope) on channel-fastest rows [R, C] (csrc/bnact.hip)."""
 
     @staticmethod
-    def forward(ctx, rows, weight, bias, running_mean, running_var, momentum, eps, slope, addend=None, nbt=None,
-                addend2=None, addend3=None, periods=(1, 1, 1), population=0):
-        """``periods``: an addend with period m has one row per m rows of the output (a per-sample vector broadcast over the
-        sample's m nodes).  ``population``: rows the statistics stand for in the running variance's unbiased correction (0 = R)."""
+    def forward(ctx, rows, weight, bias, handoff, slope, addend=None, addend2=None, addend3=None, periods=(1, 1, 1), population=0):
+        """``handoff``: the BatchNorm's ``BnHandoff`` (running statistics, counter, momentum, eps; the statistics of a producer in
+        front of it); ``weight`` / ``bias`` are its gamma / beta as arguments of their own, for autograd.  ``periods``: an addend
+        with period m has one row per m rows of the output (a per-sample vector broadcast over the sample's m nodes).
+        ``population``: rows the statistics stand for in the running variance's unbiased correction (0 = R)."""
         from .. import ops
         L = _hip.lib()
         R, C = rows.shape
         dt = _hip.dtype_code(rows)
-        stats = batch_stats(rows, (weight, bias, running_mean, running_var, nbt, momentum, eps), population)
+        stats = handoff.batch_stats(rows, population)
         y = torch.empty_like(rows)
         ctx.has_addend = tuple(a is not None for a in (addend, addend2, addend3))
         ctx.periods = tuple(periods)
@@ -607,10 +578,9 @@ class _BatchNormAct(torch.autograd.Function):
                       _hip._ptr(ws), ws.numel() * 4, _hip._ptr(fold), _hip.stream_ptr())))
         ga = [None, None, None]
         for i in range(3):
-            if ctx.has_addend[i] and ctx.needs_input_grad[(8, 10, 11)[i]]:
+            if ctx.has_addend[i] and ctx.needs_input_grad[5 + i]:
                 ga[i] = gy if ctx.periods[i] == 1 else node_sum(gy, ctx.periods[i])
-        return (gx, None if gw_sink is not None else gw, None if gb_sink is not None else gb,
-                None, None, None, None, None, ga[0], None, ga[1], ga[2], None, None)
+        return (gx, None if gw_sink is not None else gw, None if gb_sink is not None else gb, None, None, *ga, None, None)
 
 
 class BatchNormAct2d(torch.nn.BatchNorm2d):
@@ -631,13 +601,14 @@ class BatchNormAct2d(torch.nn.BatchNorm2d):
             return y
         return torch.nn.functional.leaky_relu(y, slope)
 
-    def forward(self, x, addend=None, slope=None, population_mult=1):
+    def forward(self, x, addend=None, slope=None, population_mult=1, handoff=None):
         """``addend`` (a tensor of the output's shape, or a list of up to three) is added AFTER the activation — the
         ``acc + block(x) (+ residual + skip)`` that follows every block in FactorNN rides in the apply kernel
         instead of being separate passes.  ``slope`` overrides the module's activation for this call (mp_conv_v2 asks its
         plain BatchNorm for the fused ReLU this way: an argument, not a toggled attribute).  ``population_mult`` = m: every row of
         ``x`` stands for m identical rows of the reference's tensor (a per-sample vector the reference broadcasts over m nodes
-        before this BatchNorm): same mean and biased variance, the running variance's unbiased correction counts m times the rows."""
+        before this BatchNorm): same mean and biased variance, the running variance's unbiased correction counts m times the rows.
+        ``handoff``: the ``BnHandoff`` the caller gave the producer of ``x`` (``PointwiseConv2d.forward``, ``ops.mpconv``)."""
         slope = self.slope if slope is None else float(slope)
         B, C, H, W = x.shape
         addends = as_addends(addend)
@@ -653,8 +624,7 @@ class BatchNormAct2d(torch.nn.BatchNorm2d):
         if not ok or (not self.training and wants_grad):
             if population_mult != 1 and self.training:
                 raise _hip.FgnnHipError('BatchNormAct2d: population_mult needs the HIP path (a ROCm tensor, running statistics)')
-            _drop_pending()
-            if self.training and finalised_by_producer(self.running_mean):
+            if self.training and handoff is not None and handoff.stats is not None:
                 # the map in front already finalised this BatchNorm (momentum applied, batch counted): batch statistics only here
                 y = torch.nn.functional.batch_norm(x, None, None, self.weight, self.bias, True, 0.0, self.eps)
                 return add_all(self._activate(y, slope), addends)
@@ -672,9 +642,11 @@ class BatchNormAct2d(torch.nn.BatchNorm2d):
             arows[i] = ar.view(-1, C)
         periods = tuple((periods + [1, 1, 1])[:3])
         if self.training:                               # num_batches_tracked += 1 rides in the statistics finaliser
-            y = _BatchNormAct.apply(rows, self.weight, self.bias, self.running_mean, self.running_var,
-                                    self.momentum, self.eps, slope, arows[0], self.num_batches_tracked,
-                                    arows[1], arows[2], periods, 0 if population_mult == 1 else B * H * W * population_mult)
+            if handoff is None:
+                handoff = BnHandoff(self.weight, self.bias, self.running_mean, self.running_var, self.num_batches_tracked,
+                                    self.momentum, self.eps)
+            y = _BatchNormAct.apply(rows, self.weight, self.bias, handoff, slope, *arows, periods,
+                                    0 if population_mult == 1 else B * H * W * population_mult)
         else:                                           # eval: folded affine + activation in one pass
             scale, shift = self._folded()
             y = torch.empty_like(rows)

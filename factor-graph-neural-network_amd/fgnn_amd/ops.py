@@ -526,9 +526,9 @@ def backward_tables(nn_idx, d):
 
 def mpconv_forward_raw(x, nn_idx, etype, filters, bias, nou, net, ext, agg, *,
                        post_scale=None, post_shift=None, relu=False, want_argmax=False, bn=None, addends=None):
-    """One launch of fgnn_mpconv_forward.  Returns (y, argmax-or-None).  ``bn`` (a ``pointwise.bn_spec`` tuple: the training-mode
+    """One launch of fgnn_mpconv_forward.  Returns (y, argmax-or-None).  ``bn`` (the ``pointwise.BnHandoff`` of the training-mode
     BatchNorm behind the operator): where the shape has a statistics epilogue, the launch also forms the batch statistics of y,
-    finalises that BatchNorm in its last workgroup and announces the result to it (pointwise.set_pending_stats)."""
+    finalises that BatchNorm in its last workgroup and records the result on the handle."""
     _require_device(x, nn_idx, etype, filters, bias)
     _check_shapes(x, nn_idx, etype, filters, nou, net, ext)
     nn_idx = shared_graph_view(nn_idx)
@@ -551,16 +551,14 @@ def mpconv_forward_raw(x, nn_idx, etype, filters, bias, nou, net, ext, agg, *,
     if bn is not None and STATS_EPILOGUE and post_scale is None and not relu:
         npart = int(L.fgnn_mpconv_forward_stats_partials(ctypes.byref(d)))
     if npart > 0:
-        from .mpnn import pointwise
         R = x.shape[0] * M
         ws = _workspace(x.device, int(L.fgnn_bn_workspace_bytes(R, nou)))
-        stats, fin = pointwise.make_final(bn, nou, x.device, R)
+        stats, fin = bn.final(nou, x.device, R)
         fold = _fold_scratch(x.device)
         _launch('fwd', d, nbytes, lambda: _hip.check(L.fgnn_mpconv_forward_stats(
             ctypes.byref(d), _hip._ptr(x), _hip._ptr(nn_idx), _hip._ptr(etype), _hip._ptr(filters),
             _hip._ptr(bias), _hip._ptr(y), _hip._ptr(amax), _hip._ptr(ws), fin, _hip._ptr(fold), _hip.stream_ptr())))
-        pointwise.note_state_change()
-        pointwise.set_pending_stats(y.permute(0, 2, 3, 1).reshape(R, nou), stats, bn[2])
+        bn.record(y.permute(0, 2, 3, 1).reshape(R, nou), stats)
         return y, amax
     if addends:
         # inference: the caller's running sums ride in the kernel's epilogue where it has one for them (``addends``: up to three

@@ -104,9 +104,10 @@ def syn_edge_models(hi_ef):
 
 
 def bn_spec_for(C, dev, seed=0):
-    """A ``pointwise.bn_spec`` tuple (gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps) with fresh buffers:
+    """A ``pointwise.BnHandoff`` with fresh buffers (gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps):
     what a statistics-producing launch needs to finalise the BatchNorm behind it."""
     import torch
+    from fgnn_amd.mpnn.pointwise import BnHandoff
     g = torch.Generator().manual_seed(seed)
-    return ((torch.rand(C, generator=g) + 0.5).to(dev), (torch.randn(C, generator=g) * 0.3).to(dev), torch.zeros(C, device=dev),
-            torch.ones(C, device=dev), torch.zeros((), device=dev, dtype=torch.int64), 0.1, 1e-5)
+    return BnHandoff((torch.rand(C, generator=g) + 0.5).to(dev), (torch.randn(C, generator=g) * 0.3).to(dev),
+                     torch.zeros(C, device=dev), torch.ones(C, device=dev), torch.zeros((), device=dev, dtype=torch.int64), 0.1, 1e-5)

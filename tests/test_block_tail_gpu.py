@@ -447,8 +447,8 @@ def _parity_block(dev, seed=3):
 
 def test_dropped_producer_statistics_do_not_finalise_a_batchnorm_twice(dev):
     """Round-5 advisory: a statistics-producing launch given ``bn=`` finalises that BatchNorm itself (momentum, counter).  When the
-    consumer cannot use the pending statistics — here the operator's output is NOT channel-fastest (a plain-contiguous input), so
-    the fused tail copies the rows and drops them — the second statistics pass must leave the running buffers and
+    consumer cannot use the producer's statistics — here the operator's output is NOT channel-fastest (a plain-contiguous input), so
+    the fused tail normalises a copy of the rows — the second statistics pass must leave the running buffers and
     num_batches_tracked alone: ONE momentum update and ONE count per forward, the same as for the channel-fastest input."""
     B, N, M, k = 40, 96, 48, 6
     g = torch.Generator().manual_seed(11)
@@ -473,6 +473,35 @@ def test_dropped_producer_statistics_do_not_finalise_a_batchnorm_twice(dev):
     assert H.rel_err(ya, yb) <= 2.0 ** -6
     for n in sa:
         assert H.rel_err(sa[n], sb[n]) <= 2e-3, n
+
+
+def test_an_aborted_forward_leaves_the_next_forwards_statistics_update_alone(dev):
+    """A bf16 forward of `iid_mapping_bn` that raises right after the map (whose launch finalised the BatchNorm) must not cost the
+    next forward its update: the f32 forward that follows (no statistics epilogue) counts its batch once and moves the running
+    statistics one momentum step toward that batch's statistics.  (The statistics once travelled through a process-wide mailbox;
+    the aborted forward's posting made the next statistics pass of that BatchNorm skip its update.)"""
+    from fgnn_amd.mpnn.blocks import iid_mapping_bn
+    B, N = 40, 96
+    g = torch.Generator().manual_seed(13)
+    x = (torch.randn(B, N, 1, 64, generator=g) + 0.5).to(dev).permute(0, 3, 1, 2)
+    m = iid_mapping_bn(64, 64).to(dev).train()
+    conv, bn = m.main[0], m.main[1]
+
+    def abort(*_):
+        raise RuntimeError('forward aborted by a hook')
+    hook = conv.register_forward_hook(abort)
+    with pytest.raises(RuntimeError, match='aborted'), torch.autocast('cuda', dtype=torch.bfloat16):
+        m(x)
+    hook.remove()
+    assert int(bn.num_batches_tracked) == 1                 # the map's launch finalised the BatchNorm of the aborted forward
+    rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
+    m(x)
+    assert int(bn.num_batches_tracked) == 2
+    with torch.no_grad():
+        z = torch.nn.functional.linear(x.permute(0, 2, 3, 1).reshape(B * N, 64), conv.weight.view(64, 64), conv.bias).double()
+    mom = bn.momentum
+    assert H.rel_err(bn.running_mean, (1 - mom) * rm0.double() + mom * z.mean(0)) <= 1e-4
+    assert H.rel_err(bn.running_var, (1 - mom) * rv0.double() + mom * z.var(0, unbiased=True)) <= 1e-4
 
 
 def test_training_block_takes_a_bare_tensor_addend(dev):

@@ -443,7 +443,7 @@ def test_linear_forward_with_fused_batch_statistics(cin, cout, rows, dev):
     (b) conv -> BatchNorm+LeakyReLU with the fused statistics against the same modules with the statistics pass
     (identical up to computing mean / variance from the unrounded f32 accumulators)."""
     from fgnn_amd.mpnn import PointwiseConv2d
-    from fgnn_amd.mpnn.pointwise import BatchNormAct2d
+    from fgnn_amd.mpnn.pointwise import BatchNormAct2d, BnHandoff
     B, N = rows
     g = torch.Generator().manual_seed(cin + 7 * cout + N)
     x = torch.randn(B, cin, N, 1, generator=g).bfloat16().to(dev).contiguous(memory_format=torch.channels_last)
@@ -459,7 +459,8 @@ def test_linear_forward_with_fused_batch_statistics(cin, cout, rows, dev):
     bn_b.load_state_dict(bn_a.state_dict())
     xa = x.detach().clone().requires_grad_(True)
     xb = x.detach().clone().requires_grad_(True)
-    ya = bn_a(conv(xa, bn=bn_a))                         # statistics from the GEMM epilogue, finalised by the GEMM's last workgroup
+    h = BnHandoff.of(bn_a)
+    ya = bn_a(conv(xa, bn=h), handoff=h)                 # statistics from the GEMM epilogue, finalised by the GEMM's last workgroup
     yb = bn_b(conv(xb))                                  # statistics pass over the bf16 output
     assert H.rel_err(ya.float(), yb.float()) <= 2.0 ** -6
     assert H.rel_err(bn_a.running_mean, bn_b.running_mean) <= 1e-3

@@ -149,13 +149,12 @@ def test_ws_forward_is_bit_reproducible_run_to_run(shape, dev, finaliser_mode):
     x, idx, et, W, bias, g = _problem(shape, B, dev, seed=B)
     xd, idxd, etd = _dev_views(x, idx, et, dev)
     Wd, bd = W.to(dev), bias.to(dev)
-    from fgnn_amd.mpnn import pointwise
     for stats in (True, False):
         first = None
         spec = H.bn_spec_for(nou, dev) if stats else None
         for r in range(60):
             y, am = ops.mpconv_forward_raw(xd, idxd, etd, Wd, bd, nou, 4, 0, _hip.AGG_MAX, want_argmax=True, bn=spec)
-            st = pointwise.take_pending_stats(y.permute(0, 2, 3, 1).reshape(B * M, nou)) if stats else None
+            st = spec.stats_for(y.permute(0, 2, 3, 1).reshape(B * M, nou)) if stats else None
             assert (st is not None) == stats
             if first is None:
                 first = (y.clone(), am.clone(), None if st is None else st.clone())
@@ -165,13 +164,13 @@ def test_ws_forward_is_bit_reproducible_run_to_run(shape, dev, finaliser_mode):
                     rows = y.permute(0, 2, 3, 1).reshape(B * M, nou).double()
                     mean, var = rows.mean(0), rows.var(0, unbiased=False)
                     assert H.rel_err(st[0], mean) <= 1e-5 and H.rel_err(st[1], torch.rsqrt(var + 1e-5)) <= 1e-5
-                    assert H.rel_err(st[2], spec[0].double() * torch.rsqrt(var + 1e-5)) <= 1e-5
+                    assert H.rel_err(st[2], spec.gamma.double() * torch.rsqrt(var + 1e-5)) <= 1e-5
             else:
                 assert torch.equal(y, first[0]) and torch.equal(am, first[1]), 'launch %d differs from launch 0' % r
                 if stats:            # ... whichever workgroup arrived last: bit-identical statistics
                     assert torch.equal(st, first[2]), 'statistics of launch %d differ from launch 0' % r
         if stats:
-            assert int(spec[4]) == 60 and int(ops._fold_scratch(dev)[:65].abs().sum()) == 0
+            assert int(spec.num_batches_tracked) == 60 and int(ops._fold_scratch(dev)[:65].abs().sum()) == 0
 
 
 def _regular_table(N, M, k, g):

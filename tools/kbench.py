@@ -10,6 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'factor-graph-neural-network_amd'))
 import torch  # noqa: E402
 from fgnn_amd import _hip, ops  # noqa: E402
+from fgnn_amd.mpnn import pointwise  # noqa: E402
 
 SHAPES = [  # (name, nin, nou, net, N, M, k[, extension, aggregator])
     ('parity V->F 64->64', 64, 64, 4, 96, 48, 6),
@@ -92,8 +93,8 @@ def main():
 
         spec = None
         if a.stats:     # the BatchNorm behind the operator, finalised by the operator's own launch
-            spec = (torch.ones(nou, device=dev), torch.zeros(nou, device=dev), torch.zeros(nou, device=dev), torch.ones(nou, device=dev),
-                    torch.zeros((), device=dev, dtype=torch.int64), 0.1, 1e-5)
+            spec = pointwise.BnHandoff(torch.ones(nou, device=dev), torch.zeros(nou, device=dev), torch.zeros(nou, device=dev),
+                                       torch.ones(nou, device=dev), torch.zeros((), device=dev, dtype=torch.int64), 0.1, 1e-5)
 
         def fwd():
             turn[0] = (turn[0] + 1) % K
