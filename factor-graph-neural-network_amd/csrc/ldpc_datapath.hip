@@ -6,6 +6,7 @@
 //                                                        `t2y`, MNC_py.cpp:86-102
 //   model inputs      node / hop / edge features gathered from y along the code's incidence lists
 //                                                        lib/data/ldpc_dataset.py:92-106,222-236
+//                     (or from a stored received word: `Codes.__getitem__`, ldpc_dataset.py:141-156)
 //
 // The reference does this per codeword on the host (a pybind11 call per item, numpy takes, a DataLoader); at
 // B = 4096 codewords per step per GPU that is the input bottleneck.  Here a batch is two launches of byte / gather
@@ -67,7 +68,34 @@ __device__ __forceinline__ float ld_normal(unsigned a, unsigned b) {
 }
 
 
-// One workgroup per codeword: y into LDS, then every output array is written by flat index (coalesced).
+// The gather stage shared by both feature kernels: word b's received values ys [nvar] (in LDS) -> node [2][nvar] (ys, snr[n * snr_sn]),
+// hop [dc][nchk], ef_f2v [dc+1][nvar][dv], ef_v2f [dc+1][nchk][dc], every output array written by flat index (coalesced).
+template <typename T>
+__device__ __forceinline__ void ld_gather_features(const float* ys, const float* snr, int64_t snr_sn, const int* var_to_factors,
+                                                   const int* factor_to_vars, int64_t b, int nvar, int nchk, int dv, int dc, T* node_base,
+                                                   T* hop_base, T* ef_f2v_base, T* ef_v2f_base) {
+    const int tid = threadIdx.x;
+    T* node = node_base + b * 2 * nvar;                                     // [2][nvar]
+    for (int o = tid; o < 2 * nvar; o += LD_THREADS) fgnn_st(node + o, o < nvar ? ys[o] : snr[(o - nvar) * snr_sn]);
+    T* hop = hop_base + b * dc * nchk;                                      // [dc][nchk] = hop^T
+    for (int o = tid; o < dc * nchk; o += LD_THREADS) {
+        const int j = o / nchk, f = o - j * nchk;
+        fgnn_st(hop + o, ys[factor_to_vars[f * dc + j]]);
+    }
+    T* e1 = ef_f2v_base + b * (int64_t)(dc + 1) * nvar * dv;               // [dc+1][nvar][dv]
+    for (int o = tid; o < (dc + 1) * nvar * dv; o += LD_THREADS) {
+        const int c = o / (nvar * dv), r = o - c * nvar * dv, n = r / dv, j = r - n * dv;
+        const float v = c < dc ? ys[factor_to_vars[var_to_factors[n * dv + j] * dc + c]] : ys[n];
+        fgnn_st(e1 + o, v);
+    }
+    T* e2 = ef_v2f_base + b * (int64_t)(dc + 1) * nchk * dc;               // [dc+1][nchk][dc]
+    for (int o = tid; o < (dc + 1) * nchk * dc; o += LD_THREADS) {
+        const int c = o / (nchk * dc), r = o - c * nchk * dc, f = r / dc, j = r - f * dc;
+        fgnn_st(e2 + o, ys[factor_to_vars[f * dc + (c < dc ? c : j)]]);
+    }
+}
+
+// One workgroup per codeword: y into LDS, then the shared gather stage (ld_gather_features).
 template <typename T, bool RNG>
 __global__ __launch_bounds__(LD_THREADS) void ldpc_features_kernel(const LdFeatParams p) {
     __shared__ float ys[1024];
@@ -95,24 +123,22 @@ __global__ __launch_bounds__(LD_THREADS) void ldpc_features_kernel(const LdFeatP
         p.y[i] = v;
     }
     __syncthreads();
-    T* node = static_cast<T*>(p.node) + b * 2 * nvar;                       // [2][nvar]
-    for (int o = tid; o < 2 * nvar; o += LD_THREADS) fgnn_st(node + o, o < nvar ? ys[o] : snr);
-    T* hop = static_cast<T*>(p.hop) + b * dc * nchk;                        // [dc][nchk] = hop^T
-    for (int o = tid; o < dc * nchk; o += LD_THREADS) {
-        const int j = o / nchk, f = o - j * nchk;
-        fgnn_st(hop + o, ys[p.factor_to_vars[f * dc + j]]);
-    }
-    T* e1 = static_cast<T*>(p.ef_f2v) + b * (int64_t)(dc + 1) * nvar * dv;  // [dc+1][nvar][dv]
-    for (int o = tid; o < (dc + 1) * nvar * dv; o += LD_THREADS) {
-        const int c = o / (nvar * dv), r = o - c * nvar * dv, n = r / dv, j = r - n * dv;
-        const float v = c < dc ? ys[p.factor_to_vars[p.var_to_factors[n * dv + j] * dc + c]] : ys[n];
-        fgnn_st(e1 + o, v);
-    }
-    T* e2 = static_cast<T*>(p.ef_v2f) + b * (int64_t)(dc + 1) * nchk * dc;  // [dc+1][nchk][dc]
-    for (int o = tid; o < (dc + 1) * nchk * dc; o += LD_THREADS) {
-        const int c = o / (nchk * dc), r = o - c * nchk * dc, f = r / dc, j = r - f * dc;
-        fgnn_st(e2 + o, ys[p.factor_to_vars[f * dc + (c < dc ? c : j)]]);
-    }
+    ld_gather_features(ys, p.snr_db + b, 0, p.var_to_factors, p.factor_to_vars, b, nvar, nchk, dv, dc, static_cast<T*>(p.node),
+                       static_cast<T*>(p.hop), static_cast<T*>(p.ef_f2v), static_cast<T*>(p.ef_v2f));
+}
+
+// Model inputs from a given received word (the reference's `Codes.__getitem__`, lib/data/ldpc_dataset.py:141-156): y into LDS,
+// then the same gather as ldpc_features_kernel; node row 1 is snr_db[b * snr_sb + n * snr_sn].
+template <typename T>
+__global__ __launch_bounds__(LD_THREADS) void ldpc_received_features_kernel(const float* __restrict__ y, const float* __restrict__ snr_db,
+                                                                            int64_t snr_sb, int64_t snr_sn, const int* __restrict__ var_to_factors,
+                                                                            const int* __restrict__ factor_to_vars, int nvar, int nchk, int dv,
+                                                                            int dc, T* node, T* hop, T* ef_f2v, T* ef_v2f) {
+    __shared__ float ys[1024];
+    const int64_t b = blockIdx.x;
+    for (int n = threadIdx.x; n < nvar; n += LD_THREADS) ys[n] = y[b * nvar + n];
+    __syncthreads();
+    ld_gather_features(ys, snr_db + b * snr_sb, snr_sn, var_to_factors, factor_to_vars, b, nvar, nchk, dv, dc, node, hop, ef_f2v, ef_v2f);
 }
 
 // cw [B][K+P] (bytes 0/1) = [s | G s]; s [B][K] bytes, gmask [P] 64-bit rows of G over the K <= 64 message bits.
@@ -180,6 +206,34 @@ extern "C" int fgnn_ldpc_channel_features_rng(const uint8_t* cw, const float* sn
                                               fgnn_stream_t stream) {
     return ld_channel_launch(true, cw, snr_db, sigma_b, rho, nullptr, nullptr, nullptr, seed, offset, var_to_factors,
                              factor_to_vars, B, nvar, nchk, dv, dc, dtype, y, node, hop, ef_f2v, ef_v2f, stream);
+}
+
+// Model inputs from given received words y [B][nvar] f32 (a stored test set's `noizy_sg`): the outputs of
+// fgnn_ldpc_channel_features minus y, node row 1 = snr_db[b * snr_sb + n * snr_sn] (snr_sn = 0: one value per word; snr_sb = nvar,
+// snr_sn = 1: the reference's stored per-bit `snr_dbs` rows).
+extern "C" int fgnn_ldpc_received_features(const float* y, const float* snr_db, int64_t snr_sb, int64_t snr_sn,
+                                           const int32_t* var_to_factors, const int32_t* factor_to_vars, int64_t B, int nvar, int nchk,
+                                           int dv, int dc, int dtype, void* node, void* hop, void* ef_f2v, void* ef_v2f,
+                                           fgnn_stream_t stream) {
+    if (B < 0 || nvar < 1 || nvar > 1024 || nchk < 1 || dv < 1 || dc < 1 || (dtype != FGNN_F32 && dtype != FGNN_BF16))
+        FGNN_FAIL(FGNN_EUNSUPPORTED, "ldpc_received_features: nvar=%d (<= 1024) nchk=%d dv=%d dc=%d dtype=%d", nvar, nchk, dv, dc,
+                  dtype);
+    if (snr_sb < 0 || snr_sn < 0) FGNN_FAIL(FGNN_EINVAL, "ldpc_received_features: negative snr strides");
+    if (B == 0) return FGNN_OK;
+    if (!y || !snr_db || !var_to_factors || !factor_to_vars || !node || !hop || !ef_f2v || !ef_v2f)
+        FGNN_FAIL(FGNN_EINVAL, "ldpc_received_features: null pointer");
+    fgnn_note_kernel("ldpc_received_features_kernel");
+    const dim3 grid((unsigned)B), block(LD_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == FGNN_F32)
+        hipLaunchKernelGGL(ldpc_received_features_kernel<float>, grid, block, 0, st, y, snr_db, snr_sb, snr_sn, var_to_factors,
+                           factor_to_vars, nvar, nchk, dv, dc, (float*)node, (float*)hop, (float*)ef_f2v, (float*)ef_v2f);
+    else
+        hipLaunchKernelGGL(ldpc_received_features_kernel<bf16_t>, grid, block, 0, st, y, snr_db, snr_sb, snr_sn, var_to_factors,
+                           factor_to_vars, nvar, nchk, dv, dc, (bf16_t*)node, (bf16_t*)hop, (bf16_t*)ef_f2v, (bf16_t*)ef_v2f);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_received_features launch: %s", hipGetErrorString(e));
+    return FGNN_OK;
 }
 
 // ---- the training loss behind the decoder (round 5) --------------------------------------------------------------------------------

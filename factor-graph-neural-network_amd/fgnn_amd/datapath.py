@@ -90,6 +90,77 @@ class LdpcDataPath:
             _hip.stream_ptr()))
         return y, node, hop, ef_f2v, ef_v2f
 
+    def received_features(self, y, snr_db, dtype=torch.float32):
+        """Model inputs from given received words (the reference's ``Codes.__getitem__``, lib/data/ldpc_dataset.py:141-156, over a
+        batch): y [B,96] and snr_db [B] (one value per word) or [B,96] (the stored per-bit ``snr_dbs`` rows; node row 1 is that row).
+        Returns (node_feature [B,2,96,1], hop_feature [B,6,48,1], efeature_f2v [B,7,96,3], efeature_v2f [B,7,48,6]) in ``dtype``:
+        on the ``y`` that ``channel_features`` returns, exactly that call's four feature tensors."""
+        B = check_received_args(y, snr_db, dtype)
+        dev = self.device
+        y = y.to(dev, torch.float32).contiguous()
+        snr_db = snr_db.to(dev, torch.float32).contiguous()
+        snr_sb, snr_sn = (1, 0) if snr_db.dim() == 1 else (96, 1)
+        node = torch.empty((B, 2, 96, 1), device=dev, dtype=dtype)
+        hop = torch.empty((B, 6, 48, 1), device=dev, dtype=dtype)
+        ef_f2v = torch.empty((B, 7, 96, 3), device=dev, dtype=dtype)
+        ef_v2f = torch.empty((B, 7, 48, 6), device=dev, dtype=dtype)
+        P = _hip._ptr
+        _hip.check(_hip.lib().fgnn_ldpc_received_features(
+            P(y), P(snr_db), snr_sb, snr_sn, P(self.var_to_factors), P(self.factor_to_vars), B, 96, 48, 3, 6, _hip.dtype_code(node),
+            P(node), P(hop), P(ef_f2v), P(ef_v2f), _hip.stream_ptr()))
+        return node, hop, ef_f2v, ef_v2f
+
+    def make_test_set(self, num, seed=0, snr_db=(0, 1, 2, 3, 4), sigma_b=(0, 1, 2, 3, 4, 5), burst_prob=0.05, baseline=True):
+        """A test set as the reference's generator writes it (data_generate/ldpc.py:45-89): ``num`` items per class of (SNR, burst
+        sigma_b), sigma_b outer, SNR inner.  Returns CPU tensors: ``noizy_sg`` f32 [n,96] (received words), ``gts`` int64 [n,96]
+        (the transmitted codewords), ``snr_dbs`` f32 [n,96] (constant rows), ``sigma_b`` f32 [n]; with ``baseline`` also
+        ``sp_error``, float64 [n_snr, n_sigma]: the generator's ``error`` table, the sum-product decoder's mean message-bit error per
+        class (``decode(bit_prior(y, snr), loops=100)``, lib/data/ldpc.py:18-24).
+
+        Reproducible from the arguments: the messages come from ``torch.Generator(device).manual_seed(seed)`` (one draw of [n,48]);
+        the channel's draws from the feature kernel's own generator (``channel_features(kernel_rng=(seed, 2**62 + k))`` for the k-th
+        chunk of at most 4096 items).  Why 2**62: small offsets are a training loop's step numbers (``sample(kernel_rng=True,
+        step=...)``), so test words never reuse a training batch's noise; and bit 63 of the offset selects the kernel's second (z2)
+        stream, so offsets stay below 2**63."""
+        snr_db, sigma_b = check_grids(snr_db, sigma_b)
+        num = int(num)
+        if num < 1:
+            raise ValueError('num must be >= 1, got %d' % num)
+        dev = self.device
+        nc = len(snr_db) * len(sigma_b)
+        n = num * nc
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        s = torch.randint(0, 2, (n, self.K), device=dev, generator=gen, dtype=torch.uint8)
+        cw = self.encode(s)
+        snr_cls = torch.tensor([float(v) for _ in sigma_b for v in snr_db], dtype=torch.float32)      # sigma_b outer, SNR inner
+        sb_cls = torch.tensor([float(v) for v in sigma_b for _ in snr_db], dtype=torch.float32)
+        snr = snr_cls.repeat_interleave(num).to(dev)
+        sb = sb_cls.repeat_interleave(num).to(dev)
+        y = torch.empty((n, self.K + self.P), device=dev, dtype=torch.float32)
+        chunk = 4096
+        for k in range(0, (n + chunk - 1) // chunk):
+            i, j = k * chunk, min(n, (k + 1) * chunk)
+            y[i:j] = self.channel_features(cw[i:j], snr[i:j], sb[i:j], burst_prob, kernel_rng=(seed, 2 ** 62 + k))[0]
+        out = {'noizy_sg': y.cpu(), 'gts': cw.long().cpu(), 'snr_dbs': snr[:, None].expand(-1, 96).contiguous().cpu(),
+               'sigma_b': sb.cpu()}
+        if baseline:
+            from .ldpc_eval import LdpcErrorCounts
+            acc = LdpcErrorCounts(dev, snr_db, sigma_b)
+            for i in range(0, n, chunk):
+                j = min(n, i + chunk)
+                x = self.decode(self.bit_prior(y[i:j], snr[i:j]), loops=100)[0]
+                acc.add_bits(x, cw[i:j], snr[i:j], sb[i:j])
+            out['sp_error'] = torch.from_numpy(acc.result()['err_class'])
+        return out
+
+    def write_test_set(self, path, num, seed=0, snr_db=(0, 1, 2, 3, 4), sigma_b=(0, 1, 2, 3, 4, 5), burst_prob=0.05, baseline=True):
+        """``make_test_set`` saved with ``torch.save`` as the reference's generator saves it: the four keys ``noizy_sg``, ``gts``,
+        ``snr_dbs``, ``sigma_b`` only, so the unchanged ``lib.data.Codes(path)`` (and ``train_ldpc.py --test_path``) reads it.
+        Returns the sum-product table (``sp_error``) when ``baseline``, else None."""
+        d = self.make_test_set(num, seed, snr_db, sigma_b, burst_prob, baseline)
+        torch.save({k: d[k] for k in ('noizy_sg', 'gts', 'snr_dbs', 'sigma_b')}, path)
+        return d.get('sp_error')
+
     def _incidence_tables(self, nlist, nchk):
         """alist column lists (each variable's checks in file order, -1 = padding) -> the device tables of
         `fgnn_ldpc_decode`: col_ptr, row_ptr, row_edge, row_var."""
@@ -147,3 +218,30 @@ class LdpcDataPath:
                                                              kernel_rng=(seed, step) if kernel_rng else None)
         return (node, hop, self.nn_idx_f2v.unsqueeze(0).expand(B, -1, -1), self.nn_idx_v2f.unsqueeze(0).expand(B, -1, -1),
                 ef_f2v, ef_v2f, cw.long(), sigma_b)
+
+
+def check_received_args(y, snr_db, dtype):
+    """Shapes of ``LdpcDataPath.received_features`` (before anything reaches the device): returns B."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('dtype must be float32 or bfloat16')
+    if y.dim() != 2 or y.shape[1] != 96:
+        raise ValueError('received words must be [B, 96], got %s' % (tuple(y.shape),))
+    B = y.shape[0]
+    if tuple(snr_db.shape) not in ((B,), (B, 96)):
+        raise ValueError('snr_db must be [B] or [B, 96] with B = %d, got %s' % (B, tuple(snr_db.shape)))
+    return B
+
+
+def check_grids(snr_grid, sigma_grid):
+    """The class grids of the test loop: SNR values (dB, float) and integer burst levels, at least one of each and at most 256
+    classes (fgnn_ldpc_error_counts).  Returns them as tuples of float and int."""
+    snr_grid, sigma_grid = tuple(snr_grid), tuple(sigma_grid)
+    if not snr_grid or not sigma_grid:
+        raise ValueError('empty class grid')
+    if len(snr_grid) * len(sigma_grid) > 256:
+        raise ValueError('at most 256 classes, got %d x %d' % (len(snr_grid), len(sigma_grid)))
+    if any(not np.isfinite(float(v)) for v in snr_grid):
+        raise ValueError('SNR grid values must be finite')
+    if any(not np.isfinite(float(v)) or float(v) != int(v) or abs(int(v)) >= 2 ** 31 for v in sigma_grid):
+        raise ValueError('sigma_b grid values must be 32-bit integers, got %s' % (sigma_grid,))
+    return tuple(float(v) for v in snr_grid), tuple(int(v) for v in sigma_grid)

@@ -1,0 +1,213 @@
+"""Decoding quality of LDPC decoders on the GPU: the reference's test loop and its test-set generator.
+
+The reference judges a trained decoder with ``train_ldpc.py:test()`` (/root/reference/train_ldpc.py:262-327): it reads a stored test
+set through ``lib.data.Codes``, runs the model in batches of 100 and prints the overall bit error rate of the 48 message bits and a
+5 x 6 table of bit error rates per class of (SNR in {0..4} dB, burst level sigma_b in {0..5}).  The test set comes from
+``data_generate/ldpc.py``, which prints the same table for the classical sum-product decoder beside it.
+
+Here the whole loop stays on the device: ``LdpcDataPath.received_features`` builds the model inputs from the stored received words,
+``LdpcErrorCounts`` accumulates the counts with one launch per batch (csrc/ldpc_eval.hip) and reads them back once, and
+``LdpcDataPath.make_test_set`` / ``write_test_set`` generate test sets.  ``python -m fgnn_amd.ldpc_eval`` is the command line.
+"""
+import argparse
+import contextlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import _hip
+from .datapath import LdpcDataPath, check_grids
+
+SNR_GRID = (0, 1, 2, 3, 4)              # train_ldpc.py:298 (SNR) and the acc_cnt rows
+SIGMA_GRID = (0, 1, 2, 3, 4, 5)         # train_ldpc.py:320 (range(6)) and the acc_cnt columns
+COLUMNS = ('bits', 'bit_errors', 'words', 'word_errors')
+
+
+def check_count_args(dec, label, snr_db, sigma_b, nbits):
+    """Shapes and dtypes of one ``LdpcErrorCounts`` batch (before anything reaches the device): decisions [B, >= nbits], labels
+    [B, >= nbits] int64 / uint8 / bool, snr_db [B] or [B, k] (column 0 classifies, as the reference's node_feature[:, 1, 0, 0]),
+    sigma_b [B].  Returns B."""
+    nbits = int(nbits)
+    if not 1 <= nbits <= 1024:
+        raise ValueError('nbits must be in 1..1024, got %d' % nbits)
+    if dec.dim() != 2 or dec.shape[1] < nbits:
+        raise ValueError('decisions must be [B, >= %d], got %s' % (nbits, tuple(dec.shape)))
+    B = dec.shape[0]
+    if label.dim() != 2 or label.shape[0] != B or label.shape[1] < nbits:
+        raise ValueError('labels must be [%d, >= %d], got %s' % (B, nbits, tuple(label.shape)))
+    if label.dtype not in (torch.int64, torch.uint8, torch.bool):
+        raise ValueError('labels must be int64, uint8 or bool, got %s' % label.dtype)
+    if not (snr_db.dim() == 1 and snr_db.shape[0] == B) and not (snr_db.dim() == 2 and snr_db.shape[0] == B and snr_db.shape[1] >= 1):
+        raise ValueError('snr_db must be [%d] or [%d, k], got %s' % (B, B, tuple(snr_db.shape)))
+    if tuple(sigma_b.shape) != (B,):
+        raise ValueError('sigma_b must be [%d], got %s' % (B, tuple(sigma_b.shape)))
+    return B
+
+
+class LdpcErrorCounts:
+    """Bit and word error counts of LDPC decisions per class of (SNR, sigma_b), accumulated on the device.
+
+    ``add_logits`` / ``add_bits`` only enqueue one launch of ``fgnn_ldpc_error_counts``; ``result()`` synchronises once.  The
+    classes are those of train_ldpc.py:316-324: the first SNR grid value within 1e-3 of the word's SNR (of bit 0) and the sigma_b
+    grid value equal to ``int(sigma_b)`` (truncated, as ``sigma_b.long()``); a word outside every class counts only overall."""
+
+    def __init__(self, device, snr_grid=SNR_GRID, sigma_grid=SIGMA_GRID):
+        self.snr_grid, self.sigma_grid = check_grids(snr_grid, sigma_grid)
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('LdpcErrorCounts runs on a ROCm device (no CPU fallback)')
+        self._snr = torch.tensor(self.snr_grid, dtype=torch.float32, device=self.device)
+        self._sigma = torch.tensor(self.sigma_grid, dtype=torch.int32, device=self.device)
+        self.counts = torch.zeros((len(self.snr_grid) * len(self.sigma_grid) + 1, 4), dtype=torch.int64, device=self.device)
+
+    def reset(self):
+        self.counts.zero_()
+
+    def add_logits(self, logits, label, snr_db, sigma_b, nbits=48):
+        """A model's logits [B, >= nbits] f32 / bf16: bit = logit >= 0 (the reference's test, train_ldpc.py:302)."""
+        if logits.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError('logits must be float32 or bfloat16, got %s' % logits.dtype)
+        self._add(logits, _hip.DEC_F32 if logits.dtype == torch.float32 else _hip.DEC_BF16, label, snr_db, sigma_b, nbits)
+
+    def add_bits(self, x, label, snr_db, sigma_b, nbits=48):
+        """Hard decisions [B, >= nbits] uint8 / bool (bit = x != 0), such as ``LdpcDataPath.decode``'s."""
+        if x.dtype not in (torch.uint8, torch.bool):
+            raise ValueError('hard decisions must be uint8 or bool, got %s' % x.dtype)
+        self._add(x.view(torch.uint8) if x.dtype == torch.bool else x, _hip.DEC_U8, label, snr_db, sigma_b, nbits)
+
+    def _add(self, dec, kind, label, snr_db, sigma_b, nbits):
+        B = check_count_args(dec, label, snr_db, sigma_b, nbits)
+        if B == 0:
+            return
+        dev = self.device
+        dec = dec.to(dev)
+        if dec.stride(1) != 1:
+            dec = dec.contiguous()
+        label = label.to(dev)
+        if label.dtype == torch.bool:
+            label = label.view(torch.uint8)
+        if label.stride(1) != 1:
+            label = label.contiguous()
+        snr_db = snr_db.to(dev, torch.float32)
+        snr0 = snr_db if snr_db.dim() == 1 else snr_db[:, 0]
+        sigma_b = sigma_b.to(dev, torch.float32).contiguous()
+        P = _hip._ptr
+        _hip.check(_hip.lib().fgnn_ldpc_error_counts(
+            P(dec), kind, dec.stride(0), P(label), _hip.LABEL_I64 if label.dtype == torch.int64 else _hip.LABEL_U8, label.stride(0),
+            P(snr0), snr0.stride(0), P(sigma_b), B, int(nbits), P(self._snr), len(self.snr_grid), P(self._sigma),
+            len(self.sigma_grid), P(self.counts), _hip.stream_ptr()))
+
+    def result(self):
+        """One read-back.  ``ber``: 1 - right / compared over every word (train_ldpc.py:326); ``err_class`` [n_snr, n_sigma]:
+        1 - acc_cnt / acc_tot (train_ldpc.py:327; NaN for an empty class); ``fer`` / ``fer_class``: the same for whole words;
+        ``counts`` [n_snr * n_sigma + 1, 4] int64 (columns bits, bit errors, words, word errors; rows SNR-major, the last overall)."""
+        c = self.counts.cpu().numpy()
+        ns, nb = len(self.snr_grid), len(self.sigma_grid)
+        cls = c[:-1].reshape(ns, nb, 4).astype(np.float64)
+        tot = c[-1]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            err_class = 1 - np.divide(cls[..., 0] - cls[..., 1], cls[..., 0])
+            fer_class = np.divide(cls[..., 3], cls[..., 2])
+        return {'ber': 1 - int(tot[0] - tot[1]) / int(tot[0]) if tot[0] else float('nan'),
+                'err_class': err_class,
+                'fer': int(tot[3]) / int(tot[2]) if tot[2] else float('nan'),
+                'fer_class': fer_class,
+                'counts': c}
+
+
+def load_test_set(test_set, device):
+    """A test set (the dict of ``make_test_set`` / the reference's generator, or a path to its ``torch.save`` file) on ``device``:
+    (noizy_sg [n,96] f32, gts [n,96], snr_dbs [n,96] or [n] f32, sigma_b [n] f32)."""
+    if isinstance(test_set, (str, os.PathLike)):
+        test_set = torch.load(test_set, map_location='cpu')
+    y, gts, snr, sb = (test_set[k] for k in ('noizy_sg', 'gts', 'snr_dbs', 'sigma_b'))
+    n = y.shape[0]
+    if tuple(y.shape) != (n, 96) or tuple(gts.shape) != (n, 96) or tuple(snr.shape) not in ((n, 96), (n,)) or tuple(sb.shape) != (n,):
+        raise ValueError('test set shapes: noizy_sg %s, gts %s, snr_dbs %s, sigma_b %s (want [n,96], [n,96], [n,96] or [n], [n])'
+                         % (tuple(y.shape), tuple(gts.shape), tuple(snr.shape), tuple(sb.shape)))
+    if gts.dtype not in (torch.int64, torch.uint8):
+        gts = gts.long()
+    return (y.to(device, torch.float32), gts.to(device), snr.to(device, torch.float32), sb.to(device, torch.float32))
+
+
+def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=False, snr_grid=SNR_GRID, sigma_grid=SIGMA_GRID):
+    """``train_ldpc.py:test()`` for an ``fgnn_amd.LDPCModel`` on a test set (dict or path): the model in eval mode under no_grad
+    (bf16: bf16 features under bf16 autocast), ``batch_size`` words per batch, nothing read back to the host until the end.  Returns
+    ``LdpcErrorCounts.result()`` of the model's logits; with ``baseline`` also, under 'baseline', that of the sum-product decoder
+    (``decode(bit_prior(y, snr), loops=100)``, lib/data/ldpc.py:18-24) on the same received words.  The model's training flag is
+    restored afterwards."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('dtype must be float32 or bfloat16')
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError('batch_size must be >= 1')
+    dev = next(model.parameters()).device
+    counts = LdpcErrorCounts(dev, snr_grid, sigma_grid)
+    sp = LdpcErrorCounts(dev, snr_grid, sigma_grid) if baseline else None
+    path = LdpcDataPath(dev)
+    y, gts, snr, sb = load_test_set(test_set, dev)
+    n = y.shape[0]
+    was = model.training
+    model.eval()
+    try:
+        with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16, enabled=dtype == torch.bfloat16):
+            for i in range(0, n, batch_size):
+                j = min(n, i + batch_size)
+                B = j - i
+                node, hop, ef_f2v, ef_v2f = path.received_features(y[i:j], snr[i:j], dtype)
+                logits, _ = model(node, hop, path.nn_idx_f2v.unsqueeze(0).expand(B, -1, -1),
+                                  path.nn_idx_v2f.unsqueeze(0).expand(B, -1, -1), ef_f2v, ef_v2f)
+                counts.add_logits(logits, gts[i:j], snr[i:j], sb[i:j])
+                if baseline:
+                    snr0 = snr[i:j] if snr.dim() == 1 else snr[i:j, 0]
+                    x = path.decode(path.bit_prior(y[i:j], snr0), loops=100)[0]
+                    sp.add_bits(x, gts[i:j], snr[i:j], sb[i:j])
+    finally:
+        model.train(was)
+    res = counts.result()
+    if baseline:
+        res['baseline'] = sp.result()
+    return res
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m fgnn_amd.ldpc_eval',
+                                 description='Evaluate an LDPC decoder on a stored test set (train_ldpc.py --test_path) or write a '
+                                             'test set (data_generate/ldpc.py).')
+    ap.add_argument('--test_path', help='test set to evaluate on (torch.save dict: noizy_sg, gts, snr_dbs, sigma_b)')
+    ap.add_argument('--model_path', help="checkpoint with 'model_state_dict' (train_ldpc.py's format)")
+    ap.add_argument('--batch_size', type=int, default=4096)
+    ap.add_argument('--aggregator', default='max')
+    ap.add_argument('--dtype', choices=('f32', 'bf16'), default='f32')
+    ap.add_argument('--baseline', action='store_true', help='also print the sum-product decoder\'s table')
+    ap.add_argument('--make_test_set', metavar='P', help='write a test set to P and print the sum-product table')
+    ap.add_argument('--num', type=int, default=1000, help='items per class (--make_test_set)')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--burst_prob', type=float, default=0.05)
+    args = ap.parse_args(argv)
+    dev = torch.device('cuda:0')
+    if args.make_test_set:
+        sp = LdpcDataPath(dev).write_test_set(args.make_test_set, args.num, seed=args.seed, burst_prob=args.burst_prob)
+        print(sp)
+        return 0
+    if not args.test_path or not args.model_path:
+        ap.error('give --test_path and --model_path, or --make_test_set')
+    from .ldpc import LDPCModel
+    with contextlib.redirect_stdout(sys.stderr):           # (the model's construction talks; stdout carries the result only)
+        model = LDPCModel(2, 6, 4, aggregator=args.aggregator)
+    ckpt = torch.load(args.model_path, map_location=dev)
+    model.load_state_dict(ckpt['model_state_dict'])
+    model.to(dev)
+    res = evaluate(model, args.test_path, args.batch_size, torch.bfloat16 if args.dtype == 'bf16' else torch.float32,
+                   baseline=args.baseline)
+    print(res['ber'])
+    print(torch.FloatTensor(res['err_class']))
+    if args.baseline:
+        print(torch.FloatTensor(res['baseline']['err_class']))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -548,6 +548,32 @@ int fgnn_ldpc_channel_features_rng(const uint8_t* cw, const float* snr_db, const
                                    uint64_t offset, const int32_t* var_to_factors, const int32_t* factor_to_vars, int64_t B,
                                    int32_t nvar, int32_t nchk, int32_t dv, int32_t dc, int32_t dtype, float* y, void* node,
                                    void* hop, void* ef_f2v, void* ef_v2f, fgnn_stream_t stream);
+/* The model inputs of fgnn_ldpc_channel_features (all but y) from GIVEN received words y [B][nvar] f32 — a stored test set's
+ * `noizy_sg` rows, what the reference's `Codes.__getitem__` builds per item (lib/data/ldpc_dataset.py:141-156) — with node row 1 =
+ * snr_db[b * snr_sb + n * snr_sn]: snr_sn = 0 for one value per word, (snr_sb, snr_sn) = (nvar, 1) for the stored per-bit `snr_dbs`
+ * rows.  The gather stage is the one fgnn_ldpc_channel_features runs.  Shapes / dtype outside the family: FGNN_EUNSUPPORTED; negative
+ * strides, null pointers: FGNN_EINVAL; B = 0 is a no-op. */
+int fgnn_ldpc_received_features(const float* y, const float* snr_db, int64_t snr_sb, int64_t snr_sn, const int32_t* var_to_factors,
+                                const int32_t* factor_to_vars, int64_t B, int32_t nvar, int32_t nchk, int32_t dv, int32_t dc,
+                                int32_t dtype, void* node, void* hop, void* ef_f2v, void* ef_v2f, fgnn_stream_t stream);
+
+/*
+ * The decoding-quality accounting of the reference's test loop (/root/reference/train_ldpc.py:289-327: acc_cnt / acc_tot per class,
+ * acc_seq / tot overall) for one batch, in one launch (csrc/ldpc_eval.hip).  Word b's decisions: dec [b * dec_sb + j], j < nbits,
+ * of kind FGNN_DEC_F32 / FGNN_DEC_BF16 (logits, bit = v >= 0 as at train_ldpc.py:302; -0 counts as 1) or FGNN_DEC_U8 (hard
+ * decisions, bit = v != 0); labels label [b * label_sb + j] of kind FGNN_LABEL_I64 (the reference's `gts`) or FGNN_LABEL_U8
+ * (fgnn_ldpc_encode's codewords).  Class of word b: snr index = the first k with |snr_db[b * snr_sb] - snr_grid[k]| < 1e-3 (f32;
+ * the reference classifies by bit 0's SNR), sigma index = the first k with sigma_grid[k] == (int64) sigma_b[b] (truncation, as
+ * `sigma_b.long()`); a word with no class counts only in the overall row.  ADDS to counts [n_snr * n_sigma + 1][4] int64: rows
+ * SNR-major (row = snr index * n_sigma + sigma index), the last row over every word; columns {bits compared, bit errors, words,
+ * word errors}.  Integer atomics: deterministic.  Kinds, nbits outside 1..1024, more than 256 classes: FGNN_EUNSUPPORTED; negative
+ * sizes or strides, null pointers: FGNN_EINVAL; B = 0 is a no-op.  No reference counterpart for the word-error columns.
+ */
+enum { FGNN_DEC_F32 = 0, FGNN_DEC_BF16 = 1, FGNN_DEC_U8 = 2 };
+enum { FGNN_LABEL_I64 = 0, FGNN_LABEL_U8 = 1 };
+int fgnn_ldpc_error_counts(const void* dec, int32_t dec_kind, int64_t dec_sb, const void* label, int32_t label_kind, int64_t label_sb,
+                           const float* snr_db, int64_t snr_sb, const float* sigma_b, int64_t B, int32_t nbits, const float* snr_grid,
+                           int32_t n_snr, const int32_t* sigma_grid, int32_t n_sigma, int64_t* counts, fgnn_stream_t stream);
 
 /*
  * The training loss behind the decoder (/root/reference/train_ldpc.py:222-227), two short launches forward and one backward:
