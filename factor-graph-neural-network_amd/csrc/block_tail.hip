@@ -41,6 +41,7 @@
 // A wave owns 16-row tiles and walks all Cout / 64 slabs of its tile (W2 / W2^T fragments and the per-channel constants
 // come from LDS, stored in fragment order: conflict-free 16-byte reads; the stream stays HBM-bound).
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "fgnn_gridfold.h"
 #include <stdlib.h>
 
@@ -48,7 +49,6 @@
 #define BT_WAVES 4
 #define BT_MAXGRID 1024      // = BN_MAXPART of bnact.hip: the statistics partials use its workspace layout and finalisers
 
-typedef __bf16 bt_bf16x8 __attribute__((ext_vector_type(8)));
 
 struct BtParams {
     const uint16_t* e;       // [R][64] bf16
@@ -84,19 +84,9 @@ struct BtParams {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char bt_lds[];
 
-__device__ __forceinline__ unsigned bt_pack2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
-template <typename T> __device__ __forceinline__ const T* bt_at(const void* base, unsigned byte_off) {
-    return reinterpret_cast<const T*>(static_cast<const char*>(base) + byte_off);
-}
-__device__ __forceinline__ float bt_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bt_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 __device__ __forceinline__ void bt_unpack8(const uint4 q, float (&v)[8]) {
-    v[0] = bt_lo(q.x); v[1] = bt_hi(q.x); v[2] = bt_lo(q.y); v[3] = bt_hi(q.y);
-    v[4] = bt_lo(q.z); v[5] = bt_hi(q.z); v[6] = bt_lo(q.w); v[7] = bt_hi(q.w);
+    v[0] = fgnn_lo(q.x); v[1] = fgnn_hi(q.x); v[2] = fgnn_lo(q.y); v[3] = fgnn_hi(q.y);
+    v[4] = fgnn_lo(q.z); v[5] = fgnn_hi(q.z); v[6] = fgnn_lo(q.w); v[7] = fgnn_hi(q.w);
 }
 __device__ __forceinline__ float bt_act(float v, float slope) { return v > 0.f ? v : v * slope; }
 // Scalar f32 VALU only in this file (and -fno-slp-vectorize in the Makefile): beside a bf16 MFMA stream a packed-f32 op
@@ -128,14 +118,14 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
         {   // A[i = out channel 64 sl + pr][k = input channels 16 fk + 8 fs .. + 7]
             const float* wp = p.W2 + (int64_t)(64 * sl + pr) * 64 + 16 * fk + 8 * fs;
             const f32x4 a = *reinterpret_cast<const f32x4*>(wp), b = *reinterpret_cast<const f32x4*>(wp + 4);
-            Wf[f] = make_uint4(bt_pack2(a[0], a[1]), bt_pack2(a[2], a[3]), bt_pack2(b[0], b[1]), bt_pack2(b[2], b[3]));
+            Wf[f] = make_uint4(fgnn_pack2(a[0], a[1]), fgnn_pack2(a[2], a[3]), fgnn_pack2(b[0], b[1]), fgnn_pack2(b[2], b[3]));
         }
         if (MODE == 3) {   // A[i = input channel pr][k = out channels 64 sl + 16 fk + 8 fs .. + 7]
             const float* wp = p.W2 + (int64_t)(64 * sl + 16 * fk + 8 * fs) * 64 + pr;
             float w[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) w[u] = wp[u * 64];
-            Tf[f] = make_uint4(bt_pack2(w[0], w[1]), bt_pack2(w[2], w[3]), bt_pack2(w[4], w[5]), bt_pack2(w[6], w[7]));
+            Tf[f] = make_uint4(fgnn_pack2(w[0], w[1]), fgnn_pack2(w[2], w[3]), fgnn_pack2(w[4], w[5]), fgnn_pack2(w[6], w[7]));
         }
     }
     for (int o = tid; o < COUT; o += BT_THREADS) {
@@ -223,16 +213,16 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
         const int rl = min(li, R - 1 - tl * 16);
         const uint16_t* eb = p.e + (int64_t)tl * 16 * 64;
         const unsigned off = (unsigned)((rl * 64 + 16 * lk) * 2);
-        q[0] = *bt_at<uint4>(eb, off);
-        q[1] = *bt_at<uint4>(eb, off + 16u);
+        q[0] = *fgnn_at<uint4>(eb, off);
+        q[1] = *fgnn_at<uint4>(eb, off + 16u);
     };
     auto load_g = [&](int it, uint4 (&gp)[2]) {           // a slab-bound wave knows its slab: the upstream gradient rides along (mode 2)
         const int tl = min(first + it * stride, ntile - 1);
         const int rl = min(li, R - 1 - tl * 16);
         const uint16_t* gb = p.gout + (int64_t)tl * 16 * COUT;
         const unsigned off = (unsigned)((rl * COUT + 64 * cg + 16 * lk) * 2);
-        gp[0] = *bt_at<uint4>(gb, off);
-        gp[1] = *bt_at<uint4>(gb, off + 16u);
+        gp[0] = *fgnn_at<uint4>(gb, off);
+        gp[1] = *fgnn_at<uint4>(gb, off + 16u);
     };
     // A slot is refilled right AFTER its last use, into the same registers: a refill issued while the old value is still
     // live gets registers of its own and a copy at the loop's back edge — a copy that has to wait for the load.
@@ -256,7 +246,7 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
         const uint4 zq4 = make_uint4(0, 0, 0, 0);
         const int crow = min(row, R - 1);                   // (address arithmetic of masked rows stays inside the tensors)
         // ---- a2 = act2(e s2 + t2), packed to bf16: the B operand of z3^T = W2 a2^T (and the tensor the staged path stores) ----
-        bt_bf16x8 a2f[2];
+        bf16x8 a2f[2];
         unsigned pos2 = 0u;                                // bit c: pre2 > 0 for channel 16 lk + c of this row (mode 3)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -272,13 +262,13 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
                 const int c = 8 * ks + 2 * u;
                 const float sc0 = S2REG ? s2[S2REG ? c : 0] : sl4[u >> 1][2 * (u & 1)], sc1 = S2REG ? s2[S2REG ? c + 1 : 0] : sl4[u >> 1][2 * (u & 1) + 1];
                 const float sh0 = S2REG ? t2[S2REG ? c : 0] : tl4[u >> 1][2 * (u & 1)], sh1 = S2REG ? t2[S2REG ? c + 1 : 0] : tl4[u >> 1][2 * (u & 1) + 1];
-                const float v0 = bt_act2<SL2Z>(fmaf(bt_lo(w[u]), sc0, sh0), p.slope2), v1 = bt_act2<SL2Z>(fmaf(bt_hi(w[u]), sc1, sh1), p.slope2);
-                o[u] = bt_pack2(v0, v1);
+                const float v0 = bt_act2<SL2Z>(fmaf(fgnn_lo(w[u]), sc0, sh0), p.slope2), v1 = bt_act2<SL2Z>(fmaf(fgnn_hi(w[u]), sc1, sh1), p.slope2);
+                o[u] = fgnn_pack2(v0, v1);
                 if (MODE == 3) pos2 |= (v0 > 0.f ? 1u : 0u) << c | (v1 > 0.f ? 1u : 0u) << (c + 1);
             }
             uint4 q = make_uint4(o[0], o[1], o[2], o[3]);
             if (partial && !ok) q = make_uint4(0, 0, 0, 0);      // rows past the end contribute nothing to any sum (last tile only)
-            a2f[ks] = __builtin_bit_cast(bt_bf16x8, q);
+            a2f[ks] = __builtin_bit_cast(bf16x8, q);
             if (MODE == 1 && p.out2 && ok && cg == 0) *reinterpret_cast<uint4*>(p.out2 + (int64_t)row * 64 + 16 * lk + 8 * ks) = q;
         }
         if (MODE != 3) {                                    // e of this slot is consumed: ask for the tile DEPTH ahead (pinned here)
@@ -295,7 +285,7 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
                 acc[ot] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
-                    acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bt_bf16x8, aW[WREG ? ot : 0][ks]), a2f[ks], acc[ot], 0, 0, 0);
+                    acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, aW[WREG ? ot : 0][ks]), a2f[ks], acc[ot], 0, 0, 0);
             }
 #pragma unroll
             for (int ot = 0; ot < 4; ++ot)
@@ -336,7 +326,7 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     const uint4 a = WREG ? aW[WREG ? ot : 0][ks] : Wf[((sl * 4 + ot) * 2 + ks) * 64 + lane];
-                    acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bt_bf16x8, a), a2f[ks], acc[ot], 0, 0, 0);
+                    acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), a2f[ks], acc[ot], 0, 0, 0);
                 }
             }
             // acc[ot][r] = z3 - b2 of channel o_base + 16 lk + 4 ot + r, row li
@@ -360,8 +350,8 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
                 }
                 if (ok) {
                     uint16_t* op = p.out + eoff;
-                    *reinterpret_cast<uint4*>(op) = make_uint4(bt_pack2(y[0], y[1]), bt_pack2(y[2], y[3]), bt_pack2(y[4], y[5]), bt_pack2(y[6], y[7]));
-                    *reinterpret_cast<uint4*>(op + 8) = make_uint4(bt_pack2(y[8], y[9]), bt_pack2(y[10], y[11]), bt_pack2(y[12], y[13]), bt_pack2(y[14], y[15]));
+                    *reinterpret_cast<uint4*>(op) = make_uint4(fgnn_pack2(y[0], y[1]), fgnn_pack2(y[2], y[3]), fgnn_pack2(y[4], y[5]), fgnn_pack2(y[6], y[7]));
+                    *reinterpret_cast<uint4*>(op + 8) = make_uint4(fgnn_pack2(y[8], y[9]), fgnn_pack2(y[10], y[11]), fgnn_pack2(y[12], y[13]), fgnn_pack2(y[14], y[15]));
                 }
             } else {
                 float g[16];
@@ -406,20 +396,18 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
                 }
                 if (MOM) {
                     // g' (channels 64 cg + 16 lk .. + 15 of row li) and a2 (channels 16 lk .. + 15) -> the wave's LDS tiles; back transposed
-                    typedef short bt_s16x4 __attribute__((ext_vector_type(4)));
-                    typedef __attribute__((address_space(3))) bt_s16x4 lds_s4;
                     uint4* wg = reinterpret_cast<uint4*>(bt_lds + mom_w);
-                    wg[0] = make_uint4(bt_pack2(gp16[0], gp16[1]), bt_pack2(gp16[2], gp16[3]), bt_pack2(gp16[4], gp16[5]), bt_pack2(gp16[6], gp16[7]));
-                    wg[1] = make_uint4(bt_pack2(gp16[8], gp16[9]), bt_pack2(gp16[10], gp16[11]), bt_pack2(gp16[12], gp16[13]), bt_pack2(gp16[14], gp16[15]));
+                    wg[0] = make_uint4(fgnn_pack2(gp16[0], gp16[1]), fgnn_pack2(gp16[2], gp16[3]), fgnn_pack2(gp16[4], gp16[5]), fgnn_pack2(gp16[6], gp16[7]));
+                    wg[1] = make_uint4(fgnn_pack2(gp16[8], gp16[9]), fgnn_pack2(gp16[10], gp16[11]), fgnn_pack2(gp16[12], gp16[13]), fgnn_pack2(gp16[14], gp16[15]));
                     uint4* wa = reinterpret_cast<uint4*>(bt_lds + mom_w + 2048u);
                     wa[0] = __builtin_bit_cast(uint4, a2f[0]);
                     wa[1] = __builtin_bit_cast(uint4, a2f[1]);
-                    bt_s16x4 fa[4], fb[4];
+                    s16x4 fa[4], fb[4];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         const unsigned off = ((unsigned)t ^ mom_f) << 5;
-                        fa[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_s4*>(static_cast<uintptr_t>(mom_r + off)));
-                        fb[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_s4*>(static_cast<uintptr_t>(mom_r + 2048u + off)));
+                        fa[t] = __builtin_bit_cast(s16x4, fgnn_tr16(mom_r + off));
+                        fb[t] = __builtin_bit_cast(s16x4, fgnn_tr16(mom_r + 2048u + off));
                     }
 #pragma unroll
                     for (int to = 0; to < 4; ++to)
@@ -432,35 +420,34 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
                         for (int u = 0; u < NTC; ++u)
                         {   // (selects, not an indexed register array: the column tile cg NTC + u is wave-uniform but not a constant)
                             const int tcol = cg * NTC + u;
-                            const bt_s16x4 bsel = tcol == 0 ? fb[0] : (tcol == 1 ? fb[1] : (tcol == 2 ? fb[2] : fb[3]));
+                            const s16x4 bsel = tcol == 0 ? fb[0] : (tcol == 1 ? fb[1] : (tcol == 2 ? fb[2] : fb[3]));
                             gr[MOM ? tq : 0][u] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(fb[tq], bsel, gr[MOM ? tq : 0][u], 0, 0, 0);
                         }
                     if (cg == 0) {
-                        typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-                        const v2 one = {(__bf16)1.0f, (__bf16)1.0f};
+                        const bf16x2 one = {(__bf16)1.0f, (__bf16)1.0f};
 #pragma unroll
                         for (int t = 0; t < 4; ++t) {
                             const uint2 w = __builtin_bit_cast(uint2, fb[t]);
-                            vs[t] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2, w.x), one, vs[t], false);
-                            vs[t] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2, w.y), one, vs[t], false);
+                            vs[t] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, w.x), one, vs[t], false);
+                            vs[t] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, w.y), one, vs[t], false);
                         }
                     }
                 }
                 if (MODE == 3) {
-                    const uint4 q0 = make_uint4(bt_pack2(gz[0], gz[1]), bt_pack2(gz[2], gz[3]), bt_pack2(gz[4], gz[5]), bt_pack2(gz[6], gz[7]));
-                    const uint4 q1 = make_uint4(bt_pack2(gz[8], gz[9]), bt_pack2(gz[10], gz[11]), bt_pack2(gz[12], gz[13]), bt_pack2(gz[14], gz[15]));
+                    const uint4 q0 = make_uint4(fgnn_pack2(gz[0], gz[1]), fgnn_pack2(gz[2], gz[3]), fgnn_pack2(gz[4], gz[5]), fgnn_pack2(gz[6], gz[7]));
+                    const uint4 q1 = make_uint4(fgnn_pack2(gz[8], gz[9]), fgnn_pack2(gz[10], gz[11]), fgnn_pack2(gz[12], gz[13]), fgnn_pack2(gz[14], gz[15]));
                     if (ok && p.out) {                          // (NULL: conv2's weight gradient comes from the moments, nobody reads gz3)
                         *reinterpret_cast<uint4*>(p.out + eoff) = q0;
                         *reinterpret_cast<uint4*>(p.out + eoff + 8) = q1;
                     }
                     // ga2^T += W2^T[:, slab] gz3^T[slab]: k-step s, k-group lk <-> out channels o_base + 16 lk + 8 s .. + 7 = q_s as it stands
                     const uint4 zq = make_uint4(0, 0, 0, 0);
-                    const bt_bf16x8 b0 = __builtin_bit_cast(bt_bf16x8, ok ? q0 : zq), b1 = __builtin_bit_cast(bt_bf16x8, ok ? q1 : zq);
+                    const bf16x8 b0 = __builtin_bit_cast(bf16x8, ok ? q0 : zq), b1 = __builtin_bit_cast(bf16x8, ok ? q1 : zq);
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
                         const uint4* wp = Tf + ((sl * 4 + t) * 2) * 64 + lane;
-                        g2acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bt_bf16x8, wp[0]), b0, g2acc[t], 0, 0, 0);
-                        g2acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bt_bf16x8, wp[64]), b1, g2acc[t], 0, 0, 0);
+                        g2acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wp[0]), b0, g2acc[t], 0, 0, 0);
+                        g2acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wp[64]), b1, g2acc[t], 0, 0, 0);
                     }
                 }
             }
@@ -470,7 +457,7 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
             for (int t = 0; t < 4; ++t) {
                 const unsigned w0 = t < 2 ? (t == 0 ? eq[0].x : eq[0].z) : (t == 2 ? eq[1].x : eq[1].z);
                 const unsigned w1 = t < 2 ? (t == 0 ? eq[0].y : eq[0].w) : (t == 2 ? eq[1].y : eq[1].w);
-                const float ev[4] = {bt_lo(w0), bt_hi(w0), bt_lo(w1), bt_hi(w1)};
+                const float ev[4] = {fgnn_lo(w0), fgnn_hi(w0), fgnn_lo(w1), fgnn_hi(w1)};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float gg = (pos2 >> (4 * t + r)) & 1u ? g2acc[t][r] : g2acc[t][r] * p.slope2;
@@ -481,10 +468,10 @@ __global__ __launch_bounds__(BT_THREADS, MODE == 1 ? 3 : 2) void block_tail_kern
         }
         if (MODE == 3 && ok) {       // g2acc[t][r] = ga2 of channel 16 lk + 4 t + r of row li
             uint16_t* gp = p.out2 + (int64_t)row * 64 + 16 * lk;
-            *reinterpret_cast<uint4*>(gp) = make_uint4(bt_pack2(g2acc[0][0], g2acc[0][1]), bt_pack2(g2acc[0][2], g2acc[0][3]),
-                                                       bt_pack2(g2acc[1][0], g2acc[1][1]), bt_pack2(g2acc[1][2], g2acc[1][3]));
-            *reinterpret_cast<uint4*>(gp + 8) = make_uint4(bt_pack2(g2acc[2][0], g2acc[2][1]), bt_pack2(g2acc[2][2], g2acc[2][3]),
-                                                           bt_pack2(g2acc[3][0], g2acc[3][1]), bt_pack2(g2acc[3][2], g2acc[3][3]));
+            *reinterpret_cast<uint4*>(gp) = make_uint4(fgnn_pack2(g2acc[0][0], g2acc[0][1]), fgnn_pack2(g2acc[0][2], g2acc[0][3]),
+                                                       fgnn_pack2(g2acc[1][0], g2acc[1][1]), fgnn_pack2(g2acc[1][2], g2acc[1][3]));
+            *reinterpret_cast<uint4*>(gp + 8) = make_uint4(fgnn_pack2(g2acc[2][0], g2acc[2][1]), fgnn_pack2(g2acc[2][2], g2acc[2][3]),
+                                                           fgnn_pack2(g2acc[3][0], g2acc[3][1]), fgnn_pack2(g2acc[3][2], g2acc[3][3]));
         }
         if (MODE == 3) load_e(it + DEPTH, ring_e[d]);
       }
@@ -928,7 +915,7 @@ __global__ __launch_bounds__(BT_THREADS, 3) void block_head_bwd_kernel(const BhP
         float w[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) w[u] = wp[(int64_t)u * CIN];
-        Wf[f] = make_uint4(bt_pack2(w[0], w[1]), bt_pack2(w[2], w[3]), bt_pack2(w[4], w[5]), bt_pack2(w[6], w[7]));
+        Wf[f] = make_uint4(fgnn_pack2(w[0], w[1]), fgnn_pack2(w[2], w[3]), fgnn_pack2(w[4], w[5]), fgnn_pack2(w[6], w[7]));
     }
     if (tid < 64) {
         const float m = p.mean[tid], is = p.invstd[tid], kc = p.gamma[tid] * is;
@@ -978,7 +965,7 @@ __global__ __launch_bounds__(BT_THREADS, 3) void block_head_bwd_kernel(const BhP
         uint4 (&gq)[2] = rgq[d];
         const int row = (first + it * stride) * 16 + li;
         const bool ok = it < mine && row < R;
-        bt_bf16x8 gzf[2];
+        bf16x8 gzf[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             float z[8], g[8];
@@ -995,11 +982,11 @@ __global__ __launch_bounds__(BT_THREADS, 3) void block_head_bwd_kernel(const BhP
                     const float ge = pre > 0.f ? g[2 * u + h] : g[2 * u + h] * p.slope;
                     v[h] = fmaf(s1[c], ge, fmaf(ka[c], z[2 * u + h], kb[c]));
                 }
-                o[u] = bt_pack2(v[0], v[1]);
+                o[u] = fgnn_pack2(v[0], v[1]);
             }
             uint4 q = make_uint4(o[0], o[1], o[2], o[3]);
             if (!ok) q = make_uint4(0, 0, 0, 0);
-            gzf[ks] = __builtin_bit_cast(bt_bf16x8, q);
+            gzf[ks] = __builtin_bit_cast(bf16x8, q);
             if (ok && cg == 0) *reinterpret_cast<uint4*>(p.gz + (int64_t)row * 64 + 16 * lk + 8 * ks) = q;
         }
         load2(it + HD, rz[d], rgq[d]);
@@ -1011,14 +998,14 @@ __global__ __launch_bounds__(BT_THREADS, 3) void block_head_bwd_kernel(const BhP
             acc[ot] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bt_bf16x8, aW[ot][ks]), gzf[ks], acc[ot], 0, 0, 0);
+                acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, aW[ot][ks]), gzf[ks], acc[ot], 0, 0, 0);
         }
         if (ok) {     // acc[ot][r] = gx of input channel 64 cg + 16 lk + 4 ot + r, row li
             uint16_t* op = p.gx + (int64_t)row * CIN + 64 * cg + 16 * lk;
-            *reinterpret_cast<uint4*>(op) = make_uint4(bt_pack2(acc[0][0], acc[0][1]), bt_pack2(acc[0][2], acc[0][3]),
-                                                      bt_pack2(acc[1][0], acc[1][1]), bt_pack2(acc[1][2], acc[1][3]));
-            *reinterpret_cast<uint4*>(op + 8) = make_uint4(bt_pack2(acc[2][0], acc[2][1]), bt_pack2(acc[2][2], acc[2][3]),
-                                                          bt_pack2(acc[3][0], acc[3][1]), bt_pack2(acc[3][2], acc[3][3]));
+            *reinterpret_cast<uint4*>(op) = make_uint4(fgnn_pack2(acc[0][0], acc[0][1]), fgnn_pack2(acc[0][2], acc[0][3]),
+                                                      fgnn_pack2(acc[1][0], acc[1][1]), fgnn_pack2(acc[1][2], acc[1][3]));
+            *reinterpret_cast<uint4*>(op + 8) = make_uint4(fgnn_pack2(acc[2][0], acc[2][1]), fgnn_pack2(acc[2][2], acc[2][3]),
+                                                          fgnn_pack2(acc[3][0], acc[3][1]), fgnn_pack2(acc[3][2], acc[3][3]));
         }
       }
     }

@@ -13,6 +13,7 @@
 // partial sums live in registers) + two tiny finalisers; partials of the ~1000 workgroups go through a
 // workspace, never through atomics.  Replaces 4 ATen kernels + 2 activation kernels per layer per step.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "fgnn_gridfold.h"
 #include <stdlib.h>
 
@@ -72,14 +73,7 @@ template <> struct Chunk<bf16_t> {
         v[6] = __uint_as_float(t.w << 16); v[7] = __uint_as_float(t.w & 0xffff0000u);
     }
     __device__ static void store(bf16_t* p, const float (&v)[8]) {
-        typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-        uint4 t;
-        b2 q;
-        q[0] = (__bf16)v[0]; q[1] = (__bf16)v[1]; t.x = __builtin_bit_cast(unsigned, q);
-        q[0] = (__bf16)v[2]; q[1] = (__bf16)v[3]; t.y = __builtin_bit_cast(unsigned, q);
-        q[0] = (__bf16)v[4]; q[1] = (__bf16)v[5]; t.z = __builtin_bit_cast(unsigned, q);
-        q[0] = (__bf16)v[6]; q[1] = (__bf16)v[7]; t.w = __builtin_bit_cast(unsigned, q);
-        *reinterpret_cast<uint4*>(p) = t;
+        *reinterpret_cast<uint4*>(p) = make_uint4(fgnn_pack2(v[0], v[1]), fgnn_pack2(v[2], v[3]), fgnn_pack2(v[4], v[5]), fgnn_pack2(v[6], v[7]));
     }
 };
 

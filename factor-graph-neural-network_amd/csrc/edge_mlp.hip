@@ -14,6 +14,7 @@
 //             the workgroup and writes its slab; a second kernel sums the slabs in a fixed order.  The inputs
 //             (edge features) need no gradient.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include <stdlib.h>
 
 #define EM_THREADS 256
@@ -44,9 +45,6 @@ struct EmParams {
 };
 
 __device__ __forceinline__ float em_ld(const uint16_t* p) { return __uint_as_float((unsigned)*p << 16); }
-__device__ __forceinline__ float em_bcast(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
 // lane u <- the weight record of hidden unit u
 __device__ __forceinline__ void em_load_rec(const EmParams& p, int u, float (&w)[EM_REC]) {
 #pragma unroll
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(EM_THREADS) void edge_mlp_fwd_kernel(const EmParams
         for (int u = 0; u < EM_HID; ++u) {
             float s[EM_REC];
 #pragma unroll
-            for (int j = 0; j < EM_REC; ++j) s[j] = em_bcast(wr[j], u);
+            for (int j = 0; j < EM_REC; ++j) s[j] = fgnn_bcast(wr[j], u);
 #pragma unroll
             for (int i = 0; i < EM_RPT / 2; ++i) {
                 em_f2 h = {s[8], s[8]};
@@ -128,11 +126,8 @@ __global__ __launch_bounds__(EM_THREADS) void edge_mlp_fwd_kernel(const EmParams
 
 // sum of v over the wave, in every lane (a fixed tree: quad, row of 16 by mirrors, then the 4 rows in order)
 __device__ __forceinline__ float em_wave_sum(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));   // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));   // row_mirror
-    return (em_bcast(v, 0) + em_bcast(v, 16)) + (em_bcast(v, 32) + em_bcast(v, 48));
+    v = fgnn_row_sum(v);
+    return (fgnn_bcast(v, 0) + fgnn_bcast(v, 16)) + (fgnn_bcast(v, 32) + fgnn_bcast(v, 48));
 }
 
 // Workgroup = 8 waves over one block of rows staged in LDS (bf16, 24 B a row).  The 16 blocks of 4 hidden units are
@@ -179,7 +174,7 @@ __global__ __launch_bounds__(EM_BWD_THREADS) void edge_mlp_bwd_kernel(const EmPa
 #pragma unroll
         for (int i = 0; i < EM_UB; ++i)
 #pragma unroll
-            for (int j = 0; j < EM_REC; ++j) s[i][j] = em_bcast(wr[j], u0 + i);
+            for (int j = 0; j < EM_REC; ++j) s[i][j] = fgnn_bcast(wr[j], u0 + i);
         float a2[EM_UB][EM_MAXE], a1[EM_UB][CIN], ab[EM_UB], sb2[EM_MAXE] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < EM_UB; ++i) {
@@ -245,9 +240,8 @@ __global__ __launch_bounds__(EM_BWD_THREADS) void edge_mlp_bwd_kernel(const EmPa
 // Precision: x / gy are bf16 already; every f32 quantity that enters a product (W1, W2, H, dH) goes in as bf16 hi + bf16 lo (two
 // MFMAs): 2^-17 relative, f32 accumulation — the tests' bounds (2^-8 of the output, 1e-4 of the gradients) are those of the VALU form.
 // ----------------------------------------------------------------------------------------
-typedef short em_s4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void em_split4(const float (&v)[4], em_s4& hi, em_s4& lo) {
+__device__ __forceinline__ void em_split4(const float (&v)[4], s16x4& hi, s16x4& lo) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const __bf16 h = (__bf16)v[r];
@@ -313,7 +307,7 @@ __global__ __launch_bounds__(256) void edge_mlp_fwd_mfma_kernel(const EmParams p
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, kg = lane >> 4;
     const int Cin = p.Cin, net = p.net, E = p.E;
     // resident operands: W1 rows as A (i = hidden, k = channel), W2 rows as A (i = q, k = hidden); hi / lo halves
-    em_s4 a1h[4], a1l[4], a2h[4], a2l[4];
+    s16x4 a1h[4], a1l[4], a2h[4], a2l[4];
     float bias1[4][4], bias2[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -344,7 +338,7 @@ __global__ __launch_bounds__(256) void edge_mlp_fwd_mfma_kernel(const EmParams p
             const int64_t b = pair * EM_PAIR + smp;
             if (b >= B) continue;                            // (wave-uniform)
             const uint16_t* xp = xs + smp * (EM_MAXC * EM_MAXE_ROWS) + tl * 16 + li;
-            em_s4 bx;                                        // X^T as B: lane (row li, k-group kg) holds channels 4 kg .. 4 kg + 3
+            s16x4 bx;                                        // X^T as B: lane (row li, k-group kg) holds channels 4 kg .. 4 kg + 3
 #pragma unroll
             for (int r = 0; r < 4; ++r) { const int c = 4 * kg + r; bx[r] = c < Cin ? (short)xp[c * E] : (short)0; }
             f32x4 y = {0.f, 0.f, 0.f, 0.f};
@@ -355,7 +349,7 @@ __global__ __launch_bounds__(256) void edge_mlp_fwd_mfma_kernel(const EmParams p
                 float hv[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) hv[r] = fmaxf(h[r] + bias1[t][r], 0.f);
-                em_s4 hh, hl;
+                s16x4 hh, hl;
                 em_split4(hv, hh, hl);
                 y = EM_MMA(a2h[t], hh, y);
                 y = EM_MMA(a2h[t], hl, y);
@@ -382,7 +376,7 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_mfma_kernel(const EmParams p
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, kg = lane >> 4;
     const int Cin = p.Cin, net = p.net, E = p.E;
     // resident operands: W1^T as B (k = channel, j = hidden li), W2 as B (k = q, j = hidden li)
-    em_s4 b1h[4], b1l[4], b2h[4], b2l[4];
+    s16x4 b1h[4], b1l[4], b2h[4], b2l[4];
     float bias1[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -415,7 +409,7 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_mfma_kernel(const EmParams p
             if (pair * EM_PAIR + smp >= B) continue;
             const uint16_t* xp = xs + smp * (EM_MAXC * EM_MAXE_ROWS) + tl * 16;
             const uint16_t* gp = gs + smp * (EM_MAXE * EM_MAXE_ROWS) + tl * 16;
-            em_s4 ax, ay, bxr, ayt;
+            s16x4 ax, ay, bxr, ayt;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {                   // this lane's row li: channels 4 kg .. (A of H = X W1^T), net gradients (A of dH = dY W2)
                 const int c = 4 * kg + r;
@@ -425,8 +419,8 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_mfma_kernel(const EmParams p
             {   // rows 4 kg .. 4 kg + 3 of the tile: channel li of x (B of dW1^T = dH^T X), net gradient li (A of dW2 = dY^T H)
                 const uint2 vxr = li < Cin ? *reinterpret_cast<const uint2*>(xp + li * E + 4 * kg) : make_uint2(0, 0);
                 const uint2 vgr = li < net ? *reinterpret_cast<const uint2*>(gp + li * E + 4 * kg) : make_uint2(0, 0);
-                bxr = __builtin_bit_cast(em_s4, vxr);
-                ayt = __builtin_bit_cast(em_s4, vgr);
+                bxr = __builtin_bit_cast(s16x4, vxr);
+                ayt = __builtin_bit_cast(s16x4, vgr);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) db2 += __uint_as_float((unsigned)(uint16_t)ayt[r] << 16);      // (lanes li < net: q = li, rows of k-group kg)
@@ -444,7 +438,7 @@ __global__ __launch_bounds__(256) void edge_mlp_bwd_mfma_kernel(const EmParams p
                     gv[r] = pre > 0.f ? g[r] : 0.f;
                     db1[t] += gv[r];
                 }
-                em_s4 gh, gl, hh, hl;
+                s16x4 gh, gl, hh, hl;
                 em_split4(gv, gh, gl);
                 em_split4(hv, hh, hl);
                 dW1[t] = EM_MMA(gh, bxr, dW1[t]);           // D[i = hidden 16 t + 4 kg + r][j = channel li]

@@ -36,6 +36,7 @@
 // dominate.  HBM would allow 21 us: the next step is a software pipeline over samples (projection of sample s + 1 under
 // the gather of sample s, as csrc/mpconv_fwd_sg.hip does for the bare operator).
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -52,8 +53,6 @@
 #endif
 #define FL_EPS 1e-5f
 
-typedef __bf16 fl_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 fl_bf16x2 __attribute__((ext_vector_type(2)));
 
 // packed f32 parameters (floats): two maps, then four blocks (V->F parity, F->V parity, V->F hyper, F->V hyper)
 #define FL_MAP_LEN (64 * 64)
@@ -108,57 +107,16 @@ extern __shared__ __attribute__((aligned(16))) unsigned char fl_lds[];
 #define FL_STAMP(slot) do { } while (0)
 #endif
 
-__device__ __forceinline__ unsigned fl_pack2(float a, float b) {
-    const fl_bf16x2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
 __device__ __forceinline__ float fl_round(float a) {
     const __bf16 h = (__bf16)a;
     return __uint_as_float((unsigned)__builtin_bit_cast(uint16_t, h) << 16);
-}
-__device__ __forceinline__ float fl_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float fl_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ fl_bf16x8 fl_frag8(const float* p8) {            // 8 consecutive f32 -> one fragment
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p8), b = *reinterpret_cast<const f32x4*>(p8 + 4);
-    return __builtin_bit_cast(fl_bf16x8, make_uint4(fl_pack2(a[0], a[1]), fl_pack2(a[2], a[3]), fl_pack2(b[0], b[1]), fl_pack2(b[2], b[3])));
-}
-// uniform 64-bit base + UNSIGNED 32-bit per-lane byte offset: the form that compiles to `global_load v, v_off, s[base]`.  Per-lane 64-bit
-// pointers are hoisted out of the sample loop and SPILLED at this kernel's 256 VGPRs — and a spill reload is a memory operation that waits
-// (vmcnt(0)) for every load issued before it: the next sample's prefetch then paid two or three HBM round trips back to back, ~3 000
-// cycles per sample (round 6: profiles/r06/infer_layer_phase_timeline.txt, phase 7 -> 8).
-template <typename T> __device__ __forceinline__ const T* fl_at(const void* base, unsigned byte_off) {
-    return reinterpret_cast<const T*>(static_cast<const char*>(base) + byte_off);
-}
-template <typename T> __device__ __forceinline__ T* fl_at(void* base, unsigned byte_off) {
-    return reinterpret_cast<T*>(static_cast<char*>(base) + byte_off);
-}
-// LDS-DMA piece: 64 lanes x 16 B of global memory -> lds_dst + 16 lane, no registers in between (the idiom of mpconv_bwd_ws.hip)
-__device__ __forceinline__ void fl_dma16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// sum / max over the 16 lanes of a DPP row (the 16 nodes of a tile)
-__device__ __forceinline__ float fl_row_sum(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));
-    return v;
-}
-__device__ __forceinline__ float fl_row_max(float v) {
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0xB1, 0xF, 0xF, false)));
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x4E, 0xF, 0xF, false)));
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x141, 0xF, 0xF, false)));
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x140, 0xF, 0xF, false)));
-    return v;
 }
 
 // D[i = out channel][j = node] = W (A operand, resident) x image rows (B operand), K = 64: ALL tiles of this wave at once —
 // operand loads first, then the first k-step of every tile, then the second (independent MFMA chains).  WIDE: the 96-row
 // images (tiles hf, hf + 2, hf + 4); otherwise the 48-row ones (tiles hf, hf + 2 where < 3; the rest stay 0).
 template <bool WIDE>
-__device__ __forceinline__ void fl_tiles(const fl_bf16x8 (&aW)[2], const uint16_t* img, int hf, int li, int lk, f32x4 (&acc)[3]) {
+__device__ __forceinline__ void fl_tiles(const bf16x8 (&aW)[2], const uint16_t* img, int hf, int li, int lk, f32x4 (&acc)[3]) {
     constexpr int NT = WIDE ? 3 : 2;
     uint4 x[NT][2];
     int base = (hf * 16 + li) * FL_XS + 8 * lk;       // recomputed per call (opaque): the tiles are constant offsets from it, and
@@ -178,7 +136,7 @@ __device__ __forceinline__ void fl_tiles(const fl_bf16x8 (&aW)[2], const uint16_
 #pragma unroll
         for (int i = 0; i < NT; ++i)
             if (WIDE || hf + 2 * i < 3)
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aW[ks], __builtin_bit_cast(fl_bf16x8, x[i][ks]), acc[i], 0, 0, 0);
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aW[ks], __builtin_bit_cast(bf16x8, x[i][ks]), acc[i], 0, 0, 0);
 }
 
 // gather + edge-type contraction + max over KC neighbours, then a2 = ReLU(s2 z + t2) as bf16 into `dst` rows (lane <-> channel);
@@ -214,8 +172,8 @@ __device__ __forceinline__ void fl_gather(const uint16_t* ps, const int* off_s, 
             float best = 0.f;
 #pragma unroll
             for (int j = 0; j < KC; ++j) {
-                float v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(fl_bf16x2, pk[d][j].x), __builtin_bit_cast(fl_bf16x2, ew[d][j].x), 0.f, false);
-                v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(fl_bf16x2, pk[d][j].y), __builtin_bit_cast(fl_bf16x2, ew[d][j].y), v, false);
+                float v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk[d][j].x), __builtin_bit_cast(bf16x2, ew[d][j].x), 0.f, false);
+                v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk[d][j].y), __builtin_bit_cast(bf16x2, ew[d][j].y), v, false);
                 best = j == 0 ? v : fmaxf(best, v);
             }
             const __bf16 h = (__bf16)fmaxf(fmaf(best, c2s, c2t), 0.f);
@@ -259,20 +217,20 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
     const float* b3 = w + FL_OFF_B3;      // F -> V hyper (fan-out)
 
     // ---- resident fragments: A[i = out channel][k = in channel] = W[out][in] ----
-    fl_bf16x8 aW1a[2], aW2a[2], aW1b[2], aW2b[2], aW1c[2], aW2d[2], aFa[2][2], aFb[2][2], aFc[2];
+    bf16x8 aW1a[2], aW2a[2], aW1b[2], aW2b[2], aW1c[2], aW2d[2], aFa[2][2], aFb[2][2], aFc[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
         const int o = (ot * 16 + li) * 64 + 32 * ks + 8 * lk;
         if (hf == 0) {                                  // the maps' fragments wait in LDS, in fragment order (used once per sample)
-            wmap[((0 * 2 + ks) * 4 + ot) * 64 + lane] = __builtin_bit_cast(uint4, fl_frag8(w + FL_OFF_WVV + o));
-            wmap[((1 * 2 + ks) * 4 + ot) * 64 + lane] = __builtin_bit_cast(uint4, fl_frag8(w + FL_OFF_WFF + o));
+            wmap[((0 * 2 + ks) * 4 + ot) * 64 + lane] = __builtin_bit_cast(uint4, fgnn_frag8(w + FL_OFF_WVV + o));
+            wmap[((1 * 2 + ks) * 4 + ot) * 64 + lane] = __builtin_bit_cast(uint4, fgnn_frag8(w + FL_OFF_WFF + o));
         }
-        aW1a[ks] = fl_frag8(b0 + FL_W1 + o);
-        aW2a[ks] = fl_frag8(b0 + FL_W2(256) + o);
-        aW1b[ks] = fl_frag8(b1 + FL_W1 + o);
-        aW2b[ks] = fl_frag8(b1 + FL_W2(256) + o);
-        aW1c[ks] = fl_frag8(b2 + FL_W1 + o);
-        aW2d[ks] = fl_frag8(b3 + FL_W2(64) + o);
+        aW1a[ks] = fgnn_frag8(b0 + FL_W1 + o);
+        aW2a[ks] = fgnn_frag8(b0 + FL_W2(256) + o);
+        aW1b[ks] = fgnn_frag8(b1 + FL_W1 + o);
+        aW2b[ks] = fgnn_frag8(b1 + FL_W2(256) + o);
+        aW1c[ks] = fgnn_frag8(b2 + FL_W1 + o);
+        aW2d[ks] = fgnn_frag8(b3 + FL_W2(64) + o);
     }
     // operator filters: A[i = column][k = c] = F[c][column]; parity: column slabs wave and wave + 8 of 16; fan-in: slab ot of 4
 #pragma unroll
@@ -285,15 +243,15 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
                 wa[u] = b0[FL_F + (32 * ks + 8 * lk + u) * 256 + (wave + 8 * q) * 16 + li];
                 wb[u] = b1[FL_F + (32 * ks + 8 * lk + u) * 256 + (wave + 8 * q) * 16 + li];
             }
-            aFa[q][ks] = __builtin_bit_cast(fl_bf16x8, make_uint4(fl_pack2(wa[0], wa[1]), fl_pack2(wa[2], wa[3]), fl_pack2(wa[4], wa[5]), fl_pack2(wa[6], wa[7])));
-            aFb[q][ks] = __builtin_bit_cast(fl_bf16x8, make_uint4(fl_pack2(wb[0], wb[1]), fl_pack2(wb[2], wb[3]), fl_pack2(wb[4], wb[5]), fl_pack2(wb[6], wb[7])));
+            aFa[q][ks] = __builtin_bit_cast(bf16x8, make_uint4(fgnn_pack2(wa[0], wa[1]), fgnn_pack2(wa[2], wa[3]), fgnn_pack2(wa[4], wa[5]), fgnn_pack2(wa[6], wa[7])));
+            aFb[q][ks] = __builtin_bit_cast(bf16x8, make_uint4(fgnn_pack2(wb[0], wb[1]), fgnn_pack2(wb[2], wb[3]), fgnn_pack2(wb[4], wb[5]), fgnn_pack2(wb[6], wb[7])));
         }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
         float wc[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) wc[u] = b2[FL_F + (32 * ks + 8 * lk + u) * 64 + ot * 16 + li];
-        aFc[ks] = __builtin_bit_cast(fl_bf16x8, make_uint4(fl_pack2(wc[0], wc[1]), fl_pack2(wc[2], wc[3]), fl_pack2(wc[4], wc[5]), fl_pack2(wc[6], wc[7])));
+        aFc[ks] = __builtin_bit_cast(bf16x8, make_uint4(fgnn_pack2(wc[0], wc[1]), fgnn_pack2(wc[2], wc[3]), fgnn_pack2(wc[4], wc[5]), fgnn_pack2(wc[6], wc[7])));
     }
     // ---- LDS-resident: the hyper-factor's matrix-vector maps, the shared tables ----
     for (int f = tid; f < 64 * 64; f += FL_THREADS) {
@@ -324,8 +282,8 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
         aff[f] = bb[off + c];
     }
     for (int t = tid; t < FL_NV; t += FL_THREADS) {
-        het_in[t] = p.het_v2f ? fl_lo(p.het_v2f[t]) : 1.f;
-        het_out[t] = p.het_f2v ? fl_lo(p.het_f2v[t]) : 1.f;
+        het_in[t] = p.het_v2f ? fgnn_lo(p.het_v2f[t]) : 1.f;
+        het_out[t] = p.het_f2v ? fgnn_lo(p.het_f2v[t]) : 1.f;
     }
 
     // per-lane affines of the wave's conv tiles (channels ot * 16 + 4 lk + r) and of the gathers (lane <-> channel)
@@ -350,16 +308,16 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
         asm volatile("" : "+v"(t), "+v"(l16));                          // the lane offsets are formed here, not carried across the loop
         if (wave < 6) {                                                 // 12 pieces of the variables' state, 6 of the checks'
 #pragma unroll
-            for (int u = 0; u < 2; ++u) fl_dma16(vb + (wave * 2 + u) * 1024 + l16, lds_stage + (unsigned)((wave * 2 + u) * 1024));
+            for (int u = 0; u < 2; ++u) fgnn_dma16(vb + (wave * 2 + u) * 1024 + l16, lds_stage + (unsigned)((wave * 2 + u) * 1024));
         } else {
 #pragma unroll
-            for (int u = 0; u < 3; ++u) fl_dma16(fb + ((wave - 6) * 3 + u) * 1024 + l16, lds_stage + (unsigned)(12288 + ((wave - 6) * 3 + u) * 1024));
+            for (int u = 0; u < 3; ++u) fgnn_dma16(fb + ((wave - 6) * 3 + u) * 1024 + l16, lds_stage + (unsigned)(12288 + ((wave - 6) * 3 + u) * 1024));
         }
         // UNCONDITIONAL loads (threads beyond an array re-read its first element; commit() stores under the conditions): a load in one
         // arm of a branch meets the other arm's value at the merge, and the wave waits for it there
-        e0r = *fl_at<uint2>(e0b, tid < FL_NF * FL_KF ? t * 8u : 0u);
-        e1r = *fl_at<uint2>(e1b, tid < FL_NV * FL_KV ? t * 8u : 0u);
-        hr = *fl_at<uint16_t>(hb, (t & 63u) * 2u);
+        e0r = *fgnn_at<uint2>(e0b, tid < FL_NF * FL_KF ? t * 8u : 0u);
+        e1r = *fgnn_at<uint2>(e1b, tid < FL_NV * FL_KV ? t * 8u : 0u);
+        hr = *fgnn_at<uint16_t>(hb, (t & 63u) * 2u);
     };
     auto commit = [&]() {                              // (behind a barrier that follows `s_waitcnt vmcnt(0)` on every wave: the DMA has landed)
         const uint4* st = reinterpret_cast<const uint4*>(ps);
@@ -371,7 +329,7 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
         if (tid < 384) *reinterpret_cast<uint4*>(fs + row) = st[768 + t];
         if (tid < FL_NF * FL_KF) et_vf[tid] = e0r;
         if (tid < FL_NV * FL_KV) et_fv[tid] = e1r;
-        if (tid < 64) hv[tid] = fl_lo(hr);
+        if (tid < 64) hv[tid] = fgnn_lo(hr);
     };
 
     int b = blockIdx.x;
@@ -385,9 +343,9 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
         if (p.residual) u += hv[lane];
         unsigned l2 = (unsigned)lane * 2u;
         asm volatile("" : "+v"(l2));
-        if (p.skip_fac1) u += fl_lo(skh);                 // (requested with the sample's other skip terms, a phase before the sample ended)
+        if (p.skip_fac1) u += fgnn_lo(skh);                 // (requested with the sample's other skip terms, a phase before the sample ended)
         const __bf16 h = (__bf16)u;
-        *fl_at<uint16_t>(p.out_fac1 + (int64_t)bp * 64, l2) = __builtin_bit_cast(uint16_t, h);
+        *fgnn_at<uint16_t>(p.out_fac1 + (int64_t)bp * 64, l2) = __builtin_bit_cast(uint16_t, h);
     };
     int b_prev = -1;
     for (; b < p.B; b += gridDim.x) {
@@ -414,7 +372,7 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
             for (int r = 0; r < 4; ++r) { const float u = fmaf(acc[r], s4[r], t4[r]); v[r] = u > 0.f ? u : u * slope; }
         };
         // conv1 of a block: image rows -> image A (bf16)
-        auto conv1 = [&](auto wide, const fl_bf16x8 (&aW)[2], const uint16_t* img, int blk) {
+        auto conv1 = [&](auto wide, const bf16x8 (&aW)[2], const uint16_t* img, int blk) {
             constexpr bool WIDE = decltype(wide)::value;
             f32x4 acc[3], s4, t4;
             fl_tiles<WIDE>(aW, img, hf, li, lk, acc);
@@ -426,12 +384,12 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
                 if (WIDE || hf + 2 * i < 3) {
                     float v[4];
                     act4(acc[i], s4, t4, v);
-                    *reinterpret_cast<uint2*>(as_ + sb + 2 * i * 16 * FL_XS) = make_uint2(fl_pack2(v[0], v[1]), fl_pack2(v[2], v[3]));
+                    *reinterpret_cast<uint2*>(as_ + sb + 2 * i * 16 * FL_XS) = make_uint2(fgnn_pack2(v[0], v[1]), fgnn_pack2(v[2], v[3]));
                 }
             }
         };
         // projection of image A onto the 256 operator columns -> P (bf16): three node tiles x two column slabs in flight
-        auto project = [&](const fl_bf16x8 (&aF)[2][2], int ntile) {
+        auto project = [&](const bf16x8 (&aF)[2][2], int ntile) {
             for (int n0 = 0; n0 < ntile; n0 += 3) {
                 uint4 x[3][2];
                 int rb = (n0 * 16 + li) * FL_XS + 8 * lk, wb = (n0 * 16 + li) * FL_PS + wave * 16 + 4 * lk;
@@ -453,13 +411,13 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
                     for (int t = 0; t < 3; ++t)
 #pragma unroll
                         for (int q = 0; q < 2; ++q)
-                            acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aF[q][ks], __builtin_bit_cast(fl_bf16x8, x[t][ks]), acc[t][q], 0, 0, 0);
+                            acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aF[q][ks], __builtin_bit_cast(bf16x8, x[t][ks]), acc[t][q], 0, 0, 0);
 #pragma unroll
                 for (int t = 0; t < 3; ++t)
 #pragma unroll
                     for (int q = 0; q < 2; ++q)
                         *reinterpret_cast<uint2*>(ps + wb + t * 16 * FL_PS + 8 * q * 16) =
-                            make_uint2(fl_pack2(acc[t][q][0], acc[t][q][1]), fl_pack2(acc[t][q][2], acc[t][q][3]));
+                            make_uint2(fgnn_pack2(acc[t][q][0], acc[t][q][1]), fgnn_pack2(acc[t][q][2], acc[t][q][3]));
             }
         };
         const std::integral_constant<bool, true> wide_img;
@@ -468,11 +426,11 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
         // ---- phase 1: the node-wise maps, InstanceNorm over the nodes, ReLU; conv1 of the V -> F parity block ----
         {
             f32x4 yv[3], yf[2];
-            fl_bf16x8 aVV[2], aFF[2];
+            bf16x8 aVV[2], aFF[2];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                aVV[ks] = __builtin_bit_cast(fl_bf16x8, wmap[((0 * 2 + ks) * 4 + ot) * 64 + lane]);
-                aFF[ks] = __builtin_bit_cast(fl_bf16x8, wmap[((1 * 2 + ks) * 4 + ot) * 64 + lane]);
+                aVV[ks] = __builtin_bit_cast(bf16x8, wmap[((0 * 2 + ks) * 4 + ot) * 64 + lane]);
+                aFF[ks] = __builtin_bit_cast(bf16x8, wmap[((1 * 2 + ks) * 4 + ot) * 64 + lane]);
             }
             float sv[4] = {0.f, 0.f, 0.f, 0.f}, qv[4] = {0.f, 0.f, 0.f, 0.f}, sf[4] = {0.f, 0.f, 0.f, 0.f}, qf[4] = {0.f, 0.f, 0.f, 0.f};
             {
@@ -491,7 +449,7 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
                 for (int r = 0; r < 4; ++r) { sf[r] += yf[i][r]; qf[r] = fmaf(yf[i][r], yf[i][r], qf[r]); }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                sv[r] = fl_row_sum(sv[r]); qv[r] = fl_row_sum(qv[r]); sf[r] = fl_row_sum(sf[r]); qf[r] = fl_row_sum(qf[r]);
+                sv[r] = fgnn_row_sum(sv[r]); qv[r] = fgnn_row_sum(qv[r]); sf[r] = fgnn_row_sum(sf[r]); qf[r] = fgnn_row_sum(qf[r]);
             }
             if (li == 0) {
 #pragma unroll
@@ -506,7 +464,7 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
                 // waves by input channel (lane <-> output channel); the partials meet after the barrier
                 float part = 0.f;
 #pragma unroll
-                for (int i = 0; i < 8; ++i) part = fmaf(hv[8 * wave + i], fl_lo(W1d[(8 * wave + i) * 64 + lane]), part);
+                for (int i = 0; i < 8; ++i) part = fmaf(hv[8 * wave + i], fgnn_lo(W1d[(8 * wave + i) * 64 + lane]), part);
                 mvp[wave * 64 + lane] = part;
             }
             __syncthreads();
@@ -542,7 +500,7 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
             float part = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                part = fmaf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(fo_a1), 8 * wave + i)), fl_lo(Fd[(8 * wave + i) * 64 + lane]), part);
+                part = fmaf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(fo_a1), 8 * wave + i)), fgnn_lo(Fd[(8 * wave + i) * 64 + lane]), part);
             mvp[wave * 64 + lane] = part;
         }
         __syncthreads();
@@ -614,7 +572,7 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
                 for (int r = 0; r < 4; ++r) zm[r] = fmaxf(zm[r], e * fl_round(acc[i][r]));
             }
 #pragma unroll
-            for (int r = 0; r < 4; ++r) zm[r] = fl_row_max(zm[r]);
+            for (int r = 0; r < 4; ++r) zm[r] = fgnn_row_max(zm[r]);
             if (li == 0) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) zpart[hf * 64 + ch4 + r] = zm[r];
@@ -624,7 +582,7 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
             const int m = f >> 5, c2 = (f & 31) * 2;
             const float e = het_out[m];
             const float v0 = fmaxf(fmaf(e, hv[64 + c2], hv[128 + c2]), 0.f), v1 = fmaxf(fmaf(e, hv[65 + c2], hv[129 + c2]), 0.f);
-            *reinterpret_cast<unsigned*>(bs + m * FL_XS + c2) = fl_pack2(v0, v1);
+            *reinterpret_cast<unsigned*>(bs + m * FL_XS + c2) = fgnn_pack2(v0, v1);
         }
         __syncthreads();
         FL_STAMP(9);
@@ -638,13 +596,13 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
             const uint16_t* sv_ = (p.skip_var ? p.skip_var : p.var) + (int64_t)b * FL_NV * 64;
             const uint16_t* sf_ = (p.skip_fac0 ? p.skip_fac0 : p.fac0) + (int64_t)b * FL_NF * 64;
 #pragma unroll
-            for (int i = 0; i < 3; ++i) skv[i] = *fl_at<uint2>(sv_, eo + 4096u * i);
+            for (int i = 0; i < 3; ++i) skv[i] = *fgnn_at<uint2>(sv_, eo + 4096u * i);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
-                if (hf + 2 * i < 3) skf[i] = *fl_at<uint2>(sf_, eo + 4096u * i);
+                if (hf + 2 * i < 3) skf[i] = *fgnn_at<uint2>(sf_, eo + 4096u * i);
             unsigned l2 = (unsigned)lane * 2u;
             asm volatile("" : "+v"(l2));
-            skh = *fl_at<uint16_t>((p.skip_fac1 ? p.skip_fac1 : p.fac1) + (int64_t)b * 64, l2);
+            skh = *fgnn_at<uint16_t>((p.skip_fac1 ? p.skip_fac1 : p.fac1) + (int64_t)b * 64, l2);
         }
         // ---- phase 10: the fan-out block's conv2 onto the variables; residual, skip link, store; wave 0 first closes the
         //      fan-in block (the hyper-factor's new state: a matrix-vector product) ----
@@ -655,7 +613,7 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
             float part = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                part = fmaf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(z), 8 * wave + i)), fl_lo(W2c[(8 * wave + i) * 64 + lane]), part);
+                part = fmaf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(z), 8 * wave + i)), fgnn_lo(W2c[(8 * wave + i) * 64 + lane]), part);
             mvp[wave * 64 + lane] = part;
         }
         int rsb;
@@ -675,10 +633,10 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
                 for (int r = 0; r < 4; ++r) v[r] += oV[i][r];
                 if (p.residual) {
                     const uint2 a = *reinterpret_cast<const uint2*>(vs + rsb + 2 * i * 16 * FL_XS);
-                    v[0] += fl_lo(a.x); v[1] += fl_hi(a.x); v[2] += fl_lo(a.y); v[3] += fl_hi(a.y);
+                    v[0] += fgnn_lo(a.x); v[1] += fgnn_hi(a.x); v[2] += fgnn_lo(a.y); v[3] += fgnn_hi(a.y);
                 }
-                if (p.skip_var) { v[0] += fl_lo(skv[i].x); v[1] += fl_hi(skv[i].x); v[2] += fl_lo(skv[i].y); v[3] += fl_hi(skv[i].y); }
-                *fl_at<uint2>(p.out_var + (int64_t)b * FL_NV * 64, eo + 4096u * i) = make_uint2(fl_pack2(v[0], v[1]), fl_pack2(v[2], v[3]));
+                if (p.skip_var) { v[0] += fgnn_lo(skv[i].x); v[1] += fgnn_hi(skv[i].x); v[2] += fgnn_lo(skv[i].y); v[3] += fgnn_hi(skv[i].y); }
+                *fgnn_at<uint2>(p.out_var + (int64_t)b * FL_NV * 64, eo + 4096u * i) = make_uint2(fgnn_pack2(v[0], v[1]), fgnn_pack2(v[2], v[3]));
             }
         }
 #pragma unroll
@@ -688,10 +646,10 @@ __global__ __launch_bounds__(FL_THREADS) void factor_layer_fwd_kernel(const FlPa
                 float v[4] = {oF[i][0], oF[i][1], oF[i][2], oF[i][3]};
                 if (p.residual) {
                     const uint2 a = *reinterpret_cast<const uint2*>(fs + rsb + 2 * i * 16 * FL_XS);
-                    v[0] += fl_lo(a.x); v[1] += fl_hi(a.x); v[2] += fl_lo(a.y); v[3] += fl_hi(a.y);
+                    v[0] += fgnn_lo(a.x); v[1] += fgnn_hi(a.x); v[2] += fgnn_lo(a.y); v[3] += fgnn_hi(a.y);
                 }
-                if (p.skip_fac0) { v[0] += fl_lo(skf[i].x); v[1] += fl_hi(skf[i].x); v[2] += fl_lo(skf[i].y); v[3] += fl_hi(skf[i].y); }
-                *fl_at<uint2>(p.out_fac0 + (int64_t)b * FL_NF * 64, eo + 4096u * i) = make_uint2(fl_pack2(v[0], v[1]), fl_pack2(v[2], v[3]));
+                if (p.skip_fac0) { v[0] += fgnn_lo(skf[i].x); v[1] += fgnn_hi(skf[i].x); v[2] += fgnn_lo(skf[i].y); v[3] += fgnn_hi(skf[i].y); }
+                *fgnn_at<uint2>(p.out_fac0 + (int64_t)b * FL_NF * 64, eo + 4096u * i) = make_uint2(fgnn_pack2(v[0], v[1]), fgnn_pack2(v[2], v[3]));
             }
         }
         FL_STAMP(10);

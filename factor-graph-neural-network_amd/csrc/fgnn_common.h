@@ -8,7 +8,6 @@
 #include "fgnn_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 #define FGNN_THREADS 256
 #define FGNN_WAVES 4

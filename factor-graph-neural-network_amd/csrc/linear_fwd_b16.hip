@@ -14,6 +14,7 @@
 // outputs are split over the waves of a workgroup (<= 64 output channels per wave), which then share the x rows
 // through L1.  No barriers in the streaming loop.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "fgnn_gridfold.h"
 #include <stdlib.h>
 
@@ -21,7 +22,6 @@
 #define LF_WAVES 8
 #define LF_MAXGRID 256   // one workgroup per CU (cold tensors, 393 k rows 64->64: 23.9 us; 512: 25.4; 768: 28.3; 1024: 25.6); <= BN_MAXPART of bnact.hip: the statistics partials reuse its workspace layout
 
-typedef __bf16 lf_bf16x8 __attribute__((ext_vector_type(8)));
 
 struct LfParams {
     const uint16_t* x;   // [R][Cin] bf16
@@ -38,19 +38,7 @@ struct LfParams {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char lf_lds[];
 
-__device__ __forceinline__ unsigned lf_pack2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
 
-// uniform 64-bit base + UNSIGNED 32-bit per-lane byte offset: the form that compiles to `global_load v, v_off, s[base]`
-template <typename T> __device__ __forceinline__ const T* lf_at(const void* base, unsigned byte_off) {
-    return reinterpret_cast<const T*>(static_cast<const char*>(base) + byte_off);
-}
-template <typename T> __device__ __forceinline__ T* lf_at(void* base, unsigned byte_off) {
-    return reinterpret_cast<T*>(static_cast<char*>(base) + byte_off);
-}
 
 // KS = Cin / 32 k-steps, OTW = 16-channel output tiles per wave (Cout / 16 / CG), WREG: W fragments in registers
 template <int KS, int OTW, bool WREG>
@@ -78,7 +66,7 @@ __global__ __launch_bounds__(LF_THREADS) void linear_fwd_b16_kernel(const LfPara
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int f = f0 + u * LF_THREADS;
-                if (f < total) { const int o = f / (CIN / 2), c2 = f - o * (CIN / 2); *reinterpret_cast<unsigned*>(Wl + o * WS + 2 * c2) = lf_pack2(w[u].x, w[u].y); }
+                if (f < total) { const int o = f / (CIN / 2), c2 = f - o * (CIN / 2); *reinterpret_cast<unsigned*>(Wl + o * WS + 2 * c2) = fgnn_pack2(w[u].x, w[u].y); }
             }
         }
     } else {                                              // memory is [c][o]: coalesced reads, 2-byte LDS writes
@@ -109,13 +97,13 @@ __global__ __launch_bounds__(LF_THREADS) void linear_fwd_b16_kernel(const LfPara
     auto orow = [&](int ot) { return 64 * (ot >> 2) + 16 * (li >> 2) + 4 * (ot & 3) + (li & 3); };
     auto ocol = [&](int ot) { return 64 * (ot >> 2) + 16 * lk + 4 * (ot & 3); };          // the lane's four channels of tile ot, from o_base
     auto kcol = [&](int ks) { return 8 * KS * lk + 8 * ks; };
-    lf_bf16x8 aW[WREG ? OTW : 1][WREG ? KS : 1];
+    bf16x8 aW[WREG ? OTW : 1][WREG ? KS : 1];
     if constexpr (WREG) {
 #pragma unroll
         for (int ot = 0; ot < OTW; ++ot)
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
-                aW[ot][ks] = __builtin_bit_cast(lf_bf16x8, *reinterpret_cast<const uint4*>(Wl + (o_base + orow(ot)) * WS + kcol(ks)));
+                aW[ot][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Wl + (o_base + orow(ot)) * WS + kcol(ks)));
     }
     f32x4 bv[OTW];
 #pragma unroll
@@ -136,7 +124,7 @@ __global__ __launch_bounds__(LF_THREADS) void linear_fwd_b16_kernel(const LfPara
         const int rl = tl * 16 + li < R ? li : R - 1 - tl * 16;
         const unsigned off = (unsigned)((rl * CIN + kcol(0)) * 2);
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) bx[ks] = *lf_at<uint4>(xt, off + 16u * ks);
+        for (int ks = 0; ks < KS; ++ks) bx[ks] = *fgnn_at<uint4>(xt, off + 16u * ks);
     };
     uint4 nx[KS];
     load_tile(blockIdx.x * nrg + rg, nx);
@@ -154,10 +142,10 @@ __global__ __launch_bounds__(LF_THREADS) void linear_fwd_b16_kernel(const LfPara
             acc[ot] = bv[ot];
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                lf_bf16x8 a;
+                bf16x8 a;
                 if constexpr (WREG) a = aW[ot][ks];
-                else a = __builtin_bit_cast(lf_bf16x8, *reinterpret_cast<const uint4*>(Wl + (o_base + orow(ot)) * WS + kcol(ks)));
-                acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(lf_bf16x8, bx[ks]), acc[ot], 0, 0, 0);
+                else a = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Wl + (o_base + orow(ot)) * WS + kcol(ks)));
+                acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, bx[ks]), acc[ot], 0, 0, 0);
             }
         }
         // D[i = 4 lk + r][j = row] of tile ot = channel o_base + 16 lk + 4 ot + r of this lane's row
@@ -167,10 +155,10 @@ __global__ __launch_bounds__(LF_THREADS) void linear_fwd_b16_kernel(const LfPara
 #pragma unroll
             for (int sl = 0; sl < OTW / 4; ++sl) {
                 const f32x4 (&a4)[OTW] = acc;
-                *lf_at<uint4>(yt, yo + 128u * sl) = make_uint4(lf_pack2(a4[4 * sl][0], a4[4 * sl][1]), lf_pack2(a4[4 * sl][2], a4[4 * sl][3]),
-                                                              lf_pack2(a4[4 * sl + 1][0], a4[4 * sl + 1][1]), lf_pack2(a4[4 * sl + 1][2], a4[4 * sl + 1][3]));
-                *lf_at<uint4>(yt, yo + 128u * sl + 16u) = make_uint4(lf_pack2(a4[4 * sl + 2][0], a4[4 * sl + 2][1]), lf_pack2(a4[4 * sl + 2][2], a4[4 * sl + 2][3]),
-                                                                    lf_pack2(a4[4 * sl + 3][0], a4[4 * sl + 3][1]), lf_pack2(a4[4 * sl + 3][2], a4[4 * sl + 3][3]));
+                *fgnn_at<uint4>(yt, yo + 128u * sl) = make_uint4(fgnn_pack2(a4[4 * sl][0], a4[4 * sl][1]), fgnn_pack2(a4[4 * sl][2], a4[4 * sl][3]),
+                                                              fgnn_pack2(a4[4 * sl + 1][0], a4[4 * sl + 1][1]), fgnn_pack2(a4[4 * sl + 1][2], a4[4 * sl + 1][3]));
+                *fgnn_at<uint4>(yt, yo + 128u * sl + 16u) = make_uint4(fgnn_pack2(a4[4 * sl + 2][0], a4[4 * sl + 2][1]), fgnn_pack2(a4[4 * sl + 2][2], a4[4 * sl + 2][3]),
+                                                                    fgnn_pack2(a4[4 * sl + 3][0], a4[4 * sl + 3][1]), fgnn_pack2(a4[4 * sl + 3][2], a4[4 * sl + 3][3]));
             }
             if (p.part) {
 #pragma unroll
@@ -238,7 +226,7 @@ __global__ __launch_bounds__(LF_THREADS) void linear_instnorm_fwd_kernel(const L
     for (int f = tid; f < Cout * (CIN / 2); f += LF_THREADS) {
         const int o = f / (CIN / 2), c2 = f - o * (CIN / 2);
         const float2 w = *reinterpret_cast<const float2*>(p.W + (int64_t)o * CIN + 2 * c2);
-        *reinterpret_cast<unsigned*>(Wl + o * WS + 2 * c2) = lf_pack2(w.x, w.y);
+        *reinterpret_cast<unsigned*>(Wl + o * WS + 2 * c2) = fgnn_pack2(w.x, w.y);
     }
     for (int f = tid; f < Cout; f += LF_THREADS) bl[f] = p.bias ? p.bias[f] : 0.f;
     __syncthreads();
@@ -246,13 +234,13 @@ __global__ __launch_bounds__(LF_THREADS) void linear_instnorm_fwd_kernel(const L
     const int o_base = cg * OTW * 16;
     auto orow = [&](int ot) { return 16 * (li >> 2) + 4 * ot + (li & 3); };     // (the channel permutation of linear_fwd_b16_kernel)
     auto kcol = [&](int ks) { return 8 * KS * lk + 8 * ks; };
-    lf_bf16x8 aW[WREG ? OTW : 1][WREG ? KS : 1];
+    bf16x8 aW[WREG ? OTW : 1][WREG ? KS : 1];
     if constexpr (WREG) {
 #pragma unroll
         for (int ot = 0; ot < OTW; ++ot)
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
-                aW[ot][ks] = __builtin_bit_cast(lf_bf16x8, *reinterpret_cast<const uint4*>(Wl + (o_base + orow(ot)) * WS + kcol(ks)));
+                aW[ot][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Wl + (o_base + orow(ot)) * WS + kcol(ks)));
     }
     f32x4 bv[OTW];
 #pragma unroll
@@ -291,10 +279,10 @@ __global__ __launch_bounds__(LF_THREADS) void linear_instnorm_fwd_kernel(const L
 #pragma unroll
                 for (int k = 0; k < KC; ++k) {
                     const int ks = ch * KC + k;
-                    lf_bf16x8 a;
+                    bf16x8 a;
                     if constexpr (WREG) a = aW[ot][ks];
-                    else a = __builtin_bit_cast(lf_bf16x8, *reinterpret_cast<const uint4*>(Wl + (o_base + orow(ot)) * WS + kcol(ks)));
-                    acc[t][ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(lf_bf16x8, bx[k]), acc[t][ot], 0, 0, 0);
+                    else a = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Wl + (o_base + orow(ot)) * WS + kcol(ks)));
+                    acc[t][ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, bx[k]), acc[t][ot], 0, 0, 0);
                 }
             }
         }
@@ -302,10 +290,10 @@ __global__ __launch_bounds__(LF_THREADS) void linear_instnorm_fwd_kernel(const L
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             uint4 lo, hi;
-            lo = make_uint4(lf_pack2(acc[t][0][0], acc[t][0][1]), lf_pack2(acc[t][0][2], acc[t][0][3]),
-                            lf_pack2(acc[t][1][0], acc[t][1][1]), lf_pack2(acc[t][1][2], acc[t][1][3]));
-            hi = make_uint4(lf_pack2(acc[t][2][0], acc[t][2][1]), lf_pack2(acc[t][2][2], acc[t][2][3]),
-                            lf_pack2(acc[t][3][0], acc[t][3][1]), lf_pack2(acc[t][3][2], acc[t][3][3]));
+            lo = make_uint4(fgnn_pack2(acc[t][0][0], acc[t][0][1]), fgnn_pack2(acc[t][0][2], acc[t][0][3]),
+                            fgnn_pack2(acc[t][1][0], acc[t][1][1]), fgnn_pack2(acc[t][1][2], acc[t][1][3]));
+            hi = make_uint4(fgnn_pack2(acc[t][2][0], acc[t][2][1]), fgnn_pack2(acc[t][2][2], acc[t][2][3]),
+                            fgnn_pack2(acc[t][3][0], acc[t][3][1]), fgnn_pack2(acc[t][3][2], acc[t][3][3]));
             if (q.zs) {
                 uint16_t* zp = q.zs + ((int64_t)b * N + t * 16 + li) * Cout + o_base + 16 * lk;
                 *reinterpret_cast<uint4*>(zp) = lo;
@@ -343,10 +331,10 @@ __global__ __launch_bounds__(LF_THREADS) void linear_instnorm_fwd_kernel(const L
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             uint16_t* yp = p.y + ((int64_t)b * N + t * 16 + li) * Cout + o_base + 16 * lk;
-            *reinterpret_cast<uint4*>(yp) = make_uint4(lf_pack2(acc[t][0][0], acc[t][0][1]), lf_pack2(acc[t][0][2], acc[t][0][3]),
-                                                       lf_pack2(acc[t][1][0], acc[t][1][1]), lf_pack2(acc[t][1][2], acc[t][1][3]));
-            *reinterpret_cast<uint4*>(yp + 8) = make_uint4(lf_pack2(acc[t][2][0], acc[t][2][1]), lf_pack2(acc[t][2][2], acc[t][2][3]),
-                                                           lf_pack2(acc[t][3][0], acc[t][3][1]), lf_pack2(acc[t][3][2], acc[t][3][3]));
+            *reinterpret_cast<uint4*>(yp) = make_uint4(fgnn_pack2(acc[t][0][0], acc[t][0][1]), fgnn_pack2(acc[t][0][2], acc[t][0][3]),
+                                                       fgnn_pack2(acc[t][1][0], acc[t][1][1]), fgnn_pack2(acc[t][1][2], acc[t][1][3]));
+            *reinterpret_cast<uint4*>(yp + 8) = make_uint4(fgnn_pack2(acc[t][2][0], acc[t][2][1]), fgnn_pack2(acc[t][2][2], acc[t][2][3]),
+                                                           fgnn_pack2(acc[t][3][0], acc[t][3][1]), fgnn_pack2(acc[t][3][2], acc[t][3][3]));
         }
     }
 }
@@ -581,8 +569,8 @@ __global__ __launch_bounds__(LF_THREADS) void linear_multi_b16_kernel(const LmPa
             acc[ot] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int g = 0; g < KS; ++g) {
-                const lf_bf16x8 a = __builtin_bit_cast(lf_bf16x8, *reinterpret_cast<const uint4*>(wl + (o_base + orow(ot)) * WS + (((wcol(g) >> 3) ^ ((li >> 2) << 2)) << 3)));
-                acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(lf_bf16x8, bx[g]), acc[ot], 0, 0, 0);
+                const bf16x8 a = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(wl + (o_base + orow(ot)) * WS + (((wcol(g) >> 3) ^ ((li >> 2) << 2)) << 3)));
+                acc[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, bx[g]), acc[ot], 0, 0, 0);
             }
         }
         if (ok) {       // acc[ot][r] = channel n0 + o_base + 16 lk + 4 ot + r of this lane's row
@@ -596,10 +584,10 @@ __global__ __launch_bounds__(LF_THREADS) void linear_multi_b16_kernel(const LmPa
                 }
             }
             uint16_t* yp = p.y + (int64_t)row * Cout + n0 + o_base + 16 * lk;
-            *reinterpret_cast<uint4*>(yp) = make_uint4(lf_pack2(acc[0][0], acc[0][1]), lf_pack2(acc[0][2], acc[0][3]),
-                                                       lf_pack2(acc[1][0], acc[1][1]), lf_pack2(acc[1][2], acc[1][3]));
-            *reinterpret_cast<uint4*>(yp + 8) = make_uint4(lf_pack2(acc[2][0], acc[2][1]), lf_pack2(acc[2][2], acc[2][3]),
-                                                           lf_pack2(acc[3][0], acc[3][1]), lf_pack2(acc[3][2], acc[3][3]));
+            *reinterpret_cast<uint4*>(yp) = make_uint4(fgnn_pack2(acc[0][0], acc[0][1]), fgnn_pack2(acc[0][2], acc[0][3]),
+                                                       fgnn_pack2(acc[1][0], acc[1][1]), fgnn_pack2(acc[1][2], acc[1][3]));
+            *reinterpret_cast<uint4*>(yp + 8) = make_uint4(fgnn_pack2(acc[2][0], acc[2][1]), fgnn_pack2(acc[2][2], acc[2][3]),
+                                                           fgnn_pack2(acc[3][0], acc[3][1]), fgnn_pack2(acc[3][2], acc[3][3]));
         }
     }
 }

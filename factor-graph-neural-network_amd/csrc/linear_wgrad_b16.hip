@@ -19,13 +19,12 @@
 // (fixed order), the workgroup writes its slab in REGISTER order (coalesced), and wgb_reduce_kernel sums the
 // slabs and undoes the permutation: deterministic, no atomics.
 #include "linear_wgrad.h"
+#include "fgnn_device.h"
 
 #define WB_THREADS 1024
 #define WB_WAVES 16
 #define WB_NACC 68       // 64 gW accumulators + 4 dbias partials per lane
 
-typedef __bf16 wb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wb_bf16x2 __attribute__((ext_vector_type(2)));
 
 struct WgbParams {
     const uint16_t* x;   // [R][Cin]  bf16
@@ -43,25 +42,13 @@ struct WgbParams {
 
 extern __shared__ __attribute__((aligned(16))) float wb_lds[];
 
-// rows r0..r7 each hold channels (c0 c1 | c2 c3) as two dwords: gather channel P's eight values
-template <int P>
-__device__ __forceinline__ uint4 wb_pack(const uint2 (&r)[8]) {
-    constexpr unsigned sel = (P & 1) ? 0x07060302u : 0x05040100u;     // high / low halves of (hi:b, lo:a)
-    unsigned w[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const unsigned a = P < 2 ? r[2 * q].x : r[2 * q].y, b = P < 2 ? r[2 * q + 1].x : r[2 * q + 1].y;
-        w[q] = __builtin_amdgcn_perm(b, a, sel);
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 __device__ __forceinline__ float wb_sum8(const uint4& f, float acc) {
-    const wb_bf16x2 one = {(__bf16)1.0f, (__bf16)1.0f};
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wb_bf16x2, f.x), one, acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wb_bf16x2, f.y), one, acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wb_bf16x2, f.z), one, acc, false);
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(wb_bf16x2, f.w), one, acc, false);
+    const bf16x2 one = {(__bf16)1.0f, (__bf16)1.0f};
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, f.x), one, acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, f.y), one, acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, f.z), one, acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, f.w), one, acc, false);
     return acc;
 }
 
@@ -107,15 +94,17 @@ __global__ __launch_bounds__(WB_THREADS) void linear_wgrad_b16_kernel(const WgbP
     for (int blk = blockIdx.x * p.RW + rw; blk < nblk; blk += stride) {
         load(blk);
         uint4 A[4], Bf[4];
-        A[0] = wb_pack<0>(rg); A[1] = wb_pack<1>(rg); A[2] = wb_pack<2>(rg); A[3] = wb_pack<3>(rg);
-        Bf[0] = wb_pack<0>(rx); Bf[1] = wb_pack<1>(rx); Bf[2] = wb_pack<2>(rx); Bf[3] = wb_pack<3>(rx);
+        A[0] = fgnn_perm_col<0>(rg); A[1] = fgnn_perm_col<1>(rg);
+        A[2] = fgnn_perm_col<2>(rg); A[3] = fgnn_perm_col<3>(rg);
+        Bf[0] = fgnn_perm_col<0>(rx); Bf[1] = fgnn_perm_col<1>(rx);
+        Bf[2] = fgnn_perm_col<2>(rx); Bf[3] = fgnn_perm_col<3>(rx);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             bs[a] = wb_sum8(A[a], bs[a]);
 #pragma unroll
             for (int b = 0; b < 4; ++b)
-                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wb_bf16x8, A[a]),
-                                                                    __builtin_bit_cast(wb_bf16x8, Bf[b]), acc[a][b], 0, 0, 0);
+                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A[a]),
+                                                                    __builtin_bit_cast(bf16x8, Bf[b]), acc[a][b], 0, 0, 0);
         }
     }
 
@@ -186,26 +175,13 @@ struct WglParams {
     int off[WB_MAXSRC + 1];                   // byte offset of the x image (0) and of every gy image inside a stage
 };
 
-// uniform 64-bit base (SGPR pair) + per-lane 32-bit byte offset: no 64-bit VGPR address arithmetic in the loop
-__device__ __forceinline__ void wl_dma16(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ uint2 wl_tr(unsigned lds_addr) {
-    typedef short wl_s16x4 __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(3))) wl_s16x4 lds_v4;
-    const wl_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_v4*>(static_cast<uintptr_t>(lds_addr)));
-    return __builtin_bit_cast(uint2, v);
-}
-template <int N> __device__ __forceinline__ void wl_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void wl_wait_vm_n(int n) {          // n = (stages still in flight: 0..2) x (this wave's DMA instructions per stage: 1..3)
-    if (n >= 6) wl_wait_vm<6>();
-    else if (n >= 4) wl_wait_vm<4>();
-    else if (n == 3) wl_wait_vm<3>();
-    else if (n == 2) wl_wait_vm<2>();
-    else if (n == 1) wl_wait_vm<1>();
-    else wl_wait_vm<0>();
+    if (n >= 6) fgnn_wait_vm<6>();
+    else if (n >= 4) fgnn_wait_vm<4>();
+    else if (n == 3) fgnn_wait_vm<3>();
+    else if (n == 2) fgnn_wait_vm<2>();
+    else if (n == 1) fgnn_wait_vm<1>();
+    else fgnn_wait_vm<0>();
 }
 // swizzle of the 32-byte segments of a row whose pitch is `segs` segments (4, 8 or 16)
 __device__ __forceinline__ int wl_f(int row, int segs) {
@@ -282,7 +258,7 @@ __global__ __launch_bounds__(WB_THREADS) void linear_wgrad_lds_kernel(const WglP
         for (int j = 0; j < 3; ++j)
             if (j < ndma) {
                 const uint64_t sb = (uint64_t)(uintptr_t)gbase[j] + (uint64_t)row0 * gpitch[j];
-                wl_dma16((const void*)(uintptr_t)sb, lane_off(j), __builtin_amdgcn_readfirstlane(base + ldst[j]));
+                fgnn_dma16s((const void*)(uintptr_t)sb, lane_off(j), __builtin_amdgcn_readfirstlane(base + ldst[j]));
             }
     };
     auto compute = [&](int stage) {
@@ -290,17 +266,17 @@ __global__ __launch_bounds__(WB_THREADS) void linear_wgrad_lds_kernel(const WglP
         uint4 A[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const uint2 a0 = wl_tr(base + aA[t]), a1 = wl_tr(base + aA[t] + 4u * (unsigned)pg);
+            const uint2 a0 = fgnn_tr16(base + aA[t]), a1 = fgnn_tr16(base + aA[t] + 4u * (unsigned)pg);
             A[t] = make_uint4(a0.x, a0.y, a1.x, a1.y);
         }
 #pragma unroll
         for (int b = 0; b < 4; ++b) {              // (one x fragment at a time: 16 + 4 operand registers beside the 64 accumulators)
-            const uint2 b0 = wl_tr(base + aB[b]), b1 = wl_tr(base + aB[b] + 4u * (unsigned)px);
+            const uint2 b0 = fgnn_tr16(base + aB[b]), b1 = fgnn_tr16(base + aB[b] + 4u * (unsigned)px);
             const uint4 Bf = make_uint4(b0.x, b0.y, b1.x, b1.y);
 #pragma unroll
             for (int a = 0; a < 4; ++a)
-                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wb_bf16x8, A[a]),
-                                                                    __builtin_bit_cast(wb_bf16x8, Bf), acc[a][b], 0, 0, 0);
+                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A[a]),
+                                                                    __builtin_bit_cast(bf16x8, Bf), acc[a][b], 0, 0, 0);
         }
 #pragma unroll
         for (int a = 0; a < 4; ++a) bs[a] = wb_sum8(A[a], bs[a]);
@@ -465,20 +441,21 @@ __global__ __launch_bounds__(WB_THREADS) void linear_wgrad_b16_narrow_kernel(con
         }
         const uint4 N = wb_pack_narrow(rn);
         uint4 Wd[4];
-        Wd[0] = wb_pack<0>(rwd); Wd[1] = wb_pack<1>(rwd); Wd[2] = wb_pack<2>(rwd); Wd[3] = wb_pack<3>(rwd);
+        Wd[0] = fgnn_perm_col<0>(rwd); Wd[1] = fgnn_perm_col<1>(rwd);
+        Wd[2] = fgnn_perm_col<2>(rwd); Wd[3] = fgnn_perm_col<3>(rwd);
         if (NARROW_X) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) {              // D[i][j]: o = 4 i + t, c = j
                 bs[t] = wb_sum8(Wd[t], bs[t]);
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wb_bf16x8, Wd[t]),
-                                                                 __builtin_bit_cast(wb_bf16x8, N), acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, Wd[t]),
+                                                                 __builtin_bit_cast(bf16x8, N), acc[t], 0, 0, 0);
             }
         } else {
             bs[0] = wb_sum8(N, bs[0]);
 #pragma unroll
             for (int t = 0; t < 4; ++t)                // D[i][j]: o = i, c = 4 j + t
-                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wb_bf16x8, N),
-                                                                 __builtin_bit_cast(wb_bf16x8, Wd[t]), acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, N),
+                                                                 __builtin_bit_cast(bf16x8, Wd[t]), acc[t], 0, 0, 0);
         }
     }
     // tree fold of the 16 row-waves

@@ -9,6 +9,7 @@
 // dimension of the grid and the next 32-row tile travels in registers.  Per-chunk partial blocks go to slabs that a second
 // kernel folds in a fixed order (no atomics: bit-reproducible).
 #include "linear_wgrad.h"
+#include "fgnn_device.h"
 
 #define WF_THREADS 512
 #define WF_TR 32             // rows per LDS tile (8 k-steps)
@@ -33,23 +34,11 @@ struct WfParams {
 // transpose passes): one k-step of v_mfma_f32_16x16x32_bf16 per tile, 8 fragment products x 6 piece products = 768 cycles.
 // The bias gradient is summed from the f32 registers at commit time.
 // ---------------------------------------------------------------------------------------------------------------------------
-typedef __bf16 wq_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short wq_s16x4 __attribute__((ext_vector_type(4)));
 #define WQ_NP 3
 #define WQ_ROW 256                      // bytes per image row: 128 bf16
 #define WQ_PIECE (WF_TR * WQ_ROW)       // one piece image of a 32-row tile
 
 __device__ __forceinline__ int wq_sw(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
-__device__ __forceinline__ unsigned wq_pack2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ uint2 wq_tr(unsigned lds_addr) {
-    typedef __attribute__((address_space(3))) wq_s16x4 lds_v4;
-    const wq_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_v4*>(static_cast<uintptr_t>(lds_addr)));
-    return __builtin_bit_cast(uint2, v);
-}
 
 // BO x BC = the output block (64 or 128 each: a 64-channel side takes a 64-wide block instead of padding a 128-wide one);
 // waves = 4 (o) x 2 (c): BO / 64 o tiles and BC / 32 c tiles per wave
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(WF_THREADS, 2) void linear_wgrad_f32q_kernel(const 
         unsigned char* dst = img + row * rowbytes + (((col >> 4) ^ swz(row, rowbytes)) << 5) + ((col & 15) << 1);
 #pragma unroll
         for (int t = 0; t < WQ_NP; ++t) {
-            const unsigned w0 = wq_pack2(a, b), w1 = wq_pack2(c, d);
+            const unsigned w0 = fgnn_pack2(a, b), w1 = fgnn_pack2(c, d);
             *reinterpret_cast<uint2*>(dst + t * piece) = make_uint2(w0, w1);
             if (t + 1 < WQ_NP) {
                 a -= __uint_as_float(w0 << 16); b -= __uint_as_float(w0 & 0xffff0000u);
@@ -140,22 +129,22 @@ __global__ __launch_bounds__(WF_THREADS, 2) void linear_wgrad_f32q_kernel(const 
         commit();
         if (r0 + WF_TR < r_end) prefetch(r0 + WF_TR);
         __syncthreads();
-        wq_bf16x8 ga[NO][WQ_NP], xb[NC][WQ_NP];
+        bf16x8 ga[NO][WQ_NP], xb[NC][WQ_NP];
 #pragma unroll
         for (int a = 0; a < NO; ++a)
 #pragma unroll
             for (int t = 0; t < WQ_NP; ++t) {
                 const int g = NO * wo + a;
-                const uint2 lo = wq_tr(gq0 + t * GPIECE + g0 + ((g ^ sg0) << 5)), hi = wq_tr(gq0 + t * GPIECE + g1 + ((g ^ sg1) << 5));
-                ga[a][t] = __builtin_bit_cast(wq_bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+                const uint2 lo = fgnn_tr16(gq0 + t * GPIECE + g0 + ((g ^ sg0) << 5)), hi = fgnn_tr16(gq0 + t * GPIECE + g1 + ((g ^ sg1) << 5));
+                ga[a][t] = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
             }
 #pragma unroll
         for (int b = 0; b < NC; ++b)
 #pragma unroll
             for (int t = 0; t < WQ_NP; ++t) {
                 const int g = NC * wc + b;
-                const uint2 lo = wq_tr(xq0 + t * XPIECE + x0 + ((g ^ sx0) << 5)), hi = wq_tr(xq0 + t * XPIECE + x1 + ((g ^ sx1) << 5));
-                xb[b][t] = __builtin_bit_cast(wq_bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+                const uint2 lo = fgnn_tr16(xq0 + t * XPIECE + x0 + ((g ^ sx0) << 5)), hi = fgnn_tr16(xq0 + t * XPIECE + x1 + ((g ^ sx1) << 5));
+                xb[b][t] = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
             }
 #pragma unroll
         for (int pr6 = 0; pr6 < 6; ++pr6)

@@ -17,6 +17,7 @@
 // resident in registers, two destinations in flight per wave in the gather) plus one MFMA phase in front and one
 // behind; the a2 image re-uses the x image's LDS, so the 64-wide block stays under 80 KB (2 workgroups per CU).
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include <stdlib.h>
 
 #define KB_THREADS 512
@@ -28,8 +29,6 @@
 #define KB_PSB 264       // row stride of the P image: 256 columns + 8
 #endif
 
-typedef __bf16 kb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 kb_bf16x2 __attribute__((ext_vector_type(2)));
 
 struct KbParams {
     fgnn_mpconv_desc d;  // of the message operator inside the block (nin = nou = 64, net = 4)
@@ -58,15 +57,6 @@ struct KbParams {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fgnn_lds_kb[];
 
-__device__ __forceinline__ unsigned kb_pack2(float a, float b) {
-    const kb_bf16x2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ kb_bf16x8 kb_frag8(const float* p8) {          // 8 consecutive f32 -> one fragment
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p8), b = *reinterpret_cast<const f32x4*>(p8 + 4);
-    return __builtin_bit_cast(kb_bf16x8, make_uint4(kb_pack2(a[0], a[1]), kb_pack2(a[2], a[3]),
-                                                    kb_pack2(b[0], b[1]), kb_pack2(b[2], b[3])));
-}
 
 // KC = degree, NI = nin / 64, NO = nout / 64
 template <int KC, int NI, int NO>
@@ -87,10 +77,10 @@ __global__ __launch_bounds__(KB_THREADS) void mpconv_block_fwd_kernel(const KbPa
     // ---- resident fragments ----
     const int li0 = lane & 15, lk0 = lane >> 4;
     const int ot = wave & 3;                           // this wave's 16-channel output tile of conv1 / conv2
-    kb_bf16x8 aW1[KS1], aW2[NO][2], aF[2][2];
+    bf16x8 aW1[KS1], aW2[NO][2], aF[2][2];
     f32x4 c1s, c1t, c3s[NO], c3t[NO];                  // per-lane affine of the wave's conv tiles: channels tile*16 + 4lk + r
 #pragma unroll
-    for (int ks = 0; ks < KS1; ++ks) aW1[ks] = kb_frag8(p.W1 + (ot * 16 + li0) * NIN + 32 * ks + 8 * lk0);   // A[i = o][k = c] = W1[o][c]
+    for (int ks = 0; ks < KS1; ++ks) aW1[ks] = fgnn_frag8(p.W1 + (ot * 16 + li0) * NIN + 32 * ks + 8 * lk0);   // A[i = o][k = c] = W1[o][c]
     c1s = *reinterpret_cast<const f32x4*>(p.s1 + ot * 16 + 4 * lk0);
     c1t = *reinterpret_cast<const f32x4*>(p.t1 + ot * 16 + 4 * lk0);
 #pragma unroll
@@ -100,7 +90,7 @@ __global__ __launch_bounds__(KB_THREADS) void mpconv_block_fwd_kernel(const KbPa
     for (int q = 0; q < NO; ++q) {
         const int u = ot * NO + q, g = u >> 2, qt = u & 3;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) aW2[q][ks] = kb_frag8(p.W2 + (64 * g + 16 * (li0 >> 2) + 4 * qt + (li0 & 3)) * 64 + 32 * ks + 8 * lk0);
+        for (int ks = 0; ks < 2; ++ks) aW2[q][ks] = fgnn_frag8(p.W2 + (64 * g + 16 * (li0 >> 2) + 4 * qt + (li0 & 3)) * 64 + 32 * ks + 8 * lk0);
         c3s[q] = *reinterpret_cast<const f32x4*>(p.s3 + 64 * g + 16 * lk0 + 4 * qt);
         c3t[q] = *reinterpret_cast<const f32x4*>(p.t3 + 64 * g + 16 * lk0 + 4 * qt);
     }
@@ -113,8 +103,8 @@ __global__ __launch_bounds__(KB_THREADS) void mpconv_block_fwd_kernel(const KbPa
             float w8[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) w8[u] = p.F[(32 * ks + 8 * lk0 + u) * 256 + (wave + 8 * q) * 16 + li0];
-            aF[q][ks] = __builtin_bit_cast(kb_bf16x8, make_uint4(kb_pack2(w8[0], w8[1]), kb_pack2(w8[2], w8[3]),
-                                                                 kb_pack2(w8[4], w8[5]), kb_pack2(w8[6], w8[7])));
+            aF[q][ks] = __builtin_bit_cast(bf16x8, make_uint4(fgnn_pack2(w8[0], w8[1]), fgnn_pack2(w8[2], w8[3]),
+                                                                 fgnn_pack2(w8[4], w8[5]), fgnn_pack2(w8[6], w8[7])));
         }
     const float c2s = p.s2[lane], c2t = p.t2[lane];   // gather epilogue: lane <-> channel
 
@@ -170,27 +160,27 @@ __global__ __launch_bounds__(KB_THREADS) void mpconv_block_fwd_kernel(const KbPa
             const uint16_t* bp = xs + (nt * 16 + li) * XS1 + 8 * lk;
 #pragma unroll
             for (int ks = 0; ks < KS1; ++ks)
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aW1[ks], __builtin_bit_cast(kb_bf16x8, *reinterpret_cast<const uint4*>(bp + 32 * ks)), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aW1[ks], __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp + 32 * ks)), acc, 0, 0, 0);
             float v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) { const float u = fmaf(acc[r], c1s[r], c1t[r]); v[r] = u > 0.f ? u : u * p.slope; }
             if (nt * 16 + li < N)
-                *reinterpret_cast<uint2*>(a1s + (nt * 16 + li) * KB_XSB + ot * 16 + 4 * lk) = make_uint2(kb_pack2(v[0], v[1]), kb_pack2(v[2], v[3]));
+                *reinterpret_cast<uint2*>(a1s + (nt * 16 + li) * KB_XSB + ot * 16 + 4 * lk) = make_uint2(fgnn_pack2(v[0], v[1]), fgnn_pack2(v[2], v[3]));
         }
         __syncthreads();
 
         // ---- projection P^T = F^T a1: wave's slabs w and w + 8, all node tiles ----
         for (int nt = 0; nt < ntile; ++nt) {
             const uint16_t* bp = a1s + (nt * 16 + li) * KB_XSB + 8 * lk;
-            const kb_bf16x8 b0 = __builtin_bit_cast(kb_bf16x8, *reinterpret_cast<const uint4*>(bp));
-            const kb_bf16x8 b1 = __builtin_bit_cast(kb_bf16x8, *reinterpret_cast<const uint4*>(bp + 32));
+            const bf16x8 b0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp));
+            const bf16x8 b1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp + 32));
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aF[q][0], b0, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aF[q][1], b1, acc, 0, 0, 0);
                 *reinterpret_cast<uint2*>(ps + (nt * 16 + li) * KB_PSB + (wave + 8 * q) * 16 + 4 * lk) =
-                    make_uint2(kb_pack2(acc[0], acc[1]), kb_pack2(acc[2], acc[3]));
+                    make_uint2(fgnn_pack2(acc[0], acc[1]), fgnn_pack2(acc[2], acc[3]));
             }
         }
         __syncthreads();                               // P complete; the x image is dead: it becomes a2
@@ -250,10 +240,10 @@ __global__ __launch_bounds__(KB_THREADS) void mpconv_block_fwd_kernel(const KbPa
                 float b0 = 0.f, b1 = 0.f;
 #pragma unroll
                 for (int j = 0; j < KC; ++j) {
-                    float v0 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(kb_bf16x2, pk0[j].x), __builtin_bit_cast(kb_bf16x2, ew0[j].x), 0.f, false);
-                    v0 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(kb_bf16x2, pk0[j].y), __builtin_bit_cast(kb_bf16x2, ew0[j].y), v0, false);
-                    float v1 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(kb_bf16x2, pk1[j].x), __builtin_bit_cast(kb_bf16x2, ew1[j].x), 0.f, false);
-                    v1 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(kb_bf16x2, pk1[j].y), __builtin_bit_cast(kb_bf16x2, ew1[j].y), v1, false);
+                    float v0 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk0[j].x), __builtin_bit_cast(bf16x2, ew0[j].x), 0.f, false);
+                    v0 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk0[j].y), __builtin_bit_cast(bf16x2, ew0[j].y), v0, false);
+                    float v1 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk1[j].x), __builtin_bit_cast(bf16x2, ew1[j].x), 0.f, false);
+                    v1 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk1[j].y), __builtin_bit_cast(bf16x2, ew1[j].y), v1, false);
                     b0 = j == 0 ? v0 : fmaxf(b0, v0);
                     b1 = j == 0 ? v1 : fmaxf(b1, v1);
                 }
@@ -273,8 +263,8 @@ __global__ __launch_bounds__(KB_THREADS) void mpconv_block_fwd_kernel(const KbPa
             int mt = wave >> 2;
             for (; mt < mtile; mt += 2) {
                 const uint16_t* bp = xs + (mt * 16 + li) * KB_XSB + 8 * lk;
-                const kb_bf16x8 b0 = __builtin_bit_cast(kb_bf16x8, *reinterpret_cast<const uint4*>(bp));
-                const kb_bf16x8 b1 = __builtin_bit_cast(kb_bf16x8, *reinterpret_cast<const uint4*>(bp + 32));
+                const bf16x8 b0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp));
+                const bf16x8 b1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp + 32));
                 const int m = mt * 16 + li;
                 f32x4 acur[NO];
 #pragma unroll
@@ -293,8 +283,8 @@ __global__ __launch_bounds__(KB_THREADS) void mpconv_block_fwd_kernel(const KbPa
 #pragma unroll
                         for (int r = 0; r < 4; ++r) { const float u = fmaf(acc[q][r], c3s[q][r], c3t[q][r]); v[r] = u > 0.f ? u : u * p.slope; }
                         if (adb) { v[0] += acur[q][0]; v[1] += acur[q][1]; v[2] += acur[q][2]; v[3] += acur[q][3]; }
-                        ow[2 * q] = kb_pack2(v[0], v[1]);
-                        ow[2 * q + 1] = kb_pack2(v[2], v[3]);
+                        ow[2 * q] = fgnn_pack2(v[0], v[1]);
+                        ow[2 * q + 1] = fgnn_pack2(v[2], v[3]);
                     }
                     uint16_t* yp = yb + (int64_t)m * NOUT + cbase;
                     if (NO == 1) *reinterpret_cast<uint2*>(yp) = make_uint2(ow[0], ow[1]);
@@ -426,7 +416,7 @@ __global__ __launch_bounds__(512) void mpconv_block_fanout_kernel(const KfParams
     for (int f = tid; f < nout * 32; f += 512) {
         const int q = f >> 5, c2 = f & 31;
         const float2 w = *reinterpret_cast<const float2*>(p.W2 + q * 64 + 2 * c2);
-        *reinterpret_cast<unsigned*>(W2l + q * KB_XSB + 2 * c2) = kb_pack2(w.x, w.y);
+        *reinterpret_cast<unsigned*>(W2l + q * KB_XSB + 2 * c2) = fgnn_pack2(w.x, w.y);
     }
     __syncthreads();
     const float c1s = p.s1[lane], c1t = p.t1[lane], c2s = p.s2[lane], c2t = p.t2[lane];
@@ -460,7 +450,7 @@ __global__ __launch_bounds__(512) void mpconv_block_fanout_kernel(const KfParams
         for (int mt = 0; mt < mtile; ++mt) {
             const int m = mt * 16 + li;
             const float e = m < M ? __uint_as_float((unsigned)eb[(int64_t)m * d.et_sm] << 16) : 0.f;
-            kb_bf16x8 bf[2];
+            bf16x8 bf[2];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const f32x4 p0 = *reinterpret_cast<const f32x4*>(pw + 32 * ks + 8 * lk), p1 = *reinterpret_cast<const f32x4*>(pw + 32 * ks + 8 * lk + 4);
@@ -468,7 +458,7 @@ __global__ __launch_bounds__(512) void mpconv_block_fanout_kernel(const KfParams
                 float v[8];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) { v[u] = fmaxf(fmaf(e, p0[u], t0[u]), 0.f); v[4 + u] = fmaxf(fmaf(e, p1[u], t1[u]), 0.f); }
-                bf[ks] = __builtin_bit_cast(kb_bf16x8, make_uint4(kb_pack2(v[0], v[1]), kb_pack2(v[2], v[3]), kb_pack2(v[4], v[5]), kb_pack2(v[6], v[7])));
+                bf[ks] = __builtin_bit_cast(bf16x8, make_uint4(fgnn_pack2(v[0], v[1]), fgnn_pack2(v[2], v[3]), fgnn_pack2(v[4], v[5]), fgnn_pack2(v[6], v[7])));
             }
             // Output channels in groups of 64 = four MFMA tiles whose rows are permuted (tile qt, row i <-> channel 16 (i >> 2) + 4 qt
             // + (i & 3)): lane (row li, lk) then holds the 16 CONSECUTIVE channels 16 lk .. + 15 of its row and moves them (and the
@@ -479,8 +469,8 @@ __global__ __launch_bounds__(512) void mpconv_block_fanout_kernel(const KfParams
                 for (int qt = 0; qt < 4; ++qt) {
                     const uint16_t* wr = W2l + (64 * g + 16 * (li >> 2) + 4 * qt + (li & 3)) * KB_XSB + 8 * lk;
                     acc[qt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(kb_bf16x8, *reinterpret_cast<const uint4*>(wr)), bf[0], acc[qt], 0, 0, 0);
-                    acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(kb_bf16x8, *reinterpret_cast<const uint4*>(wr + 32)), bf[1], acc[qt], 0, 0, 0);
+                    acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(wr)), bf[0], acc[qt], 0, 0, 0);
+                    acc[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(wr + 32)), bf[1], acc[qt], 0, 0, 0);
                 }
                 if (m < M) {
                     const int ch = 64 * g + 16 * lk;                       // D[i = 4 lk + r] of tile qt = channel ch + 4 qt + r
@@ -500,8 +490,8 @@ __global__ __launch_bounds__(512) void mpconv_block_fanout_kernel(const KfParams
 #pragma unroll
                             for (int u = 0; u < 8; ++u) { v[2 * u] += __uint_as_float(aw[u] << 16); v[2 * u + 1] += __uint_as_float(aw[u] & 0xffff0000u); }
                         }
-                    *reinterpret_cast<uint4*>(yb + off) = make_uint4(kb_pack2(v[0], v[1]), kb_pack2(v[2], v[3]), kb_pack2(v[4], v[5]), kb_pack2(v[6], v[7]));
-                    *reinterpret_cast<uint4*>(yb + off + 8) = make_uint4(kb_pack2(v[8], v[9]), kb_pack2(v[10], v[11]), kb_pack2(v[12], v[13]), kb_pack2(v[14], v[15]));
+                    *reinterpret_cast<uint4*>(yb + off) = make_uint4(fgnn_pack2(v[0], v[1]), fgnn_pack2(v[2], v[3]), fgnn_pack2(v[4], v[5]), fgnn_pack2(v[6], v[7]));
+                    *reinterpret_cast<uint4*>(yb + off + 8) = make_uint4(fgnn_pack2(v[8], v[9]), fgnn_pack2(v[10], v[11]), fgnn_pack2(v[12], v[13]), fgnn_pack2(v[14], v[15]));
                 }
             }
         }
@@ -521,16 +511,16 @@ __global__ __launch_bounds__(512) void mpconv_block_fanout_kernel(const KfParams
 // the operator enter as two bf16 pieces (two MFMAs: the f32 products of the kernel above up to the summation order), conv2's as
 // bf16, like there; the same bf16 rounding points (a1, P, a2, y).
 // ----------------------------------------------------------------------------------------
-__device__ __forceinline__ void kr_split8(const float* w, kb_bf16x8& hi, kb_bf16x8& lo) {      // 8 f32 -> bf16 hi + lo fragments
+__device__ __forceinline__ void kr_split8(const float* w, bf16x8& hi, bf16x8& lo) {      // 8 f32 -> bf16 hi + lo fragments
     unsigned h[4], l[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const float a = w[2 * q], b = w[2 * q + 1];
-        h[q] = kb_pack2(a, b);
-        l[q] = kb_pack2(a - __uint_as_float(h[q] << 16), b - __uint_as_float(h[q] & 0xffff0000u));
+        h[q] = fgnn_pack2(a, b);
+        l[q] = fgnn_pack2(a - __uint_as_float(h[q] << 16), b - __uint_as_float(h[q] & 0xffff0000u));
     }
-    hi = __builtin_bit_cast(kb_bf16x8, make_uint4(h[0], h[1], h[2], h[3]));
-    lo = __builtin_bit_cast(kb_bf16x8, make_uint4(l[0], l[1], l[2], l[3]));
+    hi = __builtin_bit_cast(bf16x8, make_uint4(h[0], h[1], h[2], h[3]));
+    lo = __builtin_bit_cast(bf16x8, make_uint4(l[0], l[1], l[2], l[3]));
 }
 
 template <int NI>
@@ -550,20 +540,20 @@ __global__ __launch_bounds__(64) void mpconv_block_rows1_kernel(const KfParams p
     const uint16_t* xrow = p.x + bs * d.x_sb + 8 * lk;
 #pragma unroll 2
     for (int ks = 0; ks < KS1; ++ks) {
-        const kb_bf16x8 xb = __builtin_bit_cast(kb_bf16x8, *reinterpret_cast<const uint4*>(xrow + 32 * ks));
+        const bf16x8 xb = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(xrow + 32 * ks));
 #pragma unroll
         for (int ot = 0; ot < 4; ++ot) {
             const float* wr = p.W1 + (int64_t)(16 * ot + li) * NIN + 32 * ks + 8 * lk;
             const f32x4 w0 = *reinterpret_cast<const f32x4*>(wr), w1 = *reinterpret_cast<const f32x4*>(wr + 4);
             const float w[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
-            kb_bf16x8 hi, lo;
+            bf16x8 hi, lo;
             kr_split8(w, hi, lo);
             acc1[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, xb, acc1[ot], 0, 0, 0);
             acc1[ot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, xb, acc1[ot], 0, 0, 0);
         }
     }
     // BatchNorm1 + LeakyReLU, rounded to bf16: the B fragments of the next product
-    kb_bf16x8 b2[2];
+    bf16x8 b2[2];
     {
         unsigned wq[8];
 #pragma unroll
@@ -573,11 +563,11 @@ __global__ __launch_bounds__(64) void mpconv_block_rows1_kernel(const KfParams p
             float v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) { const float u = fmaf(acc1[ot][r], s1[r], t1[r]); v[r] = u > 0.f ? u : u * p.slope; }
-            wq[2 * ot] = kb_pack2(v[0], v[1]);
-            wq[2 * ot + 1] = kb_pack2(v[2], v[3]);
+            wq[2 * ot] = fgnn_pack2(v[0], v[1]);
+            wq[2 * ot + 1] = fgnn_pack2(v[2], v[3]);
         }
-        b2[0] = __builtin_bit_cast(kb_bf16x8, make_uint4(wq[0], wq[1], wq[2], wq[3]));
-        b2[1] = __builtin_bit_cast(kb_bf16x8, make_uint4(wq[4], wq[5], wq[6], wq[7]));
+        b2[0] = __builtin_bit_cast(bf16x8, make_uint4(wq[0], wq[1], wq[2], wq[3]));
+        b2[1] = __builtin_bit_cast(bf16x8, make_uint4(wq[4], wq[5], wq[6], wq[7]));
     }
     // ---- P^T [64 o2][16 samples] = F^T a1^T: A[o2 = 16 t + li][k-slot (ks, i)] = F[o = 16 (2 ks + (i >> 2)) + 4 lk + (i & 3)][o2] ----
     f32x4 acc2[4] = {zero, zero, zero, zero};
@@ -588,14 +578,14 @@ __global__ __launch_bounds__(64) void mpconv_block_rows1_kernel(const KfParams p
             float w[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) w[i] = p.F[(16 * (2 * ks + (i >> 2)) + 4 * lk + (i & 3)) * 64 + 16 * t + li];
-            kb_bf16x8 hi, lo;
+            bf16x8 hi, lo;
             kr_split8(w, hi, lo);
             acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, b2[ks], acc2[t], 0, 0, 0);
             acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hi, b2[ks], acc2[t], 0, 0, 0);
         }
     // P rounded to bf16, a2 = ReLU(e (s2 P) + t2) rounded to bf16: the B fragments of conv2
     const float e = __uint_as_float((unsigned)p.et[bs * d.et_sb] << 16);
-    kb_bf16x8 b3[2];
+    bf16x8 b3[2];
     {
         unsigned wq[8];
 #pragma unroll
@@ -609,11 +599,11 @@ __global__ __launch_bounds__(64) void mpconv_block_rows1_kernel(const KfParams p
                 const float P = __uint_as_float((unsigned)__builtin_bit_cast(uint16_t, h) << 16);
                 v[r] = fmaxf(fmaf(e, s2[r] * P, t2[r]), 0.f);
             }
-            wq[2 * t] = kb_pack2(v[0], v[1]);
-            wq[2 * t + 1] = kb_pack2(v[2], v[3]);
+            wq[2 * t] = fgnn_pack2(v[0], v[1]);
+            wq[2 * t + 1] = fgnn_pack2(v[2], v[3]);
         }
-        b3[0] = __builtin_bit_cast(kb_bf16x8, make_uint4(wq[0], wq[1], wq[2], wq[3]));
-        b3[1] = __builtin_bit_cast(kb_bf16x8, make_uint4(wq[4], wq[5], wq[6], wq[7]));
+        b3[0] = __builtin_bit_cast(bf16x8, make_uint4(wq[0], wq[1], wq[2], wq[3]));
+        b3[1] = __builtin_bit_cast(bf16x8, make_uint4(wq[4], wq[5], wq[6], wq[7]));
     }
     // ---- y^T [nout q][16 samples] = W2 a2^T; BatchNorm3 + LeakyReLU + addends; 8 bytes (channels 16 qt + 4 lk ..) per lane and tile ----
     uint16_t* yb = p.y + bs * nout;
@@ -626,7 +616,7 @@ __global__ __launch_bounds__(64) void mpconv_block_rows1_kernel(const KfParams p
         for (int ks = 0; ks < 2; ++ks) {
             const float* wr = p.W2 + (int64_t)(16 * qt + li) * 64 + 4 * lk;
             const f32x4 w0 = *reinterpret_cast<const f32x4*>(wr + 16 * (2 * ks)), w1 = *reinterpret_cast<const f32x4*>(wr + 16 * (2 * ks + 1));
-            const kb_bf16x8 a = __builtin_bit_cast(kb_bf16x8, make_uint4(kb_pack2(w0[0], w0[1]), kb_pack2(w0[2], w0[3]), kb_pack2(w1[0], w1[1]), kb_pack2(w1[2], w1[3])));
+            const bf16x8 a = __builtin_bit_cast(bf16x8, make_uint4(fgnn_pack2(w0[0], w0[1]), fgnn_pack2(w0[2], w0[3]), fgnn_pack2(w1[0], w1[1]), fgnn_pack2(w1[2], w1[3])));
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b3[ks], acc, 0, 0, 0);
         }
         const int q = 16 * qt + 4 * lk;
@@ -641,7 +631,7 @@ __global__ __launch_bounds__(64) void mpconv_block_rows1_kernel(const KfParams p
                 v[0] += __uint_as_float(aw.x << 16); v[1] += __uint_as_float(aw.x & 0xffff0000u);
                 v[2] += __uint_as_float(aw.y << 16); v[3] += __uint_as_float(aw.y & 0xffff0000u);
             }
-        if (live) *reinterpret_cast<uint2*>(yb + q) = make_uint2(kb_pack2(v[0], v[1]), kb_pack2(v[2], v[3]));
+        if (live) *reinterpret_cast<uint2*>(yb + q) = make_uint2(fgnn_pack2(v[0], v[1]), fgnn_pack2(v[2], v[3]));
     }
 }
 
@@ -668,7 +658,7 @@ __global__ __launch_bounds__(512) void mpconv_block_fanin_kernel(const KfParams 
     for (int f = tid; f < 64 * (NIN / 2); f += 512) {
         const int c1 = f / (NIN / 2), c2 = f - c1 * (NIN / 2);
         const float2 w = *reinterpret_cast<const float2*>(p.W1 + (int64_t)c1 * NIN + 2 * c2);
-        *reinterpret_cast<unsigned*>(W1l + c1 * XW + 2 * c2) = kb_pack2(w.x, w.y);
+        *reinterpret_cast<unsigned*>(W1l + c1 * XW + 2 * c2) = fgnn_pack2(w.x, w.y);
     }
     for (int f = tid; f < nout * 64; f += 512) {
         const int oo = f >> 6, o = f & 63;
@@ -677,7 +667,7 @@ __global__ __launch_bounds__(512) void mpconv_block_fanin_kernel(const KfParams 
     }
     // resident A fragments of P^T = F^T a1^T: A[i = o][k-slot]; slot u of lane group lk in step ks is channel
     // c1 = 16 (2 ks + (u >> 2)) + 4 lk + (u & 3) — the order the a1 accumulators come in
-    kb_bf16x8 aF[4][2];
+    bf16x8 aF[4][2];
 #pragma unroll
     for (int ot = 0; ot < 4; ++ot)
 #pragma unroll
@@ -685,8 +675,8 @@ __global__ __launch_bounds__(512) void mpconv_block_fanin_kernel(const KfParams 
             float w8[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) w8[u] = p.F[(int64_t)(16 * (2 * ks + (u >> 2)) + 4 * lk + (u & 3)) * 64 + ot * 16 + li];
-            aF[ot][ks] = __builtin_bit_cast(kb_bf16x8, make_uint4(kb_pack2(w8[0], w8[1]), kb_pack2(w8[2], w8[3]),
-                                                                  kb_pack2(w8[4], w8[5]), kb_pack2(w8[6], w8[7])));
+            aF[ot][ks] = __builtin_bit_cast(bf16x8, make_uint4(fgnn_pack2(w8[0], w8[1]), fgnn_pack2(w8[2], w8[3]),
+                                                                  fgnn_pack2(w8[4], w8[5]), fgnn_pack2(w8[6], w8[7])));
         }
     float c1s[4][4], c1t[4][4];                                              // channel 16 ot + 4 lk + r
 #pragma unroll
@@ -724,16 +714,16 @@ __global__ __launch_bounds__(512) void mpconv_block_fanin_kernel(const KfParams 
                 const uint16_t* wr = W1l + woff;
 #pragma unroll
                 for (int ks = 0; ks < KS1; ++ks)
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(kb_bf16x8, *reinterpret_cast<const uint4*>(wr + 32 * ks)),
-                                                                  __builtin_bit_cast(kb_bf16x8, bx[ks]), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(wr + 32 * ks)),
+                                                                  __builtin_bit_cast(bf16x8, bx[ks]), acc, 0, 0, 0);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { const float u = fmaf(acc[r], c1s[ot][r], c1t[ot][r]); a1v[ot][r] = u > 0.f ? u : u * p.slope; }
             }
-            kb_bf16x8 bf[2];
+            bf16x8 bf[2];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                bf[ks] = __builtin_bit_cast(kb_bf16x8, make_uint4(kb_pack2(a1v[2 * ks][0], a1v[2 * ks][1]), kb_pack2(a1v[2 * ks][2], a1v[2 * ks][3]),
-                                                                  kb_pack2(a1v[2 * ks + 1][0], a1v[2 * ks + 1][1]), kb_pack2(a1v[2 * ks + 1][2], a1v[2 * ks + 1][3])));
+                bf[ks] = __builtin_bit_cast(bf16x8, make_uint4(fgnn_pack2(a1v[2 * ks][0], a1v[2 * ks][1]), fgnn_pack2(a1v[2 * ks][2], a1v[2 * ks][3]),
+                                                                  fgnn_pack2(a1v[2 * ks + 1][0], a1v[2 * ks + 1][1]), fgnn_pack2(a1v[2 * ks + 1][2], a1v[2 * ks + 1][3])));
 #pragma unroll
             for (int ot = 0; ot < 4; ++ot) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -752,11 +742,7 @@ __global__ __launch_bounds__(512) void mpconv_block_fanin_kernel(const KfParams 
         for (int ot = 0; ot < 4; ++ot)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float v = zm[ot][r];
-                v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0xB1, 0xF, 0xF, false)));
-                v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x4E, 0xF, 0xF, false)));
-                v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x141, 0xF, 0xF, false)));
-                v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x140, 0xF, 0xF, false)));
+                float v = fgnn_row_max(zm[ot][r]);
                 const int o = 16 * ot + 4 * lk + r;
                 v = fmaxf(fmaf(v, p.s2[o], p.t2[o]), 0.f);
                 const __bf16 h = (__bf16)v;

@@ -19,6 +19,7 @@
 // Rounding: x and gz arrive as bf16; P and dP are rounded to bf16 (2^-9 relative) before they feed the matrix
 // cores, which is what a bf16 autocast backward does everywhere else in the model.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "mpconv_dispatch.h"
 #include <stdlib.h>
 
@@ -33,7 +34,6 @@
 #define BB_XPAD 8
 #endif
 
-typedef __bf16 bb_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bb_bf16x4 __attribute__((ext_vector_type(4)));
 
 struct Bb16Params {
@@ -59,38 +59,6 @@ extern __shared__ __attribute__((aligned(16))) unsigned char fgnn_lds_bb[];
 
 void fgnn_launch_w_transpose(const float* W, float* Wt, int nin, int ncols, hipStream_t st);
 
-__device__ __forceinline__ float bb_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bb_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ unsigned bb_pack2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ bb_bf16x8 bb_frag_f32(const float* p8) {      // 8 consecutive f32 -> one fragment
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p8), b = *reinterpret_cast<const f32x4*>(p8 + 4);
-    return __builtin_bit_cast(bb_bf16x8, make_uint4(bb_pack2(a[0], a[1]), bb_pack2(a[2], a[3]),
-                                                    bb_pack2(b[0], b[1]), bb_pack2(b[2], b[3])));
-}
-// rows r0..r7 each hold columns (c0 c1 | c2 c3) as two dwords: gather column P's eight values
-template <int P>
-__device__ __forceinline__ bb_bf16x8 bb_tr(const uint2 (&r)[8]) {
-    constexpr unsigned sel = (P & 1) ? 0x07060302u : 0x05040100u;
-    unsigned w[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const unsigned a = P < 2 ? r[2 * q].x : r[2 * q].y, b = P < 2 ? r[2 * q + 1].x : r[2 * q + 1].y;
-        w[q] = __builtin_amdgcn_perm(b, a, sel);
-    }
-    return __builtin_bit_cast(bb_bf16x8, make_uint4(w[0], w[1], w[2], w[3]));
-}
-__device__ __forceinline__ bb_bf16x8 bb_tr_dyn(const uint2 (&r)[8], int P) {
-    switch (P) {
-        case 0: return bb_tr<0>(r);
-        case 1: return bb_tr<1>(r);
-        case 2: return bb_tr<2>(r);
-        default: return bb_tr<3>(r);
-    }
-}
 
 // phase-timeline stamps (tuning aid): compiled in only with -DFGNN_ENABLE_PROF, read with FGNN_PROF=1
 #ifdef FGNN_ENABLE_PROF
@@ -139,8 +107,8 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
     // ---- resident W fragments ----
     // aP: A of P^T = W^T x   : A[i = col][k = c] = W[c][col], 8 consecutive c (stride NCOLS)
     // aT: A of dx^T = W dP^T : A[i = c][k = col] = W[c][col],  8 consecutive cols
-    bb_bf16x8 aP[NPASS][KS2];
-    bb_bf16x8 aT[AT_RES ? NPASS : 1][4];
+    bf16x8 aP[NPASS][KS2];
+    bf16x8 aT[AT_RES ? NPASS : 1][4];
     {
         const int li0 = lane & 15, lk0 = lane >> 4;
 #pragma unroll
@@ -152,12 +120,12 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
                     alignas(16) float w8[8];
 #pragma unroll
                     for (int u = 0; u < 8; ++u) w8[u] = wp[(int64_t)u * NCOLS];
-                    aP[ps][ks] = bb_frag_f32(w8);
+                    aP[ps][ks] = fgnn_frag8(w8);
                 }
             if constexpr (AT_RES) {
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks)
-                    aT[ps][ks] = bb_frag_f32(p.W + (int64_t)(ct * 16 + li0) * NCOLS + ps * 128 + 32 * ks + 8 * lk0);
+                    aT[ps][ks] = fgnn_frag8(p.W + (int64_t)(ct * 16 + li0) * NCOLS + ps * 128 + 32 * ks + 8 * lk0);
             }
         }
     }
@@ -212,7 +180,7 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
             }
         }
         if (t < mk) {
-            *reinterpret_cast<f32x4*>(et_s + t * 4) = (f32x4){bb_lo(pe.x), bb_hi(pe.x), bb_lo(pe.y), bb_hi(pe.y)};
+            *reinterpret_cast<f32x4*>(et_s + t * 4) = (f32x4){fgnn_lo(pe.x), fgnn_hi(pe.x), fgnn_lo(pe.y), fgnn_hi(pe.y)};
             *reinterpret_cast<f32x4*>(det_s + t * 4) = (f32x4){0.f, 0.f, 0.f, 0.f};
             const long long v = ir;
             idx_s[t] = (int)(v < 0 ? 0 : (v >= N ? N - 1 : v));
@@ -221,8 +189,8 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
     auto commit_g = [&](int t) {
         if (t < 4 * M) {
             float* dst = gz_s + (t >> 2) * BB_GS + (t & 3) * 8;
-            *reinterpret_cast<f32x4*>(dst) = (f32x4){bb_lo(pg.x), bb_hi(pg.x), bb_lo(pg.y), bb_hi(pg.y)};
-            *reinterpret_cast<f32x4*>(dst + 4) = (f32x4){bb_lo(pg.z), bb_hi(pg.z), bb_lo(pg.w), bb_hi(pg.w)};
+            *reinterpret_cast<f32x4*>(dst) = (f32x4){fgnn_lo(pg.x), fgnn_hi(pg.x), fgnn_lo(pg.y), fgnn_hi(pg.y)};
+            *reinterpret_cast<f32x4*>(dst + 4) = (f32x4){fgnn_lo(pg.z), fgnn_hi(pg.z), fgnn_lo(pg.w), fgnn_hi(pg.w)};
         }
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -318,7 +286,7 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
             if constexpr (!AT_RES) {
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks)
-                    aT[0][ks] = bb_frag_f32(p.W + (int64_t)(ct * 16 + li) * NCOLS + pass * 128 + 32 * ks + 8 * lk);
+                    aT[0][ks] = fgnn_frag8(p.W + (int64_t)(ct * 16 + li) * NCOLS + pass * 128 + 32 * ks + 8 * lk);
             }
             BB_STAMP(5 + 8 * pass);
             // ---- P^T slab (wave = 16-column slab of the pass): D[i = col][j = n]; only detype needs P ----
@@ -328,9 +296,9 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
 #pragma unroll
                 for (int ks = 0; ks < KS2; ++ks)
                     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        aP[pass][ks], __builtin_bit_cast(bb_bf16x8, *reinterpret_cast<const uint4*>(bp + 32 * ks)), acc, 0, 0, 0);
+                        aP[pass][ks], __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp + 32 * ks)), acc, 0, 0, 0);
                 *reinterpret_cast<uint2*>(pb + (nt * 16 + li) * BB_PSB + wave * 16 + 4 * lk) =
-                    make_uint2(bb_pack2(acc[0], acc[1]), bb_pack2(acc[2], acc[3]));
+                    make_uint2(fgnn_pack2(acc[0], acc[1]), fgnn_pack2(acc[2], acc[3]));
             }
             // dbias: thread (row group t >> 5, channel t & 31) sums rows t >> 5, +16, ... of this pass's gz slice
             // (gz_s of this pass was committed before the previous barrier or, for pass 0, before the sample's)
@@ -361,10 +329,10 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
                     float acc[4] = {0.f, 0.f, 0.f, 0.f};
                     auto one = [&](unsigned x4, int u, float g, unsigned lo2, unsigned hi2) {
                         const float gg = ((x4 >> (8 * u)) & 0xffu) == 0u ? g : 0.f;
-                        acc[0] = fmaf(gg, bb_lo(lo2), acc[0]);
-                        acc[1] = fmaf(gg, bb_hi(lo2), acc[1]);
-                        acc[2] = fmaf(gg, bb_lo(hi2), acc[2]);
-                        acc[3] = fmaf(gg, bb_hi(hi2), acc[3]);
+                        acc[0] = fmaf(gg, fgnn_lo(lo2), acc[0]);
+                        acc[1] = fmaf(gg, fgnn_hi(lo2), acc[1]);
+                        acc[2] = fmaf(gg, fgnn_lo(hi2), acc[2]);
+                        acc[3] = fmaf(gg, fgnn_hi(hi2), acc[3]);
                     };
                     one(xa, 0, g0[0], p0.x, p0.y); one(xa, 1, g0[1], p0.z, p0.w);
                     one(xa, 2, g0[2], p1.x, p1.y); one(xa, 3, g0[3], p1.z, p1.w);
@@ -416,10 +384,10 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
                         }
                     }
                     uint4* dst = reinterpret_cast<uint4*>(db + n * BB_PSB + og * 16);
-                    dst[0] = make_uint4(bb_pack2(acc[0], acc[1]), bb_pack2(acc[2], acc[3]),
-                                        bb_pack2(acc[4], acc[5]), bb_pack2(acc[6], acc[7]));
-                    dst[1] = make_uint4(bb_pack2(acc[8], acc[9]), bb_pack2(acc[10], acc[11]),
-                                        bb_pack2(acc[12], acc[13]), bb_pack2(acc[14], acc[15]));
+                    dst[0] = make_uint4(fgnn_pack2(acc[0], acc[1]), fgnn_pack2(acc[2], acc[3]),
+                                        fgnn_pack2(acc[4], acc[5]), fgnn_pack2(acc[6], acc[7]));
+                    dst[1] = make_uint4(fgnn_pack2(acc[8], acc[9]), fgnn_pack2(acc[10], acc[11]),
+                                        fgnn_pack2(acc[12], acc[13]), fgnn_pack2(acc[14], acc[15]));
                 }
             }
             __syncthreads();
@@ -435,7 +403,7 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
 #pragma unroll
                     for (int ks = 0; ks < 4; ++ks)
                         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                            aT[APS][ks], __builtin_bit_cast(bb_bf16x8, *reinterpret_cast<const uint4*>(bp + 32 * ks)), acc, 0, 0, 0);
+                            aT[APS][ks], __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp + 32 * ks)), acc, 0, 0, 0);
                     dxacc[i] = acc;
                 }
             }
@@ -448,17 +416,17 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
                     rd[j] = *reinterpret_cast<const uint2*>(db + (row0 + j) * BB_PSB + 64 * (wave >> 2) + 4 * li);
-                const bb_bf16x8 bfr = bb_tr_dyn(rd, wave & 3);
+                const bf16x8 bfr = __builtin_bit_cast(bf16x8, fgnn_perm_col_dyn(rd, wave & 3));
 #pragma unroll
                 for (int h = 0; h < HX; ++h) {
                     uint2 rx[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
                         rx[j] = *reinterpret_cast<const uint2*>(xb + (row0 + j) * XSB + 64 * h + 4 * li);
-                    gw[pass][4 * h + 0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bb_tr<0>(rx), bfr, gw[pass][4 * h + 0], 0, 0, 0);
-                    gw[pass][4 * h + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bb_tr<1>(rx), bfr, gw[pass][4 * h + 1], 0, 0, 0);
-                    gw[pass][4 * h + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bb_tr<2>(rx), bfr, gw[pass][4 * h + 2], 0, 0, 0);
-                    gw[pass][4 * h + 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bb_tr<3>(rx), bfr, gw[pass][4 * h + 3], 0, 0, 0);
+                    gw[pass][4 * h + 0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fgnn_perm_col<0>(rx)), bfr, gw[pass][4 * h + 0], 0, 0, 0);
+                    gw[pass][4 * h + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fgnn_perm_col<1>(rx)), bfr, gw[pass][4 * h + 1], 0, 0, 0);
+                    gw[pass][4 * h + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fgnn_perm_col<2>(rx)), bfr, gw[pass][4 * h + 2], 0, 0, 0);
+                    gw[pass][4 * h + 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fgnn_perm_col<3>(rx)), bfr, gw[pass][4 * h + 3], 0, 0, 0);
                 }
             }
             BB_STAMP(10 + 8 * pass);
@@ -473,7 +441,7 @@ __global__ __launch_bounds__(BB_THREADS) void mpconv_bwd_b16_kernel(const Bb16Pa
                 const int n = nt * 16 + li;
                 if (nt < ntile && n < N)
                     *reinterpret_cast<uint2*>(gxb + (int64_t)n * NIN + ct * 16 + 4 * lk) =
-                        make_uint2(bb_pack2(dxacc[i][0], dxacc[i][1]), bb_pack2(dxacc[i][2], dxacc[i][3]));
+                        make_uint2(fgnn_pack2(dxacc[i][0], dxacc[i][1]), fgnn_pack2(dxacc[i][2], dxacc[i][3]));
             }
             if (p.get && t < mk) {                     // det_s is complete since the last pass's gather barrier
                 const f32x4 dv = *reinterpret_cast<const f32x4*>(det_s + t * 4);

@@ -25,6 +25,7 @@
 // LDS rows: x image stride 68 floats, P / dP stride 132: every access pattern above is bank-conflict-free (the k index of
 // the gW product runs over nodes in the order 4 lk + (kk & 3) + 16 (kk >> 2) for that reason).
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "mpconv_dispatch.h"
 #include <stdlib.h>
 
@@ -530,8 +531,6 @@ __global__ __launch_bounds__(BX_THREADS, 2) void mpconv_bwd_ext_kernel(const BxP
 //   * gW's node-contracted operands (x^T, dP with K = nodes) come out of the row-major piece images through ds_read_b64_tr_b16.
 // Max aggregation, 64 output channels; everything else (tables, phases B1 / dS / dT, slabs, fixed summation orders) is the
 // exact kernel's.  Same bits run to run.
-typedef __bf16 bq_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bq_s16x4 __attribute__((ext_vector_type(4)));
 #define BQ_XROW 128           // bytes per row of an x piece image (64 bf16)
 #define BQ_DROW 256           // bytes per row of a dP piece image (128 bf16)
 #define BQ_XPIECE (64 * BQ_XROW)
@@ -542,22 +541,12 @@ typedef short bq_s16x4 __attribute__((ext_vector_type(4)));
 // operand read's service group rows {0-3, 12-15} (first half of the segment) + {4-11} (second half)
 __device__ __forceinline__ int bq_swx(int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 1); }      // 128-byte rows: bank bit 5 is the row's parity
 __device__ __forceinline__ int bq_swd(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }             // 256-byte rows
-__device__ __forceinline__ unsigned bq_pack2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
 template <int NP> __device__ __forceinline__ void bq_split2(float a, float b, unsigned (&o)[NP]) {
 #pragma unroll
     for (int t = 0; t < NP; ++t) {
-        o[t] = bq_pack2(a, b);
+        o[t] = fgnn_pack2(a, b);
         if (t + 1 < NP) { a -= __uint_as_float(o[t] << 16); b -= __uint_as_float(o[t] & 0xffff0000u); }
     }
-}
-__device__ __forceinline__ uint2 bq_tr(unsigned lds_addr) {
-    typedef __attribute__((address_space(3))) bq_s16x4 lds_v4;
-    const bq_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_v4*>(static_cast<uintptr_t>(lds_addr)));
-    return __builtin_bit_cast(uint2, v);
 }
 // the piece products of a fragment pair, smallest first: (l h' + h l' + m m') + (m h' + h m') + h h'   |   NP = 2: l h' + h l' + h h'
 template <int NP> struct BqTerms;
@@ -727,8 +716,8 @@ __global__ __launch_bounds__(BX_THREADS, 1) void mpconv_bwd_extq_kernel(const Bx
 
     // ---- filter pieces of a pass: 6 NP 16-byte loads per lane; the next pass's are asked for behind the last stage of a pass, under
     //      the slab stores and the bias reduction ----
-    bq_bf16x8 wA[NP][2];                                              // P = x W: B operand [k = c 32 ks + 8 lk ..][n = this wave's column li]
-    bq_bf16x8 wG[NP][4];                                              // gx = dP Wc: B operand [k = dP column 32 ks + 8 lk ..][n = c 16 ct + li]
+    bf16x8 wA[NP][2];                                              // P = x W: B operand [k = c 32 ks + 8 lk ..][n = this wave's column li]
+    bf16x8 wG[NP][4];                                              // gx = dP Wc: B operand [k = dP column 32 ks + 8 lk ..][n = c 16 ct + li]
     auto load_w = [&](int pass) {
         const int col = 16 * (BX_PCH * pass + a_sl) + li;
         const uint16_t* base = p.wq1 + ((int64_t)a_half * 1024 + col) * 64 + 8 * lk;
@@ -736,13 +725,13 @@ __global__ __launch_bounds__(BX_THREADS, 1) void mpconv_bwd_extq_kernel(const Bx
         for (int t = 0; t < NP; ++t)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                wA[t][ks] = __builtin_bit_cast(bq_bf16x8, *reinterpret_cast<const uint4*>(base + (int64_t)t * BQ_WPIECE + 32 * ks));
+                wA[t][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(base + (int64_t)t * BQ_WPIECE + 32 * ks));
         const int c = 16 * c_ct + li;
 #pragma unroll
         for (int t = 0; t < NP; ++t)
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks)
-                wG[t][ks] = __builtin_bit_cast(bq_bf16x8, *reinterpret_cast<const uint4*>(
+                wG[t][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(
                     p.wq2 + (int64_t)t * BQ_WPIECE + ((int64_t)(ks >> 1) * 64 + c) * 1024 + 64 * pass + 32 * (ks & 1) + 8 * lk));
     };
 
@@ -794,12 +783,12 @@ __global__ __launch_bounds__(BX_THREADS, 1) void mpconv_bwd_extq_kernel(const Bx
                     const int row = 16 * nt + li;
                     const unsigned char* xrow = xq + row * BQ_XROW + ((lk & 1) << 4);
                     const int sw = bq_swx(row);
-                    bq_bf16x8 xa[NP][2];
+                    bf16x8 xa[NP][2];
 #pragma unroll
                     for (int t = 0; t < NP; ++t)
 #pragma unroll
                         for (int ks = 0; ks < 2; ++ks)
-                            xa[t][ks] = __builtin_bit_cast(bq_bf16x8, *reinterpret_cast<const uint4*>(xrow + t * BQ_XPIECE + (((2 * ks + (lk >> 1)) ^ sw) << 5)));
+                            xa[t][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(xrow + t * BQ_XPIECE + (((2 * ks + (lk >> 1)) ^ sw) << 5)));
                     f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
                     for (int pr = 0; pr < TM::N; ++pr)
@@ -934,22 +923,22 @@ __global__ __launch_bounds__(BX_THREADS, 1) void mpconv_bwd_extq_kernel(const Bx
                     const unsigned xo0 = lds0 + p.off_xq + r0 * BQ_XROW + ((li & 3) << 3), xo1 = lds0 + p.off_xq + r1 * BQ_XROW + ((li & 3) << 3);
                     const unsigned do0 = lds0 + p.off_dq + r0 * BQ_DROW + ((li & 3) << 3), do1 = lds0 + p.off_dq + r1 * BQ_DROW + ((li & 3) << 3);
                     const int sx0 = bq_swx(r0), sx1 = bq_swx(r1), sd0 = bq_swd(r0), sd1 = bq_swd(r1);
-                    bq_bf16x8 xa[2][NP], db[2][NP];
+                    bf16x8 xa[2][NP], db[2][NP];
 #pragma unroll
                     for (int a = 0; a < 2; ++a)
 #pragma unroll
                         for (int t = 0; t < NP; ++t) {
                             const int ct = 2 * w_cp + a;
-                            const uint2 lo = bq_tr(xo0 + t * BQ_XPIECE + ((ct ^ sx0) << 5)), hi = bq_tr(xo1 + t * BQ_XPIECE + ((ct ^ sx1) << 5));
-                            xa[a][t] = __builtin_bit_cast(bq_bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+                            const uint2 lo = fgnn_tr16(xo0 + t * BQ_XPIECE + ((ct ^ sx0) << 5)), hi = fgnn_tr16(xo1 + t * BQ_XPIECE + ((ct ^ sx1) << 5));
+                            xa[a][t] = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
                         }
 #pragma unroll
                     for (int h = 0; h < 2; ++h)
 #pragma unroll
                         for (int t = 0; t < NP; ++t) {
                             const int g = 4 * h + w_t;
-                            const uint2 lo = bq_tr(do0 + t * BQ_DPIECE + ((g ^ sd0) << 5)), hi = bq_tr(do1 + t * BQ_DPIECE + ((g ^ sd1) << 5));
-                            db[h][t] = __builtin_bit_cast(bq_bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
+                            const uint2 lo = fgnn_tr16(do0 + t * BQ_DPIECE + ((g ^ sd0) << 5)), hi = fgnn_tr16(do1 + t * BQ_DPIECE + ((g ^ sd1) << 5));
+                            db[h][t] = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi.x, hi.y));
                         }
 #pragma unroll
                     for (int pr = 0; pr < TM::N; ++pr)
@@ -969,12 +958,12 @@ __global__ __launch_bounds__(BX_THREADS, 1) void mpconv_bwd_extq_kernel(const Bx
                     f32x4 accx[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};       // two chains (even / odd k-steps)
 #pragma unroll
                     for (int kp = 0; kp < 2; ++kp) {
-                        bq_bf16x8 da[2][NP];
+                        bf16x8 da[2][NP];
 #pragma unroll
                         for (int q = 0; q < 2; ++q)
 #pragma unroll
                             for (int t = 0; t < NP; ++t)
-                                da[q][t] = __builtin_bit_cast(bq_bf16x8, *reinterpret_cast<const uint4*>(drow + t * BQ_DPIECE + (((2 * (2 * kp + q) + (lk >> 1)) ^ sd) << 5)));
+                                da[q][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(drow + t * BQ_DPIECE + (((2 * (2 * kp + q) + (lk >> 1)) ^ sd) << 5)));
 #pragma unroll
                         for (int pr = 0; pr < TM::N; ++pr)
 #pragma unroll

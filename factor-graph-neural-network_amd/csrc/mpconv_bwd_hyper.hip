@@ -22,6 +22,7 @@
 // workgroup's slab of the caller's workspace (summed by the slab reduce of mpconv_bwd_res.hip).
 // Both kernels are HBM-bound: fan-in writes the (mostly zero) gx, fan-out reads gz.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "mpconv_dispatch.h"
 #include <stdlib.h>
 
@@ -43,9 +44,6 @@ struct BhParams {
 
 extern __shared__ __attribute__((aligned(16))) float fgnn_lds_bh[];
 
-__device__ __forceinline__ float bh_bcast(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
 
 // Stage W [nin][nou] (row-major) transposed into LDS: Wl[o * nin + c].
 template <int NIN, int NOU>
@@ -143,7 +141,7 @@ __global__ __launch_bounds__(BH_THREADS) void mpconv_bwd_fanin_kernel(const BhPa
 #pragma unroll
             for (int ol = 0; ol < 64; ++ol) {
                 const int n = __builtin_amdgcn_readlane(ns[q], ol);
-                const float s = bh_bcast(cf[q], ol);
+                const float s = fgnn_bcast(cf[q], ol);
 #pragma unroll
                 for (int i = 0; i < NI; ++i)
                     dW[i][ol + 64 * q] =
@@ -161,7 +159,7 @@ __global__ __launch_bounds__(BH_THREADS) void mpconv_bwd_fanin_kernel(const BhPa
                 while (mask) {
                     const int ol = __builtin_ctzll(mask);
                     mask &= mask - 1;
-                    const float s = bh_bcast(cf[q], ol);
+                    const float s = fgnn_bcast(cf[q], ol);
                     const float* wr = Wl + (ol + 64 * q) * NIN + lane;
 #pragma unroll
                     for (int i = 0; i < NI; ++i) acc[i] = fmaf(s, wr[64 * i], acc[i]);
@@ -243,7 +241,7 @@ __global__ __launch_bounds__(BH_THREADS) void mpconv_bwd_fanout_kernel(const BhP
         for (int i = 0; i < NI; ++i) acc[i] = 0.f;
 #pragma unroll
         for (int o = 0; o < NOU; ++o) {
-            const float s = bh_bcast(dp[o % CH], o / CH);
+            const float s = fgnn_bcast(dp[o % CH], o / CH);
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
                 acc[i] = fmaf(s, Wl[o * NIN + lane + 64 * i], acc[i]);

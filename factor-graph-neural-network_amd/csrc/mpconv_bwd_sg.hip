@@ -24,6 +24,7 @@
 // One 1024-thread workgroup (16 waves) per CU: the LDS images of a sample (x double-buffered 2 x 14 KB, P / dP 50 KB —
 // one buffer, used in turn —, gz+argmax 12..25 KB, the per-wave detype images 55 KB) do not leave room for two.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "mpconv_dispatch.h"
 #include <stdlib.h>
 
@@ -43,7 +44,6 @@
                              // at 17 slots (272 B) every read cost 2x: 140.7 -> 132.8 us (V->F), 148.6 -> 136.4 us (F->V)
 #define BS_MAXN 96
 
-typedef __bf16 bs_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float bs_f32x2 __attribute__((ext_vector_type(2)));
 
 struct BsParams {
@@ -73,46 +73,6 @@ extern __shared__ __attribute__((aligned(16))) unsigned char bs_lds[];
 #define BS_STAMP(slot) do { } while (0)
 #endif
 
-// uniform 64-bit base + UNSIGNED 32-bit per-lane byte offset: the form the compiler turns into `global_load v, v_off, s[base]`
-// (a signed or 64-bit per-lane offset becomes a per-lane 64-bit pointer: two VGPRs each, hoisted out of the sample loop)
-template <typename T> __device__ __forceinline__ const T* bs_at(const void* base, unsigned byte_off) {
-    return reinterpret_cast<const T*>(static_cast<const char*>(base) + byte_off);
-}
-template <typename T> __device__ __forceinline__ T* bs_at(void* base, unsigned byte_off) {
-    return reinterpret_cast<T*>(static_cast<char*>(base) + byte_off);
-}
-__device__ __forceinline__ float bs_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bs_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ unsigned bs_pack2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ bs_bf16x8 bs_frag_f32(const float* p8) {      // 8 consecutive f32 -> one fragment
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p8), b = *reinterpret_cast<const f32x4*>(p8 + 4);
-    return __builtin_bit_cast(bs_bf16x8, make_uint4(bs_pack2(a[0], a[1]), bs_pack2(a[2], a[3]),
-                                                    bs_pack2(b[0], b[1]), bs_pack2(b[2], b[3])));
-}
-// rows r0..r7 each hold columns (c0 c1 | c2 c3) as two dwords: gather column P's eight values
-template <int P>
-__device__ __forceinline__ bs_bf16x8 bs_tr(const uint2 (&r)[8]) {
-    constexpr unsigned sel = (P & 1) ? 0x07060302u : 0x05040100u;
-    unsigned w[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const unsigned a = P < 2 ? r[2 * q].x : r[2 * q].y, b = P < 2 ? r[2 * q + 1].x : r[2 * q + 1].y;
-        w[q] = __builtin_amdgcn_perm(b, a, sel);
-    }
-    return __builtin_bit_cast(bs_bf16x8, make_uint4(w[0], w[1], w[2], w[3]));
-}
-__device__ __forceinline__ bs_bf16x8 bs_tr_dyn(const uint2 (&r)[8], int P) {
-    switch (P) {
-        case 0: return bs_tr<0>(r);
-        case 1: return bs_tr<1>(r);
-        case 2: return bs_tr<2>(r);
-        default: return bs_tr<3>(r);
-    }
-}
 
 // KC = destination degree (neighbour slots per destination), DEG = in-edges per source node the tables are sized for,
 // NPW = source nodes per wave (ceil(N / 16)), DPW = destinations per wave (ceil(M / 16))
@@ -195,7 +155,7 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
     //               aT: A of dx^T = W dP^T (wave & 3 = 16-channel tile): A[i = c][k = col] = W[ct*16 + i][col], 8 consecutive cols.
     //               Resident (32 VGPRs): re-reading it from L2 per sample had every CU of the chip hammering the same 64 KB —
     //               17 000 cycles per sample in the dx phase (profiles/r02).
-    bs_bf16x8 aP[2];
+    bf16x8 aP[2];
     {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -203,7 +163,7 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
             alignas(16) float w8[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) w8[u] = wp[(int64_t)u * p.w_ld];
-            aP[ks] = bs_frag_f32(w8);
+            aP[ks] = fgnn_frag8(w8);
         }
     }
     // The last two phases of a sample both only READ the dP image, so they run side by side on the two halves of the
@@ -220,13 +180,13 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
     } else {
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks)
-            R[ks] = __builtin_bit_cast(f32x4, bs_frag_f32(p.W + (int64_t)(ct * 16 + li) * p.w_ld + 32 * ks + 8 * lk));
+            R[ks] = __builtin_bit_cast(f32x4, fgnn_frag8(p.W + (int64_t)(ct * 16 + li) * p.w_ld + 32 * ks + 8 * lk));
     }
     // A operand of the channel sums: row 0 adds the even k (first edge type of a pair), row 1 the odd k, other rows nothing
-    bs_bf16x8 evod;
+    bf16x8 evod;
     {
         const unsigned w = li == 0 ? 0x00003f80u : (li == 1 ? 0x3f800000u : 0u);
-        evod = __builtin_bit_cast(bs_bf16x8, make_uint4(w, w, w, w));
+        evod = __builtin_bit_cast(bf16x8, make_uint4(w, w, w, w));
     }
     float gbacc = 0.f;                                // dbias of channel `lane` over this wave's destinations (detype phase)
 
@@ -243,18 +203,18 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
         const unsigned utid = (unsigned)t;
         const int lane = t & 63;
         px = make_uint4(0, 0, 0, 0);
-        if (t < xchunks) px = *bs_at<uint4>(p.x + (int64_t)b * p.x_sb, utid * 16u);
+        if (t < xchunks) px = *fgnn_at<uint4>(p.x + (int64_t)b * p.x_sb, utid * 16u);
         const uint16_t* gzb = p.gz + (int64_t)b * p.y_sb;
         const uint8_t* amb = p.argmax + (int64_t)b * p.y_sb;
         pg = make_uint4(0, 0, 0, 0);
         pa = make_uint2(0, 0);
         if (t < gitems) {
             const unsigned el = (utid >> 3) * (unsigned)p.y_ld + (utid & 7u) * 8u;      // row m = item >> 3, channels 8 (item & 7) ..
-            pg = *bs_at<uint4>(gzb, el * 2u);
-            pa = *bs_at<uint2>(amb, el);
+            pg = *fgnn_at<uint4>(gzb, el * 2u);
+            pa = *fgnn_at<uint2>(amb, el);
         }
         pe = make_uint2(0, 0);
-        if (lane < NPW * DEG) pe = *bs_at<uint2>(p.et + (int64_t)b * p.et_sb, (unsigned)et_goff * 2u);
+        if (lane < NPW * DEG) pe = *fgnn_at<uint2>(p.et + (int64_t)b * p.et_sb, (unsigned)et_goff * 2u);
     };
     auto commit = [&](unsigned char* xs, int t) {
         if (t < xchunks) *reinterpret_cast<uint4*>(xs + (t >> 3) * BS_XSB + (t & 7) * 16) = px;
@@ -316,12 +276,12 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
         // ---- P^T slab (wave = 16-column slab = channels 4 wave .. +3): D[i = col][j = node] ----
         for (int nt0 = 0; nt0 < ntile; nt0 += 2) {       // two node tiles in flight (ntile is even: Npad is a multiple of 32)
             f32x4 acc[2];
-            bs_bf16x8 bf[2][2];
+            bf16x8 bf[2][2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const unsigned char* bp = xs + ((nt0 + u) * 16 + li) * BS_XSB + lk * 16;
-                bf[u][0] = __builtin_bit_cast(bs_bf16x8, *reinterpret_cast<const uint4*>(bp));
-                bf[u][1] = __builtin_bit_cast(bs_bf16x8, *reinterpret_cast<const uint4*>(bp + 64));
+                bf[u][0] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp));
+                bf[u][1] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp + 64));
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
@@ -332,7 +292,7 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
 #pragma unroll
             for (int u = 0; u < 2; ++u)
                 *reinterpret_cast<uint2*>(pd + ((nt0 + u) * 16 + li) * BS_PSB + (4 * wave + lk) * 8) =
-                    make_uint2(bs_pack2(acc[u][0], acc[u][1]), bs_pack2(acc[u][2], acc[u][3]));
+                    make_uint2(fgnn_pack2(acc[u][0], acc[u][1]), fgnn_pack2(acc[u][2], acc[u][3]));
         }
         BS_STAMP(2);
         __syncthreads();                              // B_b: P complete
@@ -375,8 +335,8 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
                     const uint2 pk = pkv[d];
                     const float g = live ? __uint_as_float(dwv[d] & 0xffff0000u) : 0.f;
                     gbacc += g;
-                    const unsigned c01 = bs_pack2(g * bs_lo(pk.x), g * bs_hi(pk.x));
-                    const unsigned c23 = bs_pack2(g * bs_lo(pk.y), g * bs_hi(pk.y));
+                    const unsigned c01 = fgnn_pack2(g * fgnn_lo(pk.x), g * fgnn_hi(pk.x));
+                    const unsigned c23 = fgnn_pack2(g * fgnn_lo(pk.y), g * fgnn_hi(pk.y));
                     // column (destination u, slot jst, pair 0) <- {e0 | e1}, (.., pair 1) <- {e2 | e3}, dword `lane` of each
                     zw[u] = reinterpret_cast<unsigned*>(zb + (u * KC + jst) * (2 * BS_ZCS) + lane * 4);
                     zw[u][0] = c01;
@@ -385,9 +345,9 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
                 asm volatile("" ::: "memory");            // the image is re-read below through another type: keep the stores
                 // D[0][col] = sum over channels of the even halves, D[1][col] of the odd halves; K = 64 channels x 2
                 const unsigned char* zr = zb + li * BS_ZCS + lk * 16;
-                bs_bf16x8 fr[4];
+                bf16x8 fr[4];
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) fr[ks] = __builtin_bit_cast(bs_bf16x8, *reinterpret_cast<const uint4*>(zr + 64 * ks));
+                for (int ks = 0; ks < 4; ++ks) fr[ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(zr + 64 * ks));
                 asm volatile("" ::: "memory");
 #pragma unroll
                 for (int u = 0; u < DPP; ++u) {           // (issued right behind the reads: LDS runs a wave's operations in order)
@@ -421,16 +381,16 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
             if (t < nvec) {
                 uint4 v = *reinterpret_cast<const uint4*>(gsrc + t * 16);
                 if (p.accum) {                         // second launch of a split call: add to what the first one stored
-                    const uint4 o = *bs_at<uint4>(gdst, (unsigned)t * 16u);
-                    v = make_uint4(bs_pack2(bs_lo(v.x) + bs_lo(o.x), bs_hi(v.x) + bs_hi(o.x)), bs_pack2(bs_lo(v.y) + bs_lo(o.y), bs_hi(v.y) + bs_hi(o.y)),
-                                   bs_pack2(bs_lo(v.z) + bs_lo(o.z), bs_hi(v.z) + bs_hi(o.z)), bs_pack2(bs_lo(v.w) + bs_lo(o.w), bs_hi(v.w) + bs_hi(o.w)));
+                    const uint4 o = *fgnn_at<uint4>(gdst, (unsigned)t * 16u);
+                    v = make_uint4(fgnn_pack2(fgnn_lo(v.x) + fgnn_lo(o.x), fgnn_hi(v.x) + fgnn_hi(o.x)), fgnn_pack2(fgnn_lo(v.y) + fgnn_lo(o.y), fgnn_hi(v.y) + fgnn_hi(o.y)),
+                                   fgnn_pack2(fgnn_lo(v.z) + fgnn_lo(o.z), fgnn_hi(v.z) + fgnn_hi(o.z)), fgnn_pack2(fgnn_lo(v.w) + fgnn_lo(o.w), fgnn_hi(v.w) + fgnn_hi(o.w)));
                 }
-                *bs_at<uint4>(gdst, (unsigned)t * 16u) = v;
+                *fgnn_at<uint4>(gdst, (unsigned)t * 16u) = v;
             }
             for (int f = nvec * 8 + t; f < 4 * mk; f += BS_THREADS) {
                 uint16_t v = *reinterpret_cast<const uint16_t*>(gsrc + f * 2);
-                if (p.accum) v = (uint16_t)(bs_pack2(bs_lo(v) + bs_lo(*bs_at<uint16_t>(gdst, (unsigned)f * 2u)), 0.f) & 0xffffu);
-                *bs_at<uint16_t>(gdst, (unsigned)f * 2u) = v;
+                if (p.accum) v = (uint16_t)(fgnn_pack2(fgnn_lo(v) + fgnn_lo(*fgnn_at<uint16_t>(gdst, (unsigned)f * 2u)), 0.f) & 0xffffu);
+                *fgnn_at<uint16_t>(gdst, (unsigned)f * 2u) = v;
             }
         }
 
@@ -441,7 +401,6 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
         //      row).  Per in-edge and lane: one LDS read, a bit-field extract, an AND (the FMA form took 10 VALU instructions per
         //      in-edge: 3 300 cycles of the sample on the vector ALUs) ----
         {
-            typedef short bs_s16x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
             for (int i = 0; i < NPW; ++i) {
                 const int n = n0 + i;
@@ -462,9 +421,9 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
                         const uint2 av = *reinterpret_cast<const uint2*>(ap + 8 * g4);
                         const uint2 bv = make_uint2(__builtin_amdgcn_perm(gm[4 * g4 + 1], gm[4 * g4], 0x07060302u),
                                                     __builtin_amdgcn_perm(gm[4 * g4 + 3], gm[4 * g4 + 2], 0x07060302u));
-                        acc = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(bs_s16x4, av), __builtin_bit_cast(bs_s16x4, bv), acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(s16x4, av), __builtin_bit_cast(s16x4, bv), acc, 0, 0, 0);
                     }
-                    *reinterpret_cast<uint2*>(pd + n * BS_PSB + lane * 8) = make_uint2(bs_pack2(acc[0], acc[1]), bs_pack2(acc[2], acc[3]));
+                    *reinterpret_cast<uint2*>(pd + n * BS_PSB + lane * 8) = make_uint2(fgnn_pack2(acc[0], acc[1]), fgnn_pack2(acc[2], acc[3]));
                 }
             }
         }
@@ -486,7 +445,7 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
             for (int i = 0; i < 3; ++i) {
                 const int n = (((wave - 8) >> 2) + 2 * i) * 16 + li;
                 old[i] = make_uint2(0u, 0u);
-                if (p.accum && n < N) old[i] = *bs_at<uint2>(gxb, (unsigned)(n * NIN + ct * 16 + 4 * lk) * 2u);
+                if (p.accum && n < N) old[i] = *fgnn_at<uint2>(gxb, (unsigned)(n * NIN + ct * 16 + 4 * lk) * 2u);
             }
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -497,13 +456,13 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
 #pragma unroll
                     for (int ks = 0; ks < 8; ++ks)
                         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                            __builtin_bit_cast(bs_bf16x8, R[ks]),
-                            __builtin_bit_cast(bs_bf16x8, *reinterpret_cast<const uint4*>(bp + 64 * ks)), acc, 0, 0, 0);
+                            __builtin_bit_cast(bf16x8, R[ks]),
+                            __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp + 64 * ks)), acc, 0, 0, 0);
                     const int n = nt * 16 + li;
                     if (n < N)
-                        *bs_at<uint2>(gxb, (unsigned)(n * NIN + ct * 16 + 4 * lk) * 2u) =
-                            make_uint2(bs_pack2(acc[0] + bs_lo(old[i].x), acc[1] + bs_hi(old[i].x)),
-                                       bs_pack2(acc[2] + bs_lo(old[i].y), acc[3] + bs_hi(old[i].y)));
+                        *fgnn_at<uint2>(gxb, (unsigned)(n * NIN + ct * 16 + 4 * lk) * 2u) =
+                            make_uint2(fgnn_pack2(acc[0] + fgnn_lo(old[i].x), acc[1] + fgnn_hi(old[i].x)),
+                                       fgnn_pack2(acc[2] + fgnn_lo(old[i].y), acc[3] + fgnn_hi(old[i].y)));
                 }
             }
         } else {
@@ -511,35 +470,35 @@ __global__ __launch_bounds__(BS_THREADS, 4) void mpconv_bwd_sg_kernel(const BsPa
             //      2 (wave & 1), 2 (wave & 1) + 1 of the 64-column group wave >> 1 ----
             for (int kst = 0; kst < nkst; ++kst) {
                 const int row0 = 32 * kst + 8 * lk;
-                bs_bf16x8 bfr0, bfr1;
+                bf16x8 bfr0, bfr1;
                 {
                     uint2 rd[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
                         rd[j] = *reinterpret_cast<const uint2*>(pd + (row0 + j) * BS_PSB + 128 * (wave >> 1) + 8 * li);
-                    if (wave & 1) { bfr0 = bs_tr<2>(rd); bfr1 = bs_tr<3>(rd); }
-                    else { bfr0 = bs_tr<0>(rd); bfr1 = bs_tr<1>(rd); }
+                    if (wave & 1) { bfr0 = __builtin_bit_cast(bf16x8, fgnn_perm_col<2>(rd)); bfr1 = __builtin_bit_cast(bf16x8, fgnn_perm_col<3>(rd)); }
+                    else { bfr0 = __builtin_bit_cast(bf16x8, fgnn_perm_col<0>(rd)); bfr1 = __builtin_bit_cast(bf16x8, fgnn_perm_col<1>(rd)); }
                 }
                 uint2 rx[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) rx[j] = *reinterpret_cast<const uint2*>(xs + (row0 + j) * BS_XSB + 8 * li);
                 {
-                    const bs_bf16x8 a0 = bs_tr<0>(rx);
+                    const bf16x8 a0 = __builtin_bit_cast(bf16x8, fgnn_perm_col<0>(rx));
                     R[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bfr0, R[0], 0, 0, 0);
                     R[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bfr1, R[1], 0, 0, 0);
                 }
                 {
-                    const bs_bf16x8 a1 = bs_tr<1>(rx);
+                    const bf16x8 a1 = __builtin_bit_cast(bf16x8, fgnn_perm_col<1>(rx));
                     R[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bfr0, R[2], 0, 0, 0);
                     R[3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bfr1, R[3], 0, 0, 0);
                 }
                 {
-                    const bs_bf16x8 a2 = bs_tr<2>(rx);
+                    const bf16x8 a2 = __builtin_bit_cast(bf16x8, fgnn_perm_col<2>(rx));
                     R[4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, bfr0, R[4], 0, 0, 0);
                     R[5] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, bfr1, R[5], 0, 0, 0);
                 }
                 {
-                    const bs_bf16x8 a3 = bs_tr<3>(rx);
+                    const bf16x8 a3 = __builtin_bit_cast(bf16x8, fgnn_perm_col<3>(rx));
                     R[6] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, bfr0, R[6], 0, 0, 0);
                     R[7] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, bfr1, R[7], 0, 0, 0);
                 }

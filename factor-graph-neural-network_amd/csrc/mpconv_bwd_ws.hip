@@ -32,6 +32,7 @@
 //   3  waves 0-1 dx, waves 2,3,6,7 dW (48 MFMAs per SIMD), waves 4-5 build G / etT of sample s+1 from registers prefetched in
 //      phase 1 and wait for its x (LDS-DMA)
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "mpconv_dispatch.h"
 #include <stdlib.h>
 
@@ -43,8 +44,6 @@
 #define BW_PROW 512           // P image row: [4 edge types][64 channels] bf16, chunks swizzled per (node, edge type)
 #define BW_DROW 528           // dP image row: [64 channels][4 edge types] bf16 + 16 (conflict-free b128 operand reads)
 
-typedef __bf16 bw_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bw_s16x4 __attribute__((ext_vector_type(4)));
 typedef float bw_f32x16 __attribute__((ext_vector_type(16)));
 
 struct BwParams {
@@ -79,53 +78,12 @@ struct BwParams {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char bw_lds[];
 
-__device__ __forceinline__ unsigned bw_pack2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
 __device__ __forceinline__ unsigned bw_add2(unsigned a, unsigned b) {      // two bf16 sums, f32 arithmetic, rounded once
-    return bw_pack2(__uint_as_float(a << 16) + __uint_as_float(b << 16), __uint_as_float(a & 0xffff0000u) + __uint_as_float(b & 0xffff0000u));
+    return fgnn_pack2(__uint_as_float(a << 16) + __uint_as_float(b << 16), __uint_as_float(a & 0xffff0000u) + __uint_as_float(b & 0xffff0000u));
 }
-__device__ __forceinline__ bw_bf16x8 bw_frag_f32(const float* p8) {      // 8 consecutive f32 -> one fragment
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p8), b = *reinterpret_cast<const f32x4*>(p8 + 4);
-    return __builtin_bit_cast(bw_bf16x8, make_uint4(bw_pack2(a[0], a[1]), bw_pack2(a[2], a[3]),
-                                                    bw_pack2(b[0], b[1]), bw_pack2(b[2], b[3])));
-}
-// LDS-DMA piece (64 lanes x 16 B -> lds_dst + 16 lane) and the waits the compiler cannot place (see mpconv_fwd_ws.hip)
-__device__ __forceinline__ void bw_dma16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-// the same with a UNIFORM 64-bit base (scalar registers) + an unsigned 32-bit per-lane byte offset.  Round 6: dma_x's three per-lane
-// sources were carried across the sample loop as 64-bit register pairs, one pair was spilled in the V -> F instance, and its reload —
-// a memory operation — waited (vmcnt(0)) behind the two pieces just requested: an HBM round trip on the dW waves at the tail of every
-// sample's phase 3, the phase's long pole.
-__device__ __forceinline__ void bw_dma16s(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void bw_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // phase barrier: this wave's LDS operations done, then s_barrier — NOT __syncthreads(), which would also drain the gx /
 // getype stores and the next sample's prefetch loads four times per sample
 __device__ __forceinline__ void bw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// ds_read_b64_tr_b16: the 16 lanes of a group each name 4 consecutive bf16 of a [4 keys][16 columns] block (lane i: key i >> 2,
-// columns 4 (i & 3) ..), lane c of the group receives column c of the four keys (tools/ubench/lds_dma_tr.hip)
-__device__ __forceinline__ uint2 bw_tr(unsigned lds_addr) {
-    typedef __attribute__((address_space(3))) bw_s16x4 lds_v4;
-    const bw_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_v4*>(static_cast<uintptr_t>(lds_addr)));
-    return __builtin_bit_cast(uint2, v);
-}
-// uniform 64-bit base + UNSIGNED 32-bit per-lane byte offset: the form that compiles to `global_load v, v_off, s[base]` (anything
-// else becomes a per-lane 64-bit pointer, hoisted out of the sample loop and spilled)
-template <typename T> __device__ __forceinline__ const T* bw_at(const void* base, unsigned byte_off) {
-    return reinterpret_cast<const T*>(static_cast<const char*>(base) + byte_off);
-}
-template <typename T> __device__ __forceinline__ T* bw_at(void* base, unsigned byte_off) {
-    return reinterpret_cast<T*>(static_cast<char*>(base) + byte_off);
-}
 // Chunk swizzles of the 128-byte-row images (x, G) and of the dP image.  Each image is read two ways: 16-byte operand reads
 // (ds_read_b128: the 16 lanes of a service group {0-3,12-15,20-27} / ... must land in 16 different 16-byte slots of a 256-byte
 // window) and TRANSPOSE reads (ds_read_b64_tr_b16: a 32-lane pass fetches 4 consecutive rows x two adjacent 32-byte segments =
@@ -277,7 +235,7 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
             const int piece = dwq + 4 * u;
-            if (piece < npieces) bw_dma16s(xb, dsrc[u], lds0 + (unsigned)(OFF_X + buf * (BW_MAXN * BW_XROW) + piece * 1024));
+            if (piece < npieces) fgnn_dma16s(xb, dsrc[u], lds0 + (unsigned)(OFF_X + buf * (BW_MAXN * BW_XROW) + piece * 1024));
         }
     };
     // the first two samples' x: requested before anything else (the tables below take ~5 us)
@@ -294,8 +252,8 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             const int i = tid + BW_THREADS * it, row = i >> 5, c8 = i & 31;
-            const bw_bf16x8 f = bw_frag_f32(p.W + (int64_t)row * p.w_ld + 8 * c8);
-            *reinterpret_cast<bw_bf16x8*>(wst + row * WROW + c8 * 16) = f;
+            const bf16x8 f = fgnn_frag8(p.W + (int64_t)row * p.w_ld + 8 * c8);
+            *reinterpret_cast<bf16x8*>(wst + row * WROW + c8 * 16) = f;
         }
     }
     // the neighbour table (M k <= 288 entries: one per thread): requested now, consumed by the table pass below
@@ -305,7 +263,7 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
     // projection (all eight waves): column tile T = wave = (16-channel block ob, edge-type pair ep); A row i = 8 g + 4 h + r is
     // (edge type 2 ep + (g >> 1), channel 16 ob + 8 h + 4 (g & 1) + r): an output lane (node, h) then holds, per edge type of the
     // pair, EIGHT consecutive channels = one 16-byte chunk of the node's edge-type-major P row
-    bw_bf16x8 aP[4];
+    bf16x8 aP[4];
     unsigned xoff[4], pwo[2];
     {
         const int ob = (wave & 7) >> 1, ep = wave & 1;
@@ -316,7 +274,7 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
             unsigned w8[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) w8[u] = *reinterpret_cast<const uint16_t*>(bw_lds + OFF_G + (16 * kk + 8 * lh + u) * WROW + col * 2);
-            aP[kk] = __builtin_bit_cast(bw_bf16x8, make_uint4(w8[0] | (w8[1] << 16), w8[2] | (w8[3] << 16), w8[4] | (w8[5] << 16), w8[6] | (w8[7] << 16)));
+            aP[kk] = __builtin_bit_cast(bf16x8, make_uint4(w8[0] | (w8[1] << 16), w8[2] | (w8[3] << 16), w8[4] | (w8[5] << 16), w8[6] | (w8[7] << 16)));
             xoff[kk] = (unsigned)(l31 * BW_XROW + (((2 * kk + lh) ^ bw_swz_r(l31)) << 4));
         }
 #pragma unroll
@@ -354,8 +312,8 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
             pa[sl] = make_uint2(0, 0);
             if (build_wave && item < 8 * M) {
                 const unsigned el = (unsigned)((item >> 3) * p.y_ld + 8 * (item & 7));
-                pg[sl] = *bw_at<uint4>(gzb, el * 2u);
-                pa[sl] = *bw_at<uint2>(amb, el);
+                pg[sl] = *fgnn_at<uint4>(gzb, el * 2u);
+                pa[sl] = *fgnn_at<uint2>(amb, el);
             }
         }
     };
@@ -448,10 +406,10 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
         }
         db[r] = lds0 + (unsigned)(OFF_PD + nd * BW_DROW + (64 * dwi + 16 * (g4 & 1) + 4 * (i16 & 3)) * 2);
     }
-    bw_s16x4 ones_row0;
+    s16x4 ones_row0;
     {
         const short o = (lane & 3) == 0 ? (short)0x3f80 : (short)0;
-        ones_row0 = (bw_s16x4){o, o, o, o};
+        ones_row0 = (s16x4){o, o, o, o};
     }
     f32x4 dbacc = {0.f, 0.f, 0.f, 0.f};                // [0]: dbias of channel `lane` over this wave's nodes
 
@@ -460,7 +418,7 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
 #pragma unroll
         for (int sl = 0; sl < ESLOT; ++sl) {
             pe[sl] = make_uint2(0, 0);
-            if (et_src[sl] >= 0) pe[sl] = *bw_at<uint2>(p.et + (int64_t)b * p.et_sb, (unsigned)et_src[sl] * 8u);
+            if (et_src[sl] >= 0) pe[sl] = *fgnn_at<uint2>(p.et + (int64_t)b * p.et_sb, (unsigned)et_src[sl] * 8u);
         }
     };
     auto build = [&](const uint4 (&pg)[NSLOT], const uint2 (&pa)[NSLOT], const uint2 (&pe)[ESLOT]) {      // prefetched registers -> etT, G
@@ -512,7 +470,7 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
             uint2 pe[ESLOT];
             prefetch_e(b_begin, pe); build(pg0, pa0, pe);
         }
-        if (dma_wave) bw_wait_vm0();
+        if (dma_wave) fgnn_wait_vm<0>();
     }
     bw_barrier();
     constexpr int ntile = NMAX / 32;
@@ -543,16 +501,16 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
             for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
                 for (int t = 0; t < 3; ++t)
-                    if (t < ntile) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aP[kk], __builtin_bit_cast(bw_bf16x8, xb[t][kk]), acc[t], 0, 0, 0);
+                    if (t < ntile) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(aP[kk], __builtin_bit_cast(bf16x8, xb[t][kk]), acc[t], 0, 0, 0);
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
                 if (t < ntile) {
                     unsigned char* pp0 = bw_lds + t * 32 * BW_PROW + pwo[0];
                     unsigned char* pp1 = bw_lds + t * 32 * BW_PROW + pwo[1];
-                    *reinterpret_cast<uint4*>(pp0) = make_uint4(bw_pack2(acc[t][0], acc[t][1]), bw_pack2(acc[t][2], acc[t][3]),
-                                                                bw_pack2(acc[t][4], acc[t][5]), bw_pack2(acc[t][6], acc[t][7]));
-                    *reinterpret_cast<uint4*>(pp1) = make_uint4(bw_pack2(acc[t][8], acc[t][9]), bw_pack2(acc[t][10], acc[t][11]),
-                                                                bw_pack2(acc[t][12], acc[t][13]), bw_pack2(acc[t][14], acc[t][15]));
+                    *reinterpret_cast<uint4*>(pp0) = make_uint4(fgnn_pack2(acc[t][0], acc[t][1]), fgnn_pack2(acc[t][2], acc[t][3]),
+                                                                fgnn_pack2(acc[t][4], acc[t][5]), fgnn_pack2(acc[t][6], acc[t][7]));
+                    *reinterpret_cast<uint4*>(pp1) = make_uint4(fgnn_pack2(acc[t][8], acc[t][9]), fgnn_pack2(acc[t][10], acc[t][11]),
+                                                                fgnn_pack2(acc[t][12], acc[t][13]), fgnn_pack2(acc[t][14], acc[t][15]));
                 }
             }
         }
@@ -579,11 +537,11 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
                 f32x4 acc[NG];
     #pragma unroll
                 for (int sl = 0; sl < NG; ++sl)
-                    acc[sl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bw_bf16x8, fa[sl][0]), __builtin_bit_cast(bw_bf16x8, fb[sl][0]),
+                    acc[sl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[sl][0]), __builtin_bit_cast(bf16x8, fb[sl][0]),
                                                                       (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
     #pragma unroll
                 for (int sl = 0; sl < NG; ++sl)
-                    acc[sl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bw_bf16x8, fa[sl][1]), __builtin_bit_cast(bw_bf16x8, fb[sl][1]),
+                    acc[sl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[sl][1]), __builtin_bit_cast(bf16x8, fb[sl][1]),
                                                                       acc[sl], 0, 0, 0);
                 const int e = i16 & 3;
     #pragma unroll
@@ -591,7 +549,7 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
                     const int ed[4] = {te[sl].x, te[sl].y, te[sl].z, te[sl].w};
     #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (ed[r] >= 0) gst[e * mk + ed[r]] = (uint16_t)(bw_pack2(acc[sl][r], 0.f) & 0xffffu);
+                        if (ed[r] >= 0) gst[e * mk + ed[r]] = (uint16_t)(fgnn_pack2(acc[sl][r], 0.f) & 0xffffu);
                 }
             }
         };
@@ -604,7 +562,7 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
     #pragma unroll
                     for (int h4 = 0; h4 < QS / 4; ++h4) {
                         // (nodes >= N: their G rows and edge-type rows are zero for the kernel's lifetime -> a zero dP row, what dW needs)
-                        bv[i][h4] = bw_tr(gpat[i & 3][h4] + (unsigned)(n * QS * BW_GROW));
+                        bv[i][h4] = fgnn_tr16(gpat[i & 3][h4] + (unsigned)(n * QS * BW_GROW));
                         av[i][h4] = *reinterpret_cast<const uint2*>(bw_lds + OFF_ET + ((n * 4 + (lane & 3)) * QS + 4 * h4) * 2);
                     }
                 }
@@ -617,11 +575,11 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
                         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     #pragma unroll
                         for (int h4 = 0; h4 < QS / 4; ++h4) {
-                            const bw_s16x4 b4 = __builtin_bit_cast(bw_s16x4, bv[i][h4]);
-                            acc = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(bw_s16x4, av[i][h4]), b4, acc, 0, 0, 0);
+                            const s16x4 b4 = __builtin_bit_cast(s16x4, bv[i][h4]);
+                            acc = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(s16x4, av[i][h4]), b4, acc, 0, 0, 0);
                             dbacc = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(ones_row0, b4, dbacc, 0, 0, 0);
                         }
-                        *reinterpret_cast<uint2*>(bw_lds + OFF_PD + n * BW_DROW + lane * 8) = make_uint2(bw_pack2(acc[0], acc[1]), bw_pack2(acc[2], acc[3]));
+                        *reinterpret_cast<uint2*>(bw_lds + OFF_PD + n * BW_DROW + lane * 8) = make_uint2(fgnn_pack2(acc[0], acc[1]), fgnn_pack2(acc[2], acc[3]));
                     }
                 }
                 BW_STAMP(10);
@@ -630,10 +588,10 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
                 if (tid < nvec) {
                     uint4 v = *reinterpret_cast<const uint4*>(bw_lds + OFF_GST + tid * 16);
                     if (p.accum & 2) {                         // second launch of a split call: add to what the first one stored
-                        const uint4 o = *bw_at<uint4>(p.get + (int64_t)b * 4 * mk, (unsigned)tid * 16u);
+                        const uint4 o = *fgnn_at<uint4>(p.get + (int64_t)b * 4 * mk, (unsigned)tid * 16u);
                         v = make_uint4(bw_add2(v.x, o.x), bw_add2(v.y, o.y), bw_add2(v.z, o.z), bw_add2(v.w, o.w));
                     }
-                    *bw_at<uint4>(p.get + (int64_t)b * 4 * mk, (unsigned)tid * 16u) = v;
+                    *fgnn_at<uint4>(p.get + (int64_t)b * 4 * mk, (unsigned)tid * 16u) = v;
                 }
             }
         };
@@ -644,13 +602,13 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
                 auto load = [&](uint2 (&f)[8], int ks) {   // A: channel tiles 0 / 1 (two reads each); B: this wave's two column tiles
     #pragma unroll
                     for (int c2 = 0; c2 < 2; ++c2) {
-                        f[2 * c2] = bw_tr(xbase + xa[c2][0] + ks * (16 * BW_XROW));
-                        f[2 * c2 + 1] = bw_tr(xbase + xa[c2][1] + ks * (16 * BW_XROW));
+                        f[2 * c2] = fgnn_tr16(xbase + xa[c2][0] + ks * (16 * BW_XROW));
+                        f[2 * c2 + 1] = fgnn_tr16(xbase + xa[c2][1] + ks * (16 * BW_XROW));
                     }
     #pragma unroll
                     for (int cj = 0; cj < 2; ++cj) {
-                        f[4 + 2 * cj] = bw_tr(db[0] + ks * (16 * BW_DROW) + cj * 64);
-                        f[5 + 2 * cj] = bw_tr(db[1] + ks * (16 * BW_DROW) + cj * 64);
+                        f[4 + 2 * cj] = fgnn_tr16(db[0] + ks * (16 * BW_DROW) + cj * 64);
+                        f[5 + 2 * cj] = fgnn_tr16(db[1] + ks * (16 * BW_DROW) + cj * 64);
                     }
                 };
                 auto mma = [&](const uint2 (&f)[8]) {
@@ -659,8 +617,8 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
     #pragma unroll
                         for (int cj = 0; cj < 2; ++cj)
                             RA[2 * c2 + cj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                                __builtin_bit_cast(bw_bf16x8, make_uint4(f[2 * c2].x, f[2 * c2].y, f[2 * c2 + 1].x, f[2 * c2 + 1].y)),
-                                __builtin_bit_cast(bw_bf16x8, make_uint4(f[4 + 2 * cj].x, f[4 + 2 * cj].y, f[5 + 2 * cj].x, f[5 + 2 * cj].y)),
+                                __builtin_bit_cast(bf16x8, make_uint4(f[2 * c2].x, f[2 * c2].y, f[2 * c2 + 1].x, f[2 * c2 + 1].y)),
+                                __builtin_bit_cast(bf16x8, make_uint4(f[4 + 2 * cj].x, f[4 + 2 * cj].y, f[5 + 2 * cj].x, f[5 + 2 * cj].y)),
                                 RA[2 * c2 + cj], 0, 0, 0);
                 };
                 load(f0, 0);
@@ -732,8 +690,8 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
                         f32x4 f0, f1;
 #pragma unroll
                         for (int u = 0; u < 4; ++u) { f0[u] = RA[ks >> 2][4 * (ks & 3) + u]; f1[u] = RA[(ks + 1) >> 2][4 * ((ks + 1) & 3) + u]; }
-                        ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bw_bf16x8, f0), __builtin_bit_cast(bw_bf16x8, bf[ks]), ae, 0, 0, 0);
-                        ao = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bw_bf16x8, f1), __builtin_bit_cast(bw_bf16x8, bf[ks + 1]), ao, 0, 0, 0);
+                        ae = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f0), __builtin_bit_cast(bf16x8, bf[ks]), ae, 0, 0, 0);
+                        ao = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f1), __builtin_bit_cast(bf16x8, bf[ks + 1]), ao, 0, 0, 0);
                     }
                     const int n = nt * 32 + l31;
                     if (n < N) {
@@ -741,13 +699,13 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
                         for (int g = 0; g < 4; ++g) {
                             float v0 = ae[4 * g] + ao[4 * g], v1 = ae[4 * g + 1] + ao[4 * g + 1], v2 = ae[4 * g + 2] + ao[4 * g + 2],
                                   v3 = ae[4 * g + 3] + ao[4 * g + 3];
-                            uint2* dst = bw_at<uint2>(gxb, (unsigned)(n * XLD + 32 * wave + 8 * g + 4 * lh) * 2u);
+                            uint2* dst = fgnn_at<uint2>(gxb, (unsigned)(n * XLD + 32 * wave + 8 * g + 4 * lh) * 2u);
                             if (p.accum & 1) {
                                 const uint2 o = *dst;
                                 v0 += __uint_as_float(o.x << 16); v1 += __uint_as_float(o.x & 0xffff0000u);
                                 v2 += __uint_as_float(o.y << 16); v3 += __uint_as_float(o.y & 0xffff0000u);
                             }
-                            *dst = make_uint2(bw_pack2(v0, v1), bw_pack2(v2, v3));
+                            *dst = make_uint2(fgnn_pack2(v0, v1), fgnn_pack2(v2, v3));
                         }
                     }
                 }
@@ -757,7 +715,7 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
         // issued in front of phase 1 the twelve pieces held up the projections of the issuing waves by up to 1 000 cycles.  These
         // waves store nothing, so vmcnt(0) = "x of sample b + 1 (requested a sample ago) has landed".
         if (dma_wave) {
-            bw_wait_vm0();
+            fgnn_wait_vm<0>();
             if (b + 2 < b_end) dma_x(b + 2, cur >= 1 ? cur - 1 : 2);      // buffer (cur + 2) % 3: last read by dW of sample b - 1
         }
         BW_STAMP(7);

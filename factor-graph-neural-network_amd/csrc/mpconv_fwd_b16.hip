@@ -15,6 +15,7 @@
 //     per (edge, channel), lanes = channels, destinations walk across the 4 waves;
 //   * next sample's x / etype / nn_idx are prefetched into registers during the current sample.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "mpconv_dispatch.h"
 #include "fgnn_gridfold.h"
 #ifndef B16_XPAD
@@ -25,8 +26,6 @@
 #endif
 #include <stdlib.h>
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 #define B16_THREADS 512
 #define B16_WAVES 8
@@ -62,17 +61,6 @@ struct B16Params {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fgnn_lds_h[];
 
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-    // native fptrunc -> one v_cvt_pk_bf16_f32 (round-to-nearest-even).  NOT inline asm: an asm
-    // statement reading MFMA results directly gets none of the compiler's MFMA->VALU wait states
-    // (observed: one node tile of stale P values once the accumulators stopped living in AGPRs).
-    bf16x2_t r;
-    r[0] = (__bf16)a;
-    r[1] = (__bf16)b;
-    return __builtin_bit_cast(unsigned, r);
-}
 
 // message value of one (edge, channel): sum_e etype[e] * P[n][o*net+e], P in bf16
 template <int NET>
@@ -83,10 +71,10 @@ __device__ __forceinline__ float b16_dot(const float* __restrict__ etp, const un
     } else {
         const uint2 pk = *reinterpret_cast<const uint2*>(prow);
         const f32x4 e4 = *reinterpret_cast<const f32x4*>(etp);
-        float v = e4[0] * bf16_lo(pk.x);
-        v = fmaf(e4[1], bf16_hi(pk.x), v);
-        v = fmaf(e4[2], bf16_lo(pk.y), v);
-        v = fmaf(e4[3], bf16_hi(pk.y), v);
+        float v = e4[0] * fgnn_lo(pk.x);
+        v = fmaf(e4[1], fgnn_hi(pk.x), v);
+        v = fmaf(e4[2], fgnn_lo(pk.y), v);
+        v = fmaf(e4[3], fgnn_hi(pk.y), v);
         return v;
     }
 }
@@ -126,7 +114,7 @@ __global__ __launch_bounds__(B16_THREADS) void mpconv_fwd_b16_kernel(const B16Pa
 
     // ---- filters -> bf16 A fragments: areg[pass][q][kk] = W[c = 32kk + 8lk + 0..7][col] ----
     const int slabs_per_pass = p.pass_cols / 16;
-    bf16x8_t areg[NPASS][SWP][KSB];
+    bf16x8 areg[NPASS][SWP][KSB];
 #pragma unroll
     for (int ps_i = 0; ps_i < NPASS; ++ps_i)
 #pragma unroll
@@ -142,9 +130,9 @@ __global__ __launch_bounds__(B16_THREADS) void mpconv_fwd_b16_kernel(const B16Pa
                     const int c = 32 * kk + 8 * lk + 2 * h;
                     const float f0 = (ok && c < nin) ? p.W[(int64_t)c * ncols + col] : 0.f;
                     const float f1 = (ok && c + 1 < nin) ? p.W[(int64_t)(c + 1) * ncols + col] : 0.f;
-                    w[h] = pack_bf16(f0, f1);
+                    w[h] = fgnn_pack2(f0, f1);
                 }
-                areg[ps_i][q][kk] = __builtin_bit_cast(bf16x8_t, make_uint4(w[0], w[1], w[2], w[3]));
+                areg[ps_i][q][kk] = __builtin_bit_cast(bf16x8, make_uint4(w[0], w[1], w[2], w[3]));
             }
         }
 
@@ -244,7 +232,7 @@ __global__ __launch_bounds__(B16_THREADS) void mpconv_fwd_b16_kernel(const B16Pa
                 const unsigned char* bp = xs + (tile * 16 + li) * XSB + lk * 16;
 #pragma unroll
                 for (int kk = 0; kk < KSB; ++kk) {
-                    const bf16x8_t bfrag = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(bp + kk * 64));
+                    const bf16x8 bfrag = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp + kk * 64));
 #pragma unroll
                     for (int q = 0; q < SWP; ++q)
                         acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(areg[pass][q][kk], bfrag, acc[q], 0, 0, 0);
@@ -254,8 +242,8 @@ __global__ __launch_bounds__(B16_THREADS) void mpconv_fwd_b16_kernel(const B16Pa
                     const int slab = wave + B16_WAVES * q;
                     if (slab < slabs_per_pass) {
                         uint2 pk;
-                        pk.x = pack_bf16(acc[q][0], acc[q][1]);
-                        pk.y = pack_bf16(acc[q][2], acc[q][3]);
+                        pk.x = fgnn_pack2(acc[q][0], acc[q][1]);
+                        pk.y = fgnn_pack2(acc[q][2], acc[q][3]);
                         *reinterpret_cast<uint2*>(ps + (tile * 16 + li) * PSB + (slab * 16 + 4 * lk) * 2) = pk;
                     }
                 }
@@ -292,9 +280,9 @@ __global__ __launch_bounds__(B16_THREADS) void mpconv_fwd_b16_kernel(const B16Pa
                     res = (res + c_bias) * c_scale + c_shift;
                     if (d.relu) res = fmaxf(res, 0.f);
                     const int off = (o0 + ch) * (int)d.y_sc + m * (int)d.y_sm;
-                    const unsigned packed = pack_bf16(res, 0.f);
+                    const unsigned packed = fgnn_pack2(res, 0.f);
                     if (!(p.dbg & 8) || res == 1.2345e-30f) yb[off] = (unsigned short)packed;
-                    if (p.stats) { const float zr = bf16_lo(packed); st0 += zr; st1 = fmaf(zr, zr, st1); }     // of the value as stored
+                    if (p.stats) { const float zr = fgnn_lo(packed); st0 += zr; st1 = fmaf(zr, zr, st1); }     // of the value as stored
                     if (AGG == FGNN_AGG_MAX && ab) ab[off] = (uint8_t)arg;
                 };
                 bool paired = false;
@@ -327,10 +315,10 @@ __global__ __launch_bounds__(B16_THREADS) void mpconv_fwd_b16_kernel(const B16Pa
                                 int arg = 0;
 #pragma unroll
                                 for (int j = 0; j < KC; ++j) {
-                                    float v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, pk[u][j].x),
-                                        __builtin_bit_cast(bf16x2_t, (unsigned)__builtin_amdgcn_readlane(ew[u], 2 * j)), 0.f, false);
-                                    v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, pk[u][j].y),
-                                        __builtin_bit_cast(bf16x2_t, (unsigned)__builtin_amdgcn_readlane(ew[u], 2 * j + 1)), v, false);
+                                    float v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk[u][j].x),
+                                        __builtin_bit_cast(bf16x2, (unsigned)__builtin_amdgcn_readlane(ew[u], 2 * j)), 0.f, false);
+                                    v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk[u][j].y),
+                                        __builtin_bit_cast(bf16x2, (unsigned)__builtin_amdgcn_readlane(ew[u], 2 * j + 1)), v, false);
                                     if (j == 0 || v > best) { best = v; arg = j; }      // strict >: first occurrence
                                 }
                                 if (active && m0 + u * B16_WAVES < M) finish(m0 + u * B16_WAVES, 0, lane, best, 0.f, arg);
@@ -364,10 +352,10 @@ __global__ __launch_bounds__(B16_THREADS) void mpconv_fwd_b16_kernel(const B16Pa
                             if constexpr (NET == 4) {
                                 const unsigned e01 = __builtin_amdgcn_readlane(etv, 2 * j);
                                 const unsigned e23 = __builtin_amdgcn_readlane(etv, 2 * j + 1);
-                                v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, pk.x),
-                                                                    __builtin_bit_cast(bf16x2_t, e01), 0.f, false);
-                                v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, pk.y),
-                                                                    __builtin_bit_cast(bf16x2_t, e23), v, false);
+                                v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk.x),
+                                                                    __builtin_bit_cast(bf16x2, e01), 0.f, false);
+                                v = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pk.y),
+                                                                    __builtin_bit_cast(bf16x2, e23), v, false);
                             } else {
                                 const float e = __uint_as_float(__builtin_amdgcn_readlane(etv, j));
                                 v = e * __uint_as_float(pk.x << 16);

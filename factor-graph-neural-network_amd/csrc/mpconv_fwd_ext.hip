@@ -18,6 +18,7 @@
 //   * gather: thread = (destination, channel of the pass); per neighbour 8 LDS reads of 16 B and 16 packed FMAs.
 // One 512-thread workgroup per CU (P 65 KB + edge types <= 40 KB + x 17 KB of LDS), up to 256 VGPRs per lane.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "mpconv_dispatch.h"
 #include <stdlib.h>
 
@@ -236,20 +237,14 @@ __device__ __forceinline__ float fx_fma(float a, float b, float c) { float r; as
 // of |x w|, the size of one f32 rounding.  On the bf16 matrix cores six MFMAs cost 6 / 16 of one f32 MFMA, and — unlike the
 // f32 MFMA — they leave the SIMD's VALU to the gather running beside them (tools/ubench/mfma_f32_partner.hip).
 #define FQ_XS 72             // split x image row stride in bf16 elements (64 + 8: rows 144 bytes apart, conflict-free 16-byte reads)
-typedef __bf16 fq_bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned fq_pack2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
 // (a, b) -> packed bf16 pairs of the three terms
 __device__ __forceinline__ float fx_sub(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ void fq_split2(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
     // single (not packed) subtractions: v_pk_add_f32 does not issue beside the producers' bf16 MFMA stream
-    h = fq_pack2(a, b);
+    h = fgnn_pack2(a, b);
     const float ra = fx_sub(a, __uint_as_float(h << 16)), rb = fx_sub(b, __uint_as_float(h & 0xffff0000u));
-    m = fq_pack2(ra, rb);
-    l = fq_pack2(fx_sub(ra, __uint_as_float(m << 16)), fx_sub(rb, __uint_as_float(m & 0xffff0000u)));
+    m = fgnn_pack2(ra, rb);
+    l = fgnn_pack2(fx_sub(ra, __uint_as_float(m << 16)), fx_sub(rb, __uint_as_float(m & 0xffff0000u)));
 }
 
 template <int AGG, bool SPLIT>
@@ -399,7 +394,7 @@ __global__ __launch_bounds__(FX_THREADS, 2) void mpconv_fwd_extp_kernel(const Fx
       } else {
         // ---- SPLIT: three-term bf16 operands on v_mfma_f32_16x16x32_bf16.  k-step ks, k-group lk <-> channels 32 ks + 8 lk .. + 7 ----
         float rT[16], rB[16];                                              // raw filter rows of the next pass (c = 32 (kk >> 3) + 8 lk + (kk & 7))
-        fq_bf16x8 wS[3][2], wT[3][2];                                      // [term][k-step] B operands of this wave's S and T slab
+        bf16x8 wS[3][2], wT[3][2];                                      // [term][k-step] B operands of this wave's S and T slab
         auto load_w = [&](int pass) {
             const int col = 16 * (FP_PCH * pass + wave) + li;
 #pragma unroll
@@ -421,12 +416,12 @@ __global__ __launch_bounds__(FX_THREADS, 2) void mpconv_fwd_extp_kernel(const Fx
                     fq_split2(s0, s1, hs[q], ms[q], ls[q]);
                     fq_split2(t0, t1, ht[q], mt[q], lt[q]);
                 }
-                wS[0][ks] = __builtin_bit_cast(fq_bf16x8, make_uint4(hs[0], hs[1], hs[2], hs[3]));
-                wS[1][ks] = __builtin_bit_cast(fq_bf16x8, make_uint4(ms[0], ms[1], ms[2], ms[3]));
-                wS[2][ks] = __builtin_bit_cast(fq_bf16x8, make_uint4(ls[0], ls[1], ls[2], ls[3]));
-                wT[0][ks] = __builtin_bit_cast(fq_bf16x8, make_uint4(ht[0], ht[1], ht[2], ht[3]));
-                wT[1][ks] = __builtin_bit_cast(fq_bf16x8, make_uint4(mt[0], mt[1], mt[2], mt[3]));
-                wT[2][ks] = __builtin_bit_cast(fq_bf16x8, make_uint4(lt[0], lt[1], lt[2], lt[3]));
+                wS[0][ks] = __builtin_bit_cast(bf16x8, make_uint4(hs[0], hs[1], hs[2], hs[3]));
+                wS[1][ks] = __builtin_bit_cast(bf16x8, make_uint4(ms[0], ms[1], ms[2], ms[3]));
+                wS[2][ks] = __builtin_bit_cast(bf16x8, make_uint4(ls[0], ls[1], ls[2], ls[3]));
+                wT[0][ks] = __builtin_bit_cast(bf16x8, make_uint4(ht[0], ht[1], ht[2], ht[3]));
+                wT[1][ks] = __builtin_bit_cast(bf16x8, make_uint4(mt[0], mt[1], mt[2], mt[3]));
+                wT[2][ks] = __builtin_bit_cast(bf16x8, make_uint4(lt[0], lt[1], lt[2], lt[3]));
             }
         };
         int si = 0, pi = 0;
@@ -441,12 +436,12 @@ __global__ __launch_bounds__(FX_THREADS, 2) void mpconv_fwd_extp_kernel(const Fx
                 const uint16_t* xi = xq + (t & 1) * XQ_BUF;
                 float* pb = ps + (t & 1) * 64 * FP_PROW;
                 for (int nt = 0; nt < ((p.dbg & 1) ? 0 : ntile); ++nt) {
-                    fq_bf16x8 xa[3][2];                                    // [term][k-step] A operand: 8 consecutive channels of node row li
+                    bf16x8 xa[3][2];                                    // [term][k-step] A operand: 8 consecutive channels of node row li
 #pragma unroll
                     for (int tm = 0; tm < 3; ++tm)
 #pragma unroll
                         for (int ks = 0; ks < 2; ++ks)
-                            xa[tm][ks] = __builtin_bit_cast(fq_bf16x8, *reinterpret_cast<const uint4*>(xi + tm * XQ_TERM + (nt * 16 + li) * FQ_XS + 32 * ks + 8 * lk));
+                            xa[tm][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(xi + tm * XQ_TERM + (nt * 16 + li) * FQ_XS + 32 * ks + 8 * lk));
                     // four independent accumulator chains (S / T x the two k-steps), smallest terms first in each:
                     // l h' + h l' + m m', then m h' + h m', then h h'
                     f32x4 aS[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, aT[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};

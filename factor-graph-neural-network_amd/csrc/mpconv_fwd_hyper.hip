@@ -15,10 +15,10 @@
 // fan-out: P is 64..128 numbers per sample (lane <-> 4..8 channels, W from LDS), the output rows are streamed
 // with 8..16-byte stores.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "mpconv_dispatch.h"
 #include <stdlib.h>
 
-typedef __bf16 fh_bf16x8 __attribute__((ext_vector_type(8)));
 
 struct FhParams {
     fgnn_mpconv_desc d;
@@ -37,13 +37,6 @@ struct FhParams {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fgnn_lds_fh[];
 
-__device__ __forceinline__ float fh_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float fh_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ unsigned fh_pack2(float a, float b) {
-    typedef __bf16 v2 __attribute__((ext_vector_type(2)));
-    const v2 h = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, h);
-}
 __device__ __forceinline__ uint16_t fh_bf16(float a) {
     const __bf16 h = (__bf16)a;
     return __builtin_bit_cast(uint16_t, h);
@@ -63,7 +56,7 @@ __global__ __launch_bounds__(512) void mpconv_fwd_fanin_kernel(const FhParams p)
     uint16_t* Pl = reinterpret_cast<uint16_t*>(fgnn_lds_fh) + (size_t)wave * p.Npad16 * NOU;   // [Npad16][NOU] bf16
 
     // resident A fragments of P^T = W^T x: A[i = o][k = c] = W[c][o], 8 consecutive c (strided read, once)
-    fh_bf16x8 aP[OT][KS2];
+    bf16x8 aP[OT][KS2];
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot)
 #pragma unroll
@@ -71,8 +64,8 @@ __global__ __launch_bounds__(512) void mpconv_fwd_fanin_kernel(const FhParams p)
             float w8[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) w8[u] = p.W[(int64_t)(32 * ks + 8 * lk + u) * NOU + ot * 16 + li];
-            aP[ot][ks] = __builtin_bit_cast(fh_bf16x8, make_uint4(fh_pack2(w8[0], w8[1]), fh_pack2(w8[2], w8[3]),
-                                                                  fh_pack2(w8[4], w8[5]), fh_pack2(w8[6], w8[7])));
+            aP[ot][ks] = __builtin_bit_cast(bf16x8, make_uint4(fgnn_pack2(w8[0], w8[1]), fgnn_pack2(w8[2], w8[3]),
+                                                                  fgnn_pack2(w8[4], w8[5]), fgnn_pack2(w8[6], w8[7])));
         }
     float c_bias[NO], c_scale[NO], c_shift[NO];
 #pragma unroll
@@ -110,10 +103,10 @@ __global__ __launch_bounds__(512) void mpconv_fwd_fanin_kernel(const FhParams p)
                         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                         for (int ks = 0; ks < KS2; ++ks)
-                            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aP[ot][ks], __builtin_bit_cast(fh_bf16x8, bx[t][ks]), acc, 0, 0, 0);
+                            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aP[ot][ks], __builtin_bit_cast(bf16x8, bx[t][ks]), acc, 0, 0, 0);
                         // D[i = o 4lk+r][j = n]: four consecutive channels of node n
                         *reinterpret_cast<uint2*>(Pl + n * NOU + ot * 16 + 4 * lk) =
-                            make_uint2(fh_pack2(acc[0], acc[1]), fh_pack2(acc[2], acc[3]));
+                            make_uint2(fgnn_pack2(acc[0], acc[1]), fgnn_pack2(acc[2], acc[3]));
                     }
                 }
             }
@@ -213,7 +206,7 @@ __global__ __launch_bounds__(256) void mpconv_fwd_fanin_id_kernel(const FhParams
     const int nwaves = gridDim.x * 4;
     int b = blockIdx.x * 4 + wave;
     // the first sample's rows go out before the W fragments are fetched (64 strided 4-byte loads per lane: the kernel's fixed cost)
-    fh_bf16x8 aP[OT][KS2];
+    bf16x8 aP[OT][KS2];
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot)
 #pragma unroll
@@ -221,8 +214,8 @@ __global__ __launch_bounds__(256) void mpconv_fwd_fanin_id_kernel(const FhParams
             float w8[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) w8[u] = p.W[(int64_t)(32 * ks + 8 * lk + u) * NOU + ot * 16 + li];
-            aP[ot][ks] = __builtin_bit_cast(fh_bf16x8, make_uint4(fh_pack2(w8[0], w8[1]), fh_pack2(w8[2], w8[3]),
-                                                                  fh_pack2(w8[4], w8[5]), fh_pack2(w8[6], w8[7])));
+            aP[ot][ks] = __builtin_bit_cast(bf16x8, make_uint4(fgnn_pack2(w8[0], w8[1]), fgnn_pack2(w8[2], w8[3]),
+                                                                  fgnn_pack2(w8[4], w8[5]), fgnn_pack2(w8[6], w8[7])));
         }
     float c_bias[NO], c_scale[NO], c_shift[NO];
 #pragma unroll
@@ -263,7 +256,7 @@ __global__ __launch_bounds__(256) void mpconv_fwd_fanin_id_kernel(const FhParams
                         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                         for (int ks = 0; ks < KS2; ++ks)
-                            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aP[ot][ks], __builtin_bit_cast(fh_bf16x8, bx[t][ks]), acc, 0, 0, 0);
+                            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aP[ot][ks], __builtin_bit_cast(bf16x8, bx[t][ks]), acc, 0, 0, 0);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {                // acc[r] = P[node n][channel 16 ot + 4 lk + r]
                             const float v = ew[t] * acc[r];
@@ -371,7 +364,7 @@ __global__ __launch_bounds__(512) void mpconv_fwd_fanout_kernel(const FhParams p
             uint16_t* dst = yb + (int64_t)m * d.y_sm;
 #pragma unroll
             for (int t = 0; t < CH; t += 4)
-                *reinterpret_cast<uint2*>(dst + t) = make_uint2(fh_pack2(r[t], r[t + 1]), fh_pack2(r[t + 2], r[t + 3]));
+                *reinterpret_cast<uint2*>(dst + t) = make_uint2(fgnn_pack2(r[t], r[t + 1]), fgnn_pack2(r[t + 2], r[t + 3]));
             if (ab) {
 #pragma unroll
                 for (int t = 0; t < CH; t += 4) *reinterpret_cast<unsigned*>(ab + (int64_t)m * d.y_sm + t) = 0u;

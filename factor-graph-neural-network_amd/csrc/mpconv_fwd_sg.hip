@@ -26,25 +26,15 @@
 // [w*DPW, (w+1)*DPW).  Per sample: x (prefetched into registers one sample ahead) -> LDS image; MFMA projection ->
 // P[N][64 ch][4 et] bf16 in LDS; barrier; gather with lane = channel; barrier.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "mpconv_dispatch.h"
 #include "fgnn_gridfold.h"
 #include <stdlib.h>
 
-typedef __bf16 sg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 sg_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float sg_f32x16 __attribute__((ext_vector_type(16)));
 
 #define SG_THREADS 512
 #define SG_WAVES 8
-#ifndef SG_OPT_ASMDOT
-#define SG_OPT_ASMDOT 0       // 1: seed each message with the three-address v_dot2_f32_bf16 through inline asm (measured SLOWER: 52 vs 41 us)
-#endif
-#ifndef SG_OPT_MAX3
-#define SG_OPT_MAX3 1         // v_max3 + first-occurrence scan instead of a compare/select chain
-#endif
-#ifndef SG_OPT_EARLYCOMMIT
-#define SG_OPT_EARLYCOMMIT 1  // stage the next sample right after the projection barrier
-#endif
 #define SG_ESLOT 304          // bytes of LDS per wave for its edge-type block (<= 288 used)
 #define SG_PSB 520            // P row stride in bytes: 64 channels x 8 B + 8 (130 dwords = 2 banks mod 32)
 
@@ -80,27 +70,6 @@ extern __shared__ __attribute__((aligned(16))) unsigned char sg_lds[];
 #define SG_STAMP(slot) do { } while (0)
 #endif
 
-__device__ __forceinline__ unsigned sg_pack(float a, float b) {
-    sg_bf16x2 r;
-    r[0] = (__bf16)a;
-    r[1] = (__bf16)b;
-    return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ float sg_dot2(unsigned p, unsigned e, float acc) {
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(sg_bf16x2, p), __builtin_bit_cast(sg_bf16x2, e), acc, false);
-}
-// D = a.lo*b.lo + a.hi*b.hi + c as the three-address VOP3P form: the builtin always selects the two-address v_dot2c
-// (accumulator tied to the destination) and pays a v_mov per message to seed it.  Operands are LDS / register values
-// the compiler tracks; the instruction has no software-visible hazards of its own.
-__device__ __forceinline__ float sg_dot2_seed(unsigned p, unsigned e, float c) {
-#if SG_OPT_ASMDOT
-    float r;
-    asm("v_dot2_f32_bf16 %0, %1, %2, %3" : "=v"(r) : "v"(p), "v"(e), "v"(c));
-    return r;
-#else
-    return sg_dot2(p, e, c);
-#endif
-}
 
 // edge-type weights of one destination: KC x 4 bf16 = KC*8 bytes from this wave's LDS slot, every lane the same address
 template <int KC>
@@ -142,7 +111,7 @@ __global__ __launch_bounds__(SG_THREADS, 4) void mpconv_fwd_sg_kernel(const SgPa
     unsigned char* ps = sg_lds + Npad * XSB;                      // [Npad][SG_PSB]
 
     // ---- W^T A-fragments: areg[pass][kk] = W[c = 16kk + 8lh + 0..7][col = 256 pass + 32 wave + l31] ----
-    sg_bf16x8 areg[NPASS][KS];
+    bf16x8 areg[NPASS][KS];
     {
         const int ncols = p.w_ld;
 #pragma unroll
@@ -154,9 +123,9 @@ __global__ __launch_bounds__(SG_THREADS, 4) void mpconv_fwd_sg_kernel(const SgPa
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
                     const int c = 16 * kk + 8 * lh + 2 * h;
-                    w[h] = sg_pack(wc[(size_t)c * ncols], wc[(size_t)(c + 1) * ncols]);
+                    w[h] = fgnn_pack2(wc[(size_t)c * ncols], wc[(size_t)(c + 1) * ncols]);
                 }
-                areg[ps_i][kk] = __builtin_bit_cast(sg_bf16x8, make_uint4(w[0], w[1], w[2], w[3]));
+                areg[ps_i][kk] = __builtin_bit_cast(bf16x8, make_uint4(w[0], w[1], w[2], w[3]));
             }
         }
     }
@@ -243,13 +212,6 @@ __global__ __launch_bounds__(SG_THREADS, 4) void mpconv_fwd_sg_kernel(const SgPa
 
     for (; b < p.B; b += gridDim.x) {
         SG_STAMP(0);
-#if !SG_OPT_EARLYCOMMIT
-        if (b != (int)blockIdx.x) {                               // (the first sample was staged before the loop)
-            commit();
-            if (lane * 16 < ebytes) *reinterpret_cast<uint4*>(es + lane * 16) = er;
-            if (b + (int)gridDim.x < p.B) prefetch(b + gridDim.x);
-        }
-#endif
         unsigned short* yb = p.y + (int64_t)b * p.y_sb + (int64_t)m0 * p.y_ld;
         uint8_t* ab = (WANT_ARG && p.argmax) ? p.argmax + (int64_t)b * p.y_sb + (int64_t)m0 * p.y_ld : nullptr;
         SG_STAMP(1);
@@ -264,11 +226,11 @@ __global__ __launch_bounds__(SG_THREADS, 4) void mpconv_fwd_sg_kernel(const SgPa
             // this tile's MFMAs; nin = 128 (two groups per tile) has no registers to spare for that and loads in place.
             constexpr int KG = KS / 4;
             constexpr bool AHEAD = KG == 1;
-            sg_bf16x8 bfr[4];
+            bf16x8 bfr[4];
             auto load_group = [&](int tile, int grp) {
                 const unsigned char* bp = xs + (tile * 32 + l31) * XSB + lh * 16 + grp * 128;
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk) bfr[kk] = __builtin_bit_cast(sg_bf16x8, *reinterpret_cast<const uint4*>(bp + kk * 32));
+                for (int kk = 0; kk < 4; ++kk) bfr[kk] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(bp + kk * 32));
             };
             if (AHEAD) load_group(0, 0);
 #pragma unroll
@@ -290,8 +252,8 @@ __global__ __launch_bounds__(SG_THREADS, 4) void mpconv_fwd_sg_kernel(const SgPa
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         uint2 pk;
-                        pk.x = sg_pack(acc[4 * g + 0], acc[4 * g + 1]);
-                        pk.y = sg_pack(acc[4 * g + 2], acc[4 * g + 3]);
+                        pk.x = fgnn_pack2(acc[4 * g + 0], acc[4 * g + 1]);
+                        pk.y = fgnn_pack2(acc[4 * g + 2], acc[4 * g + 3]);
                         *reinterpret_cast<uint2*>(pw + g * 16) = pk;
                     }
                 }
@@ -299,7 +261,7 @@ __global__ __launch_bounds__(SG_THREADS, 4) void mpconv_fwd_sg_kernel(const SgPa
             SG_STAMP(3);
             __syncthreads();
             SG_STAMP(4);
-            if (SG_OPT_EARLYCOMMIT && pass == NPASS - 1) {
+            if (pass == NPASS - 1) {
                 // every wave is past the projection: the x image is free.  Stage the NEXT sample now — its loads were
                 // issued a whole gather ago, and this point lies before this sample's stores in program order, so the
                 // vmcnt wait does not have to drain them (at the loop top it did: ~800 cycles per sample)
@@ -324,9 +286,8 @@ __global__ __launch_bounds__(SG_THREADS, 4) void mpconv_fwd_sg_kernel(const SgPa
 #pragma unroll
                     for (int j = 0; j < KC; ++j) {
                         // the bias rides in the accumulator: max_j(msg_j + bias)
-                        v[j] = sg_dot2(pk[j].y, et.w[2 * j + 1], sg_dot2_seed(pk[j].x, et.w[2 * j], c_bias[pass]));
+                        v[j] = fgnn_dot2(pk[j].y, et.w[2 * j + 1], fgnn_dot2(pk[j].x, et.w[2 * j], c_bias[pass]));
                     }
-#if SG_OPT_MAX3
                     float best = v[0];
 #pragma unroll
                     for (int j = 1; j + 1 < KC; j += 2) best = fmaxf(fmaxf(best, v[j]), v[j + 1]);      // v_max3_f32
@@ -336,19 +297,10 @@ __global__ __launch_bounds__(SG_THREADS, 4) void mpconv_fwd_sg_kernel(const SgPa
 #pragma unroll
                         for (int j = KC - 2; j >= 0; --j) arg = v[j] == best ? j : arg;
                     }
-#else
-                    float best = v[0];
-                    int arg = 0;
-#pragma unroll
-                    for (int j = 1; j < KC; ++j) {
-                        if (WANT_ARG) { if (v[j] > best) { best = v[j]; arg = j; } }        // strict >: first occurrence
-                        else best = fmaxf(best, v[j]);
-                    }
-#endif
                     float res = best;
                     if (MODE >= SG_MODE_AFFINE_RELU) res = fmaf(res, c_scale[pass], c_shift[pass]);
                     if (MODE == SG_MODE_AFFINE_RELU || (MODE == SG_MODE_GENERIC && p.relu)) res = fmaxf(res, 0.f);
-                    const unsigned packed = sg_pack(res, 0.f);
+                    const unsigned packed = fgnn_pack2(res, 0.f);
                     const int off = d * p.y_ld + pass * 64 + lane;
                     yb[off] = (unsigned short)packed;
                     if (MODE == SG_MODE_TRAIN_STATS) {
@@ -361,7 +313,7 @@ __global__ __launch_bounds__(SG_THREADS, 4) void mpconv_fwd_sg_kernel(const SgPa
             }
             if (pass + 1 < NPASS) __syncthreads();                // P is rewritten by the next pass
         }
-        if (SG_OPT_EARLYCOMMIT) { unsigned char* t = es; es = es_next; es_next = t; }
+        { unsigned char* t = es; es = es_next; es_next = t; }
         SG_STAMP(5);
     }
 

@@ -26,13 +26,12 @@
 //     32 nodes on 2 bank groups, so the DMA's per-lane SOURCE addresses apply the XOR swizzle (chunk ^ (node >> 1 & 7))
 //     instead and the readers undo it.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 #include "mpconv_dispatch.h"
 #include "fgnn_gridfold.h"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef __bf16 ws_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ws_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float ws_f32x16 __attribute__((ext_vector_type(16)));
 
 #define WS_THREADS 1024
@@ -74,43 +73,10 @@ struct WsParams {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char ws_lds[];
 
-__device__ __forceinline__ unsigned ws_pack(float a, float b) {
-    ws_bf16x2 r;
-    r[0] = (__bf16)a;
-    r[1] = (__bf16)b;
-    return __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ float ws_dot2(unsigned p, unsigned e, float acc) {
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(ws_bf16x2, p), __builtin_bit_cast(ws_bf16x2, e), acc, false);
-}
-#ifndef WS_OPT_ASMDOT
-#define WS_OPT_ASMDOT 0       // 1: seed each message with the three-address v_dot2_f32_bf16 (no v_mov of the bias per message)
-#endif
-#ifndef WS_OPT_MASKARG
-#define WS_OPT_MASKARG 0      // argmax through lane masks in SGPRs (first-occurrence logic on the scalar unit) instead of a v_cmp -> s_nop -> v_cndmask chain
-#endif
-__device__ __forceinline__ float ws_dot2_seed(unsigned p, unsigned e, float c) {
-#if WS_OPT_ASMDOT
-    float r;
-    asm("v_dot2_f32_bf16 %0, %1, %2, %3" : "=v"(r) : "v"(p), "v"(e), "v"(c));
-    return r;
-#else
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(ws_bf16x2, p), __builtin_bit_cast(ws_bf16x2, e), c, false);
-#endif
-}
 __device__ __forceinline__ float ws_max3(float a, float b, float c) {
     // (not inline asm: a VALU read of a v_dot2c result needs wait states the compiler only inserts for instructions it can see)
     return fmaxf(fmaxf(a, b), c);
 }
-// one LDS-DMA piece: 64 lanes x 16 bytes, lane l's bytes land at lds_dst + 16 l (tools/ubench/lds_dma_tr.hip).  M0 is
-// compiler-reserved: saved and restored inside the statement (cdna_hip_programming.md §5.7).  Not counted by the compiler's
-// s_waitcnt bookkeeping: the producers wait with ws_wait_dma<>.
-__device__ __forceinline__ void ws_dma16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> __device__ __forceinline__ void ws_wait_dma() { asm volatile("s_waitcnt vmcnt(%0)" :: "i"(N) : "memory"); }
 
 // Dataflow flags in LDS (monotonic counters, one ds_add per wave and sample) instead of a workgroup barrier per sample: a
 // barrier makes every wave wait for the slowest of all 16 once per sample (measured: the three consumer waves of a SIMD
@@ -190,7 +156,7 @@ __global__ __launch_bounds__(WS_THREADS) void mpconv_fwd_ws_kernel(const WsParam
         // W^T A-fragments of this wave's 64 columns = channels 16 pw .. 16 pw + 15.  Row i = 8 g + 4 h + r of column tile tc is
         // channel 4 (4 pw + 2 tc + h) + g, edge type r: the D fragment of an output lane (node, h) is then the 32 bytes
         // {channels 4 q .. 4 q + 3} x {4 edge types} of q = 4 pw + 2 tc + h — one consumer lane's reads.
-        ws_bf16x8 areg[2][KS];
+        bf16x8 areg[2][KS];
 #pragma unroll
         for (int tc = 0; tc < 2; ++tc) {
             const int g = l31 >> 3, h = (l31 >> 2) & 1, r = l31 & 3;
@@ -201,9 +167,9 @@ __global__ __launch_bounds__(WS_THREADS) void mpconv_fwd_ws_kernel(const WsParam
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int c = 16 * kk + 8 * lh + 2 * u;
-                    w[u] = ws_pack(wc[(size_t)c * p.w_ld], wc[(size_t)(c + 1) * p.w_ld]);
+                    w[u] = fgnn_pack2(wc[(size_t)c * p.w_ld], wc[(size_t)(c + 1) * p.w_ld]);
                 }
-                areg[tc][kk] = __builtin_bit_cast(ws_bf16x8, make_uint4(w[0], w[1], w[2], w[3]));
+                areg[tc][kk] = __builtin_bit_cast(bf16x8, make_uint4(w[0], w[1], w[2], w[3]));
             }
         }
         // x image reads: node row l31 (+ 32 per tile), chunk 2 kk + lh, stored at chunk ^ fx(row)
@@ -234,36 +200,36 @@ __global__ __launch_bounds__(WS_THREADS) void mpconv_fwd_ws_kernel(const WsParam
             const unsigned char* xb = xg + b * p.x_sb * 2;
             const unsigned xdst = lds0 + (unsigned)((i % XBUF) * XBYTES + pw * XP * 1024);
 #pragma unroll
-            for (int u = 0; u < XP; ++u) ws_dma16(xb + dsrc[u], xdst + u * 1024);
+            for (int u = 0; u < XP; ++u) fgnn_dma16(xb + dsrc[u], xdst + u * 1024);
             // (wave 3 has no edge-type piece; it re-fetches piece 2 into the same place so that every wave counts NDMA)
             const int ep = pw < WS_EPIECES ? pw : WS_EPIECES - 1;
             const unsigned es = pw < WS_EPIECES ? esrc : (unsigned)min((ep * 64 + lane) * 16, ebytes - 16);
-            ws_dma16(eg + b * p.et_sb * 2 + es, lds0 + (unsigned)(OFF_E + (i % EBUF) * WS_ESZ + ep * 1024));
+            fgnn_dma16(eg + b * p.et_sb * 2 + es, lds0 + (unsigned)(OFF_E + (i % EBUF) * WS_ESZ + ep * 1024));
         };
         const int ntile = Npad / 32;
         auto project = [&](int i, int par) {                              // sample i: x buffer i % XBUF -> P image `par`
             const unsigned char* xs = ws_lds + (i % XBUF) * XBYTES;
             unsigned char* ps = ws_lds + OFF_P + par * PBYTES;
             auto store_tile = [&](unsigned char* pp, const ws_f32x16& acc) {
-                *reinterpret_cast<uint4*>(pp) = make_uint4(ws_pack(acc[0], acc[1]), ws_pack(acc[2], acc[3]),
-                                                           ws_pack(acc[4], acc[5]), ws_pack(acc[6], acc[7]));
-                *reinterpret_cast<uint4*>(pp + 256) = make_uint4(ws_pack(acc[8], acc[9]), ws_pack(acc[10], acc[11]),
-                                                                 ws_pack(acc[12], acc[13]), ws_pack(acc[14], acc[15]));
+                *reinterpret_cast<uint4*>(pp) = make_uint4(fgnn_pack2(acc[0], acc[1]), fgnn_pack2(acc[2], acc[3]),
+                                                           fgnn_pack2(acc[4], acc[5]), fgnn_pack2(acc[6], acc[7]));
+                *reinterpret_cast<uint4*>(pp + 256) = make_uint4(fgnn_pack2(acc[8], acc[9]), fgnn_pack2(acc[10], acc[11]),
+                                                                 fgnn_pack2(acc[12], acc[13]), fgnn_pack2(acc[14], acc[15]));
             };
             if constexpr (KS == 4) {
                 // Two accumulator chains (the wave's two column tiles) alternate on the matrix pipe — a chain alone stalls 64 cycles
                 // per link — and the next node tile's operand fragments are in flight under this tile's MFMAs.
-                ws_bf16x8 bfr[2][4];
+                bf16x8 bfr[2][4];
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk)
-                    bfr[0][kk] = __builtin_bit_cast(ws_bf16x8, *reinterpret_cast<const uint4*>(xs + xoff[kk]));
+                    bfr[0][kk] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(xs + xoff[kk]));
 #pragma unroll
                 for (int tile = 0; tile < 3; ++tile) {
                     if (tile < ntile) {
                         if (tile + 1 < ntile) {
 #pragma unroll
                             for (int kk = 0; kk < 4; ++kk)
-                                bfr[(tile + 1) & 1][kk] = __builtin_bit_cast(ws_bf16x8, *reinterpret_cast<const uint4*>(xs + (tile + 1) * 32 * XROW + xoff[kk]));
+                                bfr[(tile + 1) & 1][kk] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(xs + (tile + 1) * 32 * XROW + xoff[kk]));
                         }
                         ws_f32x16 acc0, acc1;
 #pragma unroll
@@ -290,10 +256,10 @@ __global__ __launch_bounds__(WS_THREADS) void mpconv_fwd_ws_kernel(const WsParam
                             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
                             for (int grp = 0; grp < KS / 4; ++grp) {
-                                ws_bf16x8 bfr[4];
+                                bf16x8 bfr[4];
 #pragma unroll
                                 for (int kk = 0; kk < 4; ++kk)
-                                    bfr[kk] = __builtin_bit_cast(ws_bf16x8, *reinterpret_cast<const uint4*>(xs + tile * 32 * XROW + xoff[grp * 4 + kk]));
+                                    bfr[kk] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(xs + tile * 32 * XROW + xoff[grp * 4 + kk]));
 #pragma unroll
                                 for (int kk = 0; kk < 4; ++kk)
                                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(areg[tc][grp * 4 + kk], bfr[kk], acc, 0, 0, 0);
@@ -311,8 +277,8 @@ __global__ __launch_bounds__(WS_THREADS) void mpconv_fwd_ws_kernel(const WsParam
             if (i < cnt) dma_batch(i);
         for (int t = 0; t < cnt; ++t) {
             // this wave's pieces of sample t have landed when at most the younger batches (t + 1 .. t + XBUF - 2) are outstanding
-            if (XBUF > 2 && t + 1 < cnt) ws_wait_dma<(XBUF - 2) * NDMA>();
-            else ws_wait_dma<0>();
+            if (XBUF > 2 && t + 1 < cnt) fgnn_wait_vm<(XBUF - 2) * NDMA>();
+            else fgnn_wait_vm<0>();
             ws_signal(flags + 0, lane);
             if (t >= 1) {
                 // P image t & 1 held sample t - 2, edge-type buffer (t - 1 + XBUF) % EBUF sample t - 2: consumers done with it
@@ -328,7 +294,7 @@ __global__ __launch_bounds__(WS_THREADS) void mpconv_fwd_ws_kernel(const WsParam
             ws_signal(flags + 4, lane);
             WS_STAMP(5 + 3 * t);
         }
-        ws_wait_dma<0>();
+        fgnn_wait_vm<0>();
     } else {
         // =====================================================================================  consumers
         const int cw = wave - WS_NPROD;
@@ -400,7 +366,7 @@ __global__ __launch_bounds__(WS_THREADS) void mpconv_fwd_ws_kernel(const WsParam
                         for (int c = 0; c < 4; ++c) {
                             const unsigned w0 = c == 0 ? pa[j].x : (c == 1 ? pa[j].z : (c == 2 ? pb[j].x : pb[j].z));
                             const unsigned w1 = c == 0 ? pa[j].y : (c == 1 ? pa[j].w : (c == 2 ? pb[j].y : pb[j].w));
-                            v[c][j] = ws_dot2(w1, ev[j].y, ws_dot2_seed(w0, ev[j].x, c_bias[c]));      // the bias rides in the accumulator
+                            v[c][j] = fgnn_dot2(w1, ev[j].y, fgnn_dot2(w0, ev[j].x, c_bias[c]));      // the bias rides in the accumulator
                         }
                     float best[4];
 #pragma unroll
@@ -410,36 +376,12 @@ __global__ __launch_bounds__(WS_THREADS) void mpconv_fwd_ws_kernel(const WsParam
                     }
                     unsigned args = 0u;
                     if (WANT_ARG) {                                       // first occurrence of the maximum (torch.max on CPU)
-#if WS_OPT_MASKARG
-                        // eq_j = lanes whose message j equals the maximum (v_cmp into an SGPR pair); "first such j" is resolved on
-                        // the scalar unit, and the three bits of the index come back as three selects per channel
-                        typedef unsigned long long u64;
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-                            u64 none = ~0ull, b0 = 0, b1 = 0, b2 = 0;       // none: no earlier message equals the maximum
-#pragma unroll
-                            for (int j = 0; j < KC - 1; ++j) {
-                                const u64 first = __builtin_amdgcn_fcmpf(v[c][j], best[c], 1 /* oeq */) & none;
-                                none &= ~first;
-                                if (j & 1) b0 |= first;
-                                if (j & 2) b1 |= first;
-                                if (j & 4) b2 |= first;
-                            }
-                            if ((KC - 1) & 1) b0 |= none;                    // nothing before the last slot: it is the last slot
-                            if ((KC - 1) & 2) b1 |= none;
-                            if ((KC - 1) & 4) b2 |= none;
-                            const unsigned u1 = 1u << (8 * c), u2 = 2u << (8 * c), u4 = 4u << (8 * c);
-                            args |= (__builtin_amdgcn_inverse_ballot_w64(b0) ? u1 : 0u) | (__builtin_amdgcn_inverse_ballot_w64(b1) ? u2 : 0u);
-                            if (KC > 4) args |= __builtin_amdgcn_inverse_ballot_w64(b2) ? u4 : 0u;
-                        }
-#else
                         int arg[4] = {KC - 1, KC - 1, KC - 1, KC - 1};
 #pragma unroll
                         for (int j = KC - 2; j >= 0; --j)
 #pragma unroll
                             for (int c = 0; c < 4; ++c) arg[c] = v[c][j] == best[c] ? j : arg[c];
                         args = (unsigned)arg[0] | ((unsigned)arg[1] << 8) | ((unsigned)arg[2] << 16) | ((unsigned)arg[3] << 24);
-#endif
                     }
                     float res[4];
 #pragma unroll
@@ -457,7 +399,7 @@ __global__ __launch_bounds__(WS_THREADS) void mpconv_fwd_ws_kernel(const WsParam
                                 res[2] += __uint_as_float(av[a].y << 16); res[3] += __uint_as_float(av[a].y & 0xffff0000u);
                             }
                     }
-                    const uint2 packed = make_uint2(ws_pack(res[0], res[1]), ws_pack(res[2], res[3]));
+                    const uint2 packed = make_uint2(fgnn_pack2(res[0], res[1]), fgnn_pack2(res[2], res[3]));
                     if (MODE == WS_MODE_TRAIN_STATS && valid[g]) {        // of the values as stored
                         const float z0 = __uint_as_float(packed.x << 16), z1 = __uint_as_float(packed.x & 0xffff0000u);
                         const float z2 = __uint_as_float(packed.y << 16), z3 = __uint_as_float(packed.y & 0xffff0000u);

@@ -3,6 +3,7 @@
 // a skip link: /root/reference/lib/model/mpnn/factor_mpnn_sp.py:139-170), so its gradient is a sum of 3-5 tensors;
 // autograd adds them pairwise (n-1 kernels, 3(n-1) passes over memory), this kernel reads n and writes 1.
 #include "fgnn_common.h"
+#include "fgnn_device.h"
 
 #define SN_MAX 8
 struct SnParams {
@@ -37,12 +38,7 @@ __global__ __launch_bounds__(256) void sum_n_kernel(const SnParams p) {
         }
         uint4 o;
         if constexpr (sizeof(T) == 2) {
-            typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-            b2 h;
-            h[0] = (__bf16)acc[0]; h[1] = (__bf16)acc[1]; o.x = __builtin_bit_cast(unsigned, h);
-            h[0] = (__bf16)acc[2]; h[1] = (__bf16)acc[3]; o.y = __builtin_bit_cast(unsigned, h);
-            h[0] = (__bf16)acc[4]; h[1] = (__bf16)acc[5]; o.z = __builtin_bit_cast(unsigned, h);
-            h[0] = (__bf16)acc[6]; h[1] = (__bf16)acc[7]; o.w = __builtin_bit_cast(unsigned, h);
+            o = make_uint4(fgnn_pack2(acc[0], acc[1]), fgnn_pack2(acc[2], acc[3]), fgnn_pack2(acc[4], acc[5]), fgnn_pack2(acc[6], acc[7]));
         } else {
             o = make_uint4(__float_as_uint(acc[0]), __float_as_uint(acc[1]), __float_as_uint(acc[2]), __float_as_uint(acc[3]));
         }
@@ -108,12 +104,7 @@ __global__ __launch_bounds__(256) void node_sum_kernel(const T* g, T* out, int64
         }
         uint4 o;
         if constexpr (sizeof(T) == 2) {
-            typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-            b2 h;
-            h[0] = (__bf16)acc[0]; h[1] = (__bf16)acc[1]; o.x = __builtin_bit_cast(unsigned, h);
-            h[0] = (__bf16)acc[2]; h[1] = (__bf16)acc[3]; o.y = __builtin_bit_cast(unsigned, h);
-            h[0] = (__bf16)acc[4]; h[1] = (__bf16)acc[5]; o.z = __builtin_bit_cast(unsigned, h);
-            h[0] = (__bf16)acc[6]; h[1] = (__bf16)acc[7]; o.w = __builtin_bit_cast(unsigned, h);
+            o = make_uint4(fgnn_pack2(acc[0], acc[1]), fgnn_pack2(acc[2], acc[3]), fgnn_pack2(acc[4], acc[5]), fgnn_pack2(acc[6], acc[7]));
         } else {
             o = make_uint4(__float_as_uint(acc[0]), __float_as_uint(acc[1]), __float_as_uint(acc[2]), __float_as_uint(acc[3]));
         }
