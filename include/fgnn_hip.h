@@ -652,6 +652,35 @@ int fgnn_chain_budget_lp(const float* unary, int64_t unary_sb, const float* pair
                          int64_t* labels, double* marginals, double* value, int32_t* status, int32_t* iters, fgnn_stream_t stream);
 int64_t fgnn_chain_budget_lp_lds_bytes(int32_t N, int32_t h);
 
+/*
+ * Scores of decisions on the same chain models (csrc/pgm_eval.hip), one launch per batch: the accounting of the reference's synthetic
+ * test loops (/root/reference/train_syn_hop_factor.py:349-409, train_syn_pw_factor.py:349-411, train_syn_fixed_pw_hop.py:313-362:
+ * acc, lp_acc and the cross-entropy loss) and, with no reference counterpart, whether each decision is feasible and its objective.
+ *
+ * Decisions of sample b, variable i < N, of kind
+ *   FGNN_PGM_DEC_F32 / FGNN_PGM_DEC_BF16  logits v_c = dec[b * dec_sb + c * dec_cs + i * dec_vs], c = 0, 1 (a model's [B, 2, N, 1]
+ *                        output as it is: (dec_sb, dec_cs, dec_vs) = (2N, N, 1)); x_i = 1 exactly when torch.argmax over (v0, v1)
+ *                        returns 1: v1 > v0, or v1 NaN and v0 not (ties, +-0 and a NaN v0 give 0)
+ *   FGNN_PGM_DEC_I64     assignments a = dec[b * dec_sb + i * dec_vs] int64 (dec_cs unused): x_i = (a != 0), correct where a == label
+ * label [b * label_sb + i] int64 (the exact MAP; 0 / 1).  unary, pair, caps in the layouts and batch strides of
+ * fgnn_chain_budget_map (0: shared by the batch).  Outputs, each NULL when not wanted:
+ *   correct [B] int32    variables with decision == label
+ *   feasible [B] uint8   1 when every window w < N-h+1 has sum x_w .. x_{w+h-1} <= caps[w]
+ *   objective [B] f64    sum_i unary[i][x_i] + sum_i pair[i][2 x_i + x_{i+1}], read as f32 and summed in f64 in the order of
+ *                        fgnn_chain_budget_map's recursion (u_0, then (acc + pair_{t-1}) + u_t): the MAP label scores its objective
+ *   nll [B] f64          logit kinds only (FGNN_EINVAL with assignments): sum_i logsumexp(v0, v1) - v_{label_i} (F.cross_entropy's
+ *                        summand; label != 0 reads v1), in f64, per lane in chunk order and then over the wave in a fixed order
+ *   counts [4] int64     ADDED to: {variables compared, variables correct, feasible samples, samples equal to the label in every
+ *                        variable}; integer atomics, so deterministic, and a test set accumulates on the device
+ * 1 <= h <= N <= 1024 and the three kinds, FGNN_EUNSUPPORTED otherwise; negative sizes or strides, a null dec / label / unary / pair /
+ * caps: FGNN_EINVAL; all checked before any launch.  B = 0 is a no-op.
+ */
+enum { FGNN_PGM_DEC_F32 = 0, FGNN_PGM_DEC_BF16 = 1, FGNN_PGM_DEC_I64 = 2 };
+int fgnn_chain_budget_score(const void* dec, int32_t dec_kind, int64_t dec_sb, int64_t dec_cs, int64_t dec_vs, const int64_t* label,
+                            int64_t label_sb, const float* unary, int64_t unary_sb, const float* pair, int64_t pair_sb,
+                            const int32_t* caps, int64_t caps_sb, int64_t B, int32_t N, int32_t h, int32_t* correct,
+                            uint8_t* feasible, double* objective, double* nll, int64_t* counts, fgnn_stream_t stream);
+
 const char* fgnn_last_error(void);
 /* Name (as rocprofv3 prints it) of the kernel the calling thread's last forward/backward dispatched to. */
 const char* fgnn_last_kernel(void);
@@ -661,7 +690,8 @@ const char* fgnn_last_kernel(void);
  * ldpc_channel_features_rng, backward_reduces_getype, desc.reserved = in-degree | GETYPE_REDUCED); 5: fgnn_block_tail_*;
  * 6: fgnn_block_head_backward.  11: fgnn_mpconv_block_forward_rows.  12: fgnn_block_tail_backward_moments,
  * fgnn_block_tail_wgrad_finish, fgnn_block_tail_moments_bytes.  14: fgnn_chain_budget_map, fgnn_chain_budget_map_lds_bytes,
- * fgnn_pgm_sample_rng.  15: fgnn_chain_budget_lp, fgnn_chain_budget_lp_lds_bytes. */
+ * fgnn_pgm_sample_rng.  15: fgnn_chain_budget_lp, fgnn_chain_budget_lp_lds_bytes; later additions at 15 (new entry points
+ * only, no existing one changed): fgnn_ldpc_received_features, fgnn_ldpc_error_counts, fgnn_chain_budget_score. */
 #define FGNN_ABI_VERSION 15
 /* Arithmetic of the f32 synthetic-PGM operator's BACKWARD (16 edge types, ORIG_WITH_NEIGHBOR / ORIG_WITH_DIFF, 64 -> 64, max: the
  * autograd of /root/reference/lib/model/mpnn/mp_nn.py:136-175 as train_syn_*.py reaches it): 2 (default) = every f32 operand of the three
