@@ -14,6 +14,8 @@ with the reference's plain BatchNorm2d; its "SyncBatchNorm" is an alias, mp_nn.p
 import torch
 import torch.distributed as dist
 
+from .backward_pass import PASS
+
 
 FLAT_ALIGN = 4      # elements: every parameter starts on a 16-byte boundary of the flat buffers (the kernels read filters with vector loads)
 
@@ -142,21 +144,11 @@ class FlatGradBucket:
         ops.enable_grad_sink(self.params)
 
     def zero(self):
-        # weight-gradient launches a backward pass parked and never issued (it raised half-way, ops.defer_wgrad) add into this
-        # buffer: issue them BEFORE the zeroing, so that they cannot land in the next step's sums
-        from . import ops
-        if any(ops._DEFERRED.values()):
-            ops.flush_deferred()
-        # flush_deferred issues each launch on ITS stream; the zeroing below runs on the current one: join them first (the
-        # engine's end-of-pass join never ran for a pass that died), or a parked kernel could still add behind the memset
-        if ops._DEFER_ISSUED and self.flat.is_cuda:
-            cur = torch.cuda.current_stream(self.flat.device)
-            for st in ops._DEFER_ISSUED:
-                if st != cur:
-                    cur.wait_stream(st)
-            ops._DEFER_ISSUED.clear()
-        if self.flat.is_cuda:    # (a CPU / gloo bucket never recorded a fold and must not need libfgnn_hip.so at all)
-            ops.flush_folds()    # folds a dead pass recorded and never flushed: in front of the zeroing, like its parked launches
+        # weight-gradient launches a backward pass parked and never issued (it raised half-way) add into this buffer, and so do the
+        # folds it recorded and never flushed: issue them BEFORE the zeroing, joined into the current stream, so that they cannot
+        # land in the next step's sums (the engine's end-of-pass join never ran for a pass that died)
+        if self.flat.is_cuda:    # (a CPU / gloo bucket never parked or recorded anything and must not need libfgnn_hip.so at all)
+            PASS.drain()
         self.flat.zero_()
 
     @property

@@ -9,14 +9,13 @@ Anything outside that family (f32 inputs, other widths, CPU tensors) runs the th
 """
 import torch
 
-from . import _hip
+from . import _hip, ops
 from .mpnn.pointwise import PointwiseConv2d
 
 
 class _EdgeMLPFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
-        from . import ops
         B, cin, M, k = x.shape
         net = w2.shape[0]
         E = M * k
@@ -37,7 +36,6 @@ class _EdgeMLPFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import ops
         ops.backward_node_begins()
         ops.backward_tail_begins()      # (behind this node the pass is one chain on this stream: what waits for its end goes to the side stream)
         x, w1, b1, w2 = ctx.saved_tensors
@@ -50,10 +48,8 @@ class _EdgeMLPFn(torch.autograd.Function):
         if not ((gy.stride(3) * k == gy.stride(2)) or M == 1 or k == 1):
             gy = gy.contiguous()
         gy_sr = gy.stride(3) if k > 1 else gy.stride(2)
-        sinks = [ops.grad_sink(p) for p in ctx.params]
-        shapes = [(64, cin, 1, 1), (64,), (net, 64, 1, 1), (net,)]
-        outs = [s if s is not None else torch.zeros(shp, device=x.device, dtype=torch.float32)
-                for s, shp in zip(sinks, shapes)]
+        grads = ops.param_grads(x.device)
+        outs = [grads.acc(i, p, shape) for i, (p, shape) in enumerate(zip(ctx.params, [(64, cin, 1, 1), (64,), (net, 64, 1, 1), (net,)]))]
         L = _hip.lib()
         ws = ops._workspace(x.device, int(L.fgnn_edge_mlp_workspace_bytes(B, E)))
         ops.timed('edge_mlp_bwd_kernel (MFMA where the layout allows)', 2 * B * E * (cin + net),
@@ -63,8 +59,7 @@ class _EdgeMLPFn(torch.autograd.Function):
                       _hip._ptr(outs[1]), _hip._ptr(outs[2]), _hip._ptr(outs[3]), _hip._ptr(ws), ws.numel() * 4,
                       _hip.stream_ptr())),
                   nflops=2 * B * E * 64 * (2 * cin + 2 * net))
-        grads = [None if s is not None else o.to(p.dtype) for s, o, p in zip(sinks, outs, ctx.params)]
-        return (None, *grads)
+        return (None, *[grads.result(i, p.dtype) for i, p in enumerate(ctx.params)])
 
 
 class EdgeMLP(torch.nn.Sequential):

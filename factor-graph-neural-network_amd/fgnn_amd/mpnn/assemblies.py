@@ -11,6 +11,8 @@ import contextlib
 
 import torch
 
+from .. import ops as _ops
+from ..backward_pass import PASS
 from .blocks import iid_mapping, iid_mapping_bn, iid_mapping_in, mp_conv_residual
 from .pointwise import NodeInstanceNorm, PointwiseConv2d as _Conv, add_all, instnorm_relu_dot
 from .message_op import base_mp_nn, mp_conv_type, mp_conv_v2
@@ -68,7 +70,6 @@ class _SplitNodes(torch.autograd.Function):
             g_nodes = ref.new_zeros((B, C, ctx.n, W))
         if g_factors is None:
             g_factors = ref.new_zeros((B, C, N - ctx.n, W))
-        from .. import ops as _ops
         g = _ops.concat2(g_nodes, g_factors, 2) if ctx.cl else torch.cat([g_nodes, g_factors], dim=2)
         return (g.contiguous(memory_format=torch.channels_last) if ctx.cl else g), None
 
@@ -124,7 +125,6 @@ class factor_mpnn(torch.nn.Module):
         ffeat = [m(f) for f, m in zip(factor_features, self.mapping_modules[1:])]
         history = []
         from ..ops import fan_out
-        from .. import ops as _ops
         track = torch.is_grad_enabled() and nfeat.requires_grad
         for L, row in enumerate(self.mp_nn_modules):
             to_nodes, to_factors = [], []
@@ -238,7 +238,6 @@ class FactorNN(torch.nn.Module):
         shared by the batch, four foldable blocks.  Returns (new_var, new_fac) or None (the staged path then runs)."""
         import ctypes
         from .. import _hip
-        from .blocks import _is_identity_list
         from .pointwise import refresh_in_place, state_epoch
         dims = self.dim_mapping_list
         if (not FUSE_EVAL_LAYERS or self.training or torch.is_grad_enabled() or self.nfactor_types != 2
@@ -266,7 +265,7 @@ class FactorNN(torch.nn.Module):
                 and iv.dtype == torch.int64 and if_.dtype == torch.int64):
             return None
         hv2f, hf2v = nn_idx_v2f[1], nn_idx_f2v[1]
-        if not (tuple(hv2f.shape) == (B, 1, 96) and tuple(hf2v.shape) == (B, 96, 1) and _is_identity_list(hv2f)):
+        if not (tuple(hv2f.shape) == (B, 1, 96) and tuple(hf2v.shape) == (B, 96, 1) and _ops.is_identity_list(hv2f)):
             return None
         ev, ef, hev, hef = etype_v2f[0][L], etype_f2v[0][L], etype_v2f[1][L], etype_f2v[1][L]
 
@@ -304,7 +303,6 @@ class FactorNN(torch.nn.Module):
         # algorithmic bytes: the state read and written once (+ the skip terms), the parity edge types, the parameters
         nstate = B * (96 + 48 + 1) * 64 * 2
         nbytes = nstate * (3 if skip is not None else 2) + 2 * 288 * 4 * 2 * (B if ev.stride(0) else 1) + params.numel() * 4
-        from .. import ops as _ops
         _ops.timed('factor_layer_fwd_kernel', nbytes, lambda: rcs.append(_hip.lib().fgnn_factor_layer_forward(
             B, P(var), P(fac[0]), P(f1), P(skip[0]) if skip is not None else None, P(skip[1][0]) if skip is not None else None,
             P(s1), P(iv), iv.stride(1), iv.stride(2), P(if_), if_.stride(1), if_.stride(2), P(ev), ev.stride(0), P(ef), ef.stride(0),
@@ -323,7 +321,6 @@ class FactorNN(torch.nn.Module):
         var = self.node_mapping_module(node_feature)
         fac = [m(f) for f, m in zip(hop_features, self.factor_mapping_modules)]
         from ..ops import fan_out
-        from .. import ops as _ops
         nft = self.nfactor_types
         nL = len(self.v2f_modules)
         # the neighbour tables serve all layers: convert once, and recognise B equal copies of one graph (what the
@@ -375,7 +372,7 @@ class FactorNN(torch.nn.Module):
             # parity factors' f2f map as well serialises the join and costs 2 ms).
             two = _ops.SIDE_STREAM and nft > 1 and var.is_cuda
             if two:
-                _ops.SIDE_ACTIVE = True        # (weight gradients are only parked once a second stream exists: ops.defer_wgrad)
+                PASS.side_active = True        # (weight gradients are only parked once a second stream exists: BackwardPass.park)
             new_fac, h = [None] * nft, []
             if two:
                 main, side = torch.cuda.current_stream(var.device), _ops.side_stream(var.device)

@@ -5,12 +5,15 @@ Mirrors (names, constructor signatures, state_dict keys) of
   iid_mapping / _bn / _in            /root/reference/lib/model/mpnn/base_model.py:43-90
   max_pool_layer, flatten            /root/reference/lib/model/mpnn/base_model.py:19-40
 """
+import ctypes
 
 import torch
 
-from .message_op import base_mp_nn, mp_conv_type, mp_conv_v2
-from .. import ops
-from .pointwise import BatchNormAct2d, BnHandoff, NodeInstanceNorm, PointwiseConv2d, as_addends, refresh_in_place
+from .. import _hip, ops
+from . import pointwise
+from .message_op import _EXT_CODE, base_mp_nn, mp_conv_type, mp_conv_v2
+from .pointwise import (BatchNormAct2d, BnHandoff, NodeInstanceNorm, PointwiseConv2d, _InstNormAct, _RowLinear, as_addends, node_sum,
+                        refresh_in_place)
 from .pointwise import state_epoch as pointwise_state_epoch
 
 
@@ -65,8 +68,6 @@ class iid_mapping_in(torch.nn.Module):
         The pre-norm tensor is written only when a backward will read it, and never read back in the forward.  The autograd graph
         is the staged one (the map's and the norm's own Functions, handed their outputs): the backward is unchanged.  None: the
         staged path runs (other widths / dtypes / layouts, autocast off, CPU)."""
-        from .. import _hip, ops
-        from .pointwise import _InstNormAct, _RowLinear
         if not FUSE_IID_IN or not x.is_cuda or x.dim() != 4 or x.shape[3] != 1 or x.shape[2] not in (48, 96):
             return None
         conv, norm = self.main[0], self.main[1]
@@ -125,10 +126,6 @@ class flatten(torch.nn.Module):
         return input.view(input.size(0), -1)
 
 
-def _is_identity_list(nn_idx):
-    return ops.is_identity_list(nn_idx)
-
-
 TAIL_WGRAD_MOMENTS = True    # training: conv2's weight gradient from the moments of the tail's reduce pass (no gz3 / a2 in memory)
 FUSE_TRAIN_TAIL = True       # training: BatchNorm2 + ReLU -> conv2 -> BatchNorm3 + LeakyReLU (+ addends) without storing conv2's output
 
@@ -154,8 +151,6 @@ class _BlockHead(torch.autograd.Function):
     def forward(ctx, rows, weight, bias, bn_w, bn_b, handoff, slope, box=None):
         """``handoff``: BatchNorm1's ``BnHandoff``; ``bn_w`` / ``bn_b`` are its gamma / beta as arguments of their own, for autograd."""
         ctx.box = box                   # the ops.FanBox of the state `rows` views: the backward deposits (gz1, W1) there instead of forming gx
-        from .. import _hip
-        from . import pointwise
         L = _hip.lib()
         P = _hip._ptr
         z1 = pointwise.hip_linear(rows, weight, bias, bn=handoff)       # the map's last workgroup finalises BatchNorm1's statistics
@@ -173,7 +168,6 @@ class _BlockHead(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, ga1):
-        from .. import _hip
         ops.backward_node_begins()
         L = _hip.lib()
         P = _hip._ptr
@@ -184,15 +178,10 @@ class _BlockHead(torch.autograd.Function):
         ga1 = ga1.contiguous()
         if ga1.dtype != z1.dtype:
             ga1 = ga1.to(z1.dtype)
-
-        def sink(param, shape):
-            g = ops.grad_sink(param)
-            return (g, True) if g is not None else (torch.zeros(shape, device=dev, dtype=torch.float32), False)
-        gw1, s_w1 = sink(pw, (64,))
-        gb1, s_b1 = sink(pb, (64,))
-        Wbase = pW._base if pW._base is not None and pW._base.numel() == pW.numel() else pW
-        gW, s_W = sink(Wbase, (64, cin))
-        gbias, s_bias = sink(pbias, (64,)) if pbias is not None else (None, True)
+        grads = ops.param_grads(dev)
+        gw1, gb1 = grads.acc('gamma', pw, (64,)), grads.acc('beta', pb, (64,))
+        gW, gbias = grads.acc('W', pW, (64, cin)), grads.acc('bias', pbias, (64,))
+        sinks = grads.all_sunk('W', 'bias')         # (conv1's job; BatchNorm's gamma / beta are written by the kernel below)
         gz1 = torch.empty_like(z1)
         lazy = ctx.needs_input_grad[0] and ctx.box is not None and weight.is_contiguous() and weight.dtype == torch.float32
         gx = None if lazy else torch.empty((R, cin), device=dev, dtype=z1.dtype)
@@ -205,26 +194,20 @@ class _BlockHead(torch.autograd.Function):
         if lazy:
             # (gz1 @ W1 joins the state's other gradients in the fan-out's backward; with conv1's parameter gradients going to sinks its
             # weight gradient joins the state's other consumers' there too — ops.FanBox: one pass over the state's rows for all)
-            taken = ctx.box.deposit(gz1, weight.detach(), wgrad=(rows, gW, gbias) if (s_W and s_bias) else None)
+            taken = ctx.box.deposit(gz1, weight.detach(), wgrad=(rows, gW, gbias) if sinks else None)
         if taken != 2:
-            record = s_W and s_bias and ops.folds_deferrable()
-
-            def launch(rows=rows, gz1=gz1, gW=gW, gbias=gbias):
+            def launch(record, rows=rows, gz1=gz1, gW=gW, gbias=gbias):
                 ops.linear_wgrad(rows, [(gz1, gW.view(64, cin), gbias)], record)
-            if s_W and s_bias:
-                ops.defer_wgrad(launch, (rows, gz1))
-            else:
-                launch()
+            grads.run_wgrad(launch, (rows, gz1), 'W', 'bias')
         if lazy:
             if taken:
                 gx = ctx.box.placeholder(rows.shape)
             else:                                        # no slot: the product after all (gz1 is in the infinity cache)
-                from . import pointwise
                 gx = pointwise.hip_linear(gz1, weight.detach(), None, transposed=True)
                 if gx is None:
                     gx = gz1 @ pointwise.cast_cached(pW._base if pW._base is not None else pW, gz1.dtype).view(weight.shape)
-        return (gx if ctx.needs_input_grad[0] else None, None if s_W else gW.view(pW.shape).to(pW.dtype),
-                None if (s_bias or gbias is None) else gbias, None if s_w1 else gw1, None if s_b1 else gb1, None, None, None)
+        return (gx if ctx.needs_input_grad[0] else None, grads.result('W', pW.dtype), grads.result('bias'),
+                grads.result('gamma'), grads.result('beta'), None, None, None)
 
 
 LATE_JOIN = True     # the tail asks for addends of another stream behind its statistics pass
@@ -251,7 +234,6 @@ class _AddendRoute(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .pointwise import node_sum
         outs = []
         for i, q in enumerate(ctx.periods):
             if not ctx.needs_input_grad[3 + i]:
@@ -292,9 +274,6 @@ class _BlockTail(torch.autograd.Function):
         their gamma / beta are ``w2``, ``b2`` / ``w3``, ``b3``, arguments of their own for autograd.  ``population``: rows the batch
         statistics stand for in the running variances (0 = R; R * m for a per-sample vector the reference broadcasts over m nodes).
         ``periods``: see ``_AddendRoute``."""
-        import ctypes
-        from .. import _hip
-        from . import pointwise
         L = _hip.lib()
         P = _hip._ptr
         R, Cout = e.shape[0], W2.shape[0]
@@ -324,14 +303,11 @@ class _BlockTail(torch.autograd.Function):
         ctx.slopes = (slope2, slope3)
         ctx.has_add = tuple(a is not None and a.requires_grad for a in adds)
         ctx.periods = tuple(periods)
-        ctx.has_bias2 = bias2 is not None
         ctx.params = (w2, b2, W2, bias2, w3, b3)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        from .. import _hip
-        from . import pointwise
         ops.backward_node_begins()
         L = _hip.lib()
         P = _hip._ptr
@@ -343,17 +319,10 @@ class _BlockTail(torch.autograd.Function):
         gout = gout.contiguous()
         if gout.dtype != e.dtype:
             gout = gout.to(e.dtype)
-
-        def sink(param, shape):
-            g = ops.grad_sink(param)
-            return (g, True) if g is not None else (torch.zeros(shape, device=dev, dtype=torch.float32), False)
-        gw3, s_w3 = sink(pw3, (Cout,))
-        gb3, s_b3 = sink(pb3, (Cout,))
-        gw2, s_w2 = sink(pw2, (64,))
-        gb2, s_b2 = sink(pb2, (64,))
-        Wbase = pW2._base if pW2._base is not None and pW2._base.numel() == pW2.numel() else pW2
-        gW2, s_W2 = sink(Wbase, (Cout, 64))
-        gbias2, s_bias2 = sink(pbias2, (Cout,)) if ctx.has_bias2 else (None, True)
+        grads = ops.param_grads(dev)
+        gw3, gb3 = grads.acc('gamma3', pw3, (Cout,)), grads.acc('beta3', pb3, (Cout,))
+        gw2, gb2 = grads.acc('gamma2', pw2, (64,)), grads.acc('beta2', pb2, (64,))
+        gW2, gbias2 = grads.acc('W2', pW2, (Cout, 64)), grads.acc('bias2', pbias2, (Cout,))
         moments = a2 is None
         gz3 = None if moments else torch.empty((R, Cout), device=dev, dtype=e.dtype)
         ga2 = torch.empty_like(e)
@@ -386,33 +355,27 @@ class _BlockTail(torch.autograd.Function):
             P(e), P(ga2), P(ge), R, 64, _hip.BF16, P(st2[0]), P(st2[1]), P(w2.detach()), P(b2.detach()), slope2, P(dsum2),
             _hip.stream_ptr())))
         # conv2's weight / bias gradient: gz3^T a2 over the R rows (csrc/linear_wgrad_b16.hip); parked when it goes to the flat
-        # bucket (ops.defer_wgrad: nothing in the backward reads it)
-        record = s_W2 and s_bias2 and ops.folds_deferrable()
-
+        # bucket (backward_pass.run_wgrad: nothing in the backward reads it)
         if moments:
             scale3 = st3[2]
 
-            def launch(mom=mom, gW2=gW2, scale3=scale3, W2d=W2.detach(), bias2c=bias2c):
+            def launch(record, mom=mom, gW2=gW2, scale3=scale3, W2d=W2.detach(), bias2c=bias2c):
                 # (conv2's BIAS gradient in front of a batch-statistics BatchNorm is identically zero — sum gz3 = 0 — nothing is added to it)
                 ops.timed('block_tail_wgrad_finish (fold + combine)', 4 * mom.numel(), lambda: _hip.check(L.fgnn_block_tail_wgrad_finish(
                     P(mom), mom.numel() * 4, R, Cout, P(W2d), P(bias2c), P(scale3), P(gW2.view(Cout, 64)), _hip.stream_ptr())))
             operands = (mom, scale3)
         else:
-            def launch(a2=a2, gz3=gz3, gW2=gW2, gbias2=gbias2):
+            def launch(record, a2=a2, gz3=gz3, gW2=gW2, gbias2=gbias2):
                 ops.linear_wgrad(a2, [(gz3, gW2.view(Cout, 64), gbias2)], record)
             operands = (a2, gz3)
-        if s_W2 and s_bias2:
-            ops.defer_wgrad(launch, operands)
-        else:
-            launch()
+        grads.run_wgrad(launch, operands, 'W2', 'bias2')
         ha = ctx.has_add
         gadd = [None, None, None]
         for i in range(3):
             if ha[i]:
                 gadd[i] = gout if ctx.periods[i] == 1 else pointwise.node_sum(gout, ctx.periods[i])
-        return (ge, None if s_w2 else gw2, None if s_b2 else gb2, None, None, None, None,
-                None if s_W2 else gW2.view(pW2.shape).to(pW2.dtype), None if (s_bias2 or gbias2 is None) else gbias2,
-                None if s_w3 else gw3, None if s_b3 else gb3, None, *gadd, None)
+        return (ge, grads.result('gamma2'), grads.result('beta2'), None, None, None, None, grads.result('W2', pW2.dtype),
+                grads.result('bias2'), grads.result('gamma3'), grads.result('beta3'), None, *gadd, None)
 
 
 class mp_conv_residual(base_mp_nn):
@@ -470,8 +433,6 @@ class mp_conv_residual(base_mp_nn):
     def _fused_eval(self, x, nn_idx, etype, addend):
         """Inference: the whole block as ONE kernel (csrc/mpconv_block_fwd.hip) when it is the 64-wide bf16
         parity-check shape; None otherwise."""
-        import ctypes
-        from .. import _hip, ops
         mp = self.mp_conv
         bn1, bn2, bn3 = self.conv1[1], mp.bn, self.conv2[1]
         if (not FUSE_EVAL_BLOCKS or self.with_residual or self.training or torch.is_grad_enabled() or not x.is_cuda
@@ -486,7 +447,7 @@ class mp_conv_residual(base_mp_nn):
         nout = self.conv2[0].out_channels
         M, k = nn_idx.shape[1:]
         fanout = mp.nedge_types == 1 and N == 1 and k == 1          # the hyper-factor -> variables call
-        fanin = mp.nedge_types == 1 and M == 1 and k == N and N > 1 and _is_identity_list(nn_idx)   # variables -> it
+        fanin = mp.nedge_types == 1 and M == 1 and k == N and N > 1 and ops.is_identity_list(nn_idx)   # variables -> it
         if not (fanout or fanin) and not (mp.nedge_types == 4 and k in (3, 6)):
             return None
         xr = x.permute(0, 2, 3, 1)
@@ -604,7 +565,6 @@ class mp_conv_residual(base_mp_nn):
     def _fused_train_head(self, x):
         """Training, bf16, 64 channels in the middle: conv1 + BatchNorm + LeakyReLU as ``_BlockHead`` (same forward kernels, fused
         backward).  None = not this family."""
-        from .. import _hip
         conv, bn = self.conv1[0], self.conv1[1]
         handoff = BnHandoff.of(bn) if isinstance(bn, BatchNormAct2d) else None
         if not (FUSE_TRAIN_HEAD and self.training and torch.is_grad_enabled() and x.is_cuda and isinstance(conv, PointwiseConv2d)
@@ -629,8 +589,6 @@ class mp_conv_residual(base_mp_nn):
         """Training, bf16: the operator's pre-BatchNorm output goes straight into csrc/block_tail.hip (``_BlockTail``) —
         BatchNorm + ReLU, conv2, BatchNorm + LeakyReLU and the addends without conv2's Cout-wide output ever being stored.
         None = not this family (the staged path runs)."""
-        from .. import _hip
-        from .message_op import _EXT_CODE
         mp = self.mp_conv
         bn2, conv2, bn3 = mp.bn, self.conv2[0], self.conv2[1]
         hand2, hand3 = (BnHandoff.of(b) if isinstance(b, BatchNormAct2d) else None for b in (bn2, bn3))
@@ -644,7 +602,6 @@ class mp_conv_residual(base_mp_nn):
         B, M = h.shape[0], nn_idx.shape[1]
         if B * M < 2 or not _hip.lib().fgnn_block_tail_partials(B * M, conv2.out_channels):
             return None
-        from . import pointwise
         z = ops.mpconv(h, nn_idx, etype, mp.filters, mp.bias, mp.nou, mp.nedge_types, _EXT_CODE[mp.extension],
                        _hip.AGG_CODES[mp.aggregtor], bn=hand2 if mult == 1 else None)
         rows = z.permute(0, 2, 3, 1)

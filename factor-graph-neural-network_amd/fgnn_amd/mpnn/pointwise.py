@@ -9,12 +9,13 @@ dominate the step).  ``PointwiseConv2d`` keeps Conv2d's parameters / state_dict 
 kernel reads and writes without a transpose.  Outputs are logical [B,C,N,W] with
 channels-last strides; every consumer in this package is stride-agnostic.
 """
+import ctypes
 import dataclasses
 import weakref
 
 import torch
 
-from .. import _hip
+from .. import _hip, ops
 
 
 _CAST_CACHE = {}          # id(tensor) -> [weakref(tensor), version, epoch, low-precision copy]
@@ -162,7 +163,6 @@ class BnHandoff:
         """stats [4, C] of the BatchNorm over ``rows`` [R, C]: the producer's when they describe these rows, else one reducing launch
         of csrc/bnact.hip (its last workgroup finalises).  When the producer finalised but wrote other rows (the consumer normalises
         a contiguous copy) that launch forms scale / shift only: the batch is already counted."""
-        from .. import ops
         stats = self.stats_for(rows)
         if stats is not None:
             return stats
@@ -197,7 +197,6 @@ def hip_linear(rows, weight, bias, bn=None, transposed=False):
     npart = L.fgnn_linear_forward_partials(R, cin, cout)
     if npart == 0 or (bn is not None and R < 2):
         return None
-    from .. import ops
     w = weight.detach()
     if not w.is_contiguous():
         w = w.contiguous()
@@ -220,7 +219,6 @@ def hip_linear(rows, weight, bias, bn=None, transposed=False):
 def node_sum(g, M):
     """[R, C] -> [R / M, C]: sum over each sample's M consecutive rows (the gradient of a per-sample row that was broadcast over the
     sample's nodes), one pass (csrc/sum_n.hip: node_sum_kernel)."""
-    from .. import ops
     R, C = g.shape
     g = g.contiguous()
     out = torch.empty((R // M, C), device=g.device, dtype=g.dtype)
@@ -250,7 +248,6 @@ class _RowLinear(torch.autograd.Function):
         ``gy @ weight`` (the fan-out's backward multiplies all its consumers' pairs in one launch)."""
         ctx.box = box
         ctx.save_for_backward(rows, weight)
-        ctx.has_bias = bias is not None
         ctx.params = (weight, bias)                     # leaf tensors (ops.grad_sink)
         if precomputed is not None:
             return precomputed
@@ -264,7 +261,6 @@ class _RowLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         rows, weight = ctx.saved_tensors
-        from .. import ops
         ops.backward_node_begins()
         gy = gy.contiguous()
         if gy.dtype != rows.dtype:
@@ -272,16 +268,22 @@ class _RowLinear(torch.autograd.Function):
         R, cin = rows.shape
         cout = weight.shape[0]
         wparam, bparam = ctx.params
-        # weight may be a [cout,cin,1,1] Conv2d parameter viewed as [cout,cin]: its .grad lives on the base
-        base = wparam._base if wparam._base is not None and wparam._base.numel() == wparam.numel() else wparam
-        gw_sink, gb_sink = ops.grad_sink(base), ops.grad_sink(bparam)
-        sinks = gw_sink is not None and (not ctx.has_bias or gb_sink is not None)
+        # wide maps: bf16 multiples of 64 up to 256 and f32 multiples of 4 (csrc/linear_wgrad_f32.hip) have their own kernels;
+        # what is left (odd widths) goes to the library: plain returned tensors, no sink
+        library = cin * cout >= 256 * 256 and not (rows.dtype == torch.bfloat16 and cin % 64 == 0 and cout % 64 == 0
+                                                   and cin <= 256 and cout <= 256) and not (
+            rows.dtype == torch.float32 and cin % 4 == 0 and cout % 4 == 0 and cin <= 1024 and cout <= 1024 and R >= 2048)
+        sinks = False
+        if not library:
+            grads = ops.param_grads(rows.device)
+            gw, gb = grads.acc('weight', wparam, (cout, cin)), grads.acc('bias', bparam, (cout,))
+            sinks = grads.all_sunk('weight', 'bias')
         grows = None
         taken = 0
         if ctx.needs_input_grad[0] and ctx.box is not None:
             # (gy @ weight joins the state's other gradients in the fan-out's backward — and, with the parameter gradients going to
             # sinks, this map's weight gradient joins the other consumers' there too: one pass over the state's rows for all of them)
-            taken = ctx.box.deposit(gy, weight, wgrad=(rows, gw_sink, gb_sink if ctx.has_bias else None) if sinks else None)
+            taken = ctx.box.deposit(gy, weight, wgrad=(rows, gw, gb) if sinks else None)
         if taken:
             grows = ctx.box.placeholder(rows.shape)
         elif ctx.needs_input_grad[0]:
@@ -290,30 +292,15 @@ class _RowLinear(torch.autograd.Function):
                 grows = gy @ cast_cached(weight._base if weight._base is not None else weight, gy.dtype).view(weight.shape)
         if taken == 2:
             return grows, None, None, None, None, None
-        # wide maps: bf16 multiples of 64 up to 256 and f32 multiples of 4 (csrc/linear_wgrad_f32.hip) have their own kernels;
-        # what is left (odd widths) goes to the library
-        if cin * cout >= 256 * 256 and not (rows.dtype == torch.bfloat16 and cin % 64 == 0 and cout % 64 == 0
-                                            and cin <= 256 and cout <= 256) and not (
-                rows.dtype == torch.float32 and cin % 4 == 0 and cout % 4 == 0 and cin <= 1024 and cout <= 1024 and R >= 2048):
+        if library:
             gw = (gy.t() @ rows).float()                # f32 square 256-wide maps: rocBLAS is ahead there
-            gb = gy.float().sum(0) if ctx.has_bias else None
+            gb = gy.float().sum(0) if bparam is not None else None
             return grows, gw.to(weight.dtype), (gb.to(weight.dtype) if gb is not None else None), None, None, None
-        gw = gw_sink if gw_sink is not None else torch.zeros((cout, cin), device=rows.device, dtype=torch.float32)
-        gb = None
-        if ctx.has_bias:
-            gb = gb_sink if gb_sink is not None else torch.zeros((cout,), device=rows.device, dtype=torch.float32)
-        record = sinks and ops.folds_deferrable()        # (decided here, inside the pass: a parked launch may go out from its end-of-pass callback)
 
-        def launch(rows=rows, gy=gy, gw=gw, gb=gb):      # (the closure keeps rows / gy alive until the kernel is issued)
+        def launch(record, rows=rows, gy=gy, gw=gw, gb=gb):      # (the closure keeps rows / gy alive until the kernel is issued)
             ops.linear_wgrad(rows, [(gy, gw, gb)], record)
-        # nothing in the backward reads a weight gradient: with both gradients going to the flat bucket the kernel is parked
-        # and issued where its stream would otherwise wait for the other one (ops.defer_wgrad)
-        if sinks:
-            ops.defer_wgrad(launch, (rows, gy))
-        else:
-            launch()
-        return (grows, None if gw_sink is not None else gw.to(weight.dtype),
-                None if (gb is None or gb_sink is not None) else gb.to(weight.dtype), None, None, None)
+        grads.run_wgrad(launch, (rows, gy), 'weight', 'bias')
+        return grows, grads.result('weight', weight.dtype), grads.result('bias', weight.dtype), None, None, None
 
 
 class PointwiseConv2d(torch.nn.Conv2d):
@@ -335,7 +322,6 @@ class PointwiseConv2d(torch.nn.Conv2d):
         weight = self.weight.view(self.out_channels, C)
         if rows.is_cuda and rows.dtype in (torch.float32, torch.bfloat16) and torch.is_grad_enabled() and (
                 weight.requires_grad or rows.requires_grad):
-            from .. import ops
             y = _RowLinear.apply(rows, weight, self.bias, bn, None, ops.fan_box(x))
         else:
             needs_grad = torch.is_grad_enabled() and (weight.requires_grad or rows.requires_grad)
@@ -368,7 +354,6 @@ class _InstNormAct(torch.autograd.Function):
         if precomputed is not None:
             return precomputed.permute(0, 3, 1, 2)
         y = torch.empty_like(rows)
-        from .. import ops
         ops.timed('instnorm_fwd_kernel', 2 * rows.numel() * rows.element_size(),
                   lambda: _hip.check(_hip.lib().fgnn_instnorm_forward(_hip._ptr(rows), _hip._ptr(y), B, N, C,
                                                                       _hip.dtype_code(rows), int(relu),
@@ -378,14 +363,12 @@ class _InstNormAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         (rows,) = ctx.saved_tensors
-        from .. import ops
         ops.backward_node_begins()
         B, N, _, C = rows.shape
         g = gy.permute(0, 2, 3, 1)
         if not g.is_contiguous() or g.dtype != rows.dtype:
             g = g.to(rows.dtype).contiguous()
         gx = torch.empty_like(rows)
-        from .. import ops
         ops.timed('instnorm_bwd_kernel', 3 * rows.numel() * rows.element_size(),
                   lambda: _hip.check(_hip.lib().fgnn_instnorm_backward(_hip._ptr(rows), _hip._ptr(g), _hip._ptr(gx), B, N,
                                                                        C, _hip.dtype_code(rows), int(ctx.relu),
@@ -406,7 +389,6 @@ class _InstNormDot(torch.autograd.Function):
             rows = rows.contiguous()
         w = weight.detach().reshape(C)
         out = torch.empty((B, 1, N, 1), device=x.device, dtype=x.dtype)
-        from .. import ops
         ops.timed('instnorm_dot_kernel<fwd>', rows.numel() * rows.element_size(), lambda: _hip.check(
             _hip.lib().fgnn_instnorm_dot_forward(_hip._ptr(rows), _hip._ptr(w), _hip._ptr(None if bias is None else bias.detach()),
                                                  _hip._ptr(out), B, N, C, _hip.dtype_code(rows), _hip.stream_ptr())))
@@ -417,7 +399,6 @@ class _InstNormDot(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         rows, weight = ctx.saved_tensors
-        from .. import ops
         ops.backward_node_begins()
         B, N, _, C = rows.shape
         L = _hip.lib()
@@ -425,19 +406,15 @@ class _InstNormDot(torch.autograd.Function):
         if not g.is_contiguous() or g.dtype != rows.dtype:
             g = g.to(rows.dtype).contiguous()
         wparam, bparam = ctx.params
-        gw_sink, gb_sink = ops.grad_sink(wparam), ops.grad_sink(bparam)
-        gw = gw_sink if gw_sink is not None else torch.zeros(wparam.shape, device=rows.device, dtype=torch.float32)
-        gb = None
-        if bparam is not None:
-            gb = gb_sink if gb_sink is not None else torch.zeros((1,), device=rows.device, dtype=torch.float32)
+        grads = ops.param_grads(rows.device)
+        gw, gb = grads.acc('weight', wparam, wparam.shape), grads.acc('bias', bparam, (1,))
         gx = torch.empty_like(rows)
         ws = ops._workspace(rows.device, int(L.fgnn_instnorm_dot_workspace_bytes(B)))
         ops.timed('instnorm_dot_kernel<bwd>', 2 * rows.numel() * rows.element_size(), lambda: _hip.check(
             L.fgnn_instnorm_dot_backward(_hip._ptr(rows), _hip._ptr(weight.detach()), _hip._ptr(g), _hip._ptr(gx), _hip._ptr(gw),
                                          _hip._ptr(gb), B, N, C, _hip.dtype_code(rows), _hip._ptr(ws), ws.numel() * 4,
                                          _hip.stream_ptr())))
-        return (gx.permute(0, 3, 1, 2), None if gw_sink is not None else gw.to(wparam.dtype),
-                None if (gb is None or gb_sink is not None) else gb.to(bparam.dtype))
+        return gx.permute(0, 3, 1, 2), grads.result('weight', wparam.dtype), grads.result('bias', None if bparam is None else bparam.dtype)
 
 
 INSTNORM_DOT = True       # (module switch: the classifier's closing pair staged when False)
@@ -458,7 +435,6 @@ def instnorm_relu_dot(x, conv):
     if not rows.is_contiguous():
         rows = rows.contiguous()
     out = torch.empty((B, 1, N, 1), device=x.device, dtype=x.dtype)
-    from .. import ops
     ops.timed('instnorm_dot_kernel<fwd>', rows.numel() * rows.element_size(), lambda: _hip.check(
         _hip.lib().fgnn_instnorm_dot_forward(_hip._ptr(rows), _hip._ptr(conv.weight.detach()),
                                              _hip._ptr(None if conv.bias is None else conv.bias.detach()),
@@ -524,7 +500,6 @@ def split_broadcast(addends):
 
 
 def period_array(periods):
-    import ctypes
     periods = (list(periods) + [1, 1, 1])[:3]
     return None if all(q == 1 for q in periods) else (ctypes.c_int32 * 3)(*periods)
 
@@ -538,7 +513,6 @@ class _BatchNormAct(torch.autograd.Function):
         front of it); ``weight`` / ``bias`` are its gamma / beta as arguments of their own, for autograd.  ``periods``: an addend
         with period m has one row per m rows of the output (a per-sample vector broadcast over the sample's m nodes).
         ``population``: rows the statistics stand for in the running variance's unbiased correction (0 = R)."""
-        from .. import ops
         L = _hip.lib()
         R, C = rows.shape
         dt = _hip.dtype_code(rows)
@@ -557,7 +531,6 @@ class _BatchNormAct(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from .. import ops
         ops.backward_node_begins()
         rows, weight, bias, stats = ctx.saved_tensors
         L = _hip.lib()
@@ -566,9 +539,8 @@ class _BatchNormAct(torch.autograd.Function):
         if gy.dtype != rows.dtype:
             gy = gy.to(rows.dtype)
         gx = torch.empty_like(rows)
-        gw_sink, gb_sink = ops.grad_sink(ctx.params[0]), ops.grad_sink(ctx.params[1])
-        gw = gw_sink if gw_sink is not None else torch.zeros(C, device=rows.device, dtype=torch.float32)
-        gb = gb_sink if gb_sink is not None else torch.zeros(C, device=rows.device, dtype=torch.float32)
+        grads = ops.param_grads(rows.device)
+        gw, gb = grads.acc('gamma', ctx.params[0], (C,)), grads.acc('beta', ctx.params[1], (C,))
         ws = ops._workspace(rows.device, int(L.fgnn_bn_workspace_bytes(R, C)))
         fold = ops._fold_scratch(rows.device)
         ops.timed('bn_backward (reduce + finalise + apply)', 5 * rows.numel() * rows.element_size(),
@@ -580,7 +552,7 @@ class _BatchNormAct(torch.autograd.Function):
         for i in range(3):
             if ctx.has_addend[i] and ctx.needs_input_grad[5 + i]:
                 ga[i] = gy if ctx.periods[i] == 1 else node_sum(gy, ctx.periods[i])
-        return (gx, None if gw_sink is not None else gw, None if gb_sink is not None else gb, None, None, *ga, None, None)
+        return (gx, grads.result('gamma'), grads.result('beta'), None, None, *ga, None, None)
 
 
 class BatchNormAct2d(torch.nn.BatchNorm2d):
@@ -613,8 +585,7 @@ class BatchNormAct2d(torch.nn.BatchNorm2d):
         B, C, H, W = x.shape
         addends = as_addends(addend)
         if len(addends) > 3:
-            from ..ops import add_n
-            addends = addends[:2] + [add_n(addends[2:])]
+            addends = addends[:2] + [ops.add_n(addends[2:])]
         # momentum=None (cumulative average) and a one-value batch in training mode (torch raises) stay with torch
         ok = (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and self.track_running_stats and
               self.affine and self.momentum is not None and (not self.training or B * H * W > 1) and

@@ -14,6 +14,8 @@ import os
 import torch
 
 from . import _hip
+from .backward_pass import PASS, ParamGrads, run_wgrad
+from .verdicts import Verdicts, remembered  # noqa: F401  (fastpath records and replays ops.Verdicts)
 
 
 class KernelTimer:
@@ -78,115 +80,17 @@ def timed(symbol, nbytes, fn, nflops=0):
         TIMER.run(symbol, nbytes, nflops, fn, use_note=False)
 
 
-# ---- deferred weight-gradient kernels -------------------------------------------------------------------------------------
-# Nothing in a backward pass READS a weight gradient: the kernels that produce them (2.6 ms of a 18.8 ms LDPC step) only have to be
-# done before the optimizer.  FactorNN's two streams spend the backward waiting for each other at every layer's joins (the
-# main stream 3.5 ms, the side stream 7 ms of a step: profiles/r03/train_step_timeline.txt), so a weight-gradient kernel that sits
-# in stream order IN FRONT of a kernel the other stream waits for is on the critical path for nothing.  With DEFER_WGRAD the
-# launches are parked per stream and issued when the autograd engine moves on to a node of ANOTHER stream — i.e. right behind the
-# stream's last critical kernel, into the slot where it would otherwise idle until the join — and at the latest when the
-# backward pass ends (an engine callback, which also joins every such stream into the caller's).  Only gradients that go to
-# a sink (ops.grad_sink: the flat bucket) are deferred: a gradient tensor handed back to autograd must be complete in stream order.
-DEFER_WGRAD = True          # (module switch: tests compare parked against inline launches)
-# (round 5 also tried the parked launches on a THIRD stream and on the side stream, each behind an event on its operands: 15.5 / 15.1
-#  against 13.8 ms — every kernel that overlaps an operator launch waits for a CU; profiles/r05/README.md.  Removed.)
-SIDE_ACTIVE = False         # set by the assemblies the first time a forward actually forks onto the side stream: with ONE stream in
-                            # play parking buys no overlap and only keeps every layer's operands alive until the end of the backward
-_DEFERRED = {}              # stream -> [(launch closure, operands)]
-_DEFER_CALLBACK = [None]     # id of the backward pass (autograd graph task) whose end-of-pass callback is queued
-_DEFER_ISSUED = set()       # streams that got parked launches issued during the current backward pass
-
-
-def defer_wgrad(launch, operands=()):
-    """Park `launch` (a closure that enqueues one weight-gradient kernel on the CURRENT stream).  `operands`: the tensors the
-    kernel reads.  They are kept alive until the kernel is issued and then marked as in use by its stream: an activation the
-    OTHER stream allocated is otherwise handed back to that stream's allocator the moment the last reference drops — the
-    engine's join with this stream happened before the parked kernel went out, so nothing else orders the reuse behind it
-    (found as three weight gradients of hyper-factor maps reading overwritten rows on hipGraph replay)."""
-    if not DEFER_WGRAD or not SIDE_ACTIVE:
-        launch()
-        return
-    st = torch.cuda.current_stream()
-    task = torch._C._current_graph_task_id()           # (-1 outside a backward pass: then nothing would ever issue the launch)
-    if task < 0:
-        launch()
-        return
-    _register_backward_callback(task)
-    _DEFERRED.setdefault(st, []).append((launch, tuple(operands)))
-
-
-def _register_backward_callback(task):
-    if _DEFER_CALLBACK[0] != task:
-        # Another backward pass than the one that parked what is in the lists: a NESTED (re-entrant) pass inside it — checkpointing,
-        # a custom Function calling backward() — or a pass that died half-way.  Either way the parked launches are ISSUED, never
-        # dropped (they accumulate into sinked .grad buffers behind autograd's back: dropping them would lose gradients silently;
-        # issuing those of a dead pass only finishes an accumulation its owner discards).  The outer pass re-registers itself
-        # with its next parked launch; its own end-of-pass callback is still queued.
-        if any(_DEFERRED.values()):
-            flush_deferred()
-        flush_folds()
-        _DEFER_CALLBACK[0] = task
-        torch.autograd.Variable._execution_engine.queue_callback(_flush_at_end_of_backward)
-
-
-# ---- recorded parameter-gradient folds -------------------------------------------------------------------------------------------
-# Every weight / filter gradient kernel leaves per-workgroup slabs that a small launch folds into the accumulator: ~100 launches of
-# 5-15 us per LDPC step, a third of them in the main stream's dependent chain (csrc/fold_batch.hip).  When the gradient goes to a
-# sink (ops.grad_sink: nothing in the pass reads it) the fold is RECORDED instead — the call gets a slab buffer of its own, kept
-# alive here — and ONE launch at the end of the pass folds them all (a fixed summation order of its own: reproducible, equal to the
-# immediate folds' sums to f32 rounding).
-DEFER_FOLDS = True          # (module switch: tests compare recorded against immediate folds)
-_FOLD_KEEP = []
-
-
-def folds_deferrable():
-    """True inside a backward pass whose end this module gets to see (the engine callback that flushes the recorded folds)."""
-    if not DEFER_FOLDS:
-        return False
-    task = torch._C._current_graph_task_id()
-    if task < 0:
-        return False
-    _register_backward_callback(task)
-    return True
-
-
-class fold_scope:
-    """``with fold_scope(defer):`` — the gradient entry points called inside record their slab folds (csrc/fold_batch.hip) when
-    ``defer``; ``slabs(device, nbytes)`` is the workspace to hand them: a private buffer (alive until the flush) then, else the
-    stream's shared scratch."""
-
-    def __init__(self, defer):
-        self.defer = bool(defer)
-
-    def slabs(self, device, nbytes):
-        if not self.defer:
-            return _workspace(device, nbytes)
-        t = torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
-        _FOLD_KEEP.append(t)
-        return t
-
-    def __enter__(self):
-        if self.defer:
-            _hip.lib().fgnn_fold_defer(1)
-        return self
-
-    def __exit__(self, *exc):
-        if self.defer:
-            _hip.lib().fgnn_fold_defer(0)
-        return False
-
-
 def linear_wgrad(rows, jobs, record):
     """gW += gy^T rows and gb += the column sums of gy (gb may be None) for every job (gy [R, K], gW [K, C] f32, gb [K] f32) of
     node-wise maps that read the same rows [R, C]: ONE csrc/linear_wgrad_b16.hip launch over several jobs when its merged form takes
     them (``fgnn_linear_wgrad_multi``: the rows are read once), else one ``fgnn_linear_wgrad`` launch per job.  ``record``: the
-    slab folds are recorded (fold_scope)."""
+    slab folds are recorded (backward_pass.PASS.fold_scope)."""
     L = _hip.lib()
     P = _hip._ptr
     R, C = rows.shape
     symbol = 'linear_wgrad_b16_kernel' if rows.dtype == torch.bfloat16 else 'linear_wgrad_kernel'
     couts = (ctypes.c_int32 * len(jobs))(*[gy.shape[1] for gy, _, _ in jobs])
-    with fold_scope(record) as scope:
+    with PASS.fold_scope(record, _workspace) as scope:
         nb = int(L.fgnn_linear_wgrad_multi_workspace_bytes(R, C, len(jobs), couts)) if len(jobs) > 1 else -1
         if nb > 0:
             ws = scope.slabs(rows.device, nb)
@@ -204,86 +108,21 @@ def linear_wgrad(rows, jobs, record):
                                                          _hip.stream_ptr())), nflops=2 * R * C * K)
 
 
-def flush_folds():
-    """Fold everything recorded, on the current stream (the caller has ordered it behind every producer)."""
-    L = _hip.lib()
-    if L.fgnn_fold_pending():
-        _hip.check(L.fgnn_fold_flush(_hip.stream_ptr()))
-        cur = torch.cuda.current_stream()
-        for t in _FOLD_KEEP:            # slabs another stream allocated are read by this stream's launch: not that stream's to reuse yet
-            t.record_stream(cur)
-    _FOLD_KEEP.clear()
-
-
-def flush_deferred(except_stream=None):
-    """Issue the parked launches of every stream but `except_stream`, each on its own stream."""
-    for st, lst in _DEFERRED.items():
-        if not lst or st == except_stream:
-            continue
-        with torch.cuda.stream(st):
-            for fn, operands in lst:
-                fn()
-                for t in operands:
-                    t.record_stream(st)
-        lst.clear()
-        _DEFER_ISSUED.add(st)
-
-
-def _flush_at_end_of_backward():
-    _DEFER_CALLBACK[0] = None
-    flush_deferred()
-    cur = torch.cuda.current_stream()
-    for st in _DEFER_ISSUED:    # the engine joined its streams BEFORE this callback: what was issued since needs its own join
-        if st != cur:
-            cur.wait_stream(st)
-    flush_folds()               # every producer is now in front of the current stream: one launch folds all their slabs
-    _DEFER_ISSUED.clear()
-
-
 def backward_node_begins():
-    """Called at the top of every hand-written backward: the engine has moved to a node on the current stream, so the other
-    streams' parked weight-gradient launches go out now (behind their last critical kernel)."""
+    """Called at the top of every hand-written backward (``backward_pass.PASS.node_begins``)."""
     if STAMPS is not None:
         import sys
         f = sys._getframe(1)
         cur = torch.cuda.current_stream()
         stamp('bwd %s %s:%d' % ('side' if (SIDE_STREAM and cur == side_stream(cur.device)) else 'main',
                                 f.f_code.co_filename.rsplit('/', 1)[-1], f.f_lineno))
-    if _DEFER_CALLBACK[0] is not None and _DEFER_CALLBACK[0] == torch._C._current_graph_task_id():
-        flush_deferred(except_stream=torch.cuda.current_stream())
-
-
-TAIL_TO_SIDE = True         # see backward_tail_begins (module switch for the A/B in tools/ and the tests)
+    PASS.node_begins()
 
 
 def backward_tail_begins():
-    """Called by a backward node behind which the pass is ONE dependent chain on the current stream — the edge-type MLPs' backward,
-    which needs the edge-weight gradients of all eight layers (/root/reference/train_ldpc.py:68-69: `emodel_*` feed every layer).
-    What is parked for the end of the pass — this stream's weight-gradient launches and every recorded parameter-gradient fold —
-    used to run BEHIND that chain, alone on the chip (0.3 ms of a 13 ms step: profiles/r06/README.md); it goes to the side stream
-    NOW, behind an event on this stream, and runs beside the chain.  The end-of-pass callback joins the side stream as before."""
-    if not (TAIL_TO_SIDE and SIDE_ACTIVE and _DEFER_CALLBACK[0] is not None
-            and _DEFER_CALLBACK[0] == torch._C._current_graph_task_id()):
-        return
-    cur = torch.cuda.current_stream()
-    side = side_stream(cur.device)
-    if side == cur:
-        return
-    flush_deferred(except_stream=cur)            # (the other streams' parked launches go out on their own streams, as at any node)
-    mine = _DEFERRED.get(cur) or []
-    if not mine and not _hip.lib().fgnn_fold_pending():
-        return
-    ready = torch.cuda.Event()
-    ready.record(cur)
-    with torch.cuda.stream(side):
-        side.wait_event(ready)
-        for fn, operands in mine:
-            fn()
-            for t in operands:
-                t.record_stream(side)
-        mine.clear()
-        flush_folds()       # every producer recorded so far is in front of `ready` on this stream or earlier on the side stream
-    _DEFER_ISSUED.add(side)
+    """Called by a backward node behind which the pass is one dependent chain on the current stream: what waits for the end of the
+    pass goes to the side stream now (``backward_pass.PASS.tail_begins``)."""
+    PASS.tail_begins(side_stream)
 
 
 def _require_device(*tensors):
@@ -335,83 +174,14 @@ def _check_index_range(nn_idx, N):
     """Debug aid (FGNN_CHECK_INDICES=1): the kernels CLAMP neighbour ids into [0, N) so that a bad table can never
     fault; the reference's ``torch.gather`` raises instead (CPU) or device-asserts (CUDA).  With the check on, an
     out-of-range table raises IndexError here — one device reduction + host sync per distinct table, remembered on the
-    tensor that owns the memory (same scheme as blocks._is_identity_list)."""
-    owner = nn_idx._base if nn_idx._base is not None else nn_idx
-    key = (nn_idx._version, nn_idx.storage_offset(), tuple(nn_idx.shape), tuple(nn_idx.stride()), N)
-    memo = getattr(owner, '_fgnn_index_range', None)
-    if memo is None or memo[0] != key:
-        lo, hi = (int(v) for v in torch.aminmax(nn_idx)) if nn_idx.numel() else (0, 0)
-        memo = (key, lo, hi)
-        owner._fgnn_index_range = memo
-    if memo[1] < 0 or memo[2] >= N:
-        raise IndexError('nn_idx holds neighbour ids in [%d, %d] but x has %d nodes' % (memo[1], memo[2], N))
+    tensor that owns the memory (verdicts.remembered)."""
+    lo, hi = remembered(nn_idx, '_fgnn_index_range', (nn_idx.storage_offset(), N),
+                        lambda: tuple(int(v) for v in torch.aminmax(nn_idx)) if nn_idx.numel() else (0, 0))
+    if lo < 0 or hi >= N:
+        raise IndexError('nn_idx holds neighbour ids in [%d, %d] but x has %d nodes' % (lo, hi, N))
 
 
 DEDUPE_GRAPHS = True     # recognise batch-identical neighbour tables passed as B copies (the reference's calling convention)
-
-
-class Verdicts:
-    """The host-side verdicts of one forward (is this table shared by the batch?  an identity list?  its in-degree?  are these
-    edge weights equal over the nodes?) in call order, so that a hipGraph capture of the SAME forward can take the fast paths for
-    tensors it meets for the first time — tensors the model builds inside its forward (the reference's
-    ``self.hnn_idx_f2v.repeat(bsize, 1, 1)``, /root/reference/train_ldpc.py:77-84) — where no host read is possible.
-
-    ``with Verdicts.recording() as v:`` around an EAGER run notes every device check + host read; ``with v.replaying():`` around the
-    capture hands them back in the same order, each only to a tensor of the same site, shape, strides and dtype (anything else:
-    the conservative answer, as before).  Sound when the capture runs the same module on the same inputs in the same state — the
-    tensors checked are functions of the integer inputs and of frozen parameters only; fastpath.GraphedForward re-validates both
-    before every replay."""
-    current = None
-
-    def __init__(self):
-        self.fifo = {}
-        self.mode = None
-        self.taken = 0          # verdicts handed to a capture
-
-    @staticmethod
-    def _sig(t):
-        return (tuple(t.shape), tuple(t.stride()), t.dtype)
-
-    @classmethod
-    def note(cls, site, t, value):
-        v = cls.current
-        if v is not None and v.mode == 'record':
-            v.fifo.setdefault(site, []).append((cls._sig(t), value))
-        return value
-
-    @classmethod
-    def recall(cls, site, t):
-        """The recorded verdict for the next check at ``site`` (None: nothing recorded / another tensor geometry)."""
-        v = cls.current
-        if v is None or v.mode != 'replay':
-            return None
-        q = v.fifo.get(site)
-        if not q or q[0][0] != cls._sig(t):
-            return None
-        v.taken += 1
-        return q.pop(0)[1]
-
-    class _Mode:
-        def __init__(self, v, mode):
-            self.v, self.mode = v, mode
-
-        def __enter__(self):
-            self.prev = Verdicts.current
-            self.v.mode = self.mode
-            Verdicts.current = self.v
-            return self.v
-
-        def __exit__(self, *exc):
-            Verdicts.current = self.prev
-            self.v.mode = None
-            return False
-
-    @classmethod
-    def recording(cls):
-        return cls._Mode(cls(), 'record')
-
-    def replaying(self):
-        return Verdicts._Mode(self, 'replay')
 
 
 def shared_graph_view(nn_idx):
@@ -425,19 +195,9 @@ def shared_graph_view(nn_idx):
     B = nn_idx.shape[0]
     if not DEDUPE_GRAPHS or B <= 1 or nn_idx.stride(0) == 0 or not nn_idx.is_cuda:
         return nn_idx
-    owner = nn_idx._base if nn_idx._base is not None else nn_idx
-    key = (nn_idx._version, nn_idx.data_ptr(), tuple(nn_idx.shape), tuple(nn_idx.stride()))
-    memo = getattr(owner, '_fgnn_shared_graph', None)
-    if memo is None or memo[0] != key:
-        if torch.cuda.is_current_stream_capturing():
-            v = Verdicts.recall('shared_graph', nn_idx)
-            if v is None:
-                return nn_idx
-            memo = (key, v)
-        else:
-            memo = (key, Verdicts.note('shared_graph', nn_idx, bool((nn_idx == nn_idx[:1]).all().item())))
-        owner._fgnn_shared_graph = memo
-    return nn_idx[:1].expand(B, -1, -1) if memo[1] else nn_idx
+    shared = remembered(nn_idx, '_fgnn_shared_graph', (nn_idx.data_ptr(),), lambda: bool((nn_idx == nn_idx[:1]).all().item()),
+                        site='shared_graph', during_capture=False)
+    return nn_idx[:1].expand(B, -1, -1) if shared else nn_idx
 
 
 def is_identity_list(nn_idx):
@@ -445,21 +205,9 @@ def is_identity_list(nn_idx):
     once per table; the verdict is remembered ON the tensor that owns the memory (the view's base, e.g. LDPCModel's frozen
     `hnn_idx_v2f` behind its per-call `expand`), keyed by version and view geometry, so it can never outlive or be confused with
     another table.  While a hipGraph is being captured no host read is possible: an unseen table is then taken as general."""
-    owner = nn_idx._base if nn_idx._base is not None else nn_idx
-    key = (nn_idx._version, nn_idx.storage_offset(), tuple(nn_idx.shape), tuple(nn_idx.stride()))
-    memo = getattr(owner, '_fgnn_identity_list', None)
-    if memo is None or memo[0] != key:
-        if nn_idx.is_cuda and torch.cuda.is_current_stream_capturing():
-            hit = Verdicts.recall('identity_list', nn_idx)
-            if hit is None:
-                return False
-        else:
-            k = nn_idx.shape[-1]
-            hit = Verdicts.note('identity_list', nn_idx, bool(
-                (nn_idx == torch.arange(k, device=nn_idx.device, dtype=nn_idx.dtype)).all().item()))
-        memo = (key, hit)
-        owner._fgnn_identity_list = memo
-    return memo[1]
+    return remembered(nn_idx, '_fgnn_identity_list', (nn_idx.storage_offset(),), lambda: bool(
+        (nn_idx == torch.arange(nn_idx.shape[-1], device=nn_idx.device, dtype=nn_idx.dtype)).all().item()),
+        site='identity_list', during_capture=False)
 
 
 def max_in_degree(nn_idx, N):
@@ -471,20 +219,10 @@ def max_in_degree(nn_idx, N):
     the call to the first-generation kernels."""
     if nn_idx.shape[0] > 1 and nn_idx.stride(0) != 0:
         return 0
-    owner = nn_idx._base if nn_idx._base is not None else nn_idx
-    key = (nn_idx._version, nn_idx.data_ptr(), tuple(nn_idx.shape), tuple(nn_idx.stride()), N)
-    memo = getattr(owner, '_fgnn_in_degree', None)
-    if memo is None or memo[0] != key:
-        if torch.cuda.is_current_stream_capturing():
-            deg = Verdicts.recall('in_degree', nn_idx)
-            if deg is None:
-                return 0
-            memo = (key, deg)
-        else:
-            flat = nn_idx[0].reshape(-1).clamp(0, N - 1)
-            memo = (key, Verdicts.note('in_degree', nn_idx, int(torch.bincount(flat, minlength=N).max().item()) if flat.numel() else 0))
-        owner._fgnn_in_degree = memo
-    return memo[1]
+    def measure():
+        flat = nn_idx[0].reshape(-1).clamp(0, N - 1)
+        return int(torch.bincount(flat, minlength=N).max().item()) if flat.numel() else 0
+    return remembered(nn_idx, '_fgnn_in_degree', (nn_idx.data_ptr(), N), measure, site='in_degree', during_capture=0)
 
 
 # Off by default: measured on MI355X (gpurun_out/r05c, 4096 codewords) the pre-built tables change nothing — stand-alone 90.3 / 79.9 us
@@ -506,22 +244,17 @@ def backward_tables(nn_idx, d):
     nbytes = int(L.fgnn_mpconv_backward_tables_bytes(ctypes.byref(d)))
     if nbytes == 0:
         return None
-    owner = nn_idx._base if nn_idx._base is not None else nn_idx
-    key = (nn_idx._version, nn_idx.data_ptr(), tuple(nn_idx.shape), tuple(nn_idx.stride()), d.N, d.M, d.k, d.reserved & 0xffff)
-    memo = getattr(owner, '_fgnn_bwd_tables', None)
-    if memo is None or memo[0] != key:
-        if torch.cuda.is_current_stream_capturing():
-            return None          # (a first sight during capture: the launch would be recorded and its buffer owned by the graph's pool)
+    def build():
         t = torch.empty(nbytes // 4, device=nn_idx.device, dtype=torch.int32)
         rc = L.fgnn_mpconv_backward_tables(ctypes.byref(d), _hip._ptr(nn_idx), _hip._ptr(t), _hip.stream_ptr())
         if rc == _hip.EUNSUPPORTED:
-            t = None             # (an in-degree beyond the table-driven kernel's slots: the call goes to another kernel anyway)
-        else:
-            _hip.check(rc)
-            torch.cuda.current_stream(nn_idx.device).synchronize()      # other streams will read it
-        memo = (key, t)
-        owner._fgnn_bwd_tables = memo
-    return memo[1]
+            return None          # (an in-degree beyond the table-driven kernel's slots: the call goes to another kernel anyway)
+        _hip.check(rc)
+        torch.cuda.current_stream(nn_idx.device).synchronize()      # other streams will read it
+        return t
+    # (no site: a first sight during capture is never answered from a recording — the launch would be recorded and its buffer owned
+    # by the graph's pool)
+    return remembered(nn_idx, '_fgnn_bwd_tables', (nn_idx.data_ptr(), d.N, d.M, d.k, d.reserved & 0xffff), build, during_capture=None)
 
 
 def mpconv_forward_raw(x, nn_idx, etype, filters, bias, nou, net, ext, agg, *,
@@ -604,6 +337,11 @@ def grad_sink(param):
             or g.shape != param.shape or g.requires_grad):
         return None
     return g
+
+
+def param_grads(device):
+    """The gradient accumulators of one backward node (``backward_pass.ParamGrads`` over ``grad_sink``)."""
+    return ParamGrads(device, grad_sink)
 
 
 def enable_grad_sink(params, on=True):
@@ -702,7 +440,6 @@ class _MPConv(torch.autograd.Function):
         if ROUTE_TAP is not None:
             ROUTE_TAP(filters, amax)
         ctx.cfg = (nou, net, ext, agg)
-        ctx.has_bias = bias is not None
         ctx.params = (filters, bias)                     # the leaf tensors themselves (for grad_sink)
         ctx.save_for_backward(x, nn_idx, etype, filters, amax)
         return z
@@ -724,12 +461,9 @@ class _MPConv(torch.autograd.Function):
         gx = torch.empty_like(xx)                        # preserve_format keeps xx's strides
         want_get = ctx.needs_input_grad[2]
         get = torch.empty((B, net, M, k), device=x.device, dtype=etype.dtype) if want_get else None
-        fparam, bparam = ctx.params
-        gw_sink, gb_sink = grad_sink(fparam), grad_sink(bparam)
-        gw = gw_sink if gw_sink is not None else torch.zeros(filters.shape, device=x.device, dtype=torch.float32)
-        gb = None
-        if ctx.has_bias:
-            gb = gb_sink if gb_sink is not None else torch.zeros((nou,), device=x.device, dtype=torch.float32)
+        grads = param_grads(x.device)
+        gw = grads.acc('filters', ctx.params[0], filters.shape)
+        gb = grads.acc('bias', ctx.params[1], (nou,))
         w = filters.detach().float().contiguous()
         d = _hip.make_desc(xx, nn_idx, etype, nou, net, ext, agg, False, gz)
         d.reserved = max_in_degree(nn_idx, x.shape[2])
@@ -738,7 +472,8 @@ class _MPConv(torch.autograd.Function):
         if reduced:
             d.reserved |= _hip.DESC_GETYPE_REDUCED
             get = torch.empty((1, net, M, k), device=x.device, dtype=torch.float32)
-        scope = fold_scope(gw_sink is not None and (gb is None or gb_sink is not None) and folds_deferrable())
+        # (the operator's backward is never parked; its folds are recorded when both of its parameter gradients go to sinks)
+        scope = PASS.fold_scope(grads.all_sunk('filters', 'bias') and PASS.folds_deferrable(), _workspace)
         ws = scope.slabs(x.device, int(L.fgnn_mpconv_backward_workspace_bytes(ctypes.byref(d))))
         nbytes = 0
         if TIMER is not None:
@@ -761,8 +496,7 @@ class _MPConv(torch.autograd.Function):
             get = get.sum(dim=0, keepdim=True)
         if want_get and get.dtype != etype.dtype:
             get = get.to(etype.dtype)
-        return (gx, None, get, None if gw_sink is not None else gw.to(filters.dtype),
-                None if gb_sink is not None else gb, None, None, None, None, None)
+        return (gx, None, get, grads.result('filters', filters.dtype), grads.result('bias'), None, None, None, None, None)
 
 
 def _unexpanded(etype):
@@ -833,8 +567,8 @@ def single_source_fanout(x, nn_idx, etype):
     [B, M, 1], etype [B, net, M, 1] equal for all m — so that every destination receives the same message and the operator's
     output is a per-sample vector broadcast over the nodes (the LDPC hyper-factor's call, /root/reference/train_ldpc.py:40-46,82-88:
     `hnn_idx_f2v` == 0, `hetype_f2v` == 1); else 0.  Equality of the edge weights over the nodes is read from a stride-0 node axis,
-    or checked on the device once per tensor WITHOUT a gradient (remembered on the tensor that owns the memory, as
-    blocks._is_identity_list; never while a hipGraph is being captured: an unseen tensor is then taken as general)."""
+    or checked on the device once per tensor WITHOUT a gradient (remembered on the tensor that owns the memory,
+    verdicts.remembered; never while a hipGraph is being captured: an unseen tensor is then taken as general)."""
     if not FANOUT_BROADCAST or x.dim() != 4 or x.shape[2] != 1 or x.shape[3] != 1 or nn_idx.dim() != 3:
         return 0
     B, M, k = nn_idx.shape
@@ -844,19 +578,9 @@ def single_source_fanout(x, nn_idx, etype):
         return M
     if etype.requires_grad:
         return 0
-    owner = etype._base if etype._base is not None else etype
-    key = (etype._version, etype.data_ptr(), tuple(etype.shape), tuple(etype.stride()))
-    memo = getattr(owner, '_fgnn_node_invariant', None)
-    if memo is None or memo[0] != key:
-        if torch.cuda.is_current_stream_capturing():
-            v = Verdicts.recall('node_invariant', etype)
-            if v is None:
-                return 0
-            memo = (key, v)
-        else:
-            memo = (key, Verdicts.note('node_invariant', etype, bool((etype == etype[:, :, :1, :]).all().item())))
-        owner._fgnn_node_invariant = memo
-    return M if memo[1] else 0
+    same = remembered(etype, '_fgnn_node_invariant', (etype.data_ptr(),), lambda: bool((etype == etype[:, :, :1, :]).all().item()),
+                      site='node_invariant', during_capture=False)
+    return M if same else 0
 
 
 FANOUT_BROADCAST = True     # (module switch: tests compare against the materialised rows)
@@ -1025,8 +749,7 @@ class FanBox:
     def _park_wgrad_group(self, jobs):
         rows = jobs[0][1][0]
         wjobs = [(gz, gW, gb) for gz, (_, gW, gb) in jobs]
-        record = folds_deferrable()          # (decided inside the pass: the parked launch may go out from its end-of-pass callback)
-        defer_wgrad(lambda: linear_wgrad(rows, wjobs, record), (rows,) + tuple(j[0] for j in wjobs))
+        run_wgrad(lambda record: linear_wgrad(rows, wjobs, record), (rows,) + tuple(j[0] for j in wjobs), sunk=True)
 
     def merge(self, grads):
         """The state's gradient from the deposits + the gradients that arrived as tensors."""

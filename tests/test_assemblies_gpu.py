@@ -894,12 +894,12 @@ def test_one_kernel_factor_layer_vs_per_block_path_and_oracle(B, hyper_weights, 
 
 
 def test_parked_weight_gradients_equal_inline_ones_bitwise(dev, monkeypatch):
-    """ops.defer_wgrad parks the weight-gradient kernels of a backward pass and issues them where their stream would wait for
+    """backward_pass.PASS.park parks the weight-gradient kernels of a backward pass and issues them where their stream would wait for
     the other one (at the latest from an engine callback when the pass ends).  Same kernels, same operands, another place in
     stream order: the flat gradient must come out bit-identical to the inline schedule — eagerly, twice, and with the addends'
     gradient routed through its own node or through the fused tail's backward."""
     import fgnn_amd
-    from fgnn_amd import ops
+    from fgnn_amd import backward_pass
     from fgnn_amd.dp import FlatGradBucket
     from fgnn_amd.ldpc import synthetic_batch
     from fgnn_amd.mpnn import blocks
@@ -916,13 +916,13 @@ def test_parked_weight_gradients_equal_inline_ones_bitwise(dev, monkeypatch):
             logits, snr = m(*data[:6])
         (torch.nn.functional.binary_cross_entropy_with_logits(logits.float(), data[6]) + 0.1 * snr.float().pow(2).mean()).backward()
         torch.cuda.synchronize()
-        assert not any(lst for lst in ops._DEFERRED.values())                  # nothing is left parked after a backward pass
+        assert not backward_pass.PASS.parked()                  # nothing is left parked after a backward pass
         return bucket.flat.clone()
 
-    monkeypatch.setattr(ops, 'DEFER_WGRAD', False)
+    monkeypatch.setattr(backward_pass, 'DEFER_WGRAD', False)
     inline = grads()
     assert float(inline.abs().max()) > 0
-    monkeypatch.setattr(ops, 'DEFER_WGRAD', True)
+    monkeypatch.setattr(backward_pass, 'DEFER_WGRAD', True)
     assert torch.equal(grads(), inline) and torch.equal(grads(), inline)
     monkeypatch.setattr(blocks, 'ROUTE_ADDEND_GRADS', False)
     assert torch.equal(grads(), inline)
@@ -936,7 +936,7 @@ def test_parked_launches_of_a_failed_backward_pass_are_dropped(dev, monkeypatch)
     pass's sums (FlatGradBucket.zero issues it ahead of the zeroing; a pass of another id arriving first would issue it too —
     parked launches are never silently dropped, a nested pass relies on that) nor keep that pass from queueing its own callback."""
     import fgnn_amd
-    from fgnn_amd import ops
+    from fgnn_amd import backward_pass
     from fgnn_amd.dp import FlatGradBucket
     from fgnn_amd.mpnn.pointwise import PointwiseConv2d
 
@@ -950,7 +950,7 @@ def test_parked_launches_of_a_failed_backward_pass_are_dropped(dev, monkeypatch)
             raise RuntimeError('boom')
 
     torch.manual_seed(3)
-    monkeypatch.setattr(ops, 'SIDE_ACTIVE', True)       # parking is only on while an assembly runs its side stream
+    monkeypatch.setattr(backward_pass.PASS, 'side_active', True)       # parking is only on while an assembly runs its side stream
     a, b = PointwiseConv2d(64, 64).to(dev), PointwiseConv2d(64, 64).to(dev)
     bucket = FlatGradBucket(list(a.parameters()) + list(b.parameters()))
     x = torch.randn(8, 64, 96, 1, device=dev).bfloat16().contiguous(memory_format=torch.channels_last)
@@ -969,16 +969,16 @@ def test_parked_launches_of_a_failed_backward_pass_are_dropped(dev, monkeypatch)
     good = run(False)
     with pytest.raises(RuntimeError, match='boom'):
         run(True)                                       # b's weight gradient was parked, then the pass died
-    assert any(lst for lst in ops._DEFERRED.values())
+    assert backward_pass.PASS.parked()
     again = run(False)
     assert torch.equal(again, good)                     # not doubled by the stale launch, and a's / b's own gradients are there
-    assert not any(lst for lst in ops._DEFERRED.values())
+    assert not backward_pass.PASS.parked()
 
 
 def test_a_nested_backward_pass_does_not_lose_parked_launches(dev, monkeypatch):
     """a re-entrant backward (checkpointing, a Function that calls backward()) has another graph-task id than the pass
     that parked weight-gradient launches; those must be ISSUED, not cleared.  Gradients with parking on == with parking off."""
-    from fgnn_amd import ops
+    from fgnn_amd import backward_pass
     from fgnn_amd.dp import FlatGradBucket
     from fgnn_amd.mpnn.pointwise import PointwiseConv2d
     torch.manual_seed(4)
@@ -1008,9 +1008,9 @@ def test_a_nested_backward_pass_does_not_lose_parked_launches(dev, monkeypatch):
         return bucket.flat.clone()
 
     plain = run()
-    monkeypatch.setattr(ops, 'SIDE_ACTIVE', True)
+    monkeypatch.setattr(backward_pass.PASS, 'side_active', True)
     parked = run()
-    assert not any(lst for lst in ops._DEFERRED.values())
+    assert not backward_pass.PASS.parked()
     assert float(plain.abs().max()) > 0 and torch.equal(parked, plain)
 
 
@@ -1020,7 +1020,7 @@ def test_recorded_gradient_folds_equal_immediate_ones(dev):
     gradients of the folds launched one by one up to the f32 rounding of a different (fixed) summation order, bit-reproducible run to
     run; nothing stays recorded, and a second pass accumulates on top (two folds into the same accumulators: separate launches)."""
     import fgnn_amd
-    from fgnn_amd import _hip, ops
+    from fgnn_amd import _hip, backward_pass
     from fgnn_amd.dp import FlatGradBucket
     from fgnn_amd.ldpc import synthetic_batch
     torch.manual_seed(3)
@@ -1032,15 +1032,15 @@ def test_recorded_gradient_folds_equal_immediate_ones(dev):
     def grads(defer, passes=1):
         m.load_state_dict(state)
         bucket.zero()
-        ops.DEFER_FOLDS = defer
+        backward_pass.DEFER_FOLDS = defer
         try:
             for _ in range(passes):
                 with torch.autocast('cuda', dtype=torch.bfloat16):
                     logits, snr = m(*data[:6])
                 (torch.nn.functional.binary_cross_entropy_with_logits(logits.float(), data[6]) + 0.1 * snr.float().pow(2).mean()).backward()
-                assert _hip.lib().fgnn_fold_pending() == 0 and not ops._FOLD_KEEP
+                assert _hip.lib().fgnn_fold_pending() == 0 and not backward_pass.PASS.folds_kept()
         finally:
-            ops.DEFER_FOLDS = True
+            backward_pass.DEFER_FOLDS = True
         torch.cuda.synchronize()
         return bucket.flat.clone()
 
