@@ -105,3 +105,21 @@ __device__ __forceinline__ float fgnn_bcast(float v, int lane) {
 __device__ __forceinline__ float fgnn_dot2(unsigned p, unsigned e, float acc) {
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, p), __builtin_bit_cast(bf16x2, e), acc, false);
 }
+
+// ---- the synthetic-PGM labelling head (pgm_eval.hip, pgm_loss.hip): one read and one decision rule for both ----
+// the two logits of one variable, o = b * sb + i * vs its class-0 element and cs the class stride; DK = FGNN_PGM_DEC_F32 / _BF16
+template <int DK> __device__ __forceinline__ void fgnn_pgm_logits(const void* dec, int64_t o, int64_t cs, float& v0, float& v1) {
+    if (DK == FGNN_PGM_DEC_F32) {
+        const float* d = static_cast<const float*>(dec);
+        v0 = d[o]; v1 = d[o + cs];
+    } else {
+        const bf16_t* d = static_cast<const bf16_t*>(dec);
+        v0 = fgnn_ld(d + o); v1 = fgnn_ld(d + o + cs);
+    }
+}
+// variable i's label of sample b (int64, variables contiguous, sb between samples)
+__device__ __forceinline__ int64_t fgnn_pgm_label(const int64_t* label, int64_t b, int64_t sb, int i) { return label[b * sb + i]; }
+// torch.argmax over (v0, v1): the first maximum, NaN above everything (a NaN v0 keeps 0)
+__device__ __forceinline__ int fgnn_pgm_decide(float v0, float v1) {
+    return v1 > v0 || (__builtin_isnan(v1) && !__builtin_isnan(v0));
+}

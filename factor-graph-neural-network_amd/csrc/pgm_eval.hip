@@ -63,16 +63,9 @@ __global__ __launch_bounds__(PS_THREADS) void chain_budget_score_kernel(const Ps
             int64_t xv = 0, lab = 0;
             if (on) {
                 const int64_t o = b * p.d_sb + i * p.d_vs;
-                if (DK == FGNN_PGM_DEC_F32) {
-                    const float* d = static_cast<const float*>(p.dec);
-                    v0 = d[o]; v1 = d[o + p.d_cs];
-                } else if (DK == FGNN_PGM_DEC_BF16) {
-                    const bf16_t* d = static_cast<const bf16_t*>(p.dec);
-                    v0 = fgnn_ld(d + o); v1 = fgnn_ld(d + o + p.d_cs);
-                } else {
-                    xv = static_cast<const int64_t*>(p.dec)[o];
-                }
-                lab = p.label[b * p.l_sb + i];
+                if (DK == FGNN_PGM_DEC_I64) xv = static_cast<const int64_t*>(p.dec)[o];
+                else fgnn_pgm_logits<DK>(p.dec, o, p.d_cs, v0, v1);
+                lab = fgnn_pgm_label(p.label, b, p.l_sb, i);
                 const float* u = p.unary + b * p.u_sb + 2 * i;
                 u0 = u[0]; u1 = u[1];
                 if (i > 0) {
@@ -84,8 +77,7 @@ __global__ __launch_bounds__(PS_THREADS) void chain_budget_score_kernel(const Ps
             if (DK == FGNN_PGM_DEC_I64) {
                 x = xv != 0;
             } else {
-                // torch.argmax over (v0, v1): the first maximum, NaN above everything (a NaN v0 keeps 0)
-                x = v1 > v0 || (__builtin_isnan(v1) && !__builtin_isnan(v0));
+                x = fgnn_pgm_decide(v0, v1);
                 const double a = v0, c = v1, mx = a > c ? a : c;
                 const double lse = mx + log1p(exp(-fabs(a - c)));
                 if (on) nl += lse - (lab != 0 ? c : a);

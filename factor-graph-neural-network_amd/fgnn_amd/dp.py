@@ -192,11 +192,16 @@ class FlatAdam:
     parameter tensors.  In-place updates of the flat buffer do not bump the per-parameter version counters,
     so the step also invalidates this package's cached low-precision weight copies."""
 
-    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
+    def __init__(self, bucket, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False, max_grad_norm=None):
         """``capturable=True`` (ROCm device only): the step count and the learning rate live in device memory
         (``fgnn_flat_adam_dev``), so ``step`` has no step-dependent launch argument and can be recorded into a hipGraph —
         with the gradient all-reduce in front of it — and replayed.  Assigning ``opt.lr`` between replays still works (it
-        writes the device scalar); ``opt.t`` reads the device counter back (a synchronisation)."""
+        writes the device scalar); ``opt.t`` reads the device counter back (a synchronisation).
+
+        ``max_grad_norm`` (``torch.nn.utils.clip_grad_norm_``'s max_norm): ``step`` first measures the gradient's total norm
+        (``fgnn_grad_norm_clip``: two short launches, f64 sums, the result stays in device memory) and the update multiplies the clip
+        coefficient min(1, max_norm / (norm + 1e-6)) in as it reads the gradient — no pass rewrites the gradient buffer, no host read,
+        and it holds in the capturable form too.  ``opt.grad_norm`` is the [1] tensor of the last step's pre-clip norm."""
         if bucket.flat_param is None:
             raise ValueError('FlatAdam needs FlatGradBucket(..., flatten_params=True)')
         self.bucket = bucket
@@ -213,6 +218,29 @@ class FlatAdam:
         self.exp_avg = torch.zeros_like(bucket.flat_param)
         self.exp_avg_sq = torch.zeros_like(bucket.flat_param)
         self._t = 0
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._norm = None                        # [2] f32: {the last pre-clip norm, the clip coefficient}
+        if self.max_grad_norm is not None:
+            self._norm = torch.zeros(2, device=bucket.flat_param.device, dtype=torch.float32)
+            self._norm[1] = 1.0
+            if bucket.flat_param.is_cuda:        # a workspace of its own: a captured step holds its address
+                from . import _hip
+                self._norm_ws = torch.empty(int(_hip.lib().fgnn_grad_norm_clip_workspace_bytes()) // 8,
+                                            device=bucket.flat_param.device, dtype=torch.float64)
+
+    @property
+    def grad_norm(self):
+        """The total norm of the gradient the last ``step`` saw, before clipping ([1] f32 on the parameters' device; reading it
+        here does not synchronise).  None without ``max_grad_norm``."""
+        return None if self._norm is None else self._norm[:1]
+
+    def _measure(self, g, grad_scale):
+        """The norm launches in front of a clipped update; returns the device pointer of the coefficient."""
+        from . import _hip
+        P = _hip._ptr
+        _hip.check(_hip.lib().fgnn_grad_norm_clip(P(g), g.numel(), self.max_grad_norm, float(grad_scale), P(self._norm),
+                                                  P(self._norm_ws), self._norm_ws.numel() * 8, _hip.stream_ptr()))
+        return P(self._norm[1:])
 
     @property
     def lr(self):
@@ -245,10 +273,12 @@ class FlatAdam:
         if self.capturable:
             from . import _hip
             P = _hip._ptr
-            _hip.check(_hip.lib().fgnn_flat_adam_dev(P(p), P(g), P(self.exp_avg), P(self.exp_avg_sq), None, p.numel(),
-                                                     P(self._lr_dev), float(b1), float(b2), float(self.eps),
-                                                     float(self.weight_decay), float(grad_scale), P(self._step_dev),
-                                                     P(self._coef_dev), _hip.stream_ptr()))
+            args = (P(p), P(g), P(self.exp_avg), P(self.exp_avg_sq), None, p.numel(), P(self._lr_dev), float(b1), float(b2),
+                    float(self.eps), float(self.weight_decay), float(grad_scale), P(self._step_dev), P(self._coef_dev))
+            if self.max_grad_norm is not None:
+                _hip.check(_hip.lib().fgnn_flat_adam_dev_clipped(*args, self._measure(g, grad_scale), _hip.stream_ptr()))
+            else:
+                _hip.check(_hip.lib().fgnn_flat_adam_dev(*args, _hip.stream_ptr()))
             from .mpnn import pointwise
             pointwise.invalidate_casts()
             pointwise.note_state_change()
@@ -257,12 +287,19 @@ class FlatAdam:
         if p.is_cuda:
             from . import _hip
             P = _hip._ptr
-            _hip.check(_hip.lib().fgnn_flat_adam(P(p), P(g), P(self.exp_avg), P(self.exp_avg_sq), None, p.numel(),
-                                                 float(self.lr), float(b1), float(b2), float(self.eps),
-                                                 float(self.weight_decay), float(grad_scale), int(self._t),
-                                                 _hip.stream_ptr()))
+            args = (P(p), P(g), P(self.exp_avg), P(self.exp_avg_sq), None, p.numel(), float(self.lr), float(b1), float(b2),
+                    float(self.eps), float(self.weight_decay), float(grad_scale), int(self._t))
+            if self.max_grad_norm is not None:
+                _hip.check(_hip.lib().fgnn_flat_adam_clipped(*args, self._measure(g, grad_scale), _hip.stream_ptr()))
+            else:
+                _hip.check(_hip.lib().fgnn_flat_adam(*args, _hip.stream_ptr()))
         else:
-            if grad_scale != 1.0:
+            if self.max_grad_norm is not None:       # the kernels' rule: f64 sum of squares, one rounding, torch's coefficient in f32
+                norm = (g.double().square().sum().sqrt() * grad_scale).float()
+                self._norm[0] = norm
+                self._norm[1] = torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)
+                g = g * (torch.tensor(grad_scale, dtype=torch.float32) * self._norm[1])
+            elif grad_scale != 1.0:
                 g = g * grad_scale
             if self.weight_decay:
                 g = g.add(p, alpha=self.weight_decay)

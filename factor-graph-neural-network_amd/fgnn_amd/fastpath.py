@@ -386,14 +386,22 @@ class FastAdam(torch.optim.Optimizer):
     Differences from the stock class that remain: the update is DENSE — every parameter of the flat buffer is updated every
     step with whatever its gradient slice holds (zero for a parameter the loss did not reach), whereas ``torch.optim.Adam``
     skips parameters whose ``.grad`` is None; with ``weight_decay`` != 0 an unused parameter therefore decays here and not
-    there.  One hyper-parameter set for all parameters (the first group's); ``zero_grad(set_to_none=True)`` zeroes."""
+    there.  One hyper-parameter set for all parameters (the first group's); ``zero_grad(set_to_none=True)`` zeroes.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    ``max_grad_norm`` (not a hyper-parameter of the stock class: it stays out of ``param_groups`` and of the state dict): ``step``
+    clips the gradient's total norm to it inside the update, as ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm)`` in front
+    of a stock step does (``dp.FlatAdam``); ``opt.grad_norm`` is the last pre-clip norm, a [1] device tensor."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
         from .dp import FlatAdam, FlatGradBucket
         params = list(params)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.bucket = FlatGradBucket([p for g in self.param_groups for p in g['params']], flatten_params=True)
-        self.flat = FlatAdam(self.bucket, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.flat = FlatAdam(self.bucket, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+
+    @property
+    def grad_norm(self):
+        return self.flat.grad_norm
 
     @torch.no_grad()
     def step(self, closure=None):

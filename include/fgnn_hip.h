@@ -505,6 +505,36 @@ int fgnn_flat_adam_dev(float* param, const float* grad, float* exp_avg, float* e
                        int64_t* step_dev, float* coef_dev, fgnn_stream_t stream);
 
 /*
+ * Gradient-norm clipping for the two updates above (torch.nn.utils.clip_grad_norm_(parameters, max_norm) in front of
+ * optimizer.step(): /root/reference/train_syn_hop_factor.py:302, train_syn_pw_factor.py:302, train_syn_fixed_pw_hop.py:293),
+ * without a pass that rewrites the gradient.
+ *
+ * fgnn_grad_norm_clip     out[0] = sqrt(sum_i grad[i]^2) * grad_scale: the total norm of the gradient the update will see (grad_scale
+ *                         = 1 / world after an all-reduce SUM); out[1] = min(1, max_norm / (out[0] + 1e-6)), clip_grad_norm_'s
+ *                         coefficient, formed in f32 from out[0] as torch forms it.  The squares are summed in f64 (entries of 1e20
+ *                         do not overflow), per workgroup and then over the workgroups in order by a second launch: the partials'
+ *                         layout depends on n alone, so the sum is bit-reproducible; out[0] is rounded once.  A NaN norm gives a NaN
+ *                         coefficient and an infinite one 0 (then 0 * inf = NaN in the update), as torch with error_if_nonfinite=False.
+ *                         n = 0: norm 0 and the coefficient of the formula (1 for max_norm >= 1e-6).  Nothing among the launch
+ *                         arguments depends on the step: capturable.  grad 16-byte aligned; workspace:
+ *                         fgnn_grad_norm_clip_workspace_bytes() bytes, 8-byte aligned.  Null pointers, n < 0, a short workspace:
+ *                         FGNN_EINVAL, before any launch.
+ * fgnn_flat_adam_clipped, fgnn_flat_adam_dev_clipped   fgnn_flat_adam / fgnn_flat_adam_dev with one more argument, clip_dev: a device
+ *                         pointer to a coefficient (fgnn_grad_norm_clip's out + 1);  g' = grad * grad_scale * (*clip_dev) +
+ *                         weight_decay * param, the product grad_scale * (*clip_dev) formed once in f32: a coefficient of 1 gives the
+ *                         unclipped entry point's bits.  A null clip_dev: FGNN_EINVAL.
+ */
+int64_t fgnn_grad_norm_clip_workspace_bytes(void);
+int fgnn_grad_norm_clip(const float* grad, int64_t n, float max_norm, float grad_scale, float* out, void* workspace,
+                        int64_t workspace_bytes, fgnn_stream_t stream);
+int fgnn_flat_adam_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_mirror, int64_t n,
+                           float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale, int64_t step,
+                           const float* clip_dev, fgnn_stream_t stream);
+int fgnn_flat_adam_dev_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_mirror, int64_t n,
+                               const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                               int64_t* step_dev, float* coef_dev, const float* clip_dev, fgnn_stream_t stream);
+
+/*
  * The edge-type MLP in front of the operator, etype = W2 ReLU(W1 efeature + b1) + b2 with Cin <= 8 -> 64 -> net <= 4
  * (`emodel_f2v / emodel_v2f`, /root/reference/train_ldpc.py:32-38,68-69), without the 64-channel hidden tensor ever
  * reaching memory.  x is bf16 with element (b, c, r) at b*x_sb + c*x_sc + r*x_sr (r one of the E = M*k edge rows of
@@ -681,6 +711,33 @@ int fgnn_chain_budget_score(const void* dec, int32_t dec_kind, int64_t dec_sb, i
                             const int32_t* caps, int64_t caps_sb, int64_t B, int32_t N, int32_t h, int32_t* correct,
                             uint8_t* feasible, double* objective, double* nll, int64_t* counts, fgnn_stream_t stream);
 
+/*
+ * The labelling loss of the synthetic training loops (csrc/pgm_loss.hip): F.cross_entropy(pred.view(-1, 2), nlabel.view(-1)) on the
+ * permuted model output and the per-step all_correct / lp_correct accounting (/root/reference/train_syn_hop_factor.py:298-312,
+ * train_syn_pw_factor.py:298-312, train_syn_fixed_pw_hop.py:283-303), two short launches forward and one backward.
+ *
+ * logits of kind FGNN_PGM_DEC_F32 / FGNN_PGM_DEC_BF16, v_c = logits[b * sb + c * cs + i * vs] exactly as fgnn_chain_budget_score reads
+ * them (a model's [B, 2, N, 1] output as it is, no permute().contiguous()); label [b * label_sb + i] int64, != 0 reads v1.
+ *   loss [1] f32         the mean over the B N variables of logsumexp(v0, v1) - v_label, every summand in f64 from the stored values as
+ *                        a stable softplus of the logit difference, summed per workgroup and then over the workgroups in a fixed
+ *                        order (independent of timing; the grid is a function of B N), rounded once
+ *   counts [3] int64     or NULL; ADDED to: {variables, variables whose decision (fgnn_chain_budget_score's argmax rule) equals label,
+ *                        variables with lp_label == label}; the third only with lp_label (int64 [b * lp_sb + i], or NULL).  Integer
+ *                        atomics: a training loop accumulates acc / lp_acc on the device and reads them when it logs
+ *   workspace            fgnn_pgm_loss_workspace_bytes() bytes, 8-byte aligned
+ * backward: glogits[b * g_sb + c * g_cs + i * g_vs] = gloss[0] / (B N) * (softmax_c - [c == label]) in the logits' dtype, computed
+ * in f64 (as -/+ sigmoid(v_other - v_label): no cancellation) and rounded once; nothing outside those 2 B N elements is written.
+ * 1 <= N <= 1024 and the two kinds, FGNN_EUNSUPPORTED otherwise; null pointers, negative sizes or strides, a short workspace:
+ * FGNN_EINVAL; all before any launch.  B = 0 is a no-op that writes loss[0] = 0.
+ */
+int64_t fgnn_pgm_loss_workspace_bytes(void);
+int fgnn_pgm_loss_forward(const void* logits, int32_t kind, int64_t sb, int64_t cs, int64_t vs, const int64_t* label,
+                          int64_t label_sb, const int64_t* lp_label, int64_t lp_sb, int64_t B, int32_t N, float* loss,
+                          int64_t* counts, void* workspace, int64_t workspace_bytes, fgnn_stream_t stream);
+int fgnn_pgm_loss_backward(const void* logits, int32_t kind, int64_t sb, int64_t cs, int64_t vs, const int64_t* label,
+                           int64_t label_sb, const float* gloss, int64_t B, int32_t N, void* glogits, int64_t g_sb, int64_t g_cs,
+                           int64_t g_vs, fgnn_stream_t stream);
+
 const char* fgnn_last_error(void);
 /* Name (as rocprofv3 prints it) of the kernel the calling thread's last forward/backward dispatched to. */
 const char* fgnn_last_kernel(void);
@@ -691,7 +748,9 @@ const char* fgnn_last_kernel(void);
  * 6: fgnn_block_head_backward.  11: fgnn_mpconv_block_forward_rows.  12: fgnn_block_tail_backward_moments,
  * fgnn_block_tail_wgrad_finish, fgnn_block_tail_moments_bytes.  14: fgnn_chain_budget_map, fgnn_chain_budget_map_lds_bytes,
  * fgnn_pgm_sample_rng.  15: fgnn_chain_budget_lp, fgnn_chain_budget_lp_lds_bytes; later additions at 15 (new entry points
- * only, no existing one changed): fgnn_ldpc_received_features, fgnn_ldpc_error_counts, fgnn_chain_budget_score. */
+ * only, no existing one changed): fgnn_ldpc_received_features, fgnn_ldpc_error_counts, fgnn_chain_budget_score, fgnn_pgm_loss_forward,
+ * fgnn_pgm_loss_backward, fgnn_pgm_loss_workspace_bytes, fgnn_grad_norm_clip, fgnn_grad_norm_clip_workspace_bytes,
+ * fgnn_flat_adam_clipped, fgnn_flat_adam_dev_clipped. */
 #define FGNN_ABI_VERSION 15
 /* Arithmetic of the f32 synthetic-PGM operator's BACKWARD (16 edge types, ORIG_WITH_NEIGHBOR / ORIG_WITH_DIFF, 64 -> 64, max: the
  * autograd of /root/reference/lib/model/mpnn/mp_nn.py:136-175 as train_syn_*.py reaches it): 2 (default) = every f32 operand of the three

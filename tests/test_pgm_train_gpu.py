@@ -1,0 +1,312 @@
+"""GPU: the synthetic-PGM trainer's kernels and loop (csrc/pgm_loss.hip, the norm / clipped entry points of csrc/flat_adam.hip,
+fgnn_amd/pgm_train.py) against f64 references formed on the CPU from the stored values."""
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1), (3, 30), (257, 30), (2, 1024)]      # (257, 30): 7710 variables, more than one workgroup of partials
+
+
+def _ulps(a, b):
+    """Distance in units of the last place between two tensors of one dtype (f32 or bf16), elementwise, as int64."""
+    it = torch.int32 if a.dtype == torch.float32 else torch.int16
+    key = lambda t: t.contiguous().view(it).to(torch.int64)
+    fold = lambda k: torch.where(k < 0, -(k & (0x7fffffff if it == torch.int32 else 0x7fff)), k)      # sign-magnitude -> ordered
+    return (fold(key(a)) - fold(key(b))).abs()
+
+
+def _case(B, N, layout, dtype, seed=0):
+    """Logits in +-30 (a naive f32 log(sum(exp)) loses the small class), every 7th variable a tie; labels and an LP label."""
+    g = torch.Generator().manual_seed(seed + 1000 * B + N)
+    x = (torch.rand(B, 2, N, 1, generator=g) * 2 - 1) * 30
+    flat = x.view(B, 2, N)
+    tie = torch.zeros(B * N, dtype=torch.bool)
+    tie[::7] = True
+    tie = tie.view(B, N)
+    flat[:, 1][tie] = flat[:, 0][tie]
+    x = x.to(dtype)
+    label = torch.randint(0, 2, (B, N), generator=g)
+    lp = torch.where(torch.rand(B, N, generator=g) < 0.8, label, 1 - label)
+    if layout == 'slice':                                       # a channel slice of a [B, 4, N, 1] tensor
+        big = torch.full((B, 4, N, 1), 7.0, dtype=dtype)
+        big[:, 1:3] = x
+        return big, slice(1, 3), label, lp
+    return x, slice(0, 2), label, lp
+
+
+def _reference_loss(x, label):
+    z = x.double()[..., 0].permute(0, 2, 1).reshape(-1, 2)
+    return torch.nn.functional.cross_entropy(z, label.reshape(-1)), z
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['f32', 'bf16'])
+@pytest.mark.parametrize('layout', ['contiguous', 'slice'])
+@pytest.mark.parametrize('B,N', SHAPES)
+def test_loss_forward_and_counts(dev, B, N, layout, dtype):
+    """The kernel sums f64 summands and rounds once: within 1 f32 ulp of the f64 cross entropy rounded to f32.  The counts are
+    exact integers, ties decide for class 0, and a second call adds to the first."""
+    from fgnn_amd.pgm_train import labelling_loss
+    store, ch, label, lp = _case(B, N, layout, dtype)
+    ref, z = _reference_loss(store[:, ch], label)
+    d = store.to(dev)
+    pred = d[:, ch]
+    counts = torch.zeros(3, dtype=torch.int64, device=dev)
+    loss = labelling_loss(pred, label.to(dev), lp.to(dev), counts)
+    assert loss.shape == () and loss.dtype == torch.float32
+    got = loss.cpu()
+    print('B=%d N=%d %s %s: loss %.9g reference %.17g ulps %d' % (B, N, layout, dtype, float(got), float(ref),
+                                                                  int(_ulps(got.reshape(1), ref.float().reshape(1)))))
+    assert int(_ulps(got.reshape(1), ref.float().reshape(1))) <= 1
+    dec = z.argmax(-1).reshape(B, N)
+    assert (dec[(z[:, 0] == z[:, 1]).reshape(B, N)] == 0).all()            # the reference's own tie rule: class 0
+    want = [B * N, int((dec == label).sum()), int((lp == label).sum())]
+    assert counts.tolist() == want
+    loss2 = labelling_loss(pred[..., 0], label.to(dev), None, counts)      # [B, 2, N]; no LP label: the third count stays
+    assert torch.equal(loss2.cpu(), got)
+    assert counts.tolist() == [2 * want[0], 2 * want[1], want[2]]
+    assert torch.equal(d.cpu(), store)                                      # the logits (and the slice's surroundings) are only read
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['f32', 'bf16'])
+@pytest.mark.parametrize('B,N', [(1, 1), (3, 30), (257, 30)])
+def test_loss_backward(dev, B, N, dtype):
+    """glogits = gloss / (B N) (softmax_c - [c == label]) against the f64 formula (softmax_c - [c == label] written without
+    cancellation: -sigmoid(v_other - v_label) for c == label, +sigmoid(v_other - v_label) for the other class) within 1 ulp of the
+    output dtype; through autograd into a strided leaf, and through the C entry point into a channel slice whose surroundings
+    keep their sentinel.  (No torch.autograd.gradcheck: the inputs are f32 / bf16.)"""
+    from fgnn_amd import _hip
+    from fgnn_amd.pgm_train import labelling_loss
+    store, ch, label, _ = _case(B, N, 'slice', dtype, seed=3)
+    x = store[:, ch].double()[..., 0]                                        # [B, 2, N]
+    gl = 3.0
+    t = torch.where(label.bool(), x[:, 0] - x[:, 1], x[:, 1] - x[:, 0])     # v_other - v_label
+    so = gl / (B * N) * torch.sigmoid(t)
+    want = torch.stack([torch.where(label.bool(), so, -so), torch.where(label.bool(), -so, so)], 1).to(dtype)
+
+    leaf = store.to(dev).requires_grad_(True)
+    (labelling_loss(leaf[:, ch], label.to(dev)) * gl).backward()
+    got = leaf.grad.cpu()
+    assert int(_ulps(got[:, ch][..., 0], want).max()) <= 1
+    assert (got[:, 0] == 0).all() and (got[:, 3] == 0).all()
+
+    out = torch.full((B, 4, N), -5.0, dtype=dtype, device=dev)
+    d, lab = store.to(dev), label.to(dev)
+    gloss = torch.tensor([gl], device=dev)
+    P = _hip._ptr
+    sb, cs, vs = d[:, ch][..., 0].stride()
+    view = out[:, 1:3]
+    _hip.check(_hip.lib().fgnn_pgm_loss_backward(P(d[:, ch]), _hip.PGM_DEC_F32 if dtype == torch.float32 else _hip.PGM_DEC_BF16, sb,
+                                                 cs, vs, P(lab), N, P(gloss), B, N, P(view), *view.stride(), _hip.stream_ptr()))
+    o = out.cpu()
+    assert int(_ulps(o[:, 1:3], want).max()) <= 1
+    assert (o[:, 0] == -5.0).all() and (o[:, 3] == -5.0).all()
+
+
+def _norm_call(g, n, max_norm, grad_scale):
+    from fgnn_amd import _hip
+    L, P = _hip.lib(), _hip._ptr
+    out = torch.full((2,), -1.0, device=g.device)
+    ws = torch.empty(int(L.fgnn_grad_norm_clip_workspace_bytes()) // 8, dtype=torch.float64, device=g.device)
+    _hip.check(L.fgnn_grad_norm_clip(P(g), n, max_norm, grad_scale, P(out), P(ws), ws.numel() * 8, _hip.stream_ptr()))
+    return out.cpu()
+
+
+@pytest.mark.parametrize('kind', ['half', 'norm37', 'huge'])
+@pytest.mark.parametrize('n', [0, 1, 7, 4096 + 3, 1000003])
+def test_grad_norm_clip(dev, n, kind):
+    """out[0] against numpy's f64 norm of the stored values (1 f32 ulp: f64 sums, one rounding), out[1] against the formula
+    min(1, max_norm / (out[0] + 1e-6)) in f32 (1 ulp: one f32 division); two calls bit-identical.  'huge': entries of 1e20, whose
+    squares overflow f32 but not the f64 sum."""
+    g = torch.Generator().manual_seed(n)
+    x = torch.randn(max(n, 4), generator=g)
+    if kind == 'huge':
+        x = torch.full_like(x, 1e20) * torch.where(torch.rand(x.shape, generator=g) < 0.5, -1.0, 1.0)
+    elif n:
+        x = (x.double() * ((0.5 if kind == 'half' else 37.0) / x[:n].double().norm())).float()
+    max_norm, scale = 1.0, (0.5 if kind == 'norm37' else 1.0)
+    d = x.to(dev)
+    a, b = _norm_call(d, n, max_norm, scale), _norm_call(d, n, max_norm, scale)
+    assert torch.equal(a, b)
+    want = np.float32(np.sqrt(np.sum(x[:n].double().numpy() ** 2)) * scale)
+    assert int(_ulps(a[:1], torch.tensor([want], dtype=torch.float32))) <= 1, (float(a[0]), float(want))
+    coef = np.float32(max_norm) / (a[:1].numpy()[0] + np.float32(1e-6))
+    coef = np.float32(1.0) if coef > 1 else np.float32(coef)
+    assert int(_ulps(a[1:], torch.tensor([coef], dtype=torch.float32))) <= 1, (float(a[1]), float(coef))
+    if n == 0:
+        assert a.tolist() == [0.0, 1.0]
+    elif kind == 'half':
+        assert float(a[1]) == 1.0                       # a norm of 0.5: not clipped, the coefficient is exactly 1
+    else:
+        assert float(a[1]) < 1.0
+
+
+def _adam_buffers(dev, n, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    return [t.to(dev) for t in (torch.randn(n, generator=g), torch.randn(n, generator=g) * 3, torch.randn(n, generator=g) * 0.1,
+                                torch.rand(n, generator=g) * 0.01)]
+
+
+def test_clipped_adam_is_the_unclipped_update_with_the_coefficient_folded_in(dev):
+    """fgnn_flat_adam_clipped with a coefficient of 1 is bit-identical to fgnn_flat_adam; with a coefficient c it is bit-identical to
+    fgnn_flat_adam called with the f32 product grad_scale * c (the kernel forms exactly that product, once per thread); the same
+    for the device-resident form.  n = 4099: float4 chunks over more than one workgroup plus a tail."""
+    from fgnn_amd import _hip
+    L, P = _hip.lib(), _hip._ptr
+    n, hyper = 4099, (3e-3, 0.9, 0.999, 1e-8, 1e-2)
+    for c, gs in ((1.0, 1.0), (0.37, 0.5)):
+        folded = float(np.float32(gs) * np.float32(c))
+        clip = torch.tensor([c], device=dev)
+        a, b = _adam_buffers(dev, n), _adam_buffers(dev, n)
+        for step in (1, 2, 3):
+            _hip.check(L.fgnn_flat_adam(P(a[0]), P(a[1]), P(a[2]), P(a[3]), None, n, *hyper, folded, step, _hip.stream_ptr()))
+            _hip.check(L.fgnn_flat_adam_clipped(P(b[0]), P(b[1]), P(b[2]), P(b[3]), None, n, *hyper, gs, step, P(clip), _hip.stream_ptr()))
+        for s, t in zip(a, b):
+            assert torch.equal(s, t)
+        a, b = _adam_buffers(dev, n), _adam_buffers(dev, n)
+        lr = torch.tensor([hyper[0]], device=dev)
+        sa, sb = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2))
+        ca, cb = (torch.zeros(2, device=dev) for _ in range(2))
+        for _ in range(3):
+            _hip.check(L.fgnn_flat_adam_dev(P(a[0]), P(a[1]), P(a[2]), P(a[3]), None, n, P(lr), *hyper[1:], folded, P(sa), P(ca),
+                                            _hip.stream_ptr()))
+            _hip.check(L.fgnn_flat_adam_dev_clipped(P(b[0]), P(b[1]), P(b[2]), P(b[3]), None, n, P(lr), *hyper[1:], gs, P(sb), P(cb),
+                                                    P(clip), _hip.stream_ptr()))
+        assert int(sa) == int(sb) == 3
+        for s, t in zip(a, b):
+            assert torch.equal(s, t)
+
+
+def _clipped_optimizer(dev, capturable):
+    from fgnn_amd.dp import FlatAdam, FlatGradBucket
+    g = torch.Generator().manual_seed(11)
+    ps = [torch.nn.Parameter(torch.randn(s, generator=g).to(dev)) for s in ((37, 53), (53,), (1,), (3, 53))]
+    bucket = FlatGradBucket(ps, flatten_params=True)
+    opt = FlatAdam(bucket, lr=3e-3, capturable=capturable, max_grad_norm=1.0)
+    for q in ps:                                                                # a norm of ~46: clipped (the padding stays zero)
+        q.grad.copy_(torch.randn(q.shape, generator=g))
+    return ps, bucket, opt
+
+
+def test_clipped_flat_adam_against_clip_grad_norm_and_torch_adam(dev):
+    """FlatAdam(max_grad_norm=1.0) on the device against clip_grad_norm_ + torch.optim.Adam, 3 steps, at the tolerance of the
+    unclipped comparison (tests/test_parity_pins_gpu.py: test_fused_flat_adam_matches_torch_adam, rtol 2e-5, atol 2e-7)."""
+    ps, bucket, opt = _clipped_optimizer(dev, False)
+    ref = [torch.nn.Parameter(q.detach().clone()) for q in ps]
+    stock = torch.optim.Adam(ref, lr=3e-3)
+    grads = [q.grad.detach().clone() for q in ps]
+    for _ in range(3):
+        for q, gr in zip(ref, grads):
+            q.grad = gr.clone()
+        total = torch.nn.utils.clip_grad_norm_(ref, 1.0)
+        stock.step()
+        opt.step()
+        assert torch.allclose(opt.grad_norm, total.reshape(1), rtol=1e-6)
+    for q, r in zip(ps, ref):
+        assert torch.allclose(q, r, rtol=2e-5, atol=2e-7), float((q - r).abs().max())
+
+
+def test_capturable_clipped_flat_adam_replays_as_eager_steps(dev):
+    """The norm launches and the clipped update have no step-dependent launch argument: captured once in a hipGraph and replayed 3
+    times they leave the bits of 3 eager steps."""
+    eager_p, _, eager = _clipped_optimizer(dev, True)
+    for _ in range(3):
+        eager.step()
+    ps, bucket, opt = _clipped_optimizer(dev, True)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        opt.step()
+    for _ in range(3):
+        graph.replay()
+    torch.cuda.synchronize()
+    assert opt.t == eager.t == 3
+    assert torch.equal(opt.grad_norm, eager.grad_norm) and float(opt.grad_norm) > 1.0
+    for q, r in zip(ps, eager_p):
+        assert torch.equal(q, r)
+
+
+# ---- the loop ----------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def hops_runs(dev, tmp_path_factory):
+    """One eager and one graphed run of the same 60 steps x 256 (seed 0), shared by the tests below."""
+    from fgnn_amd import pgm_train
+    out = {}
+    for name, graph in (('eager', False), ('graph', True)):
+        d = tmp_path_factory.mktemp(name)
+        out[name] = pgm_train.train('hops', 1, batch_size=256, steps_per_epoch=60, seed=0, out_dir=str(d), graph=graph, log_every=10,
+                                    device=dev)
+    return out
+
+
+def test_train_hops_learns_and_its_checkpoint_evaluates(dev, hops_runs, tmp_path):
+    from fgnn_amd import pgm_eval
+    r = hops_runs['eager']
+    losses = np.asarray(r['losses'])
+    assert r['steps'] == r['gcnt'] == 60 and len(losses) == 60 and not r['graphed']
+    assert np.isfinite(losses).all()
+    print('eager: first 10 %.4f last 10 %.4f, %.2f s, window acc %.4f' % (losses[:10].mean(), losses[-10:].mean(), r['seconds'], r['acc']))
+    assert losses[-10:].mean() < losses[:10].mean()
+    assert abs(r['loss'] - losses[-10:].mean()) < 1e-6 and 0.0 <= r['acc'] <= 1.0 and r['lp_acc'] is None
+    model, edge = pgm_eval.load_checkpoint(r['checkpoint'], 'hops', device=dev)
+    ckpt = torch.load(r['checkpoint'], map_location='cpu', weights_only=True)
+    assert ckpt['epoch'] == 1 and ckpt['gcnt'] == 60
+    assert all(int(s['step']) == 60 for s in ckpt['optimizer_state_dict']['state'].values())
+    ts = str(tmp_path / 'test.pkl')
+    pgm_eval.make_test_set(ts, 'hops', 512, seed=0, device=dev)
+    test_set = pgm_eval.load_test_set(ts, 'hops', device=dev)
+    e = pgm_eval.evaluate(model, edge, test_set, 'hops')
+    nf, label = test_set[0], test_set[3]
+    baseline = float(((nf[:, 1, :, 0] > nf[:, 0, :, 0]).long() == label).float().mean())
+    print('held-out after 60 steps x 256: acc %.4f (pooled %.4f), unary-argmax baseline %.4f' % (e['acc'], e['pooled_acc'], baseline))
+    assert e['n'] == 512 and 0.0 <= e['acc'] <= 1.0 and np.isfinite(e['loss'])
+
+
+def test_graphed_steps_equal_eager_steps(hops_runs):
+    """The replayed forward / loss / backward launch the kernels of the eager step on the same inputs: the first 5 losses are
+    asserted bit-identical."""
+    a, b = hops_runs['eager'], hops_runs['graph']
+    assert b['graphed'] and b['steps'] == 60
+    diff = np.abs(np.asarray(a['losses']) - np.asarray(b['losses']))
+    print('graph vs eager: |loss difference| first 5 %s, max over 60 %.3e' % (diff[:5].tolist(), diff.max()))
+    assert a['losses'][:5] == b['losses'][:5]
+
+
+def test_resume_continues_the_run(dev, tmp_path):
+    """30 steps, a checkpoint, 30 more == 60 steps in one go (two epochs of 30): the same gcnt, so the same Philox steps, the same
+    Adam state and schedule.  Parameters compared bit for bit, as the losses of the graphed run are."""
+    from fgnn_amd import pgm_train
+    kw = dict(batch_size=64, steps_per_epoch=30, seed=2, graph=False, log_every=10, device=dev)
+    first = pgm_train.train('hops', 1, out_dir=str(tmp_path / 'a'), **kw)
+    assert first['gcnt'] == 30
+    second = pgm_train.train('hops', 2, out_dir=str(tmp_path / 'a'), model_path=first['checkpoint'], **kw)
+    whole = pgm_train.train('hops', 2, out_dir=str(tmp_path / 'b'), **kw)
+    assert second['steps'] == 30 and second['gcnt'] == whole['gcnt'] == 60 and whole['steps'] == 60
+    ca, cb = (torch.load(r['checkpoint'], map_location='cpu', weights_only=True) for r in (second, whole))
+    assert ca['epoch'] == cb['epoch'] == 2 and ca['gcnt'] == cb['gcnt'] == 60
+    assert ca['lr_sche']['last_epoch'] == cb['lr_sche']['last_epoch'] == 2
+    worst = 0.0
+    for key in ('model_state_dict', 'emodel_pw_state_dict', 'emodel_high_state_dict'):
+        for k, v in ca[key].items():
+            worst = max(worst, float((v.double() - cb[key][k].double()).abs().max()))
+    print('resume vs one go: losses equal %s, max |parameter difference| %.3e' % (second['losses'] == whole['losses'][30:], worst))
+    assert second['losses'] == whole['losses'][30:]
+    for key in ('model_state_dict', 'emodel_pw_state_dict', 'emodel_high_state_dict'):
+        for k, v in ca[key].items():
+            assert torch.equal(v, cb[key][k]), (key, k)
+    sa, sb = ca['optimizer_state_dict']['state'], cb['optimizer_state_dict']['state']
+    assert sa.keys() == sb.keys() and all(torch.equal(sa[i]['exp_avg_sq'], sb[i]['exp_avg_sq']) for i in sa)
+
+
+@pytest.mark.parametrize('family', ['raw', 'pws'])
+def test_other_families_train_and_checkpoint(dev, family, tmp_path):
+    from fgnn_amd import pgm_eval, pgm_train
+    r = pgm_train.train(family, 1, batch_size=32, steps_per_epoch=10, seed=1, out_dir=str(tmp_path), lp_label=True, log_every=5, device=dev)
+    assert r['steps'] == 10 and len(r['losses']) == 10 and np.isfinite(r['losses']).all()
+    assert 0.0 <= r['acc'] <= 1.0 and 0.0 <= r['lp_acc'] <= 1.0
+    ckpt = torch.load(r['checkpoint'], map_location='cpu', weights_only=True)
+    assert set(ckpt) == {'model_state_dict', 'optimizer_state_dict', 'lr_sche', 'epoch', 'gcnt'} | set(pgm_eval.EDGE_KEYS[family])
+    pgm_eval.load_checkpoint(r['checkpoint'], family, device=dev)
+    print('%s: graphed %s, loss %.4f -> %.4f, acc %.4f lp_acc %.4f' % (family, r['graphed'], r['losses'][0], r['losses'][-1], r['acc'], r['lp_acc']))
