@@ -4,36 +4,23 @@ PyTorch is only the owner of device memory and streams here: every call passes r
 device pointers, element strides and the current HIP stream.  There is no CPU or
 eager-PyTorch fallback: if the shared library is missing the import of the operator
 fails loudly (build it with ``python __graft_entry__.py`` or ``make -C csrc``).
+
+The header is the one place where the interface is written down: the prototypes' ctypes signatures, the list of
+exports and every mirrored constant are parsed from it when this module is imported (``signatures``, ``constants``).
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('FGNN_HIP_LIB') or os.path.join(_HERE, 'libfgnn_hip.so')      # FGNN_HIP_LIB: a tuning build
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'include', 'fgnn_hip.h'))
 
-EXT_NONE, EXT_NEIGHBOR, EXT_DIFF = 0, 1, 2
-DESC_GETYPE_REDUCED = 0x10000
-DESC_IDENTITY_LIST = 0x20000       # forward: the one-destination call's neighbour table is idx[j] == j
-AGG_MAX, AGG_LSE, AGG_MEAN = 0, 1, 2
-F32, BF16 = 0, 1
-DEC_F32, DEC_BF16, DEC_U8 = 0, 1, 2          # include/fgnn_hip.h: FGNN_DEC_* (fgnn_ldpc_error_counts)
-LABEL_I64, LABEL_U8 = 0, 1                  # FGNN_LABEL_*
-PGM_DEC_F32, PGM_DEC_BF16, PGM_DEC_I64 = 0, 1, 2   # FGNN_PGM_DEC_* (fgnn_chain_budget_score)
-ABI_VERSION = 15             # include/fgnn_hip.h: FGNN_ABI_VERSION (checked before any symbol is bound)
-EUNSUPPORTED = -3            # FGNN_EUNSUPPORTED: shape outside a kernel's family (callers fall back)
 
-AGG_CODES = {'max': AGG_MAX, 'softmax': AGG_LSE, 'mean': AGG_MEAN}
-
-EXPORTS = ('fgnn_mpconv_forward', 'fgnn_mpconv_backward', 'fgnn_mpconv_forward_lds_bytes',
-           'fgnn_mpconv_backward_workspace_bytes', 'fgnn_mpconv_backward_reduces_getype', 'fgnn_linear_wgrad', 'fgnn_linear_wgrad_workspace_bytes',
-           'fgnn_linear_wgrad_multi', 'fgnn_linear_wgrad_multi_workspace_bytes',
-           'fgnn_instnorm_forward', 'fgnn_instnorm_backward', 'fgnn_instnorm_dot_forward', 'fgnn_instnorm_dot_backward',
-           'fgnn_instnorm_dot_workspace_bytes', 'fgnn_bn_supported', 'fgnn_bn_workspace_bytes',
-           'fgnn_bn_stats', 'fgnn_bn_finalize', 'fgnn_bn_apply', 'fgnn_bn_backward',
-           'fgnn_linear_forward', 'fgnn_linear_forward_partials', 'fgnn_linear_instnorm_forward', 'fgnn_sum_n', 'fgnn_concat_pair', 'fgnn_concat_rows', 'fgnn_flat_adam', 'fgnn_flat_adam_dev', 'fgnn_edge_mlp_forward', 'fgnn_edge_mlp_workspace_bytes', 'fgnn_edge_mlp_backward', 'fgnn_ldpc_encode', 'fgnn_ldpc_channel_features', 'fgnn_ldpc_channel_features_rng', 'fgnn_ldpc_received_features', 'fgnn_ldpc_error_counts', 'fgnn_ldpc_decode', 'fgnn_ldpc_loss_forward', 'fgnn_ldpc_loss_backward', 'fgnn_ldpc_loss_workspace_bytes', 'fgnn_chain_budget_map', 'fgnn_chain_budget_map_lds_bytes', 'fgnn_pgm_sample_rng', 'fgnn_chain_budget_lp', 'fgnn_chain_budget_lp_lds_bytes', 'fgnn_chain_budget_score', 'fgnn_pgm_loss_forward', 'fgnn_pgm_loss_backward', 'fgnn_pgm_loss_workspace_bytes', 'fgnn_grad_norm_clip', 'fgnn_grad_norm_clip_workspace_bytes', 'fgnn_flat_adam_clipped', 'fgnn_flat_adam_dev_clipped', 'fgnn_linear_multi_supported', 'fgnn_linear_multi_forward', 'fgnn_fold_defer', 'fgnn_fold_pending', 'fgnn_fold_discard', 'fgnn_fold_flush', 'fgnn_mpconv_block_forward', 'fgnn_mpconv_block_forward_rows', 'fgnn_mpconv_block_forward_fanout', 'fgnn_mpconv_block_forward_fanin', 'fgnn_factor_layer_forward', 'fgnn_factor_layer_param_count', 'fgnn_mpconv_forward_stats', 'fgnn_mpconv_forward_stats_partials', 'fgnn_block_tail_partials', 'fgnn_block_tail_stats', 'fgnn_block_tail_apply', 'fgnn_block_tail_backward', 'fgnn_block_tail_backward_partials', 'fgnn_block_tail_moments_bytes', 'fgnn_block_tail_backward_moments', 'fgnn_block_tail_wgrad_finish', 'fgnn_bn_backward_apply', 'fgnn_block_head_backward', 'fgnn_node_sum', 'fgnn_set_inkernel_finalisers', 'fgnn_mpconv_backward_tables_bytes', 'fgnn_mpconv_backward_tables', 'fgnn_mpconv_backward_with_tables',
-           'fgnn_mpconv_algorithmic_bytes', 'fgnn_mpconv_forward_addends', 'fgnn_last_error', 'fgnn_last_kernel', 'fgnn_stamp', 'fgnn_spin', 'fgnn_set_ext_backward_pieces', 'fgnn_abi_version')
+class FgnnHipError(RuntimeError):
+    pass
 
 
 class MPConvDesc(ctypes.Structure):
@@ -51,7 +38,113 @@ class BnFinal(ctypes.Structure):
                [('count', ctypes.c_int64), ('population', ctypes.c_int64), ('momentum', ctypes.c_float), ('eps', ctypes.c_float)]
 
 
-FOLD_SCRATCH_BYTES = 512 + 64 * 512 * 8       # include/fgnn_hip.h: FGNN_FOLD_SCRATCH_BYTES
+class DevicePointer:
+    """``argtypes`` entry of every pointer parameter and of fgnn_stream_t: a launch site hands over the tensor itself.  A tensor
+    must live on the device (no call site of this package passes host memory as a tensor; host arrays go as ctypes arrays)."""
+
+    @classmethod
+    def from_param(cls, obj):
+        if isinstance(obj, torch.Tensor):
+            if not obj.is_cuda:
+                raise FgnnHipError('a %s tensor of shape %s was passed where libfgnn_hip expects device memory'
+                                   % (obj.device, tuple(obj.shape)))
+            return ctypes.c_void_p(obj.data_ptr())
+        if obj is None or isinstance(obj, (ctypes.c_void_p, ctypes.Array, ctypes._Pointer)):
+            return obj
+        if isinstance(obj, int):
+            return ctypes.c_void_p(obj)
+        raise TypeError('expected a tensor, None, an address or a ctypes array / pointer, got %s' % type(obj).__name__)
+
+
+_SCALARS = {'int': ctypes.c_int32, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64,
+            'float': ctypes.c_float, 'double': ctypes.c_double, 'fgnn_stream_t': DevicePointer}
+_STRUCTS = {'fgnn_mpconv_desc': MPConvDesc, 'fgnn_bn_final': BnFinal}
+
+
+def _uncommented(header_text):
+    return re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', header_text, flags=re.S))
+
+
+def _ctype(decl, proto, returned=False):
+    """ctypes type of one C type as the header spells it (``int64_t``, ``const float* const*``, ...); unknown: FgnnHipError."""
+    words = [w for w in decl.replace('*', ' * ').split() if w != 'const']
+    if words and re.fullmatch(r'\w+', words[0]) and all(w == '*' for w in words[1:]):
+        base, depth = words[0], len(words) - 1
+        if depth == 0 and base in _SCALARS:
+            return _SCALARS[base]
+        if returned:
+            if words == ['void']:
+                return None
+            if words == ['char', '*']:
+                return ctypes.c_char_p
+        elif depth == 1 and base in _STRUCTS:
+            return ctypes.POINTER(_STRUCTS[base])
+        elif depth >= 1:
+            return DevicePointer
+    raise FgnnHipError('include/fgnn_hip.h: no ctypes type for `%s` in `%s`' % (decl.strip(), proto))
+
+
+def signatures(header_text):
+    """{name: (restype, [(parameter name, argtype), ...])} of every fgnn_* prototype at file scope of the header.  Pure text
+    work (no library, no GPU).  A declaration that does not split into a prototype, or a type outside the map, raises."""
+    text = re.sub(r'^[ \t]*#.*$', '', _uncommented(header_text), flags=re.M).replace('extern "C" {', '')
+    text = re.sub(r'\{[^{}]*\}', '', text)                              # struct and enum bodies
+    out = {}
+    for stmt in text.split(';'):
+        stmt = ' '.join(stmt.split())
+        if not stmt or stmt == '}' or stmt.startswith(('typedef ', 'enum')):
+            continue
+        m = re.fullmatch(r'(.*?)\b(fgnn_\w+) ?\((.*)\)', stmt)
+        if not m:
+            raise FgnnHipError('include/fgnn_hip.h: cannot parse the declaration `%s`' % stmt)
+        ret, name, plist = m.groups()
+        params = []
+        for p in [] if plist.strip() == 'void' else plist.split(','):
+            pm = re.fullmatch(r'(.*\W)(\w+)', p.strip())
+            if not pm:
+                raise FgnnHipError('include/fgnn_hip.h: cannot parse the parameter `%s` of `%s`' % (p.strip(), stmt))
+            params.append((pm.group(2), _ctype(pm.group(1), stmt)))
+        out[name] = (_ctype(ret, stmt, returned=True), params)
+    return out
+
+
+def constants(header_text):
+    """{name without FGNN_: value} of the header's enum members and of its #defines that have a value."""
+    text = _uncommented(header_text)
+    pairs = re.findall(r'^[ \t]*#define[ \t]+FGNN_(\w+)[ \t]+(\S.*)$', text, flags=re.M)
+    for body in re.findall(r'\benum\s*\{([^}]*)\}', text):
+        pairs += re.findall(r'FGNN_(\w+)\s*=\s*([^,]+)', body)
+    out = {}
+    for name, value in pairs:
+        if not re.fullmatch(r'[\s\dxXa-fA-F()+*-]+', value):
+            raise FgnnHipError('include/fgnn_hip.h: FGNN_%s = `%s` is not an integer expression' % (name, value.strip()))
+        out[name] = int(eval(value, {'__builtins__': {}}))              # digits, parentheses, + - * only (checked above)
+    return out
+
+
+def _header():
+    if not os.path.exists(HEADER_PATH):
+        raise FgnnHipError('the C-ABI header was not found at %s — the binding is derived from it and has no built-in '
+                           'copy of the interface' % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return f.read()
+
+
+SIGNATURES, _K = (parse(_header()) for parse in (signatures, constants))
+EXPORTS = tuple(SIGNATURES)
+EXT_NONE, EXT_NEIGHBOR, EXT_DIFF = _K['EXT_NONE'], _K['EXT_NEIGHBOR'], _K['EXT_DIFF']
+DESC_GETYPE_REDUCED = _K['DESC_GETYPE_REDUCED']
+DESC_IDENTITY_LIST = _K['DESC_IDENTITY_LIST']       # forward: the one-destination call's neighbour table is idx[j] == j
+AGG_MAX, AGG_LSE, AGG_MEAN = _K['AGG_MAX'], _K['AGG_LSE'], _K['AGG_MEAN']
+F32, BF16 = _K['F32'], _K['BF16']
+DEC_F32, DEC_BF16, DEC_U8 = _K['DEC_F32'], _K['DEC_BF16'], _K['DEC_U8']              # fgnn_ldpc_error_counts
+LABEL_I64, LABEL_U8 = _K['LABEL_I64'], _K['LABEL_U8']
+PGM_DEC_F32, PGM_DEC_BF16, PGM_DEC_I64 = _K['PGM_DEC_F32'], _K['PGM_DEC_BF16'], _K['PGM_DEC_I64']   # fgnn_chain_budget_score
+ABI_VERSION = _K['ABI_VERSION']             # checked before any symbol is bound
+EUNSUPPORTED = _K['EUNSUPPORTED']           # shape outside a kernel's family (callers fall back)
+FOLD_SCRATCH_BYTES = _K['FOLD_SCRATCH_BYTES']
+
+AGG_CODES = {'max': AGG_MAX, 'softmax': AGG_LSE, 'mean': AGG_MEAN}
 
 
 def bn_final(stats, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, count, population=0):
@@ -66,10 +159,6 @@ def bn_final(stats, gamma, beta, running_mean, running_var, num_batches_tracked,
     f.count, f.population = int(count), int(population)
     f.momentum, f.eps = float(momentum), float(eps)
     return f
-
-
-class FgnnHipError(RuntimeError):
-    pass
 
 
 _lib = None
@@ -94,196 +183,32 @@ def lib():
     if have != ABI_VERSION:
         raise FgnnHipError('%s speaks C-ABI version %s, this package binds version %d (include/fgnn_hip.h): rebuild it '
                            'with `python __graft_entry__.py`' % (LIB_PATH, have, ABI_VERSION))
-    vp, dp = ctypes.c_void_p, ctypes.POINTER(MPConvDesc)
-    L.fgnn_mpconv_forward.restype = ctypes.c_int
-    L.fgnn_mpconv_forward.argtypes = [dp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.fgnn_mpconv_forward_addends.restype = ctypes.c_int
-    L.fgnn_mpconv_forward_addends.argtypes = [dp] + [vp] * 12
-    L.fgnn_mpconv_forward_stats.restype = ctypes.c_int
-    fp = ctypes.POINTER(BnFinal)
-    L.fgnn_mpconv_forward_stats.argtypes = [dp] + [vp] * 8 + [fp, vp, vp]
-    L.fgnn_mpconv_forward_stats_partials.restype = ctypes.c_int
-    L.fgnn_mpconv_forward_stats_partials.argtypes = [dp]
-    L.fgnn_mpconv_backward.restype = ctypes.c_int
-    L.fgnn_mpconv_backward.argtypes = [dp] + [vp] * 12 + [ctypes.c_int64, vp]
-    L.fgnn_mpconv_backward_with_tables.restype = ctypes.c_int
-    L.fgnn_mpconv_backward_with_tables.argtypes = [dp] + [vp] * 12 + [ctypes.c_int64, vp, vp]
-    L.fgnn_mpconv_backward_tables_bytes.restype = ctypes.c_int64
-    L.fgnn_mpconv_backward_tables_bytes.argtypes = [dp]
-    L.fgnn_mpconv_backward_tables.restype = ctypes.c_int
-    L.fgnn_mpconv_backward_tables.argtypes = [dp, vp, vp, vp]
-    L.fgnn_mpconv_backward_reduces_getype.restype = ctypes.c_int
-    L.fgnn_mpconv_backward_reduces_getype.argtypes = [dp]
-    L.fgnn_mpconv_backward_workspace_bytes.restype = ctypes.c_int64
-    L.fgnn_mpconv_backward_workspace_bytes.argtypes = [dp]
-    L.fgnn_mpconv_forward_lds_bytes.restype = ctypes.c_int64
-    L.fgnn_mpconv_forward_lds_bytes.argtypes = [dp]
-    L.fgnn_mpconv_algorithmic_bytes.restype = ctypes.c_int64
-    L.fgnn_mpconv_algorithmic_bytes.argtypes = [dp]
-    i32, i64 = ctypes.c_int32, ctypes.c_int64
-    L.fgnn_linear_wgrad.restype = ctypes.c_int
-    L.fgnn_linear_wgrad.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp, i64, vp]
-    L.fgnn_linear_wgrad_workspace_bytes.restype = i64
-    L.fgnn_linear_wgrad_workspace_bytes.argtypes = [i64, i32, i32]
-    L.fgnn_linear_wgrad_multi.restype = ctypes.c_int
-    L.fgnn_linear_wgrad_multi.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp]
-    L.fgnn_linear_wgrad_multi_workspace_bytes.restype = i64
-    L.fgnn_linear_wgrad_multi_workspace_bytes.argtypes = [i64, i32, i32, vp]
-    L.fgnn_instnorm_forward.restype = ctypes.c_int
-    L.fgnn_instnorm_forward.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
-    L.fgnn_instnorm_backward.restype = ctypes.c_int
-    L.fgnn_instnorm_backward.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    L.fgnn_linear_multi_supported.restype = ctypes.c_int
-    L.fgnn_linear_multi_supported.argtypes = [i64, vp, i32]
-    L.fgnn_linear_multi_forward.restype = ctypes.c_int
-    L.fgnn_linear_multi_forward.argtypes = [vp, vp, vp, vp, vp, i64, i32, vp]
-    L.fgnn_fold_defer.restype = ctypes.c_int
-    L.fgnn_fold_defer.argtypes = [i32]
-    L.fgnn_fold_pending.restype = ctypes.c_int
-    L.fgnn_fold_pending.argtypes = []
-    L.fgnn_fold_discard.restype = None
-    L.fgnn_fold_discard.argtypes = []
-    L.fgnn_fold_flush.restype = ctypes.c_int
-    L.fgnn_fold_flush.argtypes = [vp]
-    L.fgnn_instnorm_dot_forward.restype = ctypes.c_int
-    L.fgnn_instnorm_dot_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.fgnn_instnorm_dot_backward.restype = ctypes.c_int
-    L.fgnn_instnorm_dot_backward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]
-    L.fgnn_instnorm_dot_workspace_bytes.restype = i64
-    L.fgnn_instnorm_dot_workspace_bytes.argtypes = [i32]
-    f32 = ctypes.c_float
-    L.fgnn_bn_supported.restype = ctypes.c_int
-    L.fgnn_bn_supported.argtypes = [i64, i32, i32]
-    L.fgnn_bn_workspace_bytes.restype = i64
-    L.fgnn_bn_workspace_bytes.argtypes = [i64, i32]
-    L.fgnn_bn_stats.restype = ctypes.c_int
-    L.fgnn_bn_stats.argtypes = [vp, i64, i32, i32, fp, vp, i64, vp, vp]
-    L.fgnn_bn_finalize.restype = ctypes.c_int
-    L.fgnn_bn_finalize.argtypes = [vp, i32, i32, fp, vp]
-    L.fgnn_linear_forward.restype = ctypes.c_int
-    L.fgnn_linear_forward.argtypes = [vp, vp, vp, vp, i64, i32, i32, vp, fp, vp, i32, vp]
-    L.fgnn_set_inkernel_finalisers.restype = ctypes.c_int
-    L.fgnn_set_inkernel_finalisers.argtypes = [i32]
-    L.fgnn_node_sum.restype = ctypes.c_int
-    L.fgnn_node_sum.argtypes = [vp, vp, i64, i32, i32, i32, vp]
-    L.fgnn_linear_instnorm_forward.restype = ctypes.c_int
-    L.fgnn_linear_instnorm_forward.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp]
-    L.fgnn_ldpc_loss_forward.restype = ctypes.c_int
-    L.fgnn_ldpc_loss_forward.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, i64, vp]
-    L.fgnn_ldpc_loss_workspace_bytes.restype = i64
-    L.fgnn_ldpc_loss_workspace_bytes.argtypes = []
-    L.fgnn_ldpc_loss_backward.restype = ctypes.c_int
-    L.fgnn_ldpc_loss_backward.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, vp]
-    L.fgnn_linear_forward_partials.restype = ctypes.c_int
-    L.fgnn_linear_forward_partials.argtypes = [i64, i32, i32]
-    L.fgnn_mpconv_block_forward.restype = ctypes.c_int
-    L.fgnn_mpconv_block_forward.argtypes = [dp] + [vp] * 12 + [f32, i32, i32, vp, vp, vp, vp, vp]
-    L.fgnn_mpconv_block_forward_rows.restype = ctypes.c_int
-    L.fgnn_mpconv_block_forward_rows.argtypes = [dp] + [vp] * 12 + [f32, i32, i32, vp, vp, vp, i32, vp, vp]
-    L.fgnn_mpconv_block_forward_fanout.restype = ctypes.c_int
-    L.fgnn_mpconv_block_forward_fanout.argtypes = [dp] + [vp] * 11 + [f32, i32, i32, vp, vp, vp, vp, vp]
-    L.fgnn_mpconv_block_forward_fanin.restype = ctypes.c_int
-    L.fgnn_mpconv_block_forward_fanin.argtypes = [dp] + [vp] * 11 + [f32, i32, i32, vp, vp, vp, vp, vp]
-    L.fgnn_factor_layer_param_count.restype = ctypes.c_int64
-    L.fgnn_factor_layer_param_count.argtypes = []
-    L.fgnn_factor_layer_forward.restype = ctypes.c_int
-    L.fgnn_factor_layer_forward.argtypes = [i32] + [vp] * 6 + [vp, i32, i32, vp, i32, i32, vp, i64, vp, i64, vp, vp, vp, i32, f32,
-                                            vp, vp, vp, vp]
-    L.fgnn_flat_adam.restype = ctypes.c_int
-    L.fgnn_flat_adam.argtypes = [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, i64, vp]
-    L.fgnn_flat_adam_dev.restype = ctypes.c_int
-    L.fgnn_flat_adam_dev.argtypes = [vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp, vp, vp]
-    L.fgnn_sum_n.restype = ctypes.c_int
-    L.fgnn_sum_n.argtypes = [vp, i32, i64, i32, vp, vp]
-    L.fgnn_concat_pair.restype = ctypes.c_int
-    L.fgnn_concat_pair.argtypes = [vp, vp, vp] + [i64] * 8 + [vp]
-    L.fgnn_concat_rows.restype = ctypes.c_int
-    L.fgnn_concat_rows.argtypes = [vp, vp, vp] + [i64] * 8 + [vp]
-    L.fgnn_ldpc_decode.restype = ctypes.c_int
-    L.fgnn_ldpc_decode.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.fgnn_ldpc_encode.restype = ctypes.c_int
-    L.fgnn_ldpc_encode.argtypes = [vp, vp, i64, i32, i32, vp, vp]
-    L.fgnn_ldpc_channel_features.restype = ctypes.c_int
-    L.fgnn_ldpc_channel_features.argtypes = [vp, vp, vp, f32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp,
-                                             vp, vp, vp]
-    L.fgnn_ldpc_channel_features_rng.restype = ctypes.c_int
-    L.fgnn_ldpc_channel_features_rng.argtypes = [vp, vp, vp, f32, ctypes.c_uint64, ctypes.c_uint64, vp, vp, i64, i32, i32, i32, i32,
-                                                 i32, vp, vp, vp, vp, vp, vp]
-    L.fgnn_ldpc_received_features.restype = ctypes.c_int
-    L.fgnn_ldpc_received_features.argtypes = [vp, vp, i64, i64, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    L.fgnn_ldpc_error_counts.restype = ctypes.c_int
-    L.fgnn_ldpc_error_counts.argtypes = [vp, i32, i64, vp, i32, i64, vp, i64, vp, i64, i32, vp, i32, vp, i32, vp, vp]
-    L.fgnn_chain_budget_map.restype = ctypes.c_int
-    L.fgnn_chain_budget_map.argtypes = [vp, i64, vp, i64, vp, i64, i64, i32, i32, vp, vp, vp]
-    L.fgnn_chain_budget_map_lds_bytes.restype = i64
-    L.fgnn_chain_budget_map_lds_bytes.argtypes = [i32, i32]
-    L.fgnn_pgm_sample_rng.restype = ctypes.c_int
-    L.fgnn_pgm_sample_rng.argtypes = [i32, ctypes.c_uint64, ctypes.c_uint64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    L.fgnn_chain_budget_lp.restype = ctypes.c_int
-    L.fgnn_chain_budget_lp.argtypes = [vp, i64, vp, i64, vp, i64, i64, i32, i32, i32, ctypes.c_double, ctypes.c_double, i32, vp, vp,
-                                       vp, vp, vp, vp]
-    L.fgnn_chain_budget_lp_lds_bytes.restype = i64
-    L.fgnn_chain_budget_lp_lds_bytes.argtypes = [i32, i32]
-    L.fgnn_chain_budget_score.restype = ctypes.c_int
-    L.fgnn_chain_budget_score.argtypes = [vp, i32, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, i32, vp, vp, vp, vp,
-                                          vp, vp]
-    L.fgnn_pgm_loss_workspace_bytes.restype = i64
-    L.fgnn_pgm_loss_workspace_bytes.argtypes = []
-    L.fgnn_pgm_loss_forward.restype = ctypes.c_int
-    L.fgnn_pgm_loss_forward.argtypes = [vp, i32, i64, i64, i64, vp, i64, vp, i64, i64, i32, vp, vp, vp, i64, vp]
-    L.fgnn_pgm_loss_backward.restype = ctypes.c_int
-    L.fgnn_pgm_loss_backward.argtypes = [vp, i32, i64, i64, i64, vp, i64, vp, i64, i32, vp, i64, i64, i64, vp]
-    L.fgnn_grad_norm_clip_workspace_bytes.restype = i64
-    L.fgnn_grad_norm_clip_workspace_bytes.argtypes = []
-    L.fgnn_grad_norm_clip.restype = ctypes.c_int
-    L.fgnn_grad_norm_clip.argtypes = [vp, i64, f32, f32, vp, vp, i64, vp]
-    L.fgnn_flat_adam_clipped.restype = ctypes.c_int
-    L.fgnn_flat_adam_clipped.argtypes = [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, i64, vp, vp]
-    L.fgnn_flat_adam_dev_clipped.restype = ctypes.c_int
-    L.fgnn_flat_adam_dev_clipped.argtypes = [vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp, vp, vp, vp]
-    L.fgnn_edge_mlp_forward.restype = ctypes.c_int
-    L.fgnn_edge_mlp_forward.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]
-    L.fgnn_edge_mlp_workspace_bytes.restype = i64
-    L.fgnn_edge_mlp_workspace_bytes.argtypes = [i64, i32]
-    L.fgnn_edge_mlp_backward.restype = ctypes.c_int
-    L.fgnn_edge_mlp_backward.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]
-    L.fgnn_block_tail_partials.restype = ctypes.c_int
-    L.fgnn_block_tail_partials.argtypes = [i64, i32]
-    L.fgnn_block_tail_stats.restype = ctypes.c_int
-    L.fgnn_block_tail_stats.argtypes = [vp, vp, vp, f32, vp, vp, i64, i32, vp, fp, vp, vp]
-    L.fgnn_block_tail_apply.restype = ctypes.c_int
-    L.fgnn_block_tail_apply.argtypes = [vp, vp, vp, f32, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i64, i32, vp]
-    L.fgnn_block_tail_backward.restype = ctypes.c_int
-    L.fgnn_block_tail_backward.argtypes = [vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                           i64, i32, vp, i64, vp, vp]
-    L.fgnn_block_tail_moments_bytes.restype = i64
-    L.fgnn_block_tail_moments_bytes.argtypes = [i64, i32]
-    L.fgnn_block_tail_backward_moments.restype = ctypes.c_int
-    L.fgnn_block_tail_backward_moments.argtypes = [vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                   i64, i32, vp, i64, vp, vp, i64, vp]
-    L.fgnn_block_tail_wgrad_finish.restype = ctypes.c_int
-    L.fgnn_block_tail_wgrad_finish.argtypes = [vp, i64, i64, i32, vp, vp, vp, vp, vp]
-    L.fgnn_block_tail_backward_partials.restype = ctypes.c_int
-    L.fgnn_block_tail_backward_partials.argtypes = [i64, i32]
-    L.fgnn_block_head_backward.restype = ctypes.c_int
-    L.fgnn_block_head_backward.argtypes = [vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, i64, i32, vp, i64, vp, vp]
-    L.fgnn_bn_backward_apply.restype = ctypes.c_int
-    L.fgnn_bn_backward_apply.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, f32, vp, vp]
-    L.fgnn_bn_apply.restype = ctypes.c_int
-    L.fgnn_bn_apply.argtypes = [vp, vp, i64, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp]
-    L.fgnn_bn_backward.restype = ctypes.c_int
-    L.fgnn_bn_backward.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, i64, vp, vp]
-    L.fgnn_set_ext_backward_pieces.restype = ctypes.c_int
-    L.fgnn_set_ext_backward_pieces.argtypes = [ctypes.c_int]
-    L.fgnn_spin.restype = ctypes.c_int
-    L.fgnn_spin.argtypes = [ctypes.c_int64, vp]
-    L.fgnn_stamp.restype = ctypes.c_int
-    L.fgnn_stamp.argtypes = [vp, vp]
-    L.fgnn_last_error.restype = ctypes.c_char_p
-    L.fgnn_last_kernel.restype = ctypes.c_char_p
-    L.fgnn_abi_version.restype = ctypes.c_int
+    for name, (restype, params) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, [t for _, t in params]
     _lib = L
     return L
+
+
+def invoke(name, *args):
+    """The entry point ``name`` with the prototype's arguments, exactly (ctypes itself lets extra ones through): tensors go as they
+    are (``DevicePointer``), and a prototype that ends in ``stream`` may be called without it and then runs on torch's current
+    stream.  Returns what the entry point returns.  Tensors stay the caller's to keep alive until this returns."""
+    params = SIGNATURES[name][1]
+    if len(args) == len(params) - 1 and params[-1][0] == 'stream':
+        args += (stream_ptr(),)
+    if len(args) != len(params):
+        raise TypeError('%s takes %d arguments (%s), got %d' % (name, len(params), ', '.join(n for n, _ in params), len(args)))
+    try:
+        return getattr(lib(), name)(*args)
+    except ctypes.ArgumentError as e:       # (ctypes' wrapper around what an argtype's from_param raised, e.g. for a host tensor)
+        raise FgnnHipError('%s: %s' % (name, e)) from None
+
+
+def call(name, *args):
+    """``invoke`` for a launch, i.e. an entry point whose int return is a status: a non-zero status raises.  (A site that
+    branches on the status, such as on EUNSUPPORTED, uses ``invoke``; the size / support queries call ``lib()`` directly.)"""
+    check(invoke(name, *args))
 
 
 def check(rc):

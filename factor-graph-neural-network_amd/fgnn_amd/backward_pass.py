@@ -123,7 +123,7 @@ class BackwardPass:
         """Fold everything recorded, on the current stream (the caller has ordered it behind every producer)."""
         L = _hip.lib()
         if L.fgnn_fold_pending():
-            _hip.check(L.fgnn_fold_flush(_hip.stream_ptr()))
+            _hip.call('fgnn_fold_flush')
             cur = torch.cuda.current_stream()
             for t in self._fold_keep:       # slabs another stream allocated are read by this stream's launch: not that stream's to reuse yet
                 t.record_stream(cur)

@@ -45,8 +45,7 @@ class LdpcDataPath:
         s = s.to(self.device, torch.uint8).contiguous()
         B = s.shape[0]
         cw = torch.empty((B, self.K + self.P), device=self.device, dtype=torch.uint8)
-        _hip.check(_hip.lib().fgnn_ldpc_encode(_hip._ptr(s), _hip._ptr(self.gmask), B, self.K, self.P, _hip._ptr(cw),
-                                               _hip.stream_ptr()))
+        _hip.call('fgnn_ldpc_encode', s, self.gmask, B, self.K, self.P, cw)
         return cw
 
     def channel_features(self, cw, snr_db, sigma_b, burst_prob=0.05, noise=None, generator=None,
@@ -77,17 +76,13 @@ class LdpcDataPath:
         hop = torch.empty((B, 6, 48, 1), device=dev, dtype=dtype)
         ef_f2v = torch.empty((B, 7, 96, 3), device=dev, dtype=dtype)
         ef_v2f = torch.empty((B, 7, 48, 6), device=dev, dtype=dtype)
-        P = _hip._ptr
         if kernel_rng is not None:
             seed, offset = (int(v) & 0xFFFFFFFFFFFFFFFF for v in kernel_rng)
-            _hip.check(_hip.lib().fgnn_ldpc_channel_features_rng(
-                P(cw), P(snr_db), P(sigma_b), float(burst_prob), seed, offset, P(self.var_to_factors), P(self.factor_to_vars),
-                B, 96, 48, 3, 6, _hip.dtype_code(node), P(y), P(node), P(hop), P(ef_f2v), P(ef_v2f), _hip.stream_ptr()))
+            _hip.call('fgnn_ldpc_channel_features_rng', cw, snr_db, sigma_b, float(burst_prob), seed, offset, self.var_to_factors,
+                      self.factor_to_vars, B, 96, 48, 3, 6, _hip.dtype_code(node), y, node, hop, ef_f2v, ef_v2f)
             return y, node, hop, ef_f2v, ef_v2f
-        _hip.check(_hip.lib().fgnn_ldpc_channel_features(
-            P(cw), P(snr_db), P(sigma_b), float(burst_prob), P(z1), P(u), P(z2), P(self.var_to_factors),
-            P(self.factor_to_vars), B, 96, 48, 3, 6, _hip.dtype_code(node), P(y), P(node), P(hop), P(ef_f2v), P(ef_v2f),
-            _hip.stream_ptr()))
+        _hip.call('fgnn_ldpc_channel_features', cw, snr_db, sigma_b, float(burst_prob), z1, u, z2, self.var_to_factors, self.factor_to_vars,
+                  B, 96, 48, 3, 6, _hip.dtype_code(node), y, node, hop, ef_f2v, ef_v2f)
         return y, node, hop, ef_f2v, ef_v2f
 
     def received_features(self, y, snr_db, dtype=torch.float32):
@@ -104,10 +99,8 @@ class LdpcDataPath:
         hop = torch.empty((B, 6, 48, 1), device=dev, dtype=dtype)
         ef_f2v = torch.empty((B, 7, 96, 3), device=dev, dtype=dtype)
         ef_v2f = torch.empty((B, 7, 48, 6), device=dev, dtype=dtype)
-        P = _hip._ptr
-        _hip.check(_hip.lib().fgnn_ldpc_received_features(
-            P(y), P(snr_db), snr_sb, snr_sn, P(self.var_to_factors), P(self.factor_to_vars), B, 96, 48, 3, 6, _hip.dtype_code(node),
-            P(node), P(hop), P(ef_f2v), P(ef_v2f), _hip.stream_ptr()))
+        _hip.call('fgnn_ldpc_received_features', y, snr_db, snr_sb, snr_sn, self.var_to_factors, self.factor_to_vars, B, 96, 48, 3, 6,
+                  _hip.dtype_code(node), node, hop, ef_f2v, ef_v2f)
         return node, hop, ef_f2v, ef_v2f
 
     def make_test_set(self, num, seed=0, snr_db=(0, 1, 2, 3, 4), sigma_b=(0, 1, 2, 3, 4, 5), burst_prob=0.05, baseline=True):
@@ -196,9 +189,7 @@ class LdpcDataPath:
         q1 = torch.empty((B, N), device=self.device, dtype=torch.float64) if want_posteriors else None
         viol = torch.empty((B,), device=self.device, dtype=torch.int32)
         iters = torch.empty((B,), device=self.device, dtype=torch.int32)
-        P = _hip._ptr
-        _hip.check(_hip.lib().fgnn_ldpc_decode(P(bias), P(col_ptr), P(row_ptr), P(row_edge), P(row_var), B, N, M, E,
-                                               int(loops), P(x), P(q1), P(viol), P(iters), _hip.stream_ptr()))
+        _hip.call('fgnn_ldpc_decode', bias, col_ptr, row_ptr, row_edge, row_var, B, N, M, E, int(loops), x, q1, viol, iters)
         return (x, viol, iters, q1) if want_posteriors else (x, viol, iters)
 
     def sample(self, B, seed=0, dtype=torch.float32, snr_db=None, burst_prob=0.05, kernel_rng=False, step=0):

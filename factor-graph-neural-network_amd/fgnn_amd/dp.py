@@ -237,10 +237,9 @@ class FlatAdam:
     def _measure(self, g, grad_scale):
         """The norm launches in front of a clipped update; returns the device pointer of the coefficient."""
         from . import _hip
-        P = _hip._ptr
-        _hip.check(_hip.lib().fgnn_grad_norm_clip(P(g), g.numel(), self.max_grad_norm, float(grad_scale), P(self._norm),
-                                                  P(self._norm_ws), self._norm_ws.numel() * 8, _hip.stream_ptr()))
-        return P(self._norm[1:])
+        _hip.call('fgnn_grad_norm_clip', g, g.numel(), self.max_grad_norm, float(grad_scale), self._norm, self._norm_ws,
+                  self._norm_ws.numel() * 8)
+        return self._norm[1:]
 
     @property
     def lr(self):
@@ -272,13 +271,12 @@ class FlatAdam:
         b1, b2 = self.betas
         if self.capturable:
             from . import _hip
-            P = _hip._ptr
-            args = (P(p), P(g), P(self.exp_avg), P(self.exp_avg_sq), None, p.numel(), P(self._lr_dev), float(b1), float(b2),
-                    float(self.eps), float(self.weight_decay), float(grad_scale), P(self._step_dev), P(self._coef_dev))
+            args = (p, g, self.exp_avg, self.exp_avg_sq, None, p.numel(), self._lr_dev, float(b1), float(b2),
+                    float(self.eps), float(self.weight_decay), float(grad_scale), self._step_dev, self._coef_dev)
             if self.max_grad_norm is not None:
-                _hip.check(_hip.lib().fgnn_flat_adam_dev_clipped(*args, self._measure(g, grad_scale), _hip.stream_ptr()))
+                _hip.call('fgnn_flat_adam_dev_clipped', *args, self._measure(g, grad_scale))
             else:
-                _hip.check(_hip.lib().fgnn_flat_adam_dev(*args, _hip.stream_ptr()))
+                _hip.call('fgnn_flat_adam_dev', *args)
             from .mpnn import pointwise
             pointwise.invalidate_casts()
             pointwise.note_state_change()
@@ -286,13 +284,12 @@ class FlatAdam:
         self._t += 1
         if p.is_cuda:
             from . import _hip
-            P = _hip._ptr
-            args = (P(p), P(g), P(self.exp_avg), P(self.exp_avg_sq), None, p.numel(), float(self.lr), float(b1), float(b2),
+            args = (p, g, self.exp_avg, self.exp_avg_sq, None, p.numel(), float(self.lr), float(b1), float(b2),
                     float(self.eps), float(self.weight_decay), float(grad_scale), int(self._t))
             if self.max_grad_norm is not None:
-                _hip.check(_hip.lib().fgnn_flat_adam_clipped(*args, self._measure(g, grad_scale), _hip.stream_ptr()))
+                _hip.call('fgnn_flat_adam_clipped', *args, self._measure(g, grad_scale))
             else:
-                _hip.check(_hip.lib().fgnn_flat_adam(*args, _hip.stream_ptr()))
+                _hip.call('fgnn_flat_adam', *args)
         else:
             if self.max_grad_norm is not None:       # the kernels' rule: f64 sum of squares, one rounding, torch's coefficient in f32
                 norm = (g.double().square().sum().sqrt() * grad_scale).float()

@@ -23,11 +23,8 @@ class _EdgeMLPFn(torch.autograd.Function):
             x = x.contiguous()
         x_sr = x.stride(3) if k > 1 else x.stride(2)
         y = torch.empty((B, M, k, net), device=x.device, dtype=x.dtype)
-        L = _hip.lib()
         ops.timed('edge_mlp_fwd_kernel (MFMA where the layout allows)', 2 * B * E * (cin + net),
-                  lambda: _hip.check(L.fgnn_edge_mlp_forward(
-                      _hip._ptr(x), x.stride(0), x.stride(1), x_sr, _hip._ptr(w1), _hip._ptr(b1), _hip._ptr(w2),
-                      _hip._ptr(b2), _hip._ptr(y), B, E, cin, net, _hip.stream_ptr())),
+                  lambda: _hip.call('fgnn_edge_mlp_forward', x, x.stride(0), x.stride(1), x_sr, w1, b1, w2, b2, y, B, E, cin, net),
                   nflops=2 * B * E * 64 * (cin + net))
         ctx.save_for_backward(x, w1, b1, w2)
         ctx.params = (w1, b1, w2, b2)
@@ -53,11 +50,8 @@ class _EdgeMLPFn(torch.autograd.Function):
         L = _hip.lib()
         ws = ops._workspace(x.device, int(L.fgnn_edge_mlp_workspace_bytes(B, E)))
         ops.timed('edge_mlp_bwd_kernel (MFMA where the layout allows)', 2 * B * E * (cin + net),
-                  lambda: _hip.check(L.fgnn_edge_mlp_backward(
-                      _hip._ptr(x), x.stride(0), x.stride(1), ctx.x_sr, _hip._ptr(gy), gy.stride(0), gy.stride(1),
-                      gy_sr, _hip._ptr(w1), _hip._ptr(b1), _hip._ptr(w2), B, E, cin, net, _hip._ptr(outs[0]),
-                      _hip._ptr(outs[1]), _hip._ptr(outs[2]), _hip._ptr(outs[3]), _hip._ptr(ws), ws.numel() * 4,
-                      _hip.stream_ptr())),
+                  lambda: _hip.call('fgnn_edge_mlp_backward', x, x.stride(0), x.stride(1), ctx.x_sr, gy, gy.stride(0), gy.stride(1), gy_sr,
+                                    w1, b1, w2, B, E, cin, net, outs[0], outs[1], outs[2], outs[3], ws, ws.numel() * 4),
                   nflops=2 * B * E * 64 * (2 * cin + 2 * net))
         return (None, *[grads.result(i, p.dtype) for i, p in enumerate(ctx.params)])
 

@@ -51,7 +51,7 @@ class StepGraph:
         with torch.cuda.graph(self.graph, stream=self.stream):
             if delay_ms > 0:
                 from . import _hip
-                _hip.check(_hip.lib().fgnn_spin(int(delay_ms * 1e5), _hip.stream_ptr()))
+                _hip.call('fgnn_spin', int(delay_ms * 1e5))
             ops.stamp('step begin')
             fn()
             ops.stamp('step end')

@@ -106,9 +106,8 @@ class _DecodingLoss(torch.autograd.Function):
         from . import ops
         loss = torch.empty((), device=logits.device, dtype=torch.float32)
         ws = ops._workspace(logits.device, int(_hip.lib().fgnn_ldpc_loss_workspace_bytes()))
-        _hip.check(_hip.lib().fgnn_ldpc_loss_forward(_hip._ptr(logits), _hip._ptr(label), _hip._ptr(pred), _hip._ptr(sigma_b), B, n,
-                                                     _hip.dtype_code(logits), mse_weight, _hip._ptr(loss), _hip._ptr(ws), ws.numel() * 4,
-                                                     _hip.stream_ptr()))
+        _hip.call('fgnn_ldpc_loss_forward', logits, label, pred, sigma_b, B, n, _hip.dtype_code(logits), mse_weight, loss, ws,
+                  ws.numel() * 4)
         ctx.save_for_backward(logits, pred, label, sigma_b)
         ctx.mse_weight = mse_weight
         return loss
@@ -120,9 +119,7 @@ class _DecodingLoss(torch.autograd.Function):
         B, n = logits.shape
         gl, gp = torch.empty_like(logits), torch.empty_like(pred)
         gloss = gloss.float().contiguous()
-        _hip.check(_hip.lib().fgnn_ldpc_loss_backward(_hip._ptr(logits), _hip._ptr(label), _hip._ptr(pred), _hip._ptr(sigma_b),
-                                                      _hip._ptr(gloss), B, n, _hip.dtype_code(logits), ctx.mse_weight, _hip._ptr(gl),
-                                                      _hip._ptr(gp), _hip.stream_ptr()))
+        _hip.call('fgnn_ldpc_loss_backward', logits, label, pred, sigma_b, gloss, B, n, _hip.dtype_code(logits), ctx.mse_weight, gl, gp)
         return gl, gp, None, None, None
 
 

@@ -93,11 +93,9 @@ class LdpcErrorCounts:
         snr_db = snr_db.to(dev, torch.float32)
         snr0 = snr_db if snr_db.dim() == 1 else snr_db[:, 0]
         sigma_b = sigma_b.to(dev, torch.float32).contiguous()
-        P = _hip._ptr
-        _hip.check(_hip.lib().fgnn_ldpc_error_counts(
-            P(dec), kind, dec.stride(0), P(label), _hip.LABEL_I64 if label.dtype == torch.int64 else _hip.LABEL_U8, label.stride(0),
-            P(snr0), snr0.stride(0), P(sigma_b), B, int(nbits), P(self._snr), len(self.snr_grid), P(self._sigma),
-            len(self.sigma_grid), P(self.counts), _hip.stream_ptr()))
+        _hip.call('fgnn_ldpc_error_counts', dec, kind, dec.stride(0), label,
+                  _hip.LABEL_I64 if label.dtype == torch.int64 else _hip.LABEL_U8, label.stride(0), snr0, snr0.stride(0), sigma_b, B,
+                  int(nbits), self._snr, len(self.snr_grid), self._sigma, len(self.sigma_grid), self.counts)
 
     def result(self):
         """One read-back.  ``ber``: 1 - right / compared over every word (train_ldpc.py:326); ``err_class`` [n_snr, n_sigma]:

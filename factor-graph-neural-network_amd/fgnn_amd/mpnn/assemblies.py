@@ -298,15 +298,14 @@ class FactorNN(torch.nn.Module):
             f1 = f1.contiguous()
         if s1 is not None and not s1.is_contiguous():
             s1 = s1.contiguous()
-        P = _hip._ptr
         rcs = []
         # algorithmic bytes: the state read and written once (+ the skip terms), the parity edge types, the parameters
         nstate = B * (96 + 48 + 1) * 64 * 2
         nbytes = nstate * (3 if skip is not None else 2) + 2 * 288 * 4 * 2 * (B if ev.stride(0) else 1) + params.numel() * 4
-        _ops.timed('factor_layer_fwd_kernel', nbytes, lambda: rcs.append(_hip.lib().fgnn_factor_layer_forward(
-            B, P(var), P(fac[0]), P(f1), P(skip[0]) if skip is not None else None, P(skip[1][0]) if skip is not None else None,
-            P(s1), P(iv), iv.stride(1), iv.stride(2), P(if_), if_.stride(1), if_.stride(2), P(ev), ev.stride(0), P(ef), ef.stride(0),
-            P(hev), P(hef), P(params), 1, float(blocks[0].conv1[1].slope), P(new_var), P(new_f0), P(new_f1), _hip.stream_ptr())),
+        _ops.timed('factor_layer_fwd_kernel', nbytes, lambda: rcs.append(_hip.invoke(
+            'fgnn_factor_layer_forward', B, var, fac[0], f1, skip[0] if skip is not None else None,
+            skip[1][0] if skip is not None else None, s1, iv, iv.stride(1), iv.stride(2), if_, if_.stride(1), if_.stride(2), ev,
+            ev.stride(0), ef, ef.stride(0), hev, hef, params, 1, float(blocks[0].conv1[1].slope), new_var, new_f0, new_f1)),
             nflops=B * 2 * 64 * (64 * (96 * 5 + 48 * 3 + 3) + 256 * (96 + 48) + 64 * 96))
         rc = rcs[0]
         if rc == _hip.EUNSUPPORTED:

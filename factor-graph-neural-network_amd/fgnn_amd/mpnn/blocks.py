@@ -93,11 +93,10 @@ class iid_mapping_in(torch.nn.Module):
         b = None if conv.bias is None else conv.bias.detach().float().contiguous()
         z = torch.empty((B * N, cout), device=x.device, dtype=torch.bfloat16) if grad else None
         y = torch.empty((B, N, 1, cout), device=x.device, dtype=torch.bfloat16)
-        L = _hip.lib()
         rc = []
         ops.timed('linear_instnorm_fwd_kernel', 2 * B * N * (C + cout * (2 if grad else 1)),
-                  lambda: rc.append(L.fgnn_linear_instnorm_forward(_hip._ptr(rows), _hip._ptr(w), _hip._ptr(b), _hip._ptr(z), _hip._ptr(y),
-                                                                   B, N, C, cout, int(norm.relu), float(norm.eps), _hip.stream_ptr())),
+                  lambda: rc.append(_hip.invoke('fgnn_linear_instnorm_forward', rows, w, b, z, y, B, N, C, cout, int(norm.relu),
+                                                float(norm.eps))),
                   nflops=2 * B * N * C * cout)
         if rc[0] == _hip.EUNSUPPORTED:
             return None
@@ -151,16 +150,14 @@ class _BlockHead(torch.autograd.Function):
     def forward(ctx, rows, weight, bias, bn_w, bn_b, handoff, slope, box=None):
         """``handoff``: BatchNorm1's ``BnHandoff``; ``bn_w`` / ``bn_b`` are its gamma / beta as arguments of their own, for autograd."""
         ctx.box = box                   # the ops.FanBox of the state `rows` views: the backward deposits (gz1, W1) there instead of forming gx
-        L = _hip.lib()
-        P = _hip._ptr
         z1 = pointwise.hip_linear(rows, weight, bias, bn=handoff)       # the map's last workgroup finalises BatchNorm1's statistics
         if z1 is None:
             raise _hip.FgnnHipError('fused block head: the 1x1 map is outside csrc/linear_fwd_b16.hip (checked by the caller)')
         R = rows.shape[0]
         stats = handoff.batch_stats(z1)                               # [4, 64] mean, invstd, scale, shift
         a1 = torch.empty_like(z1)
-        ops.timed('bn_apply (forward)', 2 * z1.numel() * 2, lambda: _hip.check(L.fgnn_bn_apply(
-            P(z1), P(a1), R, 64, _hip.BF16, P(stats[2]), P(stats[3]), slope, None, None, None, None, _hip.stream_ptr())))
+        ops.timed('bn_apply (forward)', 2 * z1.numel() * 2, lambda: _hip.call(
+            'fgnn_bn_apply', z1, a1, R, 64, _hip.BF16, stats[2], stats[3], slope, None, None, None, None))
         ctx.save_for_backward(rows, z1, stats, weight, bn_w, bn_b)
         ctx.slope = slope
         ctx.params = (weight, bias, bn_w, bn_b)
@@ -170,7 +167,6 @@ class _BlockHead(torch.autograd.Function):
     def backward(ctx, ga1):
         ops.backward_node_begins()
         L = _hip.lib()
-        P = _hip._ptr
         rows, z1, stats, weight, bn_w, bn_b = ctx.saved_tensors
         pW, pbias, pw, pb = ctx.params
         R, cin = rows.shape
@@ -186,9 +182,9 @@ class _BlockHead(torch.autograd.Function):
         lazy = ctx.needs_input_grad[0] and ctx.box is not None and weight.is_contiguous() and weight.dtype == torch.float32
         gx = None if lazy else torch.empty((R, cin), device=dev, dtype=z1.dtype)
         ws = ops._workspace(dev, int(L.fgnn_bn_workspace_bytes(R, 64)))
-        ops.timed('block_head_backward (reduce + finalise + grad)', 2 * R * (5 * 64 + cin), lambda: _hip.check(L.fgnn_block_head_backward(
-            P(z1), P(ga1), P(stats[0]), P(stats[1]), P(bn_w.detach()), P(bn_b.detach()), ctx.slope, P(weight.detach()), P(gz1), P(gx),
-            P(gw1), P(gb1), R, cin, P(ws), ws.numel() * 4, P(ops._fold_scratch(dev)), _hip.stream_ptr())), nflops=2 * R * 64 * cin)
+        ops.timed('block_head_backward (reduce + finalise + grad)', 2 * R * (5 * 64 + cin), lambda: _hip.call(
+            'fgnn_block_head_backward', z1, ga1, stats[0], stats[1], bn_w.detach(), bn_b.detach(), ctx.slope, weight.detach(), gz1, gx, gw1,
+            gb1, R, cin, ws, ws.numel() * 4, ops._fold_scratch(dev)), nflops=2 * R * 64 * cin)
 
         taken = 0
         if lazy:
@@ -275,7 +271,6 @@ class _BlockTail(torch.autograd.Function):
         statistics stand for in the running variances (0 = R; R * m for a per-sample vector the reference broadcasts over m nodes).
         ``periods``: see ``_AddendRoute``."""
         L = _hip.lib()
-        P = _hip._ptr
         R, Cout = e.shape[0], W2.shape[0]
         dev = e.device
         # BatchNorm2: the operator's epilogue finalised it, else one reducing launch
@@ -288,16 +283,16 @@ class _BlockTail(torch.autograd.Function):
         bias2c = None if bias2 is None else bias2.detach()
         flops = 2 * R * 64 * Cout
         st3, fin3 = bn3.final(Cout, dev, R, population)
-        ops.timed('block_tail_stats_kernel', 2 * R * 64, lambda: _hip.check(L.fgnn_block_tail_stats(
-            P(e), P(st2[2]), P(st2[3]), slope2, P(W2c), P(bias2c), R, Cout, P(ws), fin3, P(fold), _hip.stream_ptr())), nflops=flops)
+        ops.timed('block_tail_stats_kernel', 2 * R * 64, lambda: _hip.call(
+            'fgnn_block_tail_stats', e, st2[2], st2[3], slope2, W2c, bias2c, R, Cout, ws, fin3, fold), nflops=flops)
         out = torch.empty((R, Cout), device=dev, dtype=e.dtype)
         if callable(add0):          # the addends come from another stream: asked for (and waited on) only HERE, behind the statistics
             (add0, add1, add2), periods = add0()   # pass, which does not read them (the join used to sit in front of it)
         adds = (add0, add1, add2)
         nadd = sum(a is not None for a in adds)
-        ops.timed('block_tail_apply_kernel', 2 * R * (2 * 64 + (1 + nadd) * Cout), lambda: _hip.check(L.fgnn_block_tail_apply(
-            P(e), P(st2[2]), P(st2[3]), slope2, P(W2c), P(bias2c), P(st3[2]), P(st3[3]), slope3, P(add0), P(add1), P(add2),
-            pointwise.period_array(periods), P(out), P(a2), R, Cout, _hip.stream_ptr())), nflops=flops)
+        ops.timed('block_tail_apply_kernel', 2 * R * (2 * 64 + (1 + nadd) * Cout), lambda: _hip.call(
+            'fgnn_block_tail_apply', e, st2[2], st2[3], slope2, W2c, bias2c, st3[2], st3[3], slope3, add0, add1, add2,
+            pointwise.period_array(periods), out, a2, R, Cout), nflops=flops)
         pointwise.note_state_change()                   # running statistics / num_batches_tracked were just updated in place
         ctx.save_for_backward(e, a2, st2, st3, w2, b2, W2, w3)
         ctx.slopes = (slope2, slope3)
@@ -310,7 +305,6 @@ class _BlockTail(torch.autograd.Function):
     def backward(ctx, gout):
         ops.backward_node_begins()
         L = _hip.lib()
-        P = _hip._ptr
         e, a2, st2, st3, w2, b2, W2, w3 = ctx.saved_tensors
         slope2, slope3 = ctx.slopes
         pw2, pb2, pW2, pbias2, pw3, pb3 = ctx.params
@@ -337,23 +331,20 @@ class _BlockTail(torch.autograd.Function):
             # nor a2 exists in memory; the buffer (slabs, A, Bc) is this call's own until the finish launch below has run
             mom = torch.empty(int(L.fgnn_block_tail_moments_bytes(R, Cout)) // 4, device=dev, dtype=torch.float32)
             ops.timed('block_tail_backward (reduce + moments + grad)', 2 * R * (2 * 64 + 2 * Cout + 64),
-                      lambda: _hip.check(L.fgnn_block_tail_backward_moments(
-                          P(e), P(st2[2]), P(st2[3]), slope2, P(W2.detach()), P(bias2c), P(st3[0]), P(st3[1]), P(w3.detach()), P(st3[2]),
-                          P(st3[3]), slope3, P(gout), None, P(ga2), P(gw3), P(gb3), P(st2[0]), P(st2[1]), P(gw2), P(gb2), P(dsum2),
-                          R, Cout, P(ws), ws.numel() * 4, P(ops._fold_scratch(dev)), P(mom), mom.numel() * 4, _hip.stream_ptr())),
+                      lambda: _hip.call('fgnn_block_tail_backward_moments', e, st2[2], st2[3], slope2, W2.detach(), bias2c, st3[0], st3[1],
+                                        w3.detach(), st3[2], st3[3], slope3, gout, None, ga2, gw3, gb3, st2[0], st2[1], gw2, gb2, dsum2, R,
+                                        Cout, ws, ws.numel() * 4, ops._fold_scratch(dev), mom, mom.numel() * 4),
                       nflops=8 * R * 64 * Cout)
         else:
             ops.timed('block_tail_backward (reduce + grad)', 2 * R * (2 * 64 + 2 * Cout + 64 + Cout),
-                      lambda: _hip.check(L.fgnn_block_tail_backward(
-                          P(e), P(st2[2]), P(st2[3]), slope2, P(W2.detach()), P(bias2c), P(st3[0]), P(st3[1]), P(w3.detach()), P(st3[2]),
-                          P(st3[3]), slope3, P(gout), P(gz3), P(ga2), P(gw3), P(gb3), P(st2[0]), P(st2[1]), P(gw2), P(gb2), P(dsum2),
-                          R, Cout, P(ws), ws.numel() * 4, P(ops._fold_scratch(dev)), _hip.stream_ptr())),
+                      lambda: _hip.call('fgnn_block_tail_backward', e, st2[2], st2[3], slope2, W2.detach(), bias2c, st3[0], st3[1],
+                                        w3.detach(), st3[2], st3[3], slope3, gout, gz3, ga2, gw3, gb3, st2[0], st2[1], gw2, gb2, dsum2, R,
+                                        Cout, ws, ws.numel() * 4, ops._fold_scratch(dev)),
                       nflops=6 * R * 64 * Cout)
         # BatchNorm2 + activation backward on the 64-channel tensor: one element-wise pass (no reduction pass, no finaliser)
         ge = torch.empty_like(e)
-        ops.timed('bn_backward (apply)', 3 * e.numel() * 2, lambda: _hip.check(L.fgnn_bn_backward_apply(
-            P(e), P(ga2), P(ge), R, 64, _hip.BF16, P(st2[0]), P(st2[1]), P(w2.detach()), P(b2.detach()), slope2, P(dsum2),
-            _hip.stream_ptr())))
+        ops.timed('bn_backward (apply)', 3 * e.numel() * 2, lambda: _hip.call(
+            'fgnn_bn_backward_apply', e, ga2, ge, R, 64, _hip.BF16, st2[0], st2[1], w2.detach(), b2.detach(), slope2, dsum2))
         # conv2's weight / bias gradient: gz3^T a2 over the R rows (csrc/linear_wgrad_b16.hip); parked when it goes to the flat
         # bucket (backward_pass.run_wgrad: nothing in the backward reads it)
         if moments:
@@ -361,8 +352,8 @@ class _BlockTail(torch.autograd.Function):
 
             def launch(record, mom=mom, gW2=gW2, scale3=scale3, W2d=W2.detach(), bias2c=bias2c):
                 # (conv2's BIAS gradient in front of a batch-statistics BatchNorm is identically zero — sum gz3 = 0 — nothing is added to it)
-                ops.timed('block_tail_wgrad_finish (fold + combine)', 4 * mom.numel(), lambda: _hip.check(L.fgnn_block_tail_wgrad_finish(
-                    P(mom), mom.numel() * 4, R, Cout, P(W2d), P(bias2c), P(scale3), P(gW2.view(Cout, 64)), _hip.stream_ptr())))
+                ops.timed('block_tail_wgrad_finish (fold + combine)', 4 * mom.numel(), lambda: _hip.call(
+                    'fgnn_block_tail_wgrad_finish', mom, mom.numel() * 4, R, Cout, W2d, bias2c, scale3, gW2.view(Cout, 64)))
             operands = (mom, scale3)
         else:
             def launch(record, a2=a2, gz3=gz3, gW2=gW2, gbias2=gbias2):
@@ -474,11 +465,9 @@ class mp_conv_residual(base_mp_nn):
         y = torch.empty((B, M, 1, nout), device=x.device, dtype=x.dtype).permute(0, 3, 1, 2)
         d = _hip.make_desc(x, nn_idx, etype, 64, mp.nedge_types, _hip.EXT_NONE, _hip.AGG_MAX, True, y)
         d.nin = 64                      # the inner operator's width; x / y strides stay the block's
-        P = _hip._ptr
         if fanin:
-            rc = _hip.lib().fgnn_mpconv_block_forward_fanin(ctypes.byref(d), P(x), P(etype), P(W1), P(s1), P(t1), P(F),
-                                                            P(s2), P(t2), P(W2), P(s3), P(t3), float(bn1.slope), nin, nout,
-                                                            P(a0), P(a1), P(a2), P(y), _hip.stream_ptr())
+            rc = _hip.invoke('fgnn_mpconv_block_forward_fanin', ctypes.byref(d), x, etype, W1, s1, t1, F, s2, t2, W2, s3, t3,
+                             float(bn1.slope), nin, nout, a0, a1, a2, y)
             if rc == _hip.EUNSUPPORTED:
                 return None
             _hip.check(rc)
@@ -490,22 +479,20 @@ class mp_conv_residual(base_mp_nn):
             et1 = etype[:, :, :1, :]
             d1 = _hip.make_desc(x, nn_idx[:, :1, :], et1, 64, 1, _hip.EXT_NONE, _hip.AGG_MAX, True, y1)
             d1.nin = 64
-            rc = _hip.lib().fgnn_mpconv_block_forward_fanout(ctypes.byref(d1), P(x), P(et1), P(W1), P(s1), P(t1), P(F), P(s2), P(t2), P(W2),
-                                                             P(s3), P(t3), float(bn1.slope), nin, nout, None, None, None, P(y1), _hip.stream_ptr())
+            rc = _hip.invoke('fgnn_mpconv_block_forward_fanout', ctypes.byref(d1), x, et1, W1, s1, t1, F, s2, t2, W2, s3, t3,
+                             float(bn1.slope), nin, nout, None, None, None, y1)
             if rc != _hip.EUNSUPPORTED:
                 _hip.check(rc)
                 return ops.broadcast_nodes(y1, M)
         if fanout:
-            rc = _hip.lib().fgnn_mpconv_block_forward_fanout(ctypes.byref(d), P(x), P(etype), P(W1), P(s1), P(t1), P(F),
-                                                             P(s2), P(t2), P(W2), P(s3), P(t3), float(bn1.slope), nin, nout,
-                                                             P(a0), P(a1), P(a2), P(y), _hip.stream_ptr())
+            rc = _hip.invoke('fgnn_mpconv_block_forward_fanout', ctypes.byref(d), x, etype, W1, s1, t1, F, s2, t2, W2, s3, t3,
+                             float(bn1.slope), nin, nout, a0, a1, a2, y)
             if rc == _hip.EUNSUPPORTED:
                 return None
             _hip.check(rc)
             return y
-        rc = _hip.lib().fgnn_mpconv_block_forward_rows(ctypes.byref(d), P(x), P(nn_idx), P(etype), P(W1), P(s1), P(t1), P(F),
-                                                       P(s2), P(t2), P(W2), P(s3), P(t3), float(bn1.slope), nin, nout, P(a0), P(a1),
-                                                       P(a2), row_mask, P(y), _hip.stream_ptr())
+        rc = _hip.invoke('fgnn_mpconv_block_forward_rows', ctypes.byref(d), x, nn_idx, etype, W1, s1, t1, F, s2, t2, W2, s3, t3,
+                         float(bn1.slope), nin, nout, a0, a1, a2, row_mask, y)
         if rc == _hip.EUNSUPPORTED:
             return None
         _hip.check(rc)

@@ -171,8 +171,8 @@ class BnHandoff:
         stats, fin = self.final(C, rows.device, R, population, running=self.stats is None)
         ws = ops._workspace(rows.device, int(L.fgnn_bn_workspace_bytes(R, C)))
         fold = ops._fold_scratch(rows.device)
-        ops.timed('bn_stats (reduce + finalise)', rows.numel() * rows.element_size(), lambda: _hip.check(L.fgnn_bn_stats(
-            _hip._ptr(rows), R, C, _hip.dtype_code(rows), fin, _hip._ptr(ws), ws.numel() * 4, _hip._ptr(fold), _hip.stream_ptr())))
+        ops.timed('bn_stats (reduce + finalise)', rows.numel() * rows.element_size(), lambda: _hip.call(
+            'fgnn_bn_stats', rows, R, C, _hip.dtype_code(rows), fin, ws, ws.numel() * 4, fold))
         note_state_change()
         return stats
 
@@ -208,8 +208,7 @@ def hip_linear(rows, weight, bias, bn=None, transposed=False):
         fold = ops._fold_scratch(rows.device)
         stats, fin = bn.final(cout, rows.device, R)
     ops.timed('linear_fwd_b16_kernel', 2 * R * (cin + cout),
-              lambda: _hip.check(L.fgnn_linear_forward(_hip._ptr(rows), _hip._ptr(w), _hip._ptr(b), _hip._ptr(y), R, cin,
-                                                       cout, _hip._ptr(ws), fin, _hip._ptr(fold), int(transposed), _hip.stream_ptr())),
+              lambda: _hip.call('fgnn_linear_forward', rows, w, b, y, R, cin, cout, ws, fin, fold, int(transposed)),
               nflops=2 * R * cin * cout)
     if bn is not None:
         bn.record(y, stats)
@@ -223,8 +222,8 @@ def node_sum(g, M):
     g = g.contiguous()
     out = torch.empty((R // M, C), device=g.device, dtype=g.dtype)
     rc = []
-    ops.timed('node_sum_kernel', g.numel() * g.element_size(), lambda: rc.append(_hip.lib().fgnn_node_sum(
-        _hip._ptr(g), _hip._ptr(out), R // M, M, C, _hip.dtype_code(g), _hip.stream_ptr())))
+    ops.timed('node_sum_kernel', g.numel() * g.element_size(), lambda: rc.append(_hip.invoke(
+        'fgnn_node_sum', g, out, R // M, M, C, _hip.dtype_code(g))))
     if rc[0] == _hip.EUNSUPPORTED:
         # channel counts outside the kernel's 16-byte chunks (C % 8 for bf16, % 4 for f32): the broadcast path is taken for any
         # width (ops.single_source_fanout), so its backward must exist for any width too — a device-side f32 sum
@@ -355,9 +354,7 @@ class _InstNormAct(torch.autograd.Function):
             return precomputed.permute(0, 3, 1, 2)
         y = torch.empty_like(rows)
         ops.timed('instnorm_fwd_kernel', 2 * rows.numel() * rows.element_size(),
-                  lambda: _hip.check(_hip.lib().fgnn_instnorm_forward(_hip._ptr(rows), _hip._ptr(y), B, N, C,
-                                                                      _hip.dtype_code(rows), int(relu),
-                                                                      _hip.stream_ptr())))
+                  lambda: _hip.call('fgnn_instnorm_forward', rows, y, B, N, C, _hip.dtype_code(rows), int(relu)))
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
@@ -370,9 +367,7 @@ class _InstNormAct(torch.autograd.Function):
             g = g.to(rows.dtype).contiguous()
         gx = torch.empty_like(rows)
         ops.timed('instnorm_bwd_kernel', 3 * rows.numel() * rows.element_size(),
-                  lambda: _hip.check(_hip.lib().fgnn_instnorm_backward(_hip._ptr(rows), _hip._ptr(g), _hip._ptr(gx), B, N,
-                                                                       C, _hip.dtype_code(rows), int(ctx.relu),
-                                                                       _hip.stream_ptr())))
+                  lambda: _hip.call('fgnn_instnorm_backward', rows, g, gx, B, N, C, _hip.dtype_code(rows), int(ctx.relu)))
         return gx.permute(0, 3, 1, 2), None, None
 
 
@@ -389,9 +384,8 @@ class _InstNormDot(torch.autograd.Function):
             rows = rows.contiguous()
         w = weight.detach().reshape(C)
         out = torch.empty((B, 1, N, 1), device=x.device, dtype=x.dtype)
-        ops.timed('instnorm_dot_kernel<fwd>', rows.numel() * rows.element_size(), lambda: _hip.check(
-            _hip.lib().fgnn_instnorm_dot_forward(_hip._ptr(rows), _hip._ptr(w), _hip._ptr(None if bias is None else bias.detach()),
-                                                 _hip._ptr(out), B, N, C, _hip.dtype_code(rows), _hip.stream_ptr())))
+        ops.timed('instnorm_dot_kernel<fwd>', rows.numel() * rows.element_size(), lambda: _hip.call(
+            'fgnn_instnorm_dot_forward', rows, w, None if bias is None else bias.detach(), out, B, N, C, _hip.dtype_code(rows)))
         ctx.save_for_backward(rows, weight)
         ctx.params = (weight, bias)
         return out
@@ -410,10 +404,8 @@ class _InstNormDot(torch.autograd.Function):
         gw, gb = grads.acc('weight', wparam, wparam.shape), grads.acc('bias', bparam, (1,))
         gx = torch.empty_like(rows)
         ws = ops._workspace(rows.device, int(L.fgnn_instnorm_dot_workspace_bytes(B)))
-        ops.timed('instnorm_dot_kernel<bwd>', 2 * rows.numel() * rows.element_size(), lambda: _hip.check(
-            L.fgnn_instnorm_dot_backward(_hip._ptr(rows), _hip._ptr(weight.detach()), _hip._ptr(g), _hip._ptr(gx), _hip._ptr(gw),
-                                         _hip._ptr(gb), B, N, C, _hip.dtype_code(rows), _hip._ptr(ws), ws.numel() * 4,
-                                         _hip.stream_ptr())))
+        ops.timed('instnorm_dot_kernel<bwd>', 2 * rows.numel() * rows.element_size(), lambda: _hip.call(
+            'fgnn_instnorm_dot_backward', rows, weight.detach(), g, gx, gw, gb, B, N, C, _hip.dtype_code(rows), ws, ws.numel() * 4))
         return gx.permute(0, 3, 1, 2), grads.result('weight', wparam.dtype), grads.result('bias', None if bparam is None else bparam.dtype)
 
 
@@ -435,10 +427,9 @@ def instnorm_relu_dot(x, conv):
     if not rows.is_contiguous():
         rows = rows.contiguous()
     out = torch.empty((B, 1, N, 1), device=x.device, dtype=x.dtype)
-    ops.timed('instnorm_dot_kernel<fwd>', rows.numel() * rows.element_size(), lambda: _hip.check(
-        _hip.lib().fgnn_instnorm_dot_forward(_hip._ptr(rows), _hip._ptr(conv.weight.detach()),
-                                             _hip._ptr(None if conv.bias is None else conv.bias.detach()),
-                                             _hip._ptr(out), B, N, C, _hip.dtype_code(rows), _hip.stream_ptr())))
+    ops.timed('instnorm_dot_kernel<fwd>', rows.numel() * rows.element_size(), lambda: _hip.call(
+        'fgnn_instnorm_dot_forward', rows, conv.weight.detach(), None if conv.bias is None else conv.bias.detach(), out, B, N, C,
+        _hip.dtype_code(rows)))
     return out
 
 
@@ -513,7 +504,6 @@ class _BatchNormAct(torch.autograd.Function):
         front of it); ``weight`` / ``bias`` are its gamma / beta as arguments of their own, for autograd.  ``periods``: an addend
         with period m has one row per m rows of the output (a per-sample vector broadcast over the sample's m nodes).
         ``population``: rows the statistics stand for in the running variance's unbiased correction (0 = R)."""
-        L = _hip.lib()
         R, C = rows.shape
         dt = _hip.dtype_code(rows)
         stats = handoff.batch_stats(rows, population)
@@ -521,9 +511,8 @@ class _BatchNormAct(torch.autograd.Function):
         ctx.has_addend = tuple(a is not None for a in (addend, addend2, addend3))
         ctx.periods = tuple(periods)
         ops.timed('bn_apply (forward)', (2 + sum(ctx.has_addend)) * rows.numel() * rows.element_size(),
-                  lambda: _hip.check(L.fgnn_bn_apply(_hip._ptr(rows), _hip._ptr(y), R, C, dt, _hip._ptr(stats[2]),
-                                                     _hip._ptr(stats[3]), slope, _hip._ptr(addend),
-                                                     _hip._ptr(addend2), _hip._ptr(addend3), period_array(periods), _hip.stream_ptr())))
+                  lambda: _hip.call('fgnn_bn_apply', rows, y, R, C, dt, stats[2], stats[3], slope, addend, addend2, addend3,
+                                    period_array(periods)))
         ctx.save_for_backward(rows, weight, bias, stats)
         ctx.slope = slope
         ctx.params = (weight, bias)
@@ -544,10 +533,8 @@ class _BatchNormAct(torch.autograd.Function):
         ws = ops._workspace(rows.device, int(L.fgnn_bn_workspace_bytes(R, C)))
         fold = ops._fold_scratch(rows.device)
         ops.timed('bn_backward (reduce + finalise + apply)', 5 * rows.numel() * rows.element_size(),
-                  lambda: _hip.check(L.fgnn_bn_backward(
-                      _hip._ptr(rows), _hip._ptr(gy), _hip._ptr(gx), R, C, _hip.dtype_code(rows), _hip._ptr(stats[0]),
-                      _hip._ptr(stats[1]), _hip._ptr(weight), _hip._ptr(bias), ctx.slope, _hip._ptr(gw), _hip._ptr(gb),
-                      _hip._ptr(ws), ws.numel() * 4, _hip._ptr(fold), _hip.stream_ptr())))
+                  lambda: _hip.call('fgnn_bn_backward', rows, gy, gx, R, C, _hip.dtype_code(rows), stats[0], stats[1], weight, bias,
+                                    ctx.slope, gw, gb, ws, ws.numel() * 4, fold))
         ga = [None, None, None]
         for i in range(3):
             if ctx.has_addend[i] and ctx.needs_input_grad[5 + i]:
@@ -621,9 +608,7 @@ class BatchNormAct2d(torch.nn.BatchNorm2d):
         else:                                           # eval: folded affine + activation in one pass
             scale, shift = self._folded()
             y = torch.empty_like(rows)
-            _hip.check(_hip.lib().fgnn_bn_apply(_hip._ptr(rows), _hip._ptr(y), B * H * W, C, _hip.dtype_code(rows),
-                                                _hip._ptr(scale), _hip._ptr(shift), slope, _hip._ptr(arows[0]),
-                                                _hip._ptr(arows[1]), _hip._ptr(arows[2]), period_array(periods), _hip.stream_ptr()))
+            _hip.call('fgnn_bn_apply', rows, y, B * H * W, C, _hip.dtype_code(rows), scale, shift, slope, *arows, period_array(periods))
         return y.view(B, H, W, C).permute(0, 3, 1, 2)
 
     def _folded(self):

@@ -86,7 +86,6 @@ def linear_wgrad(rows, jobs, record):
     them (``fgnn_linear_wgrad_multi``: the rows are read once), else one ``fgnn_linear_wgrad`` launch per job.  ``record``: the
     slab folds are recorded (backward_pass.PASS.fold_scope)."""
     L = _hip.lib()
-    P = _hip._ptr
     R, C = rows.shape
     symbol = 'linear_wgrad_b16_kernel' if rows.dtype == torch.bfloat16 else 'linear_wgrad_kernel'
     couts = (ctypes.c_int32 * len(jobs))(*[gy.shape[1] for gy, _, _ in jobs])
@@ -94,18 +93,18 @@ def linear_wgrad(rows, jobs, record):
         nb = int(L.fgnn_linear_wgrad_multi_workspace_bytes(R, C, len(jobs), couts)) if len(jobs) > 1 else -1
         if nb > 0:
             ws = scope.slabs(rows.device, nb)
-            ptrs = lambda i: (ctypes.c_void_p * len(jobs))(*[P(j[i]) for j in jobs])
+            ptrs = lambda i: (ctypes.c_void_p * len(jobs))(*[None if j[i] is None else j[i].data_ptr() for j in jobs])
             K = sum(couts)
             timed(symbol, rows.element_size() * R * (C + K),
-                  lambda: _hip.check(L.fgnn_linear_wgrad_multi(P(rows), R, C, len(jobs), ptrs(0), couts, ptrs(1), ptrs(2), P(ws), ws.numel() * 4,
-                                                               _hip.stream_ptr())), nflops=2 * R * C * K)
+                  lambda: _hip.call('fgnn_linear_wgrad_multi', rows, R, C, len(jobs), ptrs(0), couts, ptrs(1), ptrs(2), ws, ws.numel() * 4),
+                  nflops=2 * R * C * K)
             return
         for gy, gW, gb in jobs:
             K = gy.shape[1]
             ws = scope.slabs(rows.device, int(L.fgnn_linear_wgrad_workspace_bytes(R, C, K)))
             timed(symbol, rows.element_size() * R * (C + K),
-                  lambda: _hip.check(L.fgnn_linear_wgrad(P(rows), P(gy), R, C, K, _hip.dtype_code(rows), P(gW), P(gb), P(ws), ws.numel() * 4,
-                                                         _hip.stream_ptr())), nflops=2 * R * C * K)
+                  lambda: _hip.call('fgnn_linear_wgrad', rows, gy, R, C, K, _hip.dtype_code(rows), gW, gb, ws, ws.numel() * 4),
+                  nflops=2 * R * C * K)
 
 
 def backward_node_begins():
@@ -246,7 +245,7 @@ def backward_tables(nn_idx, d):
         return None
     def build():
         t = torch.empty(nbytes // 4, device=nn_idx.device, dtype=torch.int32)
-        rc = L.fgnn_mpconv_backward_tables(ctypes.byref(d), _hip._ptr(nn_idx), _hip._ptr(t), _hip.stream_ptr())
+        rc = _hip.invoke('fgnn_mpconv_backward_tables', ctypes.byref(d), nn_idx, t)
         if rc == _hip.EUNSUPPORTED:
             return None          # (an in-degree beyond the table-driven kernel's slots: the call goes to another kernel anyway)
         _hip.check(rc)
@@ -288,9 +287,8 @@ def mpconv_forward_raw(x, nn_idx, etype, filters, bias, nou, net, ext, agg, *,
         ws = _workspace(x.device, int(L.fgnn_bn_workspace_bytes(R, nou)))
         stats, fin = bn.final(nou, x.device, R)
         fold = _fold_scratch(x.device)
-        _launch('fwd', d, nbytes, lambda: _hip.check(L.fgnn_mpconv_forward_stats(
-            ctypes.byref(d), _hip._ptr(x), _hip._ptr(nn_idx), _hip._ptr(etype), _hip._ptr(filters),
-            _hip._ptr(bias), _hip._ptr(y), _hip._ptr(amax), _hip._ptr(ws), fin, _hip._ptr(fold), _hip.stream_ptr())))
+        _launch('fwd', d, nbytes, lambda: _hip.call('fgnn_mpconv_forward_stats', ctypes.byref(d), x, nn_idx, etype, filters, bias, y, amax,
+                                                    ws, fin, fold))
         bn.record(y.permute(0, 2, 3, 1).reshape(R, nou), stats)
         return y, amax
     if addends:
@@ -300,19 +298,16 @@ def mpconv_forward_raw(x, nn_idx, etype, filters, bias, nou, net, ext, agg, *,
                 all(a.dtype == y.dtype and a.shape == y.shape and a.stride() == y.stride() for a in addends))
         took = []
         if fits:
-            ap = [_hip._ptr(a) for a in addends] + [None] * (3 - len(addends))
-            _launch('fwd', d, nbytes + sum(a.numel() * a.element_size() for a in addends), lambda: took.append(L.fgnn_mpconv_forward_addends(
-                ctypes.byref(d), _hip._ptr(x), _hip._ptr(nn_idx), _hip._ptr(etype), _hip._ptr(filters), _hip._ptr(bias),
-                _hip._ptr(post_scale), _hip._ptr(post_shift), ap[0], ap[1], ap[2], _hip._ptr(y), _hip.stream_ptr())))
+            ap = list(addends) + [None] * (3 - len(addends))
+            _launch('fwd', d, nbytes + sum(a.numel() * a.element_size() for a in addends), lambda: took.append(_hip.invoke(
+                'fgnn_mpconv_forward_addends', ctypes.byref(d), x, nn_idx, etype, filters, bias, post_scale, post_shift, *ap, y)))
             if took[0] < 0:
                 _hip.check(took[0])
             if took[0] == 1:
                 return y, amax
             return add_n([y] + list(addends)), amax
-    _launch('fwd', d, nbytes, lambda: _hip.check(L.fgnn_mpconv_forward(
-        ctypes.byref(d), _hip._ptr(x), _hip._ptr(nn_idx), _hip._ptr(etype), _hip._ptr(filters),
-        _hip._ptr(bias), _hip._ptr(post_scale), _hip._ptr(post_shift), _hip._ptr(y),
-        _hip._ptr(amax), _hip.stream_ptr())))
+    _launch('fwd', d, nbytes, lambda: _hip.call('fgnn_mpconv_forward', ctypes.byref(d), x, nn_idx, etype, filters, bias, post_scale,
+                                                post_shift, y, amax))
     if addends:
         return add_n([y] + list(addends)), amax
     return y, amax
@@ -363,7 +358,7 @@ def stamp(tag):
     if i >= st['buf'].numel():
         return
     st['tags'].append(tag)
-    _hip.check(_hip.lib().fgnn_stamp(st['buf'].data_ptr() + 8 * i, _hip.stream_ptr()))
+    _hip.call('fgnn_stamp', st['buf'].data_ptr() + 8 * i)
 
 
 ACCUMULATE_INTO_GRAD = True      # master switch for the opted-in parameters (False: always return gradients)
@@ -488,10 +483,8 @@ class _MPConv(torch.autograd.Function):
                       + (get.element_size() * get.numel() if want_get else 0) + 8 * w.numel())
         tables = backward_tables(nn_idx, d)           # the transposed incidence, built once per graph (None: the kernel builds its own)
         with scope:
-            _launch('bwd', d, nbytes, lambda: _hip.check(L.fgnn_mpconv_backward_with_tables(
-                ctypes.byref(d), _hip._ptr(xx), _hip._ptr(nn_idx), _hip._ptr(etype), _hip._ptr(w),
-                _hip._ptr(gz), None, _hip._ptr(amax), _hip._ptr(gx), _hip._ptr(get),
-                _hip._ptr(gw), _hip._ptr(gb), _hip._ptr(ws), ws.numel() * 4, _hip._ptr(tables), _hip.stream_ptr())))
+            _launch('bwd', d, nbytes, lambda: _hip.call('fgnn_mpconv_backward_with_tables', ctypes.byref(d), xx, nn_idx, etype, w, gz, None,
+                                                        amax, gx, get, gw, gb, ws, ws.numel() * 4, tables))
         if want_get and ctx.shared_et and not reduced:
             get = get.sum(dim=0, keepdim=True)
         if want_get and get.dtype != etype.dtype:
@@ -646,8 +639,7 @@ def sum_tensors(ts):
     out = torch.empty_like(ts[0])                        # preserve_format: same strides as the inputs
     arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
     timed('sum_n_kernel', (len(ts) + 1) * ts[0].numel() * ts[0].element_size(),
-          lambda: _hip.check(_hip.lib().fgnn_sum_n(arr, len(ts), ts[0].numel(), _hip.dtype_code(ts[0]),
-                                                   _hip._ptr(out), _hip.stream_ptr())))
+          lambda: _hip.call('fgnn_sum_n', arr, len(ts), ts[0].numel(), _hip.dtype_code(ts[0]), out))
     return out
 
 
@@ -776,14 +768,13 @@ class FanBox:
             if sl is not None:
                 sl[0].record_stream(cur)                   # (a side-stream consumer allocated it; this stream's launch reads it)
         out = torch.empty((self.R, C), device=self.device, dtype=self.dtype)
-        P = _hip._ptr
-        xs = (ctypes.c_void_p * 3)(*[P(sl[0]) if sl else None for sl in slots])
-        ws = (ctypes.c_void_p * 3)(*[P(sl[1]) if sl else None for sl in slots])
+        xs = (ctypes.c_void_p * 3)(*[sl[0].data_ptr() if sl else None for sl in slots])
+        ws = (ctypes.c_void_p * 3)(*[sl[1].data_ptr() if sl else None for sl in slots])
         ks = (ctypes.c_int32 * 3)(*[sl[0].shape[1] if sl else 0 for sl in slots])
-        ad = (ctypes.c_void_p * 3)(*([P(a) for a in adds] + [None] * (3 - len(adds))))
+        ad = (ctypes.c_void_p * 3)(*([a.data_ptr() for a in adds] + [None] * (3 - len(adds))))
         ktot = sum(ks)
         timed('linear_multi_b16_kernel', 2 * self.R * (ktot + C * (1 + len(adds))),
-              lambda: _hip.check(_hip.lib().fgnn_linear_multi_forward(xs, ks, ws, ad, P(out), self.R, C, _hip.stream_ptr())),
+              lambda: _hip.call('fgnn_linear_multi_forward', xs, ks, ws, ad, out, self.R, C),
               nflops=2 * self.R * ktot * C)
         return out.view(B, H, W, C).permute(0, 3, 1, 2)
 
@@ -892,9 +883,9 @@ def _concat2_raw(a, b, dim, plan=None):
     else:
         out = torch.empty((B, a.shape[2], 1, a.shape[1] + b.shape[1]), device=a.device, dtype=a.dtype).permute(0, 3, 1, 2)
     if plan[0] == 'rows':
-        _hip.check(_hip.lib().fgnn_concat_rows(_hip._ptr(a), _hip._ptr(b), _hip._ptr(out), *plan[1:], _hip.stream_ptr()))
+        _hip.call('fgnn_concat_rows', a, b, out, *plan[1:])
     else:
-        _hip.check(_hip.lib().fgnn_concat_pair(_hip._ptr(a), _hip._ptr(b), _hip._ptr(out), *plan, _hip.stream_ptr()))
+        _hip.call('fgnn_concat_pair', a, b, out, *plan)
     return out
 
 

@@ -94,9 +94,7 @@ class PgmDataPath:
         sb = lambda t: 0 if t.shape[0] == 1 and B != 1 else t[0].numel()
         labels = torch.empty((B, self.N), device=dev, dtype=torch.int64)
         obj = torch.empty((B,), device=dev, dtype=torch.float64) if want_objective else None
-        P = _hip._ptr
-        _hip.check(_hip.lib().fgnn_chain_budget_map(P(u), u[0].numel(), P(p), sb(p), P(c), sb(c), B, self.N, self.h,
-                                                    P(labels), P(obj), _hip.stream_ptr()))
+        _hip.call('fgnn_chain_budget_map', u, u[0].numel(), p, sb(p), c, sb(c), B, self.N, self.h, labels, obj)
         return (labels, obj) if want_objective else labels
 
     def solve_lp(self, unary, pair, caps, max_iter=1000, tol=1e-6, eta=0.1, adapt=True, want_details=False):
@@ -125,12 +123,9 @@ class PgmDataPath:
             p = pair.to(dev, torch.float32).contiguous()
             c = caps.to(dev, torch.int32).contiguous()
             sb = lambda t: 0 if t.shape[0] == 1 and B != 1 else t[0].numel()
-            P = _hip._ptr
             d = det or {}
-            _hip.check(_hip.lib().fgnn_chain_budget_lp(P(u), u[0].numel(), P(p), sb(p), P(c), sb(c), B, N, self.h, max_iter, tol,
-                                                       eta, 1 if adapt else 0, P(labels), P(d.get('marginals')),
-                                                       P(d.get('value')), P(d.get('status')), P(d.get('iters')),
-                                                       _hip.stream_ptr()))
+            _hip.call('fgnn_chain_budget_lp', u, u[0].numel(), p, sb(p), c, sb(c), B, N, self.h, max_iter, tol, eta, 1 if adapt else 0,
+                      labels, d.get('marginals'), d.get('value'), d.get('status'), d.get('iters'))
         return (labels, det) if want_details else labels
 
     def lp_inputs(self, family, sampled, cap=5, transition=(0, .1, .2, 1)):
@@ -173,10 +168,8 @@ class PgmDataPath:
         label = torch.empty((B, N), device=dev, dtype=torch.int64)
         obj = torch.empty((B,), device=dev, dtype=torch.float64) if want_objective else None
         trans = (ctypes.c_float * 4)(*[float(v) for v in transition])          # host memory, copied into the launch
-        P = _hip._ptr
-        _hip.check(_hip.lib().fgnn_pgm_sample_rng(fam, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, B, N, h,
-                                                  int(cap), ctypes.cast(trans, ctypes.c_void_p), P(node), P(pws), P(hops),
-                                                  P(label), P(obj), _hip.stream_ptr()))
+        _hip.call('fgnn_pgm_sample_rng', fam, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, B, N, h, int(cap), trans,
+                  node, pws, hops, label, obj)
         out = (node, pws, hops, label) if fam == 2 else (node, pws, label) if fam == 1 else (node, label)
         if lp_label:
             out = out + (self.solve_lp(*self.lp_inputs(family, out, cap, transition)),)

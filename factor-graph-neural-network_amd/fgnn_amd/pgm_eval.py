@@ -92,11 +92,8 @@ def score(dec, label, unary, pair, caps, h=HOP_ORDER, counts=None, out=None):
         p = pair.to(dev, torch.float32).contiguous()
         c = caps.to(dev, torch.int32).contiguous()
         bs = lambda t: 0 if t.shape[0] == 1 and B != 1 else t[0].numel()
-        P = _hip._ptr
-        _hip.check(_hip.lib().fgnn_chain_budget_score(
-            P(dec), kind, sb, cs, vs, P(label), label.stride(0), P(u), u[0].numel(), P(p), bs(p), P(c), bs(c), B, N, int(h),
-            P(out.get('correct')), P(out.get('feasible')), P(out.get('objective')), P(out.get('nll') if logits else None),
-            P(counts), _hip.stream_ptr()))
+        _hip.call('fgnn_chain_budget_score', dec, kind, sb, cs, vs, label, label.stride(0), u, u[0].numel(), p, bs(p), c, bs(c), B, N,
+                  int(h), out.get('correct'), out.get('feasible'), out.get('objective'), out.get('nll') if logits else None, counts)
     res = dict(out)
     res['feasible'] = res['feasible'].view(torch.bool)
     return res

@@ -53,14 +53,13 @@ class _LabellingLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, label, lp_label, counts):
         B, _, N = pred.shape
-        L, P = _hip.lib(), _hip._ptr
+        L = _hip.lib()
         loss = torch.empty((), device=pred.device, dtype=torch.float32)
         ws = torch.empty(int(L.fgnn_pgm_loss_workspace_bytes()) // 8, device=pred.device, dtype=torch.float64)
         kind = _hip.PGM_DEC_F32 if pred.dtype == torch.float32 else _hip.PGM_DEC_BF16
         sb, cs, vs = pred.stride()
-        _hip.check(L.fgnn_pgm_loss_forward(P(pred), kind, sb, cs, vs, P(label), label.stride(0), P(lp_label),
-                                           0 if lp_label is None else lp_label.stride(0), B, N, P(loss), P(counts), P(ws),
-                                           ws.numel() * 8, _hip.stream_ptr()))
+        _hip.call('fgnn_pgm_loss_forward', pred, kind, sb, cs, vs, label, label.stride(0), lp_label,
+                  0 if lp_label is None else lp_label.stride(0), B, N, loss, counts, ws, ws.numel() * 8)
         ctx.save_for_backward(pred, label)
         ctx.kind = kind
         return loss
@@ -69,12 +68,10 @@ class _LabellingLoss(torch.autograd.Function):
     def backward(ctx, gloss):
         pred, label = ctx.saved_tensors
         B, _, N = pred.shape
-        P = _hip._ptr
         g = torch.empty((B, 2, N), device=pred.device, dtype=pred.dtype)
         gloss = gloss.reshape(1).float().contiguous()
         sb, cs, vs = pred.stride()
-        _hip.check(_hip.lib().fgnn_pgm_loss_backward(P(pred), ctx.kind, sb, cs, vs, P(label), label.stride(0), P(gloss), B, N, P(g),
-                                                     *g.stride(), _hip.stream_ptr()))
+        _hip.call('fgnn_pgm_loss_backward', pred, ctx.kind, sb, cs, vs, label, label.stride(0), gloss, B, N, g, *g.stride())
         return g, None, None, None
 
 

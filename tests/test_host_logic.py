@@ -545,3 +545,177 @@ def test_fan_box_drops_the_deposits_of_another_backward_pass():
     box.slots[0] = 'mine'
     box._enter_pass()                       # same pass: kept
     assert box.slots[0] == 'mine'
+
+
+# ---------------------------------------------------------------------------------------------
+# the binding is derived from include/fgnn_hip.h (fgnn_amd/_hip.py: signatures, constants, DevicePointer, call)
+# ---------------------------------------------------------------------------------------------
+def _header():
+    return open(os.path.join(ROOT, 'include', 'fgnn_hip.h')).read()
+
+
+def test_signatures_are_parsed_from_the_header():
+    from fgnn_amd import _hip
+    sig = _hip.signatures(_header())
+    assert len(sig) == 90 and set(sig) == set(re.findall(r'\b(fgnn_[a-z_]+)\s*\(', _header())) == set(_hip.EXPORTS)
+    types = lambda name: [t for _, t in sig[name][1]]
+    assert types('fgnn_chain_budget_lp')[10:12] == [ctypes.c_double, ctypes.c_double]
+    for name in ('fgnn_ldpc_channel_features_rng', 'fgnn_pgm_sample_rng'):
+        assert {n: t for n, t in sig[name][1]}['seed'] is ctypes.c_uint64 and dict(sig[name][1])['offset'] is ctypes.c_uint64
+    assert types('fgnn_mpconv_forward')[0] is ctypes.POINTER(_hip.MPConvDesc)
+    assert types('fgnn_bn_stats')[4] is ctypes.POINTER(_hip.BnFinal)
+    assert sig['fgnn_fold_discard'] == (None, []) and sig['fgnn_last_error'] == (ctypes.c_char_p, [])
+    bytes_queries = [n for n in sig if n.endswith('_bytes')]
+    assert len(bytes_queries) >= 10 and all(sig[n][0] is ctypes.c_int64 for n in bytes_queries)
+    assert sig['fgnn_factor_layer_param_count'] == (ctypes.c_int64, [])
+    # scalars by width, pointers of any depth and the stream as the pointer type, parameter names as the header has them
+    assert sig['fgnn_node_sum'] == (ctypes.c_int32, [('g', _hip.DevicePointer), ('out', _hip.DevicePointer), ('B', ctypes.c_int64),
+                                                     ('M', ctypes.c_int32), ('C', ctypes.c_int32), ('dtype', ctypes.c_int32),
+                                                     ('stream', _hip.DevicePointer)])
+    assert types('fgnn_linear_multi_forward')[:4] == [_hip.DevicePointer] * 4 and types('fgnn_set_ext_backward_pieces') == [ctypes.c_int32]
+    assert types('fgnn_flat_adam')[5:8] == [ctypes.c_int64, ctypes.c_float, ctypes.c_float]
+    L = _hip.lib()                                   # ... and that is what the loaded library is given, for every name
+    for name, (restype, params) in sig.items():
+        assert getattr(L, name).restype is restype and list(getattr(L, name).argtypes) == [t for _, t in params], name
+
+
+@pytest.mark.parametrize('text, word', [
+    ('int fgnn_a(int64_t n);\nint fgnn_b(size_t n);\n', 'size_t'),                         # a type outside the map
+    ('int fgnn_a(int64_t n);\nint fgnn_b(const void* x, int32_t\nint fgnn_c(void);\n', 'fgnn_b'),   # a prototype cut short
+    ('int fgnn_a(int64_t n);\nint fgnn_b(int32_t);\n', 'fgnn_b'),                          # a parameter without a name
+    ('int fgnn_a(int64_t n);\nunsigned fgnn_b(void);\n', 'unsigned'),                      # an unknown return type
+    ('int fgnn_a(int64_t n);\nstatic int helper(int x);\n', 'helper'),                     # a declaration that is no fgnn_ prototype
+])
+def test_signature_parser_refuses_what_it_cannot_type(text, word):
+    from fgnn_amd import _hip
+    assert list(_hip.signatures('int fgnn_a(int64_t n);\n')) == ['fgnn_a']
+    with pytest.raises(_hip.FgnnHipError, match=word):
+        _hip.signatures(text)
+
+
+def test_descriptor_structs_match_the_header():
+    """Field names, order and widths of MPConvDesc / BnFinal against the struct bodies of the header."""
+    from fgnn_amd import _hip
+    text = re.sub(r'/\*.*?\*/', '', _header(), flags=re.S)
+    width = {'int32_t': 4, 'int64_t': 8, 'float': 4}
+    for cname, cls in (('fgnn_mpconv_desc', _hip.MPConvDesc), ('fgnn_bn_final', _hip.BnFinal)):
+        body = re.search(r'typedef struct %s \{(.*?)\} %s;' % (cname, cname), text, flags=re.S).group(1)
+        fields = []
+        for decl in filter(None, (' '.join(s.split()) for s in body.split(';'))):
+            ctype, names = re.fullmatch(r'((?:const )?\w+\*?) (.+)', decl).groups()
+            fields += [(n.strip(), 8 if ctype.endswith('*') else width[ctype]) for n in names.split(',')]
+        assert fields == [(n, ctypes.sizeof(t)) for n, t in cls._fields_], cname
+        assert ctypes.sizeof(cls) == sum(w for _, w in fields)               # no padding: the offsets follow
+    assert len(_hip.MPConvDesc._fields_) == 25 and len(_hip.BnFinal._fields_) == 14
+
+
+def test_mirrored_constants_equal_the_header():
+    from fgnn_amd import _hip
+    text = _header()
+    k = _hip.constants(text)
+    mirrored = ('EXT_NONE', 'EXT_NEIGHBOR', 'EXT_DIFF', 'AGG_MAX', 'AGG_LSE', 'AGG_MEAN', 'F32', 'BF16', 'DEC_F32', 'DEC_BF16', 'DEC_U8',
+                'LABEL_I64', 'LABEL_U8', 'PGM_DEC_F32', 'PGM_DEC_BF16', 'PGM_DEC_I64', 'EUNSUPPORTED', 'ABI_VERSION',
+                'DESC_GETYPE_REDUCED', 'DESC_IDENTITY_LIST', 'FOLD_SCRATCH_BYTES')
+    for name in mirrored:
+        assert getattr(_hip, name) == k[name] and re.search(r'\bFGNN_%s\b' % name, text), name
+    # ... and the header's values are the ones the kernels were built with (literal pins, independent of the parser)
+    assert _hip.ABI_VERSION == 15 and _hip.FOLD_SCRATCH_BYTES == 512 + 64 * 512 * 8 == 262656
+    assert (_hip.DESC_GETYPE_REDUCED, _hip.DESC_IDENTITY_LIST, _hip.EUNSUPPORTED) == (0x10000, 0x20000, -3)
+    assert (_hip.EXT_NONE, _hip.EXT_NEIGHBOR, _hip.EXT_DIFF, _hip.AGG_MAX, _hip.AGG_LSE, _hip.AGG_MEAN, _hip.F32, _hip.BF16) == (0, 1, 2, 0, 1, 2, 0, 1)
+    assert (_hip.DEC_F32, _hip.DEC_BF16, _hip.DEC_U8, _hip.LABEL_I64, _hip.LABEL_U8) == (0, 1, 2, 0, 1)
+    assert (_hip.PGM_DEC_F32, _hip.PGM_DEC_BF16, _hip.PGM_DEC_I64) == (0, 1, 2) and (k['OK'], k['EINVAL'], k['ELAUNCH']) == (0, -1, -2)
+    with pytest.raises(_hip.FgnnHipError, match='FGNN_X'):
+        _hip.constants('#define FGNN_X sizeof(int)\n')
+
+
+def test_missing_header_is_an_error_with_its_path(monkeypatch):
+    from fgnn_amd import _hip
+    assert os.path.samefile(_hip.HEADER_PATH, os.path.join(ROOT, 'include', 'fgnn_hip.h'))
+    monkeypatch.setattr(_hip, 'HEADER_PATH', os.path.join(ROOT, 'include', 'no_such_header.h'))
+    with pytest.raises(_hip.FgnnHipError, match='no_such_header.h'):
+        _hip._header()
+
+
+def test_pointer_parameters_take_tensors_none_addresses_and_ctypes_arrays():
+    from fgnn_amd import _hip
+    conv = _hip.DevicePointer.from_param
+    assert conv(None) is None                                                  # NULL
+
+    class OnDevice(torch.Tensor):                  # stands in for a device tensor: real storage, reports is_cuda
+        is_cuda = True
+    t = torch.zeros(8).as_subclass(OnDevice)
+    got = conv(t[2:])
+    assert isinstance(got, ctypes.c_void_p) and got.value == t.data_ptr() + 8
+    with pytest.raises(_hip.FgnnHipError, match='device memory'):              # host memory never goes as a tensor
+        conv(torch.zeros(8))
+    vp, arr = ctypes.c_void_p(4096), (ctypes.c_int32 * 3)(1, 2, 3)
+    assert conv(vp) is vp and conv(arr) is arr
+    ptr = ctypes.cast(arr, ctypes.POINTER(ctypes.c_int32))
+    assert conv(ptr) is ptr
+    big = conv((1 << 40) + 16)                                                 # an address as an int keeps all 64 bits
+    assert isinstance(big, ctypes.c_void_p) and big.value == (1 << 40) + 16
+    for bad in ('x', b'x', 1.5, [1], np.zeros(2)):
+        with pytest.raises(TypeError):
+            conv(bad)
+
+
+def test_call_checks_the_argument_count_before_touching_the_library(monkeypatch):
+    from fgnn_amd import _hip
+    calls = []
+
+    class Recorder:
+        def __getattr__(self, name):
+            return lambda *a: calls.append((name, a)) or 0
+    monkeypatch.setattr(_hip, 'lib', lambda: calls.append('lib') or Recorder())
+    monkeypatch.setattr(_hip, 'stream_ptr', lambda: 'current-stream')
+    n = len(_hip.SIGNATURES['fgnn_node_sum'][1])
+    assert n == 7
+    with pytest.raises(TypeError, match='fgnn_node_sum takes 7 arguments'):
+        _hip.call('fgnn_node_sum', *range(n + 1))                              # one too many (ctypes alone would let it through)
+    with pytest.raises(TypeError, match='got 5'):
+        _hip.call('fgnn_node_sum', *range(n - 2))                              # two too few: not "the stream was left out"
+    with pytest.raises(TypeError):
+        _hip.call('fgnn_fold_discard', 1)
+    with pytest.raises(TypeError):
+        _hip.call('fgnn_bn_supported', 4096, 64)                               # last parameter is no stream: nothing is appended
+    assert calls == []
+    _hip.call('fgnn_node_sum', *range(n - 1))                                  # exactly one fewer: the current stream is appended
+    _hip.call('fgnn_node_sum', *range(n))                                      # all given: passed as they are
+    assert calls == ['lib', ('fgnn_node_sum', (0, 1, 2, 3, 4, 5, 'current-stream')), 'lib', ('fgnn_node_sum', tuple(range(7)))]
+    monkeypatch.setattr(_hip, 'check', lambda rc: calls.append(('check', rc)))
+    assert _hip.call('fgnn_fold_flush') is None and calls[-1] == ('check', 0)  # the status goes through check
+    assert _hip.invoke('fgnn_fold_flush', None) == 0 and calls[-1] == ('fgnn_fold_flush', (None,))    # invoke hands it back
+
+
+@pytest.mark.gpu
+def test_call_launches_what_the_long_spelling_launched():
+    """_hip.call with tensors, on the current stream or inside a stream context, against the spelling it replaced
+    (_ptr, stream_ptr, check): bit-identical outputs.  A host tensor is refused before anything is launched."""
+    from fgnn_amd import _hip
+    L = _hip.lib()
+    dev = torch.device('cuda')
+    gen = torch.Generator().manual_seed(5)
+    side = torch.cuda.Stream()
+    for dtype in (torch.float32, torch.bfloat16):
+        g = torch.randn(4, 2, 8, generator=gen).to(dev, dtype)                 # fgnn_node_sum: g [B = 4][M = 2][C = 8]
+        old, new, streamed = (torch.full((4, 8), float('nan'), device=dev, dtype=dtype) for _ in range(3))
+        _hip.check(L.fgnn_node_sum(_hip._ptr(g), _hip._ptr(old), 4, 2, 8, _hip.dtype_code(g), _hip.stream_ptr()))
+        _hip.call('fgnn_node_sum', g, new, 4, 2, 8, _hip.dtype_code(g))
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            _hip.call('fgnn_node_sum', g, streamed, 4, 2, 8, _hip.dtype_code(g))
+        side.synchronize()
+        torch.cuda.synchronize()
+        torch.testing.assert_close(old.float(), g.float().sum(1), rtol=2.0 ** -8, atol=0)     # f32 sums, one rounding to the dtype
+        assert torch.equal(old.view(torch.uint8), new.view(torch.uint8)) and torch.equal(old.view(torch.uint8), streamed.view(torch.uint8))
+    x = torch.randn(1, 2, 128, generator=gen).to(dev)                          # fgnn_instnorm_dot_forward: B = 1, N = 2, C = 128, no bias
+    w = torch.randn(128, generator=gen).to(dev)
+    old, new = (torch.full((1, 2), float('nan'), device=dev) for _ in range(2))
+    _hip.check(L.fgnn_instnorm_dot_forward(_hip._ptr(x), _hip._ptr(w), _hip._ptr(None), _hip._ptr(old), 1, 2, 128, _hip.F32, _hip.stream_ptr()))
+    _hip.call('fgnn_instnorm_dot_forward', x, w, None, new, 1, 2, 128, _hip.F32)
+    torch.cuda.synchronize()
+    assert not torch.isnan(old).any() and torch.equal(old.view(torch.uint8), new.view(torch.uint8))
+    before = L.fgnn_last_kernel()
+    with pytest.raises(_hip.FgnnHipError, match='device memory'):
+        _hip.call('fgnn_node_sum', g.cpu(), new, 4, 2, 8, _hip.dtype_code(g))
+    assert L.fgnn_last_kernel() == before
