@@ -15,6 +15,7 @@ import torch
 import torch.distributed as dist
 
 from .backward_pass import PASS
+from .graph import state_moved
 
 
 FLAT_ALIGN = 4      # elements: every parameter starts on a 16-byte boundary of the flat buffers (the kernels read filters with vector loads)
@@ -277,9 +278,7 @@ class FlatAdam:
                 _hip.call('fgnn_flat_adam_dev_clipped', *args, self._measure(g, grad_scale))
             else:
                 _hip.call('fgnn_flat_adam_dev', *args)
-            from .mpnn import pointwise
-            pointwise.invalidate_casts()
-            pointwise.note_state_change()
+            state_moved()
             return
         self._t += 1
         if p.is_cuda:
@@ -305,9 +304,7 @@ class FlatAdam:
             bc1, bc2 = 1.0 - b1 ** self._t, 1.0 - b2 ** self._t
             denom = (self.exp_avg_sq.sqrt() / (bc2 ** 0.5)).add_(self.eps)
             p.addcdiv_(self.exp_avg, denom, value=-self.lr / bc1)
-        from .mpnn import pointwise
-        pointwise.invalidate_casts()
-        pointwise.note_state_change()
+        state_moved()
 
     def zero_grad(self, set_to_none=False):
         self.bucket.zero()

@@ -19,8 +19,9 @@ over ~330 tensors (59.3 ms per step at 4096 codewords against 17 ms for ``bench.
   bucket, its forward and its backward are captured as two hipGraphs (the script's own lines between them — the loss, ``backward()``,
   ``optimizer.step()`` — stay eager: ~30 short launches) and replayed from then on: new inputs are copied into the captured
   buffers, the outputs come back through an autograd node whose backward replays the second graph.  Any change the graphs
-  cannot follow — another batch size, neighbour tables with other contents, eval mode, no-grad, a replaced parameter — runs that
-  call eagerly as before.  ``FGNN_FAST_GRAPH_AFTER=0`` keeps every call eager.
+  cannot follow — another batch size, neighbour tables with other contents, an argument that requires grad, eval mode, no-grad,
+  a replaced parameter — runs that call eagerly as before.  A backward through a call whose saved activations a later call has
+  overwritten (``o1 = model(x1); model(x2); o1.backward()``) raises.  ``FGNN_FAST_GRAPH_AFTER=0`` keeps every call eager.
 
 ``disable_fast_path()`` undoes the patches (modules already optimised stay so).
 """
@@ -29,6 +30,8 @@ import threading
 import weakref
 
 import torch
+
+from .graph import preserved_buffers, state_moved, warm_up
 
 _STATE = {'hook': None, 'adam': None}
 _SEEN = weakref.WeakSet()      # modules the global hook has looked at (kept here, not as an attribute on every nn.Module of the process)
@@ -89,6 +92,8 @@ class _Replay(torch.autograd.Function):
     def forward(ctx, cap, anchor):
         ctx.cap = cap
         cap.fwd.replay()
+        ctx.generation = cap.generation = cap.generation + 1     # ONE set of activations: only this replay's own backward may follow
+        state_moved()                       # (a forward-only replay moved BatchNorm's running statistics too)
         outs = tuple(o.detach().clone() for o in cap.static_out)
         ctx.mark_non_differentiable(*[o for o, g in zip(outs, cap.static_grad) if g is None])
         return outs
@@ -96,6 +101,9 @@ class _Replay(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         cap = ctx.cap
+        if ctx.generation != cap.generation:
+            raise RuntimeError('fgnn_amd fast path: a later call of the module overwrote the activations this backward needs (the '
+                               'replayed graphs keep one set); FGNN_FAST_GRAPH_AFTER=0 keeps such a loop eager')
         with torch.no_grad():
             for g, sg in zip(grads, cap.static_grad):
                 if sg is not None:
@@ -104,23 +112,13 @@ class _Replay(torch.autograd.Function):
                     else:
                         sg.copy_(g)
         cap.bwd.replay()
-        cap.after_replay()
+        state_moved()
         return None, None
 
 
 class _Captured:
-    def __init__(self):
-        self.fwd = self.bwd = None
-        self.static_in = self.static_out = self.static_grad = None
-        self.out_tree = None
-        self.pointers = None
-        self.frozen = None
-
-    @staticmethod
-    def after_replay():
-        from .mpnn import pointwise
-        pointwise.note_state_change()       # the replayed kernels moved BatchNorm buffers / gradient slices behind torch's version counters
-        pointwise.invalidate_casts()
+    fwd = bwd = static_in = static_out = static_grad = out_tree = pointers = frozen = None
+    generation = 0                          # forward replays so far (_Replay)
 
 
 class GraphedForward:
@@ -150,7 +148,7 @@ class GraphedForward:
         sig = []
         for a in args:
             if torch.is_tensor(a):
-                if not a.is_cuda:
+                if not a.is_cuda or a.requires_grad:       # (the captured backward returns no input gradients)
                     return None
                 sig.append((tuple(a.shape), a.dtype, a.device))
             else:
@@ -183,7 +181,7 @@ class GraphedForward:
         m = self.module
         if GRAPH_AFTER <= 0 or self.failed or kwargs or not m.training or not torch.is_grad_enabled():
             return self.eager(*args, **kwargs)
-        key = self._signature(args)            # (None: a CPU or non-tensor argument — nothing below touches the device then)
+        key = self._signature(args)            # (None: a CPU, grad-requiring or non-tensor argument — nothing below touches the device then)
         if key is None or torch.cuda.is_current_stream_capturing():
             return self.eager(*args, **kwargs)
         if self.cap is not None:
@@ -266,44 +264,27 @@ class GraphedForward:
             return False
 
     def _capture(self, key, args):
-        from . import ops
-        from .mpnn import pointwise
-        m = self.module
-        dev = args[0].device
-        with self._FreshLeaves(m):
-            cap = self._capture_with_fresh_leaves(key, args, dev)
+        with self._FreshLeaves(self.module):
+            cap = self._capture_with_fresh_leaves(args, args[0].device)
         cap.pointers, cap.frozen = self._pointers(), self._frozen_versions()
-        self.anchor = torch.zeros((), device=dev, requires_grad=True)
+        self.anchor = torch.zeros((), device=args[0].device, requires_grad=True)
         self.cap, self.key = cap, key
 
-    def _capture_with_fresh_leaves(self, key, args, dev):
+    def _capture_with_fresh_leaves(self, args, dev):
         from . import ops
-        from .mpnn import pointwise
-        m = self.module
         cap = _Captured()
         with torch.no_grad():
             cap.static_in = [a.clone() for a in args]
-        saved = [(b, b.detach().clone()) for b in m.buffers()]      # the warm-up runs below move BatchNorm's running statistics: put back
+        def warm():      # one eager step; its host-side verdicts are what the capture takes for tensors built inside the forward
+            with ops.Verdicts.recording() as v, _uncached_autocast():
+                live = [t for t in _flat_tensors(self.eager(*cap.static_in)) if t.requires_grad]
+                # zero upstream gradients: the pass exercises every backward kernel and adds exactly +0 to the gradient slices
+                torch.autograd.backward(live, [torch.zeros_like(t) for t in live])
+            return v
         stream = torch.cuda.Stream(dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        verdicts = None
-        with torch.cuda.stream(stream):
-            for i in range(2):          # allocator / workspace / per-stream scratch warm-up ON the capture stream; the second run's
-                rec = ops.Verdicts.recording()     # host-side verdicts are what the capture takes for tensors built inside the forward
-                with rec as v, _uncached_autocast():
-                    out = self.eager(*cap.static_in)
-                    live = [t for t in _flat_tensors(out) if t.requires_grad]
-                    # zero upstream gradients: the pass exercises every backward kernel and adds exactly +0 to the gradient slices
-                    torch.autograd.backward(live, [torch.zeros_like(t) for t in live])
-                verdicts = v
-                del out, live
-        torch.cuda.current_stream(dev).wait_stream(stream)
-        torch.cuda.synchronize(dev)
-        with torch.no_grad():
-            for b, old in saved:
-                b.copy_(old)
-        pointwise.note_state_change()
-        pointwise.invalidate_casts()           # the weight casts are recorded: every replay derives them from the parameters of that moment
+        with preserved_buffers([self.module]):
+            verdicts = warm_up(warm, 2, stream)
+        state_moved()           # (makes the weight casts stale: they are recorded, every replay derives them from the parameters of that moment)
         cap.fwd = torch.cuda.CUDAGraph()
         with verdicts.replaying(), _uncached_autocast():
             with torch.cuda.graph(cap.fwd, stream=stream):

@@ -157,7 +157,7 @@ def train(family, epochs, batch_size=32, steps_per_epoch=None, seed=0, model_nam
     if dev.index is None:
         dev = torch.device('cuda', torch.cuda.current_device())
     from .fastpath import FastAdam
-    from .mpnn import pointwise
+    from .graph import StepGraph, state_moved
     from .pgm_datapath import PgmDataPath
 
     torch.manual_seed(seed)
@@ -179,8 +179,7 @@ def train(family, epochs, batch_size=32, steps_per_epoch=None, seed=0, model_nam
         opt.load_state_dict(ckpt['optimizer_state_dict'])
         sched.load_state_dict(ckpt['lr_sche'])
         start_epoch, gcnt = int(ckpt['epoch']), int(ckpt['gcnt'])
-        pointwise.note_state_change()
-        pointwise.invalidate_casts()
+        state_moved()
     path = PgmDataPath(dev, CHAIN_LENGTH, HOP_ORDER)
     nfeat = {'raw': 1, 'pws': 2, 'hops': 3}[family]
     draw = lambda step: path.sample(batch_size, family, seed, step=step, cap=CAP, transition=TRANSITION, lp_label=lp_label)
@@ -201,19 +200,13 @@ def train(family, epochs, batch_size=32, steps_per_epoch=None, seed=0, model_nam
     graphed, static = None, None
     if graph and start_epoch < epochs:
         try:
-            from .graph import StepGraph
             static = [t.clone() for t in draw(gcnt)]
-            saved = [(b, b.detach().clone()) for m in mods for b in m.buffers()]     # the warm-up runs move BatchNorm's running statistics
-            graphed = StepGraph(lambda: compute(static))
-            with torch.no_grad():
-                for b, old in saved:
-                    b.copy_(old)
-            counts.zero_()
-            pointwise.note_state_change()
-            pointwise.invalidate_casts()
+            graphed = StepGraph(lambda: compute(static), modules=mods)
         except Exception as e:           # noqa: BLE001 — report and fall back to eager launches
             print('pgm_train: hipGraph capture failed (%s: %s); running eagerly' % (type(e).__name__, e), file=sys.stderr)
-            graphed = None
+        finally:                         # replays and eager steps alike start from the counts (and buffers) of graph=False
+            counts.zero_()
+            state_moved()
 
     losses, pending = [], 0
     last = {'loss': None, 'acc': None, 'lp_acc': None}

@@ -563,8 +563,8 @@ def test_graph_replay_reproduces_eager_gradients_bitwise(dev):
 
     g1 = eager_reference()
     state = {k: v.clone() for k, v in m.state_dict().items()}
-    graph = StepGraph(compute)                                                  # 2 warm-up steps + capture (one more step)
-    m.load_state_dict(state)
+    graph = StepGraph(compute, modules=[m])                                     # 2 warm-up steps + capture; the buffers are put back
+    assert all(torch.equal(v, state[k]) for k, v in m.state_dict().items())
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(bucket.flat, g1)
@@ -600,11 +600,7 @@ def test_graph_replayed_training_equals_eager_training_bitwise(dev):
                 logits, snr = m(*data[:6])
             (torch.nn.functional.binary_cross_entropy_with_logits(logits.float(), data[6]) + 0.1 * snr.float().pow(2).mean()).backward()
 
-        start = {k: v.clone() for k, v in m.state_dict().items()}
-        step = compute
-        if use_graph:
-            step = StepGraph(compute).replay                  # warm-up + capture advance the BatchNorm buffers: reset
-            m.load_state_dict(start)
+        step = StepGraph(compute, modules=[m]).replay if use_graph else compute      # (modules: the warm-up's buffer updates are undone)
         for _ in range(3):
             step()
             opt.step()
@@ -615,6 +611,78 @@ def test_graph_replayed_training_equals_eager_training_bitwise(dev):
     pg, bg = train(True)
     assert torch.equal(pe, pg)
     assert all(torch.equal(be[k], bg[k]) for k in be)
+
+
+def _small_block_step(dev):
+    """One bf16 training step of a 64-channel `mp_conv_residual` at the smallest parity shape — 12 rows gathering k = 3 of 6 nodes
+    through a regular table (every node 6 times), 4 edge types, batch 8 — as a closure a StepGraph can capture."""
+    from fgnn_amd.dp import FlatGradBucket
+    from fgnn_amd.mpnn import mp_conv_residual, mp_conv_type
+    B, N, M, k, net = 8, 12, 6, 3, 4
+    torch.manual_seed(5)
+    blk = mp_conv_residual(64, 64, net, extension=mp_conv_type.NO_EXTENSION, with_residual=False, aggregator='max').to(dev).train()
+    bucket = FlatGradBucket(blk.parameters(), flatten_params=True)
+    g = torch.Generator().manual_seed(6)
+    x = torch.randn(B, M, 1, 64, generator=g).bfloat16().to(dev).permute(0, 3, 1, 2)
+    idx = ((torch.arange(N).reshape(N, 1) + 2 * torch.arange(k).reshape(1, k)) % M).to(dev).reshape(1, N, k).expand(B, -1, -1)
+    et = torch.randn(B, N, k, net, generator=g).bfloat16().to(dev).permute(0, 3, 1, 2)
+    out = {}
+
+    def compute():
+        bucket.zero()
+        with torch.autocast('cuda', dtype=torch.bfloat16):
+            y = blk(x, idx, et)
+        y.float().square().mean().backward()
+        out['y'] = y.detach()
+    return blk, bucket, compute, out
+
+
+def test_step_graph_with_modules_starts_its_first_replay_from_the_callers_buffers(dev):
+    """StepGraph(compute, modules=[...]): construction (2 warm-up steps + capture) leaves every buffer bit for bit as it was, and the
+    first replay's output, parameter gradients and buffers are those of an eager step from the same state."""
+    from fgnn_amd.graph import StepGraph
+    blk, bucket, compute, out = _small_block_step(dev)
+    compute()                                                         # buffers that are not their initial values
+    torch.cuda.synchronize()
+    before = [b.clone() for b in blk.buffers()]
+    assert before and any(b.dtype == torch.int64 for b in before)
+    graph = StepGraph(compute, modules=[blk])
+    assert all(torch.equal(a, b) for a, b in zip(blk.buffers(), before))
+    y_static = out['y']
+    graph.replay()
+    torch.cuda.synchronize()
+    got = [y_static.clone(), bucket.flat.clone()] + [b.clone() for b in blk.buffers()]
+    assert not any(torch.equal(a, b) for a, b in zip(got[2:], before))          # the replay is a training step: it moved them all
+    for b, old in zip(blk.buffers(), before):
+        b.copy_(old)
+    compute()
+    torch.cuda.synchronize()
+    want = [out['y'], bucket.flat] + list(blk.buffers())
+    assert float(want[1].abs().max()) > 0 and bool(torch.isfinite(want[0]).all())
+    assert all(torch.equal(a, b) for a, b in zip(got, want))
+
+
+def test_step_graph_puts_the_buffers_back_when_a_warm_up_run_raises(dev):
+    """A step that raises (an ordinary Python exception, in its second warm-up run — nothing is being captured yet): StepGraph raises
+    it, and the buffers the first warm-up run moved are as before the call."""
+    from fgnn_amd.graph import StepGraph
+    blk, bucket, compute, out = _small_block_step(dev)
+    before = [b.clone() for b in blk.buffers()]
+    seen = []
+
+    def flaky():
+        if seen:
+            torch.cuda.synchronize()
+            seen.append([b.clone() for b in blk.buffers()])
+            raise ValueError('second warm-up run')
+        seen.append(None)
+        compute()
+    with pytest.raises(ValueError, match='second warm-up run'):
+        StepGraph(flaky, modules=[blk])
+    assert not torch.cuda.is_current_stream_capturing()
+    assert len(seen) == 2 and not any(torch.equal(a, b) for a, b in zip(seen[1], before))      # the first run had moved them
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(blk.buffers(), before))
 
 
 def test_inference_after_training_sees_the_trained_state(dev):
@@ -1305,6 +1373,42 @@ def test_fast_path_switch_for_an_unchanged_script(dev):
     assert not hasattr(torch.optim.Adam, 'stock')
 
 
+def _shim_factor_nn():
+    import os, sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'factor-graph-neural-network_amd'))
+    from lib.model.mpnn import FactorNN                           # the documented import shim
+    return FactorNN
+
+
+class ScriptModel(torch.nn.Module):
+    """train_ldpc.py:19-99, restated: the model of the fast path's hipGraph tests."""
+
+    def __init__(self):
+        super().__init__()
+        from lib.model.mpnn import FactorNN                       # the documented import shim
+        self.main = FactorNN(2, [6, 96], [64, 64, 64, 128, 256, 256, 128, 64, 64], [4, 1], 2,
+                             skip_link={4: 3, 5: 2, 7: 0}, ret_high=True, aggregator='max')
+        mk = lambda: torch.nn.Sequential(torch.nn.Conv2d(7, 64, 1), torch.nn.ReLU(inplace=True), torch.nn.Conv2d(64, 4, 1))
+        self.emodel_f2v, self.emodel_v2f = mk(), mk()
+        frozen = lambda t: torch.nn.Parameter(t, requires_grad=False)
+        self.hnn_idx_v2f = frozen(torch.arange(96).reshape(1, 1, 96))
+        self.hnn_idx_f2v = frozen(torch.zeros(1, 96, 1, dtype=torch.int64))
+        self.hetype_v2f, self.hetype_f2v = frozen(torch.ones(1, 1, 1, 96)), frozen(torch.ones(1, 1, 96, 1))
+        self.nhop_regressor = torch.nn.Sequential(torch.nn.Linear(64, 128), torch.nn.BatchNorm1d(128), torch.nn.ReLU(),
+                                                  torch.nn.Linear(128, 128), torch.nn.ReLU(), torch.nn.Linear(128, 1), torch.nn.ReLU())
+
+    def forward(self, node_feature, hop_feature, nn_idx_f2v, nn_idx_v2f, efeature_f2v, efeature_v2f):
+        etype_f2v, etype_v2f = self.emodel_f2v(efeature_f2v), self.emodel_v2f(efeature_v2f)
+        with torch.no_grad():
+            bsize = node_feature.shape[0]
+            nhop = node_feature[:, 0, :, :].reshape(bsize, 96, 1, 1)
+        res, nhops = self.main(node_feature, [hop_feature, nhop],
+                               [nn_idx_f2v, self.hnn_idx_f2v.repeat(bsize, 1, 1)], [nn_idx_v2f, self.hnn_idx_v2f.repeat(bsize, 1, 1)],
+                               [etype_f2v, self.hetype_f2v.repeat(bsize, 1, 1, 1)], [etype_v2f, self.hetype_v2f.repeat(bsize, 1, 1, 1)])
+        res = (res + node_feature[:, :1, :, :]).squeeze()
+        return res[:, :48].contiguous(), self.nhop_regressor(nhops[1].squeeze())
+
+
 def test_fast_path_replays_hipgraphs_for_an_unchanged_training_loop(dev):
     """Round 6: `fgnn_amd.enable_fast_path()` also gives an UNCHANGED loop (/root/reference/train_ldpc.py:207-231: zero_grad, model(...),
     the script's own loss lines, backward, optimizer.step, a fresh collated batch every iteration) the hipGraph replay — forward and
@@ -1312,38 +1416,9 @@ def test_fast_path_replays_hipgraphs_for_an_unchanged_training_loop(dev):
     it, INCLUDING the tables its forward builds with `.repeat` on every call (train_ldpc.py:77-84): under capture no host read can
     classify those, the verdicts recorded from the eager warm-up do (ops.Verdicts).  Checked: the replayed loop ends bit-identical to
     the same loop with the graphs off; calls the graphs cannot follow (another batch size, eval mode, other tables) run eagerly."""
-    import os, sys
     import fgnn_amd
     from fgnn_amd import fastpath
     from fgnn_amd.ldpc import synthetic_batch
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'factor-graph-neural-network_amd'))
-    from lib.model.mpnn import FactorNN
-
-    class ScriptModel(torch.nn.Module):                       # train_ldpc.py:19-99, restated
-        def __init__(self):
-            super().__init__()
-            self.main = FactorNN(2, [6, 96], [64, 64, 64, 128, 256, 256, 128, 64, 64], [4, 1], 2,
-                                 skip_link={4: 3, 5: 2, 7: 0}, ret_high=True, aggregator='max')
-            mk = lambda: torch.nn.Sequential(torch.nn.Conv2d(7, 64, 1), torch.nn.ReLU(inplace=True), torch.nn.Conv2d(64, 4, 1))
-            self.emodel_f2v, self.emodel_v2f = mk(), mk()
-            frozen = lambda t: torch.nn.Parameter(t, requires_grad=False)
-            self.hnn_idx_v2f = frozen(torch.arange(96).reshape(1, 1, 96))
-            self.hnn_idx_f2v = frozen(torch.zeros(1, 96, 1, dtype=torch.int64))
-            self.hetype_v2f, self.hetype_f2v = frozen(torch.ones(1, 1, 1, 96)), frozen(torch.ones(1, 1, 96, 1))
-            self.nhop_regressor = torch.nn.Sequential(torch.nn.Linear(64, 128), torch.nn.BatchNorm1d(128), torch.nn.ReLU(),
-                                                      torch.nn.Linear(128, 128), torch.nn.ReLU(), torch.nn.Linear(128, 1), torch.nn.ReLU())
-
-        def forward(self, node_feature, hop_feature, nn_idx_f2v, nn_idx_v2f, efeature_f2v, efeature_v2f):
-            etype_f2v, etype_v2f = self.emodel_f2v(efeature_f2v), self.emodel_v2f(efeature_v2f)
-            with torch.no_grad():
-                bsize = node_feature.shape[0]
-                nhop = node_feature[:, 0, :, :].reshape(bsize, 96, 1, 1)
-            res, nhops = self.main(node_feature, [hop_feature, nhop],
-                                   [nn_idx_f2v, self.hnn_idx_f2v.repeat(bsize, 1, 1)], [nn_idx_v2f, self.hnn_idx_v2f.repeat(bsize, 1, 1)],
-                                   [etype_f2v, self.hetype_f2v.repeat(bsize, 1, 1, 1)], [etype_v2f, self.hetype_v2f.repeat(bsize, 1, 1, 1)])
-            res = (res + node_feature[:, :1, :, :]).squeeze()
-            return res[:, :48].contiguous(), self.nhop_regressor(nhops[1].squeeze())
-
     B, steps = 256, 9
     batches = []
     for i in range(steps):                                      # what the DataLoader collates: fresh tensors, per-sample table copies
@@ -1407,3 +1482,56 @@ def test_fast_path_replays_hipgraphs_for_an_unchanged_training_loop(dev):
         assert m2.__dict__['forward'].cap is None and m2.__dict__['forward'].module is m2
     finally:
         fgnn_amd.disable_fast_path()
+
+
+def test_fast_path_graphs_refuse_a_stale_backward_and_inputs_that_need_gradients(dev):
+    """Two uses the replayed graphs cannot follow.  `o1 = m(x1); o2 = m(x2); o1.sum().backward()`: the second replay overwrote the
+    activations the first one's backward would read — RuntimeError instead of gradients computed from x2.  An input that requires
+    grad: the call runs eagerly (the captured backward returns no input gradients) and the input gets the gradient the module gives
+    with the graphs off.  Batch 8: the smallest batch of this suite's training steps."""
+    import fgnn_amd
+    from fgnn_amd import fastpath
+    from fgnn_amd.ldpc import synthetic_batch
+    batches = [synthetic_batch(8, dev, seed=60 + i, dtype=torch.float32, shared_graph=False) for i in range(2)]
+    loss_of = lambda pred, sb: pred.square().mean() + 0.1 * sb.square().mean()
+    fastpath.GRAPH_AFTER = 3
+    fgnn_amd.enable_fast_path()
+    try:
+        torch.manual_seed(3)
+        m = ScriptModel().to(dev).train()
+        opt = torch.optim.Adam(m.parameters(), lr=1e-3)
+
+        def step(d):
+            opt.zero_grad()
+            loss = loss_of(*m(*d[:6]))
+            loss.backward()
+            opt.step()
+            return float(loss)
+        for i in range(5):                                            # the hook's call, three eager sightings, the capturing call
+            step(batches[i % 2])
+        gf = m.__dict__.get('forward')
+        assert isinstance(gf, fastpath.GraphedForward) and not gf.failed and gf.cap is not None and gf.replays == 1
+        o1, _ = m(*batches[0][:6])
+        o2, _ = m(*batches[1][:6])
+        assert gf.replays == 3
+        with pytest.raises(RuntimeError, match='FGNN_FAST_GRAPH_AFTER=0'):
+            o1.sum().backward()
+        opt.zero_grad()
+        o2.sum().backward()                                           # the latest call's own backward is the ordinary loop's
+        assert float(opt.bucket.flat.abs().max()) > 0
+        last = step(batches[0])
+        assert gf.replays == 4 and last == last
+
+        def input_gradient():
+            x = [t.clone() for t in batches[1][:6]]
+            x[0].requires_grad_(True)
+            loss_of(*m(*x)).backward()
+            return x[0].grad
+        g_fast = input_gradient()
+        assert gf.replays == 4                                        # not replayed
+        fastpath.GRAPH_AFTER = 0
+        g_eager = input_gradient()
+        assert float(g_eager.abs().max()) > 0 and torch.equal(g_fast, g_eager)
+    finally:
+        fgnn_amd.disable_fast_path()
+        fastpath.GRAPH_AFTER = 3

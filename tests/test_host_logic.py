@@ -719,3 +719,52 @@ def test_call_launches_what_the_long_spelling_launched():
     with pytest.raises(_hip.FgnnHipError, match='device memory'):
         _hip.call('fgnn_node_sum', g.cpu(), new, 4, 2, 8, _hip.dtype_code(g))
     assert L.fgnn_last_kernel() == before
+
+
+@pytest.mark.parametrize('fails', [False, True], ids=['normal_exit', 'exception'])
+def test_preserved_buffers_puts_every_buffer_back(fails):
+    """graph.preserved_buffers: float AND integer buffers of nested modules leave the block bit for bit as they entered it, after a
+    normal exit and after an exception raised inside the block — which propagates."""
+    from fgnn_amd.graph import preserved_buffers
+    torch.manual_seed(0)
+    inner = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.BatchNorm1d(4))
+    outer = torch.nn.Sequential(inner, torch.nn.BatchNorm1d(4))
+    outer.register_buffer('table', torch.arange(5, dtype=torch.int32))
+    other = torch.nn.BatchNorm1d(2)
+    mods = [outer, other]
+    outer(torch.randn(6, 3))                                      # buffers that are not their initial values
+    want = [b.clone() for m in mods for b in m.buffers()]
+    assert len(want) == 10 and {b.dtype for b in want} == {torch.float32, torch.int64, torch.int32}
+
+    def block():
+        with preserved_buffers(mods):
+            outer.train()(torch.randn(6, 3) * 3 + 1)
+            other.train()(torch.randn(6, 2) * 3 + 1)
+            outer.table += 7
+            moved = [b.clone() for m in mods for b in m.buffers()]
+            assert not any(torch.equal(a, b) for a, b in zip(moved, want))      # every one of them moved inside the block
+            if fails:
+                raise KeyError('raised inside the block')
+    if fails:
+        with pytest.raises(KeyError, match='raised inside the block'):
+            block()
+    else:
+        block()
+    got = [b for m in mods for b in m.buffers()]
+    assert all(a.dtype == b.dtype and torch.equal(a, b) for a, b in zip(got, want))
+
+
+def test_graphed_forward_signature_refuses_what_a_replay_cannot_follow():
+    """fastpath.GraphedForward._signature: None — the call stays eager — for an argument that requires grad (the captured backward
+    returns no input gradients), as for a CPU or non-tensor argument; a geometry key otherwise."""
+    from fgnn_amd.fastpath import GraphedForward
+    sig = GraphedForward._signature
+    x = torch.zeros(2, 3, device='meta')                          # (is_cuda is False for it: stands for any non-ROCm tensor)
+    assert sig((x,)) is None and sig((torch.zeros(2), 3)) is None and sig(()) is None
+
+    class OnDevice(torch.Tensor):                                 # a tensor that says it lives on the device, without one
+        is_cuda = True
+    a, b = torch.zeros(2, 3).as_subclass(OnDevice), torch.zeros(4, dtype=torch.int64).as_subclass(OnDevice)
+    assert sig((a, b)) == (((2, 3), torch.float32, a.device), ((4,), torch.int64, b.device))
+    assert sig((a.clone().requires_grad_(True).as_subclass(OnDevice), b)) is None
+    assert sig((a, (a * 1.0).requires_grad_(True).as_subclass(OnDevice))) is None

@@ -57,7 +57,7 @@ def compute():
     loss.backward()
 
 
-graphed = StepGraph(compute)
+graphed = StepGraph(compute, modules=[everything])
 g_pred, g_loss = out['pred'], out['loss']
 gout = dict(out)
 for it in range(3):

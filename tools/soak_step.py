@@ -31,7 +31,7 @@ def compute():
 
 bad = 0
 for mode in ('eager', 'graph'):
-    step = compute if mode == 'eager' else StepGraph(compute)
+    step = compute if mode == 'eager' else StepGraph(compute, modules=[model])
     first = None
     for it in range(iters):
         step()
