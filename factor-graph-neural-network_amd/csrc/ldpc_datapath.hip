@@ -12,10 +12,14 @@
 // B = 4096 codewords per step per GPU that is the input bottleneck.  Here a batch is two launches of byte / gather
 // work, written once, coalesced, in the storage dtype the model kernels read.  The random draws (z1, u, z2) are
 // inputs (the transform is deterministic and is checked bit-for-bit (encode) / to f32 rounding (channel) against
-// the oracle) or come from a counter-based generator inside the kernel (fgnn_ldpc_channel_features_rng).
+// the oracle) or come from a counter-based generator inside the kernel (fgnn_ldpc_channel_features_rng).  A training loop draws
+// the messages and the (SNR, burst) classes in the kernel too: one launch per batch (fgnn_ldpc_sample_rng,
+// include/fgnn_hip_ldpc_train.h: ContinousCodesSP.__getitem__ + gen_data_item, lib/data/ldpc.py:7-30, over a batch).
 #include "fgnn_common.h"
 #include "fgnn_philox.h"
+#include "fgnn_hip_ldpc_train.h"
 #include <stdint.h>
+#include <type_traits>
 
 #define LD_THREADS 256
 #define LD_CW_PER_WG 64
@@ -61,6 +65,28 @@ struct LdFeatParams {
     unsigned long long seed, offset;     // RNG variant: Philox key and stream offset (z1 / u / z2 are not read)
 };
 
+// What the DRAW prologue of ldpc_features_kernel needs on top (fgnn_ldpc_sample_rng): the code, the class lists (by value, in the
+// kernel's parameter block) and where the drawn codewords / classes go.
+#define LD_MAX_CHOICES 16
+struct LdDrawParams {
+    const unsigned long long* gmask;     // [P]
+    float* snr_out;                      // [B]
+    float* sb_out;                       // [B]
+    uint8_t* cw_out;                     // [B][nvar] or NULL
+    float* label_out;                    // [B][K] or NULL
+    int K, n_snr, n_sigma;
+    float snr_choices[LD_MAX_CHOICES], sigma_choices[LD_MAX_CHOICES];
+};
+struct LdNoDraw {};
+
+// choices[idx] without a dynamically indexed copy of the parameter block in scratch memory
+__device__ __forceinline__ float ld_choice(const float (&choices)[LD_MAX_CHOICES], unsigned idx) {
+    float v = choices[0];
+#pragma unroll
+    for (unsigned j = 1; j < LD_MAX_CHOICES; ++j) v = idx == j ? choices[j] : v;
+    return v;
+}
+
 // standard normal from two 32-bit words (Box-Muller, cosine branch): u1 in (0, 1], u2 in [0, 1)
 __device__ __forceinline__ float ld_normal(unsigned a, unsigned b) {
     const float u1 = ((float)(a >> 8) + 1.0f) * 5.9604644775390625e-08f, u2 = (float)(b >> 8) * 5.9604644775390625e-08f;
@@ -96,12 +122,33 @@ __device__ __forceinline__ void ld_gather_features(const float* ys, const float*
 }
 
 // One workgroup per codeword: y into LDS, then the shared gather stage (ld_gather_features).
-template <typename T, bool RNG>
-__global__ __launch_bounds__(LD_THREADS) void ldpc_features_kernel(const LdFeatParams p) {
+// DRAW (fgnn_ldpc_sample_rng; with RNG): cw, snr_db and sigma_b are not read but drawn, from ONE Philox block per codeword —
+// counter (b lo, b hi | 0x80000000, offset), disjoint from the channel's blocks below, whose counter words 0, 1 hold a bit index
+// < 2^63 — and written out; everything after the prologue is the code the other variants run.
+template <typename T, bool RNG, bool DRAW = false>
+__global__ __launch_bounds__(LD_THREADS) void ldpc_features_kernel(const LdFeatParams p,
+                                                                   const typename std::conditional<DRAW, LdDrawParams, LdNoDraw>::type d) {
     __shared__ float ys[1024];
     const int64_t b = blockIdx.x;
     const int tid = threadIdx.x, nvar = p.nvar, nchk = p.nchk, dv = p.dv, dc = p.dc;
-    const float snr = p.snr_db[b], sb = p.sigma_b[b];
+    float snr = 0.f, sb = 0.f;
+    unsigned long long msg = 0;
+    if constexpr (DRAW) {
+        // nvar = K + P <= 128 here: the threads of the channel loop's one pass each form the codeword's block (10 rounds, no LDS
+        // round trip), and ys[nvar] is free to carry the drawn SNR to the gather stage
+        if (tid < nvar) {
+            unsigned r[4];
+            ld_philox((unsigned)b, (unsigned)((unsigned long long)b >> 32) | 0x80000000u, (unsigned)p.offset, (unsigned)(p.offset >> 32),
+                      (unsigned)p.seed, (unsigned)(p.seed >> 32), r);
+            msg = (unsigned long long)r[0] | ((unsigned long long)r[1] << 32);
+            if (d.K < 64) msg &= (1ull << d.K) - 1ull;
+            snr = ld_choice(d.snr_choices, (unsigned)(((unsigned long long)r[2] * (unsigned)d.n_snr) >> 32));
+            sb = ld_choice(d.sigma_choices, (unsigned)(((unsigned long long)r[3] * (unsigned)d.n_sigma) >> 32));
+            if (tid == 0) { d.snr_out[b] = snr; d.sb_out[b] = sb; ys[nvar] = snr; }
+        }
+    } else {
+        snr = p.snr_db[b]; sb = p.sigma_b[b];
+    }
     const float gcx = exp2f(snr * 0.16609640474436813f);          // 10^(snr/20) = 2^(snr log2(10)/20)
     for (int n = tid; n < nvar; n += LD_THREADS) {
         const int64_t i = b * nvar + n;
@@ -117,13 +164,21 @@ __global__ __launch_bounds__(LD_THREADS) void ldpc_features_kernel(const LdFeatP
         } else {
             z1 = p.z1[i]; u = p.u[i]; z2 = p.z2[i];
         }
-        float v = 2.f * gcx * ((float)p.cw[i] - 0.5f) + z1;
+        uint8_t bit;
+        if constexpr (DRAW) {           // codeword = [s | G s mod 2] (ldpc_encode_kernel's rule)
+            bit = (uint8_t)(n < d.K ? (unsigned)((msg >> n) & 1ull) : (unsigned)(__popcll(msg & d.gmask[n - d.K]) & 1));
+            if (d.cw_out) d.cw_out[i] = bit;
+            if (d.label_out && n < d.K) d.label_out[b * d.K + n] = (float)bit;
+        } else {
+            bit = p.cw[i];
+        }
+        float v = 2.f * gcx * ((float)bit - 0.5f) + z1;
         if (sb >= 1e-20f && u < p.rho) v += gcx * sb * z2;
         ys[n] = v;
-        p.y[i] = v;
+        if (!DRAW || p.y) p.y[i] = v;
     }
     __syncthreads();
-    ld_gather_features(ys, p.snr_db + b, 0, p.var_to_factors, p.factor_to_vars, b, nvar, nchk, dv, dc, static_cast<T*>(p.node),
+    ld_gather_features(ys, DRAW ? ys + nvar : p.snr_db + b, 0, p.var_to_factors, p.factor_to_vars, b, nvar, nchk, dv, dc, static_cast<T*>(p.node),
                        static_cast<T*>(p.hop), static_cast<T*>(p.ef_f2v), static_cast<T*>(p.ef_v2f));
 }
 
@@ -176,11 +231,11 @@ static int ld_channel_launch(bool rng, const uint8_t* cw, const float* snr_db, c
     const dim3 grid((unsigned)B), block(LD_THREADS);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == FGNN_F32) {
-        if (rng) hipLaunchKernelGGL((ldpc_features_kernel<float, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((ldpc_features_kernel<float, false>), grid, block, 0, st, p);
+        if (rng) hipLaunchKernelGGL((ldpc_features_kernel<float, true>), grid, block, 0, st, p, LdNoDraw{});
+        else hipLaunchKernelGGL((ldpc_features_kernel<float, false>), grid, block, 0, st, p, LdNoDraw{});
     } else {
-        if (rng) hipLaunchKernelGGL((ldpc_features_kernel<bf16_t, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((ldpc_features_kernel<bf16_t, false>), grid, block, 0, st, p);
+        if (rng) hipLaunchKernelGGL((ldpc_features_kernel<bf16_t, true>), grid, block, 0, st, p, LdNoDraw{});
+        else hipLaunchKernelGGL((ldpc_features_kernel<bf16_t, false>), grid, block, 0, st, p, LdNoDraw{});
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_channel_features launch: %s", hipGetErrorString(e));
@@ -206,6 +261,37 @@ extern "C" int fgnn_ldpc_channel_features_rng(const uint8_t* cw, const float* sn
                                               fgnn_stream_t stream) {
     return ld_channel_launch(true, cw, snr_db, sigma_b, rho, nullptr, nullptr, nullptr, seed, offset, var_to_factors,
                              factor_to_vars, B, nvar, nchk, dv, dc, dtype, y, node, hop, ef_f2v, ef_v2f, stream);
+}
+
+// A training batch in one launch (include/fgnn_hip_ldpc_train.h): the feature kernel with its DRAW prologue.
+extern "C" int fgnn_ldpc_sample_rng(uint64_t seed, uint64_t offset, const float* snr_choices, int n_snr, const float* sigma_choices,
+                                    int n_sigma, float rho, const uint64_t* gmask, const int32_t* var_to_factors,
+                                    const int32_t* factor_to_vars, int64_t B, int K, int P, int nchk, int dv, int dc, int dtype,
+                                    void* node, void* hop, void* ef_f2v, void* ef_v2f, float* snr_db, float* sigma_b, uint8_t* cw,
+                                    float* label, float* y, fgnn_stream_t stream) {
+    if (B < 0 || n_snr < 1 || n_sigma < 1) FGNN_FAIL(FGNN_EINVAL, "ldpc_sample_rng: B=%lld n_snr=%d n_sigma=%d (B >= 0, lists of >= 1)",
+                                                     (long long)B, n_snr, n_sigma);
+    if (K < 1 || K > 64 || P < 1 || P > 64 || nchk < 1 || dv < 1 || dc < 1 || n_snr > LD_MAX_CHOICES || n_sigma > LD_MAX_CHOICES ||
+        (dtype != FGNN_F32 && dtype != FGNN_BF16) || B > 0x7fffffffll)
+        FGNN_FAIL(FGNN_EUNSUPPORTED, "ldpc_sample_rng: K=%d P=%d (each 1..64) nchk=%d dv=%d dc=%d n_snr=%d n_sigma=%d (<= %d) dtype=%d B=%lld",
+                  K, P, nchk, dv, dc, n_snr, n_sigma, LD_MAX_CHOICES, dtype, (long long)B);
+    if (B == 0) return FGNN_OK;
+    if (!snr_choices || !sigma_choices || !gmask || !var_to_factors || !factor_to_vars || !node || !hop || !ef_f2v || !ef_v2f || !snr_db ||
+        !sigma_b)
+        FGNN_FAIL(FGNN_EINVAL, "ldpc_sample_rng: null pointer");
+    const LdFeatParams p = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, var_to_factors, factor_to_vars, y, node, hop, ef_f2v,
+                            ef_v2f, rho, K + P, nchk, dv, dc, seed, offset};
+    LdDrawParams d = {(const unsigned long long*)gmask, snr_db, sigma_b, cw, label, K, n_snr, n_sigma, {}, {}};
+    for (int i = 0; i < n_snr; ++i) d.snr_choices[i] = snr_choices[i];
+    for (int i = 0; i < n_sigma; ++i) d.sigma_choices[i] = sigma_choices[i];
+    fgnn_note_kernel("ldpc_features_kernel<rng, draw>");
+    const dim3 grid((unsigned)B), block(LD_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == FGNN_F32) hipLaunchKernelGGL((ldpc_features_kernel<float, true, true>), grid, block, 0, st, p, d);
+    else hipLaunchKernelGGL((ldpc_features_kernel<bf16_t, true, true>), grid, block, 0, st, p, d);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_sample_rng launch: %s", hipGetErrorString(e));
+    return FGNN_OK;
 }
 
 // Model inputs from given received words y [B][nvar] f32 (a stored test set's `noizy_sg`): the outputs of
@@ -254,12 +340,24 @@ __device__ __forceinline__ float ll_bce(float x, float y) {       // torch's sta
 template <typename T>
 __global__ __launch_bounds__(LL_THREADS) void ldpc_loss_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ label,
                                                                    const float* __restrict__ pred, const float* __restrict__ sigma_b,
-                                                                   int64_t nlogit, int64_t B, double* __restrict__ part) {
+                                                                   int64_t nlogit, int64_t B, double* __restrict__ part,
+                                                                   unsigned long long* __restrict__ counts) {
     __shared__ double red[2 * LL_THREADS];
+    __shared__ unsigned right_w[LL_THREADS / 64];
     const int tid = threadIdx.x;
     const int64_t step = (int64_t)gridDim.x * LL_THREADS;
     double a = 0.0, m = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * LL_THREADS + tid; i < nlogit; i += step) a += (double)ll_bce(fgnn_ld(logits + i), label[i]);
+    unsigned right = 0;                 // bits this thread decided as the label says: (logit > 0) == (label != 0), train_ldpc.py:235-237
+    for (int64_t i = (int64_t)blockIdx.x * LL_THREADS + tid; i < nlogit; i += step) {
+        const float x = fgnn_ld(logits + i), y = label[i];
+        a += (double)ll_bce(x, y);
+        right += (unsigned)((x > 0.f) == (y != 0.f));
+    }
+    if (counts) {                       // (uniform) counts[2] += {bits compared, bits right}: a wave's sum by shuffles, the waves' below
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) right += __shfl_xor(right, s);
+        if ((tid & 63) == 0) right_w[tid >> 6] = right;
+    }
     for (int64_t b = (int64_t)blockIdx.x * LL_THREADS + tid; b < B; b += step) { const float d = pred[b] - powf(10.f, sigma_b[b] * 0.05f); m += (double)(d * d); }
     red[tid] = a; red[LL_THREADS + tid] = m;
     __syncthreads();
@@ -267,16 +365,25 @@ __global__ __launch_bounds__(LL_THREADS) void ldpc_loss_fwd_kernel(const T* __re
         if (tid < s) { red[tid] += red[tid + s]; red[LL_THREADS + tid] += red[LL_THREADS + tid + s]; }
         __syncthreads();
     }
-    if (tid == 0) { part[2 * blockIdx.x] = red[0]; part[2 * blockIdx.x + 1] = red[LL_THREADS]; }
+    if (tid == 0) {
+        part[2 * blockIdx.x] = red[0]; part[2 * blockIdx.x + 1] = red[LL_THREADS];
+        if (counts) {
+            unsigned long long r = 0;
+            for (int w = 0; w < LL_THREADS / 64; ++w) r += right_w[w];
+            if (r) atomicAdd(counts + 1, r);
+            if (blockIdx.x == 0) atomicAdd(counts, (unsigned long long)nlogit);
+        }
+    }
 }
 
-// stage 2: the partials in workgroup order
+// stage 2: the partials in workgroup order; `parts`: loss[1], loss[2] = the two means on their own (fgnn_ldpc_loss_parts_forward)
 __global__ __launch_bounds__(64) void ldpc_loss_final_kernel(const double* __restrict__ part, int n, int64_t nlogit, int64_t B, float w,
-                                                             float* __restrict__ loss) {
+                                                             float* __restrict__ loss, int parts) {
     if (threadIdx.x != 0) return;
     double a = 0.0, m = 0.0;
     for (int i = 0; i < n; ++i) { a += part[2 * i]; m += part[2 * i + 1]; }
     loss[0] = (float)(a / (double)nlogit + (double)w * m / (double)B);
+    if (parts) { loss[1] = (float)(a / (double)nlogit); loss[2] = (float)(m / (double)B); }
 }
 
 template <typename T>
@@ -303,26 +410,42 @@ static int ll_check(const void* logits, const float* label, const float* pred, c
 
 extern "C" int64_t fgnn_ldpc_loss_workspace_bytes(void) { return (int64_t)LL_MAXGRID * 2 * sizeof(double); }
 
-extern "C" int fgnn_ldpc_loss_forward(const void* logits, const float* label, const float* pred, const float* sigma_b, int64_t B,
-                                      int n, int dtype, float mse_weight, float* loss, void* workspace, int64_t workspace_bytes,
-                                      fgnn_stream_t stream) {
+// Both forward entry points: loss [1] (parts = 0) or [3] (parts = 1), counts [2] or NULL.
+static int ll_forward_launch(const void* logits, const float* label, const float* pred, const float* sigma_b, int64_t B, int n, int dtype,
+                             float mse_weight, float* loss, int parts, int64_t* counts, void* workspace, int64_t workspace_bytes,
+                             fgnn_stream_t stream) {
     int rc = ll_check(logits, label, pred, sigma_b, B, n, dtype);
     if (rc) return rc;
     if (!loss) FGNN_FAIL(FGNN_EINVAL, "ldpc_loss: null pointer");
     if (!workspace || workspace_bytes < fgnn_ldpc_loss_workspace_bytes() || ((uintptr_t)workspace & 7))
         FGNN_FAIL(FGNN_EINVAL, "ldpc_loss: workspace of fgnn_ldpc_loss_workspace_bytes() bytes needed");
+    if ((uintptr_t)counts & 7) FGNN_FAIL(FGNN_EINVAL, "ldpc_loss: counts must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int64_t nl = B * n;
     int grid = (int)((nl + 4 * LL_THREADS - 1) / (4 * LL_THREADS));      // ~4 logits per thread (196 608 logits at the benched size: 48 workgroups)
     if (grid > LL_MAXGRID) grid = LL_MAXGRID;
     if (grid < 1) grid = 1;
     double* part = (double*)workspace;
-    if (dtype == FGNN_F32) hipLaunchKernelGGL(ldpc_loss_fwd_kernel<float>, dim3(grid), dim3(LL_THREADS), 0, st, (const float*)logits, label, pred, sigma_b, nl, B, part);
-    else hipLaunchKernelGGL(ldpc_loss_fwd_kernel<bf16_t>, dim3(grid), dim3(LL_THREADS), 0, st, (const bf16_t*)logits, label, pred, sigma_b, nl, B, part);
-    hipLaunchKernelGGL(ldpc_loss_final_kernel, dim3(1), dim3(64), 0, st, part, grid, nl, B, mse_weight, loss);
+    unsigned long long* cnt = (unsigned long long*)counts;
+    if (dtype == FGNN_F32) hipLaunchKernelGGL(ldpc_loss_fwd_kernel<float>, dim3(grid), dim3(LL_THREADS), 0, st, (const float*)logits, label, pred, sigma_b, nl, B, part, cnt);
+    else hipLaunchKernelGGL(ldpc_loss_fwd_kernel<bf16_t>, dim3(grid), dim3(LL_THREADS), 0, st, (const bf16_t*)logits, label, pred, sigma_b, nl, B, part, cnt);
+    hipLaunchKernelGGL(ldpc_loss_final_kernel, dim3(1), dim3(64), 0, st, part, grid, nl, B, mse_weight, loss, parts);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_loss forward launch: %s", hipGetErrorString(e));
     return FGNN_OK;
+}
+
+extern "C" int fgnn_ldpc_loss_forward(const void* logits, const float* label, const float* pred, const float* sigma_b, int64_t B,
+                                      int n, int dtype, float mse_weight, float* loss, void* workspace, int64_t workspace_bytes,
+                                      fgnn_stream_t stream) {
+    return ll_forward_launch(logits, label, pred, sigma_b, B, n, dtype, mse_weight, loss, 0, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The loss as the training script logs it (include/fgnn_hip_ldpc_train.h): out[3] = {total, BCE mean, MSE mean}, counts[2] += {bits, bits right}.
+extern "C" int fgnn_ldpc_loss_parts_forward(const void* logits, const float* label, const float* pred, const float* sigma_b, int64_t B,
+                                            int n, int dtype, float mse_weight, float* out, int64_t* counts, void* workspace,
+                                            int64_t workspace_bytes, fgnn_stream_t stream) {
+    return ll_forward_launch(logits, label, pred, sigma_b, B, n, dtype, mse_weight, out, 1, counts, workspace, workspace_bytes, stream);
 }
 
 extern "C" int fgnn_ldpc_loss_backward(const void* logits, const float* label, const float* pred, const float* sigma_b,

@@ -7,6 +7,8 @@ fails loudly (build it with ``python __graft_entry__.py`` or ``make -C csrc``).
 
 The header is the one place where the interface is written down: the prototypes' ctypes signatures, the list of
 exports and every mirrored constant are parsed from it when this module is imported (``signatures``, ``constants``).
+Entry points added beside it live in companion headers (``bind_header``: include/fgnn_hip_ldpc_train.h); ``SIGNATURES``,
+``EXPORTS`` and ``ABI_VERSION`` stay the main header's.
 """
 import ctypes
 import os
@@ -162,6 +164,57 @@ def bn_final(stats, gamma, beta, running_mean, running_var, num_batches_tracked,
 
 
 _lib = None
+COMPANIONS = {}     # {name: (restype, [(parameter name, argtype), ...])} of the companion headers bound so far (bind_header)
+_MISSING = {}       # {companion name: header file} the loaded library does not export (a build from before that header)
+
+
+def _bind_companions(L, sigs, header):
+    for name, (restype, params) in sigs.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            _MISSING[name] = header
+            continue
+        fn.restype, fn.argtypes = restype, [t for _, t in params]
+        _MISSING.pop(name, None)
+
+
+def bind_header(path):
+    """Bind the prototypes of a companion header (a file beside include/fgnn_hip.h that includes it and declares further entry
+    points in the same style): parsed by ``signatures``, given ``restype`` / ``argtypes`` on the library (now if it is loaded, else
+    when ``lib()`` loads it) and resolved by ``invoke`` / ``call`` like the main header's names, with the same argument-count check
+    and stream default.  ``SIGNATURES`` / ``EXPORTS`` are not extended.  A library without one of the symbols still loads; calling
+    that name raises FgnnHipError.  Returns the tuple of names."""
+    if not os.path.isabs(path):
+        path = os.path.join(os.path.dirname(HEADER_PATH), path)
+    if not os.path.exists(path):
+        raise FgnnHipError('the companion header %s was not found' % path)
+    with open(path) as f:
+        sigs = signatures(f.read())
+    clash = sorted(set(sigs) & set(SIGNATURES))
+    if clash:
+        raise FgnnHipError('%s declares %s again (include/fgnn_hip.h has it)' % (os.path.basename(path), ', '.join(clash)))
+    for name in sigs:
+        COMPANIONS[name] = sigs[name] + (os.path.basename(path),)
+    if _lib is not None:
+        _bind_companions(_lib, sigs, os.path.basename(path))
+    return tuple(sigs)
+
+
+def _prototype(name):
+    """(restype, params) of a main-header or companion name."""
+    if name in SIGNATURES:
+        return SIGNATURES[name]
+    return COMPANIONS[name][:2]          # (a name in neither table: KeyError, as before companions existed)
+
+
+def _entry(name):
+    """The bound function; a companion name the loaded library lacks raises FgnnHipError (never AttributeError)."""
+    L = lib()
+    if name in _MISSING:
+        raise FgnnHipError('%s does not export %s (include/%s): it was built before that header — rebuild it with '
+                           '`python __graft_entry__.py`' % (LIB_PATH, name, _MISSING[name]))
+    return getattr(L, name)
 
 
 def lib():
@@ -186,6 +239,8 @@ def lib():
     for name, (restype, params) in SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, [t for _, t in params]
+    for header in sorted({c[2] for c in COMPANIONS.values()}):
+        _bind_companions(L, {n: c[:2] for n, c in COMPANIONS.items() if c[2] == header}, header)
     _lib = L
     return L
 
@@ -194,13 +249,13 @@ def invoke(name, *args):
     """The entry point ``name`` with the prototype's arguments, exactly (ctypes itself lets extra ones through): tensors go as they
     are (``DevicePointer``), and a prototype that ends in ``stream`` may be called without it and then runs on torch's current
     stream.  Returns what the entry point returns.  Tensors stay the caller's to keep alive until this returns."""
-    params = SIGNATURES[name][1]
+    params = _prototype(name)[1]
     if len(args) == len(params) - 1 and params[-1][0] == 'stream':
         args += (stream_ptr(),)
     if len(args) != len(params):
         raise TypeError('%s takes %d arguments (%s), got %d' % (name, len(params), ', '.join(n for n, _ in params), len(args)))
     try:
-        return getattr(lib(), name)(*args)
+        return _entry(name)(*args)
     except ctypes.ArgumentError as e:       # (ctypes' wrapper around what an argtype's from_param raised, e.g. for a host tensor)
         raise FgnnHipError('%s: %s' % (name, e)) from None
 
@@ -250,3 +305,6 @@ def make_desc(x, nn_idx, etype, nou, net, ext, agg, relu, y=None):
     if y is not None:
         d.y_sb, d.y_sc, d.y_sm = y.stride(0), y.stride(1), y.stride(2)
     return d
+
+
+LDPC_TRAIN = bind_header('fgnn_hip_ldpc_train.h')      # fgnn_ldpc_sample_rng, fgnn_ldpc_loss_parts_forward

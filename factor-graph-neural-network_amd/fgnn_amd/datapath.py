@@ -7,6 +7,8 @@ calls the pybind11 MNC library for the GF(2) encode ``s2t`` and the channel ``t2
 batch of the same eight arrays with two kernels (csrc/ldpc_datapath.hip) in the dtype the model kernels read.
 No CPU fallback: the arrays are produced where they are consumed.
 """
+import collections
+import ctypes
 import os
 
 import numpy as np
@@ -14,6 +16,30 @@ import torch
 
 from . import _hip
 from .tables import _DATA, LdpcGraph
+
+
+# ``LdpcDataPath.sample_rng``'s result: the reference's DataLoader item (train_ldpc.py:207) in its order, then what the sampler drew
+# besides — the SNR per word, the whole codeword (uint8) and the received word
+LdpcBatch = collections.namedtuple('LdpcBatch', 'node_feature hop_feature nn_idx_f2v nn_idx_v2f efeature_f2v efeature_v2f label sigma_b '
+                                                'snr_db cw y')
+
+
+def check_sample_rng_args(B, seed, step, dtype, choices_snr, choices_sigma, out):
+    """Arguments of ``LdpcDataPath.sample_rng`` (before anything reaches the device)."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('dtype must be float32 or bfloat16')
+    if int(B) < 0:
+        raise ValueError('B must be >= 0, got %d' % B)
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError('seed must fit 64 bits')
+    if not 0 <= int(step) < 2 ** 63:
+        raise ValueError('step must be in [0, 2^63): bit 63 of the offset selects the channel kernel\'s second stream')
+    for what, c in (('snr_db', choices_snr), ('sigma_b', choices_sigma)):
+        if not 1 <= len(c) <= 16 or any(not np.isfinite(float(v)) for v in c):
+            raise ValueError('%s choices: 1 to 16 finite values, got %s' % (what, tuple(c)))
+    if out is not None:
+        if not isinstance(out, LdpcBatch) or out.node_feature.shape[0] != int(B) or out.node_feature.dtype != dtype:
+            raise ValueError('out must be a previous sample_rng result for the same (B, dtype)')
 
 
 class LdpcDataPath:
@@ -209,6 +235,33 @@ class LdpcDataPath:
                                                              kernel_rng=(seed, step) if kernel_rng else None)
         return (node, hop, self.nn_idx_f2v.unsqueeze(0).expand(B, -1, -1), self.nn_idx_v2f.unsqueeze(0).expand(B, -1, -1),
                 ef_f2v, ef_v2f, cw.long(), sigma_b)
+
+
+    def sample_rng(self, B, seed=0, step=0, dtype=torch.float32, snr_db=None, burst_prob=0.05, out=None):
+        """A NEW batch of B training items per ``step`` in ONE launch (fgnn_ldpc_sample_rng, include/fgnn_hip_ldpc_train.h;
+        ``ContinousCodesSP.__getitem__``, ldpc_dataset.py:222-236, over a batch): messages, SNR classes (``snr_db_choices``, or the one
+        value ``snr_db``) and burst classes (``sigma_b_choices``) come from one Philox block per codeword keyed by ``seed`` at counter
+        (b, ``step``), the channel's draws from the feature kernel's generator at the same (seed, step).  No torch generator.
+
+        Returns an ``LdpcBatch``: (node_feature, hop_feature, nn_idx_f2v, nn_idx_v2f, efeature_f2v, efeature_v2f, label [B,48] f32 =
+        the message bits, sigma_b [B]) as ``sample`` orders them (the index tables are its expanded stride-0 views), then snr_db [B],
+        cw [B,96] uint8 and y [B,96] f32.  ``out``: a previous result for the same (B, dtype); every tensor is written in place and
+        ``out`` itself is returned, so a captured step reads the same buffers each step with no copies."""
+        snr_choices = self.snr_db_choices if snr_db is None else (snr_db,)
+        check_sample_rng_args(B, seed, step, dtype, snr_choices, self.sigma_b_choices, out)
+        B, dev, N = int(B), self.device, self.K + self.P
+        if out is None:
+            new = lambda *shape, dt=dtype: torch.empty(shape, device=dev, dtype=dt)
+            out = LdpcBatch(new(B, 2, N, 1), new(B, 6, 48, 1), self.nn_idx_f2v.unsqueeze(0).expand(B, -1, -1),
+                            self.nn_idx_v2f.unsqueeze(0).expand(B, -1, -1), new(B, 7, N, 3), new(B, 7, 48, 6),
+                            new(B, self.K, dt=torch.float32), new(B, dt=torch.float32), new(B, dt=torch.float32),
+                            new(B, N, dt=torch.uint8), new(B, N, dt=torch.float32))
+        farr = lambda c: (ctypes.c_float * len(c))(*[float(v) for v in c])
+        _hip.call('fgnn_ldpc_sample_rng', int(seed), int(step), farr(snr_choices), len(snr_choices), farr(self.sigma_b_choices),
+                  len(self.sigma_b_choices), float(burst_prob), self.gmask, self.var_to_factors, self.factor_to_vars, B, self.K, self.P,
+                  48, 3, 6, _hip.F32 if dtype == torch.float32 else _hip.BF16, out.node_feature, out.hop_feature, out.efeature_f2v,
+                  out.efeature_v2f, out.snr_db, out.sigma_b, out.cw, out.label, out.y)
+        return out
 
 
 def check_received_args(y, snr_db, dtype):

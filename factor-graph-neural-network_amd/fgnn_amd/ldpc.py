@@ -136,6 +136,57 @@ def decoding_loss(logits, snr_pred, label, sigma_b, mse_weight=0.1):
     return bce + mse_weight * mse
 
 
+class _DecodingLossParts(torch.autograd.Function):
+    """``_DecodingLoss`` whose forward also leaves the two terms and the decision counts (fgnn_ldpc_loss_parts_forward: the same kernel,
+    the same partials); the backward is ``_DecodingLoss``'s."""
+
+    @staticmethod
+    def forward(ctx, logits, pred, label, sigma_b, mse_weight, counts):
+        from . import _hip, ops
+        B, n = logits.shape
+        parts = torch.empty(3, device=logits.device, dtype=torch.float32)
+        ws = ops._workspace(logits.device, int(_hip.lib().fgnn_ldpc_loss_workspace_bytes()))
+        _hip.call('fgnn_ldpc_loss_parts_forward', logits, label, pred, sigma_b, B, n, _hip.dtype_code(logits), mse_weight, parts, counts,
+                  ws, ws.numel() * 4)
+        ctx.save_for_backward(logits, pred, label, sigma_b)
+        ctx.mse_weight = mse_weight
+        ctx.mark_non_differentiable(parts)
+        return parts[0].clone(), parts
+
+    @staticmethod
+    def backward(ctx, gloss, _gparts):
+        return _DecodingLoss.backward(ctx, gloss) + (None,)
+
+
+def decoding_loss_parts(logits, snr_pred, label, sigma_b, mse_weight=0.1, counts=None):
+    """``decoding_loss`` as the training script logs it (/root/reference/train_ldpc.py:232-251): returns ``(loss, parts)`` — ``loss`` the
+    0-dim total with ``decoding_loss``'s backward and its very bits, ``parts`` the detached [3] f32 tensor {total, BCE mean (the
+    script's ``loss``), MSE mean (its ``sigma_b_loss``)}.  ``counts`` [2] int64 on the logits' device, if given, is ADDED to: bits
+    compared, bits where ``(logit > 0) == (label != 0)`` (train_ldpc.py:235-237) — the per-step ``acc`` without a host read.
+
+    logits [B, n] f32 / bf16, snr_pred [B] or [B, 1] f32, label [B, n], sigma_b [B].  Bad shapes or dtypes raise ValueError before
+    anything reaches the device; anything but a ROCm device raises RuntimeError (no CPU fallback here: ``decoding_loss`` has one)."""
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError('logits must be [B, n] with B, n >= 1, got %s' % (tuple(logits.shape),))
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('logits must be f32 or bf16, got %s' % logits.dtype)
+    B = logits.shape[0]
+    if snr_pred.dtype != torch.float32 or tuple(snr_pred.shape) not in ((B,), (B, 1)):
+        raise ValueError('snr_pred must be [%d] or [%d, 1] f32, got %s %s' % (B, B, tuple(snr_pred.shape), snr_pred.dtype))
+    if label.shape != logits.shape:
+        raise ValueError('label must be %s like the logits, got %s' % (tuple(logits.shape), tuple(label.shape)))
+    if tuple(sigma_b.shape) not in ((B,), (B, 1)):
+        raise ValueError('sigma_b must be [%d], got %s' % (B, tuple(sigma_b.shape)))
+    if counts is not None and (counts.dtype != torch.int64 or tuple(counts.shape) != (2,) or counts.device != logits.device
+                               or not counts.is_contiguous()):
+        raise ValueError('counts must be a contiguous [2] int64 tensor on %s' % logits.device)
+    if not logits.is_cuda:
+        raise RuntimeError('decoding_loss_parts runs on a ROCm device (no CPU fallback)')
+    dev = logits.device
+    return _DecodingLossParts.apply(logits.contiguous(), snr_pred.contiguous(), label.to(dev, torch.float32).contiguous(),
+                                    sigma_b.to(dev, torch.float32).contiguous(), float(mse_weight), counts)
+
+
 def synthetic_batch(B, device, seed=0, dtype=torch.float32, shared_graph=True):
     """Synthetic LDPC inputs of the exact reference shapes: received words
     y ~ N(+-1, 1) and an SNR channel in {0..4} dB; features built as ldpc_dataset.py:92-106 does.
