@@ -10,7 +10,11 @@ potentials the caller has (``solve_map``) or on models it draws itself (``sample
 The reference labels every item a second time, with the argmax of AD3's LP-relaxation posteriors (``assign1``, the ``lp_acc``
 baseline of train_syn_*.py).  ``solve_lp`` solves that LP the way AD3 does, by ADMM over the local polytope (csrc/pgm_lp.hip, one
 wave64 per sample, f64), from AD3's start with its default step, tolerance and iteration cap; ``sample(..., lp_label=True)`` and
-``write_reference_dataset(..., lp_label=True)`` add that label.  No CPU fallback.
+``write_reference_dataset(..., lp_label=True)`` add that label.
+
+``solve_bp`` is the baseline the network is named after, which the reference does not have: damped parallel max-product belief
+propagation on the same chains (csrc/pgm_bp.hip, one wave64 per sample, f64, messages in LDS); ``sample(..., bp_label=True)`` adds
+its label.  No CPU fallback.
 """
 import ctypes
 import pickle
@@ -63,6 +67,22 @@ def check_solve_args(unary, pair, caps, N, h):
         raise ValueError('caps must be integers, got %s' % caps.dtype)
     caps, _ = _batched(caps, 'caps', (N - h + 1,), B)
     return B, unary, pair, caps
+
+
+def check_bp_args(N, h, max_iter=200, damping=0.5, tol=1e-6):
+    """ValueError unless ``solve_bp`` takes these: a shape within the kernel's LDS (fgnn_chain_budget_bp_lds_bytes), max_iter >= 0,
+    damping in [0, 1), tol finite and >= 0.  No device needed.  Returns (max_iter, damping, tol) as int, float, float."""
+    L = _hip.lib()
+    if _hip.invoke('fgnn_chain_budget_bp_lds_bytes', int(N), int(h)) < 0:
+        raise ValueError(L.fgnn_last_error().decode())
+    max_iter, damping, tol = int(max_iter), float(damping), float(tol)
+    if max_iter < 0:
+        raise ValueError('max_iter must be >= 0, got %d' % max_iter)
+    if not 0 <= damping < 1:
+        raise ValueError('damping must be in [0, 1), got %r' % damping)
+    if not (np.isfinite(tol) and tol >= 0):
+        raise ValueError('tol must be a finite value >= 0, got %r' % tol)
+    return max_iter, damping, tol
 
 
 class PgmDataPath:
@@ -128,6 +148,31 @@ class PgmDataPath:
                       labels, d.get('marginals'), d.get('value'), d.get('status'), d.get('iters'))
         return (labels, det) if want_details else labels
 
+    def solve_bp(self, unary, pair, caps, max_iter=200, damping=0.5, tol=1e-6, want_details=False):
+        """Max-product belief propagation on the same B chains (inputs as ``solve_map``), csrc/pgm_bp.hip: messages as log-ratios in
+        f64, all 0 at the start, all updated in parallel, ``new = damping * old + (1 - damping) * computed``; a sample stops after
+        the iteration whose largest message change is below ``tol`` (strict: tol = 0 runs ``max_iter`` iterations) or after
+        ``max_iter``.  On these loopy graphs (overlapping windows) it is a heuristic; with every cap >= h the graph is a chain and
+        ``max_iter=N, damping=0`` gives the exact MAP.  Returns labels [B,N] int64 (1 where the final belief is > 0), and with
+        want_details also a dict of beliefs [B,N] f64, status [B] int32 (0 converged, 2 a negative cap: labels and beliefs 0, 3
+        iteration cap reached) and iters [B] int32."""
+        B, unary, pair, caps = check_solve_args(unary, pair, caps, self.N, self.h)
+        max_iter, damping, tol = check_bp_args(self.N, self.h, max_iter, damping, tol)
+        dev, N = self.device, self.N
+        labels = torch.empty((B, N), device=dev, dtype=torch.int64)
+        det = dict(beliefs=torch.empty((B, N), device=dev, dtype=torch.float64),
+                   status=torch.empty((B,), device=dev, dtype=torch.int32),
+                   iters=torch.empty((B,), device=dev, dtype=torch.int32)) if want_details else None
+        if B > 0:
+            u = unary.to(dev, torch.float32).contiguous()
+            p = pair.to(dev, torch.float32).contiguous()
+            c = caps.to(dev, torch.int32).contiguous()
+            sb = lambda t: 0 if t.shape[0] == 1 and B != 1 else t[0].numel()
+            d = det or {}
+            _hip.call('fgnn_chain_budget_bp', u, u[0].numel(), p, sb(p), c, sb(c), B, N, self.h, max_iter, tol, damping, labels,
+                      d.get('beliefs'), d.get('status'), d.get('iters'))
+        return (labels, det) if want_details else labels
+
     def lp_inputs(self, family, sampled, cap=5, transition=(0, .1, .2, 1)):
         """The (unary [B,N,2], pair, caps) of models ``sample(..., family)`` drew, rebuilt on the device from its output tuple:
         unary = node feature transposed; pair = the pws feature's to-right link ([B,N-1,4]) or the shared ``transition``; caps = the
@@ -144,7 +189,8 @@ class PgmDataPath:
             caps = int(cap)
         return unary, pair, caps
 
-    def sample(self, B, family='hops', seed=0, step=0, cap=5, transition=(0, .1, .2, 1), want_objective=False, lp_label=False):
+    def sample(self, B, family='hops', seed=0, step=0, cap=5, transition=(0, .1, .2, 1), want_objective=False, lp_label=False,
+               bp_label=False):
         """One training batch of B random models, drawn in the kernel from (seed, step) (Philox4x32-10; a training loop passes its
         step), in the tuple order the reference's ``RandomPGMData`` yields for ``family``:
           hops: (node_feature [B,2,N,1], pws [B,4,N,1], hops [B,h,N,1], label [B,N])   RandomPGMHop (per-position caps)
@@ -152,7 +198,8 @@ class PgmDataPath:
           raw:  (node_feature, label)                                                  RandomPGM (link table ``transition``)
         Features f32, labels int64 = the exact MAP.  ``cap`` >= h gives the NoHop variants.  With lp_label the LP-relaxation label
         [B,N] int64 of ``solve_lp`` at its defaults follows the MAP label (the reference's (..., assign, assign1)); with
-        want_objective the MAP objective [B] f64 is appended last."""
+        bp_label the max-product label [B,N] int64 of ``solve_bp`` at its defaults follows those; with want_objective the MAP
+        objective [B] f64 is appended last."""
         if family not in FAMILIES:
             raise ValueError('family must be one of %s, got %r' % (sorted(FAMILIES), family))
         B = int(B)
@@ -161,6 +208,8 @@ class PgmDataPath:
         if len(tuple(transition)) != 4:
             raise ValueError('transition must hold 4 values (row-major [x_i][x_{i+1}])')
         N, h, dev = self.N, self.h, self.device
+        if bp_label:
+            check_bp_args(N, h)
         fam = FAMILIES[family]
         node = torch.empty((B, 2, N, 1), device=dev, dtype=torch.float32)
         pws = torch.empty((B, 4, N, 1), device=dev, dtype=torch.float32) if fam != 0 else None
@@ -173,6 +222,8 @@ class PgmDataPath:
         out = (node, pws, hops, label) if fam == 2 else (node, pws, label) if fam == 1 else (node, label)
         if lp_label:
             out = out + (self.solve_lp(*self.lp_inputs(family, out, cap, transition)),)
+        if bp_label:
+            out = out + (self.solve_bp(*self.lp_inputs(family, out, cap, transition)),)
         return out + (obj,) if want_objective else out
 
     def write_reference_dataset(self, path, family, size, seed, step=0, batch=4096, cap=5, transition=(0, .1, .2, 1),

@@ -8,6 +8,9 @@ exact MAP label), their per-batch standard deviations and the cross-entropy loss
 every decision against the model's potentials: is it feasible (every budget window holds), what is its objective, how far is that
 from the MAP's.  The reference reports none of that; per-variable accuracy alone says little about MAP inference.
 
+``evaluate(..., bp=True)`` adds the baseline the network is named after and the reference lacks: max-product belief propagation
+(``PgmDataPath.solve_bp``, csrc/pgm_bp.hip), solved on the test set's potentials and scored like the LP label.
+
 ``load_test_set`` reads the reference's pickle stream (``RandomPGMData``'s item formats), ``make_test_set`` writes one,
 ``build_model`` / ``load_checkpoint`` rebuild the scripts' models and read their checkpoints, ``evaluate`` runs the loop and
 ``python -m fgnn_amd.pgm_eval`` is the command line.
@@ -25,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _hip
-from .pgm_datapath import FAMILIES, PgmDataPath, check_solve_args
+from .pgm_datapath import FAMILIES, PgmDataPath, check_bp_args, check_solve_args
 
 TRANSITION = (0, .1, .2, 1)          # data_generate/generate_random_pgm.py: the raw family's link table
 CAP = 5                              # ... and budget (raw, pws)
@@ -302,7 +305,7 @@ def map_figures(correct, feasible, objective, map_objective, N):
 
 
 def evaluate(model, edge_models, test_set, family, batch_size=32, eval_batch=4096, cap=CAP, transition=TRANSITION,
-             hop_order=HOP_ORDER, return_logits=False):
+             hop_order=HOP_ORDER, return_logits=False, bp=False, bp_args=None):
     """The family's test loop on ``test_set`` (``load_test_set``'s tuple, or a path to read with it) and the MAP-quality figures.
 
     The model and edge models run in eval mode under no_grad (their training flags are restored afterwards) in chunks of
@@ -318,18 +321,29 @@ def evaluate(model, edge_models, test_set, family, batch_size=32, eval_batch=409
 
     Returns a dict: acc, acc_lp, stddev, stddev_lp, loss, pooled_acc, pooled_acc_lp (acc_lp etc. None when the file has no LP
     label), 'model' and 'lp' (``map_figures``: feasible, exact_map, optimal, mean_gap; 'lp' None without the label), 'map_feasible'
-    (the labels' own feasible fraction: 1 for exact labels), n, N; with return_logits also 'logits' [n, 2, N, 1] on the device."""
+    (the labels' own feasible fraction: 1 for exact labels), n, N; with return_logits also 'logits' [n, 2, N, 1] on the device.
+
+    With ``bp`` the max-product baseline is solved per chunk on the same potentials (``PgmDataPath.solve_bp(**bp_args)``; stored test
+    sets carry no such label) and scored by the same kernel: acc_bp, stddev_bp, pooled_acc_bp (``loop_figures``' arithmetic), 'bp'
+    (``map_figures``) and bp_converged, the fraction of samples that stopped below the tolerance (status 0).  Without it the
+    dict has none of these keys."""
     _check_family(family)
     if isinstance(test_set, (str, os.PathLike)):
         test_set = load_test_set(test_set, family, device=next(model.parameters()).device)
     batch_size, eval_batch = int(batch_size), int(eval_batch)
     if batch_size < 1 or eval_batch < 1:
         raise ValueError('batch_size and eval_batch must be >= 1')
+    bp_args = dict(bp_args or {})
+    if set(bp_args) - {'max_iter', 'damping', 'tol'}:
+        raise ValueError('bp_args takes max_iter, damping and tol, got %s' % sorted(bp_args))
     *feats, label, lp = test_set
     n, N = label.shape
     dev = label.device
     h = feats[2].shape[1] if family == 'hops' else int(hop_order)
-    unary, pair, caps = PgmDataPath(dev, N, h).lp_inputs(family, tuple(feats) + (label,), cap, transition)
+    path = PgmDataPath(dev, N, h)
+    if bp:
+        check_bp_args(N, h, **bp_args)
+    unary, pair, caps = path.lp_inputs(family, tuple(feats) + (label,), cap, transition)
     if not torch.is_tensor(caps):                                  # (once on the device: no host copy per chunk)
         caps = torch.full((N - h + 1,), int(caps), dtype=torch.int32, device=dev)
     cut = lambda s, e: (unary[s:e], pair[s:e] if pair.dim() == 3 else pair, caps[s:e] if caps.dim() == 2 else caps)
@@ -343,6 +357,8 @@ def evaluate(model, edge_models, test_set, family, batch_size=32, eval_batch=409
 
     res_m, res_map = outs(True), outs(False)
     res_lp = outs(False) if lp is not None else None
+    res_bp = outs(False) if bp else None
+    bp_status = torch.empty(n, dtype=torch.int32, device=dev) if bp else None
     logits_all = torch.empty((n, 2, N, 1), dtype=torch.float32, device=dev) if return_logits else None
     mods = [model] + list(edge_models)
     was = [m.training for m in mods]
@@ -361,6 +377,10 @@ def evaluate(model, edge_models, test_set, family, batch_size=32, eval_batch=409
                 score(label[s:e], label[s:e], u, p, c, h, out=sl(res_map))
                 if lp is not None:
                     score(lp[s:e], label[s:e], u, p, c, h, out=sl(res_lp))
+                if bp:
+                    bp_label, det = path.solve_bp(u, p, c, want_details=True, **bp_args)
+                    bp_status[s:e] = det['status']
+                    score(bp_label, label[s:e], u, p, c, h, out=sl(res_bp))
     finally:
         for m, w in zip(mods, was):
             m.train(w)
@@ -368,12 +388,19 @@ def evaluate(model, edge_models, test_set, family, batch_size=32, eval_batch=409
     cols = [res_m[k].double() for k in keys + ('nll',)] + [res_map[k].double() for k in keys]
     if lp is not None:
         cols += [res_lp[k].double() for k in keys]
+    if bp:
+        cols += [res_bp[k].double() for k in keys] + [bp_status.double()]
     host = torch.stack(cols).cpu().numpy()                          # the one read-back
     mc, mf, mo, mn, _, pf, po = host[:7]
     out = loop_figures(mc.astype(np.int64), mn, host[7].astype(np.int64) if lp is not None else None, N, batch_size)
     out['model'] = map_figures(mc, mf > 0, mo, po, N)
     out['lp'] = map_figures(host[7], host[8] > 0, host[9], po, N) if lp is not None else None
     out['map_feasible'] = float((pf > 0).mean())
+    if bp:
+        bc, bf, bo, bs = host[-4:]
+        fig = loop_figures(mc.astype(np.int64), None, bc.astype(np.int64), N, batch_size)      # (the LP slot's arithmetic)
+        out.update(acc_bp=fig['acc_lp'], stddev_bp=fig['stddev_lp'], pooled_acc_bp=fig['pooled_acc_lp'],
+                   bp=map_figures(bc, bf > 0, bo, po, N), bp_converged=float((bs == 0).mean()))
     out['n'], out['N'] = int(n), int(N)
     if return_logits:
         out['logits'] = logits_all
@@ -397,6 +424,7 @@ def main(argv=None):
     ap.add_argument('--eval_batch', type=int, default=4096, help='items per model call')
     ap.add_argument('--transition', type=float, nargs=4, default=list(TRANSITION), help='raw: the link table')
     ap.add_argument('--cap', type=int, default=CAP, help='raw / pws: the budget')
+    ap.add_argument('--bp', action='store_true', help='also solve and score the max-product belief-propagation baseline')
     ap.add_argument('--json', action='store_true', help='print the figures as one JSON line instead')
     ap.add_argument('--make_test_set', metavar='PATH', help='write a test set with both labels to PATH and stop')
     ap.add_argument('--num', type=int, default=10000, help='items (--make_test_set)')
@@ -410,7 +438,8 @@ def main(argv=None):
         ap.error('give --test_path and --model_path, or --make_test_set')
     model, edge = load_checkpoint(args.model_path, args.family, args.model_name, dev)
     ts = load_test_set(args.test_path, args.family, args.test_size, dev)
-    r = evaluate(model, edge, ts, args.family, args.batch_size, args.eval_batch, cap=args.cap, transition=args.transition)
+    r = evaluate(model, edge, ts, args.family, args.batch_size, args.eval_batch, cap=args.cap, transition=args.transition,
+                 bp=args.bp)
     if args.json:
         clean = lambda v: {k: clean(x) for k, x in v.items()} if isinstance(v, dict) else (None if isinstance(v, float) and
                                                                                          math.isnan(v) else v)
@@ -419,7 +448,10 @@ def main(argv=None):
     print('testing result: acc = {}, acc_lp = {}'.format(r['acc'], r['acc_lp']))
     print('stddev = {}, stddev_lp = {}'.format(r['stddev'], r['stddev_lp']))
     print('loss = {}, pooled acc = {}, pooled acc_lp = {}'.format(r['loss'], r['pooled_acc'], r['pooled_acc_lp']))
-    for who in ('model', 'lp'):
+    if args.bp:
+        print('acc_bp = {}, stddev_bp = {}, pooled acc_bp = {}, bp converged = {}'.format(r['acc_bp'], r['stddev_bp'],
+                                                                                          r['pooled_acc_bp'], r['bp_converged']))
+    for who in ('model', 'lp') + (('bp',) if args.bp else ()):
         f = r[who]
         if f is None:
             print('%-5s  (no LP label in the test set)' % who)
