@@ -9,13 +9,12 @@ No CPU fallback: the arrays are produced where they are consumed.
 """
 import collections
 import ctypes
-import os
 
 import numpy as np
 import torch
 
 from . import _hip
-from .tables import _DATA, LdpcGraph
+from .ldpc_code import LdpcCode
 
 
 # ``LdpcDataPath.sample_rng``'s result: the reference's DataLoader item (train_ldpc.py:207) in its order, then what the sampler drew
@@ -43,26 +42,39 @@ def check_sample_rng_args(B, seed, step, dtype, choices_snr, choices_sigma, out)
 
 
 class LdpcDataPath:
-    """96.3.963 code: 48 message bits, 48 parity bits (codeword = [s | G s]), 3 checks per variable, 6 variables
-    per check.  ``sample`` mirrors ``ContinousCodesSP.__getitem__`` over a batch."""
-    K, P = 48, 48
+    """The data path of one regular LDPC code (``code``: an ``LdpcCode``; None: the built-in 96.3.963 — 48 message bits, 48 parity
+    bits, 3 checks per variable, 6 variables per check): K message bits, P parity bits (codeword = [s | G s]), N = K + P variables,
+    M checks.  The shapes below are written for the built-in code; for another, 96 reads N, 48 reads K (bits) or M (checks), 3 reads
+    dv and 6 / 7 read dc / dc + 1.  A code whose rows of G fit one 64-bit word (K, P <= 64) runs the one-word encoder and sampler
+    (csrc/ldpc_datapath.hip), as the built-in code always has; any other the W-word ones (csrc/ldpc_code.hip).
+    ``sample`` mirrors ``ContinousCodesSP.__getitem__`` over a batch."""
+    K, P = 48, 48                                   # (the built-in code's; an instance carries its code's)
     sigma_b_choices = (0, 1, 2, 3, 4, 5)            # ldpc_dataset.py:212
     snr_db_choices = (0, 1, 2, 3, 4)                # ldpc_dataset.py:216
 
-    def __init__(self, device):
+    def __init__(self, device, code=None):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise RuntimeError('LdpcDataPath runs on a ROCm device (no CPU fallback)')
-        g = LdpcGraph()
-        z = np.load(os.path.join(_DATA, 'ldpc_96_3_963_G.npz'))
-        G = z['G'].astype(np.uint64)                                                            # [P, K]
-        self._decode_tables = self._incidence_tables(z['A2_nlist'], 48)
-        masks = (G << np.arange(self.K, dtype=np.uint64)[None, :]).sum(1).astype(np.uint64)
-        self.gmask = torch.from_numpy(masks.view(np.int64)).to(self.device)
-        self.var_to_factors = torch.from_numpy(g.var_to_factors.astype(np.int32)).to(self.device)
-        self.factor_to_vars = torch.from_numpy(g.factor_to_vars.astype(np.int32)).to(self.device)
-        self.nn_idx_f2v = torch.from_numpy(g.var_to_factors).to(self.device)
-        self.nn_idx_v2f = torch.from_numpy(g.factor_to_vars).to(self.device)
+        code = LdpcCode.builtin() if code is None else code
+        if not isinstance(code, LdpcCode):
+            raise TypeError('code must be an LdpcCode or None, got %s' % type(code).__name__)
+        self.code = code
+        self.K, self.P, self.N, self.M, self.dv, self.dc, self.W = code.K, code.P, code.n_var, code.n_chk, code.dv, code.dc, code.W
+        self.one_word = code.K <= 64 and 1 <= code.P <= 64       # the one-word kernels' family (fgnn_ldpc_encode, fgnn_ldpc_sample_rng)
+        self._decode_tables = None                               # built on the first ``decode`` (a code may exceed the decoder only)
+        gwords = code.gwords.view(np.int64)                       # [P, W]; the one-word kernels' gmask is its column 0, [P]
+        self.gmask = torch.from_numpy((gwords[:, 0] if self.one_word else gwords).copy()).to(self.device)
+        self.var_to_factors = torch.from_numpy(code.var_to_factors.astype(np.int32)).to(self.device)
+        self.factor_to_vars = torch.from_numpy(code.factor_to_vars.astype(np.int32)).to(self.device)
+        self.nn_idx_f2v = torch.from_numpy(code.var_to_factors.copy()).to(self.device)
+        self.nn_idx_v2f = torch.from_numpy(code.factor_to_vars.copy()).to(self.device)
+
+    def _features(self, B, dtype):
+        """Empty (node_feature, hop_feature, efeature_f2v, efeature_v2f) for B words."""
+        new = lambda *shape: torch.empty(shape, device=self.device, dtype=dtype)
+        return (new(B, 2, self.N, 1), new(B, self.dc, self.M, 1), new(B, self.dc + 1, self.N, self.dv),
+                new(B, self.dc + 1, self.M, self.dc))
 
     def encode(self, s):
         """s [B,48] (any integer / bool dtype, values 0/1) -> codewords [B,96] uint8 = [s | G s mod 2]."""
@@ -71,7 +83,10 @@ class LdpcDataPath:
         s = s.to(self.device, torch.uint8).contiguous()
         B = s.shape[0]
         cw = torch.empty((B, self.K + self.P), device=self.device, dtype=torch.uint8)
-        _hip.call('fgnn_ldpc_encode', s, self.gmask, B, self.K, self.P, cw)
+        if self.one_word:
+            _hip.call('fgnn_ldpc_encode', s, self.gmask, B, self.K, self.P, cw)
+        else:
+            _hip.call('fgnn_ldpc_encode_words', s, self.gmask, B, self.K, self.P, self.W, cw)
         return cw
 
     def channel_features(self, cw, snr_db, sigma_b, burst_prob=0.05, noise=None, generator=None,
@@ -84,6 +99,8 @@ class LdpcDataPath:
         efeature_v2f [B,7,48,6])."""
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError('dtype must be float32 or bfloat16')
+        if cw.dim() != 2 or cw.shape[1] != self.N:
+            raise ValueError('codewords must be [B, %d], got %s' % (self.N, tuple(cw.shape)))
         B, N = cw.shape
         dev = self.device
         cw = cw.to(dev, torch.uint8).contiguous()
@@ -98,17 +115,14 @@ class LdpcDataPath:
         else:
             z1, u, z2 = [t.to(dev, torch.float32).contiguous() for t in noise]
         y = torch.empty((B, N), device=dev, dtype=torch.float32)
-        node = torch.empty((B, 2, 96, 1), device=dev, dtype=dtype)
-        hop = torch.empty((B, 6, 48, 1), device=dev, dtype=dtype)
-        ef_f2v = torch.empty((B, 7, 96, 3), device=dev, dtype=dtype)
-        ef_v2f = torch.empty((B, 7, 48, 6), device=dev, dtype=dtype)
+        node, hop, ef_f2v, ef_v2f = self._features(B, dtype)
         if kernel_rng is not None:
             seed, offset = (int(v) & 0xFFFFFFFFFFFFFFFF for v in kernel_rng)
             _hip.call('fgnn_ldpc_channel_features_rng', cw, snr_db, sigma_b, float(burst_prob), seed, offset, self.var_to_factors,
-                      self.factor_to_vars, B, 96, 48, 3, 6, _hip.dtype_code(node), y, node, hop, ef_f2v, ef_v2f)
+                      self.factor_to_vars, B, self.N, self.M, self.dv, self.dc, _hip.dtype_code(node), y, node, hop, ef_f2v, ef_v2f)
             return y, node, hop, ef_f2v, ef_v2f
         _hip.call('fgnn_ldpc_channel_features', cw, snr_db, sigma_b, float(burst_prob), z1, u, z2, self.var_to_factors, self.factor_to_vars,
-                  B, 96, 48, 3, 6, _hip.dtype_code(node), y, node, hop, ef_f2v, ef_v2f)
+                  B, self.N, self.M, self.dv, self.dc, _hip.dtype_code(node), y, node, hop, ef_f2v, ef_v2f)
         return y, node, hop, ef_f2v, ef_v2f
 
     def received_features(self, y, snr_db, dtype=torch.float32):
@@ -116,17 +130,14 @@ class LdpcDataPath:
         batch): y [B,96] and snr_db [B] (one value per word) or [B,96] (the stored per-bit ``snr_dbs`` rows; node row 1 is that row).
         Returns (node_feature [B,2,96,1], hop_feature [B,6,48,1], efeature_f2v [B,7,96,3], efeature_v2f [B,7,48,6]) in ``dtype``:
         on the ``y`` that ``channel_features`` returns, exactly that call's four feature tensors."""
-        B = check_received_args(y, snr_db, dtype)
+        B = check_received_args(y, snr_db, dtype, self.N)
         dev = self.device
         y = y.to(dev, torch.float32).contiguous()
         snr_db = snr_db.to(dev, torch.float32).contiguous()
-        snr_sb, snr_sn = (1, 0) if snr_db.dim() == 1 else (96, 1)
-        node = torch.empty((B, 2, 96, 1), device=dev, dtype=dtype)
-        hop = torch.empty((B, 6, 48, 1), device=dev, dtype=dtype)
-        ef_f2v = torch.empty((B, 7, 96, 3), device=dev, dtype=dtype)
-        ef_v2f = torch.empty((B, 7, 48, 6), device=dev, dtype=dtype)
-        _hip.call('fgnn_ldpc_received_features', y, snr_db, snr_sb, snr_sn, self.var_to_factors, self.factor_to_vars, B, 96, 48, 3, 6,
-                  _hip.dtype_code(node), node, hop, ef_f2v, ef_v2f)
+        snr_sb, snr_sn = (1, 0) if snr_db.dim() == 1 else (self.N, 1)
+        node, hop, ef_f2v, ef_v2f = self._features(B, dtype)
+        _hip.call('fgnn_ldpc_received_features', y, snr_db, snr_sb, snr_sn, self.var_to_factors, self.factor_to_vars, B, self.N, self.M,
+                  self.dv, self.dc, _hip.dtype_code(node), node, hop, ef_f2v, ef_v2f)
         return node, hop, ef_f2v, ef_v2f
 
     def make_test_set(self, num, seed=0, snr_db=(0, 1, 2, 3, 4), sigma_b=(0, 1, 2, 3, 4, 5), burst_prob=0.05, baseline=True):
@@ -160,7 +171,7 @@ class LdpcDataPath:
         for k in range(0, (n + chunk - 1) // chunk):
             i, j = k * chunk, min(n, (k + 1) * chunk)
             y[i:j] = self.channel_features(cw[i:j], snr[i:j], sb[i:j], burst_prob, kernel_rng=(seed, 2 ** 62 + k))[0]
-        out = {'noizy_sg': y.cpu(), 'gts': cw.long().cpu(), 'snr_dbs': snr[:, None].expand(-1, 96).contiguous().cpu(),
+        out = {'noizy_sg': y.cpu(), 'gts': cw.long().cpu(), 'snr_dbs': snr[:, None].expand(-1, self.N).contiguous().cpu(),
                'sigma_b': sb.cpu()}
         if baseline:
             from .ldpc_eval import LdpcErrorCounts
@@ -168,7 +179,7 @@ class LdpcDataPath:
             for i in range(0, n, chunk):
                 j = min(n, i + chunk)
                 x = self.decode(self.bit_prior(y[i:j], snr[i:j]), loops=100)[0]
-                acc.add_bits(x, cw[i:j], snr[i:j], sb[i:j])
+                acc.add_bits(x, cw[i:j], snr[i:j], sb[i:j], nbits=self.K)
             out['sp_error'] = torch.from_numpy(acc.result()['err_class'])
         return out
 
@@ -206,6 +217,9 @@ class LdpcDataPath:
         """The reference's sum-product baseline `zb2x(bias, 48, 48, A2, 1, loops)` (lib/data/ldpc.py:18-24) for a
         batch: bias [B,96] float64 = P(bit = 1) (see ``bit_prior``).  Returns (x [B,96] uint8 hard decisions — the
         message is x[:, :48] —, violated checks [B] int32, iterations [B] int32[, q1 [B,96] float64])."""
+        if self._decode_tables is None:
+            self.code.require_decoder()
+            self._decode_tables = self._incidence_tables(self.code.nlist, self.M)
         col_ptr, row_ptr, row_edge, row_var, N, M, E = self._decode_tables
         if bias.dim() != 2 or bias.shape[1] != N:
             raise ValueError('bias must be [B, %d], got %s' % (N, tuple(bias.shape)))
@@ -252,27 +266,30 @@ class LdpcDataPath:
         B, dev, N = int(B), self.device, self.K + self.P
         if out is None:
             new = lambda *shape, dt=dtype: torch.empty(shape, device=dev, dtype=dt)
-            out = LdpcBatch(new(B, 2, N, 1), new(B, 6, 48, 1), self.nn_idx_f2v.unsqueeze(0).expand(B, -1, -1),
-                            self.nn_idx_v2f.unsqueeze(0).expand(B, -1, -1), new(B, 7, N, 3), new(B, 7, 48, 6),
+            out = LdpcBatch(new(B, 2, N, 1), new(B, self.dc, self.M, 1), self.nn_idx_f2v.unsqueeze(0).expand(B, -1, -1),
+                            self.nn_idx_v2f.unsqueeze(0).expand(B, -1, -1), new(B, self.dc + 1, N, self.dv),
+                            new(B, self.dc + 1, self.M, self.dc),
                             new(B, self.K, dt=torch.float32), new(B, dt=torch.float32), new(B, dt=torch.float32),
                             new(B, N, dt=torch.uint8), new(B, N, dt=torch.float32))
         farr = lambda c: (ctypes.c_float * len(c))(*[float(v) for v in c])
-        _hip.call('fgnn_ldpc_sample_rng', int(seed), int(step), farr(snr_choices), len(snr_choices), farr(self.sigma_b_choices),
-                  len(self.sigma_b_choices), float(burst_prob), self.gmask, self.var_to_factors, self.factor_to_vars, B, self.K, self.P,
-                  48, 3, 6, _hip.F32 if dtype == torch.float32 else _hip.BF16, out.node_feature, out.hop_feature, out.efeature_f2v,
-                  out.efeature_v2f, out.snr_db, out.sigma_b, out.cw, out.label, out.y)
+        name, sizes = (('fgnn_ldpc_sample_rng', (B, self.K, self.P)) if self.one_word else
+                       ('fgnn_ldpc_sample_rng_words', (B, self.K, self.P, self.W)))
+        _hip.call(name, int(seed), int(step), farr(snr_choices), len(snr_choices), farr(self.sigma_b_choices),
+                  len(self.sigma_b_choices), float(burst_prob), self.gmask, self.var_to_factors, self.factor_to_vars, *sizes,
+                  self.M, self.dv, self.dc, _hip.F32 if dtype == torch.float32 else _hip.BF16, out.node_feature, out.hop_feature,
+                  out.efeature_f2v, out.efeature_v2f, out.snr_db, out.sigma_b, out.cw, out.label, out.y)
         return out
 
 
-def check_received_args(y, snr_db, dtype):
-    """Shapes of ``LdpcDataPath.received_features`` (before anything reaches the device): returns B."""
+def check_received_args(y, snr_db, dtype, n_var=96):
+    """Shapes of ``LdpcDataPath.received_features`` for a code of ``n_var`` variables (before anything reaches the device): returns B."""
     if dtype not in (torch.float32, torch.bfloat16):
         raise ValueError('dtype must be float32 or bfloat16')
-    if y.dim() != 2 or y.shape[1] != 96:
-        raise ValueError('received words must be [B, 96], got %s' % (tuple(y.shape),))
+    if y.dim() != 2 or y.shape[1] != n_var:
+        raise ValueError('received words must be [B, %d], got %s' % (n_var, tuple(y.shape),))
     B = y.shape[0]
-    if tuple(snr_db.shape) not in ((B,), (B, 96)):
-        raise ValueError('snr_db must be [B] or [B, 96] with B = %d, got %s' % (B, tuple(snr_db.shape)))
+    if tuple(snr_db.shape) not in ((B,), (B, n_var)):
+        raise ValueError('snr_db must be [B] or [B, %d] with B = %d, got %s' % (n_var, B, tuple(snr_db.shape)))
     return B
 
 

@@ -24,23 +24,40 @@ def _edge_mlp(cin, hidden, cout):
 
 
 class LDPCModel(torch.nn.Module):
-    def __init__(self, nfeature_dim, hop_order, nedge_type, with_residual=True, aggregator='max'):
+    def __init__(self, nfeature_dim, hop_order, nedge_type, with_residual=True, aggregator='max', n_var=96, n_msg=48):
+        """``n_var`` variables of which the first ``n_msg`` are the message bits the model decodes; ``hop_order`` = dc, the variables
+        per check.  The defaults are the 96.3.963 code's and give the reference's 651 state-dict entries and shapes."""
         super().__init__()
-        self.main = FactorNN(nfeature_dim, [hop_order, 96],
+        n_var, n_msg = int(n_var), int(n_msg)
+        if not 1 <= n_msg <= n_var:
+            raise ValueError('n_msg = %d must be in 1..n_var = %d' % (n_msg, n_var))
+        from .ldpc_code import MODEL_MAX_VAR
+        if n_var > MODEL_MAX_VAR:
+            raise ValueError('n_var = %d: the model takes at most %d variables (the largest size its forward and backward are verified '
+                             'at; its hyper-factor listens to all of them)' % (n_var, MODEL_MAX_VAR))
+        self.n_var, self.n_msg = n_var, n_msg
+        self.main = FactorNN(nfeature_dim, [hop_order, n_var],
                              [64, 64, 64, 128, 256, 256, 128, 64, 64], [nedge_type, 1], 2,
                              skip_link={4: 3, 5: 2, 7: 0}, ret_high=True, aggregator=aggregator)
-        self.emodel_f2v = _edge_mlp(7, 64, nedge_type)
-        self.emodel_v2f = _edge_mlp(7, 64, nedge_type)
+        self.emodel_f2v = _edge_mlp(hop_order + 1, 64, nedge_type)       # (dc + 1 raw edge features: 7 for dc = 6)
+        self.emodel_v2f = _edge_mlp(hop_order + 1, 64, nedge_type)
         frozen = lambda t: torch.nn.Parameter(t, requires_grad=False)
-        # hyper-factor: one factor listening to all 96 variables, every variable listening to it
-        self.hnn_idx_v2f = frozen(torch.arange(96, dtype=torch.int64).reshape(1, 1, 96))
-        self.hnn_idx_f2v = frozen(torch.zeros(1, 96, 1, dtype=torch.int64))
-        self.hetype_v2f = frozen(torch.ones(1, 1, 1, 96))
-        self.hetype_f2v = frozen(torch.ones(1, 1, 96, 1))
+        # hyper-factor: one factor listening to all n_var (96) variables, every variable listening to it
+        self.hnn_idx_v2f = frozen(torch.arange(n_var, dtype=torch.int64).reshape(1, 1, n_var))
+        self.hnn_idx_f2v = frozen(torch.zeros(1, n_var, 1, dtype=torch.int64))
+        self.hetype_v2f = frozen(torch.ones(1, 1, 1, n_var))
+        self.hetype_f2v = frozen(torch.ones(1, 1, n_var, 1))
         self.with_residual = with_residual
         self.nhop_regressor = torch.nn.Sequential(
             torch.nn.Linear(64, 128), torch.nn.BatchNorm1d(128), torch.nn.ReLU(),
             torch.nn.Linear(128, 128), torch.nn.ReLU(), torch.nn.Linear(128, 1), torch.nn.ReLU())
+
+    @classmethod
+    def for_code(cls, code, nedge_type=4, nfeature_dim=2, with_residual=True, aggregator='max'):
+        """The model for an ``LdpcCode``: ``hop_order`` = dc, ``n_var`` = N, ``n_msg`` = K (ValueError beyond the model's limit, ``LdpcCode.require_model``)."""
+        code.require_model()
+        return cls(nfeature_dim, code.dc, nedge_type, with_residual=with_residual, aggregator=aggregator, n_var=code.n_var,
+                   n_msg=code.K)
 
     def _regress(self, hop):
         """``nhop_regressor`` (train_ldpc.py:48-54,93: Linear -> BatchNorm1d -> ReLU -> Linear -> ReLU -> Linear -> ReLU on the
@@ -81,7 +98,7 @@ class LDPCModel(torch.nn.Module):
         B = node_feature.shape[0]
         etype_f2v = self.emodel_f2v(efeature_f2v)
         etype_v2f = self.emodel_v2f(efeature_v2f)
-        hyper_in = node_feature[:, 0, :, :].detach().reshape(B, 96, 1, 1)
+        hyper_in = node_feature[:, 0, :, :].detach().reshape(B, self.n_var, 1, 1)
         dt = node_feature.dtype
         # expand (batch stride 0) instead of the reference's repeat: same values, and the kernel
         # sees "one graph shared by the batch"
@@ -93,9 +110,9 @@ class LDPCModel(torch.nn.Module):
             [etype_v2f, cast_cached(self.hetype_v2f, dt).expand(B, -1, -1, -1)])
         if self.with_residual:
             res = res + node_feature[:, :1, :, :]
-        res = res.reshape(B, 96)
+        res = res.reshape(B, self.n_var)
         snr_pred = self._regress(hops[1].reshape(B, -1))
-        return res[:, :48].contiguous(), snr_pred
+        return res[:, :self.n_msg].contiguous(), snr_pred
 
 
 class _DecodingLoss(torch.autograd.Function):

@@ -115,37 +115,58 @@ class LdpcErrorCounts:
                 'counts': c}
 
 
-def load_test_set(test_set, device):
+def load_test_set(test_set, device, n_var=96):
     """A test set (the dict of ``make_test_set`` / the reference's generator, or a path to its ``torch.save`` file) on ``device``:
-    (noizy_sg [n,96] f32, gts [n,96], snr_dbs [n,96] or [n] f32, sigma_b [n] f32)."""
+    (noizy_sg [n,96] f32, gts [n,96], snr_dbs [n,96] or [n] f32, sigma_b [n] f32); 96 reads ``n_var`` for another code."""
     if isinstance(test_set, (str, os.PathLike)):
         test_set = torch.load(test_set, map_location='cpu')
     y, gts, snr, sb = (test_set[k] for k in ('noizy_sg', 'gts', 'snr_dbs', 'sigma_b'))
-    n = y.shape[0]
-    if tuple(y.shape) != (n, 96) or tuple(gts.shape) != (n, 96) or tuple(snr.shape) not in ((n, 96), (n,)) or tuple(sb.shape) != (n,):
-        raise ValueError('test set shapes: noizy_sg %s, gts %s, snr_dbs %s, sigma_b %s (want [n,96], [n,96], [n,96] or [n], [n])'
-                         % (tuple(y.shape), tuple(gts.shape), tuple(snr.shape), tuple(sb.shape)))
+    n, N = y.shape[0], int(n_var)
+    if tuple(y.shape) != (n, N) or tuple(gts.shape) != (n, N) or tuple(snr.shape) not in ((n, N), (n,)) or tuple(sb.shape) != (n,):
+        raise ValueError('test set shapes: noizy_sg %s, gts %s, snr_dbs %s, sigma_b %s (want [n,%d], [n,%d], [n,%d] or [n], [n])'
+                         % (tuple(y.shape), tuple(gts.shape), tuple(snr.shape), tuple(sb.shape), N, N, N))
     if gts.dtype not in (torch.int64, torch.uint8):
         gts = gts.long()
     return (y.to(device, torch.float32), gts.to(device), snr.to(device, torch.float32), sb.to(device, torch.float32))
 
 
-def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=False, snr_grid=SNR_GRID, sigma_grid=SIGMA_GRID):
+def load_model(model_path, code=None, aggregator='max', device='cpu'):
+    """The model of a checkpoint (``ldpc_train``'s or the reference script's) for ``code`` (None: the built-in 96.3.963).  A checkpoint
+    trained for another code — its 'code' entry, or the lack of one, says which — is refused with a ValueError."""
+    from .ldpc_code import LdpcCode
+    from .ldpc_train import build_model
+    code = LdpcCode.builtin() if code is None else code
+    ckpt = torch.load(model_path, map_location='cpu', weights_only=True)
+    code.check_checkpoint(ckpt, model_path)
+    model = build_model(aggregator, code)
+    model.load_state_dict(ckpt['model_state_dict'], strict=True)
+    return model.to(device)
+
+
+def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=False, snr_grid=SNR_GRID, sigma_grid=SIGMA_GRID, code=None):
     """``train_ldpc.py:test()`` for an ``fgnn_amd.LDPCModel`` on a test set (dict or path): the model in eval mode under no_grad
     (bf16: bf16 features under bf16 autocast), ``batch_size`` words per batch, nothing read back to the host until the end.  Returns
     ``LdpcErrorCounts.result()`` of the model's logits; with ``baseline`` also, under 'baseline', that of the sum-product decoder
     (``decode(bit_prior(y, snr), loops=100)``, lib/data/ldpc.py:18-24) on the same received words.  The model's training flag is
-    restored afterwards."""
+    restored afterwards.  ``code``: the ``LdpcCode`` the model was built for (None: the built-in 96.3.963); the errors are counted
+    over its K message bits and the baseline runs on its ``nlist``.  ``model`` may also be a checkpoint's path (``load_model``)."""
     if dtype not in (torch.float32, torch.bfloat16):
         raise ValueError('dtype must be float32 or bfloat16')
+    from .ldpc_code import LdpcCode
+    code = LdpcCode.builtin() if code is None else code
+    if isinstance(model, (str, os.PathLike)):
+        model = load_model(model, code, device='cuda')
+    if (getattr(model, 'n_var', code.n_var), getattr(model, 'n_msg', code.K)) != (code.n_var, code.K):
+        raise ValueError('the model decodes %d of %d variables, %r has K = %d of N = %d: pass the code the model was built for'
+                         % (model.n_msg, model.n_var, code, code.K, code.n_var))
     batch_size = int(batch_size)
     if batch_size < 1:
         raise ValueError('batch_size must be >= 1')
     dev = next(model.parameters()).device
     counts = LdpcErrorCounts(dev, snr_grid, sigma_grid)
     sp = LdpcErrorCounts(dev, snr_grid, sigma_grid) if baseline else None
-    path = LdpcDataPath(dev)
-    y, gts, snr, sb = load_test_set(test_set, dev)
+    path = LdpcDataPath(dev, code)
+    y, gts, snr, sb = load_test_set(test_set, dev, code.n_var)
     n = y.shape[0]
     was = model.training
     model.eval()
@@ -157,11 +178,11 @@ def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=Fal
                 node, hop, ef_f2v, ef_v2f = path.received_features(y[i:j], snr[i:j], dtype)
                 logits, _ = model(node, hop, path.nn_idx_f2v.unsqueeze(0).expand(B, -1, -1),
                                   path.nn_idx_v2f.unsqueeze(0).expand(B, -1, -1), ef_f2v, ef_v2f)
-                counts.add_logits(logits, gts[i:j], snr[i:j], sb[i:j])
+                counts.add_logits(logits, gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
                 if baseline:
                     snr0 = snr[i:j] if snr.dim() == 1 else snr[i:j, 0]
                     x = path.decode(path.bit_prior(y[i:j], snr0), loops=100)[0]
-                    sp.add_bits(x, gts[i:j], snr[i:j], sb[i:j])
+                    sp.add_bits(x, gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
     finally:
         model.train(was)
     res = counts.result()
@@ -184,22 +205,29 @@ def main(argv=None):
     ap.add_argument('--num', type=int, default=1000, help='items per class (--make_test_set)')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--burst_prob', type=float, default=0.05)
+    ap.add_argument('--code', default='builtin', help='builtin (96.3.963), the path of an alist file, or gallager:N,dv,dc,seed')
     args = ap.parse_args(argv)
     dev = torch.device('cuda:0')
+    from .ldpc_code import LdpcCode
+    code = LdpcCode.from_spec(args.code)
     if args.make_test_set:
-        sp = LdpcDataPath(dev).write_test_set(args.make_test_set, args.num, seed=args.seed, burst_prob=args.burst_prob)
+        sp = LdpcDataPath(dev, code).write_test_set(args.make_test_set, args.num, seed=args.seed, burst_prob=args.burst_prob)
         print(sp)
         return 0
     if not args.test_path or not args.model_path:
         ap.error('give --test_path and --model_path, or --make_test_set')
-    from .ldpc import LDPCModel
-    with contextlib.redirect_stdout(sys.stderr):           # (the model's construction talks; stdout carries the result only)
-        model = LDPCModel(2, 6, 4, aggregator=args.aggregator)
-    ckpt = torch.load(args.model_path, map_location=dev)
-    model.load_state_dict(ckpt['model_state_dict'])
-    model.to(dev)
+    if code.is_default:
+        from .ldpc import LDPCModel
+        with contextlib.redirect_stdout(sys.stderr):           # (the model's construction talks; stdout carries the result only)
+            model = LDPCModel(2, 6, 4, aggregator=args.aggregator)
+        ckpt = torch.load(args.model_path, map_location=dev)
+        code.check_checkpoint(ckpt, args.model_path)
+        model.load_state_dict(ckpt['model_state_dict'])
+        model.to(dev)
+    else:
+        model = load_model(args.model_path, code, args.aggregator, dev)
     res = evaluate(model, args.test_path, args.batch_size, torch.bfloat16 if args.dtype == 'bf16' else torch.float32,
-                   baseline=args.baseline)
+                   baseline=args.baseline, code=code)
     print(res['ber'])
     print(torch.FloatTensor(res['err_class']))
     if args.baseline:

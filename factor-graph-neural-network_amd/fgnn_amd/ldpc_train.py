@@ -11,7 +11,8 @@ dict: ``python -m fgnn_amd.ldpc_eval --model_path`` reads them, and they are lai
 keys are the script's class's (tests/test_host_logic.py::test_ldpc_model_state_dict_surface), and a stock ``torch.optim.Adam`` /
 ``LambdaLR`` composed as the script composes them load the other two dicts (tests/test_ldpc_train.py).
 
-``python -m fgnn_amd.ldpc_train --n_epochs 20 --batch_size 4096`` is the command line.
+``python -m fgnn_amd.ldpc_train --n_epochs 20 --batch_size 4096`` is the command line; ``--code`` (``train(code=...)``) trains a decoder
+for another regular code (``fgnn_amd.ldpc_code.LdpcCode``), which the reference cannot: its checkpoint carries the code it was trained for.
 """
 import argparse
 import contextlib
@@ -51,10 +52,14 @@ def default_steps_per_epoch(batch_size):
     return -(-TRAIN_SIZE // batch_size)
 
 
-def checkpoint_dict(model, optimizer, scheduler, epoch, gcnt):
-    """The dict the script saves (``get_model_dict``, train_ldpc.py:185-192)."""
-    return {'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(), 'lr_sche': scheduler.state_dict(),
-            'epoch': int(epoch), 'gcnt': int(gcnt)}
+def checkpoint_dict(model, optimizer, scheduler, epoch, gcnt, code=None):
+    """The dict the script saves (``get_model_dict``, train_ldpc.py:185-192); for a non-default ``code`` only, plus a 'code' entry
+    (``LdpcCode.checkpoint_entry``: n_var, n_chk, dv, dc and var_to_factors as tensors) by which a reader refuses another code's model."""
+    d = {'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(), 'lr_sche': scheduler.state_dict(),
+         'epoch': int(epoch), 'gcnt': int(gcnt)}
+    if code is not None and not code.is_default:
+        d['code'] = code.checkpoint_entry()
+    return d
 
 
 def checkpoint_path(out_dir, model_name, epoch, snr):
@@ -66,17 +71,24 @@ def _scheduler(opt):
     return torch.optim.lr_scheduler.LambdaLR(opt, lr_lambda=lr_sched)
 
 
-def build_model(aggregator='max'):
-    """``LDPCModel(2, 6, 4)`` as the script builds it (train_ldpc.py:335); its construction prints, stdout stays the caller's."""
+def build_model(aggregator='max', code=None):
+    """``LDPCModel(2, 6, 4)`` as the script builds it (train_ldpc.py:335), or ``LDPCModel.for_code(code)`` for a non-default code; its
+    construction prints, stdout stays the caller's."""
     from .ldpc import LDPCModel
     with contextlib.redirect_stdout(sys.stderr):
-        return LDPCModel(2, 6, 4, aggregator=aggregator)
+        if code is None or code.is_default:
+            return LDPCModel(2, 6, 4, aggregator=aggregator)
+        return LDPCModel.for_code(code, 4, aggregator=aggregator)
 
 
 def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=None, model_name='FactorNN', steps_per_epoch=None,
           dtype=torch.bfloat16, seed=0, out_dir='.', save_every=SAVE_EVERY, log_every=LOG_EVERY, graph=True, test_set=None, lr=LR,
-          device='cuda'):
-    """Train ``LDPCModel(2, 6, 4, aggregator)`` for ``n_epochs`` epochs of ``steps_per_epoch`` batches (default: the script's
+          device='cuda', code=None):
+    """``code``: an ``LdpcCode`` (None: the built-in 96.3.963, exactly as before) within ``LdpcCode.require_trainer``'s limits (dv = 3,
+    dc = 6, N <= 96; ValueError otherwise, before anything reaches the device): the sampler, the model (``LDPCModel.for_code``), the
+    K label bits and the evaluation follow it, and the checkpoints carry a 'code' entry that ``model_path`` and ``ldpc_eval`` check.
+
+    Train ``LDPCModel(2, 6, 4, aggregator)`` for ``n_epochs`` epochs of ``steps_per_epoch`` batches (default: the script's
     ceil(10000 / batch_size)).  Batch number ``gcnt`` (counted from 0 over the whole run, resumes included) is
     ``LdpcDataPath.sample_rng(batch_size, seed, step=gcnt, dtype, snr_db=snr)``: SNR drawn from {0..4} dB per word unless ``snr`` fixes
     it, as ``ContinousCodesSP(snr=args.snr)``; ``make_test_set`` draws at offsets from 2^62, so no test word shares noise with a
@@ -104,6 +116,9 @@ def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=Non
 
     Returns a dict: loss (BCE mean), sigma_b_loss and acc of the last log window, losses (every step's total, f32 values), steps, gcnt,
     seconds (the step loops only), graphed, checkpoint (the last one's path), and ber / err_class when evaluated."""
+    from .ldpc_code import LdpcCode
+    code = LdpcCode.builtin() if code is None else code
+    code.require_trainer()
     n_epochs, batch_size, seed = int(n_epochs), int(batch_size), int(seed)
     steps_per_epoch = default_steps_per_epoch(batch_size) if steps_per_epoch is None else int(steps_per_epoch)
     save_every = int(save_every)
@@ -122,10 +137,11 @@ def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=Non
     from .ldpc import decoding_loss_parts
 
     torch.manual_seed(seed)
-    model = build_model(aggregator)
+    model = build_model(aggregator, code)
     ckpt = None
     if model_path:
         ckpt = torch.load(model_path, map_location='cpu', weights_only=True)
+        code.check_checkpoint(ckpt, model_path)
         model.load_state_dict(ckpt['model_state_dict'], strict=True)
     model.to(dev).train()
     opt = FastAdam(model.parameters(), lr=lr, weight_decay=WEIGHT_DECAY)
@@ -136,7 +152,7 @@ def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=Non
         sched.load_state_dict(ckpt['lr_sche'])
         start_epoch, gcnt = int(ckpt['epoch']), int(ckpt['gcnt'])
         graph_mod.state_moved()
-    path = LdpcDataPath(dev)
+    path = LdpcDataPath(dev, code)
     static = path.sample_rng(batch_size, seed, step=gcnt, dtype=dtype, snr_db=snr)       # the buffers every step reads
     draw = lambda step: path.sample_rng(batch_size, seed, step=step, dtype=dtype, snr_db=snr, out=static)
 
@@ -189,7 +205,7 @@ def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=Non
     def save(epoch):
         nonlocal saved_to
         saved_to = checkpoint_path(out_dir, model_name, epoch, snr)
-        torch.save(checkpoint_dict(model, opt, sched, epoch, gcnt), saved_to)
+        torch.save(checkpoint_dict(model, opt, sched, epoch, gcnt, code), saved_to)
 
     seconds, steps = 0.0, 0
     for epoch in range(start_epoch, n_epochs):
@@ -220,7 +236,7 @@ def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=Non
               'steps': steps, 'gcnt': gcnt, 'seconds': seconds, 'graphed': graphed is not None, 'checkpoint': saved_to}
     if test_set is not None:
         from .ldpc_eval import evaluate
-        res = evaluate(model, test_set, dtype=dtype)
+        res = evaluate(model, test_set, dtype=dtype, code=code)
         result.update(ber=res['ber'], err_class=res['err_class'])
         print(res['ber'])
         print(torch.FloatTensor(res['err_class']))
@@ -245,13 +261,15 @@ def main(argv=None):
     ap.add_argument('--log_every', type=int, default=LOG_EVERY)
     ap.add_argument('--no-graph', dest='graph', action='store_false', help='eager steps, no hipGraph replay')
     ap.add_argument('--test_path', default=None, help='test set to evaluate on after the last epoch (ldpc_eval)')
+    ap.add_argument('--code', default='builtin', help='builtin (96.3.963), the path of an alist file, or gallager:N,dv,dc,seed (dv = 3, dc = 6, N <= 96)')
     ap.add_argument('--json', action='store_true', help='print the result as one JSON line at the end')
     args = ap.parse_args(argv)
     if args.model_path and not os.path.exists(args.model_path):      # (the script's default is a path that need not exist)
         args.model_path = None
+    from .ldpc_code import LdpcCode
     r = train(args.n_epochs, args.batch_size, args.snr, args.aggregator, args.model_path, args.model_name, args.steps_per_epoch,
               torch.bfloat16 if args.dtype == 'bf16' else torch.float32, args.seed, args.out_dir, args.save_every, args.log_every,
-              args.graph, args.test_path, LR, 'cuda:0')
+              args.graph, args.test_path, LR, 'cuda:0', LdpcCode.from_spec(args.code))
     if args.json:
         out = {k: v for k, v in r.items() if k not in ('losses', 'err_class')}
         if 'err_class' in r:
