@@ -41,6 +41,30 @@ def check_sample_rng_args(B, seed, step, dtype, choices_snr, choices_sigma, out)
             raise ValueError('out must be a previous sample_rng result for the same (B, dtype)')
 
 
+LLR_ALGORITHMS = {'min-sum': 0, 'offset-min-sum': 1, 'sum-product': 2}     # fgnn_ldpc_decode_llr's ``algorithm``
+LLR_SCHEDULES = ('flooding', 'layered')
+
+
+def check_decode_llr_args(llr, n_var, algorithm, schedule, max_iter, alpha, beta):
+    """Arguments of ``LdpcDataPath.decode_llr`` (before anything reaches the device).  Returns (B, the algorithm's code)."""
+    if algorithm not in LLR_ALGORITHMS:
+        raise ValueError('algorithm must be one of %s, got %r' % (', '.join(LLR_ALGORITHMS), algorithm))
+    if schedule not in LLR_SCHEDULES:
+        raise ValueError('schedule must be one of %s, got %r' % (', '.join(LLR_SCHEDULES), schedule))
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= int(max_iter) < 2 ** 31:
+        raise ValueError('max_iter must be an integer in [1, 2^31), got %r' % (max_iter,))
+    for what, v in (('alpha', alpha), ('beta', beta)):
+        if not (np.isfinite(float(v)) and 0 <= float(v) <= 3.0e38):
+            raise ValueError('%s must be a finite float32 value >= 0, got %r' % (what, v))
+    if not isinstance(llr, torch.Tensor) or llr.dim() != 2 or llr.shape[1] != int(n_var):
+        raise ValueError('llr must be a [B, %d] tensor, got %s' % (n_var, tuple(llr.shape) if isinstance(llr, torch.Tensor) else type(llr).__name__))
+    if not llr.dtype.is_floating_point:
+        raise ValueError('llr must be a floating-point tensor, got %s' % llr.dtype)
+    if llr.shape[0] >= 2 ** 31:
+        raise ValueError('at most 2^31 - 1 words per call, got %d' % llr.shape[0])
+    return llr.shape[0], LLR_ALGORITHMS[algorithm]
+
+
 class LdpcDataPath:
     """The data path of one regular LDPC code (``code``: an ``LdpcCode``; None: the built-in 96.3.963 — 48 message bits, 48 parity
     bits, 3 checks per variable, 6 variables per check): K message bits, P parity bits (codeword = [s | G s]), N = K + P variables,
@@ -63,6 +87,7 @@ class LdpcDataPath:
         self.K, self.P, self.N, self.M, self.dv, self.dc, self.W = code.K, code.P, code.n_var, code.n_chk, code.dv, code.dc, code.W
         self.one_word = code.K <= 64 and 1 <= code.P <= 64       # the one-word kernels' family (fgnn_ldpc_encode, fgnn_ldpc_sample_rng)
         self._decode_tables = None                               # built on the first ``decode`` (a code may exceed the decoder only)
+        self._llr_tables = None                                  # ... and on the first ``decode_llr``
         gwords = code.gwords.view(np.int64)                       # [P, W]; the one-word kernels' gmask is its column 0, [P]
         self.gmask = torch.from_numpy((gwords[:, 0] if self.one_word else gwords).copy()).to(self.device)
         self.var_to_factors = torch.from_numpy(code.var_to_factors.astype(np.int32)).to(self.device)
@@ -231,6 +256,38 @@ class LdpcDataPath:
         iters = torch.empty((B,), device=self.device, dtype=torch.int32)
         _hip.call('fgnn_ldpc_decode', bias, col_ptr, row_ptr, row_edge, row_var, B, N, M, E, int(loops), x, q1, viol, iters)
         return (x, viol, iters, q1) if want_posteriors else (x, viol, iters)
+
+    def bit_llr(self, y, snr_db):
+        """The log-likelihood ratio of ``bit_prior``: log P(bit = 0 | y) / P(bit = 1 | y) = -2 gcx y with gcx = 10^(snr_db / 20), f32;
+        y [B, N], snr_db [B]."""
+        gcx = torch.pow(10.0, snr_db.to(self.device, torch.float32) / 20.0)[:, None]
+        return -2.0 * gcx * y.to(self.device, torch.float32)
+
+    def decode_llr(self, llr, algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.8125, beta=0.5, want_posteriors=False):
+        """The LLR-domain decoders (fgnn_ldpc_decode_llr, include/fgnn_hip_ldpc_llr.h; no counterpart in the reference) for a batch:
+        llr [B, N] = log P(bit = 0) / P(bit = 1) (see ``bit_llr``; f32, rows may be strided).  ``algorithm``: 'min-sum' (normalized
+        by ``alpha``), 'offset-min-sum' (offset ``beta``) or 'sum-product'; ``schedule``: 'flooding', or 'layered' over
+        ``code.layers()``.  Returns (x [B, N] uint8 hard decisions — the message is x[:, :K] —, violated checks [B] int32, iterations
+        [B] int32[, post [B, N] f32: the final totals])."""
+        B, alg = check_decode_llr_args(llr, self.N, algorithm, schedule, max_iter, alpha, beta)
+        if self._llr_tables is None:
+            self.code.require_llr_decoder()
+            lp, lc = self.code.layers()
+            dev = lambda a: torch.from_numpy(np.array(a, np.int32)).to(self.device)       # (a copy: the code's arrays are read-only)
+            self._llr_tables = self._incidence_tables(self.code.nlist, self.M) + (dev(lp), dev(lc), len(lp) - 1)
+        col_ptr, row_ptr, row_edge, row_var, N, M, E, layer_ptr, layer_chk, n_layers = self._llr_tables
+        llr = llr.to(self.device, torch.float32)
+        if B and (llr.stride(1) != 1 or llr.stride(0) < N):
+            llr = llr.contiguous()
+        x = torch.empty((B, N), device=self.device, dtype=torch.uint8)
+        post = torch.empty((B, N), device=self.device, dtype=torch.float32) if want_posteriors else None
+        viol = torch.empty((B,), device=self.device, dtype=torch.int32)
+        iters = torch.empty((B,), device=self.device, dtype=torch.int32)
+        layered = schedule == 'layered'
+        _hip.call('fgnn_ldpc_decode_llr', llr, llr.stride(0) if B else N, col_ptr, row_ptr, row_edge, row_var,
+                  layer_ptr if layered else None, layer_chk if layered else None, n_layers if layered else 0, B, N, M, E, alg,
+                  int(max_iter), float(alpha), float(beta), x, post, viol, iters)
+        return (x, viol, iters, post) if want_posteriors else (x, viol, iters)
 
     def sample(self, B, seed=0, dtype=torch.float32, snr_db=None, burst_prob=0.05, kernel_rng=False, step=0):
         """A batch of B training items (ldpc_dataset.py:222-236): random messages, encoded, sent through the

@@ -14,7 +14,8 @@ original index of position i, ``H`` is the input's ``H[:, perm]`` with ALL M che
 ``G`` [P, K], as for the built-in code.
 
 Limits (``ValueError`` names the one hit): N <= 1024 for the data path (the feature kernels' LDS row), checked on construction;
-N * dv <= 1024 and degrees <= 16 for the sum-product baseline (``require_decoder``); N <= 132 for the model (``require_model``); dv = 3,
+N * dv <= 1024 and degrees <= 16 for the sum-product baseline (``require_decoder``); N <= 1024, M <= 1024 and degrees <= 16 for the
+LLR-domain decoders (``require_llr_decoder``: min-sum, offset min-sum, sum-product; csrc/ldpc_llr.hip); N <= 132 for the model (``require_model``); dv = 3,
 dc = 6 and N <= 96 for the training loop (``require_trainer``).  The operator itself takes a hyper-factor of up to 255 variables; the
 last two limits are narrower than that on purpose: they are the sizes at which the model's forward and backward, and training at any
 batch, have run on the device against the oracle — the trainer's is the shape class whose bf16 calls fall to the kernel families the
@@ -28,6 +29,7 @@ from .tables import _DATA
 
 MAX_VAR = 1024              # csrc/ldpc_datapath.hip, csrc/ldpc_code.hip: the feature kernels' LDS row
 DEC_MAXE, DEC_MAXD = 1024, 16       # csrc/ldpc_decode.hip
+LLR_MAXV, LLR_MAXD = 1024, 16       # csrc/ldpc_llr.hip: variables / checks, edges per variable / check
 MODEL_MAX_VAR = 132         # the model: verified up to here (the message operator's own bound is k <= 255)
 TRAIN_MAX_VAR, TRAIN_DV, TRAIN_DC = 96, 3, 6      # the training loop: the built-in code's shape class
 
@@ -242,6 +244,47 @@ class LdpcCode:
         if deg > DEC_MAXD:
             raise ValueError('degree %d: the sum-product decoder takes at most %d checks per variable / variables per check' % (deg, DEC_MAXD))
         return self
+
+    def require_llr_decoder(self):
+        """The LLR-domain decoders' limits (csrc/ldpc_llr.hip: LLR_MAXV variables and checks, LLR_MAXD per variable / check)."""
+        deg = max(int((self.nlist >= 0).sum(1).max()), self.dc, self.dv)
+        if self.n_var > LLR_MAXV:
+            raise ValueError('N = %d variables: the LLR-domain decoders take at most %d' % (self.n_var, LLR_MAXV))
+        if self.n_chk > LLR_MAXV:
+            raise ValueError('M = %d checks: the LLR-domain decoders take at most %d' % (self.n_chk, LLR_MAXV))
+        if deg > LLR_MAXD:
+            raise ValueError('degree %d: the LLR-domain decoders take at most %d checks per variable / variables per check' % (deg, LLR_MAXD))
+        return self
+
+    def layers(self):
+        """(layer_ptr [n_layers + 1], layer_chk [M]) int32: the checks partitioned into layers for a layered decoding schedule, no
+        two checks of a layer sharing a variable.  Fixed greedy rule: the checks in index order, each into the first layer none of
+        whose checks shares a variable with it (a Gallager code: its dv bands).  Memoised."""
+        memo = self.__dict__.get('_layers')
+        if memo is None:
+            used, members = [], []                      # per layer: the variables taken, the checks
+            rows = [[] for _ in range(self.n_chk)]      # (from nlist: the incidence the decoders' tables are built from)
+            for n, col in enumerate(self.nlist):
+                for m in col[col >= 0]:
+                    rows[int(m)].append(n)
+            for m in range(self.n_chk):
+                vs = np.asarray(rows[m], np.int64)
+                for k in range(len(used)):
+                    if not used[k][vs].any():
+                        break
+                else:
+                    k = len(used)
+                    used.append(np.zeros(self.n_var, bool))
+                    members.append([])
+                used[k][vs] = True
+                members[k].append(m)
+            layer_ptr = np.concatenate([[0], np.cumsum([len(c) for c in members])]).astype(np.int32)
+            layer_chk = np.array([m for c in members for m in c], np.int32)
+            layer_ptr.setflags(write=False)
+            layer_chk.setflags(write=False)
+            memo = (layer_ptr, layer_chk)
+            object.__setattr__(self, '_layers', memo)
+        return memo
 
     def require_model(self):
         """The model's limit (``MODEL_MAX_VAR``)."""

@@ -143,15 +143,71 @@ def load_model(model_path, code=None, aggregator='max', device='cpu'):
     return model.to(device)
 
 
+def parse_decoder(spec):
+    """A classical decoder's spec -> (canonical spec, kind, arguments).  ``'mackay'``: the reference's probability-domain sum-product
+    (``LdpcDataPath.decode``, 100 loops; ``mackay:iters=N`` for another count), kind 'mackay', arguments {'loops'}.  Otherwise
+    ``ALGORITHM[:SCHEDULE][:iters=N][:alpha=A][:beta=B]`` with ALGORITHM 'min-sum', 'offset-min-sum' or 'sum-product' and SCHEDULE
+    'flooding' (the default) or 'layered': kind 'llr', the keyword arguments of ``LdpcDataPath.decode_llr``.  The canonical spec
+    names the schedule and then only what differs from the defaults, in the order iters, alpha, beta; parsing it gives itself."""
+    from .datapath import LLR_ALGORITHMS, LLR_SCHEDULES
+    if not isinstance(spec, str) or not spec:
+        raise ValueError('a decoder spec is a non-empty string, got %r' % (spec,))
+    head, *rest = spec.split(':')
+    opts, schedule = {}, None
+    for part in rest:
+        if part in LLR_SCHEDULES and schedule is None and not opts:
+            schedule = part
+            continue
+        key, eq, val = part.partition('=')
+        if not eq or key not in ('iters', 'alpha', 'beta') or key in opts:
+            raise ValueError('decoder spec %r: cannot read %r (SCHEDULE, iters=N, alpha=A, beta=B)' % (spec, part))
+        try:
+            opts[key] = int(val) if key == 'iters' else float(val)
+        except ValueError:
+            raise ValueError('decoder spec %r: %s=%r is not a number' % (spec, key, val)) from None
+        if not (opts[key] >= (1 if key == 'iters' else 0)) or opts[key] > 3.0e38:
+            raise ValueError('decoder spec %r: %s=%r is out of range' % (spec, key, val))
+    if head == 'mackay':
+        if schedule is not None or set(opts) - {'iters'}:
+            raise ValueError('decoder spec %r: mackay takes iters=N only' % spec)
+        loops = opts.get('iters', 100)
+        return 'mackay' + (':iters=%d' % loops if loops != 100 else ''), 'mackay', {'loops': loops}
+    if head not in LLR_ALGORITHMS:
+        raise ValueError('decoder spec %r: unknown decoder %r (mackay, %s)' % (spec, head, ', '.join(LLR_ALGORITHMS)))
+    if 'alpha' in opts and head != 'min-sum' or 'beta' in opts and head != 'offset-min-sum':
+        raise ValueError('decoder spec %r: alpha belongs to min-sum, beta to offset-min-sum' % spec)
+    kw = {'algorithm': head, 'schedule': schedule or 'flooding', 'max_iter': opts.get('iters', 50), 'alpha': opts.get('alpha', 0.8125),
+          'beta': opts.get('beta', 0.5)}
+    canon = '%s:%s' % (head, kw['schedule'])
+    canon += ':iters=%d' % kw['max_iter'] if kw['max_iter'] != 50 else ''
+    canon += ':alpha=%r' % kw['alpha'] if kw['alpha'] != 0.8125 else ''
+    canon += ':beta=%r' % kw['beta'] if kw['beta'] != 0.5 else ''
+    return canon, 'llr', kw
+
+
+def run_decoder(path, decoder, y, snr0):
+    """Hard decisions, violated checks and iterations of a parsed decoder (``parse_decoder``'s result) on received words y [B, N] at
+    snr0 [B] dB, through ``path`` (an ``LdpcDataPath``)."""
+    _, kind, kw = decoder
+    if kind == 'mackay':
+        return path.decode(path.bit_prior(y, snr0), **kw)
+    return path.decode_llr(path.bit_llr(y, snr0), **kw)
+
+
 def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=False, snr_grid=SNR_GRID, sigma_grid=SIGMA_GRID, code=None):
     """``train_ldpc.py:test()`` for an ``fgnn_amd.LDPCModel`` on a test set (dict or path): the model in eval mode under no_grad
     (bf16: bf16 features under bf16 autocast), ``batch_size`` words per batch, nothing read back to the host until the end.  Returns
     ``LdpcErrorCounts.result()`` of the model's logits; with ``baseline`` also, under 'baseline', that of the sum-product decoder
     (``decode(bit_prior(y, snr), loops=100)``, lib/data/ldpc.py:18-24) on the same received words.  The model's training flag is
-    restored afterwards.  ``code``: the ``LdpcCode`` the model was built for (None: the built-in 96.3.963); the errors are counted
+    restored afterwards.  ``baseline`` may also be a decoder spec (``parse_decoder``: 'mackay', 'min-sum:layered', ...): that decoder's
+    result under 'baseline'; or a list of specs: one result each under ``res['baselines'][spec]``.  ``code``: the ``LdpcCode`` the model was built for (None: the built-in 96.3.963); the errors are counted
     over its K message bits and the baseline runs on its ``nlist``.  ``model`` may also be a checkpoint's path (``load_model``)."""
     if dtype not in (torch.float32, torch.bfloat16):
         raise ValueError('dtype must be float32 or bfloat16')
+    specs = () if baseline is None or isinstance(baseline, bool) else (baseline,) if isinstance(baseline, str) else tuple(baseline)
+    parsed = [(spec, parse_decoder(spec)) for spec in specs]
+    if len(set(specs)) != len(specs):
+        raise ValueError('baseline lists a decoder twice: %s' % (specs,))
     from .ldpc_code import LdpcCode
     code = LdpcCode.builtin() if code is None else code
     if isinstance(model, (str, os.PathLike)):
@@ -164,7 +220,8 @@ def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=Fal
         raise ValueError('batch_size must be >= 1')
     dev = next(model.parameters()).device
     counts = LdpcErrorCounts(dev, snr_grid, sigma_grid)
-    sp = LdpcErrorCounts(dev, snr_grid, sigma_grid) if baseline else None
+    sp = LdpcErrorCounts(dev, snr_grid, sigma_grid) if baseline is True else None
+    decoders = [(spec, decoder, LdpcErrorCounts(dev, snr_grid, sigma_grid)) for spec, decoder in parsed]
     path = LdpcDataPath(dev, code)
     y, gts, snr, sb = load_test_set(test_set, dev, code.n_var)
     n = y.shape[0]
@@ -179,16 +236,63 @@ def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=Fal
                 logits, _ = model(node, hop, path.nn_idx_f2v.unsqueeze(0).expand(B, -1, -1),
                                   path.nn_idx_v2f.unsqueeze(0).expand(B, -1, -1), ef_f2v, ef_v2f)
                 counts.add_logits(logits, gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
-                if baseline:
-                    snr0 = snr[i:j] if snr.dim() == 1 else snr[i:j, 0]
+                snr0 = snr[i:j] if snr.dim() == 1 else snr[i:j, 0]
+                if baseline is True:
                     x = path.decode(path.bit_prior(y[i:j], snr0), loops=100)[0]
                     sp.add_bits(x, gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
+                for _, decoder, acc in decoders:
+                    acc.add_bits(run_decoder(path, decoder, y[i:j], snr0)[0], gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
     finally:
         model.train(was)
     res = counts.result()
-    if baseline:
+    if baseline is True:
         res['baseline'] = sp.result()
+    elif isinstance(baseline, str):
+        res['baseline'] = decoders[0][2].result()
+    elif decoders:
+        res['baselines'] = {spec: acc.result() for spec, _, acc in decoders}
     return res
+
+
+def ber_curve(code, decoder, snr_db, sigma_b=0, batch=4096, min_word_errors=100, max_words=10 ** 6, seed=0, device='cuda:0'):
+    """A BER / WER-versus-SNR curve of one classical decoder (a ``parse_decoder`` spec) on ``code`` (an ``LdpcCode``; None: the
+    built-in one).  Per SNR value, batches of ``batch`` words are drawn with ``LdpcDataPath.sample_rng(batch, seed, step, snr_db=that
+    value)`` on a data path whose ``sigma_b_choices`` is the one level ``sigma_b``, decoded from the drawn ``y`` and counted against
+    the drawn ``cw`` over the K message bits (``LdpcErrorCounts``), until the first batch boundary at which the word errors reach
+    ``min_word_errors`` or the words reach ``max_words``.  The counts are read back once per batch (the stopping rule needs them).
+
+    Reproducible from the arguments: the j-th batch (j = 0, 1, ...) of the i-th SNR value (in the order given) is
+    ``sample_rng(batch, seed=seed, step=i * 2**32 + j)``, so no two batches of a curve share their draws (at most 2**32 batches per
+    point).  Returns a list of dicts, one per SNR value: snr_db, words, bit_errors, word_errors, ber, wer, mean_iters."""
+    from .ldpc_code import LdpcCode
+    code = LdpcCode.builtin() if code is None else code
+    decoder = parse_decoder(decoder)
+    snr_db = [float(v) for v in ([snr_db] if np.isscalar(snr_db) else snr_db)]
+    (_, ), (sigma_b,) = check_grids((0.0,), (sigma_b,))
+    batch, min_word_errors, max_words = int(batch), int(min_word_errors), int(max_words)
+    if not snr_db or any(not np.isfinite(v) for v in snr_db):
+        raise ValueError('snr_db: at least one finite value, got %s' % (snr_db,))
+    if batch < 1 or min_word_errors < 1 or max_words < 1:
+        raise ValueError('batch, min_word_errors and max_words must be >= 1')
+    path = LdpcDataPath(device, code)
+    path.sigma_b_choices = (sigma_b,)
+    out = []
+    for i, snr in enumerate(snr_db):
+        acc = LdpcErrorCounts(path.device, (snr,), (sigma_b,))
+        it_sum = torch.zeros((), dtype=torch.int64, device=path.device)
+        drawn = None
+        for j in range(2 ** 32):
+            drawn = path.sample_rng(batch, seed=seed, step=i * 2 ** 32 + j, snr_db=snr, out=drawn)
+            x, _, iters = run_decoder(path, decoder, drawn.y, drawn.snr_db)[:3]
+            acc.add_bits(x, drawn.cw, drawn.snr_db, drawn.sigma_b, nbits=code.K)
+            it_sum += iters.sum()
+            tot = acc.counts[-1].tolist()
+            if tot[3] >= min_word_errors or tot[2] >= max_words:
+                break
+        bits, bit_errors, words, word_errors = tot
+        out.append({'snr_db': snr, 'words': words, 'bit_errors': bit_errors, 'word_errors': word_errors, 'ber': bit_errors / bits,
+                    'wer': word_errors / words, 'mean_iters': int(it_sum) / words})
+    return out
 
 
 def main(argv=None):
@@ -201,6 +305,14 @@ def main(argv=None):
     ap.add_argument('--aggregator', default='max')
     ap.add_argument('--dtype', choices=('f32', 'bf16'), default='f32')
     ap.add_argument('--baseline', action='store_true', help='also print the sum-product decoder\'s table')
+    ap.add_argument('--decoder', action='append', default=[], metavar='SPEC',
+                    help='also print the table of a classical decoder; may be repeated.  mackay, or min-sum | offset-min-sum | '
+                         'sum-product [:flooding | :layered] [:iters=N] [:alpha=A] [:beta=B]')
+    ap.add_argument('--curve', action='store_true', help='print a BER / WER curve of the one --decoder over --snr (no model)')
+    ap.add_argument('--snr', default='0,1,2,3,4', help='--curve: SNR values in dB, comma-separated')
+    ap.add_argument('--sigma_b', type=int, default=0, help='--curve: the burst level')
+    ap.add_argument('--min_word_errors', type=int, default=100, help='--curve: stop a point at this many word errors ...')
+    ap.add_argument('--max_words', type=int, default=10 ** 6, help='--curve: ... or at this many words')
     ap.add_argument('--make_test_set', metavar='P', help='write a test set to P and print the sum-product table')
     ap.add_argument('--num', type=int, default=1000, help='items per class (--make_test_set)')
     ap.add_argument('--seed', type=int, default=0)
@@ -214,8 +326,18 @@ def main(argv=None):
         sp = LdpcDataPath(dev, code).write_test_set(args.make_test_set, args.num, seed=args.seed, burst_prob=args.burst_prob)
         print(sp)
         return 0
+    if args.curve:
+        if len(args.decoder) != 1:
+            ap.error('--curve takes exactly one --decoder')
+        rows = ber_curve(code, args.decoder[0], [float(v) for v in args.snr.split(',')], args.sigma_b, args.batch_size,
+                         args.min_word_errors, args.max_words, args.seed, dev)
+        print('%8s %10s %12s %12s %12s %12s %10s' % ('snr_db', 'words', 'bit_errors', 'word_errors', 'ber', 'wer', 'mean_iters'))
+        for r in rows:
+            print('%8.3f %10d %12d %12d %12.4e %12.4e %10.3f' % (r['snr_db'], r['words'], r['bit_errors'], r['word_errors'], r['ber'],
+                                                               r['wer'], r['mean_iters']))
+        return 0
     if not args.test_path or not args.model_path:
-        ap.error('give --test_path and --model_path, or --make_test_set')
+        ap.error('give --test_path and --model_path, or --make_test_set, or --curve')
     if code.is_default:
         from .ldpc import LDPCModel
         with contextlib.redirect_stdout(sys.stderr):           # (the model's construction talks; stdout carries the result only)
@@ -226,12 +348,17 @@ def main(argv=None):
         model.to(dev)
     else:
         model = load_model(args.model_path, code, args.aggregator, dev)
+    # one pass over the test set: with --decoder the sum-product table of --baseline is the 'mackay' spec's (the same decoder call)
+    specs = (['mackay'] if args.baseline and 'mackay' not in args.decoder else []) + args.decoder
     res = evaluate(model, args.test_path, args.batch_size, torch.bfloat16 if args.dtype == 'bf16' else torch.float32,
-                   baseline=args.baseline, code=code)
+                   baseline=specs if args.decoder else args.baseline, code=code)
     print(res['ber'])
     print(torch.FloatTensor(res['err_class']))
     if args.baseline:
-        print(torch.FloatTensor(res['baseline']['err_class']))
+        print(torch.FloatTensor((res['baselines']['mackay'] if args.decoder else res['baseline'])['err_class']))
+    for spec in args.decoder:
+        print(spec)
+        print(torch.FloatTensor(res['baselines'][spec]['err_class']))
     return 0
 
 

@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""Classical LDPC decoders, words per second: the f64 probability-domain decoder (LdpcDataPath.decode, 100 loops: csrc/ldpc_decode.hip)
+against the LLR-domain decoders (LdpcDataPath.decode_llr, max_iter 50: csrc/ldpc_llr.hip), every algorithm x schedule.
+
+4096 received words of the all-zero codeword at 2 dB (no burst; one fixed torch seed), for the built-in 96.3.963 and for
+gallager(1024, 4, 8, 2) (which the f64 decoder refuses).  Per decoder: two warm-up calls, one timed call to size the window (at least
+0.2 s of back-to-back calls), then 7 windows between device events; the median window gives the rate.  Also printed: mean iterations
+and the decoded fraction (words that end with no violated check), and the LDS bytes a word occupies.
+
+    python tools/dbench.py [--words 4096] [--snr 2.0] [--repeats 7]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'factor-graph-neural-network_amd'))
+import torch
+from fgnn_amd import _hip
+from fgnn_amd.datapath import LLR_ALGORITHMS, LLR_SCHEDULES, LdpcDataPath
+from fgnn_amd.ldpc_code import LdpcCode
+
+
+def window(run, calls):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(calls):
+        out = run()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) * 1e-3, out
+
+
+def measure(run, repeats):
+    """Seconds per call (median of ``repeats`` windows, lowest, highest) and the last call's result."""
+    for _ in range(2):
+        run()
+    torch.cuda.synchronize()
+    once, _ = window(run, 1)
+    calls = max(1, min(1000, int(0.2 / max(once, 1e-6)) + 1))
+    times = []
+    for _ in range(repeats):
+        t, out = window(run, calls)
+        times.append(t / calls)
+    return statistics.median(times), min(times), max(times), out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--words', type=int, default=4096)
+    ap.add_argument('--snr', type=float, default=2.0)
+    ap.add_argument('--repeats', type=int, default=7)
+    args = ap.parse_args()
+    dev = torch.device('cuda:0')
+    print('%-24s %-28s %12s %10s %10s %9s %9s' % ('code', 'decoder', 'words/s', 'us/call', 'spread %', 'iters', 'decoded'))
+    for name, code in (('builtin 96.3.963', LdpcCode.builtin()), ('gallager(1024,4,8,2)', LdpcCode.gallager(1024, 4, 8, 2))):
+        path = LdpcDataPath(dev, code)
+        gen = torch.Generator(device=dev).manual_seed(0)
+        gcx = 10.0 ** (args.snr / 20.0)
+        y = -gcx + torch.randn((args.words, code.n_var), device=dev, generator=gen)
+        snr = torch.full((args.words,), args.snr, device=dev)
+        llr, bias = path.bit_llr(y, snr), path.bit_prior(y, snr)
+        E = code.n_var * code.dv
+        print('# %s: %s, %d LDS bytes per word for decode_llr' % (name, code, _hip.invoke('fgnn_ldpc_decode_llr_lds_bytes',
+                                                                                          code.n_var, code.n_chk, E)))
+        runs = []
+        try:
+            code.require_decoder()
+            runs.append(('mackay f64 (100 loops)', lambda: path.decode(bias, loops=100)))
+        except ValueError as e:
+            print('%-24s %-28s refused: %s' % (name, 'mackay f64 (100 loops)', e))
+        for alg in LLR_ALGORITHMS:
+            for sched in LLR_SCHEDULES:
+                runs.append(('%s:%s' % (alg, sched), lambda alg=alg, sched=sched: path.decode_llr(llr, alg, sched, max_iter=50)))
+        for label, run in runs:
+            med, lo, hi, (x, viol, iters) = measure(run, args.repeats)
+            print('%-24s %-28s %12.0f %10.1f %10.1f %9.2f %9.4f' % (name, label, args.words / med, med * 1e6, 100 * (hi - lo) / med,
+                                                                   iters.float().mean().item(), (viol == 0).float().mean().item()))
+
+
+if __name__ == '__main__':
+    main()
