@@ -16,12 +16,13 @@ for another regular code (``fgnn_amd.ldpc_code.LdpcCode``), which the reference 
 """
 import argparse
 import contextlib
-import json
 import os
 import sys
 import time
 
 import torch
+
+from . import trainloop
 
 LR = 1e-2                            # train_ldpc.py:160-161
 WEIGHT_DECAY = 1e-8
@@ -126,12 +127,7 @@ def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=Non
         raise ValueError('n_epochs >= 0, batch_size >= 1, steps_per_epoch >= 1 and save_every >= 1 needed')
     if dtype not in (torch.float32, torch.bfloat16):
         raise ValueError('dtype must be float32 or bfloat16')
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise RuntimeError('train runs on a ROCm device (no CPU fallback)')
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
-    from . import graph as graph_mod
+    dev = trainloop.cuda_device(device)
     from .datapath import LdpcDataPath
     from .fastpath import FastAdam
     from .ldpc import decoding_loss_parts
@@ -146,19 +142,12 @@ def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=Non
     model.to(dev).train()
     opt = FastAdam(model.parameters(), lr=lr, weight_decay=WEIGHT_DECAY)
     sched = _scheduler(opt)
-    start_epoch, gcnt = 0, 0
-    if ckpt is not None:
-        opt.load_state_dict(ckpt['optimizer_state_dict'])
-        sched.load_state_dict(ckpt['lr_sche'])
-        start_epoch, gcnt = int(ckpt['epoch']), int(ckpt['gcnt'])
-        graph_mod.state_moved()
+    start_epoch, gcnt = (0, 0) if ckpt is None else trainloop.resume(ckpt, opt, sched)
     path = LdpcDataPath(dev, code)
     static = path.sample_rng(batch_size, seed, step=gcnt, dtype=dtype, snr_db=snr)       # the buffers every step reads
     draw = lambda step: path.sample_rng(batch_size, seed, step=step, dtype=dtype, snr_db=snr, out=static)
 
-    counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    ring_n = int(log_every) if log_every else 256
-    ring = torch.zeros((ring_n, 3), dtype=torch.float32, device=dev)
+    window = trainloop.LogWindow(dev, 3, 2, log_every)       # rows {total, BCE, MSE}; counts {bits, bits decided as the label}
     keep = {}
     amp = torch.autocast('cuda', dtype=torch.bfloat16, enabled=dtype == torch.bfloat16)
 
@@ -166,33 +155,22 @@ def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=Non
         opt.zero_grad()
         with amp:
             logits, pred = model(*static[:6])
-        loss, parts = decoding_loss_parts(logits, pred, static.label, static.sigma_b, MSE_WEIGHT, counts)
+        loss, parts = decoding_loss_parts(logits, pred, static.label, static.sigma_b, MSE_WEIGHT, window.counts)
         loss.backward()
         keep['parts'] = parts
 
     graphed = None
     if graph and start_epoch < n_epochs:
-        try:
-            graphed = graph_mod.StepGraph(compute, modules=[model])
-        except Exception as e:           # noqa: BLE001 — report and fall back to eager launches
-            print('ldpc_train: hipGraph capture failed (%s: %s); running eagerly' % (type(e).__name__, e), file=sys.stderr)
-        finally:                         # replays and eager steps alike start from the counts (and buffers) of graph=False
-            counts.zero_()
-            graph_mod.state_moved()
+        graphed = trainloop.capture_step(compute, [model], window.counts, 'ldpc_train')
 
-    losses, pending = [], 0
     last = {'loss': None, 'sigma_b_loss': None, 'acc': None}
 
     def drain(epoch, bcnt, say):
-        """Read the ring's new rows and the counts back (the one synchronisation of a log window) and start the next window."""
-        nonlocal pending
-        if not pending:
+        """Read the window back (its one synchronisation) and start the next one."""
+        read = window.read()
+        if read is None:
             return
-        got = ring[:pending].tolist()
-        n, right = counts.tolist()
-        counts.zero_()
-        losses.extend(row[0] for row in got)
-        pending = 0
+        got, (n, right) = read
         last.update(loss=sum(row[1] for row in got) / len(got), sigma_b_loss=sum(row[2] for row in got) / len(got),
                     acc=right / n if n else None)
         if say:
@@ -219,12 +197,11 @@ def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=Non
                 graphed.replay()
             else:
                 compute()
-            ring[pending].copy_(keep['parts'])
+            full = window.push(keep['parts'])
             opt.step()
             gcnt += 1
             steps += 1
-            pending += 1
-            if (log_every and gcnt % log_every == 0) or pending == ring_n:      # the script's `if gcnt % 10 == 0` (train_ldpc.py:242)
+            if (log_every and gcnt % log_every == 0) or full:      # the script's `if gcnt % 10 == 0` (train_ldpc.py:242)
                 drain(epoch, bcnt, bool(log_every))
         torch.cuda.synchronize(dev)
         seconds += time.perf_counter() - t0
@@ -232,7 +209,7 @@ def train(n_epochs=10, batch_size=32, snr=None, aggregator='max', model_path=Non
     drain(n_epochs - 1, steps_per_epoch - 1, False)      # the steps behind the last line: a last, shorter window
     if start_epoch < n_epochs:
         save(n_epochs)
-    result = {'model_name': model_name, 'loss': last['loss'], 'sigma_b_loss': last['sigma_b_loss'], 'acc': last['acc'], 'losses': losses,
+    result = {'model_name': model_name, 'loss': last['loss'], 'sigma_b_loss': last['sigma_b_loss'], 'acc': last['acc'], 'losses': window.losses,
               'steps': steps, 'gcnt': gcnt, 'seconds': seconds, 'graphed': graphed is not None, 'checkpoint': saved_to}
     if test_set is not None:
         from .ldpc_eval import evaluate
@@ -264,20 +241,13 @@ def main(argv=None):
     ap.add_argument('--code', default='builtin', help='builtin (96.3.963), the path of an alist file, or gallager:N,dv,dc,seed (dv = 3, dc = 6, N <= 96)')
     ap.add_argument('--json', action='store_true', help='print the result as one JSON line at the end')
     args = ap.parse_args(argv)
-    if args.model_path and not os.path.exists(args.model_path):      # (the script's default is a path that need not exist)
-        args.model_path = None
     from .ldpc_code import LdpcCode
-    r = train(args.n_epochs, args.batch_size, args.snr, args.aggregator, args.model_path, args.model_name, args.steps_per_epoch,
-              torch.bfloat16 if args.dtype == 'bf16' else torch.float32, args.seed, args.out_dir, args.save_every, args.log_every,
-              args.graph, args.test_path, LR, 'cuda:0', LdpcCode.from_spec(args.code))
-    if args.json:
-        out = {k: v for k, v in r.items() if k not in ('losses', 'err_class')}
-        if 'err_class' in r:
-            out['err_class'] = [[float(v) for v in row] for row in r['err_class']]
-        print(json.dumps(out))
-    else:
-        print('training done: {} steps in {:.2f} s, loss = {}, acc = {}, checkpoint {}'.format(
-            r['steps'], r['seconds'], r['loss'], r['acc'], r['checkpoint']))
+    r = train(args.n_epochs, args.batch_size, args.snr, args.aggregator, trainloop.existing_or_none(args.model_path), args.model_name,
+              args.steps_per_epoch, torch.bfloat16 if args.dtype == 'bf16' else torch.float32, args.seed, args.out_dir, args.save_every,
+              args.log_every, args.graph, args.test_path, LR, 'cuda:0', LdpcCode.from_spec(args.code))
+    if 'err_class' in r:                 # (an array: as lists for the JSON line; the last key either way)
+        r['err_class'] = [[float(v) for v in row] for row in r['err_class']]
+    trainloop.report(r, args.json)
     return 0
 
 

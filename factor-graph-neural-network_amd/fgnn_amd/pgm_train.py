@@ -12,7 +12,6 @@ unchanged ``train_syn_*.py --model_path`` resumes from them.
 ``python -m fgnn_amd.pgm_train --family hops --train_epoches 20`` is the command line.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -20,7 +19,7 @@ import warnings
 
 import torch
 
-from . import _hip
+from . import _hip, trainloop
 from .pgm_datapath import FAMILIES
 from .pgm_eval import CAP, EDGE_KEYS, HOP_ORDER, MODEL_NAMES, TRANSITION, _check_family, build_model, run_batch
 
@@ -151,13 +150,8 @@ def train(family, epochs, batch_size=32, steps_per_epoch=None, seed=0, model_nam
     if epochs < 0 or batch_size < 1 or steps_per_epoch < 1:
         raise ValueError('epochs >= 0, batch_size >= 1 and steps_per_epoch >= 1 needed')
     model_name = model_name or MODEL_NAMES[family][0]
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise RuntimeError('train runs on a ROCm device (no CPU fallback)')
-    if dev.index is None:
-        dev = torch.device('cuda', torch.cuda.current_device())
+    dev = trainloop.cuda_device(device)
     from .fastpath import FastAdam
-    from .graph import StepGraph, state_moved
     from .pgm_datapath import PgmDataPath
 
     torch.manual_seed(seed)
@@ -174,53 +168,36 @@ def train(family, epochs, batch_size=32, steps_per_epoch=None, seed=0, model_nam
     params = [p for m in mods for p in m.parameters()]
     opt = FastAdam(params, lr=LR, max_grad_norm=MAX_GRAD_NORM)
     sched = _scheduler(opt)
-    start_epoch, gcnt = 0, 0
-    if ckpt is not None:
-        opt.load_state_dict(ckpt['optimizer_state_dict'])
-        sched.load_state_dict(ckpt['lr_sche'])
-        start_epoch, gcnt = int(ckpt['epoch']), int(ckpt['gcnt'])
-        state_moved()
+    start_epoch, gcnt = (0, 0) if ckpt is None else trainloop.resume(ckpt, opt, sched)
     path = PgmDataPath(dev, CHAIN_LENGTH, HOP_ORDER)
     nfeat = {'raw': 1, 'pws': 2, 'hops': 3}[family]
     draw = lambda step: path.sample(batch_size, family, seed, step=step, cap=CAP, transition=TRANSITION, lp_label=lp_label)
 
-    counts = torch.zeros(3, dtype=torch.int64, device=dev)
-    ring_n = int(log_every) if log_every else 256
-    ring = torch.zeros(ring_n, dtype=torch.float32, device=dev)
+    window = trainloop.LogWindow(dev, 1, 3, log_every)       # rows {loss}; counts {variables, argmax == label, LP label == label}
     keep = {}
 
     def compute(batch):
         feats, label, lp = batch[:nfeat], batch[nfeat], batch[nfeat + 1] if lp_label else None
         opt.zero_grad()
         pred = run_batch(model, edge, family, feats, HOP_ORDER)
-        loss = labelling_loss(pred, label, lp, counts)
+        loss = labelling_loss(pred, label, lp, window.counts)
         loss.backward()
         keep['loss'] = loss.detach()
 
     graphed, static = None, None
     if graph and start_epoch < epochs:
-        try:
-            static = [t.clone() for t in draw(gcnt)]
-            graphed = StepGraph(lambda: compute(static), modules=mods)
-        except Exception as e:           # noqa: BLE001 — report and fall back to eager launches
-            print('pgm_train: hipGraph capture failed (%s: %s); running eagerly' % (type(e).__name__, e), file=sys.stderr)
-        finally:                         # replays and eager steps alike start from the counts (and buffers) of graph=False
-            counts.zero_()
-            state_moved()
+        static = [t.clone() for t in draw(gcnt)]
+        graphed = trainloop.capture_step(lambda: compute(static), mods, window.counts, 'pgm_train')
 
-    losses, pending = [], 0
     last = {'loss': None, 'acc': None, 'lp_acc': None}
 
     def drain(epoch, bcnt, say):
-        """Read the ring's new losses and the counts back (the one synchronisation of a log window)."""
-        nonlocal pending
-        if not pending:
+        """Read the window back (its one synchronisation) and start the next one."""
+        read = window.read()
+        if read is None:
             return
-        got = ring[:pending].tolist()
-        n, right, lp_right = counts.tolist()
-        counts.zero_()
-        losses.extend(got)
-        pending = 0
+        rows, (n, right, lp_right) = read
+        got = [row[0] for row in rows]
         last.update(loss=sum(got) / len(got), acc=right / n if n else None, lp_acc=lp_right / n if n and lp_label else None)
         if say:
             line = 'epoch = {} bcnt = {} loss = {} acc = {}'.format(epoch, bcnt, last['loss'], last['acc'])
@@ -250,12 +227,11 @@ def train(family, epochs, batch_size=32, steps_per_epoch=None, seed=0, model_nam
                 graphed.replay()
             else:
                 compute(batch)
-            ring[pending].copy_(keep['loss'])
+            full = window.push(keep['loss'])
             opt.step()
             gcnt += 1
             steps += 1
-            pending += 1
-            if pending == ring_n:
+            if full:
                 drain(epoch, bcnt, bool(log_every))
         drain(epoch, steps_per_epoch - 1, False)
         torch.cuda.synchronize(dev)
@@ -263,7 +239,7 @@ def train(family, epochs, batch_size=32, steps_per_epoch=None, seed=0, model_nam
     if start_epoch < epochs:
         save(epochs)
     return {'family': family, 'model_name': model_name, 'loss': last['loss'], 'acc': last['acc'], 'lp_acc': last['lp_acc'],
-            'losses': losses, 'steps': steps, 'gcnt': gcnt, 'seconds': seconds, 'graphed': graphed is not None,
+            'losses': window.losses, 'steps': steps, 'gcnt': gcnt, 'seconds': seconds, 'graphed': graphed is not None,
             'checkpoint': saved_to}
 
 
@@ -284,15 +260,9 @@ def main(argv=None):
     ap.add_argument('--log_every', type=int, default=10)
     ap.add_argument('--json', action='store_true', help='print the result as one JSON line at the end')
     args = ap.parse_args(argv)
-    if args.model_path and not os.path.exists(args.model_path):      # (the scripts' default is a path that need not exist)
-        args.model_path = None
-    r = train(args.family, args.train_epoches, args.batch_size, args.steps_per_epoch, args.seed, args.model_name, args.model_path,
-              args.out_dir, args.lp_label, args.graph, args.log_every, 'cuda:0')
-    if args.json:
-        print(json.dumps({k: v for k, v in r.items() if k != 'losses'}))
-    else:
-        print('training done: {} steps in {:.2f} s, loss = {}, acc = {}, checkpoint {}'.format(
-            r['steps'], r['seconds'], r['loss'], r['acc'], r['checkpoint']))
+    r = train(args.family, args.train_epoches, args.batch_size, args.steps_per_epoch, args.seed, args.model_name,
+              trainloop.existing_or_none(args.model_path), args.out_dir, args.lp_label, args.graph, args.log_every, 'cuda:0')
+    trainloop.report(r, args.json)
     return 0
 
 
