@@ -1,0 +1,456 @@
+// ldpc_nms.hip — the learned ("neural") min-sum LDPC decoder: a flooding min-sum whose normalisation weights alpha and offsets beta
+// are parameters per iteration, per (iteration, check) or per (iteration, edge), with the backward that trains them.  The reference has
+// no counterpart; the steps are stated in include/fgnn_hip_ldpc_nms.h and restated in tests/ldpc_nms_oracle.py.
+//
+//   fgnn_ldpc_nms_forward                     one launch: decode mode (early stop) or train mode (every iteration's totals + the record)
+//   fgnn_ldpc_nms_backward                    g_alpha, g_beta (batch sums, no floating-point atomics) and g_llr: two launches
+//   fgnn_ldpc_nms_record_bytes, fgnn_ldpc_nms_backward_workspace_bytes, fgnn_ldpc_nms_lds_bytes, fgnn_ldpc_nms_backward_workgroups
+//
+// Built with -ffp-contract=off: the decode mode with constant weights is fgnn_ldpc_decode_llr's flooding min-sum bit for bit, and the
+// backward recomputes u = alpha * mag - beta with the forward's own rounding.
+//
+// Forward layout (ldpc_llr.hip's): one workgroup per word; 64 threads for max(N, M) <= 256, 128 for <= 512, 256 above.  Per word in LDS
+// for the whole run: f32 R [E], T [N], prior [N]; the row table packed as edge | var << 16 [E]; 4 ints (violated checks per wave);
+// 16-bit row_ptr [M + 1], col_ptr [N + 1].  The weights are read from global memory where they are used (one value per check update
+// with share 0 / 1, one per edge with share 2).
+//
+// Record (train mode), per word b and iteration t three planes of M 32-bit values, plane k of check m at
+// ((b * n_iter + t - 1) * 3 + k) * M + m (a lane owns a check: the planes are read and written coalesced):
+//   plane 0  m1 (f32 bits)     plane 1  m2 (f32 bits)
+//   plane 2  bits 0..15 the signs of q_0 .. q_{L-1} (1 = q < 0), bits 16..20 i1, bits 21..25 i2 (31 = none)
+// 12 B M n_iter per word.  mag, the other-sign parity and u > 0 follow from these and the weights.
+//
+// Backward layout: workgroup g of G = min(B, 512) takes the words g, g + G, ...; the same thread counts.  In LDS: f32 gT [N] (this
+// iteration's total gradients), gP [N] (g_prior), gQ [E] (the g_q of the iteration above, by edge: variable n's edges are
+// contiguous, so what an iteration sends back to T[n] is a gather in edge order, not a scatter), the packed row table [E], 8 floats of
+// wave sums, 16-bit row_ptr and col_ptr; and the workgroup's partial of g_alpha / g_beta [2][n_iter W] where the whole stays within
+// 64 KiB (two workgroups per CU and more), else in the workgroup's own slice of the workspace.  Every partial element has one owner
+// thread (share 1: the check's lane; share 2: the edge's check's lane; share 0: thread 0, after a fixed-order wave and workgroup
+// reduction), which adds to it word after word in the order of its words: no atomics, the same bits every time.  The second launch adds
+// the G slices in a fixed order (ldpc_nms_sum_kernel).
+#include "fgnn_common.h"
+#include "fgnn_hip_ldpc_nms.h"
+#include <atomic>
+#include <math.h>
+#include <stdint.h>
+
+#define NMS_MAXV 1024       // variables, checks
+#define NMS_MAXD 16         // edges per variable / per check
+#define NMS_MAXIT 64
+#define NMS_CLAMP 4096.0f
+#define NMS_BWD_GROUPS 512
+#define NMS_PARTIAL_LDS (64 * 1024)     // the backward keeps its partial in LDS while state + partial stay within this
+#define NMS_NONE 31u
+#define NMS_MAX_DEVICES 64
+
+extern __shared__ __attribute__((aligned(16))) unsigned char nms_lds[];
+
+struct NmsFwdParams {
+    const float* llr; int64_t llr_sb;
+    const int32_t *col_ptr, *row_ptr, *row_edge, *row_var;
+    const float *alpha, *beta;
+    uint8_t* x;
+    float *post, *totals;
+    int32_t *viol, *iters;
+    uint32_t* record;
+    int64_t B;
+    int N, M, E, n_iter, share;
+};
+
+struct NmsBwdParams {
+    const float *g_totals, *llr; int64_t llr_sb;
+    const int32_t *col_ptr, *row_ptr, *row_edge, *row_var;
+    const float *alpha, *beta;
+    const uint32_t* record;
+    float *g_llr, *ws;
+    int64_t B;
+    int N, M, E, n_iter, share, W;
+};
+
+static bool nms_shape_ok(int N, int M, int E) {
+    return N >= 1 && N <= NMS_MAXV && M >= 1 && M <= NMS_MAXV && E >= 1 && E <= (int64_t)NMS_MAXD * N && E <= (int64_t)NMS_MAXD * M;
+}
+
+__host__ __device__ static inline int64_t nms_u16_bytes(int N, int M) { return (2 * ((int64_t)(M + 1) + (N + 1)) + 15) / 16 * 16; }
+
+// forward: R, rtab [E]; T, prior [N]; 4 ints; the 16-bit tables.  backward: gQ, rtab [E]; gT, gP [N]; 8 floats; the 16-bit tables.
+__host__ __device__ static inline int64_t nms_state_bytes(int N, int M, int E, int backward) {
+    return (4 * (2 * (int64_t)E + 2 * (int64_t)N) + (backward ? 32 : 16) + 15) / 16 * 16 + nms_u16_bytes(N, M);
+}
+
+static int nms_threads(int N, int M) {
+    const int big = N > M ? N : M;
+    return big <= 256 ? 64 : big <= 512 ? 128 : 256;
+}
+
+__device__ __forceinline__ float nms_weight(const float* w, int it, int W, int share, int m, int e) {
+    return w[(int64_t)(it - 1) * W + (share == 0 ? 0 : share == 1 ? m : e)];
+}
+
+template <bool TRAIN>
+__global__ __launch_bounds__(256) void ldpc_nms_fwd_kernel(const NmsFwdParams p) {
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+    const int N = p.N, M = p.M, E = p.E, share = p.share;
+    const int W = share == 0 ? 1 : share == 1 ? M : E;
+    const int64_t b = blockIdx.x;
+    float* R = (float*)nms_lds;
+    float* T = R + E;
+    float* prior = T + N;
+    uint32_t* rtab = (uint32_t*)(prior + N);
+    int* wsum = (int*)(rtab + E);
+    uint16_t* rp = (uint16_t*)(wsum + 4);
+    uint16_t* cp = rp + (M + 1);
+
+    for (int e = tid; e < E; e += nt) {
+        rtab[e] = ((uint32_t)p.row_edge[e] & 0xffffu) | ((uint32_t)p.row_var[e] << 16);
+        R[e] = 0.0f;
+    }
+    for (int m = tid; m <= M; m += nt) rp[m] = (uint16_t)p.row_ptr[m];
+    for (int n = tid; n <= N; n += nt) cp[n] = (uint16_t)p.col_ptr[n];
+    {
+        const float* in = p.llr + b * p.llr_sb;
+        for (int n = tid; n < N; n += nt) {
+            float v = in[n];
+            if (v != v) v = 0.0f;
+            v = fminf(fmaxf(v, -NMS_CLAMP), NMS_CLAMP);
+            prior[n] = v;
+            T[n] = v;
+        }
+    }
+    __syncthreads();
+
+    int it = 0, viol = 0;
+    for (;;) {
+        ++it;
+        for (int m = tid; m < M; m += nt) {
+            const int r0 = rp[m], r1 = rp[m + 1], L = r1 - r0;
+            float m1 = INFINITY, m2 = INFINITY;
+            int i1 = -1, i2 = -1;
+            uint32_t signs = 0;
+            bool par = false;
+            for (int r = r0; r < r1; ++r) {
+                const uint32_t ev = rtab[r];
+                const float q = T[ev >> 16] - R[ev & 0xffffu];
+                const float a = fabsf(q);
+                const bool neg = q < 0.0f;
+                par ^= neg;
+                signs |= (uint32_t)neg << (r - r0);
+                if (a < m1) { m2 = m1; i2 = i1; m1 = a; i1 = r; }
+                else if (a < m2) { m2 = a; i2 = r; }
+            }
+            if (TRAIN) {
+                uint32_t* rec = p.record + ((b * p.n_iter + (it - 1)) * 3) * M + m;
+                rec[0] = __float_as_uint(m1);
+                rec[M] = __float_as_uint(m2);
+                rec[2 * (int64_t)M] = signs | (i1 < 0 ? NMS_NONE : (uint32_t)(i1 - r0)) << 16 | (i2 < 0 ? NMS_NONE : (uint32_t)(i2 - r0)) << 21;
+            }
+            float al = 0.0f, be = 0.0f;
+            if (share != 2) { al = nms_weight(p.alpha, it, W, share, m, 0); be = nms_weight(p.beta, it, W, share, m, 0); }
+            for (int r = r0; r < r1; ++r) {
+                const int e = rtab[r] & 0xffffu;
+                if (share == 2) { al = nms_weight(p.alpha, it, W, 2, m, e); be = nms_weight(p.beta, it, W, 2, m, e); }
+                const float mag = r == i1 ? m2 : m1;
+                const float u = al * mag - be;
+                float o = fmaxf(u, 0.0f);
+                if (par != (bool)((signs >> (r - r0)) & 1u)) o = -o;
+                if (L == 1) o = 0.0f;
+                R[e] = o;
+            }
+        }
+        __syncthreads();
+        for (int n = tid; n < N; n += nt) {
+            float sum = prior[n];
+            const int e1 = cp[n + 1];
+            for (int e = cp[n]; e < e1; ++e) sum = sum + R[e];
+            T[n] = sum;
+            if (TRAIN) p.totals[((int64_t)(it - 1) * p.B + b) * N + n] = sum;
+        }
+        __syncthreads();
+        int cnt = 0;                                                            // checks of odd parity: per wave, then over the waves
+        for (int m0 = wave * 64; m0 < M; m0 += nt) {
+            const int m = m0 + lane;
+            bool odd = false;
+            if (m < M) {
+                const int r1 = rp[m + 1];
+                for (int r = rp[m]; r < r1; ++r) odd ^= T[rtab[r] >> 16] < 0.0f;
+            }
+            cnt += __popcll(__ballot(odd));
+        }
+        if (lane == 0) wsum[wave] = cnt;
+        __syncthreads();                // (the next write of wsum comes after a later barrier: every wave has read it by then)
+        viol = 0;
+        for (int w = 0; w < nw; ++w) viol += wsum[w];
+        if ((!TRAIN && viol == 0) || it >= p.n_iter) break;
+    }
+
+    for (int n = tid; n < N; n += nt) {
+        const float v = T[n];
+        if (p.x) p.x[b * N + n] = v < 0.0f ? 1 : 0;
+        if (p.post) p.post[b * N + n] = v;
+    }
+    if (tid == 0) {
+        if (p.viol) p.viol[b] = viol;
+        if (p.iters) p.iters[b] = it;
+    }
+}
+
+// PART_LDS: the workgroup's partial [2][n_iter W] lies in LDS behind the state (and is copied to its workspace slice at the end);
+// otherwise it is the slice itself.
+template <bool PART_LDS>
+__global__ __launch_bounds__(256) void ldpc_nms_bwd_kernel(const NmsBwdParams p) {
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+    const int N = p.N, M = p.M, E = p.E, share = p.share, W = p.W, n_iter = p.n_iter;
+    const int cnt = n_iter * W;
+    float* gQ = (float*)nms_lds;
+    float* gT = gQ + E;
+    float* gP = gT + N;
+    uint32_t* rtab = (uint32_t*)(gP + N);
+    float* red = (float*)(rtab + E);
+    uint16_t* rp = (uint16_t*)(red + 8);
+    uint16_t* cp = rp + (M + 1);
+    float* slice = p.ws + (int64_t)blockIdx.x * 2 * cnt;
+    float* part = PART_LDS ? (float*)(nms_lds + nms_state_bytes(N, M, E, 1)) : slice;
+
+    for (int e = tid; e < E; e += nt) rtab[e] = ((uint32_t)p.row_edge[e] & 0xffffu) | ((uint32_t)p.row_var[e] << 16);
+    for (int m = tid; m <= M; m += nt) rp[m] = (uint16_t)p.row_ptr[m];
+    for (int n = tid; n <= N; n += nt) cp[n] = (uint16_t)p.col_ptr[n];
+    for (int i = tid; i < 2 * cnt; i += nt) part[i] = 0.0f;
+    __syncthreads();
+
+    for (int64_t b = blockIdx.x; b < p.B; b += gridDim.x) {
+        for (int e = tid; e < E; e += nt) gQ[e] = 0.0f;
+        for (int n = tid; n < N; n += nt) gP[n] = 0.0f;
+        __syncthreads();
+        for (int t = n_iter; t >= 1; --t) {
+            for (int n = tid; n < N; n += nt) {                                 // gT_t = g_totals[t] + what iteration t + 1 sent back
+                float back = 0.0f;
+                const int e1 = cp[n + 1];
+                for (int e = cp[n]; e < e1; ++e) back += gQ[e];
+                const float g = p.g_totals[((int64_t)(t - 1) * p.B + b) * N + n] + back;
+                gT[n] = g;
+                gP[n] += g;
+            }
+            __syncthreads();
+            float sa = 0.0f, sb = 0.0f;                                         // share 0: this thread's part of the iteration's sums
+            for (int m = tid; m < M; m += nt) {
+                const int r0 = rp[m], L = rp[m + 1] - r0;
+                const uint32_t* rec = p.record + ((b * n_iter + (t - 1)) * 3) * M + m;
+                const float m1 = __uint_as_float(rec[0]), m2 = __uint_as_float(rec[M]);
+                const uint32_t pk = rec[2 * (int64_t)M];
+                const uint32_t signs = pk & 0xffffu;
+                const int i1 = (pk >> 16) & 31u, i2 = (pk >> 21) & 31u;
+                const bool par = __popc(signs) & 1;
+                float al = 0.0f, be = 0.0f;
+                if (share != 2) { al = nms_weight(p.alpha, t, W, share, m, 0); be = nms_weight(p.beta, t, W, share, m, 0); }
+                float ca = 0.0f, cb = 0.0f, gm1 = 0.0f, gm2 = 0.0f;
+                if (L > 1)
+                    for (int l = 0; l < L; ++l) {
+                        const uint32_t ev = rtab[r0 + l];
+                        const int e = ev & 0xffffu;
+                        if (share == 2) { al = nms_weight(p.alpha, t, W, 2, m, e); be = nms_weight(p.beta, t, W, 2, m, e); }
+                        const float mag = l == i1 ? m2 : m1;
+                        const float u = al * mag - be;
+                        float go = gT[ev >> 16] - gQ[e];                        // g_e: gR_t[e] = -g_q_e of iteration t + 1
+                        if (par != (bool)((signs >> l) & 1u)) go = -go;
+                        if (!(u > 0.0f)) go = 0.0f;
+                        const float ga = go * mag;
+                        if (share == 2) {
+                            float* pa = part + (int64_t)(t - 1) * W + e;
+                            pa[0] += ga;
+                            pa[cnt] -= go;
+                        } else {
+                            ca += ga;
+                            cb -= go;
+                        }
+                        const float gmag = go * al;
+                        if (l == i1) gm2 = gmag; else gm1 += gmag;
+                    }
+                for (int l = 0; l < L; ++l) {                                   // g_q: places i1 and i2 only
+                    float gq = l == i1 ? gm1 : l == i2 ? gm2 : 0.0f;
+                    if ((signs >> l) & 1u) gq = -gq;
+                    gQ[rtab[r0 + l] & 0xffffu] = gq;
+                }
+                if (share == 1) {
+                    float* pa = part + (int64_t)(t - 1) * W + m;
+                    pa[0] += ca;
+                    pa[cnt] += cb;
+                } else {
+                    sa += ca;
+                    sb += cb;
+                }
+            }
+            if (share == 0) {                                                   // lanes in a fixed order, then the waves in order
+                for (int off = 32; off >= 1; off >>= 1) {
+                    sa += __shfl_down(sa, off);
+                    sb += __shfl_down(sb, off);
+                }
+                if (lane == 0) { red[2 * wave] = sa; red[2 * wave + 1] = sb; }
+            }
+            __syncthreads();
+            if (share == 0 && tid == 0) {       // (red is written again only behind the next iteration's first barrier)
+                float a = red[0], c = red[1];
+                for (int w = 1; w < nw; ++w) { a += red[2 * w]; c += red[2 * w + 1]; }
+                part[t - 1] += a;
+                part[cnt + t - 1] += c;
+            }
+        }
+        for (int n = tid; n < N; n += nt) {                                     // t = 0: T_0 = prior
+            float g = gP[n];
+            const int e1 = cp[n + 1];
+            for (int e = cp[n]; e < e1; ++e) g += gQ[e];
+            if (p.g_llr) {
+                const float v = p.llr[b * p.llr_sb + n];
+                p.g_llr[b * N + n] = (v >= -NMS_CLAMP && v <= NMS_CLAMP) ? g : 0.0f;
+            }
+        }
+        __syncthreads();
+    }
+    if (PART_LDS)
+        for (int i = tid; i < 2 * cnt; i += nt) slice[i] = part[i];
+}
+
+// out[i] = the sum over the slices g of ws[g][i], i over [2][cnt] (g_alpha then g_beta), in a fixed order: lane group k of 8 adds the
+// slices g = k, k + 8, ... in that order, then one thread adds the 8 sums in the order k = 0 .. 7.  32 outputs per workgroup: a group
+// reads 128 contiguous bytes of a slice.
+__global__ __launch_bounds__(256) void ldpc_nms_sum_kernel(const float* ws, int G, int cnt, float* g_alpha, float* g_beta) {
+    __shared__ float sh[8][32];
+    const int ii = threadIdx.x & 31, k = threadIdx.x >> 5;
+    const int i = blockIdx.x * 32 + ii;
+    float s = 0.0f;
+    if (i < 2 * cnt)
+        for (int g = k; g < G; g += 8) s += ws[(int64_t)g * 2 * cnt + i];
+    sh[k][ii] = s;
+    __syncthreads();
+    if (k != 0 || i >= 2 * cnt) return;
+    for (int j = 1; j < 8; ++j) s += sh[j][ii];
+    if (i < cnt) g_alpha[i] = s; else g_beta[i - cnt] = s;
+}
+
+static int nms_check_sizes(const char* who, int64_t B, int N, int M, int E, int n_iter, int share) {
+    if (N < 1 || N > NMS_MAXV) FGNN_FAIL(FGNN_EUNSUPPORTED, "%s: N=%d variables outside 1..%d", who, N, NMS_MAXV);
+    if (M < 1 || M > NMS_MAXV) FGNN_FAIL(FGNN_EUNSUPPORTED, "%s: M=%d checks outside 1..%d", who, M, NMS_MAXV);
+    if (!nms_shape_ok(N, M, E))
+        FGNN_FAIL(FGNN_EUNSUPPORTED, "%s: E=%d edges outside 1..%d for N=%d, M=%d (degrees are at most %d)", who, E,
+                  NMS_MAXD * (N < M ? N : M), N, M, NMS_MAXD);
+    if (B < 0 || B > 0x7fffffffll) FGNN_FAIL(FGNN_EINVAL, "%s: batch %lld outside 0 .. 2^31-1", who, (long long)B);
+    if (n_iter < 1 || n_iter > NMS_MAXIT) FGNN_FAIL(FGNN_EINVAL, "%s: n_iter=%d outside 1..%d", who, n_iter, NMS_MAXIT);
+    if (share < 0 || share > 2) FGNN_FAIL(FGNN_EINVAL, "%s: share=%d outside 0..2", who, share);
+    return FGNN_OK;
+}
+
+extern "C" int64_t fgnn_ldpc_nms_lds_bytes(int N, int M, int E, int backward) {
+    if (nms_check_sizes("ldpc_nms_lds_bytes", 0, N, M, E, 1, 0) != FGNN_OK) return -1;
+    return nms_state_bytes(N, M, E, backward != 0);
+}
+
+extern "C" int64_t fgnn_ldpc_nms_record_bytes(int64_t B, int N, int M, int E, int n_iter) {
+    if (nms_check_sizes("ldpc_nms_record_bytes", B, N, M, E, n_iter, 0) != FGNN_OK) return -1;
+    return B * n_iter * 3 * (int64_t)M * 4;
+}
+
+extern "C" int64_t fgnn_ldpc_nms_backward_workgroups(int64_t B) { return B < 0 ? 0 : B < NMS_BWD_GROUPS ? B : NMS_BWD_GROUPS; }
+
+extern "C" int64_t fgnn_ldpc_nms_backward_workspace_bytes(int64_t B, int N, int M, int E, int n_iter, int share) {
+    if (nms_check_sizes("ldpc_nms_backward_workspace_bytes", B, N, M, E, n_iter, share) != FGNN_OK) return -1;
+    const int64_t W = share == 0 ? 1 : share == 1 ? M : E;
+    return fgnn_ldpc_nms_backward_workgroups(B) * 2 * n_iter * W * 4;
+}
+
+// Above 48 KiB a kernel needs its dynamic-LDS limit raised once per device; the largest value set so far is remembered per
+// (device, kernel), so that a step replayed or captured after its warm-up makes no such call.
+static int nms_set_lds(const void* kernel, int slot, int lds) {
+    static std::atomic<int> set_to[NMS_MAX_DEVICES][4];
+    if (lds <= 48 * 1024) return FGNN_OK;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= NMS_MAX_DEVICES) dev = -1;
+    if (dev >= 0 && set_to[dev][slot].load() >= lds) return FGNN_OK;
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
+    if (dev >= 0) set_to[dev][slot].store(lds);
+    return FGNN_OK;
+}
+
+extern "C" int fgnn_ldpc_nms_forward(const float* llr, int64_t llr_sb, const int32_t* col_ptr, const int32_t* row_ptr,
+                                     const int32_t* row_edge, const int32_t* row_var, const float* alpha, const float* beta, int64_t B,
+                                     int N, int M, int E, int n_iter, int share, int stop_early, uint8_t* x, float* post, int32_t* viol,
+                                     int32_t* iters, float* totals, void* record, int64_t record_bytes, fgnn_stream_t stream) {
+    const int rc = nms_check_sizes("ldpc_nms_forward", B, N, M, E, n_iter, share);
+    if (rc != FGNN_OK) return rc;
+    if (stop_early < 0 || stop_early > 1) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: stop_early=%d outside 0..1", stop_early);
+    if (llr_sb < 0) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: negative row stride");
+    if (stop_early && (totals || record)) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: totals and record belong to the train mode (stop_early = 0)");
+    if (B == 0) return FGNN_OK;
+    if (!llr || !col_ptr || !row_ptr || !row_edge || !row_var || !alpha || !beta) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: null input pointer");
+    if (stop_early && (!x || !viol || !iters)) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: null output pointer");
+    if (!stop_early) {
+        if (!totals || !record) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: null totals or record in train mode");
+        const int64_t need = fgnn_ldpc_nms_record_bytes(B, N, M, E, n_iter);
+        if (record_bytes < need)
+            FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: a record of %lld bytes, %lld needed", (long long)record_bytes, (long long)need);
+    }
+    NmsFwdParams p = {};
+    p.llr = llr; p.llr_sb = llr_sb;
+    p.col_ptr = col_ptr; p.row_ptr = row_ptr; p.row_edge = row_edge; p.row_var = row_var;
+    p.alpha = alpha; p.beta = beta;
+    p.x = x; p.post = post; p.totals = totals; p.viol = viol; p.iters = iters; p.record = (uint32_t*)record;
+    p.B = B; p.N = N; p.M = M; p.E = E; p.n_iter = n_iter; p.share = share;
+    void (*kernel)(const NmsFwdParams) = stop_early ? ldpc_nms_fwd_kernel<false> : ldpc_nms_fwd_kernel<true>;
+    const int threads = nms_threads(N, M), lds = (int)nms_state_bytes(N, M, E, 0);
+    if (nms_set_lds((const void*)kernel, stop_early ? 0 : 1, lds) != FGNN_OK) return FGNN_ELAUNCH;
+    fgnn_note_kernel("ldpc_nms_fwd_kernel<%d>x%d", !stop_early, threads);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, (hipStream_t)stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_nms_forward launch: %s", hipGetErrorString(e));
+    return FGNN_OK;
+}
+
+extern "C" int fgnn_ldpc_nms_backward(const float* g_totals, const float* llr, int64_t llr_sb, const int32_t* col_ptr,
+                                      const int32_t* row_ptr, const int32_t* row_edge, const int32_t* row_var, const float* alpha,
+                                      const float* beta, const void* record, int64_t record_bytes, int64_t B, int N, int M, int E,
+                                      int n_iter, int share, float* g_alpha, float* g_beta, float* g_llr, void* workspace,
+                                      int64_t workspace_bytes, fgnn_stream_t stream) {
+    const int rc = nms_check_sizes("ldpc_nms_backward", B, N, M, E, n_iter, share);
+    if (rc != FGNN_OK) return rc;
+    if (llr_sb < 0) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: negative row stride");
+    const int W = share == 0 ? 1 : share == 1 ? M : E;
+    const int cnt = n_iter * W;
+    if (B == 0) {
+        if (g_alpha && g_beta) {
+            hipError_t e = hipMemsetAsync(g_alpha, 0, 4 * (size_t)cnt, (hipStream_t)stream);
+            if (e == hipSuccess) e = hipMemsetAsync(g_beta, 0, 4 * (size_t)cnt, (hipStream_t)stream);
+            if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_nms_backward: hipMemsetAsync: %s", hipGetErrorString(e));
+        }
+        return FGNN_OK;
+    }
+    if (!g_totals || !col_ptr || !row_ptr || !row_edge || !row_var || !alpha || !beta || !record)
+        FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: null input pointer");
+    if (!g_alpha || !g_beta || !workspace) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: null output or workspace pointer");
+    if (g_llr && !llr) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: g_llr needs llr (the load's clamp)");
+    const int64_t need_rec = fgnn_ldpc_nms_record_bytes(B, N, M, E, n_iter);
+    if (record_bytes < need_rec)
+        FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: a record of %lld bytes, %lld needed", (long long)record_bytes, (long long)need_rec);
+    const int64_t need_ws = fgnn_ldpc_nms_backward_workspace_bytes(B, N, M, E, n_iter, share);
+    if (workspace_bytes < need_ws)
+        FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: a workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need_ws);
+    NmsBwdParams p = {};
+    p.g_totals = g_totals; p.llr = llr; p.llr_sb = llr_sb;
+    p.col_ptr = col_ptr; p.row_ptr = row_ptr; p.row_edge = row_edge; p.row_var = row_var;
+    p.alpha = alpha; p.beta = beta; p.record = (const uint32_t*)record;
+    p.g_llr = g_llr; p.ws = (float*)workspace;
+    p.B = B; p.N = N; p.M = M; p.E = E; p.n_iter = n_iter; p.share = share; p.W = W;
+    const int G = (int)fgnn_ldpc_nms_backward_workgroups(B);
+    const int64_t state = nms_state_bytes(N, M, E, 1);
+    const bool part_lds = state + 8 * (int64_t)cnt <= NMS_PARTIAL_LDS;
+    void (*kernel)(const NmsBwdParams) = part_lds ? ldpc_nms_bwd_kernel<true> : ldpc_nms_bwd_kernel<false>;
+    const int threads = nms_threads(N, M), lds = (int)(state + (part_lds ? 8 * (int64_t)cnt : 0));
+    if (nms_set_lds((const void*)kernel, part_lds ? 2 : 3, lds) != FGNN_OK) return FGNN_ELAUNCH;
+    fgnn_note_kernel("ldpc_nms_bwd_kernel<%d>x%d", part_lds, threads);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)G), dim3(threads), lds, (hipStream_t)stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_nms_backward launch: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(ldpc_nms_sum_kernel, dim3((unsigned)((2 * cnt + 31) / 32)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)workspace, G, cnt, g_alpha, g_beta);
+    e = hipGetLastError();
+    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_nms_backward sum launch: %s", hipGetErrorString(e));
+    return FGNN_OK;
+}

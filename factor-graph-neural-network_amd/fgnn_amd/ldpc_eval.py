@@ -148,10 +148,19 @@ def parse_decoder(spec):
     (``LdpcDataPath.decode``, 100 loops; ``mackay:iters=N`` for another count), kind 'mackay', arguments {'loops'}.  Otherwise
     ``ALGORITHM[:SCHEDULE][:iters=N][:alpha=A][:beta=B]`` with ALGORITHM 'min-sum', 'offset-min-sum' or 'sum-product' and SCHEDULE
     'flooding' (the default) or 'layered': kind 'llr', the keyword arguments of ``LdpcDataPath.decode_llr``.  The canonical spec
-    names the schedule and then only what differs from the defaults, in the order iters, alpha, beta; parsing it gives itself."""
+    names the schedule and then only what differs from the defaults, in the order iters, alpha, beta; parsing it gives itself.
+    ``learned-min-sum:CHECKPOINT``: the trained min-sum decoder of an ``ldpc_nms_train`` checkpoint (``ldpc_nms.LearnedMinSum``), kind
+    'learned', arguments {'path'}; everything behind the first colon is the path (it may hold colons), and the spec is canonical as
+    it stands."""
     from .datapath import LLR_ALGORITHMS, LLR_SCHEDULES
+    from .ldpc_nms import KIND as LEARNED
     if not isinstance(spec, str) or not spec:
         raise ValueError('a decoder spec is a non-empty string, got %r' % (spec,))
+    if spec == LEARNED or spec.startswith(LEARNED + ':'):
+        ckpt = spec[len(LEARNED) + 1:]
+        if not ckpt:
+            raise ValueError('decoder spec %r: %s:CHECKPOINT needs the path of a checkpoint' % (spec, LEARNED))
+        return spec, 'learned', {'path': ckpt}
     head, *rest = spec.split(':')
     opts, schedule = {}, None
     for part in rest:
@@ -187,10 +196,17 @@ def parse_decoder(spec):
 
 def run_decoder(path, decoder, y, snr0):
     """Hard decisions, violated checks and iterations of a parsed decoder (``parse_decoder``'s result) on received words y [B, N] at
-    snr0 [B] dB, through ``path`` (an ``LdpcDataPath``)."""
+    snr0 [B] dB, through ``path`` (an ``LdpcDataPath``).  A learned decoder's checkpoint is loaded on the first call and kept on
+    ``path`` (once per checkpoint path); one trained for another code than ``path.code`` is refused (``LdpcCode.check_checkpoint``)."""
     _, kind, kw = decoder
     if kind == 'mackay':
         return path.decode(path.bit_prior(y, snr0), **kw)
+    if kind == 'learned':
+        loaded = path.__dict__.setdefault('_learned', {})
+        if kw['path'] not in loaded:
+            from .ldpc_nms import load_checkpoint
+            loaded[kw['path']] = load_checkpoint(kw['path'], path.code, path.device)
+        return loaded[kw['path']].decode(path.bit_llr(y, snr0))
     return path.decode_llr(path.bit_llr(y, snr0), **kw)
 
 
@@ -307,7 +323,8 @@ def main(argv=None):
     ap.add_argument('--baseline', action='store_true', help='also print the sum-product decoder\'s table')
     ap.add_argument('--decoder', action='append', default=[], metavar='SPEC',
                     help='also print the table of a classical decoder; may be repeated.  mackay, or min-sum | offset-min-sum | '
-                         'sum-product [:flooding | :layered] [:iters=N] [:alpha=A] [:beta=B]')
+                         'sum-product [:flooding | :layered] [:iters=N] [:alpha=A] [:beta=B], or learned-min-sum:CHECKPOINT '
+                         '(python -m fgnn_amd.ldpc_nms_train)')
     ap.add_argument('--curve', action='store_true', help='print a BER / WER curve of the one --decoder over --snr (no model)')
     ap.add_argument('--snr', default='0,1,2,3,4', help='--curve: SNR values in dB, comma-separated')
     ap.add_argument('--sigma_b', type=int, default=0, help='--curve: the burst level')

@@ -1,0 +1,207 @@
+"""Learned ("neural") min-sum LDPC decoding: a flooding min-sum whose normalisation weights ``alpha`` and offsets ``beta`` are trained
+(Nachmani et al.'s neural min-sum, Lugosch & Gross's neural offset min-sum) — the learned decoder FGNN's papers compare against.
+
+The reference has no counterpart.  The decoder is defined in include/fgnn_hip_ldpc_nms.h: ``n_iter`` flooding iterations, in iteration
+t every check sends ``s * max(alpha_t[w] * mag - beta_t[w], 0)`` with ``mag`` the smallest |q| among the other edges, and the weights
+are shared per iteration, per (iteration, check) or per (iteration, edge).  Forward and backward are the two kernels of
+csrc/ldpc_nms.hip; there is no torch fallback.  It takes every code ``LdpcCode.require_llr_decoder`` takes (N, M <= 1024, degrees <= 16).
+
+    dec = LearnedMinSum(code, n_iter=5, share='edge').cuda()
+    totals = dec(llr)                         # [n_iter, B, N]: every iteration's totals, differentiable in alpha, beta and llr
+    multi_loss(totals, cw).backward()
+    x, viol, iters = dec.decode(llr)          # early stopping, no gradient
+
+``python -m fgnn_amd.ldpc_nms_train`` trains one; ``python -m fgnn_amd.ldpc_eval --decoder learned-min-sum:CHECKPOINT`` evaluates it.
+"""
+import numpy as np
+import torch
+
+from . import _hip
+from .ldpc_code import LdpcCode
+
+SHARES = {'iteration': 0, 'check': 1, 'edge': 2}       # fgnn_ldpc_nms_forward's ``share``
+MAX_ITER = 64
+KIND = 'learned-min-sum'                               # a checkpoint's decoder['kind'], and the head of ldpc_eval's spec
+
+
+def check_nms_args(llr, n_var, n_chk, n_edges, n_iter, share, alpha, beta):
+    """Arguments of ``LearnedMinSum.forward`` / ``decode`` (before anything reaches the device): llr [B, n_var] floating point,
+    ``n_iter`` an integer in 1..64, ``share`` one of ``SHARES``, alpha and beta f32 tensors [n_iter, W] with W = 1, n_chk or n_edges.
+    Returns (B, the share's code, W)."""
+    W = weights_per_iteration(n_iter, share, n_chk, n_edges)
+    for what, v in (('alpha', alpha), ('beta', beta)):
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != (int(n_iter), W):
+            raise ValueError('%s must be a float32 tensor [%d, %d], got %s' % (
+                what, n_iter, W, '%s %s' % (v.dtype, tuple(v.shape)) if isinstance(v, torch.Tensor) else type(v).__name__))
+    if not isinstance(llr, torch.Tensor) or llr.dim() != 2 or llr.shape[1] != int(n_var):
+        raise ValueError('llr must be a [B, %d] tensor, got %s' % (n_var, tuple(llr.shape) if isinstance(llr, torch.Tensor) else type(llr).__name__))
+    if not llr.dtype.is_floating_point:
+        raise ValueError('llr must be a floating-point tensor, got %s' % llr.dtype)
+    if llr.shape[0] >= 2 ** 31:
+        raise ValueError('at most 2^31 - 1 words per call, got %d' % llr.shape[0])
+    return llr.shape[0], SHARES[share], W
+
+
+def weights_per_iteration(n_iter, share, n_chk, n_edges):
+    """W of alpha / beta [n_iter, W]; refuses an ``n_iter`` outside 1..64 and an unknown ``share``."""
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or not 1 <= int(n_iter) <= MAX_ITER:
+        raise ValueError('n_iter must be an integer in 1..%d, got %r' % (MAX_ITER, n_iter))
+    if not isinstance(share, str) or share not in SHARES:
+        raise ValueError('share must be one of %s, got %r' % (', '.join(SHARES), share))
+    return (1, int(n_chk), int(n_edges))[SHARES[share]]
+
+
+def incidence_tables(code):
+    """(col_ptr [N + 1], row_ptr [M + 1], row_edge [E], row_var [E]) int32 of a code, as ``LdpcDataPath._incidence_tables`` builds
+    them: edge e = col_ptr[n] + u is variable n's u-th check; each check's edges in increasing variable order."""
+    cols = [[int(m) for m in row if m >= 0] for row in code.nlist]
+    col_ptr = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int32)
+    rows = [[] for _ in range(code.n_chk)]
+    for n, c in enumerate(cols):
+        for u, m in enumerate(c):
+            rows[m].append((int(col_ptr[n]) + u, n))
+    row_ptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    row_edge = np.array([e for r in rows for e, _ in r], np.int32)
+    row_var = np.array([n for r in rows for _, n in r], np.int32)
+    return col_ptr, row_ptr, row_edge, row_var
+
+
+def backward_workgroups(B):
+    """The number of workgroups ``fgnn_ldpc_nms_backward`` launches over B words (workgroup g takes the words g, g + G, ...)."""
+    return int(_hip.invoke('fgnn_ldpc_nms_backward_workgroups', int(B)))
+
+
+def _query(name, *args):
+    r = int(_hip.invoke(name, *args))
+    if r < 0:
+        raise _hip.FgnnHipError('libfgnn_hip: %s' % _hip.lib().fgnn_last_error().decode())
+    return r
+
+
+def nms_forward_raw(llr, tables, sizes, alpha, beta, n_iter, share):
+    """The train-mode launch: (totals [n_iter, B, N] f32, record uint8 [record bytes]).  llr [B, N] f32 on the device, unit column stride."""
+    N, M, E = sizes
+    B = llr.shape[0]
+    totals = torch.empty((n_iter, B, N), device=llr.device, dtype=torch.float32)
+    nbytes = _query('fgnn_ldpc_nms_record_bytes', B, N, M, E, n_iter)
+    record = torch.empty((nbytes,), device=llr.device, dtype=torch.uint8)
+    _hip.call('fgnn_ldpc_nms_forward', llr, llr.stride(0) if B else N, *tables, alpha, beta, B, N, M, E, n_iter, share, 0, None, None,
+              None, None, totals, record, nbytes)
+    return totals, record
+
+
+def nms_backward_raw(g_totals, llr, tables, sizes, alpha, beta, record, n_iter, share, want_llr=True):
+    """The backward's two launches: (g_alpha, g_beta [n_iter, W] f32, g_llr [B, N] f32 or None).  g_totals [n_iter, B, N], any
+    strides (the kernel reads it densely: a strided one is copied)."""
+    N, M, E = sizes
+    B = llr.shape[0]
+    if tuple(g_totals.shape) != (n_iter, B, N):
+        raise ValueError('g_totals must be [%d, %d, %d], got %s' % (n_iter, B, N, tuple(g_totals.shape)))
+    g_totals = g_totals.to(torch.float32).contiguous()
+    g_alpha, g_beta = torch.empty_like(alpha), torch.empty_like(beta)
+    g_llr = torch.empty((B, N), device=llr.device, dtype=torch.float32) if want_llr else None
+    nbytes = _query('fgnn_ldpc_nms_backward_workspace_bytes', B, N, M, E, n_iter, share)
+    ws = torch.empty((max(nbytes, 16),), device=llr.device, dtype=torch.uint8)
+    _hip.call('fgnn_ldpc_nms_backward', g_totals, llr, llr.stride(0) if B else N, *tables, alpha, beta, record, record.numel(), B, N, M, E,
+              n_iter, share, g_alpha, g_beta, g_llr, ws, ws.numel())
+    return g_alpha, g_beta, g_llr
+
+
+class _NmsFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, llr, alpha, beta, tables, sizes, n_iter, share):
+        alpha, beta = alpha.detach().contiguous(), beta.detach().contiguous()
+        totals, record = nms_forward_raw(llr, tables, sizes, alpha, beta, n_iter, share)
+        ctx.save_for_backward(llr, alpha, beta, record)
+        ctx.nms = (tables, sizes, n_iter, share)
+        return totals
+
+    @staticmethod
+    def backward(ctx, g_totals):
+        llr, alpha, beta, record = ctx.saved_tensors
+        tables, sizes, n_iter, share = ctx.nms
+        g_alpha, g_beta, g_llr = nms_backward_raw(g_totals, llr, tables, sizes, alpha, beta, record, n_iter, share,
+                                                  want_llr=ctx.needs_input_grad[0])
+        return g_llr, g_alpha, g_beta, None, None, None, None
+
+
+class LearnedMinSum(torch.nn.Module):
+    """Min-sum with trained weights for ``code`` (an ``LdpcCode`` within ``require_llr_decoder``'s limits; None: the built-in
+    96.3.963): parameters ``alpha`` and ``beta`` [n_iter, W] f32, W = 1 (``share='iteration'``), M ('check') or E ('edge', indexed by
+    the edge id e = col_ptr[n] + u), filled with the constants ``alpha`` / ``beta``.  ``state_dict()`` is these two tensors; the
+    incidence tables are buffers outside it and follow ``.to(device)``.  The module runs on a ROCm device only."""
+
+    def __init__(self, code=None, n_iter=5, share='edge', alpha=0.8125, beta=0.0):
+        super().__init__()
+        code = LdpcCode.builtin() if code is None else code
+        if not isinstance(code, LdpcCode):
+            raise TypeError('code must be an LdpcCode or None, got %s' % type(code).__name__)
+        code.require_llr_decoder()
+        tabs = incidence_tables(code)
+        self.N, self.M, self.E = code.n_var, code.n_chk, int(tabs[0][-1])
+        W = weights_per_iteration(n_iter, share, self.M, self.E)
+        self.code, self.n_iter, self.share = code, int(n_iter), share
+        for name, value in (('alpha', alpha), ('beta', beta)):
+            if not np.isfinite(float(value)):
+                raise ValueError('%s must be finite, got %r' % (name, value))
+            self.register_parameter(name, torch.nn.Parameter(torch.full((self.n_iter, W), float(value))))
+        for name, a in zip(('col_ptr', 'row_ptr', 'row_edge', 'row_var'), tabs):
+            self.register_buffer(name, torch.from_numpy(a.copy()), persistent=False)
+
+    def extra_repr(self):
+        return '%r, n_iter=%d, share=%r' % (self.code, self.n_iter, self.share)
+
+    def decoder_entry(self):
+        """What a checkpoint carries under 'decoder'."""
+        return {'kind': KIND, 'n_iter': int(self.n_iter), 'share': self.share}
+
+    def _prepare(self, llr):
+        B, share, _ = check_nms_args(llr, self.N, self.M, self.E, self.n_iter, self.share, self.alpha, self.beta)
+        if self.alpha.device.type != 'cuda':
+            raise RuntimeError('LearnedMinSum runs on a ROCm device (no CPU fallback): move the module there first')
+        llr = llr.to(self.alpha.device, torch.float32)
+        if B and (llr.stride(1) != 1 or llr.stride(0) < self.N):
+            llr = llr.contiguous()
+        return llr, B, share, (self.col_ptr, self.row_ptr, self.row_edge, self.row_var), (self.N, self.M, self.E)
+
+    def forward(self, llr):
+        """llr [B, N] = log P(bit = 0) / P(bit = 1) -> totals [n_iter, B, N] f32, every iteration's totals (no early stop), through
+        the train mode of ``fgnn_ldpc_nms_forward``; differentiable in ``alpha``, ``beta`` and, where it asks for it, ``llr``."""
+        llr, _, share, tables, sizes = self._prepare(llr)
+        return _NmsFunction.apply(llr, self.alpha, self.beta, tables, sizes, int(self.n_iter), share)
+
+    @torch.no_grad()
+    def decode(self, llr, want_posteriors=False):
+        """The decode mode (a word stops after the first iteration that leaves no violated check): (x [B, N] uint8 hard decisions —
+        the message is x[:, :K] —, violated checks [B] int32, iterations [B] int32[, post [B, N] f32: the final totals])."""
+        llr, B, share, tables, (N, M, E) = self._prepare(llr)
+        dev = llr.device
+        x = torch.empty((B, N), device=dev, dtype=torch.uint8)
+        post = torch.empty((B, N), device=dev, dtype=torch.float32) if want_posteriors else None
+        viol = torch.empty((B,), device=dev, dtype=torch.int32)
+        iters = torch.empty((B,), device=dev, dtype=torch.int32)
+        _hip.call('fgnn_ldpc_nms_forward', llr, llr.stride(0) if B else N, *tables, self.alpha.detach().contiguous(),
+                  self.beta.detach().contiguous(), B, N, M, E, int(self.n_iter), share, 1, x, post, viol, iters, None, None, 0)
+        return (x, viol, iters, post) if want_posteriors else (x, viol, iters)
+
+
+def multi_loss(totals, cw):
+    """The multi-loss of the neural decoders' papers: the mean over iterations, words and all N bits of
+    ``binary_cross_entropy_with_logits(-totals, cw)`` (a total is log P(0) / P(1): the logit of bit = 1 is -T).  totals [n_iter, B,
+    N], cw [B, N] (the transmitted codeword, any dtype)."""
+    target = cw.to(totals.dtype).unsqueeze(0).expand_as(totals)
+    return torch.nn.functional.binary_cross_entropy_with_logits(-totals, target)
+
+
+def load_checkpoint(path, code=None, device='cpu'):
+    """The ``LearnedMinSum`` of an ``ldpc_nms_train`` checkpoint for ``code`` (None: the built-in 96.3.963).  A checkpoint trained for
+    another code, or one that holds no learned min-sum decoder, is refused with a ValueError."""
+    code = LdpcCode.builtin() if code is None else code
+    ckpt = torch.load(path, map_location='cpu', weights_only=True)
+    entry = ckpt.get('decoder') if isinstance(ckpt, dict) else None
+    if not isinstance(entry, dict) or entry.get('kind') != KIND:
+        raise ValueError('%s holds no learned min-sum decoder (no \'decoder\' entry of kind %r)' % (path, KIND))
+    code.check_checkpoint(ckpt, path)
+    dec = LearnedMinSum(code, int(entry['n_iter']), entry['share'])
+    dec.load_state_dict(ckpt['model_state_dict'], strict=True)
+    return dec.to(device)

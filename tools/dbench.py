@@ -7,7 +7,11 @@ gallager(1024, 4, 8, 2) (which the f64 decoder refuses).  Per decoder: two warm-
 0.2 s of back-to-back calls), then 7 windows between device events; the median window gives the rate.  Also printed: mean iterations
 and the decoded fraction (words that end with no violated check), and the LDS bytes a word occupies.
 
-    python tools/dbench.py [--words 4096] [--snr 2.0] [--repeats 7]
+The learned min-sum decoder (fgnn_amd.ldpc_nms.LearnedMinSum.decode, csrc/ldpc_nms.hip: the decode mode, early stopping) follows,
+beside min-sum:flooding at the same iteration count (--learned_iters), with untrained weights (alpha 0.8125, beta 0: the same
+decisions) shared per iteration, per check and per edge: the weight reads are its only extra work in the loop.
+
+    python tools/dbench.py [--words 4096] [--snr 2.0] [--repeats 7] [--learned_iters 5]
 """
 import argparse
 import os
@@ -20,6 +24,7 @@ import torch
 from fgnn_amd import _hip
 from fgnn_amd.datapath import LLR_ALGORITHMS, LLR_SCHEDULES, LdpcDataPath
 from fgnn_amd.ldpc_code import LdpcCode
+from fgnn_amd.ldpc_nms import SHARES, LearnedMinSum
 
 
 def window(run, calls):
@@ -51,9 +56,10 @@ def main():
     ap.add_argument('--words', type=int, default=4096)
     ap.add_argument('--snr', type=float, default=2.0)
     ap.add_argument('--repeats', type=int, default=7)
+    ap.add_argument('--learned_iters', type=int, default=5)
     args = ap.parse_args()
     dev = torch.device('cuda:0')
-    print('%-24s %-28s %12s %10s %10s %9s %9s' % ('code', 'decoder', 'words/s', 'us/call', 'spread %', 'iters', 'decoded'))
+    print('%-24s %-34s %12s %10s %10s %9s %9s' % ('code', 'decoder', 'words/s', 'us/call', 'spread %', 'iters', 'decoded'))
     for name, code in (('builtin 96.3.963', LdpcCode.builtin()), ('gallager(1024,4,8,2)', LdpcCode.gallager(1024, 4, 8, 2))):
         path = LdpcDataPath(dev, code)
         gen = torch.Generator(device=dev).manual_seed(0)
@@ -69,13 +75,18 @@ def main():
             code.require_decoder()
             runs.append(('mackay f64 (100 loops)', lambda: path.decode(bias, loops=100)))
         except ValueError as e:
-            print('%-24s %-28s refused: %s' % (name, 'mackay f64 (100 loops)', e))
+            print('%-24s %-34s refused: %s' % (name, 'mackay f64 (100 loops)', e))
         for alg in LLR_ALGORITHMS:
             for sched in LLR_SCHEDULES:
                 runs.append(('%s:%s' % (alg, sched), lambda alg=alg, sched=sched: path.decode_llr(llr, alg, sched, max_iter=50)))
+        n = args.learned_iters
+        runs.append(('min-sum:flooding:iters=%d' % n, lambda: path.decode_llr(llr, 'min-sum', 'flooding', max_iter=n)))
+        for share in SHARES:
+            dec = LearnedMinSum(code, n, share).to(dev)
+            runs.append(('learned-min-sum %s iters=%d' % (share, n), lambda dec=dec: dec.decode(llr)))
         for label, run in runs:
             med, lo, hi, (x, viol, iters) = measure(run, args.repeats)
-            print('%-24s %-28s %12.0f %10.1f %10.1f %9.2f %9.4f' % (name, label, args.words / med, med * 1e6, 100 * (hi - lo) / med,
+            print('%-24s %-34s %12.0f %10.1f %10.1f %9.2f %9.4f' % (name, label, args.words / med, med * 1e6, 100 * (hi - lo) / med,
                                                                    iters.float().mean().item(), (viol == 0).float().mean().item()))
 
 
