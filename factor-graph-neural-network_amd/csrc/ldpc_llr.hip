@@ -5,9 +5,9 @@
 //   fgnn_ldpc_decode_llr              one launch decodes the batch: hard decisions, totals, violated checks, iterations
 //   fgnn_ldpc_decode_llr_lds_bytes    the LDS one word occupies, or < 0 where the shape is not taken
 //
-// Tables (fgnn_ldpc_decode's): edge e = col_ptr[n] + u is variable n's u-th check; check m's edges are row_edge[row_ptr[m] ..
-// row_ptr[m + 1] - 1], their variables row_var[..], in increasing variable order.  Layers: the checks of layer k are
-// layer_chk[layer_ptr[k] .. layer_ptr[k + 1] - 1]; no two of them share a variable.
+// The tables, the per-word LDS layout, the thread rule and the steps shared with the learned min-sum kernels (staging, load, variable
+// pass, violated-check count, the min-sum scan) are ldpc_word.h's.  Layers: the checks of layer k are layer_chk[layer_ptr[k] ..
+// layer_ptr[k + 1] - 1]; no two of them share a variable.
 //
 // Steps, all f32, each expression in the order written (this file is built with -ffp-contract=off):
 //   load     prior[n] = llr[n]; NaN -> 0; clamped to +-4096.  T[n] = prior[n], R[e] = 0.
@@ -25,24 +25,14 @@
 //            IEEE; a NaN q (inf - inf) is skipped by the two minima (both comparisons are `<`), counts as non-negative and makes the
 //            totals it enters NaN, whose hard decision is 0.  Sum-product messages are at most 2 atanhf(1 - 2^-24) = 17.33: no overflow.
 //
-// Layout: one workgroup per word; 64 threads (one wave) for max(N, M) <= 256, 128 for <= 512, 256 above, so a lane owns at most
-// four checks and four variables per pass and small codes pay for no barrier between waves.  Per word in LDS for the whole run: f32
-// R [E], T [N], prior [N]; the row table packed as edge | var << 16 [E]; 16-bit row_ptr [M + 1], col_ptr [N + 1], layer_chk [M],
-// layer_ptr [M + 1]; one int per wave for the violated-check count.  Global memory is read once (tables, llr) and written once.  A
-// lane runs one check's update at a time: min-sum in two sweeps over the check's edges (two minima, the place of the first, the
-// sign parity: no array), sum-product with its 16 tanh values and prefix products in registers (fully unrolled, predicated on L).
-#include "fgnn_common.h"
+// Layout: one workgroup per word, ldpc_word.h's state for the whole run with 16-bit layer_chk [M], layer_ptr [M + 1] appended.  Global
+// memory is read once (tables, llr) and written once.  A lane runs one check's update at a time: min-sum in two sweeps over the
+// check's edges (ldpc_min_scan, then the emit: no array), sum-product with its 16 tanh values and prefix products in registers
+// (fully unrolled, predicated on L).
 #include "fgnn_hip_ldpc_llr.h"
-#include <math.h>
-#include <stdint.h>
+#include "ldpc_word.h"
 
-#define LLR_MAXV 1024       // variables, checks
-#define LLR_MAXD 16         // edges per variable / per check
-#define LLR_MAXE (LLR_MAXV * LLR_MAXD)
-#define LLR_CLAMP 4096.0f
 #define LLR_PMAX 0.99999994f        // 1 - 2^-24
-
-extern __shared__ __attribute__((aligned(16))) unsigned char llr_lds[];
 
 struct LlrParams {
     const float* llr; int64_t llr_sb;
@@ -54,30 +44,11 @@ struct LlrParams {
     float alpha, beta;
 };
 
-struct LlrLds {
-    float *R, *T, *prior;
-    uint32_t* rtab;
-    uint16_t *rp, *cp, *lc, *lp;
-    int* wsum;
-};
-
-static int64_t llr_word_bytes(int N, int M, int E) {
-    if (N < 1 || N > LLR_MAXV || M < 1 || M > LLR_MAXV || E < 1 || E > LLR_MAXE || E > (int64_t)LLR_MAXD * N || E > (int64_t)LLR_MAXD * M)
-        return -1;
-    const int64_t u16s = (int64_t)(M + 1) + (N + 1) + M + (M + 1);
-    const int64_t bytes = 4 * (2 * (int64_t)E + 2 * (int64_t)N) + (2 * u16s + 3) / 4 * 4 + 16;
-    return (bytes + 15) / 16 * 16;
-}
+struct LlrLds : LdpcWord { uint16_t *lc, *lp; };        // the layer tables, behind cp
 
 __device__ __forceinline__ LlrLds llr_carve(int N, int M, int E) {
     LlrLds s;
-    s.R = (float*)llr_lds;
-    s.T = s.R + E;
-    s.prior = s.T + N;
-    s.rtab = (uint32_t*)(s.prior + N);
-    s.wsum = (int*)(s.rtab + E);
-    s.rp = (uint16_t*)(s.wsum + 4);
-    s.cp = s.rp + (M + 1);
+    (LdpcWord&)s = ldpc_word_carve(N, M, E, 4);
     s.lc = s.cp + (N + 1);
     s.lp = s.lc + M;
     return s;
@@ -85,36 +56,26 @@ __device__ __forceinline__ LlrLds llr_carve(int N, int M, int E) {
 
 // one check's update (see Steps)
 template <int ALG, bool LAYERED>
-__device__ __forceinline__ void llr_check(const LlrLds& s, int m, float alpha, float beta) {
+__device__ __forceinline__ void llr_check(const LdpcWord& s, int m, float alpha, float beta) {
     const int r0 = s.rp[m], r1 = s.rp[m + 1], L = r1 - r0;
     if (ALG != 2) {
-        float m1 = INFINITY, m2 = INFINITY;
-        int i1 = -1;
-        bool par = false;
-        for (int r = r0; r < r1; ++r) {
-            const uint32_t ev = s.rtab[r];
-            const float q = s.T[ev >> 16] - s.R[ev & 0xffffu];
-            const float a = fabsf(q);
-            par ^= q < 0.0f;
-            if (a < m1) { m2 = m1; m1 = a; i1 = r; }
-            else if (a < m2) m2 = a;
-        }
+        const LdpcMinScan c = ldpc_min_scan(s, r0, r1);
         for (int r = r0; r < r1; ++r) {
             const uint32_t ev = s.rtab[r];
             const int e = ev & 0xffffu, v = ev >> 16;
             const float q = s.T[v] - s.R[e];
-            const float mag = r == i1 ? m2 : m1;
+            const float mag = r == c.i1 ? c.m2 : c.m1;
             float o = ALG == 0 ? alpha * mag : fmaxf(mag - beta, 0.0f);
-            if (par != (q < 0.0f)) o = -o;
+            if (c.par != (q < 0.0f)) o = -o;
             if (L == 1) o = 0.0f;
             s.R[e] = o;
             if (LAYERED) s.T[v] = q + o;
         }
     } else {
-        float t[LLR_MAXD], pf[LLR_MAXD];
+        float t[LDPC_MAXD], pf[LDPC_MAXD];
         float F = 1.0f;
 #pragma unroll
-        for (int l = 0; l < LLR_MAXD; ++l)
+        for (int l = 0; l < LDPC_MAXD; ++l)
             if (l < L) {
                 const uint32_t ev = s.rtab[r0 + l];
                 const float q = s.T[ev >> 16] - s.R[ev & 0xffffu];
@@ -124,7 +85,7 @@ __device__ __forceinline__ void llr_check(const LlrLds& s, int m, float alpha, f
             }
         float S = 1.0f;
 #pragma unroll
-        for (int l = LLR_MAXD - 1; l >= 0; --l)
+        for (int l = LDPC_MAXD - 1; l >= 0; --l)
             if (l < L) {
                 const uint32_t ev = s.rtab[r0 + l];
                 const int e = ev & 0xffffu, v = ev >> 16;
@@ -142,31 +103,17 @@ __device__ __forceinline__ void llr_check(const LlrLds& s, int m, float alpha, f
 
 template <int ALG, bool LAYERED>
 __global__ __launch_bounds__(256) void ldpc_llr_kernel(const LlrParams p) {
-    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
-    const int N = p.N, M = p.M, E = p.E;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int N = p.N, M = p.M;
     const int64_t b = blockIdx.x;
-    const LlrLds s = llr_carve(N, M, E);
+    const LlrLds s = llr_carve(N, M, p.E);
 
-    for (int e = tid; e < E; e += nt) {
-        s.rtab[e] = ((uint32_t)p.row_edge[e] & 0xffffu) | ((uint32_t)p.row_var[e] << 16);
-        s.R[e] = 0.0f;
-    }
-    for (int m = tid; m <= M; m += nt) s.rp[m] = (uint16_t)p.row_ptr[m];
-    for (int n = tid; n <= N; n += nt) s.cp[n] = (uint16_t)p.col_ptr[n];
+    ldpc_stage_tables(s, p, true);
     if (LAYERED) {
         for (int i = tid; i < M; i += nt) s.lc[i] = (uint16_t)p.layer_chk[i];
         for (int k = tid; k <= p.n_layers; k += nt) s.lp[k] = (uint16_t)p.layer_ptr[k];
     }
-    {
-        const float* in = p.llr + b * p.llr_sb;
-        for (int n = tid; n < N; n += nt) {
-            float v = in[n];
-            if (v != v) v = 0.0f;
-            v = fminf(fmaxf(v, -LLR_CLAMP), LLR_CLAMP);
-            s.prior[n] = v;
-            s.T[n] = v;
-        }
-    }
+    ldpc_load_word(s, p.llr + b * p.llr_sb, N);
     __syncthreads();
 
     const float alpha = p.alpha, beta = p.beta;
@@ -176,12 +123,7 @@ __global__ __launch_bounds__(256) void ldpc_llr_kernel(const LlrParams p) {
         if (!LAYERED) {
             for (int m = tid; m < M; m += nt) llr_check<ALG, false>(s, m, alpha, beta);
             __syncthreads();
-            for (int n = tid; n < N; n += nt) {
-                float sum = s.prior[n];
-                const int e1 = s.cp[n + 1];
-                for (int e = s.cp[n]; e < e1; ++e) sum = sum + s.R[e];
-                s.T[n] = sum;
-            }
+            for (int n = tid; n < N; n += nt) s.T[n] = ldpc_var_sum(s, n, s.prior[n]);
             __syncthreads();
         } else {
             for (int k = 0; k < p.n_layers; ++k) {
@@ -190,20 +132,7 @@ __global__ __launch_bounds__(256) void ldpc_llr_kernel(const LlrParams p) {
                 __syncthreads();
             }
         }
-        int cnt = 0;                                                            // checks of odd parity: per wave, then over the waves
-        for (int m0 = wave * 64; m0 < M; m0 += nt) {
-            const int m = m0 + lane;
-            bool odd = false;
-            if (m < M) {
-                const int r1 = s.rp[m + 1];
-                for (int r = s.rp[m]; r < r1; ++r) odd ^= s.T[s.rtab[r] >> 16] < 0.0f;
-            }
-            cnt += __popcll(__ballot(odd));
-        }
-        if (lane == 0) s.wsum[wave] = cnt;
-        __syncthreads();                // (the next write of wsum comes after a later barrier: every wave has read it by then)
-        viol = 0;
-        for (int w = 0; w < nw; ++w) viol += s.wsum[w];
+        viol = ldpc_count_violated(s, M);
         if (viol == 0 || it >= p.max_iter) break;
     }
 
@@ -216,14 +145,7 @@ __global__ __launch_bounds__(256) void ldpc_llr_kernel(const LlrParams p) {
 }
 
 extern "C" int64_t fgnn_ldpc_decode_llr_lds_bytes(int N, int M, int E) {
-    const int64_t r = llr_word_bytes(N, M, E);
-    if (r < 0) {
-        if (N < 1 || N > LLR_MAXV) fgnn_set_error("ldpc_decode_llr: N=%d variables outside 1..%d", N, LLR_MAXV);
-        else if (M < 1 || M > LLR_MAXV) fgnn_set_error("ldpc_decode_llr: M=%d checks outside 1..%d", M, LLR_MAXV);
-        else fgnn_set_error("ldpc_decode_llr: E=%d edges outside 1..%d for N=%d, M=%d (degrees are at most %d)", E,
-                            LLR_MAXD * (N < M ? N : M), N, M, LLR_MAXD);
-    }
-    return r;
+    return ldpc_word_check_sizes("ldpc_decode_llr", N, M, E) == FGNN_OK ? ldpc_word_bytes_llr(N, M, E) : -1;
 }
 
 typedef void (*llr_kernel_t)(const LlrParams);
@@ -257,12 +179,8 @@ extern "C" int fgnn_ldpc_decode_llr(const float* llr, int64_t llr_sb, const int3
                                                {ldpc_llr_kernel<1, false>, ldpc_llr_kernel<1, true>},
                                                {ldpc_llr_kernel<2, false>, ldpc_llr_kernel<2, true>}};
     const llr_kernel_t kernel = kernels[algorithm][n_layers > 0];
-    const int big = N > M ? N : M, threads = big <= 256 ? 64 : big <= 512 ? 128 : 256;
-    const int lds = (int)per;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
+    const int threads = ldpc_word_threads(N, M), lds = (int)per;
+    if (ldpc_set_lds((const void*)kernel, 2 * algorithm + (n_layers > 0), lds) != FGNN_OK) return FGNN_ELAUNCH;      // slots 0..5: kernels[][]
     fgnn_note_kernel("ldpc_llr_kernel<%d,%d>x%d", algorithm, n_layers > 0, threads);
     hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, (hipStream_t)stream, p);
     hipError_t e = hipGetLastError();

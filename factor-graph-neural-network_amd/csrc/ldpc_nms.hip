@@ -9,10 +9,9 @@
 // Built with -ffp-contract=off: the decode mode with constant weights is fgnn_ldpc_decode_llr's flooding min-sum bit for bit, and the
 // backward recomputes u = alpha * mag - beta with the forward's own rounding.
 //
-// Forward layout (ldpc_llr.hip's): one workgroup per word; 64 threads for max(N, M) <= 256, 128 for <= 512, 256 above.  Per word in LDS
-// for the whole run: f32 R [E], T [N], prior [N]; the row table packed as edge | var << 16 [E]; 4 ints (violated checks per wave);
-// 16-bit row_ptr [M + 1], col_ptr [N + 1].  The weights are read from global memory where they are used (one value per check update
-// with share 0 / 1, one per edge with share 2).
+// Forward layout: one workgroup per word, ldpc_word.h's state and thread rule; the min-sum scan, the variable pass and the violated-
+// check count are its functions, the carve, staging and load rule are written out in the kernel.  The weights are read from global
+// memory where they are used (one value per check update with share 0 / 1, one per edge with share 2).
 //
 // Record (train mode), per word b and iteration t three planes of M 32-bit values, plane k of check m at
 // ((b * n_iter + t - 1) * 3 + k) * M + m (a lane owns a check: the planes are read and written coalesced):
@@ -20,30 +19,21 @@
 //   plane 2  bits 0..15 the signs of q_0 .. q_{L-1} (1 = q < 0), bits 16..20 i1, bits 21..25 i2 (31 = none)
 // 12 B M n_iter per word.  mag, the other-sign parity and u > 0 follow from these and the weights.
 //
-// Backward layout: workgroup g of G = min(B, 512) takes the words g, g + G, ...; the same thread counts.  In LDS: f32 gT [N] (this
-// iteration's total gradients), gP [N] (g_prior), gQ [E] (the g_q of the iteration above, by edge: variable n's edges are
-// contiguous, so what an iteration sends back to T[n] is a gather in edge order, not a scatter), the packed row table [E], 8 floats of
-// wave sums, 16-bit row_ptr and col_ptr; and the workgroup's partial of g_alpha / g_beta [2][n_iter W] where the whole stays within
-// 64 KiB (two workgroups per CU and more), else in the workgroup's own slice of the workspace.  Every partial element has one owner
-// thread (share 1: the check's lane; share 2: the edge's check's lane; share 0: thread 0, after a fixed-order wave and workgroup
-// reduction), which adds to it word after word in the order of its words: no atomics, the same bits every time.  The second launch adds
-// the G slices in a fixed order (ldpc_nms_sum_kernel).
-#include "fgnn_common.h"
+// Backward layout: workgroup g of G = min(B, 512) takes the words g, g + G, ...; the same thread counts.  In LDS, ldpc_word.h's
+// state with, in the places of R, T and prior, f32 gQ [E] (the g_q of the iteration above, by edge: variable n's edges are
+// contiguous, so what an iteration sends back to T[n] is a gather in edge order, not a scatter), gT [N] (this iteration's total
+// gradients) and gP [N] (g_prior), and 8 floats of wave sums as the scratch words; and the workgroup's partial of g_alpha / g_beta
+// [2][n_iter W] where the whole stays within 64 KiB (two workgroups per CU and more), else in the workgroup's own slice of the
+// workspace.  Every partial element has one owner thread (share 1: the check's lane; share 2: the edge's check's lane; share 0:
+// thread 0, after a fixed-order wave and workgroup reduction), which adds to it word after word in the order of its words: no
+// atomics, the same bits every time.  The second launch adds the G slices in a fixed order (ldpc_nms_sum_kernel).
 #include "fgnn_hip_ldpc_nms.h"
-#include <atomic>
-#include <math.h>
-#include <stdint.h>
+#include "ldpc_word.h"
 
-#define NMS_MAXV 1024       // variables, checks
-#define NMS_MAXD 16         // edges per variable / per check
 #define NMS_MAXIT 64
-#define NMS_CLAMP 4096.0f
 #define NMS_BWD_GROUPS 512
 #define NMS_PARTIAL_LDS (64 * 1024)     // the backward keeps its partial in LDS while state + partial stay within this
 #define NMS_NONE 31u
-#define NMS_MAX_DEVICES 64
-
-extern __shared__ __attribute__((aligned(16))) unsigned char nms_lds[];
 
 struct NmsFwdParams {
     const float* llr; int64_t llr_sb;
@@ -67,20 +57,9 @@ struct NmsBwdParams {
     int N, M, E, n_iter, share, W;
 };
 
-static bool nms_shape_ok(int N, int M, int E) {
-    return N >= 1 && N <= NMS_MAXV && M >= 1 && M <= NMS_MAXV && E >= 1 && E <= (int64_t)NMS_MAXD * N && E <= (int64_t)NMS_MAXD * M;
-}
-
-__host__ __device__ static inline int64_t nms_u16_bytes(int N, int M) { return (2 * ((int64_t)(M + 1) + (N + 1)) + 15) / 16 * 16; }
-
-// forward: R, rtab [E]; T, prior [N]; 4 ints; the 16-bit tables.  backward: gQ, rtab [E]; gT, gP [N]; 8 floats; the 16-bit tables.
+// the state's bytes: 4 scratch ints forward, 8 floats backward
 __host__ __device__ static inline int64_t nms_state_bytes(int N, int M, int E, int backward) {
-    return (4 * (2 * (int64_t)E + 2 * (int64_t)N) + (backward ? 32 : 16) + 15) / 16 * 16 + nms_u16_bytes(N, M);
-}
-
-static int nms_threads(int N, int M) {
-    const int big = N > M ? N : M;
-    return big <= 256 ? 64 : big <= 512 ? 128 : 256;
+    return ldpc_word_bytes_nms(N, M, E, backward ? 32 : 16);
 }
 
 __device__ __forceinline__ float nms_weight(const float* w, int it, int W, int share, int m, int e) {
@@ -89,33 +68,32 @@ __device__ __forceinline__ float nms_weight(const float* w, int it, int W, int s
 
 template <bool TRAIN>
 __global__ __launch_bounds__(256) void ldpc_nms_fwd_kernel(const NmsFwdParams p) {
-    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+    const int tid = threadIdx.x, nt = blockDim.x;
     const int N = p.N, M = p.M, E = p.E, share = p.share;
     const int W = share == 0 ? 1 : share == 1 ? M : E;
     const int64_t b = blockIdx.x;
-    float* R = (float*)nms_lds;
+    // ldpc_word_carve, ldpc_stage_tables and ldpc_load_word written out: as calls they cost the decode mode 1 %
+    float* R = (float*)ldpc_lds;
     float* T = R + E;
     float* prior = T + N;
     uint32_t* rtab = (uint32_t*)(prior + N);
     int* wsum = (int*)(rtab + E);
     uint16_t* rp = (uint16_t*)(wsum + 4);
     uint16_t* cp = rp + (M + 1);
-
+    const LdpcWord s = {R, T, prior, rtab, wsum, rp, cp};
     for (int e = tid; e < E; e += nt) {
         rtab[e] = ((uint32_t)p.row_edge[e] & 0xffffu) | ((uint32_t)p.row_var[e] << 16);
         R[e] = 0.0f;
     }
     for (int m = tid; m <= M; m += nt) rp[m] = (uint16_t)p.row_ptr[m];
     for (int n = tid; n <= N; n += nt) cp[n] = (uint16_t)p.col_ptr[n];
-    {
-        const float* in = p.llr + b * p.llr_sb;
-        for (int n = tid; n < N; n += nt) {
-            float v = in[n];
-            if (v != v) v = 0.0f;
-            v = fminf(fmaxf(v, -NMS_CLAMP), NMS_CLAMP);
-            prior[n] = v;
-            T[n] = v;
-        }
+    const float* in = p.llr + b * p.llr_sb;
+    for (int n = tid; n < N; n += nt) {
+        float v = in[n];
+        if (v != v) v = 0.0f;
+        v = fminf(fmaxf(v, -LDPC_CLAMP), LDPC_CLAMP);
+        prior[n] = v;
+        T[n] = v;
     }
     __syncthreads();
 
@@ -124,62 +102,34 @@ __global__ __launch_bounds__(256) void ldpc_nms_fwd_kernel(const NmsFwdParams p)
         ++it;
         for (int m = tid; m < M; m += nt) {
             const int r0 = rp[m], r1 = rp[m + 1], L = r1 - r0;
-            float m1 = INFINITY, m2 = INFINITY;
-            int i1 = -1, i2 = -1;
-            uint32_t signs = 0;
-            bool par = false;
-            for (int r = r0; r < r1; ++r) {
-                const uint32_t ev = rtab[r];
-                const float q = T[ev >> 16] - R[ev & 0xffffu];
-                const float a = fabsf(q);
-                const bool neg = q < 0.0f;
-                par ^= neg;
-                signs |= (uint32_t)neg << (r - r0);
-                if (a < m1) { m2 = m1; i2 = i1; m1 = a; i1 = r; }
-                else if (a < m2) { m2 = a; i2 = r; }
-            }
+            const LdpcMinScan c = ldpc_min_scan(s, r0, r1);
             if (TRAIN) {
                 uint32_t* rec = p.record + ((b * p.n_iter + (it - 1)) * 3) * M + m;
-                rec[0] = __float_as_uint(m1);
-                rec[M] = __float_as_uint(m2);
-                rec[2 * (int64_t)M] = signs | (i1 < 0 ? NMS_NONE : (uint32_t)(i1 - r0)) << 16 | (i2 < 0 ? NMS_NONE : (uint32_t)(i2 - r0)) << 21;
+                rec[0] = __float_as_uint(c.m1);
+                rec[M] = __float_as_uint(c.m2);
+                rec[2 * (int64_t)M] = c.signs | (c.i1 < 0 ? NMS_NONE : (uint32_t)(c.i1 - r0)) << 16 | (c.i2 < 0 ? NMS_NONE : (uint32_t)(c.i2 - r0)) << 21;
             }
             float al = 0.0f, be = 0.0f;
             if (share != 2) { al = nms_weight(p.alpha, it, W, share, m, 0); be = nms_weight(p.beta, it, W, share, m, 0); }
             for (int r = r0; r < r1; ++r) {
                 const int e = rtab[r] & 0xffffu;
                 if (share == 2) { al = nms_weight(p.alpha, it, W, 2, m, e); be = nms_weight(p.beta, it, W, 2, m, e); }
-                const float mag = r == i1 ? m2 : m1;
+                const float mag = r == c.i1 ? c.m2 : c.m1;
                 const float u = al * mag - be;
                 float o = fmaxf(u, 0.0f);
-                if (par != (bool)((signs >> (r - r0)) & 1u)) o = -o;
+                if (c.par != (bool)((c.signs >> (r - r0)) & 1u)) o = -o;
                 if (L == 1) o = 0.0f;
                 R[e] = o;
             }
         }
         __syncthreads();
         for (int n = tid; n < N; n += nt) {
-            float sum = prior[n];
-            const int e1 = cp[n + 1];
-            for (int e = cp[n]; e < e1; ++e) sum = sum + R[e];
+            const float sum = ldpc_var_sum(s, n, prior[n]);
             T[n] = sum;
             if (TRAIN) p.totals[((int64_t)(it - 1) * p.B + b) * N + n] = sum;
         }
         __syncthreads();
-        int cnt = 0;                                                            // checks of odd parity: per wave, then over the waves
-        for (int m0 = wave * 64; m0 < M; m0 += nt) {
-            const int m = m0 + lane;
-            bool odd = false;
-            if (m < M) {
-                const int r1 = rp[m + 1];
-                for (int r = rp[m]; r < r1; ++r) odd ^= T[rtab[r] >> 16] < 0.0f;
-            }
-            cnt += __popcll(__ballot(odd));
-        }
-        if (lane == 0) wsum[wave] = cnt;
-        __syncthreads();                // (the next write of wsum comes after a later barrier: every wave has read it by then)
-        viol = 0;
-        for (int w = 0; w < nw; ++w) viol += wsum[w];
+        viol = ldpc_count_violated(s, M);
         if ((!TRAIN && viol == 0) || it >= p.n_iter) break;
     }
 
@@ -201,19 +151,14 @@ __global__ __launch_bounds__(256) void ldpc_nms_bwd_kernel(const NmsBwdParams p)
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
     const int N = p.N, M = p.M, E = p.E, share = p.share, W = p.W, n_iter = p.n_iter;
     const int cnt = n_iter * W;
-    float* gQ = (float*)nms_lds;
-    float* gT = gQ + E;
-    float* gP = gT + N;
-    uint32_t* rtab = (uint32_t*)(gP + N);
-    float* red = (float*)(rtab + E);
-    uint16_t* rp = (uint16_t*)(red + 8);
-    uint16_t* cp = rp + (M + 1);
+    const LdpcWord s = ldpc_word_carve(N, M, E, 8);
+    float *gQ = s.R, *gT = s.T, *gP = s.prior, *red = (float*)s.wsum;
+    const uint32_t* rtab = s.rtab;
+    const uint16_t* rp = s.rp;
     float* slice = p.ws + (int64_t)blockIdx.x * 2 * cnt;
-    float* part = PART_LDS ? (float*)(nms_lds + nms_state_bytes(N, M, E, 1)) : slice;
+    float* part = PART_LDS ? (float*)(ldpc_lds + nms_state_bytes(N, M, E, 1)) : slice;
 
-    for (int e = tid; e < E; e += nt) rtab[e] = ((uint32_t)p.row_edge[e] & 0xffffu) | ((uint32_t)p.row_var[e] << 16);
-    for (int m = tid; m <= M; m += nt) rp[m] = (uint16_t)p.row_ptr[m];
-    for (int n = tid; n <= N; n += nt) cp[n] = (uint16_t)p.col_ptr[n];
+    ldpc_stage_tables(s, p, false);
     for (int i = tid; i < 2 * cnt; i += nt) part[i] = 0.0f;
     __syncthreads();
 
@@ -223,10 +168,7 @@ __global__ __launch_bounds__(256) void ldpc_nms_bwd_kernel(const NmsBwdParams p)
         __syncthreads();
         for (int t = n_iter; t >= 1; --t) {
             for (int n = tid; n < N; n += nt) {                                 // gT_t = g_totals[t] + what iteration t + 1 sent back
-                float back = 0.0f;
-                const int e1 = cp[n + 1];
-                for (int e = cp[n]; e < e1; ++e) back += gQ[e];
-                const float g = p.g_totals[((int64_t)(t - 1) * p.B + b) * N + n] + back;
+                const float g = p.g_totals[((int64_t)(t - 1) * p.B + b) * N + n] + ldpc_var_sum(s, n, 0.0f);
                 gT[n] = g;
                 gP[n] += g;
             }
@@ -295,12 +237,10 @@ __global__ __launch_bounds__(256) void ldpc_nms_bwd_kernel(const NmsBwdParams p)
             }
         }
         for (int n = tid; n < N; n += nt) {                                     // t = 0: T_0 = prior
-            float g = gP[n];
-            const int e1 = cp[n + 1];
-            for (int e = cp[n]; e < e1; ++e) g += gQ[e];
+            const float g = ldpc_var_sum(s, n, gP[n]);
             if (p.g_llr) {
                 const float v = p.llr[b * p.llr_sb + n];
-                p.g_llr[b * N + n] = (v >= -NMS_CLAMP && v <= NMS_CLAMP) ? g : 0.0f;
+                p.g_llr[b * N + n] = (v >= -LDPC_CLAMP && v <= LDPC_CLAMP) ? g : 0.0f;
             }
         }
         __syncthreads();
@@ -327,11 +267,7 @@ __global__ __launch_bounds__(256) void ldpc_nms_sum_kernel(const float* ws, int 
 }
 
 static int nms_check_sizes(const char* who, int64_t B, int N, int M, int E, int n_iter, int share) {
-    if (N < 1 || N > NMS_MAXV) FGNN_FAIL(FGNN_EUNSUPPORTED, "%s: N=%d variables outside 1..%d", who, N, NMS_MAXV);
-    if (M < 1 || M > NMS_MAXV) FGNN_FAIL(FGNN_EUNSUPPORTED, "%s: M=%d checks outside 1..%d", who, M, NMS_MAXV);
-    if (!nms_shape_ok(N, M, E))
-        FGNN_FAIL(FGNN_EUNSUPPORTED, "%s: E=%d edges outside 1..%d for N=%d, M=%d (degrees are at most %d)", who, E,
-                  NMS_MAXD * (N < M ? N : M), N, M, NMS_MAXD);
+    if (ldpc_word_check_sizes(who, N, M, E) != FGNN_OK) return FGNN_EUNSUPPORTED;
     if (B < 0 || B > 0x7fffffffll) FGNN_FAIL(FGNN_EINVAL, "%s: batch %lld outside 0 .. 2^31-1", who, (long long)B);
     if (n_iter < 1 || n_iter > NMS_MAXIT) FGNN_FAIL(FGNN_EINVAL, "%s: n_iter=%d outside 1..%d", who, n_iter, NMS_MAXIT);
     if (share < 0 || share > 2) FGNN_FAIL(FGNN_EINVAL, "%s: share=%d outside 0..2", who, share);
@@ -354,20 +290,6 @@ extern "C" int64_t fgnn_ldpc_nms_backward_workspace_bytes(int64_t B, int N, int 
     if (nms_check_sizes("ldpc_nms_backward_workspace_bytes", B, N, M, E, n_iter, share) != FGNN_OK) return -1;
     const int64_t W = share == 0 ? 1 : share == 1 ? M : E;
     return fgnn_ldpc_nms_backward_workgroups(B) * 2 * n_iter * W * 4;
-}
-
-// Above 48 KiB a kernel needs its dynamic-LDS limit raised once per device; the largest value set so far is remembered per
-// (device, kernel), so that a step replayed or captured after its warm-up makes no such call.
-static int nms_set_lds(const void* kernel, int slot, int lds) {
-    static std::atomic<int> set_to[NMS_MAX_DEVICES][4];
-    if (lds <= 48 * 1024) return FGNN_OK;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= NMS_MAX_DEVICES) dev = -1;
-    if (dev >= 0 && set_to[dev][slot].load() >= lds) return FGNN_OK;
-    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    if (dev >= 0) set_to[dev][slot].store(lds);
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_ldpc_nms_forward(const float* llr, int64_t llr_sb, const int32_t* col_ptr, const int32_t* row_ptr,
@@ -395,8 +317,8 @@ extern "C" int fgnn_ldpc_nms_forward(const float* llr, int64_t llr_sb, const int
     p.x = x; p.post = post; p.totals = totals; p.viol = viol; p.iters = iters; p.record = (uint32_t*)record;
     p.B = B; p.N = N; p.M = M; p.E = E; p.n_iter = n_iter; p.share = share;
     void (*kernel)(const NmsFwdParams) = stop_early ? ldpc_nms_fwd_kernel<false> : ldpc_nms_fwd_kernel<true>;
-    const int threads = nms_threads(N, M), lds = (int)nms_state_bytes(N, M, E, 0);
-    if (nms_set_lds((const void*)kernel, stop_early ? 0 : 1, lds) != FGNN_OK) return FGNN_ELAUNCH;
+    const int threads = ldpc_word_threads(N, M), lds = (int)nms_state_bytes(N, M, E, 0);
+    if (ldpc_set_lds((const void*)kernel, stop_early ? 0 : 1, lds) != FGNN_OK) return FGNN_ELAUNCH;     // slots 0, 1: the forward's
     fgnn_note_kernel("ldpc_nms_fwd_kernel<%d>x%d", !stop_early, threads);
     hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, (hipStream_t)stream, p);
     hipError_t e = hipGetLastError();
@@ -442,8 +364,8 @@ extern "C" int fgnn_ldpc_nms_backward(const float* g_totals, const float* llr, i
     const int64_t state = nms_state_bytes(N, M, E, 1);
     const bool part_lds = state + 8 * (int64_t)cnt <= NMS_PARTIAL_LDS;
     void (*kernel)(const NmsBwdParams) = part_lds ? ldpc_nms_bwd_kernel<true> : ldpc_nms_bwd_kernel<false>;
-    const int threads = nms_threads(N, M), lds = (int)(state + (part_lds ? 8 * (int64_t)cnt : 0));
-    if (nms_set_lds((const void*)kernel, part_lds ? 2 : 3, lds) != FGNN_OK) return FGNN_ELAUNCH;
+    const int threads = ldpc_word_threads(N, M), lds = (int)(state + (part_lds ? 8 * (int64_t)cnt : 0));
+    if (ldpc_set_lds((const void*)kernel, part_lds ? 2 : 3, lds) != FGNN_OK) return FGNN_ELAUNCH;       // slots 2, 3: the backward's
     fgnn_note_kernel("ldpc_nms_bwd_kernel<%d>x%d", part_lds, threads);
     hipLaunchKernelGGL(kernel, dim3((unsigned)G), dim3(threads), lds, (hipStream_t)stream, p);
     hipError_t e = hipGetLastError();

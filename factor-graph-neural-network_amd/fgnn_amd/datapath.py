@@ -65,6 +65,23 @@ def check_decode_llr_args(llr, n_var, algorithm, schedule, max_iter, alpha, beta
     return llr.shape[0], LLR_ALGORITHMS[algorithm]
 
 
+def _llr_batch(llr, device, n_var):
+    """A checked [B, n_var] LLR batch as the decoder kernels read it: f32 on ``device``, unit column stride, rows that do not
+    overlap (copied only where it is not)."""
+    llr = llr.to(device, torch.float32)
+    if llr.shape[0] and (llr.stride(1) != 1 or llr.stride(0) < n_var):
+        llr = llr.contiguous()
+    return llr
+
+
+def _decode_outputs(B, n_var, device, post_dtype=None):
+    """A decoder's outputs, uninitialised: (x [B, n_var] uint8, posteriors [B, n_var] ``post_dtype`` or None, viol [B] int32,
+    iters [B] int32)."""
+    return (torch.empty((B, n_var), device=device, dtype=torch.uint8),
+            None if post_dtype is None else torch.empty((B, n_var), device=device, dtype=post_dtype),
+            torch.empty((B,), device=device, dtype=torch.int32), torch.empty((B,), device=device, dtype=torch.int32))
+
+
 class LdpcDataPath:
     """The data path of one regular LDPC code (``code``: an ``LdpcCode``; None: the built-in 96.3.963 — 48 message bits, 48 parity
     bits, 3 checks per variable, 6 variables per check): K message bits, P parity bits (codeword = [s | G s]), N = K + P variables,
@@ -216,22 +233,12 @@ class LdpcDataPath:
         torch.save({k: d[k] for k in ('noizy_sg', 'gts', 'snr_dbs', 'sigma_b')}, path)
         return d.get('sp_error')
 
-    def _incidence_tables(self, nlist, nchk):
-        """alist column lists (each variable's checks in file order, -1 = padding) -> the device tables of
-        `fgnn_ldpc_decode`: col_ptr, row_ptr, row_edge, row_var."""
-        cols = [[int(m) for m in row if m >= 0] for row in nlist]
-        col_ptr = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int32)
-        rows = [[] for _ in range(nchk)]
-        for n, c in enumerate(cols):
-            for u, m in enumerate(c):
-                rows[m].append((int(col_ptr[n]) + u, n))
-        if max(len(c) for c in cols) > 16 or max(len(r) for r in rows) > 16:
-            raise ValueError('at most 16 checks per variable / variables per check')
-        row_ptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
-        row_edge = np.array([e for r in rows for e, _ in r], np.int32)
-        row_var = np.array([n for r in rows for _, n in r], np.int32)
-        dev = lambda a: torch.from_numpy(a).to(self.device)
-        return dev(col_ptr), dev(row_ptr), dev(row_edge), dev(row_var), len(cols), nchk, int(col_ptr[-1])
+    def _incidence_tables(self):
+        """``code.incidence_tables()`` on the device, then (N, M, E).  (The degree limits are ``require_decoder``'s /
+        ``require_llr_decoder``'s, which the callers run first.)"""
+        tabs = self.code.incidence_tables()
+        dev = lambda a: torch.from_numpy(a.copy()).to(self.device)      # (a copy: the code's arrays are read-only)
+        return tuple(dev(a) for a in tabs) + (self.code.n_var, self.code.n_chk, int(tabs[0][-1]))
 
     def bit_prior(self, y, snr_db):
         """`y2b` (MNC_py.cpp:104-108): P(bit = 1 | y) = 1 / (1 + exp(-2 gcx y)), float64."""
@@ -244,16 +251,13 @@ class LdpcDataPath:
         message is x[:, :48] —, violated checks [B] int32, iterations [B] int32[, q1 [B,96] float64])."""
         if self._decode_tables is None:
             self.code.require_decoder()
-            self._decode_tables = self._incidence_tables(self.code.nlist, self.M)
+            self._decode_tables = self._incidence_tables()
         col_ptr, row_ptr, row_edge, row_var, N, M, E = self._decode_tables
         if bias.dim() != 2 or bias.shape[1] != N:
             raise ValueError('bias must be [B, %d], got %s' % (N, tuple(bias.shape)))
         bias = bias.to(self.device, torch.float64).contiguous()
         B = bias.shape[0]
-        x = torch.empty((B, N), device=self.device, dtype=torch.uint8)
-        q1 = torch.empty((B, N), device=self.device, dtype=torch.float64) if want_posteriors else None
-        viol = torch.empty((B,), device=self.device, dtype=torch.int32)
-        iters = torch.empty((B,), device=self.device, dtype=torch.int32)
+        x, q1, viol, iters = _decode_outputs(B, N, self.device, torch.float64 if want_posteriors else None)
         _hip.call('fgnn_ldpc_decode', bias, col_ptr, row_ptr, row_edge, row_var, B, N, M, E, int(loops), x, q1, viol, iters)
         return (x, viol, iters, q1) if want_posteriors else (x, viol, iters)
 
@@ -274,15 +278,10 @@ class LdpcDataPath:
             self.code.require_llr_decoder()
             lp, lc = self.code.layers()
             dev = lambda a: torch.from_numpy(np.array(a, np.int32)).to(self.device)       # (a copy: the code's arrays are read-only)
-            self._llr_tables = self._incidence_tables(self.code.nlist, self.M) + (dev(lp), dev(lc), len(lp) - 1)
+            self._llr_tables = self._incidence_tables() + (dev(lp), dev(lc), len(lp) - 1)
         col_ptr, row_ptr, row_edge, row_var, N, M, E, layer_ptr, layer_chk, n_layers = self._llr_tables
-        llr = llr.to(self.device, torch.float32)
-        if B and (llr.stride(1) != 1 or llr.stride(0) < N):
-            llr = llr.contiguous()
-        x = torch.empty((B, N), device=self.device, dtype=torch.uint8)
-        post = torch.empty((B, N), device=self.device, dtype=torch.float32) if want_posteriors else None
-        viol = torch.empty((B,), device=self.device, dtype=torch.int32)
-        iters = torch.empty((B,), device=self.device, dtype=torch.int32)
+        llr = _llr_batch(llr, self.device, N)
+        x, post, viol, iters = _decode_outputs(B, N, self.device, torch.float32 if want_posteriors else None)
         layered = schedule == 'layered'
         _hip.call('fgnn_ldpc_decode_llr', llr, llr.stride(0) if B else N, col_ptr, row_ptr, row_edge, row_var,
                   layer_ptr if layered else None, layer_chk if layered else None, n_layers if layered else 0, B, N, M, E, alg,

@@ -29,7 +29,7 @@ from .tables import _DATA
 
 MAX_VAR = 1024              # csrc/ldpc_datapath.hip, csrc/ldpc_code.hip: the feature kernels' LDS row
 DEC_MAXE, DEC_MAXD = 1024, 16       # csrc/ldpc_decode.hip
-LLR_MAXV, LLR_MAXD = 1024, 16       # csrc/ldpc_llr.hip: variables / checks, edges per variable / check
+LLR_MAXV, LLR_MAXD = 1024, 16       # csrc/ldpc_word.h's LDPC_MAXV, LDPC_MAXD: variables / checks, edges per variable / check
 MODEL_MAX_VAR = 132         # the model: verified up to here (the message operator's own bound is k <= 255)
 TRAIN_MAX_VAR, TRAIN_DV, TRAIN_DC = 96, 3, 6      # the training loop: the built-in code's shape class
 
@@ -246,7 +246,7 @@ class LdpcCode:
         return self
 
     def require_llr_decoder(self):
-        """The LLR-domain decoders' limits (csrc/ldpc_llr.hip: LLR_MAXV variables and checks, LLR_MAXD per variable / check)."""
+        """The LLR-domain decoders' limits (``LLR_MAXV`` variables and checks, ``LLR_MAXD`` per variable / check: csrc/ldpc_word.h's LDPC_MAXV, LDPC_MAXD)."""
         deg = max(int((self.nlist >= 0).sum(1).max()), self.dc, self.dv)
         if self.n_var > LLR_MAXV:
             raise ValueError('N = %d variables: the LLR-domain decoders take at most %d' % (self.n_var, LLR_MAXV))
@@ -255,6 +255,25 @@ class LdpcCode:
         if deg > LLR_MAXD:
             raise ValueError('degree %d: the LLR-domain decoders take at most %d checks per variable / variables per check' % (deg, LLR_MAXD))
         return self
+
+    def incidence_tables(self):
+        """(col_ptr [N + 1], row_ptr [M + 1], row_edge [E], row_var [E]) read-only int32, the decoders' tables (``fgnn_ldpc_decode``'s;
+        csrc/ldpc_word.h): edge e = col_ptr[n] + u is variable n's u-th check in ``nlist``'s order; check m's edges are
+        row_edge[row_ptr[m] .. row_ptr[m + 1] - 1], their variables row_var[..], in increasing variable order.  Memoised."""
+        memo = self.__dict__.get('_incidence')
+        if memo is None:
+            cols = [[int(m) for m in row if m >= 0] for row in self.nlist]
+            col_ptr = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int32)
+            rows = [[] for _ in range(self.n_chk)]
+            for n, c in enumerate(cols):
+                for u, m in enumerate(c):
+                    rows[m].append((int(col_ptr[n]) + u, n))
+            row_ptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+            memo = (col_ptr, row_ptr, np.array([e for r in rows for e, _ in r], np.int32), np.array([n for r in rows for _, n in r], np.int32))
+            for a in memo:
+                a.setflags(write=False)
+            object.__setattr__(self, '_incidence', memo)
+        return memo
 
     def layers(self):
         """(layer_ptr [n_layers + 1], layer_chk [M]) int32: the checks partitioned into layers for a layered decoding schedule, no

@@ -4,7 +4,8 @@
 The reference has no counterpart.  The decoder is defined in include/fgnn_hip_ldpc_nms.h: ``n_iter`` flooding iterations, in iteration
 t every check sends ``s * max(alpha_t[w] * mag - beta_t[w], 0)`` with ``mag`` the smallest |q| among the other edges, and the weights
 are shared per iteration, per (iteration, check) or per (iteration, edge).  Forward and backward are the two kernels of
-csrc/ldpc_nms.hip; there is no torch fallback.  It takes every code ``LdpcCode.require_llr_decoder`` takes (N, M <= 1024, degrees <= 16).
+csrc/ldpc_nms.hip; there is no torch fallback.  It takes every code ``LdpcCode.require_llr_decoder`` takes (csrc/ldpc_word.h's
+limits: N, M <= 1024, degrees <= 16).
 
     dec = LearnedMinSum(code, n_iter=5, share='edge').cuda()
     totals = dec(llr)                         # [n_iter, B, N]: every iteration's totals, differentiable in alpha, beta and llr
@@ -17,10 +18,11 @@ import numpy as np
 import torch
 
 from . import _hip
+from .datapath import _decode_outputs, _llr_batch
 from .ldpc_code import LdpcCode
 
 SHARES = {'iteration': 0, 'check': 1, 'edge': 2}       # fgnn_ldpc_nms_forward's ``share``
-MAX_ITER = 64
+MAX_ITER = 64                                          # csrc/ldpc_nms.hip's NMS_MAXIT
 KIND = 'learned-min-sum'                               # a checkpoint's decoder['kind'], and the head of ldpc_eval's spec
 
 
@@ -49,21 +51,6 @@ def weights_per_iteration(n_iter, share, n_chk, n_edges):
     if not isinstance(share, str) or share not in SHARES:
         raise ValueError('share must be one of %s, got %r' % (', '.join(SHARES), share))
     return (1, int(n_chk), int(n_edges))[SHARES[share]]
-
-
-def incidence_tables(code):
-    """(col_ptr [N + 1], row_ptr [M + 1], row_edge [E], row_var [E]) int32 of a code, as ``LdpcDataPath._incidence_tables`` builds
-    them: edge e = col_ptr[n] + u is variable n's u-th check; each check's edges in increasing variable order."""
-    cols = [[int(m) for m in row if m >= 0] for row in code.nlist]
-    col_ptr = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int32)
-    rows = [[] for _ in range(code.n_chk)]
-    for n, c in enumerate(cols):
-        for u, m in enumerate(c):
-            rows[m].append((int(col_ptr[n]) + u, n))
-    row_ptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
-    row_edge = np.array([e for r in rows for e, _ in r], np.int32)
-    row_var = np.array([n for r in rows for _, n in r], np.int32)
-    return col_ptr, row_ptr, row_edge, row_var
 
 
 def backward_workgroups(B):
@@ -137,7 +124,7 @@ class LearnedMinSum(torch.nn.Module):
         if not isinstance(code, LdpcCode):
             raise TypeError('code must be an LdpcCode or None, got %s' % type(code).__name__)
         code.require_llr_decoder()
-        tabs = incidence_tables(code)
+        tabs = code.incidence_tables()
         self.N, self.M, self.E = code.n_var, code.n_chk, int(tabs[0][-1])
         W = weights_per_iteration(n_iter, share, self.M, self.E)
         self.code, self.n_iter, self.share = code, int(n_iter), share
@@ -159,10 +146,7 @@ class LearnedMinSum(torch.nn.Module):
         B, share, _ = check_nms_args(llr, self.N, self.M, self.E, self.n_iter, self.share, self.alpha, self.beta)
         if self.alpha.device.type != 'cuda':
             raise RuntimeError('LearnedMinSum runs on a ROCm device (no CPU fallback): move the module there first')
-        llr = llr.to(self.alpha.device, torch.float32)
-        if B and (llr.stride(1) != 1 or llr.stride(0) < self.N):
-            llr = llr.contiguous()
-        return llr, B, share, (self.col_ptr, self.row_ptr, self.row_edge, self.row_var), (self.N, self.M, self.E)
+        return _llr_batch(llr, self.alpha.device, self.N), B, share, (self.col_ptr, self.row_ptr, self.row_edge, self.row_var), (self.N, self.M, self.E)
 
     def forward(self, llr):
         """llr [B, N] = log P(bit = 0) / P(bit = 1) -> totals [n_iter, B, N] f32, every iteration's totals (no early stop), through
@@ -175,11 +159,7 @@ class LearnedMinSum(torch.nn.Module):
         """The decode mode (a word stops after the first iteration that leaves no violated check): (x [B, N] uint8 hard decisions —
         the message is x[:, :K] —, violated checks [B] int32, iterations [B] int32[, post [B, N] f32: the final totals])."""
         llr, B, share, tables, (N, M, E) = self._prepare(llr)
-        dev = llr.device
-        x = torch.empty((B, N), device=dev, dtype=torch.uint8)
-        post = torch.empty((B, N), device=dev, dtype=torch.float32) if want_posteriors else None
-        viol = torch.empty((B,), device=dev, dtype=torch.int32)
-        iters = torch.empty((B,), device=dev, dtype=torch.int32)
+        x, post, viol, iters = _decode_outputs(B, N, llr.device, torch.float32 if want_posteriors else None)
         _hip.call('fgnn_ldpc_nms_forward', llr, llr.stride(0) if B else N, *tables, self.alpha.detach().contiguous(),
                   self.beta.detach().contiguous(), B, N, M, E, int(self.n_iter), share, 1, x, post, viol, iters, None, None, 0)
         return (x, viol, iters, post) if want_posteriors else (x, viol, iters)

@@ -30,7 +30,7 @@ PMAX = 1.0 - 2.0 ** -24
 
 def tables(nlist, nchk):
     """alist column lists (each variable's checks in file order, -1 = padding) -> (col_ptr, row_ptr, row_edge, row_var), as
-    ``LdpcDataPath._incidence_tables`` builds them."""
+    ``LdpcCode.incidence_tables`` builds them (restated here on purpose)."""
     cols = [[int(m) for m in row if m >= 0] for row in nlist]
     col_ptr = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int64)
     rows = [[] for _ in range(nchk)]

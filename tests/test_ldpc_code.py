@@ -298,3 +298,17 @@ def test_host_layers_take_a_code_without_a_device():
         assert set(ldpc_train.checkpoint_dict(m, opt, sched, 1, 2, default)) == {'model_state_dict', 'optimizer_state_dict', 'lr_sche', 'epoch', 'gcnt'}
     with pytest.raises(ValueError, match='K = 48 of N = 96'):
         ldpc_eval.evaluate(m, ts)                                                 # a model of another code, before any device work
+
+
+@pytest.mark.parametrize('name', ('g12', 'builtin', 'g32', 'g384', 'g1024'))
+def test_incidence_tables_are_the_restatements(name):
+    import ldpc_llr_oracle as LO
+    import test_ldpc_llr_gpu as G
+    assert G.CODES == ('g12', 'builtin', 'g32', 'g384', 'g1024')
+    code = G.case(name)[0]
+    got, want = code.incidence_tables(), LO.tables(code.nlist, code.n_chk)
+    assert len(got) == len(want) == 4
+    for a, b in zip(got, want):
+        assert isinstance(a, np.ndarray) and a.dtype == np.int32 and not a.flags.writeable
+        assert a.shape == np.shape(b) and np.array_equal(a, b)
+    assert all(a is b for a, b in zip(code.incidence_tables(), got))          # memoised

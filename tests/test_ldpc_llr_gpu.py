@@ -61,10 +61,10 @@ def case(name, sum_product=False):
     return code, LO.tables(code.nlist, code.n_chk), code.layers(), received(code, 1000 + CODES.index(name), SNR_DB[name])
 
 
-def received(code, seed, snr_db):
+def received(code, seed, snr_db, words=B):
     rng = np.random.RandomState(seed)
-    gcx = 10.0 ** (np.linspace(snr_db[0], snr_db[1], B)[:, None] / 20.0)
-    y = (-gcx + rng.standard_normal((B, code.n_var))).astype(np.float32)
+    gcx = 10.0 ** (np.linspace(snr_db[0], snr_db[1], words)[:, None] / 20.0)
+    y = (-gcx + rng.standard_normal((words, code.n_var))).astype(np.float32)
     llr = ((-2.0 * gcx).astype(np.float32) * y).astype(np.float32)
     llr.setflags(write=False)
     return llr
@@ -211,6 +211,41 @@ def test_decode_llr_takes_the_code_decode_refuses(paths):
     x, viol, iters = path.decode_llr(torch.from_numpy(case('g1024')[3]).cuda(), 'min-sum', 'layered')
     assert x.shape == (B, 1024) and int((viol == 0).sum()) > 0
     assert path.decode_llr(torch.zeros(0, 1024, device='cuda'))[0].shape == (0, 1024)          # B = 0: no launch
+
+
+def test_a_code_above_48_kib_of_lds():
+    """N = 768, M = 384, E = 6144 on 256 threads: the word state (59168 B here, 57632 B in the learned forward) passes the 48 KiB
+    a kernel gets without its dynamic-LDS limit raised, which no other code of this file does (g1024: about 46 KB).  Five words at
+    4 dB, 10 iterations: in the restatement flooding min-sum decodes four (iterations 3, 4, 4, 4) and leaves one with 8 violated
+    checks, the layered schedule decodes all five; no NaN appears."""
+    from fgnn_amd import _hip
+    from fgnn_amd.datapath import LdpcDataPath
+    from fgnn_amd.ldpc_code import LdpcCode
+    from fgnn_amd.ldpc_nms import LearnedMinSum
+    code = LdpcCode.gallager(768, 8, 16, 1)
+    tabs, layers = LO.tables(code.nlist, code.n_chk), code.layers()
+    N, M, E = code.n_var, code.n_chk, len(tabs[2])
+    assert (N, M, E) == (768, 384, 6144)
+    assert int(_hip.invoke('fgnn_ldpc_decode_llr_lds_bytes', N, M, E)) == 59168 > 48 * 1024
+    assert int(_hip.invoke('fgnn_ldpc_nms_lds_bytes', N, M, E, 0)) == 57632 > 48 * 1024
+    llr = received(code, 7, (4.0, 4.0), 5)
+    path = LdpcDataPath('cuda:0', code)
+    flooding = None
+    for algorithm in ('min-sum', 'offset-min-sum'):
+        for schedule in SCHEDULES:
+            want = LO.decode(llr, tabs, layers if schedule == 'layered' else None, algorithm, 10)
+            assert not np.isnan(want['post']).any()
+            if (algorithm, schedule) == ('min-sum', 'flooding'):
+                flooding = want
+                assert (want['viol'] == 0).any() and (want['viol'] != 0).any()          # decoded and undecoded words
+            first = run(path, llr, algorithm=algorithm, schedule=schedule, max_iter=10)
+            assert_bitwise(first, want)
+            again = run(path, llr, algorithm=algorithm, schedule=schedule, max_iter=10)  # (the limit is raised once: no call now)
+            assert all(np.array_equal(a, b) for a, b in zip(first[:3], again[:3])) and np.array_equal(bits(first[3]), bits(again[3]))
+    dec = LearnedMinSum(code, 10, 'iteration', alpha=0.8125, beta=0.0).cuda()
+    for _ in range(2):
+        x, viol, iters, post = dec.decode(torch.from_numpy(np.array(llr)).cuda(), want_posteriors=True)
+        assert_bitwise((x.cpu().numpy(), viol.cpu().numpy(), iters.cpu().numpy(), post.cpu().numpy()), flooding)
 
 
 class _Zero(torch.nn.Module):
