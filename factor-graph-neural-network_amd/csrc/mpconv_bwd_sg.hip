@@ -568,7 +568,8 @@ int fgnn_bwd_sg_rules(const FgnnBwdCall& c, const FgnnSwitches& sw, bool layout_
     pl->fn = nullptr;
     if (KC == 6 && NPW <= 6 && DPW <= 3 && GSL == 1) pl->fn = (void*)mpconv_bwd_sg_kernel<6, 3, 6, 3, 1>;
     else if (KC == 3 && NPW <= 3 && DPW <= 6) pl->fn = GSL == 1 ? (void*)mpconv_bwd_sg_kernel<3, 6, 3, 6, 1> : (void*)mpconv_bwd_sg_kernel<3, 6, 3, 6, 2>;
-    if (!pl->fn) FGNN_REJECT("sg backward", 14);
+    // (no instance — k = 3 with more than 48 nodes: 3 per wave — is rule 14 of fgnn_bwd_sg_plan, not of the shared rules: the ws
+    // backward has its own node limit, 64 for k = 3, and picks its own kernel)
     pl->mode = GSL;
     pl->split = split ? 1 : 0;
     return 1;
@@ -597,6 +598,7 @@ static int bs_layout(const fgnn_mpconv_desc* d, BsParams* p) {
 int fgnn_bwd_sg_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
     const int r = fgnn_bwd_sg_rules(c, sw, false, pl);
     if (r <= 0) return r;
+    if (!pl->fn) FGNN_REJECT("sg backward", 14);
     BsParams p;
     pl->lds = bs_layout(c.d, &p);
     if (pl->lds > 160 * 1024) FGNN_REJECT("sg backward", 15);

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
     static_assert(NL % 16 == 0 && NL <= LY::NMAX && (NL / 8) % NPG == 0, "NL");
     constexpr int NG = NL / NPG / 8;                  // detype tiles per wave
     constexpr int NSLOT = KC == 3 ? 2 : 1;            // staging items per staging thread (8 M <= 768 / 384 items, 384 staging threads)
-    constexpr int ESLOT = 1;                          // in-edge slots per staging thread (N QS <= 384)
+    constexpr int ESLOT = (NL * QS + 383) / 384;      // in-edge slots per staging thread: N QS <= 384 but for k = 3 with 49..64 nodes (512)
     constexpr int MAXNPW = NL / 8;                    // source nodes per wave in the dP phase (a multiple of 16 / QS: the dP read patterns below)
     const int tid = threadIdx.x;
     BW_STAMP_G(0);

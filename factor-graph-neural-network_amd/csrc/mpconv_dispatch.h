@@ -90,7 +90,8 @@ int fgnn_bwd_res_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl
 int fgnn_bwd_res_launch(const FgnnBwdCall& c, const FgnnPlan& pl);
 // The shared-graph rules the sg and ws backward both need (mpconv_bwd_sg.hip).  layout_only: the family and layout rules (off
 // switch, dtype / aggregator, degree, batch-shared table, operands present, strides); otherwise also widths, sizes, in-degree,
-// alignment, workspace and the sg kernel choice (pl->fn, pl->mode = its GSL, pl->split = 64 -> 128 as two launches).
+// alignment, workspace and the sg kernel choice (pl->fn — NULL where the sg family has no instance for the size, which only its
+// own plan rejects —, pl->mode = its GSL, pl->split = 64 -> 128 as two launches).
 int fgnn_bwd_sg_rules(const FgnnBwdCall& c, const FgnnSwitches& sw, bool layout_only, FgnnPlan* pl);
 
 // ---- shared helpers ----

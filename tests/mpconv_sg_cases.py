@@ -1,0 +1,360 @@
+"""Irregular and ragged shared graphs for the operator backward's two fast kernel families (csrc/mpconv_bwd_sg.hip, csrc/mpconv_bwd_ws.hip):
+the table generator, the two references and the case list that tests/test_mpconv_sg_cases.py (CPU) and
+tests/test_mpconv_sg_irregular_gpu.py (GPU) share.  A helper module like the ``*_oracle.py`` files, not a test module.
+
+Both families build a transposed incidence of the batch-shared neighbour table in LDS (per-node in-edge slots, padding entries for the
+unused ones) and trust the caller's in-degree bound DEG (3 for k = 6, 6 for k = 3).  ``bounded_table`` prescribes the in-degree profile:
+nodes nobody lists, nodes below DEG next to nodes at DEG; ``with_tied_rows`` lists one node twice in a destination's row.
+
+Layouts used throughout (the natural ones, channel / edge type last): x [B, N, nin], et [B, M, k, net], gz / z [B, M, nou],
+W [nin, nou * net] (column o * net + e), idx [1, M, k].
+
+Run as a program (``python tests/mpconv_sg_cases.py --set switch --B 37``) it runs a list of cases on the device in order, stops at the
+first exception and prints one JSON line per case and reference: how tests/test_mpconv_sg_irregular_gpu.py reaches the older kernel
+generations behind ``FGNN_NO_WS=1``, a switch that is read once per process."""
+import json
+import os
+import sys
+
+import torch
+
+NET = 4
+DEG = {6: 3, 3: 6}                      # destination degree k -> in-edge slots per source node the fast kernels are built for
+TOL = 2.0 ** -6                         # the project's bound for these kernels: P, dP and the outputs are rounded to bf16
+FIRM = 2.0 ** -7                        # (see firm_outputs)
+TIE_EVERY = 5
+
+# (family the plan must choose, suffix of the kernel name, (nin, nou, N, M, k))
+CASES = [
+    ('mpconv_bwd_ws', '', (64, 64, 96, 40, 6)), ('mpconv_bwd_ws', '', (64, 64, 91, 45, 6)), ('mpconv_bwd_ws', '', (64, 64, 33, 7, 6)),
+    ('mpconv_bwd_ws', '', (64, 64, 40, 1, 6)),
+    ('mpconv_bwd_ws', '', (64, 64, 37, 60, 3)), ('mpconv_bwd_ws', '', (64, 64, 17, 30, 3)),                  # the N <= 48 variant
+    ('mpconv_bwd_ws', '', (64, 64, 64, 96, 3)), ('mpconv_bwd_ws', '', (64, 64, 50, 64, 3)),                  # the N > 48 variant
+    ('mpconv_bwd_ws', ' x2', (64, 128, 91, 40, 6)), ('mpconv_bwd_ws', ' x2', (64, 128, 37, 60, 3)),
+    ('mpconv_bwd_ws', ' k2', (128, 64, 91, 40, 6)), ('mpconv_bwd_ws', ' k2', (128, 64, 37, 60, 3)),
+    ('mpconv_bwd_ws', ' k2', (128, 64, 50, 64, 3)),                                                         # N > 48 in two launches
+    ('mpconv_bwd_sg', '', (64, 64, 48, 95, 3)), ('mpconv_bwd_sg', '', (64, 64, 37, 71, 3)), ('mpconv_bwd_sg', ' x2', (64, 128, 37, 71, 3)),   # M k odd
+]
+# in a process started with FGNN_NO_WS=1: the second generation on the third's shapes; 128 -> 64 has no sg form
+SWITCH_CASES = [
+    ('mpconv_bwd_sg', '', (64, 64, 96, 40, 6)), ('mpconv_bwd_sg', '', (64, 64, 33, 7, 6)), ('mpconv_bwd_sg', ' x2', (64, 128, 91, 40, 6)),
+    ('mpconv_bwd_b16', '', (128, 64, 91, 40, 6)),
+]
+BATCHES = [37, 257]                     # 257: the grid cap of 256 gives workgroups of 2 samples and a last workgroup of 1
+
+# Per-node / per-edge yardstick (tests/test_mpconv_sg_cases.py::test_rounding_model_error measures it, and asserts these values hold):
+# the routed reference evaluated once more with P and dP rounded to bf16 and gx / getype rounded to bf16 -- the rounding points the two
+# kernel headers name -- against the unrounded one, every CASES entry at B = 37, tied rows in.  Worst node of gx, each node's error over
+# that node's own reference range over the batch; worst edge of getype likewise.
+D_NODE = 4.7e-3                        # measured 4.6421e-03 (64x128x91x40x6 x2)
+D_EDGE = 6.0e-3                        # measured 5.9725e-03 (64x64x96x40x6)
+
+
+def case_id(case):
+    return 'x'.join(map(str, case[2])) + case[1].replace(' ', '_')
+
+
+def empties_for(N, M, k):
+    """How many nodes a case's table leaves without in-edges: 2 or 1 where M k still fits under the cap with room to spare, else
+    where it fits at all, else none."""
+    cap = DEG[k]
+    for strict in (True, False):
+        for empty in (2, 1):
+            room = (N - empty) * cap - M * k
+            if room > 0 or (room == 0 and not strict):
+                return empty
+    return 0
+
+
+def bounded_table(N, M, k, deg_cap, gen, empty):
+    """A shared neighbour table [1, M, k] with a prescribed in-degree profile, and the in-degree vector [N]: ``empty`` nodes nobody
+    lists, at least one node listed exactly ``deg_cap`` times, no node more often, the others spread below the cap (at least three
+    distinct degrees where M k leaves room for them).  Needs M k <= (N - empty) deg_cap."""
+    E = M * k
+    assert 0 < E <= (N - empty) * deg_cap, (N, M, k, deg_cap, empty)
+    live = torch.randperm(N, generator=gen)[empty:]
+    deg = torch.zeros(N, dtype=torch.long)
+    deg[live[0]] = min(deg_cap, E)
+    while int(deg.sum()) < E:
+        n = int(live[int(torch.randint(0, len(live), (1,), generator=gen))])
+        if deg[n] < deg_cap:
+            deg[n] += 1
+    # fewer than three distinct degrees: split a pair of equals (d, d -> d - 1, d + 1), or level a capped node with a low one
+    for _ in range(4):
+        if len(torch.unique(deg)) >= 3:
+            break
+        moved = False
+        for d in range(deg_cap - 1, 1, -1):
+            at = (deg == d).nonzero().flatten()
+            if len(at) >= 2:
+                deg[at[0]] -= 1
+                deg[at[1]] += 1
+                moved = True
+                break
+        if not moved:
+            top, low = (deg == deg_cap).nonzero().flatten(), ((deg > 0) & (deg <= deg_cap - 3)).nonzero().flatten()
+            if len(top) >= 2 and len(low) >= 1:
+                deg[top[0]] -= 1
+                deg[low[0]] += 1
+                moved = True
+        if not moved:
+            break
+    slots = torch.arange(N).repeat_interleave(deg)[torch.randperm(E, generator=gen)]
+    return slots.reshape(1, M, k), deg
+
+
+def with_tied_rows(idx, et, every):
+    """Rows ``::every`` list the node of slot 0 again in slot k - 1, with the same edge-type row: two messages that tie exactly.  The
+    entry of slot k - 1 is SWAPPED with another position of the table that holds that node, so the in-degree profile stays; a row whose
+    first node is listed nowhere else stays as it is.  Returns (idx, et, the tied rows).  For the routed reference only: under the
+    oracle's own routing an exact tie is a coin flip."""
+    idx, et = idx.clone(), et.clone()
+    M, k = idx.shape[1], idx.shape[2]
+    flat = idx[0].reshape(-1)
+    rows = list(range(0, M, every))
+    pinned = set(r * k for r in rows) | set(r * k + k - 1 for r in rows)          # slots a tie depends on, this row's and the others'
+    tied = []
+    for r in rows:
+        n = int(flat[r * k])
+        if int(flat[r * k + k - 1]) != n:
+            where = [p for p in (flat == n).nonzero().flatten().tolist() if p not in pinned]
+            if not where:
+                continue
+            p = where[0]
+            flat[p], flat[r * k + k - 1] = flat[r * k + k - 1].clone(), flat[p].clone()
+        et[:, r, k - 1, :] = et[:, r, 0, :]
+        tied.append(r)
+    return idx, et, tied
+
+
+def problem(shape, B, tied=False, seed=0):
+    """The inputs of one case as CPU tensors (bf16 values held as bf16; W holds bf16 values in f32): a dict."""
+    nin, nou, N, M, k = shape
+    g = torch.Generator().manual_seed(seed + 1000 + N + 7 * M + 13 * nou + nin + B)
+    empty = empties_for(N, M, k)
+    idx, deg = bounded_table(N, M, k, DEG[k], g, empty)
+    x = torch.randn(B, N, nin, generator=g).bfloat16()
+    et = torch.randn(B, M, k, NET, generator=g).bfloat16()
+    W = (torch.randn(nin, nou * NET, generator=g) * 0.1).bfloat16().float()      # what the bf16 matrix cores multiply by
+    bias = torch.randn(nou, generator=g)
+    gz = torch.randn(B, M, nou, generator=g).bfloat16()
+    rows = []
+    if tied:
+        idx, et, rows = with_tied_rows(idx, et, TIE_EVERY)
+    return dict(shape=shape, B=B, x=x, idx=idx, et=et, W=W, bias=bias, gz=gz, deg=deg, empty=empty, tied=rows)
+
+
+def in_degree(idx, N):
+    return torch.bincount(idx[0].reshape(-1), minlength=N)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# references
+# ----------------------------------------------------------------------------------------------------------------------------------
+def messages(x, idx, et, W, nou):
+    """(P [B, N, nou, net], E [B, M, k, nou]) in the dtype of the inputs: the projections and the per-slot messages."""
+    B, N = x.shape[0], x.shape[1]
+    P = torch.einsum('bnc,cq->bnq', x, W).reshape(B, N, nou, et.shape[-1])
+    return P, (P[:, idx[0]] * et[:, :, :, None, :]).sum(-1)
+
+
+def first_argmax(E):
+    """[B, M, nou]: the first slot that holds each output's largest message (the kernels' rule for exact ties)."""
+    k = E.shape[2]
+    slot = torch.arange(k)[None, None, :, None].expand_as(E)
+    return torch.where(E == E.amax(2, keepdim=True), slot, torch.full_like(slot, k)).amin(2)
+
+
+def routed_reference(x, idx, et, W, bias, gz, sel, dtype=torch.float32):
+    """Torch autograd through a GIVEN routing ``sel`` [B, M, nou] (the slot every output takes its maximum from: the kernel's own
+    argmax), in ``dtype`` on the given values.  Returns (z, gx, getype, gW, gbias)."""
+    nou = gz.shape[-1]
+    xr, er = x.to(dtype).clone().requires_grad_(True), et.to(dtype).clone().requires_grad_(True)
+    Wr, br = W.to(dtype).clone().requires_grad_(True), bias.to(dtype).clone().requires_grad_(True)
+    _, E = messages(xr, idx, er, Wr, nou)
+    zr = E.gather(2, sel.long()[:, :, None, :])[:, :, 0, :] + br[None, None, :]
+    zr.backward(gz.to(dtype))
+    return zr.detach(), xr.grad, er.grad, Wr.grad, br.grad
+
+
+def routed_by_hand(x, idx, et, W, gz, sel, rounded):
+    """The same four gradients written out (f32), optionally with the kernels' rounding points: P and dP held as bf16, gx and getype
+    stored as bf16.  Unrounded it equals ``routed_reference`` (asserted on the CPU); rounded it is the model D_NODE / D_EDGE come from."""
+    rb = (lambda t: t.bfloat16().float()) if rounded else (lambda t: t)
+    B, N, nin = x.shape
+    M, k = idx.shape[1], idx.shape[2]
+    nou, net = gz.shape[-1], et.shape[-1]
+    xf, ef, gf = x.float(), et.float(), gz.float()
+    P = rb(torch.einsum('bnc,cq->bnq', xf, W).reshape(B, N, nou, net))
+    G = gf[:, :, None, :] * (sel.long()[:, :, None, :] == torch.arange(k)[None, None, :, None])       # [B, M, k, nou]
+    get = rb(torch.einsum('bmjo,bmjoe->bmje', G, P[:, idx[0]]))
+    dP = torch.zeros(B, N, nou, net)
+    dP.index_add_(1, idx[0].reshape(-1), (G[..., None] * ef[:, :, :, None, :]).reshape(B, M * k, nou, net))
+    dP = rb(dP).reshape(B, N, nou * net)
+    gx = rb(torch.einsum('bnq,cq->bnc', dP, W))
+    gW = torch.einsum('bnc,bnq->cq', xf, dP)
+    return gx, get, gW, gf.sum((0, 1))
+
+
+def firm_outputs(x, idx, et, W, nou):
+    """[B, M, nou] bool: outputs whose best two messages lie further apart than the bf16 rounding of P can move them (P is rounded to
+    bf16, 2^-9 relative per term, before the 4-term edge-type contraction).  On the others two correct implementations may route
+    differently."""
+    P, E = messages(x.float(), idx, et.float(), W, nou)
+    if E.shape[2] < 2:
+        return torch.ones(E.shape[0], E.shape[1], nou, dtype=torch.bool)
+    top2 = E.topk(2, dim=2)[0]
+    mag = (P[:, idx[0]].abs() * et.float().abs()[:, :, :, None, :]).sum(-1).amax(dim=2)
+    return (top2[:, :, 0] - top2[:, :, 1]) > FIRM * mag
+
+
+def oracle_reference(x, idx, et, W, bias, gz, dtype=torch.float32):
+    """The ORACLE's autograd (``fgnn_oracle.mp_conv``, reference op order) routed by the oracle's own maxima.  Returns
+    (z, gx, getype, gW, gbias) in this module's layouts."""
+    import fgnn_oracle as O
+    B, nou = x.shape[0], gz.shape[-1]
+    xo = x.to(dtype).permute(0, 2, 1)[:, :, :, None].contiguous().requires_grad_(True)       # [B, nin, N, 1]
+    eo = et.to(dtype).permute(0, 3, 1, 2).contiguous().requires_grad_(True)                  # [B, net, M, k]
+    sd = {'filters': W.to(dtype).clone().requires_grad_(True), 'bias': bias.to(dtype).clone().requires_grad_(True)}
+    zo = O.mp_conv(sd, '', xo, idx.expand(B, -1, -1).contiguous(), eo, nou=nou, net=et.shape[-1], extension=0, aggregator='max',
+                   relu=False)
+    zo.backward(gz.to(dtype).permute(0, 2, 1)[:, :, :, None])
+    return (zo.detach()[:, :, :, 0].permute(0, 2, 1), xo.grad[:, :, :, 0].permute(0, 2, 1), eo.grad.permute(0, 2, 3, 1),
+            sd['filters'].grad, sd['bias'].grad)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# the device side
+# ----------------------------------------------------------------------------------------------------------------------------------
+def device_backward(x, idx, et, W, bias, gz, dev, idx_dev=None):
+    """Forward and backward of the operator on the device: (z, argmax [B, M, nou], gx, getype, gW, gbias, kernel name of the
+    backward), tensors on the CPU in this module's layouts (z / gx / getype as the bf16 the kernels stored, held in f32).
+    ``idx_dev``: a device table [1, M, k] to use (and keep the remembered verdicts of) instead of a fresh copy of ``idx``."""
+    from fgnn_amd import _hip, ops
+    B, nou = x.shape[0], gz.shape[-1]
+    xd = x.to(dev)[:, :, None, :].permute(0, 3, 1, 2).requires_grad_(True)                   # [B, nin, N, 1], channel-fastest
+    etd = et.to(dev).permute(0, 3, 1, 2).requires_grad_(True)                                # [B, net, M, k], edge-type fastest
+    idxd = (idx.to(dev) if idx_dev is None else idx_dev).expand(B, -1, -1)
+    Wd, bd = W.to(dev).requires_grad_(True), bias.to(dev).requires_grad_(True)
+    z = ops.mpconv(xd, idxd, etd, Wd, bd, nou, et.shape[-1], 0, _hip.AGG_MAX)
+    _, am = ops.mpconv_forward_raw(xd.detach(), idxd, etd.detach(), W.to(dev), bias.to(dev), nou, et.shape[-1], 0, _hip.AGG_MAX,
+                                   want_argmax=True)
+    z.backward(gz.to(dev)[:, :, None, :].permute(0, 3, 1, 2))
+    kern = _hip.lib().fgnn_last_kernel().decode()
+    nat = lambda t: t.detach().float().cpu()[:, :, :, 0].permute(0, 2, 1)
+    return (nat(z), am.cpu().long()[:, :, :, 0].permute(0, 2, 1), nat(xd.grad), etd.grad.float().cpu().permute(0, 2, 3, 1),
+            Wd.grad.cpu(), bd.grad.cpu(), kern)
+
+
+def rel_err(a, b):
+    """helpers.rel_err: the largest error over the reference's range (at least 1)."""
+    a, b = a.detach().double(), b.detach().double()
+    return float((a - b).abs().max()) / max(1.0, float(b.abs().max())) if a.numel() else 0.0
+
+
+def per_row_error(a, b, dims):
+    """(worst row's error, rows whose reference is all zero but ``a`` is not): every row's largest error over that ROW's own reference
+    range, rows = what is left of the tensors after reducing ``dims``."""
+    err, rng = (a.double() - b.double()).abs().amax(dims), b.double().abs().amax(dims)
+    live = rng > 0
+    worst = float((err[live] / rng[live]).max()) if bool(live.any()) else 0.0
+    return worst, int((err[~live] != 0).sum())
+
+
+def run_case(case, B, dev, ref, tables=None):
+    """One case on the device against one reference: 'oracle' (the oracle's own routing, no forced ties, gz zeroed off the firm
+    outputs) or 'routed' (the kernel's own argmax, tied rows, every gz live).  Returns a dict of plain numbers: the kernel name, the
+    error of z and of each gradient over that tensor's range, and for 'routed' the per-node / per-edge errors and the exactness counts."""
+    family, suffix, shape = case
+    nin, nou, N, M, k = shape
+    q = problem(shape, B, tied=(ref == 'routed'))
+    x, idx, et, W, bias, gz = q['x'], q['idx'], q['et'], q['W'], q['bias'], q['gz']
+    out = dict(case=case_id(case), B=B, ref=ref, family=family, suffix=suffix, max_in_degree=int(in_degree(idx, N).max()))
+    if ref == 'oracle':
+        firm = firm_outputs(x, idx, et, W, nou)
+        out['firm'] = float(firm.float().mean())
+        gz = (gz.float() * firm).bfloat16()
+    if tables is not None:
+        from fgnn_amd import ops
+        was, ops.BACKWARD_TABLES = ops.BACKWARD_TABLES, tables
+    idx_dev = idx.to(dev)
+    try:
+        z, am, gx, get, gW, gb, kern = device_backward(x, idx, et, W, bias, gz, dev, idx_dev=idx_dev)
+    finally:
+        if tables is not None:
+            ops.BACKWARD_TABLES = was
+    out['kern'] = kern
+    out['built_tables'] = getattr(idx_dev, '_fgnn_bwd_tables', (None, None))[1] is not None       # (remembered on the table's owner)
+    if ref == 'oracle':
+        r = oracle_reference(x, idx, et, W, bias, gz)
+    else:
+        r = routed_reference(x, idx, et, W, bias, gz, am)
+    for name, a, b in zip(('z', 'gx', 'getype', 'gW', 'gbias'), (z, gx, get, gW, gb), r):
+        out['err_' + name] = rel_err(a, b)
+    if ref == 'routed':
+        deg = in_degree(idx, N)
+        out['empty_nodes'] = int((deg == 0).sum())
+        out['gx_nonzero_on_empty'] = int((gx[:, deg == 0, :].view(torch.int32) != 0).sum())       # every bit: -0.0 counts
+        out['gx_finite'] = bool(torch.isfinite(gx).all())
+        out['node_err'], out['node_stray'] = per_row_error(gx, r[1], (0, 2))
+        out['edge_err'], out['edge_stray'] = per_row_error(get, r[2], (0, 3))
+        rows = q['tied']
+        out['tied_rows'] = len(rows)
+        if rows:
+            pair = lambda t: t[:, rows][:, :, [0, k - 1], :]
+            dv, rf = pair(get), pair(r[2])
+            out['tied_err'] = float((dv - rf).abs().max()) / max(1.0, float(r[2].abs().max()))
+            differ = rf[:, :, 0, :] != rf[:, :, 1, :]
+            same = differ & (dv[:, :, 0, :] == dv[:, :, 1, :])
+            out['tied_differ'] = int(differ.sum())
+            out['tied_nonzero_where_reference_is_zero'] = int(((rf == 0) & (dv != 0)).sum())
+            out['tied_same_where_reference_differs'] = int(same.sum())
+            out['tied_same_and_not_zero'] = int((same & (dv[:, :, 0, :] != 0)).sum())
+    out['grads'] = (gx, get, gW, gb)
+    return out
+
+
+def check(out, node_bound=None, edge_bound=None):
+    """The assertions every run shares, on a ``run_case`` result (or its JSON form): the family, the bounds."""
+    kern = out['kern']
+    assert out['family'] in kern and kern.endswith(' x2') == (out['suffix'] == ' x2') and kern.endswith(' k2') == (out['suffix'] == ' k2'), out
+    if out['ref'] == 'oracle':
+        assert out['firm'] > 0.9, out
+    for name in ('z', 'gx', 'getype', 'gW', 'gbias'):
+        assert out['err_' + name] <= TOL, (name, out['err_' + name], kern, out['case'])
+    if out['ref'] == 'routed':
+        assert out['gx_finite'] and out['gx_nonzero_on_empty'] == 0, out
+        assert out['node_stray'] == 0 and out['edge_stray'] == 0, out
+        if out['tied_rows']:
+            # the slot the argmax names gets the gradient, the other tied slot exactly nothing: the two differ wherever the reference's
+            # do.  The two-launch forms add two bf16 partial results in the named slot, which can cancel to an exact zero (measured:
+            # 1 to 15 of the 8224 tied entries at B = 257) -- allowed there, and only as zeros; the per-edge bound holds their size.
+            assert out['tied_err'] <= TOL and out['tied_nonzero_where_reference_is_zero'] == 0, out
+            assert out['tied_same_and_not_zero'] == 0, out
+            if not out['suffix'] and 'mpconv_bwd_b16' not in kern:
+                assert out['tied_same_where_reference_differs'] == 0, out
+        if node_bound is not None:
+            assert out['node_err'] <= node_bound and out['edge_err'] <= edge_bound, out
+
+
+def _main(argv):
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--set', choices=['cases', 'switch'], default='cases')
+    ap.add_argument('--B', type=int, default=37)
+    ap.add_argument('--refs', default='oracle,routed')
+    a = ap.parse_args(argv)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for p in (os.path.join(root, 'factor-graph-neural-network_amd'), os.path.join(root, 'oracle'), os.path.join(root, 'tests'), root):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    dev = torch.device('cuda:0')
+    for case in (SWITCH_CASES if a.set == 'switch' else CASES):
+        for ref in a.refs.split(','):
+            out = run_case(case, a.B, dev, ref)
+            out.pop('grads')
+            print(json.dumps(out), flush=True)
+
+
+if __name__ == '__main__':
+    _main(sys.argv[1:])

@@ -8,6 +8,7 @@ import torch
 
 import fgnn_oracle as O
 import helpers as H
+import mpconv_sg_cases as C
 
 pytestmark = pytest.mark.gpu
 
@@ -211,19 +212,13 @@ def test_sg_backward_vs_routed_reference(shape, B, dev):
     z.backward(gz.to(dev).permute(0, 3, 1, 2))
     kern = _hip.lib().fgnn_last_kernel().decode()          # third generation (mpconv_bwd_ws.hip) where it tiles, else the second
     assert 'mpconv_bwd_ws' in kern or 'mpconv_bwd_sg' in kern, kern
-    xr = x[:, :, 0, :].float().clone().requires_grad_(True)                                # [B,N,nin]
-    er = et.float().clone().requires_grad_(True)                                           # [B,M,k,net]
-    Wr, br = W.clone().requires_grad_(True), bias.clone().requires_grad_(True)
-    P = torch.einsum('bnc,cq->bnq', xr, Wr).reshape(B, N, nou, net)
-    E = (P[:, idx[0]] * er[:, :, :, None, :]).sum(-1)                                      # [B,M,k,nou]
-    sel = am.cpu().long()[..., 0].permute(0, 2, 1)[:, :, None, :]                          # [B,M,1,nou]
-    zr = E.gather(2, sel)[:, :, 0, :] + br[None, None, :]                                  # [B,M,nou]
-    zr.backward(gz[:, :, 0, :].float())
+    sel = am.cpu().long()[..., 0].permute(0, 2, 1)                                          # [B,M,nou]
+    _, gxr, ger, gWr, gbr = C.routed_reference(x[:, :, 0, :], idx, et, W, bias, gz[:, :, 0, :], sel)      # (tests/mpconv_sg_cases.py)
     tol = 2.0 ** -6
-    assert H.rel_err(xd.grad.float().permute(0, 2, 3, 1)[:, :, 0, :], xr.grad) <= tol
-    assert H.rel_err(etd.grad.float().permute(0, 2, 3, 1), er.grad) <= tol
-    assert H.rel_err(Wd.grad, Wr.grad) <= tol
-    assert H.rel_err(bd.grad, br.grad) <= tol
+    assert H.rel_err(xd.grad.float().permute(0, 2, 3, 1)[:, :, 0, :], gxr) <= tol
+    assert H.rel_err(etd.grad.float().permute(0, 2, 3, 1), ger) <= tol
+    assert H.rel_err(Wd.grad, gWr) <= tol
+    assert H.rel_err(bd.grad, gbr) <= tol
 
 
 # (nin, nou, N, M, k): the second-generation backward (64 -> 64) and the wide shapes of LDPCModel's layers 2 / 6
@@ -261,21 +256,11 @@ def _backward_vs_oracle_autograd(shape, B, dev):
     W = (torch.randn(nin, nou * net, generator=g) * 0.1).bfloat16().float()     # what the bf16 matrix cores multiply by
     bias = torch.randn(nou, generator=g)
     gz = torch.randn(B, M, 1, nou, generator=g).bfloat16()
-    # messages in f32 (reference order), gap between the best two per output
-    P = torch.einsum('bnc,cq->bnq', x[:, :, 0, :].float(), W).reshape(B, N, nou, net)
-    E = (P[:, idx[0]] * et.float()[:, :, :, None, :]).sum(-1)                              # [B,M,k,nou]
-    top2 = E.topk(2, dim=2)[0]
-    # what bf16 cannot resolve: P is rounded to bf16 (2^-9 relative per term) before the 4-term edge-type contraction
-    mag = (P[:, idx[0]].abs() * et.float().abs()[:, :, :, None, :]).sum(-1).amax(dim=2)    # [B,M,nou]
-    firm = (top2[:, :, 0] - top2[:, :, 1]) > 2.0 ** -7 * mag
+    # the outputs whose best two f32 messages bf16 can tell apart, and the oracle's autograd on them (tests/mpconv_sg_cases.py)
+    firm = C.firm_outputs(x[:, :, 0, :], idx, et, W, nou)
     assert float(firm.float().mean()) > 0.9, float(firm.float().mean())
     gz = (gz[:, :, 0, :].float() * firm).bfloat16()[:, :, None, :]
-    xo = x.permute(0, 3, 1, 2).float().contiguous().requires_grad_(True)                   # [B,nin,N,1]
-    eo = et.permute(0, 3, 1, 2).float().contiguous().requires_grad_(True)                  # [B,net,M,k]
-    sd = {'filters': W.clone().requires_grad_(True), 'bias': bias.clone().requires_grad_(True)}
-    zo = O.mp_conv(sd, '', xo, idx.expand(B, -1, -1).contiguous(), eo, nou=nou, net=net, extension=0, aggregator='max',
-                   relu=False)
-    zo.backward(gz.permute(0, 3, 1, 2).float())
+    zo, gxo, geo, gWo, gbo = C.oracle_reference(x[:, :, 0, :], idx, et, W, bias, gz[:, :, 0, :])      # [B,M,nou], [B,N,nin], [B,M,k,net]
     xd = x.to(dev).permute(0, 3, 1, 2).requires_grad_(True)
     etd = et.to(dev).permute(0, 3, 1, 2).requires_grad_(True)
     Wd, bd = W.to(dev).requires_grad_(True), bias.to(dev).requires_grad_(True)
@@ -288,12 +273,12 @@ def _backward_vs_oracle_autograd(shape, B, dev):
             assert 'mpconv_bwd_ws' in kern, kern
     else:               # 128 -> 64 (round 5): the third-generation kernel, two launches over the halves of the input channels
         assert 'mpconv_bwd_ws' in kern and kern.endswith(' k2'), kern
-    assert H.rel_err(z.float(), zo) <= 2.0 ** -6
+    assert H.rel_err(z.float()[:, :, :, 0].permute(0, 2, 1), zo) <= 2.0 ** -6
     tol = 2.0 ** -6
-    assert H.rel_err(xd.grad.float(), xo.grad) <= tol, kern
-    assert H.rel_err(etd.grad.float(), eo.grad) <= tol, kern
-    assert H.rel_err(Wd.grad, sd['filters'].grad) <= tol, kern
-    assert H.rel_err(bd.grad, sd['bias'].grad) <= tol, kern
+    assert H.rel_err(xd.grad.float()[:, :, :, 0].permute(0, 2, 1), gxo) <= tol, kern
+    assert H.rel_err(etd.grad.float().permute(0, 2, 3, 1), geo) <= tol, kern
+    assert H.rel_err(Wd.grad, gWo) <= tol, kern
+    assert H.rel_err(bd.grad, gbo) <= tol, kern
 
 
 def test_sg_backward_is_bitwise_reproducible_and_matches_first_generation(dev, monkeypatch):
