@@ -34,7 +34,7 @@
 // sample: the phases are short dependent chains with two waves per SIMD to hide them) against ~300 us for the dozen kernels
 // it replaces — the inference forward goes from 4.92 to 4.78 ms, and from 0.98 to 0.83 ms at 64 codewords where launches
 // dominate.  HBM would allow 21 us: the next step is a software pipeline over samples (projection of sample s + 1 under
-// the gather of sample s, as csrc/mpconv_fwd_sg.hip does for the bare operator).
+// the gather of sample s, as the producer and consumer waves of csrc/mpconv_fwd_ws.hip do for the bare operator).
 #include "fgnn_common.h"
 #include "fgnn_device.h"
 #include <stdlib.h>

@@ -24,7 +24,7 @@
 //
 // SCOPE (round 2): this file is the fallback for shapes no specialised kernel takes — odd channel counts, per-sample graphs
 // with an extension, per-sample edge-type gradients, the `mean` aggregator.  Every call of the reference's models goes
-// elsewhere: the LDPC family to mpconv_bwd_sg / _b16 / _res / _hyper.hip, the synthetic-PGM family (16 edge types,
+// elsewhere: the LDPC family to mpconv_bwd_ws / _b16 / _res / _hyper.hip, the synthetic-PGM family (16 edge types,
 // DIFF / NEIGHBOR, max and softmax, 2..64 output channels) to mpconv_bwd_ext.hip.  Like those, this kernel is free of
 // atomics (tests/test_mpconv_gpu.py::test_generic_backward_is_bitwise_reproducible).
 #include "fgnn_common.h"
@@ -537,9 +537,8 @@ static int generic_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
 static const struct { FgnnBwdPlanFn plan; FgnnBwdLaunchFn launch; } kBwdFamilies[] = {
     {fgnn_bwd_ext_plan, fgnn_bwd_ext_launch},         // f32 synthetic-PGM calls
     {fgnn_bwd_hyper_plan, fgnn_bwd_hyper_launch},     // hyper-edge calls: fan-in / fan-out
-    {fgnn_bwd_ws_plan, fgnn_bwd_ws_launch},           // bf16 LDPC parity calls: third generation
-    {fgnn_bwd_sg_plan, fgnn_bwd_sg_launch},           //   second generation
-    {fgnn_bwd_b16_plan, fgnn_bwd_b16_launch},         //   first generation
+    {fgnn_bwd_ws_plan, fgnn_bwd_ws_launch},           // bf16 LDPC parity calls: batch-shared table, even M k
+    {fgnn_bwd_b16_plan, fgnn_bwd_b16_launch},         //   every other one (per-sample tables, odd M k, FGNN_NO_WS)
     {fgnn_bwd_res_plan, fgnn_bwd_res_launch},         // W resident in LDS
     {generic_plan, generic_launch},
 };

@@ -1,7 +1,9 @@
 // mpconv_bwd_ws.hip — third-generation backward of the VF/FV message operator for the LDPC parity-check calls: bf16
 // channel-fastest x / gz / etype, 64 -> 64 channels, 4 edge types, max aggregation, degree 3 / 6, ONE neighbour table shared
-// by the batch whose transposed incidence has in-degree <= 3 / 6.  Same maths and rounding points as mpconv_bwd_sg.hip
-// (autograd through /root/reference/lib/model/mpnn/mp_nn.py:115-175):
+// by the batch whose transposed incidence has in-degree <= 3 / 6.  The maths is autograd through
+// /root/reference/lib/model/mpnn/mp_nn.py:115-175; the rounding points are those of mpconv_bwd_b16.hip: x, gz and etype arrive
+// as bf16, the recomputed P and dP are rounded to bf16 (2^-9 relative) before they feed the matrix cores, every sum is f32, gx
+// and getype are rounded to bf16 once per launch, dW and dbias stay f32:
 //
 //     G[(n,q),o]    = gz[m,o] [j == argmax[m,o]]   for the q-th in-edge (m, j) of source node n     (bf16, exact)
 //     P[n,o,e]      = sum_c x[n,c] W[c,o*4+e]                                                      (recomputed, bf16)
@@ -757,17 +759,33 @@ __global__ __launch_bounds__(BW_THREADS) void mpconv_bwd_ws_kernel(const BwParam
 // ----------------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------------
-// Does this descriptor go to the kernel above, and with how many table entries?  (The shape rules of fgnn_bwd_ws_plan that do
-// not depend on pointers.)
-static int bw_tables_count(const fgnn_mpconv_desc* d) {
-    if (fgnn_switches().no_ws || d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->net != 4 || d->agg != FGNN_AGG_MAX) return 0;
-    if (d->nin != 64 || (d->nou != 64 && d->nou != 128) || (d->k != 3 && d->k != 6)) return 0;
-    if (d->idx_sb != 0 && d->B > 1) return 0;
-    if (!(d->idx_sk == 1 && d->idx_sm == d->k)) return 0;
+// The rules of fgnn_bwd_ws_plan that need no pointer, i.e. everything the descriptor decides but the in-degree bound (d->reserved):
+// 1 = the kernel above takes this shape.  fgnn_bwd_ws_plan and bw_tables_count both ask here, so the per-graph tables are sized for
+// exactly the descriptors the plan accepts.
+static int bw_shape(const fgnn_mpconv_desc* d, const FgnnSwitches& sw) {
+    if (sw.no_ws) FGNN_REJECT("ws backward", 0);
+    if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->agg != FGNN_AGG_MAX || d->net != 4) FGNN_REJECT("ws backward", 1);
     const int KC = d->k;
-    if (KC == 6 ? (d->N > 96 || d->M > 48) : (d->N > 64 || d->M > 96)) return 0;
-    if ((d->M * KC) & 1) return 0;
-    return (KC == 6 ? BwLayout<6>::NMAX * BwLayout<6>::QS : BwLayout<3>::NMAX * BwLayout<3>::QS) + 4 + 8 * d->M * KC;
+    if (KC != 3 && KC != 6) FGNN_REJECT("ws backward", 2);
+    // the kernel is 64 -> 64; 64 -> 128 and 128 -> 64 run it twice (fgnn_bwd_ws_plan)
+    if (!((d->nin == 64 && (d->nou == 64 || d->nou == 128)) || (d->nin == 128 && d->nou == 64))) FGNN_REJECT("ws backward", 3);
+    // what the instance's LDS layout is sized for: 96 nodes / 48 destinations of degree 6, 64 / 96 of degree 3
+    if (KC == 6 ? (d->N > BwLayout<6>::NMAX || d->M > BwLayout<6>::MMAX) : (d->N > BwLayout<3>::NMAX || d->M > BwLayout<3>::MMAX))
+        FGNN_REJECT("ws backward", 4);
+    if ((d->M * KC) & 1) FGNN_REJECT("ws backward", 5);                  // getype leaves as whole 16-byte lanes
+    if (d->idx_sb != 0 && d->B > 1) FGNN_REJECT("ws backward", 6);       // per-sample graphs: mpconv_bwd_b16.hip
+    if (!(d->idx_sk == 1 && d->idx_sm == KC)) FGNN_REJECT("ws backward", 7);
+    if (!(d->x_sc == 1 && d->x_sn == d->nin && d->x_sb % 8 == 0)) FGNN_REJECT("ws backward", 8);
+    if (!(d->y_sc == 1 && (d->y_sm == d->nou || d->M == 1) && d->y_sb % 8 == 0)) FGNN_REJECT("ws backward", 9);
+    if (!(d->et_se == 1 && d->et_sk == 4 && (d->et_sm == 4 * KC || d->M == 1) && d->et_sb % 4 == 0)) FGNN_REJECT("ws backward", 10);
+    return 1;
+}
+
+// With how many per-graph table entries does this descriptor go to the kernel above?  (0: it does not, or it is a 128 -> 64 call,
+// whose two launches build their own.)
+static int bw_tables_count(const fgnn_mpconv_desc* d) {
+    if (!bw_shape(d, fgnn_switches()) || d->nin != 64) return 0;
+    return (d->k == 6 ? BwLayout<6>::NMAX * BwLayout<6>::QS : BwLayout<3>::NMAX * BwLayout<3>::QS) + 4 + 8 * d->M * d->k;
 }
 
 // Bytes of the per-graph tables the backward of this descriptor can take (0: the shape does not use any).
@@ -791,31 +809,30 @@ extern "C" int fgnn_mpconv_backward_tables(const fgnn_mpconv_desc* d, const int6
     return FGNN_OK;
 }
 
-// Asked before the second-generation kernel, behind its rules (fgnn_bwd_sg_rules): 64 -> 64, 64 -> 128 as two launches over the
-// output-channel halves (pl->split), 128 -> 64 as two launches over the input-channel halves (pl->mode).  pl->aux: the call's
-// per-graph tables fit this descriptor.
+// 64 -> 64, 64 -> 128 as two launches over the output-channel halves (pl->split), 128 -> 64 as two launches over the input-channel
+// halves (pl->mode).  pl->aux: the call's per-graph tables fit this descriptor.  d->reserved carries the largest in-degree of the
+// (batch-shared) neighbour table as the caller measured it (0 = unknown: not this kernel).
 int fgnn_bwd_ws_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
     const fgnn_mpconv_desc* d = c.d;
+    if (!bw_shape(d, sw)) return 0;                           // rules 0 .. 10
+    // 64 -> 128: the output channels are independent and every gradient is a sum over them, so the call runs as TWO launches of the
+    // 64 -> 64 kernel over the halves of gz / argmax / W's columns; the second one ADDS to gx and getype (one more bf16 rounding of
+    // those two) and its dW / dbias land in the upper halves of gfilters' columns / gbias.
+    const bool split = d->nin == 64 && d->nou == 128;
     // 128 -> 64 (round 5): two launches over the halves of the INPUT channels.  Everything the kernel computes is linear in the
     // input-channel block it is given — P = P_lo + P_hi, so detype = sum_o G P splits into two addends (the second launch ADDS to
     // getype); dP depends on G and etype only; dx and dW are per input channel — so the 64-channel kernel runs twice on x / W / gx /
     // gfilters offset by 64 channels / rows (x and gx rows stay 128 apart in memory: x_ld), dbias counted once.  Replaces the
     // first-generation mpconv_bwd_b16_kernel<4,2> for these calls (245 us at 4096 codewords, profiles/r04).
     const bool ksplit = d->nin == 128 && d->nou == 64;
-    const int r = fgnn_bwd_sg_rules(c, sw, ksplit, pl);     // (128 -> 64: the layout rules only; the sg kernel has no such form)
-    if (r <= 0) return r;
-    if (sw.no_ws) FGNN_REJECT("ws backward", 0);            // (tests: the second-generation kernels on the same shapes)
-    const bool split = !ksplit && pl->split;                 // 64 -> 128: two launches over the halves of the output channels
-    const int KC = d->k, DEG = KC == 6 ? 3 : 6;
+    const int KC = d->k, DEG = KC == 6 ? 3 : 6;               // LDPC: degree-6 checks <-> degree-3 variables
     const int indeg = d->reserved & 0xffff;
-    if (indeg < 1 || indeg > DEG) FGNN_REJECT("ws backward", 2);
-    if (KC == 6 ? (d->N > 96 || d->M > 48) : (d->N > 64 || d->M > 96)) FGNN_REJECT("ws backward", 3);
-    if ((d->M * KC) & 1) FGNN_REJECT("ws backward", 4);                  // getype leaves as whole 16-byte lanes
+    if (indeg < 1 || indeg > DEG) FGNN_REJECT("ws backward", 11);
+    if (!c.getype || !c.argmax || !c.gbias) FGNN_REJECT("ws backward", 12);
     if (((uintptr_t)c.getype & 15) || ((uintptr_t)c.x & 15) || ((uintptr_t)c.gz & 15) || ((uintptr_t)c.argmax & 7) || ((uintptr_t)c.gx & 7) ||
-        ((uintptr_t)c.et & 7)) FGNN_REJECT("ws backward", 5);
-    if ((d->x_sb % 8) != 0 || (d->y_sb % 8) != 0 || (d->et_sb % 4) != 0) FGNN_REJECT("ws backward", 6);
-    const int64_t slab_len = 64 * 256 + 64;
-    if (!c.workspace || c.workspace_bytes < ((split || ksplit) ? 2 : 1) * 256 * slab_len * 4) FGNN_REJECT("ws backward", 7);
+        ((uintptr_t)c.et & 7)) FGNN_REJECT("ws backward", 13);
+    const int64_t slab_len = 64 * 256 + 64;                    // of ONE launch
+    if (!c.workspace || c.workspace_bytes < ((split || ksplit) ? 2 : 1) * 256 * slab_len * 4) FGNN_REJECT("ws backward", 14);
     const bool nl48 = KC == 3 && d->N <= 48;                   // the LDPC F -> V call: 48 factor nodes
     pl->fn = ksplit ? (KC == 6 ? (void*)mpconv_bwd_ws_kernel<6, 3, 128> : nl48 ? (void*)mpconv_bwd_ws_kernel<3, 6, 128, 48> : (void*)mpconv_bwd_ws_kernel<3, 6, 128>)
                     : (KC == 6 ? (void*)mpconv_bwd_ws_kernel<6, 3> : nl48 ? (void*)mpconv_bwd_ws_kernel<3, 6, 64, 48> : (void*)mpconv_bwd_ws_kernel<3, 6>);

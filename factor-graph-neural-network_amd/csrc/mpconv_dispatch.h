@@ -13,8 +13,6 @@ struct FgnnFold;
 struct FgnnSwitches {
     bool force_generic;     // FGNN_FORCE_GENERIC
     bool no_ws;             // FGNN_NO_WS
-    bool no_sg;             // FGNN_NO_SG
-    bool sg_nosplit;        // FGNN_SG_NOSPLIT
     bool no_bwd_b16;        // FGNN_NO_BWD_B16
     bool no_fwd_hyper;      // FGNN_NO_FWD_HYPER
     bool no_fanin_id;       // FGNN_NO_FANIN_ID
@@ -63,16 +61,12 @@ int fgnn_fwd_hyper_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* 
 int fgnn_fwd_hyper_launch(const FgnnFwdCall& c, const FgnnPlan& pl);
 int fgnn_fwd_ws_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
 int fgnn_fwd_ws_launch(const FgnnFwdCall& c, const FgnnPlan& pl);
-int fgnn_fwd_sg_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
-int fgnn_fwd_sg_launch(const FgnnFwdCall& c, const FgnnPlan& pl);
 int fgnn_fwd_b16_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
 int fgnn_fwd_b16_launch(const FgnnFwdCall& c, const FgnnPlan& pl);
 int fgnn_fwd_ext_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
 int fgnn_fwd_ext_launch(const FgnnFwdCall& c, const FgnnPlan& pl);
 int fgnn_fwd_res_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
 int fgnn_fwd_res_launch(const FgnnFwdCall& c, const FgnnPlan& pl);
-// The shared-graph layout both the sg and the ws forward need (mpconv_fwd_sg.hip): 1 with pl->mode / split set, 0, or < 0.
-int fgnn_fwd_sg_layout(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
 
 // ---- backward families (dispatch order: mpconv_bwd.hip) ----
 int fgnn_bwd_ext_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
@@ -82,17 +76,10 @@ int fgnn_bwd_hyper_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* 
 int fgnn_bwd_hyper_launch(const FgnnBwdCall& c, const FgnnPlan& pl);
 int fgnn_bwd_ws_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
 int fgnn_bwd_ws_launch(const FgnnBwdCall& c, const FgnnPlan& pl);
-int fgnn_bwd_sg_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
-int fgnn_bwd_sg_launch(const FgnnBwdCall& c, const FgnnPlan& pl);
 int fgnn_bwd_b16_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
 int fgnn_bwd_b16_launch(const FgnnBwdCall& c, const FgnnPlan& pl);
 int fgnn_bwd_res_plan(const FgnnBwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl);
 int fgnn_bwd_res_launch(const FgnnBwdCall& c, const FgnnPlan& pl);
-// The shared-graph rules the sg and ws backward both need (mpconv_bwd_sg.hip).  layout_only: the family and layout rules (off
-// switch, dtype / aggregator, degree, batch-shared table, operands present, strides); otherwise also widths, sizes, in-degree,
-// alignment, workspace and the sg kernel choice (pl->fn — NULL where the sg family has no instance for the size, which only its
-// own plan rejects —, pl->mode = its GSL, pl->split = 64 -> 128 as two launches).
-int fgnn_bwd_sg_rules(const FgnnBwdCall& c, const FgnnSwitches& sw, bool layout_only, FgnnPlan* pl);
 
 // ---- shared helpers ----
 int fgnn_check_desc(const fgnn_mpconv_desc* d);

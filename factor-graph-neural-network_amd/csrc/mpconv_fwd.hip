@@ -349,8 +349,6 @@ const FgnnSwitches& fgnn_switches() {
         FgnnSwitches s;
         s.force_generic = getenv("FGNN_FORCE_GENERIC") != nullptr;
         s.no_ws = getenv("FGNN_NO_WS") != nullptr;
-        s.no_sg = getenv("FGNN_NO_SG") != nullptr;
-        s.sg_nosplit = getenv("FGNN_SG_NOSPLIT") != nullptr;
         s.no_bwd_b16 = getenv("FGNN_NO_BWD_B16") != nullptr;
         s.no_fwd_hyper = getenv("FGNN_NO_FWD_HYPER") != nullptr;
         s.no_fanin_id = getenv("FGNN_NO_FANIN_ID") != nullptr;
@@ -395,9 +393,8 @@ static int generic_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
 // The forward's families, most specialised first; the first whose plan takes the call runs it.
 static const struct { FgnnFwdPlanFn plan; FgnnFwdLaunchFn launch; } kFwdFamilies[] = {
     {fgnn_fwd_hyper_plan, fgnn_fwd_hyper_launch},     // bf16 hyper-edge calls: fan-in (identity list) / fan-in / fan-out
-    {fgnn_fwd_ws_plan, fgnn_fwd_ws_launch},           // bf16 LDPC parity calls: third generation
-    {fgnn_fwd_sg_plan, fgnn_fwd_sg_launch},           //   second generation
-    {fgnn_fwd_b16_plan, fgnn_fwd_b16_launch},         //   first generation (per-sample tables too)
+    {fgnn_fwd_ws_plan, fgnn_fwd_ws_launch},           // bf16 LDPC parity calls: batch-shared table, even M k
+    {fgnn_fwd_b16_plan, fgnn_fwd_b16_launch},         //   every other one (per-sample tables, odd M k, FGNN_NO_WS)
     {fgnn_fwd_ext_plan, fgnn_fwd_ext_launch},         // f32 synthetic-PGM calls
     {fgnn_fwd_res_plan, fgnn_fwd_res_launch},         // f32 LDPC shapes: W resident in LDS
     {generic_plan, generic_launch},

@@ -1,9 +1,10 @@
 // mpconv_fwd_ws.hip — third-generation bf16 forward of the VF/FV message operator for the LDPC parity-check calls
 // (NO_EXTENSION, 4 edge types, max aggregation, degree 3 / 6, graph shared by the batch; reference:
-// /root/reference/lib/model/mpnn/mp_nn.py:115-134,160-175).  Same maths and rounding points as mpconv_fwd_sg.hip (x, etype,
-// filters and the projected rows P are bf16, every sum is f32, the output is rounded to bf16 once).
+// /root/reference/lib/model/mpnn/mp_nn.py:115-134,160-175).  Rounding points, as in mpconv_fwd_b16.hip: x, etype, filters and
+// the projected rows P are bf16, every sum is f32, the output is rounded to bf16 once.
 //
-// What was wrong with the second generation (profiles/r03/pmc_fwd_*.json): every wave ran projection -> barrier -> gather
+// What was wrong with the second generation (since deleted: 512-thread workgroups, two per CU, lane = channel, the neighbour
+// rows' LDS addresses in registers as here; profiles/r03/pmc_fwd_*.json): every wave ran projection -> barrier -> gather
 // -> barrier for ONE sample; waves waited 44 % of their cycles and issued 27 %.  Per sample and CU the resources it needs are
 // ~770 matrix-pipe cycles, ~750 VALU cycles and ~2 300 LDS cycles (of which 580 were the edge-type BROADCAST reads and 540
 // the x image's write + eight-fold operand re-read) against a byte bound of ~1 900 cycles — it took 5 700–6 600.
@@ -317,7 +318,9 @@ __global__ __launch_bounds__(WS_THREADS) void mpconv_fwd_ws_kernel(const WsParam
                 v = v < 0 ? 0 : (v >= N ? N - 1 : v);                  // never read outside the image
                 const unsigned n = (unsigned)v;
                 addr[g][j] = n * WS_PROW + ((q ^ (n & 7u)) << 4);
-                asm volatile("" : "+v"(addr[g][j]));                    // (keep it a per-lane register: see mpconv_fwd_sg.hip)
+                // keep it a per-lane register: left alone, the compiler notices that the table entry n is wave-uniform, moves it to
+                // an SGPR (then spills the lot into VGPR lanes) and re-adds the lane's offset on every edge
+                asm volatile("" : "+v"(addr[g][j]));
             }
             eoff[g] = (unsigned)(mm * KC * 8);
             yoff[g] = (unsigned)(mm * p.y_ld + 4 * q);
@@ -471,33 +474,47 @@ static void* ws_pick_mode(int mode) {
     return nullptr;
 }
 
-// Asked before the second-generation kernel, behind the same shared-graph layout (fgnn_fwd_sg_layout: mode, split) with 64 output
-// channels per launch.  pl->aux = 1: the inference addends of the call go into this launch's epilogue.
+// The kernel's rules, the pointer-free ones first.  64 output channels per launch; pl->mode: the epilogue; pl->split: a 64 -> 128 call
+// (two launches); pl->aux = 1: the inference addends of the call go into this launch's epilogue.
 int fgnn_fwd_ws_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* pl) {
-    const int r = fgnn_fwd_sg_layout(c, sw, pl);
-    if (r <= 0) return r;
     const fgnn_mpconv_desc* d = c.d;
-    if (sw.no_ws) return 0;
-    if (d->nou != 64 && !pl->split) return 0;
+    if (sw.no_ws) FGNN_REJECT("ws forward", 0);
+    if (d->dtype != FGNN_BF16 || d->ext != FGNN_EXT_NONE || d->net != 4 || d->agg != FGNN_AGG_MAX) FGNN_REJECT("ws forward", 1);
     const int KC = d->k;
-    if (d->N > WS_MAXN || d->M > (KC == 6 ? 48 : 96)) return 0;
-    if ((d->M * KC) & 1) return 0;                                    // a sample's edge types: whole 16-byte DMA lanes
-    if (d->M * KC * 8 > WS_ESZ || d->M * KC * 8 < 16) return 0;
-    if ((d->et_sb % 8) != 0 || (d->y_sb % 4) != 0) return 0;
-    if (c.x && ((((uintptr_t)c.et) & 15) || (((uintptr_t)c.y) & 7) || (c.argmax && (((uintptr_t)c.argmax) & 3)))) {
-        // (as in fgnn_fwd_sg_layout: the statistics rows were planned for this kernel's grid)
-        if (c.stats_epilogue) FGNN_FAIL(FGNN_EINVAL, "mpconv forward with statistics: etype must be 16-byte, y 8-byte and argmax 4-byte aligned (the partial rows were planned for the table-driven kernel)");
-        return 0;
+    if (KC != 3 && KC != 6) FGNN_REJECT("ws forward", 2);
+    // 64 -> 128: the kernel keeps the W fragments of 64 output channels resident; the output channels are independent, so the call runs
+    // as TWO launches over the halves of W's columns and of the 128-wide y / argmax / statistics rows (x and etype are read twice:
+    // +60 MB at 4 096 codewords)
+    const bool split = d->nin == 64 && d->nou == 128;
+    if (!((d->nin == 64 && (d->nou == 64 || split)) || (d->nin == 128 && d->nou == 64))) FGNN_REJECT("ws forward", 3);
+    static_assert(48 * 6 * 8 <= WS_ESZ && 96 * 3 * 8 <= WS_ESZ, "a sample's edge types fit one edge-type buffer");
+    if (d->N < 1 || d->N > WS_MAXN || d->M < 1 || d->M > (KC == 6 ? 48 : 96)) FGNN_REJECT("ws forward", 4);
+    if ((d->M * KC) & 1) FGNN_REJECT("ws forward", 5);              // a sample's edge types: whole 16-byte DMA lanes
+    if (d->idx_sb != 0 && d->B > 1) FGNN_REJECT("ws forward", 6);   // per-sample graphs: mpconv_fwd_b16.hip
+    // nn_idx: dense [M][k]; x: dense channel-fastest sample block, 16-byte aligned rows; y / argmax: channel-fastest, dense per sample;
+    // etype: edge-type fastest [M][k][4], a sample's block 16-byte aligned
+    if (!(d->idx_sk == 1 && d->idx_sm == KC)) FGNN_REJECT("ws forward", 7);
+    if (!(d->x_sc == 1 && d->x_sn == d->nin) || (d->x_sb % 8) != 0) FGNN_REJECT("ws forward", 8);
+    if (!(d->y_sc == 1 && (d->M == 1 || d->y_sm == d->nou)) || (d->y_sb % 4) != 0) FGNN_REJECT("ws forward", 9);
+    if (!(d->et_se == 1 && d->et_sk == 4 && d->et_sm == 4 * KC) || (d->et_sb % 8) != 0) FGNN_REJECT("ws forward", 10);
+    if (c.x && ((((uintptr_t)c.x) & 15) || (((uintptr_t)c.et) & 15) || (((uintptr_t)c.y) & 7) || (c.argmax && (((uintptr_t)c.argmax) & 3)))) {
+        // the pointerless plan (fgnn_mpconv_forward_stats_partials) announced this kernel's grid, and the caller sized that many
+        // statistics rows: another family (another grid) would leave rows unwritten or overrun them, silently
+        if (c.stats_epilogue) FGNN_FAIL(FGNN_EINVAL, "mpconv forward with statistics: x and etype must be 16-byte, y 8-byte and argmax 4-byte aligned (the partial rows were planned for the table-driven kernel)");
+        FGNN_REJECT("ws forward", 11);
     }
+    if (c.stats_epilogue) pl->mode = WS_MODE_TRAIN_STATS;
+    else if (!c.pscale && !d->relu) pl->mode = WS_MODE_TRAIN;
+    else if (c.pscale && d->relu && !c.argmax && c.bias) pl->mode = WS_MODE_AFFINE_RELU;
+    else pl->mode = WS_MODE_GENERIC;
+    pl->split = split ? 1 : 0;
     const int Npad = fgnn_round_up(d->N, 32);
     const int xbuf = d->nin == 64 ? 3 : 2;
     pl->lds = xbuf * WS_MAXN * d->nin * 2 + 2 * Npad * WS_PROW + (xbuf + 1) * WS_ESZ + 64;      // + the dataflow flags
-    if (pl->lds > 160 * 1024) return 0;
-    pl->fn = nullptr;
-    if (d->nin == 64) pl->fn = KC == 6 ? ws_pick_mode<64, 6, 3>(pl->mode) : ws_pick_mode<64, 3, 3>(pl->mode);
+    if (pl->lds > 160 * 1024) FGNN_REJECT("ws forward", 12);
     // (nin = 128: 64 resident A registers per producer; what spills under 128 VGPRs is the fragment-loading prologue only — none in the sample loops)
-    else if (d->nin == 128) pl->fn = KC == 6 ? ws_pick_mode<128, 6, 2>(pl->mode) : ws_pick_mode<128, 3, 2>(pl->mode);
-    if (!pl->fn) return 0;
+    if (d->nin == 64) pl->fn = KC == 6 ? ws_pick_mode<64, 6, 3>(pl->mode) : ws_pick_mode<64, 3, 3>(pl->mode);
+    else pl->fn = KC == 6 ? ws_pick_mode<128, 6, 2>(pl->mode) : ws_pick_mode<128, 3, 2>(pl->mode);
     pl->grid = d->B < 256 ? d->B : 256;      // one workgroup per CU
     pl->block = WS_THREADS;
     pl->aux = 0;

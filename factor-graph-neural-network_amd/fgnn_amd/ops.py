@@ -211,8 +211,8 @@ def is_identity_list(nn_idx):
 
 def max_in_degree(nn_idx, N):
     """Largest number of times one source node appears in a batch-SHARED neighbour table (the degree of the transposed
-    incidence), 0 when unknown.  The second-generation backward (csrc/mpconv_bwd_sg.hip) keeps every source node's
-    in-edges in registers and needs this bound up front (LDPC 96.3.963: 3 for the variables, 6 for the checks); it is
+    incidence), 0 when unknown.  The table-driven backward (csrc/mpconv_bwd_ws.hip) keeps a fixed number of in-edge slots
+    per source node and needs this bound up front (LDPC 96.3.963: 3 for the variables, 6 for the checks); it is
     measured once per table — one bincount + host read, remembered on the tensor that owns the memory — and travels to the
     C ABI in ``fgnn_mpconv_desc.reserved``.  Unknown (a per-sample table, or a first sight during hipGraph capture) sends
     the call to the first-generation kernels."""

@@ -1,17 +1,19 @@
-"""Irregular and ragged shared graphs for the operator backward's two fast kernel families (csrc/mpconv_bwd_sg.hip, csrc/mpconv_bwd_ws.hip):
-the table generator, the two references and the case list that tests/test_mpconv_sg_cases.py (CPU) and
-tests/test_mpconv_sg_irregular_gpu.py (GPU) share.  A helper module like the ``*_oracle.py`` files, not a test module.
+"""Irregular and ragged shared graphs for the operator backward on a batch-shared neighbour table: the table-driven family
+(csrc/mpconv_bwd_ws.hip) and, for the calls it turns down, the first-generation one (csrc/mpconv_bwd_b16.hip).  The table generator, the
+two references and the case list that tests/test_mpconv_sg_cases.py (CPU) and tests/test_mpconv_sg_irregular_gpu.py (GPU) share.  A
+helper module like the ``*_oracle.py`` files, not a test module.
 
-Both families build a transposed incidence of the batch-shared neighbour table in LDS (per-node in-edge slots, padding entries for the
-unused ones) and trust the caller's in-degree bound DEG (3 for k = 6, 6 for k = 3).  ``bounded_table`` prescribes the in-degree profile:
-nodes nobody lists, nodes below DEG next to nodes at DEG; ``with_tied_rows`` lists one node twice in a destination's row.
+The table-driven family builds a transposed incidence of the batch-shared neighbour table in LDS (per-node in-edge slots, padding
+entries for the unused ones) and trusts the caller's in-degree bound DEG (3 for k = 6, 6 for k = 3); the first-generation family builds
+a CSR transpose per sample and takes any in-degree.  ``bounded_table`` prescribes the in-degree profile: nodes nobody lists, nodes
+below DEG next to nodes at DEG; ``with_tied_rows`` lists one node twice in a destination's row.
 
 Layouts used throughout (the natural ones, channel / edge type last): x [B, N, nin], et [B, M, k, net], gz / z [B, M, nou],
 W [nin, nou * net] (column o * net + e), idx [1, M, k].
 
 Run as a program (``python tests/mpconv_sg_cases.py --set switch --B 37``) it runs a list of cases on the device in order, stops at the
-first exception and prints one JSON line per case and reference: how tests/test_mpconv_sg_irregular_gpu.py reaches the older kernel
-generations behind ``FGNN_NO_WS=1``, a switch that is read once per process."""
+first exception and prints one JSON line per case and reference: how tests/test_mpconv_sg_irregular_gpu.py reaches the first-generation
+kernels on the table-driven family's shapes behind ``FGNN_NO_WS=1``, a switch that is read once per process."""
 import json
 import os
 import sys
@@ -19,7 +21,7 @@ import sys
 import torch
 
 NET = 4
-DEG = {6: 3, 3: 6}                      # destination degree k -> in-edge slots per source node the fast kernels are built for
+DEG = {6: 3, 3: 6}                      # destination degree k -> in-edge slots per source node the table-driven kernel is built for
 TOL = 2.0 ** -6                         # the project's bound for these kernels: P, dP and the outputs are rounded to bf16
 FIRM = 2.0 ** -7                        # (see firm_outputs)
 TIE_EVERY = 5
@@ -33,11 +35,11 @@ CASES = [
     ('mpconv_bwd_ws', ' x2', (64, 128, 91, 40, 6)), ('mpconv_bwd_ws', ' x2', (64, 128, 37, 60, 3)),
     ('mpconv_bwd_ws', ' k2', (128, 64, 91, 40, 6)), ('mpconv_bwd_ws', ' k2', (128, 64, 37, 60, 3)),
     ('mpconv_bwd_ws', ' k2', (128, 64, 50, 64, 3)),                                                         # N > 48 in two launches
-    ('mpconv_bwd_sg', '', (64, 64, 48, 95, 3)), ('mpconv_bwd_sg', '', (64, 64, 37, 71, 3)), ('mpconv_bwd_sg', ' x2', (64, 128, 37, 71, 3)),   # M k odd
+    ('mpconv_bwd_b16', '', (64, 64, 48, 95, 3)), ('mpconv_bwd_b16', '', (64, 64, 37, 71, 3)), ('mpconv_bwd_b16', '', (64, 128, 37, 71, 3)),   # M k odd
 ]
-# in a process started with FGNN_NO_WS=1: the second generation on the third's shapes; 128 -> 64 has no sg form
+# in a process started with FGNN_NO_WS=1: the first generation on the table-driven family's shapes (every call is one launch)
 SWITCH_CASES = [
-    ('mpconv_bwd_sg', '', (64, 64, 96, 40, 6)), ('mpconv_bwd_sg', '', (64, 64, 33, 7, 6)), ('mpconv_bwd_sg', ' x2', (64, 128, 91, 40, 6)),
+    ('mpconv_bwd_b16', '', (64, 64, 96, 40, 6)), ('mpconv_bwd_b16', '', (64, 64, 33, 7, 6)), ('mpconv_bwd_b16', '', (64, 128, 91, 40, 6)),
     ('mpconv_bwd_b16', '', (128, 64, 91, 40, 6)),
 ]
 BATCHES = [37, 257]                     # 257: the grid cap of 256 gives workgroups of 2 samples and a last workgroup of 1

@@ -125,7 +125,8 @@ def test_forward_planner_picks_the_statistics_grid_without_a_gpu():
     assert rows(64, 64, 4, 48, 96, 3) == 256                 # F->V
     assert rows(64, 128, 4, 96, 48, 6) == 256                # 64 -> 128: two ws launches
     assert rows(128, 64, 4, 96, 48, 6) == 256
-    assert rows(64, 64, 4, 95, 47, 3) == 512                 # odd M * k: the shared-graph (sg) kernel
+    assert rows(64, 64, 4, 64, 96, 3) == 256                 # degree 3 with 49..64 nodes: ws too
+    assert rows(64, 64, 4, 95, 47, 3) == 512                 # odd M * k: the first-generation bf16 kernel, 66 224 B of LDS: 2 workgroups per CU
     assert rows(64, 64, 4, 96, 48, 6, shared=False) == 512   # per-sample table: the first-generation bf16 kernel
     assert rows(64, 64, 1, 48, 1, 48) == 0                   # hyper-factor fan-in: no statistics epilogue
 

@@ -1,5 +1,6 @@
-"""GPU parity of the second-generation parity-check kernels (csrc/mpconv_fwd_sg.hip, csrc/mpconv_bwd_sg.hip): the
-calls of the LDPC model with a batch-shared graph, bf16 channel-fastest storage, 4 edge types, max aggregation.
+"""GPU parity of the shared-graph parity-check kernels (csrc/mpconv_fwd_ws.hip, csrc/mpconv_bwd_ws.hip; with an odd M k
+csrc/mpconv_fwd_b16.hip, csrc/mpconv_bwd_b16.hip): the calls of the LDPC model with a batch-shared graph, bf16
+channel-fastest storage, 4 edge types, max aggregation.
 Forward against the f32 ORACLE on the same bf16-rounded inputs (2^-6 of the output range: P and the output are rounded
 to bf16), the argmax under the near-tie rule, the statistics epilogue against a direct reduction of the stored output;
 backward against torch autograd through the forward's own routing."""
@@ -58,14 +59,14 @@ def test_sg_forward_vs_oracle(shape, mode, dev):
         kw.update(relu=True)
     xd, idxd, etd = _dev_views(x, idx, et, dev)
     y, am = ops.mpconv_forward_raw(xd, idxd, etd, W.to(dev), bias.to(dev), nou, 4, 0, _hip.AGG_MAX, **kw)
-    # 64 -> 128 runs as two launches of the 64 -> 64 kernel over the halves of the output channels
     kern = _hip.lib().fgnn_last_kernel().decode()
-    # the third-generation kernel (mpconv_fwd_ws.hip) takes the 64-channel-input calls it can tile, mpconv_fwd_sg.hip the rest
-    assert ('mpconv_fwd_ws' in kern or 'mpconv_fwd_sg' in kern) and kern.endswith(' x2') == (nou == 128), kern
-    if (M * k) % 2 == 0:
-        assert 'mpconv_fwd_ws' in kern, kern
+    # the table-driven kernel (mpconv_fwd_ws.hip) takes every call with an even M k, 64 -> 128 as two launches of the 64 -> 64 kernel
+    # over the halves of the output channels; mpconv_fwd_b16.hip takes the others in one launch
+    even = (M * k) % 2 == 0
+    assert ('mpconv_fwd_ws' if even else 'mpconv_fwd_b16') in kern and kern.endswith(' x2') == (even and nou == 128), kern
     assert y.dtype == torch.bfloat16 and y.shape == ref.shape and y.stride(1) == 1
     err = float((y.float().cpu() - ref).abs().max() / ref.abs().max())
+    print('%s %s %s: error %.2e of the output range (bound %.2e)' % ('x'.join(map(str, shape)), mode, kern, err, 2.0 ** -6))
     assert err <= 2.0 ** -6, err
     if am is not None:
         # near-tie rule: the named neighbour's f32 message is the maximum up to the bf16 rounding of P
@@ -92,7 +93,7 @@ def test_sg_forward_matches_first_generation_kernel(shape, dev, monkeypatch):
     xd, idxd, etd = _dev_views(x, idx, et, dev)
     y1, a1 = ops.mpconv_forward_raw(xd, idxd, etd, W.to(dev), bias.to(dev), nou, 4, 0, _hip.AGG_MAX, want_argmax=True)
     kern = _hip.lib().fgnn_last_kernel().decode()
-    assert 'mpconv_fwd_ws' in kern or 'mpconv_fwd_sg' in kern, kern
+    assert 'mpconv_fwd_ws' in kern, kern
     monkeypatch.setattr(ops, 'DEDUPE_GRAPHS', False)
     y2, a2 = ops.mpconv_forward_raw(xd, idxd.contiguous(), etd, W.to(dev), bias.to(dev), nou, 4, 0, _hip.AGG_MAX,
                                     want_argmax=True)
@@ -130,7 +131,7 @@ def test_sg_statistics_epilogue(shape, B, dev):
                 m.filters.grad.clone(), names)
 
     a, b = run(True), run(False)
-    assert any('mpconv_fwd_sg' in n or 'mpconv_fwd_ws' in n for n in a[5]), a[5]
+    assert any(('mpconv_fwd_ws' if (M * k) % 2 == 0 else 'mpconv_fwd_b16') in n for n in a[5]), a[5]
     assert not any(n.startswith('bn_stats') for n in a[5]), a[5]           # the epilogue is what ran
     assert any(n.startswith('bn_stats') for n in b[5]), b[5]
     assert H.rel_err(a[0], b[0]) <= 2.0 ** -7 and H.rel_err(a[3], b[3]) <= 2.0 ** -6
@@ -142,8 +143,8 @@ def test_ws_forward_is_bit_reproducible_run_to_run(shape, dev, finaliser_mode):
     """The wave-specialised forward synchronises its producer and consumer waves with LDS counters, not barriers: a protocol error
     shows as rare run-to-run differences, not as a parity failure (round 4: a single cumulative "image consumed" counter let fast
     consumer waves' signals for the next sample stand in for a slow wave's, the image was overwritten under it: ~1 launch in 3 at
-    B = 1100 had a few wrong values in the last destinations of one sample).  120 launches on the same inputs, all bit-identical,
-    and identical to the barrier-synchronised second-generation kernel is covered by the parity tests above."""
+    B = 1100 had a few wrong values in the last destinations of one sample).  120 launches on the same inputs, all bit-identical;
+    that the values are right is covered by the parity tests above."""
     from fgnn_amd import _hip, ops
     nin, nou, N, M, k = shape
     B = 1100
@@ -187,7 +188,7 @@ BWD_SHAPES = [(96, 48, 6), (48, 96, 3), (64, 32, 6), (32, 64, 3), (96, 16, 6), (
 @pytest.mark.parametrize('shape', BWD_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
 @pytest.mark.parametrize('B', [1, 37, 600])
 def test_sg_backward_vs_routed_reference(shape, B, dev):
-    """Shared regular graph, 64 -> 64 channels: csrc/mpconv_bwd_sg.hip against torch autograd through the forward's own
+    """Shared regular graph, 64 -> 64 channels: csrc/mpconv_bwd_ws.hip against torch autograd through the forward's own
     routing (same bf16-rounded x / etype / gz, f32 arithmetic): what remains is the bf16 rounding of P, dP, the routed
     products and the bf16 outputs -> 2^-6 of each gradient's range.  Ragged batches (B = 37: chunks of different length per
     workgroup; B = 600: several samples per workgroup) and the real LDPC degrees (3 in / 6 out, 6 in / 3 out)."""
@@ -210,8 +211,8 @@ def test_sg_backward_vs_routed_reference(shape, B, dev):
     _, am = ops.mpconv_forward_raw(xd.detach(), idxd, etd.detach(), W.to(dev), bias.to(dev), nou, net, 0, _hip.AGG_MAX,
                                    want_argmax=True)
     z.backward(gz.to(dev).permute(0, 3, 1, 2))
-    kern = _hip.lib().fgnn_last_kernel().decode()          # third generation (mpconv_bwd_ws.hip) where it tiles, else the second
-    assert 'mpconv_bwd_ws' in kern or 'mpconv_bwd_sg' in kern, kern
+    kern = _hip.lib().fgnn_last_kernel().decode()          # M k is even for every one of BWD_SHAPES
+    assert 'mpconv_bwd_ws' in kern, kern
     sel = am.cpu().long()[..., 0].permute(0, 2, 1)                                          # [B,M,nou]
     _, gxr, ger, gWr, gbr = C.routed_reference(x[:, :, 0, :], idx, et, W, bias, gz[:, :, 0, :], sel)      # (tests/mpconv_sg_cases.py)
     tol = 2.0 ** -6
@@ -221,7 +222,7 @@ def test_sg_backward_vs_routed_reference(shape, B, dev):
     assert H.rel_err(bd.grad, gbr) <= tol
 
 
-# (nin, nou, N, M, k): the second-generation backward (64 -> 64) and the wide shapes of LDPCModel's layers 2 / 6
+# (nin, nou, N, M, k): the 64 -> 64 backward and the wide shapes of LDPCModel's layers 2 / 6
 ORACLE_BWD_SHAPES = [(64, 64, 96, 48, 6), (64, 64, 48, 96, 3), (64, 128, 96, 48, 6), (64, 128, 48, 96, 3), (128, 64, 96, 48, 6),
                      (128, 64, 48, 96, 3)]
 
@@ -267,11 +268,9 @@ def _backward_vs_oracle_autograd(shape, B, dev):
     z = ops.mpconv(xd, idx.to(dev).expand(B, -1, -1), etd, Wd, bd, nou, net, 0, _hip.AGG_MAX)
     z.backward(gz.to(dev).permute(0, 3, 1, 2))
     kern = _hip.lib().fgnn_last_kernel().decode()
-    if nin == 64:       # 64 -> 64 in one launch of the second-generation kernel, 64 -> 128 as two over the output halves
-        assert ('mpconv_bwd_ws' in kern or 'mpconv_bwd_sg' in kern) and kern.endswith(' x2') == (nou == 128), kern
-        if nou == 64:
-            assert 'mpconv_bwd_ws' in kern, kern
-    else:               # 128 -> 64 (round 5): the third-generation kernel, two launches over the halves of the input channels
+    if nin == 64:       # 64 -> 64 in one launch of the table-driven kernel, 64 -> 128 as two over the output halves
+        assert 'mpconv_bwd_ws' in kern and kern.endswith(' x2') == (nou == 128), kern
+    else:               # 128 -> 64 (round 5): the same kernel, two launches over the halves of the input channels
         assert 'mpconv_bwd_ws' in kern and kern.endswith(' k2'), kern
     assert H.rel_err(z.float()[:, :, :, 0].permute(0, 2, 1), zo) <= 2.0 ** -6
     tol = 2.0 ** -6
@@ -300,7 +299,7 @@ def test_sg_backward_is_bitwise_reproducible_and_matches_first_generation(dev, m
         return xd.grad, ed.grad, Wd.grad, bd.grad, _hip.lib().fgnn_last_kernel().decode()
 
     a, b = run(), run()
-    assert 'mpconv_bwd_ws' in a[4] or 'mpconv_bwd_sg' in a[4]
+    assert 'mpconv_bwd_ws' in a[4]
     assert all(torch.equal(u, v) for u, v in zip(a[:4], b[:4]))
     monkeypatch.setattr(ops, 'max_in_degree', lambda *_: 0)
     c = run()

@@ -1,11 +1,11 @@
-"""GPU: the operator backward's two fast kernel families for a batch-shared neighbour table (csrc/mpconv_bwd_sg.hip, second generation;
-csrc/mpconv_bwd_ws.hip, third) on the graphs tests/test_mpconv_sg_gpu.py never gives them: irregular in-degree (nodes nobody lists,
-whose gx row must be written as zeros; nodes below DEG next to nodes at DEG: partly filled slot rows and their padding entries), a
-node listed twice by one destination, ragged N and M (the ``n < N`` / ``m < M`` guards, the pad rows of the LDS images), and the
-DEG / DEG + 1 boundary of the in-degree bound the kernels trust.  Cases, generator and references: tests/mpconv_sg_cases.py (its contract
-is tests/test_mpconv_sg_cases.py, CPU).  Every case asserts the kernel family through ``fgnn_last_kernel``, so a dispatch change cannot
-quietly move it elsewhere; ``mpconv_bwd_sg_kernel<6, 3, 6, 3, 1>`` is reachable only behind ``FGNN_NO_WS=1``, which is read once per
-process: ``test_second_generation_behind_the_switch`` runs it in one child process.
+"""GPU: the operator backward for a batch-shared neighbour table -- the table-driven family (csrc/mpconv_bwd_ws.hip) and, where M k is
+odd or behind ``FGNN_NO_WS=1``, the first-generation one (csrc/mpconv_bwd_b16.hip) -- on the graphs tests/test_mpconv_sg_gpu.py never
+gives them: irregular in-degree (nodes nobody lists, whose gx row must be written as zeros; nodes below DEG next to nodes at DEG: partly
+filled slot rows and their padding entries), a node listed twice by one destination, ragged N and M (the ``n < N`` / ``m < M`` guards,
+the pad rows of the LDS images), and the DEG / DEG + 1 boundary of the in-degree bound the table-driven kernel trusts.  Cases, generator
+and references: tests/mpconv_sg_cases.py (its contract is tests/test_mpconv_sg_cases.py, CPU).  Every case asserts the kernel family
+through ``fgnn_last_kernel``, so a dispatch change cannot quietly move it elsewhere; ``FGNN_NO_WS=1`` is read once per process:
+``test_first_generation_behind_the_switch`` runs the table-driven family's shapes on the first generation in one child process.
 
 Bounds.  z and the four gradients: 2^-6 of each tensor's range, the project's bound for these kernels (P, dP and the outputs are bf16),
 against the oracle's autograd (its own routing; gz zero where the best two messages are closer than bf16 resolves, > 0.9 of the outputs
@@ -17,10 +17,13 @@ B = 37: d_node 4.6421e-03 (recorded as D_NODE = 4.7e-3), d_edge 5.9725e-03 (D_ED
 summation order and the second bf16 rounding of gx / getype in the two-launch forms.  The device's figures are printed beside the
 bounds (-s); first measured on an MI355X: worst node 5.56e-03, worst edge 8.24e-03, z and the gradients at most 6.2e-03 of their range.
 
-What these cases found.  The degree-3 instances of the third generation for more than 48 nodes (64x64x64x96x3, 64x64x50x64x3,
-128x64x50x64x3) had never run: the 64-channel calls were turned down by the second generation's own node limit before the third
-generation's plan saw them, and the kernel staged the edge types of the first 384 in-edge slots only (48 nodes of 8 slots), so gx of
-nodes 48.. was zero (worst node 1.0) and gW was off by half its range.  Those cases are the regression test."""
+What these cases found.  The degree-3 instances of the table-driven family for more than 48 nodes (64x64x64x96x3, 64x64x50x64x3,
+128x64x50x64x3) had never run: the 64-channel calls were turned down by the node limit of a second kernel generation (since deleted)
+whose rules the plan then shared, and the kernel staged the edge types of the first 384 in-edge slots only (48 nodes of 8 slots), so
+gx of nodes 48.. was zero (worst node 1.0) and gW was off by half its range.  Those cases are the regression test.
+
+The moved cases on mpconv_bwd_b16 (first measured on an MI355X): the three with an odd M k and the four behind FGNN_NO_WS=1 give z and
+the gradients at most 4.3e-03 of their range, worst node 4.94e-03, worst edge 5.97e-03."""
 import json
 import os
 import subprocess
@@ -35,7 +38,7 @@ pytestmark = pytest.mark.gpu
 
 IDS = [C.case_id(c) for c in C.CASES]
 NODE_BOUND, EDGE_BOUND = 4 * C.D_NODE, 4 * C.D_EDGE
-FAST = ('mpconv_bwd_ws', 'mpconv_bwd_sg')
+FAST = ('mpconv_bwd_ws',)
 
 
 def by_shape(shape):
@@ -119,12 +122,13 @@ def _against_routed(q, idx, dev, idx_dev):
 
 
 # M k <= N (DEG - 1): room for a table that stays below the cap
-BOUNDARY_SHAPES = [(64, 64, 96, 30, 6), (64, 64, 37, 60, 3), (64, 64, 64, 96, 3), (64, 128, 91, 30, 6), (64, 64, 37, 59, 3)]
+BOUNDARY_SHAPES = [(64, 64, 96, 30, 6), (64, 64, 37, 60, 3), (64, 64, 64, 96, 3), (64, 128, 91, 30, 6)]
+ODD_SHAPE = (64, 64, 37, 59, 3)            # M k odd: mpconv_bwd_b16, which takes any in-degree
 
 
 @pytest.mark.parametrize('shape', BOUNDARY_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
 def test_in_degree_boundary_and_remeasurement_after_an_in_place_edit(shape, dev):
-    """The kernels drop an in-edge beyond DEG without a word, so the bound the caller measured (ops.max_in_degree, remembered on the
+    """The table-driven kernel drops an in-edge beyond DEG without a word, so the bound the caller measured (ops.max_in_degree, remembered on the
     tensor) must be right: one entry edited so that a node has exactly DEG in-edges -> still a fast family; the SAME device tensor
     edited in place to DEG + 1 -> the remembered value is measured again and the call goes to mpconv_bwd_b16.  Both within 2^-6 of
     the routed reference."""
@@ -153,10 +157,11 @@ def test_in_degree_boundary_and_remeasurement_after_an_in_place_edit(shape, dev)
     assert 'mpconv_bwd_b16' in names[1], names
 
 
-@pytest.mark.parametrize('shape', BOUNDARY_SHAPES[:3] + BOUNDARY_SHAPES[4:], ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', BOUNDARY_SHAPES[:3] + [ODD_SHAPE], ids=lambda s: 'x'.join(map(str, s)))
 def test_out_of_range_ids_are_clamped(shape, dev):
     """The kernels clamp neighbour ids into [0, N): a table holding -1 and N in a few slots gives the gradients of the same table with
-    0 and N - 1 written there, bit for bit -- including when the clamp is what brings node 0 to exactly DEG in-edges."""
+    0 and N - 1 written there, bit for bit -- including when the clamp is what brings node 0 to exactly DEG in-edges.  The shape with
+    an odd M k runs mpconv_bwd_b16 (and mpconv_fwd_b16), which clamp when they stage the table."""
     from fgnn_amd import ops
     nin, nou, N, M, k = shape
     cap = C.DEG[k]
@@ -180,16 +185,15 @@ def test_out_of_range_ids_are_clamped(shape, dev):
     k1, e1, g1 = _against_routed(q, clean, dev, clean.to(dev))
     x, et, W, bias, gz = q['x'], q['et'], q['W'], q['bias'], q['gz']
     out = C.device_backward(x, clean, et, W, bias, gz, dev, idx_dev=raw_dev)
-    assert any(f in k1 for f in FAST) and out[6] == k1, (k1, out[6])
+    assert ('mpconv_bwd_b16' if shape == ODD_SHAPE else 'mpconv_bwd_ws') in k1 and out[6] == k1, (k1, out[6])
     assert max(e1) <= C.TOL, e1
     for u, v in zip(g1, out[2:6]):
         assert torch.equal(u, v)
 
 
-def test_second_generation_behind_the_switch(dev):
-    """FGNN_NO_WS=1 is read once per process: ONE child process (started fresh, nothing else on the device beside it) runs the cases
-    the third generation takes in this process -- mpconv_bwd_sg_kernel<6, 3, 6, 3, 1> is reachable no other way -- against both
-    references; 128 -> 64 has no second-generation form and must go to the first."""
+def test_first_generation_behind_the_switch(dev):
+    """FGNN_NO_WS=1 is read once per process: ONE child process (started fresh, nothing else on the device beside it) runs cases the
+    table-driven family takes in this process against both references; every one must go to mpconv_bwd_b16."""
     helper = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'mpconv_sg_cases.py')
     env = dict(os.environ, FGNN_NO_WS='1')
     r = subprocess.run([sys.executable, helper, '--set', 'switch', '--B', '37', '--refs', 'oracle,routed'], env=env, timeout=300,
@@ -203,4 +207,4 @@ def test_second_generation_behind_the_switch(dev):
             + ('' if o['ref'] == 'oracle' else ', worst node %.4e (bound %.4e), worst edge %.4e (bound %.4e)' % (
                 o['node_err'], NODE_BOUND, o['edge_err'], EDGE_BOUND)))
         C.check(o, NODE_BOUND, EDGE_BOUND)
-    assert 'mpconv_bwd_sg_kernel<6, 3, 6, 3, 1>' in outs[0]['kern'], outs[0]['kern']
+    assert all('mpconv_bwd_b16' in o['kern'] for o in outs), [o['kern'] for o in outs]

@@ -205,7 +205,7 @@ def test_whole_model_gradients_vs_oracle_autograd(bn_mode, dev):
 @pytest.mark.parametrize('bn_mode', ['eval_stats', 'batch_stats'])
 def test_benched_bf16_whole_model_gradients_vs_oracle_autograd(bn_mode, dev):
     """The bf16 twin of the test above — what bench.py TIMES: LDPCModel under bf16 autocast (bf16 activations, messages and
-    matrix cores, the second-generation backward kernels, bf16 weight-gradient kernels), forward + backward on 128 data-path
+    matrix cores, the table-driven operator backward kernels, bf16 weight-gradient kernels), forward + backward on 128 data-path
     codewords, against the f32 ORACLE's autograd on the same bf16-rounded inputs and the same parameters.
 
     What bf16 itself costs on this model is MEASURED, not assumed: the same oracle run under torch's CPU bf16 autocast (bf16

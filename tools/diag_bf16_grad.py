@@ -93,5 +93,5 @@ cmp('B oracle cpu-bf16 vs A', Bg, A)
 cmp('C hip bf16 vs A', C, A, per_layer=True)
 cmp('C hip bf16 vs B', C, Bg)
 cmp('C hip bf16 vs D hip f32', C, D)
-if os.environ.get('FGNN_NO_SG') is None:
-    print('(re-run with FGNN_NO_SG=1 for the first-generation kernels)')
+if os.environ.get('FGNN_NO_WS') is None:
+    print('(re-run with FGNN_NO_WS=1 for the first-generation kernels)')
