@@ -153,11 +153,19 @@ def in_degree(idx, N):
 # ----------------------------------------------------------------------------------------------------------------------------------
 # references
 # ----------------------------------------------------------------------------------------------------------------------------------
+def rows_of(P, idx):
+    """P [B, N, ...] gathered through a neighbour table [1 or B, M, k]: [B, M, k, ...].  A batch-shared table ([1, M, k]) serves every
+    sample; a per-sample one (tests/mpconv_b16_cases.py) indexes its own sample."""
+    if idx.shape[0] == 1:
+        return P[:, idx[0]]
+    return P[torch.arange(P.shape[0])[:, None, None], idx]
+
+
 def messages(x, idx, et, W, nou):
     """(P [B, N, nou, net], E [B, M, k, nou]) in the dtype of the inputs: the projections and the per-slot messages."""
     B, N = x.shape[0], x.shape[1]
     P = torch.einsum('bnc,cq->bnq', x, W).reshape(B, N, nou, et.shape[-1])
-    return P, (P[:, idx[0]] * et[:, :, :, None, :]).sum(-1)
+    return P, (rows_of(P, idx) * et[:, :, :, None, :]).sum(-1)
 
 
 def first_argmax(E):
@@ -189,9 +197,14 @@ def routed_by_hand(x, idx, et, W, gz, sel, rounded):
     xf, ef, gf = x.float(), et.float(), gz.float()
     P = rb(torch.einsum('bnc,cq->bnq', xf, W).reshape(B, N, nou, net))
     G = gf[:, :, None, :] * (sel.long()[:, :, None, :] == torch.arange(k)[None, None, :, None])       # [B, M, k, nou]
-    get = rb(torch.einsum('bmjo,bmjoe->bmje', G, P[:, idx[0]]))
-    dP = torch.zeros(B, N, nou, net)
-    dP.index_add_(1, idx[0].reshape(-1), (G[..., None] * ef[:, :, :, None, :]).reshape(B, M * k, nou, net))
+    get = rb(torch.einsum('bmjo,bmjoe->bmje', G, rows_of(P, idx)))
+    if idx.shape[0] == 1:
+        dP = torch.zeros(B, N, nou, net)
+        dP.index_add_(1, idx[0].reshape(-1), (G[..., None] * ef[:, :, :, None, :]).reshape(B, M * k, nou, net))
+    else:                                                                       # per-sample tables: sample b's rows are b N + n
+        dP = torch.zeros(B * N, nou, net)
+        dP.index_add_(0, (idx + N * torch.arange(B)[:, None, None]).reshape(-1),
+                      (G[..., None] * ef[:, :, :, None, :]).reshape(B * M * k, nou, net))
     dP = rb(dP).reshape(B, N, nou * net)
     gx = rb(torch.einsum('bnq,cq->bnc', dP, W))
     gW = torch.einsum('bnc,bnq->cq', xf, dP)

@@ -204,6 +204,9 @@ def test_bf16_mfma_kernel_vs_oracle(shape, agg, dev):
     etd = et.to(dev).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)      # edge-type fastest
     y, am = ops.mpconv_forward_raw(xd, idx.to(dev), etd, W.to(dev), sd['bias'].to(dev), nou, net, 0,
                                    _hip.AGG_CODES[agg], want_argmax=True)
+    # per-sample tables keep the table-driven family away, M > 1 at one edge type the hyper-edge one
+    kern = _hip.lib().fgnn_last_kernel().decode()
+    assert kern.startswith('mpconv_fwd_b16_kernel<%d, %d, ' % (net, _hip.AGG_CODES[agg])), kern
     assert y.dtype == torch.bfloat16 and y.stride(1) == 1
     err = float((y.float().cpu() - ref).abs().max() / ref.abs().max())
     assert err <= 2.0 ** -6, err
