@@ -1,7 +1,8 @@
 // Host-side dispatch of the node-wise maps' weight gradients, the message operator's pattern (mpconv_dispatch.h):
 // every kernel family of linear_wgrad*.hip has a pure host plan(call, &plan) — 1 = takes the call, 0 = not its shape (FGNN_TRACE
 // says why); pointer alignment is checked only when the call carries pointers — and a launch(call, plan): FGNN_OK or < 0.  The
-// entry points in linear_wgrad.hip ask the families in one ordered table; no family calls another.
+// entry points in linear_wgrad.hip ask the families in one ordered table; no family calls another.  name(call, plan): the kernel
+// that launch(call, plan) runs, through the helper the launch itself chooses by (fgnn_linear_wgrad_kernel, include/fgnn_hip_wgrad.h).
 #pragma once
 #include "fgnn_common.h"
 
@@ -24,9 +25,13 @@ struct FgnnWgradPlan {
 
 typedef int (*FgnnWgradPlanFn)(const FgnnWgradCall&, FgnnWgradPlan*);
 typedef int (*FgnnWgradLaunchFn)(const FgnnWgradCall&, const FgnnWgradPlan&);
+typedef const char* (*FgnnWgradNameFn)(const FgnnWgradCall&, const FgnnWgradPlan&);
 int fgnn_wgrad_narrow_plan(const FgnnWgradCall& c, FgnnWgradPlan* pl);
 int fgnn_wgrad_narrow_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl);
+const char* fgnn_wgrad_narrow_name(const FgnnWgradCall& c, const FgnnWgradPlan& pl);
 int fgnn_wgrad_b16_plan(const FgnnWgradCall& c, FgnnWgradPlan* pl);
 int fgnn_wgrad_b16_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl);
+const char* fgnn_wgrad_b16_name(const FgnnWgradCall& c, const FgnnWgradPlan& pl);
 int fgnn_wgrad_f32_plan(const FgnnWgradCall& c, FgnnWgradPlan* pl);
 int fgnn_wgrad_f32_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl);
+const char* fgnn_wgrad_f32_name(const FgnnWgradCall& c, const FgnnWgradPlan& pl);

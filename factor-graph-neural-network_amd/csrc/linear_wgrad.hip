@@ -10,6 +10,7 @@
 // and x in LDS (row-major, as in memory) and accumulates its partial gW with exact-f32 MFMA; partials go
 // to a workspace slab per workgroup and a second kernel sums them (no contended atomics).
 #include "linear_wgrad.h"
+#include "fgnn_hip_wgrad.h"
 
 #define WG_THREADS 256
 #define WG_WAVES 4
@@ -313,6 +314,28 @@ static int wgrad_plan(const FgnnWgradCall& c, FgnnWgradPlan* pl) {
     return 1;
 }
 
+// The kernel of a plan: the vectorised kernel with the small register tiling when its tiles and chunks fit 4 each, else the large
+// one; the scalar kernel where the plan found no 16-byte rows.  Chosen here for the launch and for the name.
+struct WgradKernel { void* fn; const char* name; };
+static const WgradKernel kWgradVec[2][2] = {
+    {{(void*)linear_wgrad_vec_kernel<float, 4, 4>, "linear_wgrad_vec_kernel<float, 4, 4>"},
+     {(void*)linear_wgrad_vec_kernel<float, 16, 10>, "linear_wgrad_vec_kernel<float, 16, 10>"}},
+    {{(void*)linear_wgrad_vec_kernel<bf16_t, 4, 4>, "linear_wgrad_vec_kernel<bf16, 4, 4>"},
+     {(void*)linear_wgrad_vec_kernel<bf16_t, 16, 10>, "linear_wgrad_vec_kernel<bf16, 16, 10>"}},
+};
+static const WgradKernel kWgradScalar[2] = {{(void*)linear_wgrad_kernel<float>, "linear_wgrad_kernel<float>"},
+                                            {(void*)linear_wgrad_kernel<bf16_t>, "linear_wgrad_kernel<bf16>"}};
+static const WgradKernel& wgrad_kernel(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
+    const int t = c.dtype == FGNN_F32 ? 0 : 1;
+    if (!pl.mode) return kWgradScalar[t];
+    const int epc = c.dtype == FGNN_F32 ? 4 : 8, oc = pl.aux;
+    const int tm = ((fgnn_round_up(oc, 16) / 16) * (fgnn_round_up(c.Cin, 16) / 16) + WG_WAVES - 1) / WG_WAVES;
+    const int nchunks = (WV_ROWS * (c.Cin + oc) / epc + WG_THREADS - 1) / WG_THREADS;
+    return kWgradVec[t][tm <= 4 && nchunks <= 4 ? 0 : 1];
+}
+
+static const char* wgrad_name(const FgnnWgradCall& c, const FgnnWgradPlan& pl) { return wgrad_kernel(c, pl).name; }
+
 static int wgrad_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
     const int Cin = c.Cin, Cout = c.cout[0], dtype = c.dtype, epc = dtype == FGNN_F32 ? 4 : 8;
     WgradParams p;
@@ -327,17 +350,7 @@ static int wgrad_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
     p.xmagic = xpr == 1 ? 0u : (unsigned)((0x100000000ULL + xpr - 1) / xpr);
     p.omagic = p.oc == 1 ? 0u : (unsigned)((0x100000000ULL + p.oc - 1) / p.oc);
     const int lds = (pl.mode ? WV_ROWS : WG_ROWS) * (p.XS + p.GS) * 4;
-    void* fn;
-    if (pl.mode) {
-        const int tm = ((p.Cop / 16) * (p.Cip / 16) + WG_WAVES - 1) / WG_WAVES;
-        const int nchunks = (WV_ROWS * (Cin + p.oc) / epc + WG_THREADS - 1) / WG_THREADS;
-#define WV_PICK(T) (tm <= 4 && nchunks <= 4 ? (void*)linear_wgrad_vec_kernel<T, 4, 4> : \
-                                              (void*)linear_wgrad_vec_kernel<T, 16, 10>)
-        fn = dtype == FGNN_F32 ? WV_PICK(float) : WV_PICK(bf16_t);
-#undef WV_PICK
-    } else {
-        fn = dtype == FGNN_F32 ? (void*)linear_wgrad_kernel<float> : (void*)linear_wgrad_kernel<bf16_t>;
-    }
+    void* fn = wgrad_kernel(c, pl).fn;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
@@ -355,12 +368,23 @@ static int wgrad_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
 
 // The families, most specialised first, each for one storage type (-1: both); the first whose plan takes the call
 // runs it.  fgnn_linear_wgrad_multi asks the b16 family alone, in its merged form.
-static const struct { int dtype; FgnnWgradPlanFn plan; FgnnWgradLaunchFn launch; } kWgradFamilies[] = {
-    {FGNN_BF16, fgnn_wgrad_narrow_plan, fgnn_wgrad_narrow_launch},   // linear_wgrad_b16.hip: one operand <= 16 channels
-    {FGNN_BF16, fgnn_wgrad_b16_plan, fgnn_wgrad_b16_launch},         //   multiples of 64: register-direct or LDS-staged
-    {FGNN_F32, fgnn_wgrad_f32_plan, fgnn_wgrad_f32_launch},          // linear_wgrad_f32.hip: output-blocked
-    {-1, wgrad_plan, wgrad_launch},
+static const struct { int dtype; FgnnWgradPlanFn plan; FgnnWgradLaunchFn launch; FgnnWgradNameFn name; } kWgradFamilies[] = {
+    {FGNN_BF16, fgnn_wgrad_narrow_plan, fgnn_wgrad_narrow_launch, fgnn_wgrad_narrow_name},   // linear_wgrad_b16.hip: one operand <= 16 channels
+    {FGNN_BF16, fgnn_wgrad_b16_plan, fgnn_wgrad_b16_launch, fgnn_wgrad_b16_name},            //   multiples of 64: register-direct or LDS-staged
+    {FGNN_F32, fgnn_wgrad_f32_plan, fgnn_wgrad_f32_launch, fgnn_wgrad_f32_name},             // linear_wgrad_f32.hip: output-blocked
+    {-1, wgrad_plan, wgrad_launch, wgrad_name},
 };
+
+// The first family of the call's storage type whose plan takes it (its index, the plan in *pl), or -1.
+static int wgrad_family(const FgnnWgradCall& c, FgnnWgradPlan* pl) {
+    int i = 0;
+    for (const auto& f : kWgradFamilies) {
+        *pl = {};
+        if ((f.dtype < 0 || f.dtype == c.dtype) && f.plan(c, pl) == 1) return i;
+        ++i;
+    }
+    return -1;
+}
 
 // The largest workspace of the families that take the shape, whatever their storage type; -1 if none does.
 extern "C" int64_t fgnn_linear_wgrad_workspace_bytes(int64_t R, int Cin, int Cout) {
@@ -383,14 +407,26 @@ extern "C" int fgnn_linear_wgrad(const void* x, const void* gy, int64_t R, int C
     if (R <= 0 || R > 0x7fffffff || Cin <= 0 || Cout <= 0) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: bad sizes");
     if (dtype != FGNN_F32 && dtype != FGNN_BF16) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: unknown dtype %d", dtype);
     const FgnnWgradCall c = {x, R, Cin, dtype, 1, false, {gy}, {Cout}, {gW}, {gb}, workspace, workspace_bytes, (hipStream_t)stream};
-    for (const auto& f : kWgradFamilies) {
-        FgnnWgradPlan pl = {};
-        if ((f.dtype >= 0 && f.dtype != dtype) || f.plan(c, &pl) != 1) continue;
-        if (workspace_bytes < pl.ws_bytes) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: workspace %lld < %lld bytes",
-                                                     (long long)workspace_bytes, (long long)pl.ws_bytes);
-        return f.launch(c, pl);
-    }
-    FGNN_FAIL(FGNN_EUNSUPPORTED, "linear_wgrad: Cin=%d too wide for the register tiling", Cin);
+    FgnnWgradPlan pl;
+    const int f = wgrad_family(c, &pl);
+    if (f < 0) FGNN_FAIL(FGNN_EUNSUPPORTED, "linear_wgrad: Cin=%d too wide for the register tiling", Cin);
+    if (workspace_bytes < pl.ws_bytes) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: workspace %lld < %lld bytes",
+                                                 (long long)workspace_bytes, (long long)pl.ws_bytes);
+    return kWgradFamilies[f].launch(c, pl);
+}
+
+// The kernel fgnn_linear_wgrad would launch for that call (include/fgnn_hip_wgrad.h): the same walk over the table, the same
+// plan, and the family's own choice among its kernels.  The plans read a pointer's low four bits only, so the call carries
+// addresses that are never dereferenced.  Pure host work, no state.
+extern "C" const char* fgnn_linear_wgrad_kernel(int64_t R, int32_t Cin, int32_t Cout, int32_t dtype, int32_t x_low_bits,
+                                                int32_t gy_low_bits) {
+    if (R <= 0 || R > 0x7fffffff || Cin <= 0 || Cout <= 0 || (dtype != FGNN_F32 && dtype != FGNN_BF16)) return "";
+    const void* x = (const void*)(uintptr_t)(16 + (x_low_bits & 15));
+    const void* gy = (const void*)(uintptr_t)(16 + (gy_low_bits & 15));
+    const FgnnWgradCall c = {x, R, Cin, dtype, 1, false, {gy}, {Cout}};
+    FgnnWgradPlan pl;
+    const int f = wgrad_family(c, &pl);
+    return f < 0 ? "" : kWgradFamilies[f].name(c, pl);
 }
 
 // The merged form's call; nsrc outside 1..WB_MAXSRC leaves it without sources (no plan takes it).  gy == NULL: a query.

@@ -557,13 +557,21 @@ int fgnn_wgrad_narrow_plan(const FgnnWgradCall& c, FgnnWgradPlan* pl) {
     return 1;
 }
 
+// The narrow kernel of a plan: NARROW_X when x is the narrow operand.  Chosen here for the launch and for the name.
+static bool wn_narrow_x(const FgnnWgradPlan& pl) { return pl.mode != 0; }
+
+const char* fgnn_wgrad_narrow_name(const FgnnWgradCall&, const FgnnWgradPlan& pl) {
+    return wn_narrow_x(pl) ? "linear_wgrad_b16_narrow_kernel<true>" : "linear_wgrad_b16_narrow_kernel<false>";
+}
+
 int fgnn_wgrad_narrow_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
+    const bool narrow_x = wn_narrow_x(pl);
     WgbParams p = {};
     p.x = (const uint16_t*)c.x; p.gy = (const uint16_t*)c.gy[0]; p.ws = (float*)c.workspace;
     p.R = (int)c.R; p.Cin = c.Cin; p.Cout = c.cout[0]; p.nso = 1; p.S = 1; p.RW = WB_WAVES;
     const int lds = (WB_WAVES / 2) * WN_NACC * 64 * 4;
-    for (int woff = 0; woff < (pl.mode ? p.Cout : p.Cin); woff += 64) {     // the kernel reads 64 channels from the pointer, rows at the full stride
-        if (pl.mode) {
+    for (int woff = 0; woff < (narrow_x ? p.Cout : p.Cin); woff += 64) {     // the kernel reads 64 channels from the pointer, rows at the full stride
+        if (narrow_x) {
             p.gy = (const uint16_t*)c.gy[0] + woff;
             hipLaunchKernelGGL(linear_wgrad_b16_narrow_kernel<true>, dim3(pl.gx), dim3(WB_THREADS), lds, c.stream, p);
             hipLaunchKernelGGL(wgn_reduce_kernel<true>, dim3(WN_NACC), dim3(1024), 0, c.stream, p.ws, pl.gx, p.Cin, p.Cout, woff, c.gW[0], c.gb[0]);
@@ -624,8 +632,24 @@ int fgnn_wgrad_b16_plan(const FgnnWgradCall& c, FgnnWgradPlan* pl) {
     return 1;
 }
 
+// The kernel of a plan: the LDS-staged form or the register-direct one, named with the slices per workgroup (S row-waves share a
+// block of rows; 16 / S of them fold).  Chosen here for the launch and for the name.
+struct WbKernel { bool staged; void* fn; const char* name; };
+static WbKernel wb_kernel(const FgnnWgradPlan& pl) {
+    static const char* const direct[] = {"linear_wgrad_b16_kernel S=1", "linear_wgrad_b16_kernel S=2", "linear_wgrad_b16_kernel S=4",
+                                         "linear_wgrad_b16_kernel S=8", "linear_wgrad_b16_kernel S=16"};
+    int l = 0;
+    while ((1 << l) < pl.aux) ++l;                                     // S is a power of two <= 16
+    if (pl.mode)                                                       // (the plan stages 8 or 16 slices only)
+        return {true, (void*)linear_wgrad_lds_kernel, pl.aux == 8 ? "linear_wgrad_lds_kernel S=8" : "linear_wgrad_lds_kernel S=16"};
+    return {false, (void*)linear_wgrad_b16_kernel, direct[l]};
+}
+
+const char* fgnn_wgrad_b16_name(const FgnnWgradCall&, const FgnnWgradPlan& pl) { return wb_kernel(pl).name; }
+
 int fgnn_wgrad_b16_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
     const int S = pl.aux, RW = 16 / S, gx = pl.gx;
+    const WbKernel k = wb_kernel(pl);
     WgbParams p = {};
     p.x = (const uint16_t*)c.x; p.gy = (const uint16_t*)c.gy[0]; p.ws = (float*)c.workspace;
     p.R = (int)c.R; p.Cin = c.Cin; p.Cout = c.cout[0]; p.nso = c.cout[0] / 64; p.S = S; p.RW = RW;
@@ -635,18 +659,18 @@ int fgnn_wgrad_b16_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
     }
     for (int s = 0; s <= WB_MAXSRC; ++s) p.sb[s] = pl.sb[s];
     hipError_t e;
-    if (pl.mode) {
+    if (k.staged) {
         WglParams q = {};
         wl_stages(c, S, &q);
         q.b = p;
-        void* fn = (void*)linear_wgrad_lds_kernel;
+        void* fn = k.fn;
         const int bytes = q.nst * q.stage_bytes;
         e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
         void* args[] = {(void*)&q};
         e = hipLaunchKernel(fn, dim3(gx), dim3(WB_THREADS), args, bytes, c.stream);
     } else {
-        void* fn = (void*)linear_wgrad_b16_kernel;
+        void* fn = k.fn;
         const int lds = S * (RW / 2) * WB_NACC * 64 * 4;                   // 0 when every slice has one row-wave
         if (lds > 48 * 1024) {
             e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -661,8 +685,8 @@ int fgnn_wgrad_b16_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
         const int Ss = pl.sb[s + 1] - pl.sb[s], nso = c.cout[s] / 64;
         const int64_t len = (int64_t)Ss * WB_NACC * 64;
         const float* ws_s = p.ws + (int64_t)pl.sb[s] * WB_NACC * 64;
-        if (fgnn_fold_push(ws_s, gx, stride, len, c.gW[s], c.gb[s], pl.mode ? 2 : 1, Ss, nso, c.Cin, c.cout[s])) continue;      // recorded (fold_batch.hip)
-        if (pl.mode)
+        if (fgnn_fold_push(ws_s, gx, stride, len, c.gW[s], c.gb[s], k.staged ? 2 : 1, Ss, nso, c.Cin, c.cout[s])) continue;      // recorded (fold_batch.hip)
+        if (k.staged)
             hipLaunchKernelGGL(wgb_reduce_kernel<true>, dim3((unsigned)(len / 64)), dim3(1024), 0, c.stream, ws_s, gx, stride, nso, c.Cin, c.cout[s],
                                c.gW[s], c.gb[s]);
         else

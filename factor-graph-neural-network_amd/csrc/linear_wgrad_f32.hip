@@ -206,6 +206,20 @@ int fgnn_wgrad_f32_plan(const FgnnWgradCall& c, FgnnWgradPlan* pl) {
     return 1;
 }
 
+// The piece-form kernel of a map: a side of <= 64 channels takes a 64-wide block.  Chosen here for the launch and for the name.
+enum { WQ_64x64, WQ_64x128, WQ_128x64, WQ_128x128 };
+static int wq_form(int Cin, int Cout) {
+    if (Cout <= 64 && Cin <= 64) return WQ_64x64;
+    if (Cout <= 64) return WQ_64x128;
+    return Cin <= 64 ? WQ_128x64 : WQ_128x128;
+}
+
+const char* fgnn_wgrad_f32_name(const FgnnWgradCall& c, const FgnnWgradPlan&) {
+    static const char* const names[] = {"linear_wgrad_f32q_kernel<64, 64>", "linear_wgrad_f32q_kernel<64, 128>",
+                                        "linear_wgrad_f32q_kernel<128, 64>", "linear_wgrad_f32q_kernel<128, 128>"};
+    return names[wq_form(c.Cin, c.cout[0])];
+}
+
 int fgnn_wgrad_f32_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
     const int Cin = c.Cin, Cout = c.cout[0];
     const int64_t nw = (int64_t)Cout * Cin, slab_len = nw + Cout;
@@ -213,10 +227,12 @@ int fgnn_wgrad_f32_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
     p.x = (const float*)c.x; p.gy = (const float*)c.gy[0]; p.ws = (float*)c.workspace; p.R = (int)c.R; p.Cin = Cin; p.Cout = Cout;
     p.rows_per_chunk = pl.rows; p.nblk_c = pl.aux; p.want_bias = c.gb[0] != nullptr;
     const dim3 grid(pl.gx, pl.gy), block(WF_THREADS);
-    if (Cout <= 64 && Cin <= 64) hipLaunchKernelGGL((linear_wgrad_f32q_kernel<64, 64>), grid, block, 0, c.stream, p);
-    else if (Cout <= 64) hipLaunchKernelGGL((linear_wgrad_f32q_kernel<64, 128>), grid, block, 0, c.stream, p);
-    else if (Cin <= 64) hipLaunchKernelGGL((linear_wgrad_f32q_kernel<128, 64>), grid, block, 0, c.stream, p);
-    else hipLaunchKernelGGL((linear_wgrad_f32q_kernel<128, 128>), grid, block, 0, c.stream, p);
+    switch (wq_form(Cin, Cout)) {
+    case WQ_64x64: hipLaunchKernelGGL((linear_wgrad_f32q_kernel<64, 64>), grid, block, 0, c.stream, p); break;
+    case WQ_64x128: hipLaunchKernelGGL((linear_wgrad_f32q_kernel<64, 128>), grid, block, 0, c.stream, p); break;
+    case WQ_128x64: hipLaunchKernelGGL((linear_wgrad_f32q_kernel<128, 64>), grid, block, 0, c.stream, p); break;
+    default: hipLaunchKernelGGL((linear_wgrad_f32q_kernel<128, 128>), grid, block, 0, c.stream, p); break;
+    }
     fgnn_launch_slab_reduce(p.ws, pl.gx, slab_len, nw, c.gW[0], c.gb[0], c.stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad f32 launch: %s", hipGetErrorString(e));

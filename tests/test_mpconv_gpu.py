@@ -694,6 +694,8 @@ def test_f32_blocked_weight_gradient_vs_torch(R, cin, cout, dev):
     gy = torch.randn(R, cout, generator=g).to(dev)
     ref_w = (gy.double().t() @ x.double())
     ref_b = gy.double().sum(0)
+    kernel = _hip.invoke('fgnn_linear_wgrad_kernel', R, cin, cout, _hip.dtype_code(x), x.data_ptr() & 15, gy.data_ptr() & 15)
+    assert kernel.startswith(b'linear_wgrad_f32q_kernel<'), kernel       # the family this test is about, not the general kernel
     outs = []
     for _ in range(2):
         gw = torch.ones(cout, cin, device=dev)
@@ -753,6 +755,9 @@ def test_bf16_weight_gradients_of_several_maps_over_one_state(R, cin, couts, def
                 for gy, gw, gb, c in zip(gys, gws, gbs, couts):
                     ws = torch.empty(int(L.fgnn_linear_wgrad_workspace_bytes(R, cin, c)) // 4, device=dev)
                     keep.append(ws)
+                    S = (c // 64) * (cin // 64)          # one map alone: the b16 family, LDS-staged only when wide and long
+                    kernel = _hip.invoke('fgnn_linear_wgrad_kernel', R, cin, c, _hip.BF16, x.data_ptr() & 15, gy.data_ptr() & 15).decode()
+                    assert kernel in ('linear_wgrad_b16_kernel S=%d' % S,) + (('linear_wgrad_lds_kernel S=%d' % S,) if S >= 8 and R >= 2048 else ())
                     _hip.check(L.fgnn_linear_wgrad(P(x), P(gy), R, cin, c, _hip.BF16, P(gw), P(gb), P(ws), ws.numel() * 4, _hip.stream_ptr()))
         finally:
             L.fgnn_fold_defer(0)
