@@ -667,14 +667,9 @@ static int bt_launch(const BtParams& p, int grid, hipStream_t st) {
         const int fold = CG * (64 + 16 * (4 / CG) + 4) * 64 * 4;
         if (fold > lds) lds = fold;
     }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
+    static const char* const what[] = {"block_tail (mode 0)", "block_tail (mode 1)", "block_tail (mode 2)", "block_tail (mode 3)"};
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(BT_THREADS), args, lds, st);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "block_tail launch (mode %d): %s", MODE, hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch_fn(what[MODE], fn, dim3(grid), dim3(BT_THREADS), lds, st, args);
 }
 
 static int bt_check(const char* who, const void* e, const float* s2, const float* t2, const float* W2, int64_t R, int Cout, int* grid, bool apply = false) {
@@ -699,10 +694,8 @@ extern "C" int fgnn_block_tail_stats(const void* e, const float* scale2, const f
     p.fin.shift_k = b2;                       // the kernel sums z3 - b2
     const bool inkernel = fold_scratch && !fgnn_separate_finalisers();
     p.fold = fgnn_fold_make(partials, inkernel ? fold_scratch : nullptr, grid, Cout);
-    if ((rc = bt_launch<0>(p, grid, (hipStream_t)stream))) return rc;
-    if (!inkernel && fgnn_bn_finalize_launch(partials, grid, Cout, &p.fin, (hipStream_t)stream))
-        FGNN_FAIL(FGNN_ELAUNCH, "block_tail_stats finaliser launch: %s", hipGetErrorString(hipGetLastError()));
-    return FGNN_OK;
+    if ((rc = bt_launch<0>(p, grid, fgnn_stream(stream)))) return rc;
+    return inkernel ? FGNN_OK : fgnn_bn_finalize_launch(partials, grid, Cout, &p.fin, fgnn_stream(stream));
 }
 
 extern "C" int fgnn_block_tail_apply(const void* e, const float* scale2, const float* shift2, float slope2, const float* W2,
@@ -729,7 +722,7 @@ extern "C" int fgnn_block_tail_apply(const void* e, const float* scale2, const f
     p.add2 = (const uint16_t*)(na > 2 ? ads[2] : nullptr);
     for (int a = 0; a < 3; ++a) p.aperiod[a] = a < na ? per[a] : 1;
     p.out = (uint16_t*)out; p.out2 = (uint16_t*)a2_out; p.R = (int)R; p.Cout = Cout; p.slope2 = slope2; p.slope3 = slope3;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     switch (na) {
         case 0: return bt_launch<1, 0>(p, grid, st);
         case 1: return bt_launch<1, 1>(p, grid, st);
@@ -776,8 +769,6 @@ __global__ __launch_bounds__(256) void block_tail_wgrad_combine_kernel(const flo
     gW2[(int64_t)o * 64 + c] += fmaf(s3[o], T[(int64_t)o * 64 + c], fmaf(a, m2, k * Gp[64 * 64 + c]));
 }
 
-void fgnn_launch_slab_store(const float* ws, int nslab, int64_t slab_len, float* out, hipStream_t st);     // mpconv_bwd_res.hip
-
 // Fold the moments fgnn_block_tail_backward_moments left and ADD conv2's weight gradient to gW2 [Cout][64] (two short launches; nothing
 // in a backward pass reads a weight gradient: callers park this call like any other weight-gradient launch).
 extern "C" int fgnn_block_tail_wgrad_finish(void* moments, int64_t moments_bytes, int64_t R, int Cout, const float* W2, const float* b2,
@@ -790,12 +781,9 @@ extern "C" int fgnn_block_tail_wgrad_finish(void* moments, int64_t moments_bytes
     float* A = m + (int64_t)nslab * len;
     float* Bc = A + Cout;
     float* T = Bc + Cout;
-    hipStream_t st = (hipStream_t)stream;
-    fgnn_launch_slab_store(m, nslab, len, T, st);
-    hipLaunchKernelGGL(block_tail_wgrad_combine_kernel, dim3(Cout / 4), dim3(256), 0, st, T, W2, b2, scale3, A, Bc, gW2, Cout);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "block_tail_wgrad_finish launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    hipStream_t st = fgnn_stream(stream);
+    const int rc = fgnn_launch_slab_store(m, nslab, len, T, st);
+    return rc ? rc : fgnn_launch("block_tail_wgrad_finish", block_tail_wgrad_combine_kernel, dim3(Cout / 4), dim3(256), 0, st, T, W2, b2, scale3, A, Bc, gW2, Cout);
 }
 
 static int bt_backward(const void* e, const float* scale2, const float* shift2, float slope2,
@@ -822,7 +810,7 @@ static int bt_backward(const void* e, const float* scale2, const float* shift2, 
         A = moments + (int64_t)bt_mom_nslab(R, Cout) * bt_mom_slab_len(Cout);
         Bc = A + Cout;
     }
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     const bool inkernel = fold_scratch && !fgnn_separate_finalisers();
     BtParams p = {};
     p.e = (const uint16_t*)e; p.s2 = scale2; p.t2 = shift2; p.W2 = W2; p.b2 = b2; p.s3 = scale3; p.t3 = shift3;
@@ -833,18 +821,13 @@ static int bt_backward(const void* e, const float* scale2, const float* shift2, 
     if ((rc = moments ? bt_launch<2, 1>(p, grid, st) : bt_launch<2>(p, grid, st))) return rc;
     int grid3;
     (void)bt_plan(R, Cout, &grid3, false);
-    if (!inkernel)
-        hipLaunchKernelGGL(block_tail_bwd_final_kernel, dim3((Cout + 3) / 4), dim3(256), 0, st, ws, grid, Cout, R, b2, mean3,
-                           invstd3, gamma3, A, Bc, gweight3, gbias3);
+    if (!inkernel && (rc = fgnn_launch("block_tail_backward", block_tail_bwd_final_kernel, dim3((Cout + 3) / 4), dim3(256), 0, st, ws, grid, Cout, R, b2,
+                                       mean3, invstd3, gamma3, A, Bc, gweight3, gbias3))) return rc;
     p.ga = A; p.gb = Bc; p.out = (uint16_t*)gz3; p.out2 = (uint16_t*)ga2; p.part = nullptr; p.part2 = bn2_dsum ? part2 : nullptr;
     p.mean2 = mean2; p.invstd2 = invstd2; p.dsum2 = bn2_dsum; p.gweight2 = gweight2; p.gbias2 = gbias2;
     p.fold = fgnn_fold_make(part2, (inkernel && bn2_dsum) ? fold_scratch : nullptr, grid3, 64);
     if ((rc = bt_launch<3>(p, grid3, st))) return rc;
-    if (!inkernel && bn2_dsum && fgnn_bn_bwd_final_raw_launch(part2, grid3, 64, mean2, invstd2, bn2_dsum, gweight2, gbias2, st))
-        FGNN_FAIL(FGNN_ELAUNCH, "block_tail_backward finaliser launch: %s", hipGetErrorString(hipGetLastError()));
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "block_tail_backward launch: %s", hipGetErrorString(e2));
-    return FGNN_OK;
+    return (!inkernel && bn2_dsum) ? fgnn_bn_bwd_final_raw_launch(part2, grid3, 64, mean2, invstd2, bn2_dsum, gweight2, gbias2, st) : FGNN_OK;
 }
 
 extern "C" int fgnn_block_tail_backward(const void* e, const float* scale2, const float* shift2, float slope2,
@@ -1025,10 +1008,11 @@ extern "C" int fgnn_block_head_backward(const void* z1, const void* ga1, const f
     if (bt_plan(R, Cin, &grid, true, true) || (((uintptr_t)z1 | (uintptr_t)ga1 | (uintptr_t)gz1 | (uintptr_t)gx) & 15))      // (3 workgroups per CU: the 768 cap)
         FGNN_FAIL(FGNN_EUNSUPPORTED, "block_head_backward: Cin=%d / alignment outside the fused block head's family", Cin);
     if (workspace_bytes < (int64_t)BT_MAXGRID * 2 * 64 * 4 + 2 * 64 * 4) FGNN_FAIL(FGNN_EINVAL, "block_head_backward: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     const float* dsum = nullptr;
-    if (fgnn_bn_backward_sums_bf16(z1, ga1, R, 64, mean, invstd, gamma, beta, slope, gweight, gbias, workspace, fold_scratch, st, &dsum))
-        FGNN_FAIL(FGNN_EUNSUPPORTED, "block_head_backward: BatchNorm reduction plan failed");
+    const int rc = fgnn_bn_backward_sums_bf16(z1, ga1, R, 64, mean, invstd, gamma, beta, slope, gweight, gbias, workspace, fold_scratch, st, &dsum);
+    if (rc == FGNN_EUNSUPPORTED) FGNN_FAIL(FGNN_EUNSUPPORTED, "block_head_backward: BatchNorm reduction plan failed");
+    if (rc) return rc;
     BhParams p = {};
     p.z = (const uint16_t*)z1; p.g = (const uint16_t*)ga1; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta;
     p.dsum = dsum; p.W = W1; p.gz = (uint16_t*)gz1; p.gx = (uint16_t*)gx; p.R = (int)R; p.Cin = Cin; p.slope = slope;
@@ -1036,13 +1020,7 @@ extern "C" int fgnn_block_head_backward(const void* z1, const void* ga1, const f
     const int CG = Cin / 64;
     void* fn = CG == 1 ? (void*)block_head_bwd_kernel<1> : (CG == 2 ? (void*)block_head_bwd_kernel<2> : (void*)block_head_bwd_kernel<4>);
     const int lds = CG * 8 * 64 * 16 + 5 * 64 * 4;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
     fgnn_note_kernel("block_head_bwd_kernel<%d>", CG);
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(BT_THREADS), args, lds, st);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "block_head_backward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch_fn("block_head_backward", fn, dim3(grid), dim3(BT_THREADS), lds, st, args);
 }

@@ -334,8 +334,7 @@ static int bn_check_final(const char* who, const fgnn_bn_final* fin) {
 
 // Host-side helper of the other translation units: the stand-alone forward finaliser.
 int fgnn_bn_finalize_launch(const float* partials, int npartials, int C, const fgnn_bn_final* fin, hipStream_t st) {
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + BN_FC - 1) / BN_FC), dim3(256), 0, st, partials, npartials, C, *fin);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return fgnn_launch("bn_finalize", bn_stats_final_kernel, dim3((C + BN_FC - 1) / BN_FC), dim3(256), 0, st, partials, npartials, C, *fin);
 }
 
 // Forward statistics of x [R][C] (count = R rows): one reducing launch whose last workgroup finalises (fgnn_bn_final).
@@ -349,7 +348,7 @@ extern "C" int fgnn_bn_stats(const void* x, int64_t R, int C, int dtype, const f
     if (bn_plan(R, C, dtype, &p, &grid)) FGNN_FAIL(FGNN_EUNSUPPORTED, "bn: C=%d not a supported channel count", C);
     if (workspace_bytes < fgnn_bn_workspace_bytes(R, C)) FGNN_FAIL(FGNN_EINVAL, "bn: workspace too small");
     float* ws = (float*)workspace;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     // per-channel shift K = x[0][:] (f32): row 0 of x where it lies — the reducing kernel and the finaliser read it there (until round 6 a
     // 4 us launch copied it into the workspace first: 39 launches of a synthetic-PGM training step); nothing writes x between the two
     const float* ref = dtype == FGNN_F32 ? (const float*)x : nullptr;      // bf16: accumulate against K = 0 (values are O(1) after the
@@ -362,12 +361,9 @@ extern "C" int fgnn_bn_stats(const void* x, int64_t R, int C, int dtype, const f
     }
     const bool inkernel = fold_scratch && 2 * C <= FGNN_FOLD_MAXJ && !fgnn_separate_finalisers();
     p.fold = fgnn_fold_make(ws, inkernel ? fold_scratch : nullptr, grid, C);
-    if (dtype == FGNN_F32) hipLaunchKernelGGL((bn_reduce_kernel<float, 0>), dim3(grid), dim3(BN_THREADS), 0, st, p);
-    else hipLaunchKernelGGL((bn_reduce_kernel<bf16_t, 0>), dim3(grid), dim3(BN_THREADS), 0, st, p);
-    if (!inkernel) hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + BN_FC - 1) / BN_FC), dim3(256), 0, st, ws, grid, C, p.fin);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "bn_stats launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const auto reduce = dtype == FGNN_F32 ? bn_reduce_kernel<float, 0> : bn_reduce_kernel<bf16_t, 0>;
+    if ((rc = fgnn_launch("bn_stats", reduce, dim3(grid), dim3(BN_THREADS), 0, st, p))) return rc;
+    return inkernel ? FGNN_OK : fgnn_launch("bn_stats", bn_stats_final_kernel, dim3((C + BN_FC - 1) / BN_FC), dim3(256), 0, st, ws, grid, C, p.fin);
 }
 
 // Forward statistics from per-workgroup partials somebody else produced: partials[w][0][c] = sum (y - K), partials[w][1][c] =
@@ -378,9 +374,7 @@ extern "C" int fgnn_bn_finalize(const float* partials, int npartials, int C, con
     if (!partials) FGNN_FAIL(FGNN_EINVAL, "bn_finalize: null pointer");
     if ((rc = bn_check_final("bn_finalize", fin))) return rc;
     if (npartials < 1 || npartials > BN_MAXPART || C < 1) FGNN_FAIL(FGNN_EINVAL, "bn_finalize: bad sizes");
-    if (fgnn_bn_finalize_launch(partials, npartials, C, fin, (hipStream_t)stream))
-        FGNN_FAIL(FGNN_ELAUNCH, "bn_finalize launch: %s", hipGetErrorString(hipGetLastError()));
-    return FGNN_OK;
+    return fgnn_bn_finalize_launch(partials, npartials, C, fin, fgnn_stream(stream));
 }
 
 // y = act(x * scale + shift) [+ addend + addend2 + addend3], act = LeakyReLU(slope) (slope 0: ReLU, slope 1: identity).
@@ -398,23 +392,20 @@ extern "C" int fgnn_bn_apply(const void* x, void* y, int64_t R, int C, int dtype
         p.aperiod[a] = addend_period ? addend_period[a] : 1;
         if (p.aperiod[a] < 1) FGNN_FAIL(FGNN_EINVAL, "bn_apply: addend period < 1");
     }
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == FGNN_F32) hipLaunchKernelGGL((bn_apply_kernel<float, 0>), dim3(grid), dim3(BN_THREADS), 0, st, p);
-    else hipLaunchKernelGGL((bn_apply_kernel<bf16_t, 0>), dim3(grid), dim3(BN_THREADS), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "bn_apply launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const auto apply = dtype == FGNN_F32 ? bn_apply_kernel<float, 0> : bn_apply_kernel<bf16_t, 0>;
+    return fgnn_launch("bn_apply", apply, dim3(grid), dim3(BN_THREADS), 0, fgnn_stream(stream), p);
 }
 
 // The reduction half of the backward: per-channel dbeta / dgamma -> dsum [2][C] (in the workspace, behind the partial rows) and
 // ACCUMULATED into gweight / gbias (may be NULL); one launch (the last workgroup finalises).  Host-side helper of this library
-// (csrc/block_tail.hip: BatchNorm1's sums in front of the fused head kernel), not C ABI.
+// (csrc/block_tail.hip: BatchNorm1's sums in front of the fused head kernel), not C ABI.  FGNN_EUNSUPPORTED (no message set: the
+// caller names itself) = no plan for this C; FGNN_ELAUNCH = a launch failed, message set.
 int fgnn_bn_backward_sums(const void* x, const void* gy, int64_t R, int C, int dtype, const float* mean, const float* invstd,
                           const float* gamma, const float* beta, float slope, float* gweight, float* gbias,
                           void* workspace, void* fold_scratch, hipStream_t st, BnParams* out, const float** dsum_out) {
     BnParams p = {};
     int grid;
-    if (bn_plan(R, C, dtype, &p, &grid)) return -1;
+    if (bn_plan(R, C, dtype, &p, &grid)) return FGNN_EUNSUPPORTED;
     float* ws = (float*)workspace;
     float* dsum = ws + (int64_t)BN_MAXPART * 2 * C;
     p.x = x; p.gy = gy; p.out = nullptr; p.ws = ws; p.a = mean; p.b = invstd; p.gamma = gamma; p.beta = beta;
@@ -422,12 +413,13 @@ int fgnn_bn_backward_sums(const void* x, const void* gy, int64_t R, int C, int d
     p.dsum = dsum; p.gweight = gweight; p.gbias = gbias;
     const bool inkernel = fold_scratch && 2 * C <= FGNN_FOLD_MAXJ && !fgnn_separate_finalisers();
     p.fold = fgnn_fold_make(ws, inkernel ? fold_scratch : nullptr, grid, C);
-    if (dtype == FGNN_F32) hipLaunchKernelGGL((bn_reduce_kernel<float, 1>), dim3(grid), dim3(BN_THREADS), 0, st, p);
-    else hipLaunchKernelGGL((bn_reduce_kernel<bf16_t, 1>), dim3(grid), dim3(BN_THREADS), 0, st, p);
-    if (!inkernel) hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + BN_FC - 1) / BN_FC), dim3(256), 0, st, ws, grid, C, dsum, gweight, gbias);
+    const auto reduce = dtype == FGNN_F32 ? bn_reduce_kernel<float, 1> : bn_reduce_kernel<bf16_t, 1>;
+    int rc = fgnn_launch("bn_backward sums", reduce, dim3(grid), dim3(BN_THREADS), 0, st, p);
+    if (!rc && !inkernel)
+        rc = fgnn_launch("bn_backward sums", bn_bwd_final_kernel, dim3((C + BN_FC - 1) / BN_FC), dim3(256), 0, st, ws, grid, C, dsum, gweight, gbias);
     if (out) *out = p;
     if (dsum_out) *dsum_out = dsum;
-    return 0;
+    return rc;
 }
 
 int fgnn_bn_backward_sums_bf16(const void* x, const void* gy, int64_t R, int C, const float* mean, const float* invstd,
@@ -446,20 +438,18 @@ extern "C" int fgnn_bn_backward(const void* x, const void* gy, void* gx, int64_t
     if (!x || !gy || !gx || !mean || !invstd || !gamma || !beta || !workspace)
         FGNN_FAIL(FGNN_EINVAL, "bn_backward: null pointer");
     if (workspace_bytes < fgnn_bn_workspace_bytes(R, C)) FGNN_FAIL(FGNN_EINVAL, "bn: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     BnParams p;
-    if (fgnn_bn_backward_sums(x, gy, R, C, dtype, mean, invstd, gamma, beta, slope, gweight, gbias, workspace, fold_scratch, st, &p, nullptr))
-        FGNN_FAIL(FGNN_EUNSUPPORTED, "bn: C=%d not a supported channel count", C);
+    const int rc = fgnn_bn_backward_sums(x, gy, R, C, dtype, mean, invstd, gamma, beta, slope, gweight, gbias, workspace, fold_scratch, st, &p, nullptr);
+    if (rc == FGNN_EUNSUPPORTED) FGNN_FAIL(FGNN_EUNSUPPORTED, "bn: C=%d not a supported channel count", C);
+    if (rc) return rc;
     int agrid;
     BnParams pa = p;
     pa.out = gx;
     pa.fold.tickets = nullptr;
     (void)bn_plan(R, C, dtype, &pa, &agrid, bn_apply_grid());   // same fields, finer row split
-    if (dtype == FGNN_F32) hipLaunchKernelGGL((bn_apply_kernel<float, 1>), dim3(agrid), dim3(BN_THREADS), 0, st, pa);
-    else hipLaunchKernelGGL((bn_apply_kernel<bf16_t, 1>), dim3(agrid), dim3(BN_THREADS), 0, st, pa);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "bn_backward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const auto apply = dtype == FGNN_F32 ? bn_apply_kernel<float, 1> : bn_apply_kernel<bf16_t, 1>;
+    return fgnn_launch("bn_backward", apply, dim3(agrid), dim3(BN_THREADS), 0, st, pa);
 }
 
 // backward finaliser for partials of (sum g, sum g * x) with the RAW x: dbeta = S0, dgamma = invstd (S1 - mean S0)
@@ -479,9 +469,8 @@ __global__ __launch_bounds__(256) void bn_bwd_final_raw_kernel(const float* ws, 
 
 int fgnn_bn_bwd_final_raw_launch(const float* partials, int npartials, int C, const float* mean, const float* invstd, float* dsum,
                                  float* gweight, float* gbias, hipStream_t st) {
-    hipLaunchKernelGGL(bn_bwd_final_raw_kernel, dim3((C + BN_FC - 1) / BN_FC), dim3(256), 0, st, partials, npartials, C, mean,
-                       invstd, dsum, gweight, gbias);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return fgnn_launch("bn_bwd_final_raw", bn_bwd_final_raw_kernel, dim3((C + BN_FC - 1) / BN_FC), dim3(256), 0, st, partials, npartials, C,
+                       mean, invstd, dsum, gweight, gbias);
 }
 
 // The element-wise half of the backward alone: gx = gamma invstd (g - dbeta / R - xhat dgamma / R), g = gy act'(pre), from sums
@@ -494,12 +483,8 @@ extern "C" int fgnn_bn_backward_apply(const void* x, const void* gy, void* gx, i
     if (!x || !gy || !gx || !mean || !invstd || !gamma || !beta || !dsum)
         FGNN_FAIL(FGNN_EINVAL, "bn_backward_apply: null pointer");
     if (bn_plan(R, C, dtype, &p, &grid, bn_apply_grid())) FGNN_FAIL(FGNN_EUNSUPPORTED, "bn: C=%d not a supported channel count", C);
-    hipStream_t st = (hipStream_t)stream;
     p.x = x; p.gy = gy; p.out = gx; p.a = mean; p.b = invstd; p.gamma = gamma; p.beta = beta;
     p.slope = slope; p.dsum_scale = 1.0f / (float)R; p.dbeta = dsum; p.dgamma = dsum + C;
-    if (dtype == FGNN_F32) hipLaunchKernelGGL((bn_apply_kernel<float, 1>), dim3(grid), dim3(BN_THREADS), 0, st, p);
-    else hipLaunchKernelGGL((bn_apply_kernel<bf16_t, 1>), dim3(grid), dim3(BN_THREADS), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "bn_backward_apply launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const auto apply = dtype == FGNN_F32 ? bn_apply_kernel<float, 1> : bn_apply_kernel<bf16_t, 1>;
+    return fgnn_launch("bn_backward_apply", apply, dim3(grid), dim3(BN_THREADS), 0, fgnn_stream(stream), p);
 }

@@ -535,17 +535,13 @@ extern "C" int fgnn_edge_mlp_forward(const void* x, int64_t x_sb, int64_t x_sc, 
         int64_t g = (B + EM_PAIR - 1) / EM_PAIR;
         if (g > 1024) g = 1024;
         fgnn_note_kernel("edge_mlp_fwd_mfma_kernel");
-        hipLaunchKernelGGL(edge_mlp_fwd_mfma_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, p);
-    } else {
-        int64_t g = (p.R + EM_THREADS * EM_RPT - 1) / (EM_THREADS * EM_RPT);
-        if (g > 4096) g = 4096;
-        fgnn_note_kernel("edge_mlp_fwd_kernel");
-        if (Cin == 7) hipLaunchKernelGGL(edge_mlp_fwd_kernel<7>, dim3((unsigned)g), dim3(EM_THREADS), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(edge_mlp_fwd_kernel<8>, dim3((unsigned)g), dim3(EM_THREADS), 0, (hipStream_t)stream, p);
+        return fgnn_launch("edge_mlp_forward", edge_mlp_fwd_mfma_kernel, dim3((unsigned)g), dim3(256), 0, fgnn_stream(stream), p);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "edge_mlp_forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    int64_t g = (p.R + EM_THREADS * EM_RPT - 1) / (EM_THREADS * EM_RPT);
+    if (g > 4096) g = 4096;
+    fgnn_note_kernel("edge_mlp_fwd_kernel");
+    return fgnn_launch("edge_mlp_forward", Cin == 7 ? edge_mlp_fwd_kernel<7> : edge_mlp_fwd_kernel<8>, dim3((unsigned)g), dim3(EM_THREADS), 0,
+                       fgnn_stream(stream), p);
 }
 
 // one workgroup per CU while its rows fit the LDS staging buffer, more workgroups beyond that
@@ -578,24 +574,15 @@ extern "C" int fgnn_edge_mlp_backward(const void* x, int64_t x_sb, int64_t x_sc,
     const int grid = (int)em_bwd_grid(p.R);
     p.rows_per_wg = (int)((p.R + grid - 1) / grid);
     const size_t lds = (size_t)p.rows_per_wg * 24;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     if (em_mfma_ok(p, true)) {
         fgnn_note_kernel("edge_mlp_bwd_mfma_kernel");
-        hipLaunchKernelGGL(edge_mlp_bwd_mfma_kernel, dim3(grid), dim3(256), 0, st, p);
+        rc = fgnn_launch("edge_mlp_backward", edge_mlp_bwd_mfma_kernel, dim3(grid), dim3(256), 0, st, p);
     } else {
         fgnn_note_kernel("edge_mlp_bwd_kernel");
-        static bool attr_done = false;
-        if (!attr_done) {
-            (void)hipFuncSetAttribute((const void*)edge_mlp_bwd_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, EM_LDS_ROWS * 24);
-            (void)hipFuncSetAttribute((const void*)edge_mlp_bwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, EM_LDS_ROWS * 24);
-            attr_done = true;
-        }
-        if (Cin == 7) hipLaunchKernelGGL(edge_mlp_bwd_kernel<7>, dim3(grid), dim3(EM_BWD_THREADS), lds, st, p);
-        else hipLaunchKernelGGL(edge_mlp_bwd_kernel<8>, dim3(grid), dim3(EM_BWD_THREADS), lds, st, p);
+        rc = fgnn_launch("edge_mlp_backward", Cin == 7 ? edge_mlp_bwd_kernel<7> : edge_mlp_bwd_kernel<8>, dim3(grid), dim3(EM_BWD_THREADS), lds, st, p);
     }
-    hipLaunchKernelGGL(edge_mlp_reduce_kernel, dim3((EM_SLAB + 15) / 16), dim3(256), 0, st, p.ws, grid, Cin, net, gW1, gb1,
+    if (rc) return rc;
+    return fgnn_launch("edge_mlp_backward", edge_mlp_reduce_kernel, dim3((EM_SLAB + 15) / 16), dim3(256), 0, st, p.ws, grid, Cin, net, gW1, gb1,
                        gW2, gb2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "edge_mlp_backward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
 }

@@ -693,8 +693,6 @@ extern "C" int fgnn_factor_layer_forward(int32_t B, const void* var, const void*
     p.idx_v2f_sm = idx_v2f_sm; p.idx_v2f_sk = idx_v2f_sk; p.idx_f2v_sm = idx_f2v_sm; p.idx_f2v_sk = idx_f2v_sk;
     const int lds = (FL_NV + FL_NF + 2 * FL_NV) * FL_XS * 2 + FL_NV * FL_PS * 2 + (FL_NF * FL_KF + FL_NV * FL_KV) * (4 + 8) +
                     2 * FL_NV * 4 + (512 + 128 + 256 + 512 + 24 * 64) * 4 + 2 * 2 * 4 * 64 * 16 + 3 * 64 * 64 * 2;
-    hipError_t e = hipFuncSetAttribute((const void*)factor_layer_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
     int grid = 256;
     if (grid > B) grid = B;
     fgnn_note_kernel("factor_layer_fwd_kernel");
@@ -707,9 +705,8 @@ extern "C" int fgnn_factor_layer_forward(int32_t B, const void* var, const void*
         p.prof = prof_buf;
     }
 #endif
-    void* args[] = {(void*)&p};
-    e = hipLaunchKernel((const void*)factor_layer_fwd_kernel, dim3(grid), dim3(FL_THREADS), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "factor_layer_forward launch: %s", hipGetErrorString(e));
+    const int rc = fgnn_launch("factor_layer_forward", factor_layer_fwd_kernel, dim3(grid), dim3(FL_THREADS), lds, fgnn_stream(stream), p);
+    if (rc) return rc;
 #ifdef FGNN_ENABLE_PROF
     if (p.prof) {                                     // tuning aid: the fourth sample of workgroup 0, shader clocks after every barrier
         long long h[128];

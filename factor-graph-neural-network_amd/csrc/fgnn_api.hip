@@ -75,8 +75,7 @@ __global__ void fgnn_stamp_kernel(unsigned long long* dst) { *dst = wall_clock64
 
 extern "C" int fgnn_stamp(void* dst, void* stream) {
     if (!dst) { fgnn_set_error("fgnn_stamp: null destination"); return FGNN_EINVAL; }
-    hipLaunchKernelGGL(fgnn_stamp_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), static_cast<unsigned long long*>(dst));
-    return FGNN_OK;
+    return fgnn_launch("fgnn_stamp", fgnn_stamp_kernel, dim3(1), dim3(1), 0, fgnn_stream(stream), static_cast<unsigned long long*>(dst));
 }
 
 // diagnostic: one thread spins until the device clock has advanced by `ticks` (100 MHz).  At the head of a captured step it gives
@@ -90,6 +89,5 @@ __global__ void fgnn_spin_kernel(unsigned long long ticks) {
 
 extern "C" int fgnn_spin(int64_t ticks, void* stream) {
     if (ticks < 0 || ticks > 100000000) { fgnn_set_error("fgnn_spin: 0 .. 1e8 ticks (1 s)"); return FGNN_EINVAL; }
-    hipLaunchKernelGGL(fgnn_spin_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), (unsigned long long)ticks);
-    return FGNN_OK;
+    return fgnn_launch("fgnn_spin", fgnn_spin_kernel, dim3(1), dim3(1), 0, fgnn_stream(stream), (unsigned long long)ticks);
 }

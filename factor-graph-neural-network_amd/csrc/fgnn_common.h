@@ -61,12 +61,17 @@ static inline void fgnn_prof_print(const long long*, const char*, int, int, int,
 
 static inline int fgnn_round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+#include "fgnn_launch.h"   // every kernel launch and its error report
+
 // ---- host helpers shared by the translation units (not C ABI) ---------------------------
+// The launching ones return FGNN_OK or FGNN_ELAUNCH with the message already set (fgnn_launch.h): callers pass the code up.
 // mpconv_bwd_res.hip: fold nslab slabs (slab_len apart) of [nw weights + bias] floats into gW / gbias in a fixed order; _ld: the
 // slab's [nw / ncols][ncols] weight block lands in rows `ld` apart (a column block of a wider gW)
-void fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias, hipStream_t st);
-void fgnn_launch_slab_reduce_ld(const float* ws, int nslab, int64_t slab_len, int64_t nw, int ncols, int ld, float* gW,
-                                float* gbias, hipStream_t st);
+int fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias, hipStream_t st);
+int fgnn_launch_slab_reduce_ld(const float* ws, int nslab, int64_t slab_len, int64_t nw, int ncols, int ld, float* gW,
+                               float* gbias, hipStream_t st);
+// the same fold, STORED (out[i] = sum over the slabs): for outputs that are not accumulators
+int fgnn_launch_slab_store(const float* ws, int nslab, int64_t slab_len, float* out, hipStream_t st);
 // fold_batch.hip: called instead of launching a slab fold: true = recorded (deferral is on), false = launch it yourself
 bool fgnn_fold_push(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gb, int kind, int a, int b, int c, int d);
 // bnact.hip: the stand-alone BatchNorm finalisers and the bf16 backward sums

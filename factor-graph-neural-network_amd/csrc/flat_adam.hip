@@ -86,10 +86,7 @@ static int flat_adam_launch(FaParams& a, hipStream_t stream) {
     int64_t g = (a.n4 + 255) / 256;
     if (g > 2048) g = 2048;
     if (g < 1) g = 1;
-    hipLaunchKernelGGL(flat_adam_kernel, dim3((unsigned)g), dim3(256), 0, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "flat_adam launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("flat_adam", flat_adam_kernel, dim3((unsigned)g), dim3(256), 0, stream, a);
 }
 
 // step = 1-based step count (bias corrections 1 - beta^step are formed in double on the host)
@@ -106,7 +103,7 @@ static int flat_adam_host(float* param, const float* grad, float* exp_avg, float
     a.lr_bc1 = (float)((double)lr / bc1);
     a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
     a.eps = eps; a.b1 = beta1; a.b2 = beta2; a.wd = weight_decay; a.gscale = grad_scale;
-    return flat_adam_launch(a, (hipStream_t)stream);
+    return flat_adam_launch(a, fgnn_stream(stream));
 }
 
 // The same update with NOTHING step-dependent in the launch arguments, so that the launch can be recorded into a hipGraph and
@@ -117,15 +114,13 @@ static int flat_adam_dev(float* param, const float* grad, float* exp_avg, float*
                          float grad_scale, int64_t* step_dev, float* coef_dev, const float* clip, fgnn_stream_t stream) {
     if (int rc = flat_adam_check(param, grad, exp_avg, exp_avg_sq, bf16_mirror, n)) return rc;
     if (!lr_dev || !step_dev || !coef_dev) FGNN_FAIL(FGNN_EINVAL, "flat_adam_dev: null lr / step / coefficient buffer");
-    hipLaunchKernelGGL(flat_adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev, lr_dev, beta1, beta2, coef_dev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "flat_adam_tick launch: %s", hipGetErrorString(e));
+    if (int rc = fgnn_launch("flat_adam_tick", flat_adam_tick_kernel, dim3(1), dim3(1), 0, fgnn_stream(stream), step_dev, lr_dev, beta1, beta2, coef_dev)) return rc;
     if (n == 0) return FGNN_OK;
     FaParams a;
     a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.mirror = (uint16_t*)bf16_mirror;
     a.n = n; a.n4 = n / 4; a.coef = coef_dev; a.lr_bc1 = 0.f; a.inv_sqrt_bc2 = 0.f; a.clip = clip;
     a.eps = eps; a.b1 = beta1; a.b2 = beta2; a.wd = weight_decay; a.gscale = grad_scale;
-    return flat_adam_launch(a, (hipStream_t)stream);
+    return flat_adam_launch(a, fgnn_stream(stream));
 }
 
 extern "C" int fgnn_flat_adam(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* bf16_mirror,
@@ -208,15 +203,14 @@ extern "C" int fgnn_grad_norm_clip(const float* grad, int64_t n, float max_norm,
     if ((uintptr_t)grad & 15) FGNN_FAIL(FGNN_EINVAL, "grad_norm_clip: the gradient must be 16-byte aligned");
     if (!workspace || workspace_bytes < fgnn_grad_norm_clip_workspace_bytes() || ((uintptr_t)workspace & 7))
         FGNN_FAIL(FGNN_EINVAL, "grad_norm_clip: an 8-byte aligned workspace of fgnn_grad_norm_clip_workspace_bytes() bytes needed");
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     double* part = (double*)workspace;
     const int64_t n4 = n / 4;
     int64_t g = (n4 + 4 * 256 - 1) / (4 * 256);          // ~4 chunks per thread
     if (g > GN_MAXGRID) g = GN_MAXGRID;
     if (g < 1) g = 1;
-    if (n > 0) hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)g), dim3(256), 0, st, grad, n4, n, part);
-    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(1), 0, st, part, n > 0 ? (int)g : 0, max_norm, grad_scale, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "grad_norm_clip launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    if (n > 0) {
+        if (int rc = fgnn_launch("grad_norm_clip", grad_sumsq_kernel, dim3((unsigned)g), dim3(256), 0, st, grad, n4, n, part)) return rc;
+    }
+    return fgnn_launch("grad_norm_clip", grad_norm_final_kernel, dim3(1), dim3(1), 0, st, part, n > 0 ? (int)g : 0, max_norm, grad_scale, out);
 }

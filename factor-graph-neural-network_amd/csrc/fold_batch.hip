@@ -146,7 +146,7 @@ extern "C" int fgnn_fold_flush(fgnn_stream_t stream) {
         std::lock_guard<std::mutex> lk(g_mu);
         jobs.swap(g_jobs);
     }
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     std::vector<char> done(jobs.size(), 0);
     size_t left = jobs.size();
     while (left) {
@@ -167,9 +167,10 @@ extern "C" int fgnn_fold_flush(fgnn_stream_t stream) {
             --left;
         }
         t.first[t.njobs] = blocks;
-        if (blocks > 0) hipLaunchKernelGGL(fold_batch_kernel, dim3(blocks), dim3(1024), 0, st, t);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "fold_batch launch: %s", hipGetErrorString(e));
+        if (blocks > 0) {
+            const int rc = fgnn_launch("fold_batch", fold_batch_kernel, dim3(blocks), dim3(1024), 0, st, t);
+            if (rc) return rc;
+        }
     }
     return FGNN_OK;
 }

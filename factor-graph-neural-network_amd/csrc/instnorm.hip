@@ -256,23 +256,23 @@ static int in_check(const void* a, const void* b, int B, int N, int C, int dtype
 // rows a thread holds = ceil(N / row groups), rounded up to an instantiated count: fewer registers -> more workgroups
 // per CU -> more bytes in flight (N = 96 at 64 channels needs 3 of the 4 rows N = 128 would)
 template <typename T, bool BWD, int CH>
-static void in_launch_rows(int grid, int N, hipStream_t st, const InParams& p) {
+static int in_launch_rows(const char* what, int grid, int N, hipStream_t st, const InParams& p) {
     constexpr int RG = IN_THREADS / (CH / InChunk<T>::EPC), FULL = 128 / RG;
     const int need = (N + RG - 1) / RG;
-    if (need * 4 <= FULL) hipLaunchKernelGGL((instnorm_vec_kernel<T, BWD, CH, (FULL / 4 > 0 ? FULL / 4 : 1)>), dim3(grid), dim3(IN_THREADS), 0, st, p);
-    else if (need * 2 <= FULL) hipLaunchKernelGGL((instnorm_vec_kernel<T, BWD, CH, (FULL / 2 > 0 ? FULL / 2 : 1)>), dim3(grid), dim3(IN_THREADS), 0, st, p);
-    else if (need * 4 <= FULL * 3) hipLaunchKernelGGL((instnorm_vec_kernel<T, BWD, CH, (FULL * 3 / 4 > 0 ? FULL * 3 / 4 : 1)>), dim3(grid), dim3(IN_THREADS), 0, st, p);
-    else hipLaunchKernelGGL((instnorm_vec_kernel<T, BWD, CH, FULL>), dim3(grid), dim3(IN_THREADS), 0, st, p);
+    void (*kernel)(InParams);
+    if (need * 4 <= FULL) kernel = instnorm_vec_kernel<T, BWD, CH, (FULL / 4 > 0 ? FULL / 4 : 1)>;
+    else if (need * 2 <= FULL) kernel = instnorm_vec_kernel<T, BWD, CH, (FULL / 2 > 0 ? FULL / 2 : 1)>;
+    else if (need * 4 <= FULL * 3) kernel = instnorm_vec_kernel<T, BWD, CH, (FULL * 3 / 4 > 0 ? FULL * 3 / 4 : 1)>;
+    else kernel = instnorm_vec_kernel<T, BWD, CH, FULL>;
+    return fgnn_launch(what, kernel, dim3(grid), dim3(IN_THREADS), 0, st, p);
 }
 
 template <bool BWD>
-static void in_launch_vec(int grid64, int N, int C, int dtype, hipStream_t st, const InParams& p) {
+static int in_launch_vec(const char* what, int grid64, int N, int C, int dtype, hipStream_t st, const InParams& p) {
     // 128 channels per workgroup where the width allows: 256-byte row pieces and every thread busy at N = 48
-    if (C % 128 == 0 && in_wide()) {
-        if (dtype == FGNN_F32) in_launch_rows<float, BWD, 128>(grid64 / 2, N, st, p);
-        else in_launch_rows<bf16_t, BWD, 128>(grid64 / 2, N, st, p);
-    } else if (dtype == FGNN_F32) in_launch_rows<float, BWD, 64>(grid64, N, st, p);
-    else in_launch_rows<bf16_t, BWD, 64>(grid64, N, st, p);
+    if (C % 128 == 0 && in_wide())
+        return dtype == FGNN_F32 ? in_launch_rows<float, BWD, 128>(what, grid64 / 2, N, st, p) : in_launch_rows<bf16_t, BWD, 128>(what, grid64 / 2, N, st, p);
+    return dtype == FGNN_F32 ? in_launch_rows<float, BWD, 64>(what, grid64, N, st, p) : in_launch_rows<bf16_t, BWD, 64>(what, grid64, N, st, p);
 }
 
 extern "C" int fgnn_instnorm_forward(const void* x, void* y, int B, int N, int C, int dtype, int relu,
@@ -282,13 +282,9 @@ extern "C" int fgnn_instnorm_forward(const void* x, void* y, int B, int N, int C
     if (B == 0) return FGNN_OK;
     InParams p = {x, nullptr, nullptr, y, B, N, C, relu};
     const int grid = B * ((C + IN_CH - 1) / IN_CH);
-    if (in_vec_ok(x, y, nullptr, N, C)) {
-        in_launch_vec<false>(grid, N, C, dtype, (hipStream_t)stream, p);
-    } else if (dtype == FGNN_F32) hipLaunchKernelGGL(instnorm_fwd_kernel<float>, dim3(grid), dim3(IN_THREADS), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(instnorm_fwd_kernel<bf16_t>, dim3(grid), dim3(IN_THREADS), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "instnorm forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    if (in_vec_ok(x, y, nullptr, N, C)) return in_launch_vec<false>("instnorm forward", grid, N, C, dtype, fgnn_stream(stream), p);
+    const auto kernel = dtype == FGNN_F32 ? instnorm_fwd_kernel<float> : instnorm_fwd_kernel<bf16_t>;
+    return fgnn_launch("instnorm forward", kernel, dim3(grid), dim3(IN_THREADS), 0, fgnn_stream(stream), p);
 }
 
 extern "C" int fgnn_instnorm_backward(const void* x, const void* gy, void* gx, int B, int N, int C, int dtype,
@@ -299,13 +295,9 @@ extern "C" int fgnn_instnorm_backward(const void* x, const void* gy, void* gx, i
     if (B == 0) return FGNN_OK;
     InParams p = {x, nullptr, gy, gx, B, N, C, relu};
     const int grid = B * ((C + IN_CH - 1) / IN_CH);
-    if (in_vec_ok(x, gy, gx, N, C)) {
-        in_launch_vec<true>(grid, N, C, dtype, (hipStream_t)stream, p);
-    } else if (dtype == FGNN_F32) hipLaunchKernelGGL(instnorm_bwd_kernel<float>, dim3(grid), dim3(IN_THREADS), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(instnorm_bwd_kernel<bf16_t>, dim3(grid), dim3(IN_THREADS), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "instnorm backward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    if (in_vec_ok(x, gy, gx, N, C)) return in_launch_vec<true>("instnorm backward", grid, N, C, dtype, fgnn_stream(stream), p);
+    const auto kernel = dtype == FGNN_F32 ? instnorm_bwd_kernel<float> : instnorm_bwd_kernel<bf16_t>;
+    return fgnn_launch("instnorm backward", kernel, dim3(grid), dim3(IN_THREADS), 0, fgnn_stream(stream), p);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -468,12 +460,14 @@ static int ind_check(const void* x, const float* w, const void* o, int B, int N,
 }
 
 template <typename T, bool BWD>
-static void ind_launch(int grid, int N, hipStream_t st, const IndParams& p) {
+static int ind_launch(const char* what, int grid, int N, hipStream_t st, const IndParams& p) {
     constexpr int RG = IN_THREADS / (IND_CH / InChunk<T>::EPC), FULL = 128 / RG;
     const int need = (N + RG - 1) / RG;
-    if (need * 2 <= FULL) hipLaunchKernelGGL((instnorm_dot_kernel<T, BWD, FULL / 2>), dim3(grid), dim3(IN_THREADS), 0, st, p);
-    else if (need * 4 <= FULL * 3) hipLaunchKernelGGL((instnorm_dot_kernel<T, BWD, FULL * 3 / 4>), dim3(grid), dim3(IN_THREADS), 0, st, p);
-    else hipLaunchKernelGGL((instnorm_dot_kernel<T, BWD, FULL>), dim3(grid), dim3(IN_THREADS), 0, st, p);
+    void (*kernel)(IndParams);
+    if (need * 2 <= FULL) kernel = instnorm_dot_kernel<T, BWD, FULL / 2>;
+    else if (need * 4 <= FULL * 3) kernel = instnorm_dot_kernel<T, BWD, FULL * 3 / 4>;
+    else kernel = instnorm_dot_kernel<T, BWD, FULL>;
+    return fgnn_launch(what, kernel, dim3(grid), dim3(IN_THREADS), 0, st, p);
 }
 
 extern "C" int fgnn_instnorm_dot_forward(const void* x, const float* w, const float* bias, void* out, int B, int N, int C,
@@ -482,10 +476,9 @@ extern "C" int fgnn_instnorm_dot_forward(const void* x, const float* w, const fl
     if (rc) return rc;
     if (B == 0) return FGNN_OK;
     IndParams p = {x, w, bias, nullptr, out, nullptr, B, N};
-    if (dtype == FGNN_F32) ind_launch<float, false>(B, N, (hipStream_t)stream, p);
-    else ind_launch<bf16_t, false>(B, N, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "instnorm_dot forward launch: %s", hipGetErrorString(e));
+    rc = dtype == FGNN_F32 ? ind_launch<float, false>("instnorm_dot forward", B, N, fgnn_stream(stream), p)
+                           : ind_launch<bf16_t, false>("instnorm_dot forward", B, N, fgnn_stream(stream), p);
+    if (rc) return rc;
     fgnn_note_kernel("instnorm_dot_kernel<fwd>");
     return FGNN_OK;
 }
@@ -505,11 +498,10 @@ extern "C" int fgnn_instnorm_dot_backward(const void* x, const float* w, const v
     if (!ws || ws_bytes < fgnn_instnorm_dot_workspace_bytes(B)) FGNN_FAIL(FGNN_EINVAL, "instnorm_dot backward: workspace too small");
     const int grid = B < IND_MAXGRID ? B : IND_MAXGRID;
     IndParams p = {x, w, nullptr, gout, gx, static_cast<float*>(ws), B, N};
-    if (dtype == FGNN_F32) ind_launch<float, true>(grid, N, (hipStream_t)stream, p);
-    else ind_launch<bf16_t, true>(grid, N, (hipStream_t)stream, p);
-    hipLaunchKernelGGL(instnorm_dot_reduce_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, static_cast<const float*>(ws), grid, gw, gbias);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "instnorm_dot backward launch: %s", hipGetErrorString(e));
+    rc = dtype == FGNN_F32 ? ind_launch<float, true>("instnorm_dot backward", grid, N, fgnn_stream(stream), p)
+                           : ind_launch<bf16_t, true>("instnorm_dot backward", grid, N, fgnn_stream(stream), p);
+    if (!rc) rc = fgnn_launch("instnorm_dot backward", instnorm_dot_reduce_kernel, dim3(1), dim3(1024), 0, fgnn_stream(stream), static_cast<const float*>(ws), grid, gw, gbias);
+    if (rc) return rc;
     fgnn_note_kernel("instnorm_dot_kernel<bwd>");
     return FGNN_OK;
 }

@@ -151,11 +151,8 @@ extern "C" int fgnn_ldpc_encode_words(const uint8_t* s, const uint64_t* gwords, 
     if (!s || (!gwords && P > 0) || !cw) FGNN_FAIL(FGNN_EINVAL, "ldpc_encode_words: null pointer");
     const size_t lds = (size_t)(LD_CW_PER_WG + P) * W * sizeof(unsigned long long);          // <= 41 400 B (K = 513, P = 511)
     fgnn_note_kernel("ldpc_encode_words_kernel");
-    hipLaunchKernelGGL(ldpc_encode_words_kernel, dim3((unsigned)grid), dim3(LD_THREADS), lds, (hipStream_t)stream, s,
+    return fgnn_launch("ldpc_encode_words", ldpc_encode_words_kernel, dim3((unsigned)grid), dim3(LD_THREADS), lds, fgnn_stream(stream), s,
                        (const unsigned long long*)gwords, B, K, P, W, cw);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_encode_words launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
 }
 
 extern "C" int fgnn_ldpc_sample_rng_words(uint64_t seed, uint64_t offset, const float* snr_choices, int n_snr, const float* sigma_choices,
@@ -182,10 +179,6 @@ extern "C" int fgnn_ldpc_sample_rng_words(uint64_t seed, uint64_t offset, const 
     for (int i = 0; i < n_sigma; ++i) p.sigma_choices[i] = sigma_choices[i];
     fgnn_note_kernel("ldpc_sample_words_kernel");
     const dim3 grid((unsigned)B), block(LD_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == FGNN_F32) hipLaunchKernelGGL(ldpc_sample_words_kernel<float>, grid, block, 0, st, p);
-    else hipLaunchKernelGGL(ldpc_sample_words_kernel<bf16_t>, grid, block, 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_sample_rng_words launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const auto kernel = dtype == FGNN_F32 ? ldpc_sample_words_kernel<float> : ldpc_sample_words_kernel<bf16_t>;
+    return fgnn_launch("ldpc_sample_rng_words", kernel, grid, block, 0, fgnn_stream(stream), p);
 }

@@ -159,11 +159,8 @@ extern "C" int fgnn_ldpc_encode(const uint8_t* s, const uint64_t* gmask, int64_t
     if (!s || !gmask || !cw) FGNN_FAIL(FGNN_EINVAL, "ldpc_encode: null pointer");
     const int64_t grid = (B + LD_CW_PER_WG - 1) / LD_CW_PER_WG;
     fgnn_note_kernel("ldpc_encode_kernel");
-    hipLaunchKernelGGL(ldpc_encode_kernel, dim3((unsigned)grid), dim3(LD_THREADS), 0, (hipStream_t)stream, s,
+    return fgnn_launch("ldpc_encode", ldpc_encode_kernel, dim3((unsigned)grid), dim3(LD_THREADS), 0, fgnn_stream(stream), s,
                        (const unsigned long long*)gmask, B, K, P, cw);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_encode launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
 }
 
 // Received words and the model's inputs for B codewords of a (nvar, nchk) code with dv checks per variable and dc
@@ -184,17 +181,10 @@ static int ld_channel_launch(bool rng, const uint8_t* cw, const float* snr_db, c
                       rho, nvar, nchk, dv, dc, seed, offset};
     fgnn_note_kernel(rng ? "ldpc_features_kernel<rng>" : "ldpc_features_kernel");
     const dim3 grid((unsigned)B), block(LD_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == FGNN_F32) {
-        if (rng) hipLaunchKernelGGL((ldpc_features_kernel<float, true>), grid, block, 0, st, p, LdNoDraw{});
-        else hipLaunchKernelGGL((ldpc_features_kernel<float, false>), grid, block, 0, st, p, LdNoDraw{});
-    } else {
-        if (rng) hipLaunchKernelGGL((ldpc_features_kernel<bf16_t, true>), grid, block, 0, st, p, LdNoDraw{});
-        else hipLaunchKernelGGL((ldpc_features_kernel<bf16_t, false>), grid, block, 0, st, p, LdNoDraw{});
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_channel_features launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    void (*kernel)(LdFeatParams, LdNoDraw);
+    if (dtype == FGNN_F32) kernel = rng ? ldpc_features_kernel<float, true> : ldpc_features_kernel<float, false>;
+    else kernel = rng ? ldpc_features_kernel<bf16_t, true> : ldpc_features_kernel<bf16_t, false>;
+    return fgnn_launch("ldpc_channel_features", kernel, grid, block, 0, fgnn_stream(stream), p, LdNoDraw{});
 }
 
 extern "C" int fgnn_ldpc_channel_features(const uint8_t* cw, const float* snr_db, const float* sigma_b, float rho,
@@ -241,12 +231,8 @@ extern "C" int fgnn_ldpc_sample_rng(uint64_t seed, uint64_t offset, const float*
     for (int i = 0; i < n_sigma; ++i) d.sigma_choices[i] = sigma_choices[i];
     fgnn_note_kernel("ldpc_features_kernel<rng, draw>");
     const dim3 grid((unsigned)B), block(LD_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == FGNN_F32) hipLaunchKernelGGL((ldpc_features_kernel<float, true, true>), grid, block, 0, st, p, d);
-    else hipLaunchKernelGGL((ldpc_features_kernel<bf16_t, true, true>), grid, block, 0, st, p, d);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_sample_rng launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const auto kernel = dtype == FGNN_F32 ? ldpc_features_kernel<float, true, true> : ldpc_features_kernel<bf16_t, true, true>;
+    return fgnn_launch("ldpc_sample_rng", kernel, grid, block, 0, fgnn_stream(stream), p, d);
 }
 
 // Model inputs from given received words y [B][nvar] f32 (a stored test set's `noizy_sg`): the outputs of
@@ -265,16 +251,12 @@ extern "C" int fgnn_ldpc_received_features(const float* y, const float* snr_db, 
         FGNN_FAIL(FGNN_EINVAL, "ldpc_received_features: null pointer");
     fgnn_note_kernel("ldpc_received_features_kernel");
     const dim3 grid((unsigned)B), block(LD_THREADS);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     if (dtype == FGNN_F32)
-        hipLaunchKernelGGL(ldpc_received_features_kernel<float>, grid, block, 0, st, y, snr_db, snr_sb, snr_sn, var_to_factors,
+        return fgnn_launch("ldpc_received_features", ldpc_received_features_kernel<float>, grid, block, 0, st, y, snr_db, snr_sb, snr_sn, var_to_factors,
                            factor_to_vars, nvar, nchk, dv, dc, (float*)node, (float*)hop, (float*)ef_f2v, (float*)ef_v2f);
-    else
-        hipLaunchKernelGGL(ldpc_received_features_kernel<bf16_t>, grid, block, 0, st, y, snr_db, snr_sb, snr_sn, var_to_factors,
-                           factor_to_vars, nvar, nchk, dv, dc, (bf16_t*)node, (bf16_t*)hop, (bf16_t*)ef_f2v, (bf16_t*)ef_v2f);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_received_features launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("ldpc_received_features", ldpc_received_features_kernel<bf16_t>, grid, block, 0, st, y, snr_db, snr_sb, snr_sn, var_to_factors,
+                       factor_to_vars, nvar, nchk, dv, dc, (bf16_t*)node, (bf16_t*)hop, (bf16_t*)ef_f2v, (bf16_t*)ef_v2f);
 }
 
 // ---- the training loss behind the decoder (round 5) --------------------------------------------------------------------------------
@@ -375,19 +357,18 @@ static int ll_forward_launch(const void* logits, const float* label, const float
     if (!workspace || workspace_bytes < fgnn_ldpc_loss_workspace_bytes() || ((uintptr_t)workspace & 7))
         FGNN_FAIL(FGNN_EINVAL, "ldpc_loss: workspace of fgnn_ldpc_loss_workspace_bytes() bytes needed");
     if ((uintptr_t)counts & 7) FGNN_FAIL(FGNN_EINVAL, "ldpc_loss: counts must be 8-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     const int64_t nl = B * n;
     int grid = (int)((nl + 4 * LL_THREADS - 1) / (4 * LL_THREADS));      // ~4 logits per thread (196 608 logits at the benched size: 48 workgroups)
     if (grid > LL_MAXGRID) grid = LL_MAXGRID;
     if (grid < 1) grid = 1;
     double* part = (double*)workspace;
     unsigned long long* cnt = (unsigned long long*)counts;
-    if (dtype == FGNN_F32) hipLaunchKernelGGL(ldpc_loss_fwd_kernel<float>, dim3(grid), dim3(LL_THREADS), 0, st, (const float*)logits, label, pred, sigma_b, nl, B, part, cnt);
-    else hipLaunchKernelGGL(ldpc_loss_fwd_kernel<bf16_t>, dim3(grid), dim3(LL_THREADS), 0, st, (const bf16_t*)logits, label, pred, sigma_b, nl, B, part, cnt);
-    hipLaunchKernelGGL(ldpc_loss_final_kernel, dim3(1), dim3(64), 0, st, part, grid, nl, B, mse_weight, loss, parts);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_loss forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    rc = dtype == FGNN_F32
+        ? fgnn_launch("ldpc_loss forward", ldpc_loss_fwd_kernel<float>, dim3(grid), dim3(LL_THREADS), 0, st, (const float*)logits, label, pred, sigma_b, nl, B, part, cnt)
+        : fgnn_launch("ldpc_loss forward", ldpc_loss_fwd_kernel<bf16_t>, dim3(grid), dim3(LL_THREADS), 0, st, (const bf16_t*)logits, label, pred, sigma_b, nl, B, part, cnt);
+    if (rc) return rc;
+    return fgnn_launch("ldpc_loss forward", ldpc_loss_final_kernel, dim3(1), dim3(64), 0, st, part, grid, nl, B, mse_weight, loss, parts);
 }
 
 extern "C" int fgnn_ldpc_loss_forward(const void* logits, const float* label, const float* pred, const float* sigma_b, int64_t B,
@@ -409,12 +390,10 @@ extern "C" int fgnn_ldpc_loss_backward(const void* logits, const float* label, c
     int rc = ll_check(logits, label, pred, sigma_b, B, n, dtype);
     if (rc) return rc;
     if (!gloss || !glogits || !gpred) FGNN_FAIL(FGNN_EINVAL, "ldpc_loss: null pointer");
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     const int64_t nl = B * n;
     const int grid = (int)((nl + 255) / 256);
-    if (dtype == FGNN_F32) hipLaunchKernelGGL(ldpc_loss_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)logits, label, pred, sigma_b, gloss, nl, B, mse_weight, (float*)glogits, gpred);
-    else hipLaunchKernelGGL(ldpc_loss_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)logits, label, pred, sigma_b, gloss, nl, B, mse_weight, (bf16_t*)glogits, gpred);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_loss backward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    if (dtype == FGNN_F32)
+        return fgnn_launch("ldpc_loss backward", ldpc_loss_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)logits, label, pred, sigma_b, gloss, nl, B, mse_weight, (float*)glogits, gpred);
+    return fgnn_launch("ldpc_loss backward", ldpc_loss_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)logits, label, pred, sigma_b, gloss, nl, B, mse_weight, (bf16_t*)glogits, gpred);
 }

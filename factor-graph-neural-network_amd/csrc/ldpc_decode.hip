@@ -133,8 +133,5 @@ extern "C" int fgnn_ldpc_decode(const double* bias, const int32_t* col_ptr, cons
         FGNN_FAIL(FGNN_EINVAL, "ldpc_decode: null pointer");
     DecParams p = {bias, col_ptr, row_ptr, row_edge, row_var, x, q1, viol, iters, N, M, E, loops, 1e-40, 0.9999999999};
     fgnn_note_kernel("ldpc_decode_kernel");
-    hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_decode launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("ldpc_decode", ldpc_decode_kernel, dim3((unsigned)B), dim3(64), 0, fgnn_stream(stream), p);
 }

@@ -140,21 +140,16 @@ extern "C" int fgnn_ldpc_error_counts(const void* dec, int dec_kind, int64_t dec
     int64_t grid = (B + LE_WAVES * LE_UNROLL - 1) / (LE_WAVES * LE_UNROLL);
     if (grid > LE_MAXGRID) grid = LE_MAXGRID;
     const size_t lds = (size_t)LE_WAVES * (n_snr * n_sigma + 1) * 4 * sizeof(unsigned long long);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 g((unsigned)grid), blk(LE_THREADS);
     fgnn_note_kernel("ldpc_error_counts_kernel");
-#define LE_LAUNCH(DK, LK) hipLaunchKernelGGL((ldpc_error_counts_kernel<DK, LK>), g, blk, lds, st, p)
+    void (*kernel)(LeParams);
     if (label_kind == FGNN_LABEL_I64) {
-        if (dec_kind == FGNN_DEC_F32) LE_LAUNCH(FGNN_DEC_F32, FGNN_LABEL_I64);
-        else if (dec_kind == FGNN_DEC_BF16) LE_LAUNCH(FGNN_DEC_BF16, FGNN_LABEL_I64);
-        else LE_LAUNCH(FGNN_DEC_U8, FGNN_LABEL_I64);
+        if (dec_kind == FGNN_DEC_F32) kernel = ldpc_error_counts_kernel<FGNN_DEC_F32, FGNN_LABEL_I64>;
+        else if (dec_kind == FGNN_DEC_BF16) kernel = ldpc_error_counts_kernel<FGNN_DEC_BF16, FGNN_LABEL_I64>;
+        else kernel = ldpc_error_counts_kernel<FGNN_DEC_U8, FGNN_LABEL_I64>;
     } else {
-        if (dec_kind == FGNN_DEC_F32) LE_LAUNCH(FGNN_DEC_F32, FGNN_LABEL_U8);
-        else if (dec_kind == FGNN_DEC_BF16) LE_LAUNCH(FGNN_DEC_BF16, FGNN_LABEL_U8);
-        else LE_LAUNCH(FGNN_DEC_U8, FGNN_LABEL_U8);
+        if (dec_kind == FGNN_DEC_F32) kernel = ldpc_error_counts_kernel<FGNN_DEC_F32, FGNN_LABEL_U8>;
+        else if (dec_kind == FGNN_DEC_BF16) kernel = ldpc_error_counts_kernel<FGNN_DEC_BF16, FGNN_LABEL_U8>;
+        else kernel = ldpc_error_counts_kernel<FGNN_DEC_U8, FGNN_LABEL_U8>;
     }
-#undef LE_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_error_counts launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("ldpc_error_counts", kernel, dim3((unsigned)grid), dim3(LE_THREADS), lds, fgnn_stream(stream), p);
 }

@@ -180,10 +180,6 @@ extern "C" int fgnn_ldpc_decode_llr(const float* llr, int64_t llr_sb, const int3
                                                {ldpc_llr_kernel<2, false>, ldpc_llr_kernel<2, true>}};
     const llr_kernel_t kernel = kernels[algorithm][n_layers > 0];
     const int threads = ldpc_word_threads(N, M), lds = (int)per;
-    if (ldpc_set_lds((const void*)kernel, 2 * algorithm + (n_layers > 0), lds) != FGNN_OK) return FGNN_ELAUNCH;      // slots 0..5: kernels[][]
     fgnn_note_kernel("ldpc_llr_kernel<%d,%d>x%d", algorithm, n_layers > 0, threads);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_decode_llr launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("ldpc_decode_llr", kernel, dim3((unsigned)B), dim3(threads), lds, fgnn_stream(stream), p);
 }

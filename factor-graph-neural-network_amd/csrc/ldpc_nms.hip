@@ -318,12 +318,8 @@ extern "C" int fgnn_ldpc_nms_forward(const float* llr, int64_t llr_sb, const int
     p.B = B; p.N = N; p.M = M; p.E = E; p.n_iter = n_iter; p.share = share;
     void (*kernel)(const NmsFwdParams) = stop_early ? ldpc_nms_fwd_kernel<false> : ldpc_nms_fwd_kernel<true>;
     const int threads = ldpc_word_threads(N, M), lds = (int)nms_state_bytes(N, M, E, 0);
-    if (ldpc_set_lds((const void*)kernel, stop_early ? 0 : 1, lds) != FGNN_OK) return FGNN_ELAUNCH;     // slots 0, 1: the forward's
     fgnn_note_kernel("ldpc_nms_fwd_kernel<%d>x%d", !stop_early, threads);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_nms_forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("ldpc_nms_forward", kernel, dim3((unsigned)B), dim3(threads), lds, fgnn_stream(stream), p);
 }
 
 extern "C" int fgnn_ldpc_nms_backward(const float* g_totals, const float* llr, int64_t llr_sb, const int32_t* col_ptr,
@@ -338,8 +334,8 @@ extern "C" int fgnn_ldpc_nms_backward(const float* g_totals, const float* llr, i
     const int cnt = n_iter * W;
     if (B == 0) {
         if (g_alpha && g_beta) {
-            hipError_t e = hipMemsetAsync(g_alpha, 0, 4 * (size_t)cnt, (hipStream_t)stream);
-            if (e == hipSuccess) e = hipMemsetAsync(g_beta, 0, 4 * (size_t)cnt, (hipStream_t)stream);
+            hipError_t e = hipMemsetAsync(g_alpha, 0, 4 * (size_t)cnt, fgnn_stream(stream));
+            if (e == hipSuccess) e = hipMemsetAsync(g_beta, 0, 4 * (size_t)cnt, fgnn_stream(stream));
             if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_nms_backward: hipMemsetAsync: %s", hipGetErrorString(e));
         }
         return FGNN_OK;
@@ -365,14 +361,8 @@ extern "C" int fgnn_ldpc_nms_backward(const float* g_totals, const float* llr, i
     const bool part_lds = state + 8 * (int64_t)cnt <= NMS_PARTIAL_LDS;
     void (*kernel)(const NmsBwdParams) = part_lds ? ldpc_nms_bwd_kernel<true> : ldpc_nms_bwd_kernel<false>;
     const int threads = ldpc_word_threads(N, M), lds = (int)(state + (part_lds ? 8 * (int64_t)cnt : 0));
-    if (ldpc_set_lds((const void*)kernel, part_lds ? 2 : 3, lds) != FGNN_OK) return FGNN_ELAUNCH;       // slots 2, 3: the backward's
     fgnn_note_kernel("ldpc_nms_bwd_kernel<%d>x%d", part_lds, threads);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)G), dim3(threads), lds, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_nms_backward launch: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(ldpc_nms_sum_kernel, dim3((unsigned)((2 * cnt + 31) / 32)), dim3(256), 0, (hipStream_t)stream,
+    if (int rc = fgnn_launch("ldpc_nms_backward", kernel, dim3((unsigned)G), dim3(threads), lds, fgnn_stream(stream), p)) return rc;
+    return fgnn_launch("ldpc_nms_backward sum", ldpc_nms_sum_kernel, dim3((unsigned)((2 * cnt + 31) / 32)), dim3(256), 0, fgnn_stream(stream),
                        (const float*)workspace, G, cnt, g_alpha, g_beta);
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_nms_backward sum launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
 }

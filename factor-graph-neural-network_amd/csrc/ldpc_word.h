@@ -11,15 +11,12 @@
 // violated checks per wave; 8 floats backward); 16-bit row_ptr [M + 1], col_ptr [N + 1]; then whatever the kernel appends.
 #pragma once
 #include "fgnn_common.h"
-#include <atomic>
 #include <math.h>
 #include <stdint.h>
 
 #define LDPC_MAXV 1024      // variables, checks
 #define LDPC_MAXD 16        // edges per variable / per check
 #define LDPC_CLAMP 4096.0f
-#define LDPC_MAX_DEVICES 64
-#define LDPC_LDS_SLOTS 8
 
 extern __shared__ __attribute__((aligned(16))) unsigned char ldpc_lds[];
 
@@ -139,20 +136,4 @@ __device__ __forceinline__ LdpcMinScan ldpc_min_scan(const LdpcWord& s, int r0, 
         else if (a < m2) { m2 = a; i2 = r; }
     }
     return {m1, m2, i1, i2, signs, par};
-}
-
-// Above 48 KiB a kernel needs its dynamic-LDS limit raised once per device; the largest value set so far is remembered per
-// (device, kernel), so that a step replayed or captured after its warm-up makes no such call.  slot: the including file's own number
-// for the kernel, below LDPC_LDS_SLOTS (the function is static: each file has its own memo).
-static int ldpc_set_lds(const void* kernel, int slot, int lds) {
-    static std::atomic<int> set_to[LDPC_MAX_DEVICES][LDPC_LDS_SLOTS];
-    if (slot < 0 || slot >= LDPC_LDS_SLOTS) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_set_lds: slot %d outside 0..%d", slot, LDPC_LDS_SLOTS - 1);
-    if (lds <= 48 * 1024) return FGNN_OK;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= LDPC_MAX_DEVICES) dev = -1;
-    if (dev >= 0 && set_to[dev][slot].load() >= lds) return FGNN_OK;
-    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    if (dev >= 0) set_to[dev][slot].store(lds);
-    return FGNN_OK;
 }

@@ -392,16 +392,10 @@ extern "C" int fgnn_linear_forward(const void* x, const float* W, const float* b
         default: fn = otw == 8 ? (void*)linear_fwd_b16_kernel<8, 8, false> : (void*)linear_fwd_b16_kernel<8, 4, false>; break;
     }
     const int lds = Cout * (Cin + 8) * 2 + Cout * 4 + (LF_WAVES / CG) * 2 * Cout * 4;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(LF_THREADS), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_forward launch: %s", hipGetErrorString(e));
-    if (fin && !inkernel && fgnn_bn_finalize_launch(stats_partials, grid, Cout, fin, (hipStream_t)stream))
-        FGNN_FAIL(FGNN_ELAUNCH, "linear_forward finaliser launch: %s", hipGetErrorString(hipGetLastError()));
-    return FGNN_OK;
+    const int rc = fgnn_launch_fn("linear_forward", fn, dim3(grid), dim3(LF_THREADS), lds, fgnn_stream(stream), args);
+    if (rc || !fin || inkernel) return rc;
+    return fgnn_bn_finalize_launch(stats_partials, grid, Cout, fin, fgnn_stream(stream));
 }
 
 
@@ -435,14 +429,8 @@ extern "C" int fgnn_linear_instnorm_forward(const void* x, const float* W, const
     }
 #undef LI_PICK
     const int lds = Cout * (Cin + 8) * 2 + Cout * 4;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
     void* args[] = {(void*)&q};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(LF_THREADS), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_instnorm_forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch_fn("linear_instnorm_forward", fn, dim3(grid), dim3(LF_THREADS), lds, fgnn_stream(stream), args);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -637,13 +625,7 @@ extern "C" int fgnn_linear_multi_forward(const void* const* x, const int32_t* K,
     if (g < 1) g = 1;
     void* fn = lm_pick(K[0] / 32, K[1] / 32, K[2] / 32);
     const int lds = NW * ws_row * 2;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
     fgnn_note_kernel("linear_multi_b16_kernel<%d, %d, %d>", K[0] / 32, K[1] / 32, K[2] / 32);
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3((unsigned)g, (unsigned)ny), dim3(LF_THREADS), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_multi_forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch_fn("linear_multi_forward", fn, dim3((unsigned)g, (unsigned)ny), dim3(LF_THREADS), lds, fgnn_stream(stream), args);
 }

@@ -351,19 +351,12 @@ static int wgrad_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
     p.omagic = p.oc == 1 ? 0u : (unsigned)((0x100000000ULL + p.oc - 1) / p.oc);
     const int lds = (pl.mode ? WV_ROWS : WG_ROWS) * (p.XS + p.GS) * 4;
     void* fn = wgrad_kernel(c, pl).fn;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(pl.gx, pl.gy), dim3(WG_THREADS), args, lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad launch: %s", hipGetErrorString(e));
+    const int rc = fgnn_launch_fn("linear_wgrad", fn, dim3(pl.gx, pl.gy), dim3(WG_THREADS), lds, c.stream, args);
+    if (rc) return rc;
     const int64_t slab_len = (int64_t)p.Cop * p.Cip + p.Cop;
-    hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3((unsigned)((slab_len + 15) / 16), pl.gy), dim3(256), 0,
+    return fgnn_launch("linear_wgrad reduce", linear_wgrad_reduce_kernel, dim3((unsigned)((slab_len + 15) / 16), pl.gy), dim3(256), 0,
                        c.stream, p.ws, pl.gx, Cin, Cout, p.Cip, p.Cop, p.oc, c.gW[0], c.gb[0]);
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad reduce launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
 }
 
 // The families, most specialised first, each for one storage type (-1: both); the first whose plan takes the call
@@ -406,7 +399,7 @@ extern "C" int fgnn_linear_wgrad(const void* x, const void* gy, int64_t R, int C
     if (!x || !gy || !gW || !workspace) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: null pointer");
     if (R <= 0 || R > 0x7fffffff || Cin <= 0 || Cout <= 0) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: bad sizes");
     if (dtype != FGNN_F32 && dtype != FGNN_BF16) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad: unknown dtype %d", dtype);
-    const FgnnWgradCall c = {x, R, Cin, dtype, 1, false, {gy}, {Cout}, {gW}, {gb}, workspace, workspace_bytes, (hipStream_t)stream};
+    const FgnnWgradCall c = {x, R, Cin, dtype, 1, false, {gy}, {Cout}, {gW}, {gb}, workspace, workspace_bytes, fgnn_stream(stream)};
     FgnnWgradPlan pl;
     const int f = wgrad_family(c, &pl);
     if (f < 0) FGNN_FAIL(FGNN_EUNSUPPORTED, "linear_wgrad: Cin=%d too wide for the register tiling", Cin);
@@ -468,6 +461,6 @@ extern "C" int fgnn_linear_wgrad_multi(const void* x, int64_t R, int32_t Cin, in
     }
     if ((uintptr_t)x & 7) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: x not 8-byte aligned");
     if (workspace_bytes < pl.ws_bytes) FGNN_FAIL(FGNN_EINVAL, "linear_wgrad_multi: workspace too small");
-    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = (hipStream_t)stream;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = fgnn_stream(stream);
     return fgnn_wgrad_b16_launch(c, pl);
 }

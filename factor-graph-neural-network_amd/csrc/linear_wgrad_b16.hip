@@ -570,19 +570,16 @@ int fgnn_wgrad_narrow_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
     p.x = (const uint16_t*)c.x; p.gy = (const uint16_t*)c.gy[0]; p.ws = (float*)c.workspace;
     p.R = (int)c.R; p.Cin = c.Cin; p.Cout = c.cout[0]; p.nso = 1; p.S = 1; p.RW = WB_WAVES;
     const int lds = (WB_WAVES / 2) * WN_NACC * 64 * 4;
+    auto kernel = linear_wgrad_b16_narrow_kernel<true>;
+    auto reduce = wgn_reduce_kernel<true>;
+    if (!narrow_x) { kernel = linear_wgrad_b16_narrow_kernel<false>; reduce = wgn_reduce_kernel<false>; }
     for (int woff = 0; woff < (narrow_x ? p.Cout : p.Cin); woff += 64) {     // the kernel reads 64 channels from the pointer, rows at the full stride
-        if (narrow_x) {
-            p.gy = (const uint16_t*)c.gy[0] + woff;
-            hipLaunchKernelGGL(linear_wgrad_b16_narrow_kernel<true>, dim3(pl.gx), dim3(WB_THREADS), lds, c.stream, p);
-            hipLaunchKernelGGL(wgn_reduce_kernel<true>, dim3(WN_NACC), dim3(1024), 0, c.stream, p.ws, pl.gx, p.Cin, p.Cout, woff, c.gW[0], c.gb[0]);
-        } else {
-            p.x = (const uint16_t*)c.x + woff;
-            hipLaunchKernelGGL(linear_wgrad_b16_narrow_kernel<false>, dim3(pl.gx), dim3(WB_THREADS), lds, c.stream, p);
-            hipLaunchKernelGGL(wgn_reduce_kernel<false>, dim3(WN_NACC), dim3(1024), 0, c.stream, p.ws, pl.gx, p.Cin, p.Cout, woff, c.gW[0], c.gb[0]);
-        }
+        if (narrow_x) p.gy = (const uint16_t*)c.gy[0] + woff;
+        else p.x = (const uint16_t*)c.x + woff;
+        int rc = fgnn_launch("linear_wgrad_b16 narrow", kernel, dim3(pl.gx), dim3(WB_THREADS), lds, c.stream, p);
+        if (!rc) rc = fgnn_launch("linear_wgrad_b16 narrow", reduce, dim3(WN_NACC), dim3(1024), 0, c.stream, p.ws, pl.gx, p.Cin, p.Cout, woff, c.gW[0], c.gb[0]);
+        if (rc) return rc;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad_b16 narrow launch: %s", hipGetErrorString(e));
     return FGNN_OK;
 }
 
@@ -658,42 +655,28 @@ int fgnn_wgrad_b16_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
         p.couts[s] = c.cout[s < c.nsrc ? s : 0];
     }
     for (int s = 0; s <= WB_MAXSRC; ++s) p.sb[s] = pl.sb[s];
-    hipError_t e;
+    int rc;
     if (k.staged) {
         WglParams q = {};
         wl_stages(c, S, &q);
         q.b = p;
-        void* fn = k.fn;
-        const int bytes = q.nst * q.stage_bytes;
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
         void* args[] = {(void*)&q};
-        e = hipLaunchKernel(fn, dim3(gx), dim3(WB_THREADS), args, bytes, c.stream);
+        rc = fgnn_launch_fn("linear_wgrad_b16", k.fn, dim3(gx), dim3(WB_THREADS), q.nst * q.stage_bytes, c.stream, args);
     } else {
-        void* fn = k.fn;
         const int lds = S * (RW / 2) * WB_NACC * 64 * 4;                   // 0 when every slice has one row-wave
-        if (lds > 48 * 1024) {
-            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        }
         void* args[] = {(void*)&p};
-        e = hipLaunchKernel(fn, dim3(gx), dim3(WB_THREADS), args, lds, c.stream);
+        rc = fgnn_launch_fn("linear_wgrad_b16", k.fn, dim3(gx), dim3(WB_THREADS), lds, c.stream, args);
     }
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad_b16 launch: %s", hipGetErrorString(e));
+    if (rc) return rc;
     const int64_t stride = (int64_t)S * WB_NACC * 64;                  // distance between the workgroups' slabs
     for (int s = 0; s < c.nsrc; ++s) {
         const int Ss = pl.sb[s + 1] - pl.sb[s], nso = c.cout[s] / 64;
         const int64_t len = (int64_t)Ss * WB_NACC * 64;
         const float* ws_s = p.ws + (int64_t)pl.sb[s] * WB_NACC * 64;
         if (fgnn_fold_push(ws_s, gx, stride, len, c.gW[s], c.gb[s], k.staged ? 2 : 1, Ss, nso, c.Cin, c.cout[s])) continue;      // recorded (fold_batch.hip)
-        if (k.staged)
-            hipLaunchKernelGGL(wgb_reduce_kernel<true>, dim3((unsigned)(len / 64)), dim3(1024), 0, c.stream, ws_s, gx, stride, nso, c.Cin, c.cout[s],
-                               c.gW[s], c.gb[s]);
-        else
-            hipLaunchKernelGGL(wgb_reduce_kernel<false>, dim3((unsigned)(len / 64)), dim3(1024), 0, c.stream, ws_s, gx, stride, nso, c.Cin, c.cout[s],
-                               c.gW[s], c.gb[s]);
+        const auto reduce = k.staged ? wgb_reduce_kernel<true> : wgb_reduce_kernel<false>;
+        if ((rc = fgnn_launch("linear_wgrad_b16 reduce", reduce, dim3((unsigned)(len / 64)), dim3(1024), 0, c.stream, ws_s, gx, stride, nso, c.Cin, c.cout[s],
+                              c.gW[s], c.gb[s]))) return rc;
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad_b16 reduce launch: %s", hipGetErrorString(e));
     return FGNN_OK;
 }

@@ -227,14 +227,13 @@ int fgnn_wgrad_f32_launch(const FgnnWgradCall& c, const FgnnWgradPlan& pl) {
     p.x = (const float*)c.x; p.gy = (const float*)c.gy[0]; p.ws = (float*)c.workspace; p.R = (int)c.R; p.Cin = Cin; p.Cout = Cout;
     p.rows_per_chunk = pl.rows; p.nblk_c = pl.aux; p.want_bias = c.gb[0] != nullptr;
     const dim3 grid(pl.gx, pl.gy), block(WF_THREADS);
+    void (*kernel)(WfParams);
     switch (wq_form(Cin, Cout)) {
-    case WQ_64x64: hipLaunchKernelGGL((linear_wgrad_f32q_kernel<64, 64>), grid, block, 0, c.stream, p); break;
-    case WQ_64x128: hipLaunchKernelGGL((linear_wgrad_f32q_kernel<64, 128>), grid, block, 0, c.stream, p); break;
-    case WQ_128x64: hipLaunchKernelGGL((linear_wgrad_f32q_kernel<128, 64>), grid, block, 0, c.stream, p); break;
-    default: hipLaunchKernelGGL((linear_wgrad_f32q_kernel<128, 128>), grid, block, 0, c.stream, p); break;
+    case WQ_64x64: kernel = linear_wgrad_f32q_kernel<64, 64>; break;
+    case WQ_64x128: kernel = linear_wgrad_f32q_kernel<64, 128>; break;
+    case WQ_128x64: kernel = linear_wgrad_f32q_kernel<128, 64>; break;
+    default: kernel = linear_wgrad_f32q_kernel<128, 128>; break;
     }
-    fgnn_launch_slab_reduce(p.ws, pl.gx, slab_len, nw, c.gW[0], c.gb[0], c.stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "linear_wgrad f32 launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const int rc = fgnn_launch("linear_wgrad f32", kernel, grid, block, 0, c.stream, p);
+    return rc ? rc : fgnn_launch_slab_reduce(p.ws, pl.gx, slab_len, nw, c.gW[0], c.gb[0], c.stream);
 }

@@ -358,10 +358,6 @@ extern "C" int fgnn_mpconv_block_forward_rows(const fgnn_mpconv_desc* d, const v
 #undef KB_CASE
     if (!fn) FGNN_FAIL(FGNN_EUNSUPPORTED, "mpconv_block_forward: nin=%d nout=%d not instantiated", nin, nout);
     if (lds > 160 * 1024) FGNN_FAIL(FGNN_EUNSUPPORTED, "mpconv_block_forward: %d B of LDS", lds);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
     int wg_per_cu = (160 * 1024) / lds;
     if (wg_per_cu > 2) wg_per_cu = 2;
     if (wg_per_cu < 1) wg_per_cu = 1;
@@ -369,9 +365,7 @@ extern "C" int fgnn_mpconv_block_forward_rows(const fgnn_mpconv_desc* d, const v
     if (grid > d->B) grid = d->B;
     fgnn_note_kernel("mpconv_block_fwd_kernel<%d, %d, %d>", d->k, nin / 64, nout / 64);
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(KB_THREADS), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv_block_forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch_fn("mpconv_block_forward", fn, dim3(grid), dim3(KB_THREADS), lds, fgnn_stream(stream), args);
 }
 
 // ========================================================================================
@@ -805,24 +799,16 @@ extern "C" int fgnn_mpconv_block_forward_fanout(const fgnn_mpconv_desc* d, const
         void* fr = nin == 64 ? (void*)mpconv_block_rows1_kernel<1> : nin == 128 ? (void*)mpconv_block_rows1_kernel<2> : (void*)mpconv_block_rows1_kernel<4>;
         fgnn_note_kernel("mpconv_block_rows1_kernel<%d>", nin / 64);
         void* rargs[] = {(void*)&p};
-        hipError_t er = hipLaunchKernel(fr, dim3((d->B + 15) / 16), dim3(64), rargs, 0, (hipStream_t)stream);
-        if (er != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv_block_forward_fanout (one row) launch: %s", hipGetErrorString(er));
-        return FGNN_OK;
+        return fgnn_launch_fn("mpconv_block_forward_fanout (one row)", fr, dim3((d->B + 15) / 16), dim3(64), 0, fgnn_stream(stream), rargs);
     }
     const int lds = nin * 64 * 4 + 64 * 64 * 4 + nout * KB_XSB * 2 + 8 * 128 * 4;
     void* fn = nin == 64 ? (void*)mpconv_block_fanout_kernel<1> : nin == 128 ? (void*)mpconv_block_fanout_kernel<2>
                                                                              : (void*)mpconv_block_fanout_kernel<4>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
     int grid = (d->B + 7) / 8;
     if (grid > 512) grid = 512;
     fgnn_note_kernel("mpconv_block_fanout_kernel<%d>", nin / 64);
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(512), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv_block_forward_fanout launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch_fn("mpconv_block_forward_fanout", fn, dim3(grid), dim3(512), lds, fgnn_stream(stream), args);
 }
 
 // Fan-in form: d describes the inner operator with M = 1, k = N, net = 1, nin = nou = 64, and the neighbour list must
@@ -849,15 +835,9 @@ extern "C" int fgnn_mpconv_block_forward_fanin(const fgnn_mpconv_desc* d, const 
     const int lds = 64 * (nin + 8) * 2 + 64 * nout * 2 + 8 * 64 * 4;
     void* fn = nin == 64 ? (void*)mpconv_block_fanin_kernel<1> : nin == 128 ? (void*)mpconv_block_fanin_kernel<2>
                                                                             : (void*)mpconv_block_fanin_kernel<4>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
     int grid = (d->B + 7) / 8;
     if (grid > 512) grid = 512;
     fgnn_note_kernel("mpconv_block_fanin_kernel<%d>", nin / 64);
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(512), args, lds, (hipStream_t)stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv_block_forward_fanin launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch_fn("mpconv_block_forward_fanin", fn, dim3(grid), dim3(512), lds, fgnn_stream(stream), args);
 }

@@ -518,19 +518,11 @@ static int generic_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
     const int64_t nw = R_rows * d->nou * d->net, slab_len = nw + d->nou;
     p.slab = (float*)c.workspace;
     p.chunk = pl.aux;
-    if (pl.lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
-    }
     fgnn_note_kernel("mpconv_bwd_kernel<%s, %d, %d>", d->dtype ? "bf16_t" : "float",
                      (d->net == 1 || d->net == 4 || d->net == 16) ? d->net : 0, d->agg);
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward launch: %s", hipGetErrorString(e));
-    fgnn_launch_slab_reduce(p.slab, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward fold launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const int rc = fgnn_launch_fn("mpconv backward", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args);
+    return rc ? rc : fgnn_launch_slab_reduce(p.slab, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
 }
 
 // The backward's families, most specialised first; the first whose plan takes the call runs it.
@@ -570,7 +562,7 @@ extern "C" int fgnn_mpconv_backward_with_tables(const fgnn_mpconv_desc* d, const
     if (d->agg == FGNN_AGG_MAX && !argmax) FGNN_FAIL(FGNN_EINVAL, "max aggregator needs the forward's argmax");
     if (d->B == 0) return FGNN_OK;
     const FgnnBwdCall c = {d, x, nn_idx, etype, filters, gz, z, argmax, gx, getype, gfilters, gbias, workspace, workspace_bytes,
-                           tables, (hipStream_t)stream};
+                           tables, fgnn_stream(stream)};
     return bwd_run(c);
 }
 

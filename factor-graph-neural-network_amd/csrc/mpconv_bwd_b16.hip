@@ -57,8 +57,6 @@ struct Bb16Params {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fgnn_lds_bb[];
 
-void fgnn_launch_w_transpose(const float* W, float* Wt, int nin, int ncols, hipStream_t st);
-
 
 // phase-timeline stamps (tuning aid): compiled in only with -DFGNN_ENABLE_PROF, read with FGNN_PROF=1
 #ifdef FGNN_ENABLE_PROF
@@ -554,18 +552,12 @@ int fgnn_bwd_b16_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
     p.ws = (float*)c.workspace;
     p.Wt = p.ws + 256 * slab_len;
     { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
-    if (pl.lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
-    }
     fgnn_note_kernel("mpconv_bwd_b16_kernel<%d, %d>", d->nin / 32, d->nou / 32);
     p.prof = fgnn_prof_begin();
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv bf16 backward launch: %s", hipGetErrorString(e));
-    fgnn_launch_slab_reduce(p.ws, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward helper launch: %s", hipGetErrorString(e));
+    int rc = fgnn_launch_fn("mpconv bf16 backward", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args);
+    if (!rc) rc = fgnn_launch_slab_reduce(p.ws, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
+    if (rc) return rc;
     fgnn_prof_print(p.prof, "b16 bwd", 0, 1, 41, 0);             // phase timeline of one sample (cycles at 100 MHz s_memtime)
     return FGNN_OK;
 }

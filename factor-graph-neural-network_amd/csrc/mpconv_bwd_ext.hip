@@ -1144,22 +1144,15 @@ int fgnn_bwd_ext_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
     p.et_se = d->et_se; p.et_sm = d->et_sm; p.et_sk = d->et_sk;
     p.slab_len = slab_len; p.get_len = get_len;
     bx_layout(d, pl.mode, pl.split, &p);
-    hipError_t e;
+    int rc;
     if (pl.mode) {                                    // the filters' bf16 pieces, behind the slabs in the workspace
         uint16_t* wq = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(c.workspace) + (grid * slab_len + (c.getype ? grid * get_len : 0)) * 4);
         p.wq1 = wq;
         p.wq2 = wq + (int64_t)3 * BQ_WPIECE;
-        void* prep = pl.mode == 3 ? (void*)bq_prep_kernel<3> : (void*)bq_prep_kernel<2>;
-        const float* Wf = c.W;
-        uint16_t* a1 = wq;
-        uint16_t* a2 = wq + (int64_t)3 * BQ_WPIECE;
-        int is_diff = d->ext == FGNN_EXT_DIFF;
-        void* pargs[] = {(void*)&Wf, (void*)&a1, (void*)&a2, (void*)&is_diff};
-        e = hipLaunchKernel(prep, dim3(BX_NCOLS / 256, BX_NIN), dim3(256), pargs, 0, c.stream);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ext backward (filter pieces) launch: %s", hipGetErrorString(e));
+        const auto prep = pl.mode == 3 ? bq_prep_kernel<3> : bq_prep_kernel<2>;
+        if ((rc = fgnn_launch("mpconv ext backward (filter pieces)", prep, dim3(BX_NCOLS / 256, BX_NIN), dim3(256), 0, c.stream,
+                              c.W, wq, wq + (int64_t)3 * BQ_WPIECE, d->ext == FGNN_EXT_DIFF))) return rc;
     }
-    e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
     if (pl.mode) fgnn_note_kernel("mpconv_bwd_extq_kernel<%d, %s>", pl.mode, pl.split ? "true" : "false");
     else fgnn_note_kernel("mpconv_bwd_ext_kernel<%d, %s, %s>", d->agg, d->nou != BX_NOU ? "true" : "false", p.wvec ? "true" : "false");
     p.prof = fgnn_prof_begin();
@@ -1168,13 +1161,9 @@ int fgnn_bwd_ext_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
     if (!pl.mode && getenv("FGNN_EXT_DBG")) p.dbg = atoi(getenv("FGNN_EXT_DBG"));
 #endif
     void* args[] = {(void*)&p};
-    e = hipLaunchKernel(pl.fn, dim3(grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, pl.mode ? "mpconv ext backward (split form) launch: %s" : "mpconv ext backward launch: %s", hipGetErrorString(e));
+    if ((rc = fgnn_launch_fn(pl.mode ? "mpconv ext backward (split form)" : "mpconv ext backward", pl.fn, dim3(grid), dim3(pl.block), pl.lds, c.stream, args))) return rc;
     // (exact kernel: one stage of workgroup 0: A start, A end, B1 start, B1 end, B2 end, C start, C end; shader clocks)
     fgnn_prof_print(p.prof, pl.mode ? "extq bwd" : "ext bwd", 0, 8, 8, 8);
-    fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW, c.gbias, c.stream);
-    if (c.getype) fgnn_launch_slab_store(p.get_ws, grid, get_len, (float*)c.getype, c.stream);
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ext backward helper launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    if ((rc = fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW, c.gbias, c.stream))) return rc;
+    return c.getype ? fgnn_launch_slab_store(p.get_ws, grid, get_len, (float*)c.getype, c.stream) : FGNN_OK;
 }

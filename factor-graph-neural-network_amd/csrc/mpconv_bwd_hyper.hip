@@ -290,20 +290,12 @@ int fgnn_bwd_hyper_plan(const FgnnBwdCall& c, const FgnnSwitches&, FgnnPlan* pl)
 int fgnn_bwd_hyper_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
     const fgnn_mpconv_desc* d = c.d;
     const int64_t nw = (int64_t)d->nin * d->nou, slab_len = nw + d->nou;
-    if (pl.lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
-    }
     BhParams p;
     p.d = *d;
     p.x = c.x; p.idx = c.idx; p.et = c.et; p.W = c.W; p.gz = c.gz; p.argmax = c.argmax; p.gx = c.gx;
     p.ws = (float*)c.workspace; p.has_bias = c.gbias != nullptr;
     fgnn_note_kernel("mpconv_bwd_%s_kernel<%s, %d, %d>", pl.mode ? "fanin" : "fanout", d->dtype ? "bf16_t" : "float", d->nin / 64, d->nou / 64);
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv hyper-edge backward launch: %s", hipGetErrorString(e));
-    fgnn_launch_slab_reduce(p.ws, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward helper launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const int rc = fgnn_launch_fn("mpconv hyper-edge backward", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args);
+    return rc ? rc : fgnn_launch_slab_reduce(p.ws, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
 }

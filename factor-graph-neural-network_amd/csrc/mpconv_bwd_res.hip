@@ -602,30 +602,25 @@ __global__ __launch_bounds__(1024) void bres_reduce_kernel(const float* __restri
 }
 
 // (fgnn_common.h) Fold `nslab` slabs of [nw + nou] floats into gW / gbias.
-void fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias,
-                             hipStream_t st) {
-    if (fgnn_fold_push(ws, nslab, slab_len, nw, gW, gbias, 0, 1, 1, 0, 0)) return;       // recorded: one launch folds every slab set of the pass
-    hipLaunchKernelGGL(bres_reduce_kernel, dim3((unsigned)((slab_len + 63) / 64)), dim3(1024), 0, st, ws, nslab,
+int fgnn_launch_slab_reduce(const float* ws, int nslab, int64_t slab_len, int64_t nw, float* gW, float* gbias,
+                            hipStream_t st) {
+    if (fgnn_fold_push(ws, nslab, slab_len, nw, gW, gbias, 0, 1, 1, 0, 0)) return FGNN_OK;       // recorded: one launch folds every slab set of the pass
+    return fgnn_launch("slab reduce", bres_reduce_kernel, dim3((unsigned)((slab_len + 63) / 64)), dim3(1024), 0, st, ws, nslab,
                        slab_len, nw, gW, gbias, 0, 1, 1);
 }
 
 // The same with the slab's [nw / ncols][ncols] weight block landing in rows `ld` apart (a column block of a wider gfilters).
-void fgnn_launch_slab_reduce_ld(const float* ws, int nslab, int64_t slab_len, int64_t nw, int ncols, int ld, float* gW,
-                                float* gbias, hipStream_t st) {
-    if (fgnn_fold_push(ws, nslab, slab_len, nw, gW, gbias, 0, ncols, ld, 0, 0)) return;
-    hipLaunchKernelGGL(bres_reduce_kernel, dim3((unsigned)((slab_len + 63) / 64)), dim3(1024), 0, st, ws, nslab,
+int fgnn_launch_slab_reduce_ld(const float* ws, int nslab, int64_t slab_len, int64_t nw, int ncols, int ld, float* gW,
+                               float* gbias, hipStream_t st) {
+    if (fgnn_fold_push(ws, nslab, slab_len, nw, gW, gbias, 0, ncols, ld, 0, 0)) return FGNN_OK;
+    return fgnn_launch("slab reduce", bres_reduce_kernel, dim3((unsigned)((slab_len + 63) / 64)), dim3(1024), 0, st, ws, nslab,
                        slab_len, nw, gW, gbias, 0, ncols, ld);
 }
 
 // The same fold, STORED (out[i] = sum_w ws[w][i]): for outputs that are not accumulators (the batch-summed edge-type gradient).
-void fgnn_launch_slab_store(const float* ws, int nslab, int64_t slab_len, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(bres_reduce_kernel, dim3((unsigned)((slab_len + 63) / 64)), dim3(1024), 0, st, ws, nslab,
-                       slab_len, slab_len, out, (float*)nullptr, 1, 1, 1);
-}
-
-void fgnn_launch_w_transpose(const float* W, float* Wt, int nin, int ncols, hipStream_t st) {
-    hipLaunchKernelGGL(bres_transpose_kernel, dim3((ncols + 31) / 32, (nin + 31) / 32), dim3(256), 0, st, W, Wt, nin,
-                       ncols);
+int fgnn_launch_slab_store(const float* ws, int nslab, int64_t slab_len, float* out, hipStream_t st) {
+    return fgnn_launch("slab store", bres_reduce_kernel, dim3((unsigned)((slab_len + 63) / 64)), dim3(1024), 0, st, ws, nslab,
+                       slab_len, slab_len, out, nullptr, 1, 1, 1);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -759,25 +754,18 @@ int fgnn_bwd_res_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
     p.x = c.x; p.idx = c.idx; p.et = c.et; p.W = c.W; p.gz = c.gz; p.argmax = c.argmax;
     p.gx = c.gx; p.get = c.getype; p.has_bias = c.gbias != nullptr;
     { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
-    if (pl.lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
-    }
     const int ncols = d->nou * d->net, KS = d->nin / 4, NPASS = (ncols + BR_PASS_COLS - 1) / BR_PASS_COLS;
     const int64_t nw = (int64_t)d->nin * ncols;
     const int64_t slab_len = nw + d->nou;
     p.ws = (float*)c.workspace;
     float* Wt = p.ws + 256 * slab_len;
     p.Wt = Wt;
-    hipLaunchKernelGGL(bres_transpose_kernel, dim3((ncols + 31) / 32, (d->nin + 31) / 32), dim3(256), 0, c.stream,
-                       c.W, Wt, d->nin, ncols);
+    int rc = fgnn_launch("mpconv backward helper", bres_transpose_kernel, dim3((ncols + 31) / 32, (d->nin + 31) / 32), dim3(256), 0, c.stream,
+                         c.W, Wt, d->nin, ncols);
+    if (rc) return rc;
     fgnn_note_kernel("mpconv_bwd_res_kernel<%s, %d, %d, %d, %s>", d->dtype ? "bf16_t" : "float", d->net, KS, NPASS,
                      (KS == 16 && NPASS <= 2) ? "true" : "false");
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv resident backward launch: %s", hipGetErrorString(e));
-    fgnn_launch_slab_reduce(p.ws, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward helper launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    if ((rc = fgnn_launch_fn("mpconv resident backward", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args))) return rc;
+    return fgnn_launch_slab_reduce(p.ws, pl.grid, slab_len, nw, c.gW, c.gbias, c.stream);
 }

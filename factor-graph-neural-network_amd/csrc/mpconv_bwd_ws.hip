@@ -802,11 +802,8 @@ extern "C" int fgnn_mpconv_backward_tables(const fgnn_mpconv_desc* d, const int6
     const int KC = d->k, DEG = KC == 6 ? 3 : 6, indeg = d->reserved & 0xffff;
     if (bw_tables_count(d) == 0 || indeg < 1 || indeg > DEG)
         FGNN_FAIL(FGNN_EUNSUPPORTED, "mpconv_backward_tables: not a shape / in-degree of the table-driven backward");
-    if (KC == 6) hipLaunchKernelGGL((mpconv_bwd_ws_tables_kernel<6, 3>), dim3(1), dim3(BW_THREADS), 0, (hipStream_t)stream, nn_idx, d->N, d->M, (int*)tables);
-    else hipLaunchKernelGGL((mpconv_bwd_ws_tables_kernel<3, 6>), dim3(1), dim3(BW_THREADS), 0, (hipStream_t)stream, nn_idx, d->N, d->M, (int*)tables);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv_backward_tables launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const auto kernel = KC == 6 ? mpconv_bwd_ws_tables_kernel<6, 3> : mpconv_bwd_ws_tables_kernel<3, 6>;
+    return fgnn_launch("mpconv_backward_tables", kernel, dim3(1), dim3(BW_THREADS), 0, fgnn_stream(stream), nn_idx, d->N, d->M, (int*)tables);
 }
 
 // 64 -> 64, 64 -> 128 as two launches over the output-channel halves (pl->split), 128 -> 64 as two launches over the input-channel
@@ -861,38 +858,30 @@ int fgnn_bwd_ws_launch(const FgnnBwdCall& c, const FgnnPlan& pl) {
     p.y_ld = d->nou; p.w_ld = d->nou * 4; p.x_ld = d->nin; p.accum = 0;
     p.x_sb = d->x_sb; p.et_sb = d->et_sb; p.y_sb = d->y_sb;
     p.tables = pl.aux ? (const int*)c.tables : nullptr;
-    hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
     const int grid = pl.grid;
     hipStream_t st = c.stream;
     fgnn_note_kernel(split ? "mpconv_bwd_ws_kernel<%d, %d> x2" : (ksplit ? "mpconv_bwd_ws_kernel<%d, %d> k2" : "mpconv_bwd_ws_kernel<%d, %d>"), KC, DEG);
     p.prof = fgnn_prof_begin();
     void* args[] = {(void*)&p};
-    e = hipLaunchKernel(pl.fn, dim3(grid), dim3(pl.block), args, pl.lds, st);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ws backward launch: %s", hipGetErrorString(e));
+    int rc;
+    if ((rc = fgnn_launch_fn("mpconv ws backward", pl.fn, dim3(grid), dim3(pl.block), pl.lds, st, args))) return rc;
     // per-wave slots: 0 sample start, 1/2 projection done / released, 3/4 detype, 5/6 dP, 7/8 dx | dW | staging; from 128 on the
     // kernel-wide stamps: 1 early-dma, 2 zero+idx, 6 rank, 7 gtab, 3 consts, 4 loop-end, 5 end, 8.. sample starts, 40..44 setup
     fgnn_prof_print(p.prof, "ws bwd", 0, 8, 11, 16);
     fgnn_prof_print(p.prof, "ws bwd kernel", 128, 1, 45, 0);
     if (ksplit) {
-        fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW, c.gbias, st);                    // rows 0..63 of gfilters, dbias
+        if ((rc = fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW, c.gbias, st))) return rc;   // rows 0..63 of gfilters, dbias
         p.ws += (int64_t)grid * slab_len;                                                         // (its own slabs: the first launch's fold may be a recorded one)
         p.x += 64; p.W += 64 * (int64_t)p.w_ld; p.gx += 64; p.accum = 2;                          // input channels 64..127: getype accumulates
-        e = hipLaunchKernel(pl.fn, dim3(grid), dim3(pl.block), args, pl.lds, st);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ws backward launch (upper input channels): %s", hipGetErrorString(e));
-        fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW + nw, nullptr, st);               // rows 64..127 (dbias was counted by the first launch)
-    } else if (!split) fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW, c.gbias, st);
-    else {
-        // slab rows are 256 columns of gfilters' 512: lower half, then the second launch on the upper 64 output channels, which ADDS
-        // to gx / getype (one more bf16 rounding of those two) and folds its dW / dbias into the upper column / channel blocks
-        fgnn_launch_slab_reduce_ld(p.ws, grid, slab_len, nw, 256, 512, c.gW, c.gbias, st);
-        p.ws += (int64_t)grid * slab_len;
-        p.W += 256; p.gz += 64; p.argmax += 64; p.accum = 3;
-        e = hipLaunchKernel(pl.fn, dim3(grid), dim3(pl.block), args, pl.lds, st);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ws backward launch (upper half): %s", hipGetErrorString(e));
-        fgnn_launch_slab_reduce_ld(p.ws, grid, slab_len, nw, 256, 512, c.gW + 256, c.gbias + 64, st);
+        if ((rc = fgnn_launch_fn("mpconv ws backward (upper input channels)", pl.fn, dim3(grid), dim3(pl.block), pl.lds, st, args))) return rc;
+        return fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW + nw, nullptr, st);        // rows 64..127 (dbias was counted by the first launch)
     }
-    e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv backward helper launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    if (!split) return fgnn_launch_slab_reduce(p.ws, grid, slab_len, nw, c.gW, c.gbias, st);
+    // slab rows are 256 columns of gfilters' 512: lower half, then the second launch on the upper 64 output channels, which ADDS
+    // to gx / getype (one more bf16 rounding of those two) and folds its dW / dbias into the upper column / channel blocks
+    if ((rc = fgnn_launch_slab_reduce_ld(p.ws, grid, slab_len, nw, 256, 512, c.gW, c.gbias, st))) return rc;
+    p.ws += (int64_t)grid * slab_len;
+    p.W += 256; p.gz += 64; p.argmax += 64; p.accum = 3;
+    if ((rc = fgnn_launch_fn("mpconv ws backward (upper half)", pl.fn, dim3(grid), dim3(pl.block), pl.lds, st, args))) return rc;
+    return fgnn_launch_slab_reduce_ld(p.ws, grid, slab_len, nw, 256, 512, c.gW + 256, c.gbias + 64, st);
 }

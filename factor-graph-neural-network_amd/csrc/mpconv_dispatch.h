@@ -84,5 +84,4 @@ int fgnn_bwd_res_launch(const FgnnBwdCall& c, const FgnnPlan& pl);
 // ---- shared helpers ----
 int fgnn_check_desc(const fgnn_mpconv_desc* d);
 void fgnn_stats_upper_half(FgnnFold* fold, fgnn_bn_final* fin);
-void fgnn_launch_slab_store(const float* ws, int nslab, int64_t slab_len, float* out, hipStream_t st);
 int64_t fgnn_mpconv_backward_ext_extra_bytes(const fgnn_mpconv_desc* d);

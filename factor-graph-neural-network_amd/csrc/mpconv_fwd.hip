@@ -378,16 +378,10 @@ static int generic_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
     p.x = c.x; p.idx = c.idx; p.et = c.et; p.W = c.W; p.bias = c.bias;
     p.pscale = c.pscale; p.pshift = c.pshift; p.y = c.y; p.argmax = c.argmax;
     plan_forward(d, &p);
-    if (pl.lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
-    }
     fgnn_note_kernel("mpconv_fwd_kernel<%s, %d, %d>", d->dtype ? "bf16_t" : "float",
                      (d->net == 1 || d->net == 4 || d->net == 16) ? d->net : 0, d->agg);
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch_fn("mpconv forward", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args);
 }
 
 // The forward's families, most specialised first; the first whose plan takes the call runs it.
@@ -437,7 +431,7 @@ extern "C" int fgnn_mpconv_forward(const fgnn_mpconv_desc* d, const void* x, con
     int rc = fwd_check(d, x, nn_idx, etype, filters, post_scale, post_shift, y);
     if (rc || d->B == 0) return rc;
     FgnnFwdCall c = {d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y, argmax};
-    c.stream = (hipStream_t)stream;
+    c.stream = fgnn_stream(stream);
     FgnnPlan pl;
     return fwd_run(c, &pl);
 }
@@ -477,7 +471,7 @@ extern "C" int fgnn_mpconv_forward_stats(const fgnn_mpconv_desc* d, const void* 
     const bool inkernel = fin && fold_scratch && !fgnn_separate_finalisers();
     FgnnFwdCall c = {d, x, nn_idx, etype, filters, bias, nullptr, nullptr, y, argmax, true, stats_partials,
                      inkernel ? fin : nullptr, inkernel ? fold_scratch : nullptr};
-    c.stream = (hipStream_t)stream;
+    c.stream = fgnn_stream(stream);
     FgnnPlan pl;
     rc = d->B == 0 ? 0 : fwd_plan(c, &pl);
     if (rc < 0) return rc;
@@ -485,10 +479,8 @@ extern "C" int fgnn_mpconv_forward_stats(const fgnn_mpconv_desc* d, const void* 
     if (fin && (!fin->mean || !fin->invstd || !fin->scale || !fin->shift || fin->shift_k || fin->count != (int64_t)d->B * d->M))
         FGNN_FAIL(FGNN_EINVAL, "mpconv_forward_stats: fgnn_bn_final needs its outputs, count == B * M and no shift_k");
     rc = kFwdFamilies[pl.family].launch(c, pl);
-    if (rc) return rc;
-    if (fin && !inkernel && fgnn_bn_finalize_launch(stats_partials, pl.grid, d->nou, fin, c.stream))
-        FGNN_FAIL(FGNN_ELAUNCH, "mpconv_forward_stats finaliser launch: %s", hipGetErrorString(hipGetLastError()));
-    return FGNN_OK;
+    if (rc || !fin || inkernel) return rc;
+    return fgnn_bn_finalize_launch(stats_partials, pl.grid, d->nou, fin, c.stream);
 }
 
 // fgnn_mpconv_forward with up to three ADDENDS of y's layout (the caller's running sum, residual, skip term: factor_mpnn_sp.py:139-168
@@ -504,7 +496,7 @@ extern "C" int fgnn_mpconv_forward_addends(const fgnn_mpconv_desc* d, const void
     if (rc || d->B == 0) return rc;
     FgnnFwdCall c = {d, x, nn_idx, etype, filters, bias, post_scale, post_shift, y, nullptr};
     c.add[0] = addend0; c.add[1] = addend1; c.add[2] = addend2;
-    c.stream = (hipStream_t)stream;
+    c.stream = fgnn_stream(stream);
     FgnnPlan pl;
     rc = fwd_run(c, &pl);
     if (rc) return rc;

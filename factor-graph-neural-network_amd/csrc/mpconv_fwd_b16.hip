@@ -566,18 +566,14 @@ int fgnn_fwd_b16_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
     // the BatchNorm behind the operator, finalised by this launch (fgnn_mpconv_forward_stats)
     p.fold = fgnn_fold_make(c.stats, (c.stats && c.fin) ? c.fold_scratch : nullptr, pl.grid, d->nou);
     if (c.fin) p.fin = *c.fin;
-    if (pl.lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
-    }
     int KSB, SWP, NPASS;
     b16_widths(d, p, &KSB, &SWP, &NPASS);
     fgnn_note_kernel("mpconv_fwd_b16_kernel<%d, %d, %d, %d, %d, %d>", d->net, d->agg, KSB, SWP, NPASS,
                      (d->agg == FGNN_AGG_MAX && d->net == 4 && (d->k == 3 || d->k == 6)) ? d->k : 0);
     p.prof = fgnn_prof_begin();
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv bf16 forward launch: %s", hipGetErrorString(e));
+    const int rc = fgnn_launch_fn("mpconv bf16 forward", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args);
+    if (rc) return rc;
     fgnn_prof_print(p.prof, "b16 fwd", 0, 1, 20, 0);             // phase timeline of one sample (shader clocks)
     return FGNN_OK;
 }

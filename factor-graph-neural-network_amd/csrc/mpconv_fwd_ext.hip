@@ -637,8 +637,6 @@ int fgnn_fwd_ext_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
     p.x_sb = d->x_sb; p.y_sb = d->y_sb; p.idx_sb = d->idx_sb; p.idx_sm = d->idx_sm; p.idx_sk = d->idx_sk;
     p.et_sb = d->et_sb; p.et_se = d->et_se; p.et_sm = d->et_sm; p.et_sk = d->et_sk;
     fx_layout(d, pl.mode, pl.split, &p);
-    hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
     fgnn_note_kernel(pl.mode ? (pl.split ? "mpconv_fwd_extp_kernel<%d, true>" : "mpconv_fwd_extp_kernel<%d, false>") : "mpconv_fwd_ext_kernel<%d>", d->agg);
     p.prof = fgnn_prof_begin();
     p.dbg = 0;
@@ -646,8 +644,8 @@ int fgnn_fwd_ext_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
     if (getenv("FGNN_EXT_DBG")) p.dbg = atoi(getenv("FGNN_EXT_DBG"));
 #endif
     void* args[] = {(void*)&p};
-    e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ext forward launch: %s", hipGetErrorString(e));
+    const int rc = fgnn_launch_fn("mpconv ext forward", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args);
+    if (rc) return rc;
     if (pl.mode) fgnn_prof_print(p.prof, "ext fwd", 0, 8, 16, 16);     // stages 8..11 of workgroup 0, 4 stamps each (shader clocks)
     return FGNN_OK;
 }

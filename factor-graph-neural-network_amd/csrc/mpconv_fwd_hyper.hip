@@ -444,16 +444,10 @@ int fgnn_fwd_hyper_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
     p.Npad16 = fgnn_round_up(d->N, 16);
     if (pl.mode == FH_FANIN_ID) fgnn_note_kernel("mpconv_fwd_fanin_id_kernel<%d, %d>", d->nin / 32, d->nou / 16);
     else {
-        if (pl.lds > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-            if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
-        }
         p.waves = pl.aux;
         if (pl.mode == FH_FANIN) fgnn_note_kernel("mpconv_fwd_fanin_kernel<%d, %d, %d>", d->agg, d->nin / 32, d->nou / 16);
         else fgnn_note_kernel("mpconv_fwd_fanout_kernel<%d, %d>", d->nin / 64, d->nou / 16);
     }
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv hyper-edge forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch_fn("mpconv hyper-edge forward", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args);
 }

@@ -457,15 +457,9 @@ int fgnn_fwd_res_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
     p.x = c.x; p.idx = c.idx; p.et = c.et; p.W = c.W; p.bias = c.bias;
     p.pscale = c.pscale; p.pshift = c.pshift; p.y = c.y; p.argmax = c.argmax;
     { const char* e = getenv("FGNN_DBG"); p.dbg = e ? atoi(e) : 0; }
-    if (pl.lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
-    }
     int KS, SWP, NPASS;
     res_widths(d, p, &KS, &SWP, &NPASS);
     fgnn_note_kernel("mpconv_fwd_res_kernel<%s, %d, %d, %d, %d, %d>", d->dtype ? "bf16_t" : "float", d->net, d->agg, KS, SWP, NPASS);
     void* args[] = {(void*)&p};
-    hipError_t e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv resident forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch_fn("mpconv resident forward", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args);
 }

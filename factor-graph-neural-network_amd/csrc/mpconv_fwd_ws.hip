@@ -539,14 +539,12 @@ int fgnn_fwd_ws_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
     p.fold = fgnn_fold_make(c.stats, (c.stats && c.fin) ? c.fold_scratch : nullptr, pl.grid, 64, 2 * d->nou, d->nou);
     if (c.fin) p.fin = *c.fin;
     for (int a = 0; a < 3; ++a) p.add[a] = pl.aux ? static_cast<const unsigned short*>(c.add[a]) : nullptr;
-    hipError_t e = hipFuncSetAttribute(pl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", pl.lds, hipGetErrorString(e));
     fgnn_note_kernel(pl.split ? "mpconv_fwd_ws_kernel<%d, %d, %d, %d> x2" : "mpconv_fwd_ws_kernel<%d, %d, %d, %d>", d->nin, d->k, pl.mode,
                      d->nin == 64 ? 3 : 2);
     p.prof = fgnn_prof_begin();
     void* args[] = {(void*)&p};
-    e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ws forward launch: %s", hipGetErrorString(e));
+    const int rc = fgnn_launch_fn("mpconv ws forward", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args);
+    if (rc) return rc;
     // per-stage timeline of workgroup 0 (shader clocks); slots: 0 / 1 = sample 8 started / finished, 3 / 4 = sample 9, 6 / 7 = sample 10
     fgnn_prof_print(p.prof, "ws fwd", 0, 16, 8, 8);
     p.prof = nullptr;
@@ -559,8 +557,7 @@ int fgnn_fwd_ws_launch(const FgnnFwdCall& c, const FgnnPlan& pl) {
         if (p.argmax) p.argmax += 64;
         if (p.stats) p.stats += 64;
         fgnn_stats_upper_half(&p.fold, &p.fin);
-        e = hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.block), args, pl.lds, c.stream);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "mpconv ws forward launch (upper half): %s", hipGetErrorString(e));
+        return fgnn_launch_fn("mpconv ws forward (upper half)", pl.fn, dim3(pl.grid), dim3(pl.block), pl.lds, c.stream, args);
     }
     return FGNN_OK;
 }

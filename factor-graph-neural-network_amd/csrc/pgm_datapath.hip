@@ -222,18 +222,10 @@ static int cb_launch(bool sampler, CbParams& p, hipStream_t st) {
     p.spw = spw;
     p.sample_bytes = (int)per;
     const int lds = spw * (int)per;
-    const void* fn = sampler ? (const void*)chain_budget_map_kernel<true> : (const void*)chain_budget_map_kernel<false>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
+    const auto kernel = sampler ? chain_budget_map_kernel<true> : chain_budget_map_kernel<false>;
     fgnn_note_kernel(sampler ? "chain_budget_map_kernel<sampler>" : "chain_budget_map_kernel");
     const unsigned grid = (unsigned)((p.B + spw - 1) / spw);
-    if (sampler) hipLaunchKernelGGL(chain_budget_map_kernel<true>, dim3(grid), dim3(64 * spw), lds, st, p);
-    else hipLaunchKernelGGL(chain_budget_map_kernel<false>, dim3(grid), dim3(64 * spw), lds, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "chain_budget_map launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("chain_budget_map", kernel, dim3(grid), dim3(64 * spw), lds, st, p);
 }
 
 extern "C" int fgnn_chain_budget_map(const float* unary, int64_t unary_sb, const float* pair, int64_t pair_sb, const int32_t* caps,
@@ -247,7 +239,7 @@ extern "C" int fgnn_chain_budget_map(const float* unary, int64_t unary_sb, const
     p.caps = caps; p.c_sb = caps_sb;
     p.labels = labels; p.objective = objective;
     p.B = B; p.N = N; p.h = h;
-    return cb_launch(false, p, (hipStream_t)stream);
+    return cb_launch(false, p, fgnn_stream(stream));
 }
 
 extern "C" int fgnn_pgm_sample_rng(int family, uint64_t seed, uint64_t offset, int64_t B, int N, int h, int cap,
@@ -267,5 +259,5 @@ extern "C" int fgnn_pgm_sample_rng(int family, uint64_t seed, uint64_t offset, i
     p.hops = family == CB_HOPS ? hops : nullptr;
     p.labels = labels; p.objective = objective;
     p.B = B; p.N = N; p.h = h;
-    return cb_launch(true, p, (hipStream_t)stream);
+    return cb_launch(true, p, fgnn_stream(stream));
 }

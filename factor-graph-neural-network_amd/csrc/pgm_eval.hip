@@ -162,13 +162,10 @@ extern "C" int fgnn_chain_budget_score(const void* dec, int dec_kind, int64_t de
                         correct, feasible, objective, nll, (unsigned long long*)counts, B, N, h};
     int64_t grid = (B + PS_WAVES - 1) / PS_WAVES;
     if (grid > PS_MAXGRID) grid = PS_MAXGRID;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 g((unsigned)grid), blk(PS_THREADS);
     fgnn_note_kernel("chain_budget_score_kernel");
-    if (dec_kind == FGNN_PGM_DEC_F32) hipLaunchKernelGGL(chain_budget_score_kernel<FGNN_PGM_DEC_F32>, g, blk, 0, st, p);
-    else if (dec_kind == FGNN_PGM_DEC_BF16) hipLaunchKernelGGL(chain_budget_score_kernel<FGNN_PGM_DEC_BF16>, g, blk, 0, st, p);
-    else hipLaunchKernelGGL(chain_budget_score_kernel<FGNN_PGM_DEC_I64>, g, blk, 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "chain_budget_score launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    void (*kernel)(PsParams);
+    if (dec_kind == FGNN_PGM_DEC_F32) kernel = chain_budget_score_kernel<FGNN_PGM_DEC_F32>;
+    else if (dec_kind == FGNN_PGM_DEC_BF16) kernel = chain_budget_score_kernel<FGNN_PGM_DEC_BF16>;
+    else kernel = chain_budget_score_kernel<FGNN_PGM_DEC_I64>;
+    return fgnn_launch("chain_budget_score", kernel, dim3((unsigned)grid), dim3(PS_THREADS), 0, fgnn_stream(stream), p);
 }

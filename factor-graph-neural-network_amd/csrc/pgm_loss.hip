@@ -143,21 +143,18 @@ extern "C" int fgnn_pgm_loss_forward(const void* logits, int kind, int64_t sb, i
     if (!loss) FGNN_FAIL(FGNN_EINVAL, "pgm_loss_forward: null pointer");
     if (!workspace || workspace_bytes < fgnn_pgm_loss_workspace_bytes() || ((uintptr_t)workspace & 7))
         FGNN_FAIL(FGNN_EINVAL, "pgm_loss_forward: an 8-byte aligned workspace of fgnn_pgm_loss_workspace_bytes() bytes needed");
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = fgnn_stream(stream);
     const int64_t total = B * N;
     const unsigned grid = pl_grid(total);
     double* part = (double*)workspace;
     if (B > 0) {
         const PlParams p = {logits, sb, cs, vs, label, label_sb, lp_label, lp_sb, part, (unsigned long long*)counts, total, N};
         fgnn_note_kernel("pgm_loss_fwd_kernel");
-        if (kind == FGNN_PGM_DEC_F32) hipLaunchKernelGGL(pgm_loss_fwd_kernel<FGNN_PGM_DEC_F32>, dim3(grid), dim3(PL_THREADS), 0, st, p);
-        else hipLaunchKernelGGL(pgm_loss_fwd_kernel<FGNN_PGM_DEC_BF16>, dim3(grid), dim3(PL_THREADS), 0, st, p);
+        const auto kernel = kind == FGNN_PGM_DEC_F32 ? pgm_loss_fwd_kernel<FGNN_PGM_DEC_F32> : pgm_loss_fwd_kernel<FGNN_PGM_DEC_BF16>;
+        if (int rc = fgnn_launch("pgm_loss forward", kernel, dim3(grid), dim3(PL_THREADS), 0, st, p)) return rc;
     }
     // B = 0: no partials, and the mean of nothing is written as 0
-    hipLaunchKernelGGL(pgm_loss_final_kernel, dim3(1), dim3(1), 0, st, part, B > 0 ? (int)grid : 0, B > 0 ? total : 1, loss);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "pgm_loss forward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("pgm_loss forward", pgm_loss_final_kernel, dim3(1), dim3(1), 0, st, part, B > 0 ? (int)grid : 0, B > 0 ? total : 1, loss);
 }
 
 extern "C" int fgnn_pgm_loss_backward(const void* logits, int kind, int64_t sb, int64_t cs, int64_t vs, const int64_t* label,
@@ -169,13 +166,9 @@ extern "C" int fgnn_pgm_loss_backward(const void* logits, int kind, int64_t sb, 
     if (B == 0) return FGNN_OK;
     const int64_t total = B * N;
     const PlBwdParams p = {logits, sb, cs, vs, label, label_sb, gloss, glogits, g_sb, g_cs, g_vs, total, N};
-    hipStream_t st = (hipStream_t)stream;
     fgnn_note_kernel("pgm_loss_bwd_kernel");
     int64_t g = (total + PL_THREADS - 1) / PL_THREADS;
     if (g > 4096) g = 4096;
-    if (kind == FGNN_PGM_DEC_F32) hipLaunchKernelGGL(pgm_loss_bwd_kernel<FGNN_PGM_DEC_F32>, dim3((unsigned)g), dim3(PL_THREADS), 0, st, p);
-    else hipLaunchKernelGGL(pgm_loss_bwd_kernel<FGNN_PGM_DEC_BF16>, dim3((unsigned)g), dim3(PL_THREADS), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "pgm_loss backward launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const auto kernel = kind == FGNN_PGM_DEC_F32 ? pgm_loss_bwd_kernel<FGNN_PGM_DEC_F32> : pgm_loss_bwd_kernel<FGNN_PGM_DEC_BF16>;
+    return fgnn_launch("pgm_loss backward", kernel, dim3((unsigned)g), dim3(PL_THREADS), 0, fgnn_stream(stream), p);
 }

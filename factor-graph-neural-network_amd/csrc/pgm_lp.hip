@@ -293,13 +293,6 @@ extern "C" int fgnn_chain_budget_lp(const float* unary, int64_t unary_sb, const 
     p.tol2 = tol * tol; p.eta = eta;
     p.N = N; p.h = h; p.max_iter = max_iter; p.adapt = adapt ? 1 : 0;
     const int lds = (int)per;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)chain_budget_lp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", lds, hipGetErrorString(e));
-    }
     fgnn_note_kernel("chain_budget_lp_kernel");
-    hipLaunchKernelGGL(chain_budget_lp_kernel, dim3((unsigned)B), dim3(64), lds, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "chain_budget_lp launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("chain_budget_lp", chain_budget_lp_kernel, dim3((unsigned)B), dim3(64), lds, fgnn_stream(stream), p);
 }

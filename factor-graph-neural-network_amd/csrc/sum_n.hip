@@ -62,11 +62,8 @@ extern "C" int fgnn_sum_n(const void* const* inputs, int n, int64_t numel, int d
     p.out = out; p.nchunks = bytes / 16; p.n = n;
     int64_t g = (p.nchunks + 255) / 256;
     if (g > 4096) g = 4096;
-    if (dtype == FGNN_F32) hipLaunchKernelGGL(sum_n_kernel<float>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(sum_n_kernel<bf16_t>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "sum_n launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    const auto kernel = dtype == FGNN_F32 ? sum_n_kernel<float> : sum_n_kernel<bf16_t>;
+    return fgnn_launch("sum_n", kernel, dim3((unsigned)g), dim3(256), 0, fgnn_stream(stream), p);
 }
 
 
@@ -122,13 +119,9 @@ extern "C" int fgnn_node_sum(const void* g, void* out, int64_t B, int M, int C, 
     if (B == 0) return FGNN_OK;
     int64_t grid = (B * (C / epc) + 255) / 256;
     if (grid > 8192) grid = 8192;
-    if (dtype == FGNN_F32) hipLaunchKernelGGL(node_sum_kernel<float>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream,
-                                              (const float*)g, (float*)out, B, M, C);
-    else hipLaunchKernelGGL(node_sum_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream,
-                            (const bf16_t*)g, (bf16_t*)out, B, M, C);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "node_sum launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    if (dtype == FGNN_F32)
+        return fgnn_launch("node_sum", node_sum_kernel<float>, dim3((unsigned)grid), dim3(256), 0, fgnn_stream(stream), (const float*)g, (float*)out, B, M, C);
+    return fgnn_launch("node_sum", node_sum_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), 0, fgnn_stream(stream), (const bf16_t*)g, (bf16_t*)out, B, M, C);
 }
 
 
@@ -203,10 +196,7 @@ extern "C" int fgnn_concat_rows(const void* a, const void* b, void* out, int64_t
     p.total = samples * (rows_a + rows_b) * (int64_t)p.uc;
     int64_t grid = (p.total + 255) / 256;
     if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(concat_rows_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "concat_rows launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("concat_rows", concat_rows_kernel, dim3((unsigned)grid), dim3(256), 0, fgnn_stream(stream), p);
 }
 
 extern "C" int fgnn_concat_pair(const void* a, const void* b, void* out, int64_t samples, int64_t inner, int64_t chunk_a_bytes,
@@ -228,8 +218,5 @@ extern "C" int fgnn_concat_pair(const void* a, const void* b, void* out, int64_t
     p.total = samples * inner * (int64_t)(p.ua + p.ub);
     int64_t grid = (p.total + 255) / 256;
     if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(concat_pair_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "concat_pair launch: %s", hipGetErrorString(e));
-    return FGNN_OK;
+    return fgnn_launch("concat_pair", concat_pair_kernel, dim3((unsigned)grid), dim3(256), 0, fgnn_stream(stream), p);
 }
