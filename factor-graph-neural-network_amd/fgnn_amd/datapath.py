@@ -65,6 +65,39 @@ def check_decode_llr_args(llr, n_var, algorithm, schedule, max_iter, alpha, beta
     return llr.shape[0], LLR_ALGORITHMS[algorithm]
 
 
+OSD_MAX_ORDER, OSD_MAX_PAIR_SPAN = 2, 256       # fgnn_ldpc_osd's limits (csrc/ldpc_osd.hip)
+
+
+def check_decode_osd_args(rel, metric, viol, n_var, order, span):
+    """Arguments of ``LdpcDataPath.decode_osd`` (before anything reaches the device).  Returns (B, span with its default filled in:
+    ``n_var`` for order 0 and 1, 64 for order 2)."""
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 0 <= int(order) <= OSD_MAX_ORDER:
+        raise ValueError('order must be an integer in 0..%d, got %r' % (OSD_MAX_ORDER, order))
+    if span is None:
+        span = 64 if int(order) == 2 else int(n_var)
+    if isinstance(span, bool) or not isinstance(span, (int, np.integer)) or not 1 <= int(span) < 2 ** 31:
+        raise ValueError('span must be an integer in [1, 2^31), got %r' % (span,))
+    if int(order) == 2 and int(span) > OSD_MAX_PAIR_SPAN:
+        raise ValueError('span must be at most %d with order 2, got %d' % (OSD_MAX_PAIR_SPAN, span))
+    for what, t in (('rel', rel), ('metric', metric)):
+        if t is None and what == 'metric':
+            continue
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != int(n_var):
+            raise ValueError('%s must be a [B, %d] tensor, got %s' % (what, n_var, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if not t.dtype.is_floating_point:
+            raise ValueError('%s must be a floating-point tensor, got %s' % (what, t.dtype))
+    B = rel.shape[0]
+    if B >= 2 ** 31:
+        raise ValueError('at most 2^31 - 1 words per call, got %d' % B)
+    if metric is not None and metric.shape[0] != B:
+        raise ValueError('metric must hold rel\'s %d words, got %d' % (B, metric.shape[0]))
+    if viol is not None:
+        if not isinstance(viol, torch.Tensor) or tuple(viol.shape) != (B,) or viol.dtype != torch.int32:
+            raise ValueError('viol must be a [%d] int32 tensor, got %s' % (B, '%s %s' % (tuple(viol.shape), viol.dtype) if isinstance(viol, torch.Tensor)
+                                                                         else type(viol).__name__))
+    return B, int(span)
+
+
 def _llr_batch(llr, device, n_var):
     """A checked [B, n_var] LLR batch as the decoder kernels read it: f32 on ``device``, unit column stride, rows that do not
     overlap (copied only where it is not)."""
@@ -105,6 +138,7 @@ class LdpcDataPath:
         self.one_word = code.K <= 64 and 1 <= code.P <= 64       # the one-word kernels' family (fgnn_ldpc_encode, fgnn_ldpc_sample_rng)
         self._decode_tables = None                               # built on the first ``decode`` (a code may exceed the decoder only)
         self._llr_tables = None                                  # ... and on the first ``decode_llr``
+        self._osd_tables = None                                  # ... and on the first ``decode_osd``
         gwords = code.gwords.view(np.int64)                       # [P, W]; the one-word kernels' gmask is its column 0, [P]
         self.gmask = torch.from_numpy((gwords[:, 0] if self.one_word else gwords).copy()).to(self.device)
         self.var_to_factors = torch.from_numpy(code.var_to_factors.astype(np.int32)).to(self.device)
@@ -287,6 +321,31 @@ class LdpcDataPath:
                   layer_ptr if layered else None, layer_chk if layered else None, n_layers if layered else 0, B, N, M, E, alg,
                   int(max_iter), float(alpha), float(beta), x, post, viol, iters)
         return (x, viol, iters, post) if want_posteriors else (x, viol, iters)
+
+    def decode_osd(self, rel, metric=None, viol=None, order=1, span=None):
+        """Ordered-statistics reprocessing (fgnn_ldpc_osd, include/fgnn_hip_ldpc_osd.h; no counterpart in the reference) for a batch:
+        rel [B, N] orders the positions and gives the hard decisions (a decoder's posteriors: ``decode_llr(..., want_posteriors=True)``),
+        ``metric`` [B, N] is what candidates are scored against (the channel LLRs, ``bit_llr``; None: rel), ``viol`` [B] int32 the
+        decoder's violated checks: a word with none passes through (None: every word is reprocessed).  ``order`` 0, 1 or 2 over the
+        ``span`` least reliable non-pivot positions (default: N for order 0 and 1, 64 for order 2; at most 256 with order 2).  Rows may
+        be strided.  Returns (x [B, N] uint8 — every reprocessed word satisfies every check —, cost [B] int32: the quantised
+        discrepancy of x to ``metric``, pattern [B] int32: the winning candidate's index, -1 for a word passed through)."""
+        B, span = check_decode_osd_args(rel, metric, viol, self.N, order, span)
+        if self._osd_tables is None:
+            self.code.require_llr_decoder()
+            _, row_ptr, _, row_var, N, M, E = self._incidence_tables()
+            if int(_hip.invoke('fgnn_ldpc_osd_lds_bytes', N, M)) < 0:
+                raise ValueError(_hip.lib().fgnn_last_error().decode())
+            self._osd_tables = (row_ptr, row_var, N, M, E)
+        row_ptr, row_var, N, M, E = self._osd_tables
+        rel = _llr_batch(rel, self.device, N)
+        metric = None if metric is None else _llr_batch(metric, self.device, N)
+        viol = None if viol is None else viol.to(self.device).contiguous()
+        x = torch.empty((B, N), device=self.device, dtype=torch.uint8)
+        cost, pattern = (torch.empty((B,), device=self.device, dtype=torch.int32) for _ in range(2))
+        _hip.call('fgnn_ldpc_osd', rel, rel.stride(0) if B else N, metric, metric.stride(0) if B and metric is not None else N, viol,
+                  row_ptr, row_var, B, N, M, E, int(order), span, x, cost, pattern)
+        return x, cost, pattern
 
     def sample(self, B, seed=0, dtype=torch.float32, snr_db=None, burst_prob=0.05, kernel_rng=False, step=0):
         """A batch of B training items (ldpc_dataset.py:222-236): random messages, encoded, sent through the

@@ -146,13 +146,17 @@ def load_model(model_path, code=None, aggregator='max', device='cpu'):
 def parse_decoder(spec):
     """A classical decoder's spec -> (canonical spec, kind, arguments).  ``'mackay'``: the reference's probability-domain sum-product
     (``LdpcDataPath.decode``, 100 loops; ``mackay:iters=N`` for another count), kind 'mackay', arguments {'loops'}.  Otherwise
-    ``ALGORITHM[:SCHEDULE][:iters=N][:alpha=A][:beta=B]`` with ALGORITHM 'min-sum', 'offset-min-sum' or 'sum-product' and SCHEDULE
-    'flooding' (the default) or 'layered': kind 'llr', the keyword arguments of ``LdpcDataPath.decode_llr``.  The canonical spec
+    ``ALGORITHM[:SCHEDULE][:iters=N][:alpha=A][:beta=B][:osd=W[:span=L]]`` with ALGORITHM 'min-sum', 'offset-min-sum' or
+    'sum-product' and SCHEDULE 'flooding' (the default) or 'layered': kind 'llr', the keyword arguments of ``LdpcDataPath.decode_llr``.  The canonical spec
     names the schedule and then only what differs from the defaults, in the order iters, alpha, beta; parsing it gives itself.
+    The LLR-domain specs take two more options behind ``beta``: ``osd=W`` (0..2) runs ordered-statistics reprocessing of order W on
+    the words the decoder leaves with violated checks (``LdpcDataPath.decode_osd``), and ``span=L`` (>= 1; needs osd >= 1; at most
+    256 with osd=2) bounds the positions it flips; the arguments then hold 'osd' (and 'span'), and the canonical spec appends them in
+    that order.
     ``learned-min-sum:CHECKPOINT``: the trained min-sum decoder of an ``ldpc_nms_train`` checkpoint (``ldpc_nms.LearnedMinSum``), kind
     'learned', arguments {'path'}; everything behind the first colon is the path (it may hold colons), and the spec is canonical as
     it stands."""
-    from .datapath import LLR_ALGORITHMS, LLR_SCHEDULES
+    from .datapath import LLR_ALGORITHMS, LLR_SCHEDULES, OSD_MAX_ORDER, OSD_MAX_PAIR_SPAN
     from .ldpc_nms import KIND as LEARNED
     if not isinstance(spec, str) or not spec:
         raise ValueError('a decoder spec is a non-empty string, got %r' % (spec,))
@@ -168,13 +172,13 @@ def parse_decoder(spec):
             schedule = part
             continue
         key, eq, val = part.partition('=')
-        if not eq or key not in ('iters', 'alpha', 'beta') or key in opts:
-            raise ValueError('decoder spec %r: cannot read %r (SCHEDULE, iters=N, alpha=A, beta=B)' % (spec, part))
+        if not eq or key not in ('iters', 'alpha', 'beta', 'osd', 'span') or key in opts:
+            raise ValueError('decoder spec %r: cannot read %r (SCHEDULE, iters=N, alpha=A, beta=B, osd=W, span=L)' % (spec, part))
         try:
-            opts[key] = int(val) if key == 'iters' else float(val)
+            opts[key] = int(val) if key in ('iters', 'osd', 'span') else float(val)
         except ValueError:
             raise ValueError('decoder spec %r: %s=%r is not a number' % (spec, key, val)) from None
-        if not (opts[key] >= (1 if key == 'iters' else 0)) or opts[key] > 3.0e38:
+        if not (opts[key] >= (1 if key in ('iters', 'span') else 0)) or opts[key] > (OSD_MAX_ORDER if key == 'osd' else 3.0e38):
             raise ValueError('decoder spec %r: %s=%r is out of range' % (spec, key, val))
     if head == 'mackay':
         if schedule is not None or set(opts) - {'iters'}:
@@ -191,6 +195,12 @@ def parse_decoder(spec):
     canon += ':iters=%d' % kw['max_iter'] if kw['max_iter'] != 50 else ''
     canon += ':alpha=%r' % kw['alpha'] if kw['alpha'] != 0.8125 else ''
     canon += ':beta=%r' % kw['beta'] if kw['beta'] != 0.5 else ''
+    if 'span' in opts and (opts.get('osd', 0) < 1 or opts['span'] >= 2 ** 31 or opts['osd'] == 2 and opts['span'] > OSD_MAX_PAIR_SPAN):
+        raise ValueError('decoder spec %r: span=L needs osd=1 or osd=2 (then L <= %d)' % (spec, OSD_MAX_PAIR_SPAN))
+    for key in ('osd', 'span'):
+        if key in opts:
+            kw[key] = opts[key]
+            canon += ':%s=%d' % (key, opts[key])
     return canon, 'llr', kw
 
 
@@ -207,7 +217,13 @@ def run_decoder(path, decoder, y, snr0):
             from .ldpc_nms import load_checkpoint
             loaded[kw['path']] = load_checkpoint(kw['path'], path.code, path.device)
         return loaded[kw['path']].decode(path.bit_llr(y, snr0))
-    return path.decode_llr(path.bit_llr(y, snr0), **kw)
+    llr = path.bit_llr(y, snr0)
+    if 'osd' in kw:         # BP-OSD: the words the decoder leaves with violated checks are reprocessed against the channel LLRs
+        bp = {k: v for k, v in kw.items() if k not in ('osd', 'span')}
+        _, viol, iters, post = path.decode_llr(llr, want_posteriors=True, **bp)
+        x = path.decode_osd(post, metric=llr, viol=viol, order=kw['osd'], span=kw.get('span'))[0]
+        return x, torch.zeros_like(viol), iters
+    return path.decode_llr(llr, **kw)
 
 
 def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=False, snr_grid=SNR_GRID, sigma_grid=SIGMA_GRID, code=None):
@@ -323,8 +339,8 @@ def main(argv=None):
     ap.add_argument('--baseline', action='store_true', help='also print the sum-product decoder\'s table')
     ap.add_argument('--decoder', action='append', default=[], metavar='SPEC',
                     help='also print the table of a classical decoder; may be repeated.  mackay, or min-sum | offset-min-sum | '
-                         'sum-product [:flooding | :layered] [:iters=N] [:alpha=A] [:beta=B], or learned-min-sum:CHECKPOINT '
-                         '(python -m fgnn_amd.ldpc_nms_train)')
+                         'sum-product [:flooding | :layered] [:iters=N] [:alpha=A] [:beta=B] [:osd=W [:span=L]] (osd: ordered-'
+                         'statistics reprocessing of order W), or learned-min-sum:CHECKPOINT (python -m fgnn_amd.ldpc_nms_train)')
     ap.add_argument('--curve', action='store_true', help='print a BER / WER curve of the one --decoder over --snr (no model)')
     ap.add_argument('--snr', default='0,1,2,3,4', help='--curve: SNR values in dB, comma-separated')
     ap.add_argument('--sigma_b', type=int, default=0, help='--curve: the burst level')

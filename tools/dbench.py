@@ -3,13 +3,18 @@
 against the LLR-domain decoders (LdpcDataPath.decode_llr, max_iter 50: csrc/ldpc_llr.hip), every algorithm x schedule.
 
 4096 received words of the all-zero codeword at 2 dB (no burst; one fixed torch seed), for the built-in 96.3.963 and for
-gallager(1024, 4, 8, 2) (which the f64 decoder refuses).  Per decoder: two warm-up calls, one timed call to size the window (at least
-0.2 s of back-to-back calls), then 7 windows between device events; the median window gives the rate.  Also printed: mean iterations
+gallager(384, 3, 6, 1) and gallager(1024, 4, 8, 2) (which the f64 decoder refuses).  Per decoder: two warm-up calls, one timed call
+to size the window (at least 0.2 s of back-to-back calls), then 7 windows between device events; the median window gives the rate.  Also printed: mean iterations
 and the decoded fraction (words that end with no violated check), and the LDS bytes a word occupies.
 
 The learned min-sum decoder (fgnn_amd.ldpc_nms.LearnedMinSum.decode, csrc/ldpc_nms.hip: the decode mode, early stopping) follows,
 beside min-sum:flooding at the same iteration count (--learned_iters), with untrained weights (alpha 0.8125, beta 0: the same
 decisions) shared per iteration, per check and per edge: the weight reads are its only extra work in the loop.
+
+Ordered-statistics reprocessing (LdpcDataPath.decode_osd, csrc/ldpc_osd.hip) follows as min-sum:layered:osd=0|1|2 (order 2: the
+default span, 64), each row the whole composition ``ldpc_eval.run_decoder`` runs — the decoder with posteriors, then the reprocessing
+of the words it leaves with violated checks — to be read beside the plain min-sum:layered row; ``decoded`` is 1 there by construction.
+A third code, gallager(384, 3, 6, 1), sits between the two (128 threads per word).
 
     python tools/dbench.py [--words 4096] [--snr 2.0] [--repeats 7] [--learned_iters 5]
 """
@@ -24,6 +29,7 @@ import torch
 from fgnn_amd import _hip
 from fgnn_amd.datapath import LLR_ALGORITHMS, LLR_SCHEDULES, LdpcDataPath
 from fgnn_amd.ldpc_code import LdpcCode
+from fgnn_amd.ldpc_eval import parse_decoder, run_decoder
 from fgnn_amd.ldpc_nms import SHARES, LearnedMinSum
 
 
@@ -60,7 +66,8 @@ def main():
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     print('%-24s %-34s %12s %10s %10s %9s %9s' % ('code', 'decoder', 'words/s', 'us/call', 'spread %', 'iters', 'decoded'))
-    for name, code in (('builtin 96.3.963', LdpcCode.builtin()), ('gallager(1024,4,8,2)', LdpcCode.gallager(1024, 4, 8, 2))):
+    for name, code in (('builtin 96.3.963', LdpcCode.builtin()), ('gallager(384,3,6,1)', LdpcCode.gallager(384, 3, 6, 1)),
+                       ('gallager(1024,4,8,2)', LdpcCode.gallager(1024, 4, 8, 2))):
         path = LdpcDataPath(dev, code)
         gen = torch.Generator(device=dev).manual_seed(0)
         gcx = 10.0 ** (args.snr / 20.0)
@@ -68,8 +75,9 @@ def main():
         snr = torch.full((args.words,), args.snr, device=dev)
         llr, bias = path.bit_llr(y, snr), path.bit_prior(y, snr)
         E = code.n_var * code.dv
-        print('# %s: %s, %d LDS bytes per word for decode_llr' % (name, code, _hip.invoke('fgnn_ldpc_decode_llr_lds_bytes',
-                                                                                          code.n_var, code.n_chk, E)))
+        print('# %s: %s, %d LDS bytes per word for decode_llr, %d for decode_osd'
+              % (name, code, _hip.invoke('fgnn_ldpc_decode_llr_lds_bytes', code.n_var, code.n_chk, E),
+                 _hip.invoke('fgnn_ldpc_osd_lds_bytes', code.n_var, code.n_chk)))
         runs = []
         try:
             code.require_decoder()
@@ -79,6 +87,9 @@ def main():
         for alg in LLR_ALGORITHMS:
             for sched in LLR_SCHEDULES:
                 runs.append(('%s:%s' % (alg, sched), lambda alg=alg, sched=sched: path.decode_llr(llr, alg, sched, max_iter=50)))
+        for order in (0, 1, 2):
+            decoder = parse_decoder('min-sum:layered:osd=%d' % order)
+            runs.append((decoder[0], lambda decoder=decoder: run_decoder(path, decoder, y, snr)))
         n = args.learned_iters
         runs.append(('min-sum:flooding:iters=%d' % n, lambda: path.decode_llr(llr, 'min-sum', 'flooding', max_iter=n)))
         for share in SHARES:
