@@ -1,4 +1,5 @@
-"""The LDPC data path in front of the decoder, per batch on the GPU.
+"""The LDPC data path in front of the decoder, per batch on the GPU: the encoder, the channel, the model's
+features, the batch samplers and the test-set writers.  The classical decoders a path also runs live in ``ldpc_decoders``.
 
 The reference builds every training item on the host: ``gen_data_item`` (/root/reference/lib/data/ldpc.py:7-30)
 calls the pybind11 MNC library for the GF(2) encode ``s2t`` and the channel ``t2y``
@@ -15,6 +16,7 @@ import torch
 
 from . import _hip
 from .ldpc_code import LdpcCode
+from .ldpc_decoders import LdpcDecoders, parse_decoder
 
 
 # ``LdpcDataPath.sample_rng``'s result: the reference's DataLoader item (train_ldpc.py:207) in its order, then what the sampler drew
@@ -41,87 +43,14 @@ def check_sample_rng_args(B, seed, step, dtype, choices_snr, choices_sigma, out)
             raise ValueError('out must be a previous sample_rng result for the same (B, dtype)')
 
 
-LLR_ALGORITHMS = {'min-sum': 0, 'offset-min-sum': 1, 'sum-product': 2}     # fgnn_ldpc_decode_llr's ``algorithm``
-LLR_SCHEDULES = ('flooding', 'layered')
-
-
-def check_decode_llr_args(llr, n_var, algorithm, schedule, max_iter, alpha, beta):
-    """Arguments of ``LdpcDataPath.decode_llr`` (before anything reaches the device).  Returns (B, the algorithm's code)."""
-    if algorithm not in LLR_ALGORITHMS:
-        raise ValueError('algorithm must be one of %s, got %r' % (', '.join(LLR_ALGORITHMS), algorithm))
-    if schedule not in LLR_SCHEDULES:
-        raise ValueError('schedule must be one of %s, got %r' % (', '.join(LLR_SCHEDULES), schedule))
-    if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= int(max_iter) < 2 ** 31:
-        raise ValueError('max_iter must be an integer in [1, 2^31), got %r' % (max_iter,))
-    for what, v in (('alpha', alpha), ('beta', beta)):
-        if not (np.isfinite(float(v)) and 0 <= float(v) <= 3.0e38):
-            raise ValueError('%s must be a finite float32 value >= 0, got %r' % (what, v))
-    if not isinstance(llr, torch.Tensor) or llr.dim() != 2 or llr.shape[1] != int(n_var):
-        raise ValueError('llr must be a [B, %d] tensor, got %s' % (n_var, tuple(llr.shape) if isinstance(llr, torch.Tensor) else type(llr).__name__))
-    if not llr.dtype.is_floating_point:
-        raise ValueError('llr must be a floating-point tensor, got %s' % llr.dtype)
-    if llr.shape[0] >= 2 ** 31:
-        raise ValueError('at most 2^31 - 1 words per call, got %d' % llr.shape[0])
-    return llr.shape[0], LLR_ALGORITHMS[algorithm]
-
-
-OSD_MAX_ORDER, OSD_MAX_PAIR_SPAN = 2, 256       # fgnn_ldpc_osd's limits (csrc/ldpc_osd.hip)
-
-
-def check_decode_osd_args(rel, metric, viol, n_var, order, span):
-    """Arguments of ``LdpcDataPath.decode_osd`` (before anything reaches the device).  Returns (B, span with its default filled in:
-    ``n_var`` for order 0 and 1, 64 for order 2)."""
-    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 0 <= int(order) <= OSD_MAX_ORDER:
-        raise ValueError('order must be an integer in 0..%d, got %r' % (OSD_MAX_ORDER, order))
-    if span is None:
-        span = 64 if int(order) == 2 else int(n_var)
-    if isinstance(span, bool) or not isinstance(span, (int, np.integer)) or not 1 <= int(span) < 2 ** 31:
-        raise ValueError('span must be an integer in [1, 2^31), got %r' % (span,))
-    if int(order) == 2 and int(span) > OSD_MAX_PAIR_SPAN:
-        raise ValueError('span must be at most %d with order 2, got %d' % (OSD_MAX_PAIR_SPAN, span))
-    for what, t in (('rel', rel), ('metric', metric)):
-        if t is None and what == 'metric':
-            continue
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != int(n_var):
-            raise ValueError('%s must be a [B, %d] tensor, got %s' % (what, n_var, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
-        if not t.dtype.is_floating_point:
-            raise ValueError('%s must be a floating-point tensor, got %s' % (what, t.dtype))
-    B = rel.shape[0]
-    if B >= 2 ** 31:
-        raise ValueError('at most 2^31 - 1 words per call, got %d' % B)
-    if metric is not None and metric.shape[0] != B:
-        raise ValueError('metric must hold rel\'s %d words, got %d' % (B, metric.shape[0]))
-    if viol is not None:
-        if not isinstance(viol, torch.Tensor) or tuple(viol.shape) != (B,) or viol.dtype != torch.int32:
-            raise ValueError('viol must be a [%d] int32 tensor, got %s' % (B, '%s %s' % (tuple(viol.shape), viol.dtype) if isinstance(viol, torch.Tensor)
-                                                                         else type(viol).__name__))
-    return B, int(span)
-
-
-def _llr_batch(llr, device, n_var):
-    """A checked [B, n_var] LLR batch as the decoder kernels read it: f32 on ``device``, unit column stride, rows that do not
-    overlap (copied only where it is not)."""
-    llr = llr.to(device, torch.float32)
-    if llr.shape[0] and (llr.stride(1) != 1 or llr.stride(0) < n_var):
-        llr = llr.contiguous()
-    return llr
-
-
-def _decode_outputs(B, n_var, device, post_dtype=None):
-    """A decoder's outputs, uninitialised: (x [B, n_var] uint8, posteriors [B, n_var] ``post_dtype`` or None, viol [B] int32,
-    iters [B] int32)."""
-    return (torch.empty((B, n_var), device=device, dtype=torch.uint8),
-            None if post_dtype is None else torch.empty((B, n_var), device=device, dtype=post_dtype),
-            torch.empty((B,), device=device, dtype=torch.int32), torch.empty((B,), device=device, dtype=torch.int32))
-
-
-class LdpcDataPath:
+class LdpcDataPath(LdpcDecoders):
     """The data path of one regular LDPC code (``code``: an ``LdpcCode``; None: the built-in 96.3.963 — 48 message bits, 48 parity
     bits, 3 checks per variable, 6 variables per check): K message bits, P parity bits (codeword = [s | G s]), N = K + P variables,
     M checks.  The shapes below are written for the built-in code; for another, 96 reads N, 48 reads K (bits) or M (checks), 3 reads
     dv and 6 / 7 read dc / dc + 1.  A code whose rows of G fit one 64-bit word (K, P <= 64) runs the one-word encoder and sampler
     (csrc/ldpc_datapath.hip), as the built-in code always has; any other the W-word ones (csrc/ldpc_code.hip).
-    ``sample`` mirrors ``ContinousCodesSP.__getitem__`` over a batch."""
+    ``sample`` mirrors ``ContinousCodesSP.__getitem__`` over a batch.  The decoders (``decode``, ``decode_llr``, ``decode_osd``) are
+    the base class's (``ldpc_decoders.LdpcDecoders``)."""
     K, P = 48, 48                                   # (the built-in code's; an instance carries its code's)
     sigma_b_choices = (0, 1, 2, 3, 4, 5)            # ldpc_dataset.py:212
     snr_db_choices = (0, 1, 2, 3, 4)                # ldpc_dataset.py:216
@@ -136,9 +65,7 @@ class LdpcDataPath:
         self.code = code
         self.K, self.P, self.N, self.M, self.dv, self.dc, self.W = code.K, code.P, code.n_var, code.n_chk, code.dv, code.dc, code.W
         self.one_word = code.K <= 64 and 1 <= code.P <= 64       # the one-word kernels' family (fgnn_ldpc_encode, fgnn_ldpc_sample_rng)
-        self._decode_tables = None                               # built on the first ``decode`` (a code may exceed the decoder only)
-        self._llr_tables = None                                  # ... and on the first ``decode_llr``
-        self._osd_tables = None                                  # ... and on the first ``decode_osd``
+        super().__init__()                                       # the decoders' state: device tables, loaded learned checkpoints
         gwords = code.gwords.view(np.int64)                       # [P, W]; the one-word kernels' gmask is its column 0, [P]
         self.gmask = torch.from_numpy((gwords[:, 0] if self.one_word else gwords).copy()).to(self.device)
         self.var_to_factors = torch.from_numpy(code.var_to_factors.astype(np.int32)).to(self.device)
@@ -250,11 +177,11 @@ class LdpcDataPath:
         out = {'noizy_sg': y.cpu(), 'gts': cw.long().cpu(), 'snr_dbs': snr[:, None].expand(-1, self.N).contiguous().cpu(),
                'sigma_b': sb.cpu()}
         if baseline:
-            from .ldpc_eval import LdpcErrorCounts
-            acc = LdpcErrorCounts(dev, snr_db, sigma_b)
+            from .ldpc_eval import LdpcErrorCounts      # (here: ldpc_eval imports this module)
+            acc, mackay = LdpcErrorCounts(dev, snr_db, sigma_b), parse_decoder('mackay')
             for i in range(0, n, chunk):
                 j = min(n, i + chunk)
-                x = self.decode(self.bit_prior(y[i:j], snr[i:j]), loops=100)[0]
+                x = mackay.run(self, y[i:j], snr[i:j])[0]
                 acc.add_bits(x, cw[i:j], snr[i:j], sb[i:j], nbits=self.K)
             out['sp_error'] = torch.from_numpy(acc.result()['err_class'])
         return out
@@ -266,86 +193,6 @@ class LdpcDataPath:
         d = self.make_test_set(num, seed, snr_db, sigma_b, burst_prob, baseline)
         torch.save({k: d[k] for k in ('noizy_sg', 'gts', 'snr_dbs', 'sigma_b')}, path)
         return d.get('sp_error')
-
-    def _incidence_tables(self):
-        """``code.incidence_tables()`` on the device, then (N, M, E).  (The degree limits are ``require_decoder``'s /
-        ``require_llr_decoder``'s, which the callers run first.)"""
-        tabs = self.code.incidence_tables()
-        dev = lambda a: torch.from_numpy(a.copy()).to(self.device)      # (a copy: the code's arrays are read-only)
-        return tuple(dev(a) for a in tabs) + (self.code.n_var, self.code.n_chk, int(tabs[0][-1]))
-
-    def bit_prior(self, y, snr_db):
-        """`y2b` (MNC_py.cpp:104-108): P(bit = 1 | y) = 1 / (1 + exp(-2 gcx y)), float64."""
-        gcx = torch.pow(10.0, snr_db.to(self.device, torch.float64) / 20.0)[:, None]
-        return 1.0 / (1.0 + torch.exp(-2.0 * gcx * y.to(self.device, torch.float64)))
-
-    def decode(self, bias, loops=100, want_posteriors=False):
-        """The reference's sum-product baseline `zb2x(bias, 48, 48, A2, 1, loops)` (lib/data/ldpc.py:18-24) for a
-        batch: bias [B,96] float64 = P(bit = 1) (see ``bit_prior``).  Returns (x [B,96] uint8 hard decisions — the
-        message is x[:, :48] —, violated checks [B] int32, iterations [B] int32[, q1 [B,96] float64])."""
-        if self._decode_tables is None:
-            self.code.require_decoder()
-            self._decode_tables = self._incidence_tables()
-        col_ptr, row_ptr, row_edge, row_var, N, M, E = self._decode_tables
-        if bias.dim() != 2 or bias.shape[1] != N:
-            raise ValueError('bias must be [B, %d], got %s' % (N, tuple(bias.shape)))
-        bias = bias.to(self.device, torch.float64).contiguous()
-        B = bias.shape[0]
-        x, q1, viol, iters = _decode_outputs(B, N, self.device, torch.float64 if want_posteriors else None)
-        _hip.call('fgnn_ldpc_decode', bias, col_ptr, row_ptr, row_edge, row_var, B, N, M, E, int(loops), x, q1, viol, iters)
-        return (x, viol, iters, q1) if want_posteriors else (x, viol, iters)
-
-    def bit_llr(self, y, snr_db):
-        """The log-likelihood ratio of ``bit_prior``: log P(bit = 0 | y) / P(bit = 1 | y) = -2 gcx y with gcx = 10^(snr_db / 20), f32;
-        y [B, N], snr_db [B]."""
-        gcx = torch.pow(10.0, snr_db.to(self.device, torch.float32) / 20.0)[:, None]
-        return -2.0 * gcx * y.to(self.device, torch.float32)
-
-    def decode_llr(self, llr, algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.8125, beta=0.5, want_posteriors=False):
-        """The LLR-domain decoders (fgnn_ldpc_decode_llr, include/fgnn_hip_ldpc_llr.h; no counterpart in the reference) for a batch:
-        llr [B, N] = log P(bit = 0) / P(bit = 1) (see ``bit_llr``; f32, rows may be strided).  ``algorithm``: 'min-sum' (normalized
-        by ``alpha``), 'offset-min-sum' (offset ``beta``) or 'sum-product'; ``schedule``: 'flooding', or 'layered' over
-        ``code.layers()``.  Returns (x [B, N] uint8 hard decisions — the message is x[:, :K] —, violated checks [B] int32, iterations
-        [B] int32[, post [B, N] f32: the final totals])."""
-        B, alg = check_decode_llr_args(llr, self.N, algorithm, schedule, max_iter, alpha, beta)
-        if self._llr_tables is None:
-            self.code.require_llr_decoder()
-            lp, lc = self.code.layers()
-            dev = lambda a: torch.from_numpy(np.array(a, np.int32)).to(self.device)       # (a copy: the code's arrays are read-only)
-            self._llr_tables = self._incidence_tables() + (dev(lp), dev(lc), len(lp) - 1)
-        col_ptr, row_ptr, row_edge, row_var, N, M, E, layer_ptr, layer_chk, n_layers = self._llr_tables
-        llr = _llr_batch(llr, self.device, N)
-        x, post, viol, iters = _decode_outputs(B, N, self.device, torch.float32 if want_posteriors else None)
-        layered = schedule == 'layered'
-        _hip.call('fgnn_ldpc_decode_llr', llr, llr.stride(0) if B else N, col_ptr, row_ptr, row_edge, row_var,
-                  layer_ptr if layered else None, layer_chk if layered else None, n_layers if layered else 0, B, N, M, E, alg,
-                  int(max_iter), float(alpha), float(beta), x, post, viol, iters)
-        return (x, viol, iters, post) if want_posteriors else (x, viol, iters)
-
-    def decode_osd(self, rel, metric=None, viol=None, order=1, span=None):
-        """Ordered-statistics reprocessing (fgnn_ldpc_osd, include/fgnn_hip_ldpc_osd.h; no counterpart in the reference) for a batch:
-        rel [B, N] orders the positions and gives the hard decisions (a decoder's posteriors: ``decode_llr(..., want_posteriors=True)``),
-        ``metric`` [B, N] is what candidates are scored against (the channel LLRs, ``bit_llr``; None: rel), ``viol`` [B] int32 the
-        decoder's violated checks: a word with none passes through (None: every word is reprocessed).  ``order`` 0, 1 or 2 over the
-        ``span`` least reliable non-pivot positions (default: N for order 0 and 1, 64 for order 2; at most 256 with order 2).  Rows may
-        be strided.  Returns (x [B, N] uint8 — every reprocessed word satisfies every check —, cost [B] int32: the quantised
-        discrepancy of x to ``metric``, pattern [B] int32: the winning candidate's index, -1 for a word passed through)."""
-        B, span = check_decode_osd_args(rel, metric, viol, self.N, order, span)
-        if self._osd_tables is None:
-            self.code.require_llr_decoder()
-            _, row_ptr, _, row_var, N, M, E = self._incidence_tables()
-            if int(_hip.invoke('fgnn_ldpc_osd_lds_bytes', N, M)) < 0:
-                raise ValueError(_hip.lib().fgnn_last_error().decode())
-            self._osd_tables = (row_ptr, row_var, N, M, E)
-        row_ptr, row_var, N, M, E = self._osd_tables
-        rel = _llr_batch(rel, self.device, N)
-        metric = None if metric is None else _llr_batch(metric, self.device, N)
-        viol = None if viol is None else viol.to(self.device).contiguous()
-        x = torch.empty((B, N), device=self.device, dtype=torch.uint8)
-        cost, pattern = (torch.empty((B,), device=self.device, dtype=torch.int32) for _ in range(2))
-        _hip.call('fgnn_ldpc_osd', rel, rel.stride(0) if B else N, metric, metric.stride(0) if B and metric is not None else N, viol,
-                  row_ptr, row_var, B, N, M, E, int(order), span, x, cost, pattern)
-        return x, cost, pattern
 
     def sample(self, B, seed=0, dtype=torch.float32, snr_db=None, burst_prob=0.05, kernel_rng=False, step=0):
         """A batch of B training items (ldpc_dataset.py:222-236): random messages, encoded, sent through the

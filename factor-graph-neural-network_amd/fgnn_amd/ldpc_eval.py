@@ -7,7 +7,8 @@ set through ``lib.data.Codes``, runs the model in batches of 100 and prints the 
 
 Here the whole loop stays on the device: ``LdpcDataPath.received_features`` builds the model inputs from the stored received words,
 ``LdpcErrorCounts`` accumulates the counts with one launch per batch (csrc/ldpc_eval.hip) and reads them back once, and
-``LdpcDataPath.make_test_set`` / ``write_test_set`` generate test sets.  ``python -m fgnn_amd.ldpc_eval`` is the command line.
+``LdpcDataPath.make_test_set`` / ``write_test_set`` generate test sets.  The classical decoders evaluated beside a model are
+``ldpc_decoders.parse_decoder``'s ``Decoder`` values.  ``python -m fgnn_amd.ldpc_eval`` is the command line.
 """
 import argparse
 import contextlib
@@ -19,6 +20,10 @@ import torch
 
 from . import _hip
 from .datapath import LdpcDataPath, check_grids
+from .ldpc import LDPCModel
+from .ldpc_code import LdpcCode
+from .ldpc_decoders import parse_decoder
+from .ldpc_train import build_model
 
 SNR_GRID = (0, 1, 2, 3, 4)              # train_ldpc.py:298 (SNR) and the acc_cnt rows
 SIGMA_GRID = (0, 1, 2, 3, 4, 5)         # train_ldpc.py:320 (range(6)) and the acc_cnt columns
@@ -133,97 +138,12 @@ def load_test_set(test_set, device, n_var=96):
 def load_model(model_path, code=None, aggregator='max', device='cpu'):
     """The model of a checkpoint (``ldpc_train``'s or the reference script's) for ``code`` (None: the built-in 96.3.963).  A checkpoint
     trained for another code — its 'code' entry, or the lack of one, says which — is refused with a ValueError."""
-    from .ldpc_code import LdpcCode
-    from .ldpc_train import build_model
     code = LdpcCode.builtin() if code is None else code
     ckpt = torch.load(model_path, map_location='cpu', weights_only=True)
     code.check_checkpoint(ckpt, model_path)
     model = build_model(aggregator, code)
     model.load_state_dict(ckpt['model_state_dict'], strict=True)
     return model.to(device)
-
-
-def parse_decoder(spec):
-    """A classical decoder's spec -> (canonical spec, kind, arguments).  ``'mackay'``: the reference's probability-domain sum-product
-    (``LdpcDataPath.decode``, 100 loops; ``mackay:iters=N`` for another count), kind 'mackay', arguments {'loops'}.  Otherwise
-    ``ALGORITHM[:SCHEDULE][:iters=N][:alpha=A][:beta=B][:osd=W[:span=L]]`` with ALGORITHM 'min-sum', 'offset-min-sum' or
-    'sum-product' and SCHEDULE 'flooding' (the default) or 'layered': kind 'llr', the keyword arguments of ``LdpcDataPath.decode_llr``.  The canonical spec
-    names the schedule and then only what differs from the defaults, in the order iters, alpha, beta; parsing it gives itself.
-    The LLR-domain specs take two more options behind ``beta``: ``osd=W`` (0..2) runs ordered-statistics reprocessing of order W on
-    the words the decoder leaves with violated checks (``LdpcDataPath.decode_osd``), and ``span=L`` (>= 1; needs osd >= 1; at most
-    256 with osd=2) bounds the positions it flips; the arguments then hold 'osd' (and 'span'), and the canonical spec appends them in
-    that order.
-    ``learned-min-sum:CHECKPOINT``: the trained min-sum decoder of an ``ldpc_nms_train`` checkpoint (``ldpc_nms.LearnedMinSum``), kind
-    'learned', arguments {'path'}; everything behind the first colon is the path (it may hold colons), and the spec is canonical as
-    it stands."""
-    from .datapath import LLR_ALGORITHMS, LLR_SCHEDULES, OSD_MAX_ORDER, OSD_MAX_PAIR_SPAN
-    from .ldpc_nms import KIND as LEARNED
-    if not isinstance(spec, str) or not spec:
-        raise ValueError('a decoder spec is a non-empty string, got %r' % (spec,))
-    if spec == LEARNED or spec.startswith(LEARNED + ':'):
-        ckpt = spec[len(LEARNED) + 1:]
-        if not ckpt:
-            raise ValueError('decoder spec %r: %s:CHECKPOINT needs the path of a checkpoint' % (spec, LEARNED))
-        return spec, 'learned', {'path': ckpt}
-    head, *rest = spec.split(':')
-    opts, schedule = {}, None
-    for part in rest:
-        if part in LLR_SCHEDULES and schedule is None and not opts:
-            schedule = part
-            continue
-        key, eq, val = part.partition('=')
-        if not eq or key not in ('iters', 'alpha', 'beta', 'osd', 'span') or key in opts:
-            raise ValueError('decoder spec %r: cannot read %r (SCHEDULE, iters=N, alpha=A, beta=B, osd=W, span=L)' % (spec, part))
-        try:
-            opts[key] = int(val) if key in ('iters', 'osd', 'span') else float(val)
-        except ValueError:
-            raise ValueError('decoder spec %r: %s=%r is not a number' % (spec, key, val)) from None
-        if not (opts[key] >= (1 if key in ('iters', 'span') else 0)) or opts[key] > (OSD_MAX_ORDER if key == 'osd' else 3.0e38):
-            raise ValueError('decoder spec %r: %s=%r is out of range' % (spec, key, val))
-    if head == 'mackay':
-        if schedule is not None or set(opts) - {'iters'}:
-            raise ValueError('decoder spec %r: mackay takes iters=N only' % spec)
-        loops = opts.get('iters', 100)
-        return 'mackay' + (':iters=%d' % loops if loops != 100 else ''), 'mackay', {'loops': loops}
-    if head not in LLR_ALGORITHMS:
-        raise ValueError('decoder spec %r: unknown decoder %r (mackay, %s)' % (spec, head, ', '.join(LLR_ALGORITHMS)))
-    if 'alpha' in opts and head != 'min-sum' or 'beta' in opts and head != 'offset-min-sum':
-        raise ValueError('decoder spec %r: alpha belongs to min-sum, beta to offset-min-sum' % spec)
-    kw = {'algorithm': head, 'schedule': schedule or 'flooding', 'max_iter': opts.get('iters', 50), 'alpha': opts.get('alpha', 0.8125),
-          'beta': opts.get('beta', 0.5)}
-    canon = '%s:%s' % (head, kw['schedule'])
-    canon += ':iters=%d' % kw['max_iter'] if kw['max_iter'] != 50 else ''
-    canon += ':alpha=%r' % kw['alpha'] if kw['alpha'] != 0.8125 else ''
-    canon += ':beta=%r' % kw['beta'] if kw['beta'] != 0.5 else ''
-    if 'span' in opts and (opts.get('osd', 0) < 1 or opts['span'] >= 2 ** 31 or opts['osd'] == 2 and opts['span'] > OSD_MAX_PAIR_SPAN):
-        raise ValueError('decoder spec %r: span=L needs osd=1 or osd=2 (then L <= %d)' % (spec, OSD_MAX_PAIR_SPAN))
-    for key in ('osd', 'span'):
-        if key in opts:
-            kw[key] = opts[key]
-            canon += ':%s=%d' % (key, opts[key])
-    return canon, 'llr', kw
-
-
-def run_decoder(path, decoder, y, snr0):
-    """Hard decisions, violated checks and iterations of a parsed decoder (``parse_decoder``'s result) on received words y [B, N] at
-    snr0 [B] dB, through ``path`` (an ``LdpcDataPath``).  A learned decoder's checkpoint is loaded on the first call and kept on
-    ``path`` (once per checkpoint path); one trained for another code than ``path.code`` is refused (``LdpcCode.check_checkpoint``)."""
-    _, kind, kw = decoder
-    if kind == 'mackay':
-        return path.decode(path.bit_prior(y, snr0), **kw)
-    if kind == 'learned':
-        loaded = path.__dict__.setdefault('_learned', {})
-        if kw['path'] not in loaded:
-            from .ldpc_nms import load_checkpoint
-            loaded[kw['path']] = load_checkpoint(kw['path'], path.code, path.device)
-        return loaded[kw['path']].decode(path.bit_llr(y, snr0))
-    llr = path.bit_llr(y, snr0)
-    if 'osd' in kw:         # BP-OSD: the words the decoder leaves with violated checks are reprocessed against the channel LLRs
-        bp = {k: v for k, v in kw.items() if k not in ('osd', 'span')}
-        _, viol, iters, post = path.decode_llr(llr, want_posteriors=True, **bp)
-        x = path.decode_osd(post, metric=llr, viol=viol, order=kw['osd'], span=kw.get('span'))[0]
-        return x, torch.zeros_like(viol), iters
-    return path.decode_llr(llr, **kw)
 
 
 def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=False, snr_grid=SNR_GRID, sigma_grid=SIGMA_GRID, code=None):
@@ -236,11 +156,12 @@ def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=Fal
     over its K message bits and the baseline runs on its ``nlist``.  ``model`` may also be a checkpoint's path (``load_model``)."""
     if dtype not in (torch.float32, torch.bfloat16):
         raise ValueError('dtype must be float32 or bfloat16')
-    specs = () if baseline is None or isinstance(baseline, bool) else (baseline,) if isinstance(baseline, str) else tuple(baseline)
-    parsed = [(spec, parse_decoder(spec)) for spec in specs]
+    if baseline is True:
+        baseline = 'mackay'         # the sum-product table is that spec's
+    specs = () if baseline is None or baseline is False else (baseline,) if isinstance(baseline, str) else tuple(baseline)
+    parsed = [parse_decoder(spec) for spec in specs]
     if len(set(specs)) != len(specs):
         raise ValueError('baseline lists a decoder twice: %s' % (specs,))
-    from .ldpc_code import LdpcCode
     code = LdpcCode.builtin() if code is None else code
     if isinstance(model, (str, os.PathLike)):
         model = load_model(model, code, device='cuda')
@@ -252,8 +173,7 @@ def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=Fal
         raise ValueError('batch_size must be >= 1')
     dev = next(model.parameters()).device
     counts = LdpcErrorCounts(dev, snr_grid, sigma_grid)
-    sp = LdpcErrorCounts(dev, snr_grid, sigma_grid) if baseline is True else None
-    decoders = [(spec, decoder, LdpcErrorCounts(dev, snr_grid, sigma_grid)) for spec, decoder in parsed]
+    decoders = [(spec, decoder, LdpcErrorCounts(dev, snr_grid, sigma_grid)) for spec, decoder in zip(specs, parsed)]
     path = LdpcDataPath(dev, code)
     y, gts, snr, sb = load_test_set(test_set, dev, code.n_var)
     n = y.shape[0]
@@ -269,17 +189,12 @@ def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=Fal
                                   path.nn_idx_v2f.unsqueeze(0).expand(B, -1, -1), ef_f2v, ef_v2f)
                 counts.add_logits(logits, gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
                 snr0 = snr[i:j] if snr.dim() == 1 else snr[i:j, 0]
-                if baseline is True:
-                    x = path.decode(path.bit_prior(y[i:j], snr0), loops=100)[0]
-                    sp.add_bits(x, gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
                 for _, decoder, acc in decoders:
-                    acc.add_bits(run_decoder(path, decoder, y[i:j], snr0)[0], gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
+                    acc.add_bits(decoder.run(path, y[i:j], snr0)[0], gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
     finally:
         model.train(was)
     res = counts.result()
-    if baseline is True:
-        res['baseline'] = sp.result()
-    elif isinstance(baseline, str):
+    if isinstance(baseline, str):
         res['baseline'] = decoders[0][2].result()
     elif decoders:
         res['baselines'] = {spec: acc.result() for spec, _, acc in decoders}
@@ -296,7 +211,6 @@ def ber_curve(code, decoder, snr_db, sigma_b=0, batch=4096, min_word_errors=100,
     Reproducible from the arguments: the j-th batch (j = 0, 1, ...) of the i-th SNR value (in the order given) is
     ``sample_rng(batch, seed=seed, step=i * 2**32 + j)``, so no two batches of a curve share their draws (at most 2**32 batches per
     point).  Returns a list of dicts, one per SNR value: snr_db, words, bit_errors, word_errors, ber, wer, mean_iters."""
-    from .ldpc_code import LdpcCode
     code = LdpcCode.builtin() if code is None else code
     decoder = parse_decoder(decoder)
     snr_db = [float(v) for v in ([snr_db] if np.isscalar(snr_db) else snr_db)]
@@ -315,7 +229,7 @@ def ber_curve(code, decoder, snr_db, sigma_b=0, batch=4096, min_word_errors=100,
         drawn = None
         for j in range(2 ** 32):
             drawn = path.sample_rng(batch, seed=seed, step=i * 2 ** 32 + j, snr_db=snr, out=drawn)
-            x, _, iters = run_decoder(path, decoder, drawn.y, drawn.snr_db)[:3]
+            x, _, iters = decoder.run(path, drawn.y, drawn.snr_db)[:3]
             acc.add_bits(x, drawn.cw, drawn.snr_db, drawn.sigma_b, nbits=code.K)
             it_sum += iters.sum()
             tot = acc.counts[-1].tolist()
@@ -353,7 +267,6 @@ def main(argv=None):
     ap.add_argument('--code', default='builtin', help='builtin (96.3.963), the path of an alist file, or gallager:N,dv,dc,seed')
     args = ap.parse_args(argv)
     dev = torch.device('cuda:0')
-    from .ldpc_code import LdpcCode
     code = LdpcCode.from_spec(args.code)
     if args.make_test_set:
         sp = LdpcDataPath(dev, code).write_test_set(args.make_test_set, args.num, seed=args.seed, burst_prob=args.burst_prob)
@@ -372,7 +285,6 @@ def main(argv=None):
     if not args.test_path or not args.model_path:
         ap.error('give --test_path and --model_path, or --make_test_set, or --curve')
     if code.is_default:
-        from .ldpc import LDPCModel
         with contextlib.redirect_stdout(sys.stderr):           # (the model's construction talks; stdout carries the result only)
             model = LDPCModel(2, 6, 4, aggregator=args.aggregator)
         ckpt = torch.load(args.model_path, map_location=dev)

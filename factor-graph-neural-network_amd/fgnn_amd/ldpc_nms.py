@@ -18,12 +18,11 @@ import numpy as np
 import torch
 
 from . import _hip
-from .datapath import _decode_outputs, _llr_batch
 from .ldpc_code import LdpcCode
+from .ldpc_decoders import LEARNED as KIND, check_word_batch, decode_outputs, llr_batch   # KIND: a checkpoint's decoder['kind']
 
 SHARES = {'iteration': 0, 'check': 1, 'edge': 2}       # fgnn_ldpc_nms_forward's ``share``
 MAX_ITER = 64                                          # csrc/ldpc_nms.hip's NMS_MAXIT
-KIND = 'learned-min-sum'                               # a checkpoint's decoder['kind'], and the head of ldpc_eval's spec
 
 
 def check_nms_args(llr, n_var, n_chk, n_edges, n_iter, share, alpha, beta):
@@ -35,13 +34,7 @@ def check_nms_args(llr, n_var, n_chk, n_edges, n_iter, share, alpha, beta):
         if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != (int(n_iter), W):
             raise ValueError('%s must be a float32 tensor [%d, %d], got %s' % (
                 what, n_iter, W, '%s %s' % (v.dtype, tuple(v.shape)) if isinstance(v, torch.Tensor) else type(v).__name__))
-    if not isinstance(llr, torch.Tensor) or llr.dim() != 2 or llr.shape[1] != int(n_var):
-        raise ValueError('llr must be a [B, %d] tensor, got %s' % (n_var, tuple(llr.shape) if isinstance(llr, torch.Tensor) else type(llr).__name__))
-    if not llr.dtype.is_floating_point:
-        raise ValueError('llr must be a floating-point tensor, got %s' % llr.dtype)
-    if llr.shape[0] >= 2 ** 31:
-        raise ValueError('at most 2^31 - 1 words per call, got %d' % llr.shape[0])
-    return llr.shape[0], SHARES[share], W
+    return check_word_batch('llr', llr, n_var), SHARES[share], W
 
 
 def weights_per_iteration(n_iter, share, n_chk, n_edges):
@@ -146,7 +139,7 @@ class LearnedMinSum(torch.nn.Module):
         B, share, _ = check_nms_args(llr, self.N, self.M, self.E, self.n_iter, self.share, self.alpha, self.beta)
         if self.alpha.device.type != 'cuda':
             raise RuntimeError('LearnedMinSum runs on a ROCm device (no CPU fallback): move the module there first')
-        return _llr_batch(llr, self.alpha.device, self.N), B, share, (self.col_ptr, self.row_ptr, self.row_edge, self.row_var), (self.N, self.M, self.E)
+        return llr_batch(llr, self.alpha.device, self.N), B, share, (self.col_ptr, self.row_ptr, self.row_edge, self.row_var), (self.N, self.M, self.E)
 
     def forward(self, llr):
         """llr [B, N] = log P(bit = 0) / P(bit = 1) -> totals [n_iter, B, N] f32, every iteration's totals (no early stop), through
@@ -159,7 +152,7 @@ class LearnedMinSum(torch.nn.Module):
         """The decode mode (a word stops after the first iteration that leaves no violated check): (x [B, N] uint8 hard decisions —
         the message is x[:, :K] —, violated checks [B] int32, iterations [B] int32[, post [B, N] f32: the final totals])."""
         llr, B, share, tables, (N, M, E) = self._prepare(llr)
-        x, post, viol, iters = _decode_outputs(B, N, llr.device, torch.float32 if want_posteriors else None)
+        x, post, viol, iters = decode_outputs(B, N, llr.device, torch.float32 if want_posteriors else None)
         _hip.call('fgnn_ldpc_nms_forward', llr, llr.stride(0) if B else N, *tables, self.alpha.detach().contiguous(),
                   self.beta.detach().contiguous(), B, N, M, E, int(self.n_iter), share, 1, x, post, viol, iters, None, None, 0)
         return (x, viol, iters, post) if want_posteriors else (x, viol, iters)

@@ -137,7 +137,7 @@ def reprocess(rel, metric, viol, H, order, span, sts=None):
 
 
 def bp_osd(llr, tabs, layers, H, order, span, algorithm='min-sum', max_iter=20, **kw):
-    """The composition ``ldpc_eval.run_decoder`` runs: ``ldpc_llr_oracle.decode``, then reprocessing of its posteriors against the
+    """The composition ``ldpc_decoders.Decoder.run`` runs: ``ldpc_llr_oracle.decode``, then reprocessing of its posteriors against the
     channel LLRs, the words it finished passed through.  Returns (x, cost, pattern, the decoder's result)."""
     import ldpc_llr_oracle as LO
     r = LO.decode(llr, tabs, layers, algorithm, max_iter, **kw)

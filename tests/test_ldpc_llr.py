@@ -129,35 +129,41 @@ def test_require_llr_decoder():
     assert 'require_llr_decoder' in C.__doc__ and (C.LLR_MAXV, C.LLR_MAXD) == (1024, 16)
 
 
+# decoder specs -> parse_decoder's (canonical spec, kind, arguments), and specs it refuses: test_ldpc_nms.py and test_ldpc_osd.py hold
+# the parser to the same table
+PARSED = (
+    ('mackay', 'mackay', 'mackay', {'loops': 100}),
+    ('mackay:iters=20', 'mackay:iters=20', 'mackay', {'loops': 20}),
+    ('min-sum', 'min-sum:flooding', 'llr', dict(algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.8125, beta=0.5)),
+    ('min-sum:layered', 'min-sum:layered', 'llr', dict(algorithm='min-sum', schedule='layered', max_iter=50, alpha=0.8125, beta=0.5)),
+    ('min-sum:alpha=0.75', 'min-sum:flooding:alpha=0.75', 'llr',
+     dict(algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.75, beta=0.5)),
+    ('offset-min-sum:layered:beta=0.25', 'offset-min-sum:layered:beta=0.25', 'llr',
+     dict(algorithm='offset-min-sum', schedule='layered', max_iter=50, alpha=0.8125, beta=0.25)),
+    ('sum-product:flooding:iters=100', 'sum-product:flooding:iters=100', 'llr',
+     dict(algorithm='sum-product', schedule='flooding', max_iter=100, alpha=0.8125, beta=0.5)),
+    ('sum-product:layered:iters=50', 'sum-product:layered', 'llr',
+     dict(algorithm='sum-product', schedule='layered', max_iter=50, alpha=0.8125, beta=0.5)))
+JUNK = ('', None, 7, 'max-sum', 'min-sum:', 'min-sum:zigzag', 'min-sum:layered:flooding', 'min-sum:iters=0', 'min-sum:iters=x',
+        'min-sum:iters=2:iters=3', 'min-sum:alpha=-1', 'min-sum:alpha=nan', 'min-sum:alpha=inf', 'min-sum:beta=0.5',
+        'offset-min-sum:alpha=0.5', 'sum-product:alpha=0.5', 'min-sum:iters=3:layered', 'mackay:layered', 'mackay:alpha=1',
+        'min-sum:gamma=1', 'min-sum:iters')
+
+
 def test_parse_decoder_round_trips_and_refuses_junk():
     from fgnn_amd.ldpc_eval import parse_decoder
-    for spec, canon, kind, kw in (
-            ('mackay', 'mackay', 'mackay', {'loops': 100}),
-            ('mackay:iters=20', 'mackay:iters=20', 'mackay', {'loops': 20}),
-            ('min-sum', 'min-sum:flooding', 'llr', dict(algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.8125, beta=0.5)),
-            ('min-sum:layered', 'min-sum:layered', 'llr', dict(algorithm='min-sum', schedule='layered', max_iter=50, alpha=0.8125, beta=0.5)),
-            ('min-sum:alpha=0.75', 'min-sum:flooding:alpha=0.75', 'llr',
-             dict(algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.75, beta=0.5)),
-            ('offset-min-sum:layered:beta=0.25', 'offset-min-sum:layered:beta=0.25', 'llr',
-             dict(algorithm='offset-min-sum', schedule='layered', max_iter=50, alpha=0.8125, beta=0.25)),
-            ('sum-product:flooding:iters=100', 'sum-product:flooding:iters=100', 'llr',
-             dict(algorithm='sum-product', schedule='flooding', max_iter=100, alpha=0.8125, beta=0.5)),
-            ('sum-product:layered:iters=50', 'sum-product:layered', 'llr',
-             dict(algorithm='sum-product', schedule='layered', max_iter=50, alpha=0.8125, beta=0.5))):
+    for spec, canon, kind, kw in PARSED:
         got = parse_decoder(spec)
         assert got == (canon, kind, kw), spec
         assert parse_decoder(canon) == got                                  # the canonical spec parses to itself
-    for junk in ('', None, 7, 'max-sum', 'min-sum:', 'min-sum:zigzag', 'min-sum:layered:flooding', 'min-sum:iters=0', 'min-sum:iters=x',
-                 'min-sum:iters=2:iters=3', 'min-sum:alpha=-1', 'min-sum:alpha=nan', 'min-sum:alpha=inf', 'min-sum:beta=0.5',
-                 'offset-min-sum:alpha=0.5', 'sum-product:alpha=0.5', 'min-sum:iters=3:layered', 'mackay:layered', 'mackay:alpha=1',
-                 'min-sum:gamma=1', 'min-sum:iters'):
+    for junk in JUNK:
         with pytest.raises(ValueError):
             parse_decoder(junk)
 
 
 def test_check_decode_llr_args():
     import torch
-    from fgnn_amd.datapath import check_decode_llr_args
+    from fgnn_amd.ldpc_decoders import check_decode_llr_args
     llr = torch.zeros(5, 96)
     ok = dict(llr=llr, n_var=96, algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.8125, beta=0.5)
     assert check_decode_llr_args(**ok) == (5, 0)

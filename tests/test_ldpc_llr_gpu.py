@@ -29,6 +29,7 @@ import pytest
 import torch
 
 import ldpc_llr_oracle as LO
+from ldpc_decoder_cases import ZeroLogits, code as named_code, make_paths, received
 
 pytestmark = pytest.mark.gpu
 
@@ -51,23 +52,9 @@ def case(name, sum_product=False):
     """(code, tables, layers, llr [B, N] f32) of one code: the min-sum inputs, or the sum-product ones."""
     if sum_product:
         code, tabs, layers, _ = case(name)
-        return code, tabs, layers, received(code, 2000 + CODES.index(name), SP_SNR_DB[name])
-    from fgnn_amd.ldpc_code import LdpcCode
-    code = {'g12': lambda: LdpcCode.gallager(12, 3, 6, 1),              # one partly filled wave, 6 checks
-            'builtin': LdpcCode.builtin,                                # 96.3.963
-            'g32': lambda: LdpcCode.gallager(32, 16, 16, 3),            # degree 16: the per-lane worst case
-            'g384': lambda: LdpcCode.gallager(384, 3, 6, 1),            # E = 1152: the first size the f64 decoder refuses
-            'g1024': lambda: LdpcCode.gallager(1024, 4, 8, 2)}[name]()  # N at the limit, E = 4096
-    return code, LO.tables(code.nlist, code.n_chk), code.layers(), received(code, 1000 + CODES.index(name), SNR_DB[name])
-
-
-def received(code, seed, snr_db, words=B):
-    rng = np.random.RandomState(seed)
-    gcx = 10.0 ** (np.linspace(snr_db[0], snr_db[1], words)[:, None] / 20.0)
-    y = (-gcx + rng.standard_normal((words, code.n_var))).astype(np.float32)
-    llr = ((-2.0 * gcx).astype(np.float32) * y).astype(np.float32)
-    llr.setflags(write=False)
-    return llr
+        return code, tabs, layers, received(code, 2000 + CODES.index(name), SP_SNR_DB[name], B)
+    code = named_code(name)                 # (ldpc_decoder_cases.CODES says why each is here)
+    return code, LO.tables(code.nlist, code.n_chk), code.layers(), received(code, 1000 + CODES.index(name), SNR_DB[name], B)
 
 
 @functools.lru_cache(maxsize=None)
@@ -89,16 +76,7 @@ def restatement_error():
     return d, max(int((m <= 4 * d).sum()) for m in cases)
 
 
-@pytest.fixture(scope='module')
-def paths():
-    from fgnn_amd.datapath import LdpcDataPath
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = LdpcDataPath('cuda:0', case(name)[0])
-        return made[name]
-    return get
+paths = pytest.fixture(scope='module', name='paths')(make_paths)
 
 
 def bits(a):
@@ -248,22 +226,11 @@ def test_a_code_above_48_kib_of_lds():
         assert_bitwise((x.cpu().numpy(), viol.cpu().numpy(), iters.cpu().numpy(), post.cpu().numpy()), flooding)
 
 
-class _Zero(torch.nn.Module):
-    """A stand-in model: logits 0 for every message bit (evaluate only needs a module with a parameter on the device)."""
-
-    def __init__(self):
-        super().__init__()
-        self.w = torch.nn.Parameter(torch.zeros(1))
-
-    def forward(self, node, *rest):
-        return node[:, 0, :48, 0] * self.w, None
-
-
 def test_evaluate_takes_decoder_specs(paths):
     from fgnn_amd import ldpc_eval
     path = paths('builtin')
     ts = path.make_test_set(num=2, baseline=False)
-    model = _Zero().cuda()
+    model = ZeroLogits().cuda()
     res = ldpc_eval.evaluate(model, ts, baseline=['mackay', 'min-sum:layered'])
     old = ldpc_eval.evaluate(model, ts, baseline=True)
     assert 'baseline' not in res and set(res['baselines']) == {'mackay', 'min-sum:layered'}

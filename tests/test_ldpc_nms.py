@@ -24,6 +24,7 @@ import torch
 import ldpc_llr_oracle as LO
 import ldpc_nms_oracle as NO
 import test_ldpc_llr_gpu as LG
+from test_ldpc_llr import JUNK, PARSED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMPANION = os.path.join(ROOT, 'include', 'fgnn_hip_ldpc_nms.h')
@@ -232,26 +233,11 @@ def test_parse_decoder_takes_the_learned_spec_and_the_old_table_holds():
         with pytest.raises(ValueError):
             parse_decoder(junk)
     # tests/test_ldpc_llr.py::test_parse_decoder_round_trips_and_refuses_junk's table and junk list, as they are there
-    for spec, canon, kind, kw in (
-            ('mackay', 'mackay', 'mackay', {'loops': 100}),
-            ('mackay:iters=20', 'mackay:iters=20', 'mackay', {'loops': 20}),
-            ('min-sum', 'min-sum:flooding', 'llr', dict(algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.8125, beta=0.5)),
-            ('min-sum:layered', 'min-sum:layered', 'llr', dict(algorithm='min-sum', schedule='layered', max_iter=50, alpha=0.8125, beta=0.5)),
-            ('min-sum:alpha=0.75', 'min-sum:flooding:alpha=0.75', 'llr',
-             dict(algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.75, beta=0.5)),
-            ('offset-min-sum:layered:beta=0.25', 'offset-min-sum:layered:beta=0.25', 'llr',
-             dict(algorithm='offset-min-sum', schedule='layered', max_iter=50, alpha=0.8125, beta=0.25)),
-            ('sum-product:flooding:iters=100', 'sum-product:flooding:iters=100', 'llr',
-             dict(algorithm='sum-product', schedule='flooding', max_iter=100, alpha=0.8125, beta=0.5)),
-            ('sum-product:layered:iters=50', 'sum-product:layered', 'llr',
-             dict(algorithm='sum-product', schedule='layered', max_iter=50, alpha=0.8125, beta=0.5))):
+    for spec, canon, kind, kw in PARSED:
         got = parse_decoder(spec)
         assert got == (canon, kind, kw), spec
         assert parse_decoder(canon) == got
-    for junk in ('', None, 7, 'max-sum', 'min-sum:', 'min-sum:zigzag', 'min-sum:layered:flooding', 'min-sum:iters=0', 'min-sum:iters=x',
-                 'min-sum:iters=2:iters=3', 'min-sum:alpha=-1', 'min-sum:alpha=nan', 'min-sum:alpha=inf', 'min-sum:beta=0.5',
-                 'offset-min-sum:alpha=0.5', 'sum-product:alpha=0.5', 'min-sum:iters=3:layered', 'mackay:layered', 'mackay:alpha=1',
-                 'min-sum:gamma=1', 'min-sum:iters'):
+    for junk in JUNK:
         with pytest.raises(ValueError):
             parse_decoder(junk)
 

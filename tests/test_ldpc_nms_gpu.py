@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import ldpc_nms_oracle as NO
+from ldpc_decoder_cases import ZeroLogits, make_paths, received
 import test_ldpc_llr_gpu as LG
 import test_ldpc_nms as NC
 
@@ -26,16 +27,7 @@ CODES, SHARES, N_ITER = NC.CODES, NC.SHARES, NC.N_ITER
 BOUND = {k: 4 * d for k, d in NC.D.items()}
 
 
-@pytest.fixture(scope='module')
-def paths():
-    from fgnn_amd.datapath import LdpcDataPath
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = LdpcDataPath('cuda:0', LG.case(name)[0])
-        return made[name]
-    return get
+paths = pytest.fixture(scope='module', name='paths')(make_paths)
 
 
 def cuda(a):
@@ -161,7 +153,7 @@ def test_backward_is_deterministic_and_loops_over_its_words(share):
     G = backward_workgroups(10 ** 6)
     assert backward_workgroups(3) == 3 and G >= 64
     sets = -(-(G + 67) // LG.B)
-    llr = np.concatenate([LG.received(LG.case(name)[0], 5000 + i, LG.SNR_DB[name]) for i in range(sets)])
+    llr = np.concatenate([received(LG.case(name)[0], 5000 + i, LG.SNR_DB[name], LG.B) for i in range(sets)])
     B = len(llr)
     assert B > G and backward_workgroups(B) == G
     g = np.random.RandomState(4100).standard_normal((N_ITER[name], B, 12)).astype(np.float32)
@@ -228,7 +220,7 @@ def test_module_gradients_are_the_abi_calls():
     assert bwd() == 0 and torch.equal(ga, g_alpha) and torch.equal(gb, g_beta)
 
 
-def test_training_lowers_the_loss_and_its_checkpoint_evaluates(paths, tmp_path):
+def test_training_lowers_the_loss_and_its_checkpoint_evaluates(paths, tmp_path, monkeypatch):
     """``ldpc_nms_train.train`` on the built-in code: n_iter 5, per-edge weights from alpha = 1, beta = 0, 2 dB, batch 256, 40 steps.
 
     The same 40 steps through the float64 restatement on the CPU (torch autograd over ``ldpc_nms_oracle.torch_forward``, stock Adam
@@ -261,17 +253,28 @@ def test_training_lowers_the_loss_and_its_checkpoint_evaluates(paths, tmp_path):
 
     spec, fixed = 'learned-min-sum:' + ckpt, 'min-sum:flooding:iters=5:alpha=1.0'
     ts = path.make_test_set(num=200, snr_db=(2,), baseline=False)               # 1200 words at 2 dB, every burst level
-    res = ldpc_eval.evaluate(LG._Zero().cuda(), ts, baseline=[spec, fixed])
+    res = ldpc_eval.evaluate(ZeroLogits().cuda(), ts, baseline=[spec, fixed])
     learned, classical = res['baselines'][spec], res['baselines'][fixed]
     assert learned['counts'].shape == (31, 4) and learned['err_class'].shape == (5, 6)
     assert learned['counts'][-1][0] == 48 * 1200 and learned['counts'][-1][2] == 1200
     print('BER at 2 dB: learned %.5f, %s %.5f' % (learned['ber'], fixed, classical['ber']))
     assert learned['ber'] <= classical['ber']
-    single = ldpc_eval.evaluate(LG._Zero().cuda(), ts, baseline=spec)
+    single = ldpc_eval.evaluate(ZeroLogits().cuda(), ts, baseline=spec)
     assert np.array_equal(single['baseline']['counts'], learned['counts'])
     rows = ldpc_eval.ber_curve(None, spec, snr_db=(2.0,), batch=256, max_words=512, min_word_errors=10 ** 9)
     assert len(rows) == 1 and rows[0]['words'] == 512 and rows[0]['snr_db'] == 2.0 and 0 < rows[0]['ber'] < 0.5
     assert 1 <= rows[0]['mean_iters'] <= 5
+    # two runs of the spec on one path load the checkpoint once, into the dict the path declares
+    from fgnn_amd.datapath import LdpcDataPath
+    one, loads = LdpcDataPath('cuda:0'), []
+    assert one._learned == {}
+    monkeypatch.setattr(torch, 'load', lambda f, *a, _load=torch.load, **kw: loads.append(f) or _load(f, *a, **kw))
+    decoder = ldpc_eval.parse_decoder(spec)
+    first, again = decoder.run(one, held.y, held.snr_db), decoder.run(one, held.y, held.snr_db)
+    monkeypatch.undo()
+    assert loads == [ckpt] and list(one._learned) == [ckpt] and isinstance(one._learned[ckpt], LearnedMinSum)
+    assert len(first) == 3 and all(torch.equal(a, b) for a, b in zip(first, again))
+    assert all(torch.equal(a, b) for a, b in zip(first, trained.decode(llr)))
     from fgnn_amd.ldpc_code import LdpcCode
     with pytest.raises(ValueError, match='trained for'):                        # a checkpoint of another code is refused
         ldpc_eval.ber_curve(LdpcCode.gallager(24, 3, 6, 0), spec, snr_db=(2.0,), batch=64, max_words=64)

@@ -20,6 +20,7 @@ import pytest
 import ldpc_llr_oracle as LO
 import ldpc_osd_oracle as OO
 import test_ldpc_osd_gpu as G
+from test_ldpc_llr import JUNK, PARSED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMPANION = os.path.join(ROOT, 'include', 'fgnn_hip_ldpc_osd.h')
@@ -90,7 +91,7 @@ def test_library_footprint_and_validation_without_a_device():
 
 def test_check_decode_osd_args():
     import torch
-    from fgnn_amd.datapath import check_decode_osd_args
+    from fgnn_amd.ldpc_decoders import check_decode_osd_args
     rel = torch.zeros(5, 96)
     ok = dict(rel=rel, metric=None, viol=None, n_var=96, order=1, span=None)
     assert check_decode_osd_args(**ok) == (5, 96)                                          # the default spans
@@ -141,28 +142,13 @@ def test_parse_decoder_takes_osd_and_span():
         assert got == (canon, 'llr', kw), spec
         assert parse_decoder(canon) == got                                  # the canonical spec parses to itself
     # the table of test_ldpc_llr.py: identical triples, no 'osd' and no 'span' among the arguments
-    for spec, canon, kind, kw in (
-            ('mackay', 'mackay', 'mackay', {'loops': 100}),
-            ('mackay:iters=20', 'mackay:iters=20', 'mackay', {'loops': 20}),
-            ('min-sum', 'min-sum:flooding', 'llr', dict(algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.8125, beta=0.5)),
-            ('min-sum:layered', 'min-sum:layered', 'llr', dict(algorithm='min-sum', schedule='layered', max_iter=50, alpha=0.8125, beta=0.5)),
-            ('min-sum:alpha=0.75', 'min-sum:flooding:alpha=0.75', 'llr',
-             dict(algorithm='min-sum', schedule='flooding', max_iter=50, alpha=0.75, beta=0.5)),
-            ('offset-min-sum:layered:beta=0.25', 'offset-min-sum:layered:beta=0.25', 'llr',
-             dict(algorithm='offset-min-sum', schedule='layered', max_iter=50, alpha=0.8125, beta=0.25)),
-            ('sum-product:flooding:iters=100', 'sum-product:flooding:iters=100', 'llr',
-             dict(algorithm='sum-product', schedule='flooding', max_iter=100, alpha=0.8125, beta=0.5)),
-            ('sum-product:layered:iters=50', 'sum-product:layered', 'llr',
-             dict(algorithm='sum-product', schedule='layered', max_iter=50, alpha=0.8125, beta=0.5))):
+    for spec, canon, kind, kw in PARSED:
         assert parse_decoder(spec) == (canon, kind, kw), spec
     for junk in ('min-sum:osd=3', 'min-sum:osd=-1', 'min-sum:span=4', 'min-sum:osd=0:span=4', 'min-sum:osd=2:span=257', 'mackay:osd=1',
                  'min-sum:osd=1:osd=1', 'min-sum:osd=1:span=0', 'min-sum:span=0', 'min-sum:osd', 'min-sum:osd=x', 'min-sum:osd=1.5',
                  'min-sum:osd=1:span=2:span=2', 'min-sum:osd=1:layered', 'mackay:span=4', 'learned-min-sum', 'min-sum:osd=1:span=-1',
                  # the junk of test_ldpc_llr.py stays junk
-                 '', None, 7, 'max-sum', 'min-sum:', 'min-sum:zigzag', 'min-sum:layered:flooding', 'min-sum:iters=0', 'min-sum:iters=x',
-                 'min-sum:iters=2:iters=3', 'min-sum:alpha=-1', 'min-sum:alpha=nan', 'min-sum:alpha=inf', 'min-sum:beta=0.5',
-                 'offset-min-sum:alpha=0.5', 'sum-product:alpha=0.5', 'min-sum:iters=3:layered', 'mackay:layered', 'mackay:alpha=1',
-                 'min-sum:gamma=1', 'min-sum:iters'):
+                 *JUNK):
         with pytest.raises(ValueError):
             parse_decoder(junk)
     assert parse_decoder('learned-min-sum:a:osd=1')[2] == {'path': 'a:osd=1'}           # (a learned spec: all of it is the path)

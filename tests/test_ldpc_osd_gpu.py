@@ -15,6 +15,7 @@ import torch
 
 import ldpc_llr_oracle as LO
 import ldpc_osd_oracle as OO
+from ldpc_decoder_cases import ZeroLogits, code as named_code, make_paths, received
 
 pytestmark = pytest.mark.gpu
 
@@ -25,30 +26,13 @@ SNR_DB = {'g12': (1.0, 1.0), 'g33': (3.0, 3.0), 'g63': (3.0, 3.0), 'g64': (3.0, 
           'g384': (0.5, 6.5), 'g1024': (1.0, 7.0)}          # (lo, hi) dB
 
 
-def received(code, seed, snr_db, words=B):
-    rng = np.random.RandomState(seed)
-    gcx = 10.0 ** (np.linspace(snr_db[0], snr_db[1], words)[:, None] / 20.0)
-    y = (-gcx + rng.standard_normal((words, code.n_var))).astype(np.float32)
-    llr = ((-2.0 * gcx).astype(np.float32) * y).astype(np.float32)
-    llr.setflags(write=False)
-    return llr
-
-
 @functools.lru_cache(maxsize=None)
 def case(name):
     """(code, tables, H [M, N], llr [B, N] f32, the min-sum restatement's result on llr) of one code: computed once, never written."""
-    from fgnn_amd.ldpc_code import LdpcCode
-    code = {'g12': lambda: LdpcCode.gallager(12, 3, 6, 1),              # matrix and syndrome bit in one word
-            'g33': lambda: LdpcCode.gallager(33, 3, 11, 0),             # N + 1 = 34
-            'g63': lambda: LdpcCode.gallager(63, 3, 7, 1),              # the syndrome in bit 31 of word 1
-            'g64': lambda: LdpcCode.gallager(64, 3, 8, 1),              # the syndrome bit opens a new word
-            'builtin': LdpcCode.builtin,                                # 96 / 48, one wave
-            'g32': lambda: LdpcCode.gallager(32, 16, 16, 3),            # dense, heavily rank-deficient
-            'g384': lambda: LdpcCode.gallager(384, 3, 6, 1),            # 128 threads
-            'g1024': lambda: LdpcCode.gallager(1024, 4, 8, 2)}[name]()  # 256 threads, > 48 KiB of LDS, an even dv's rank deficiency
+    code = named_code(name)                 # (ldpc_decoder_cases.CODES says why each is here)
     tabs = LO.tables(code.nlist, code.n_chk)
     H = OO.dense(tabs[1], tabs[3], code.n_var)
-    llr = received(code, 3000 + CODES.index(name), SNR_DB[name])
+    llr = received(code, 3000 + CODES.index(name), SNR_DB[name], B)
     bp = LO.decode(llr, tabs, code.layers(), 'min-sum', BP_ITERS)
     bp['post'].setflags(write=False)
     return code, tabs, H, llr, bp
@@ -79,16 +63,7 @@ def restated(name, order, span):
     return OO.reprocess(bp['post'], llr, None, H, order, span, eliminated(name))
 
 
-@pytest.fixture(scope='module')
-def paths():
-    from fgnn_amd.datapath import LdpcDataPath
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = LdpcDataPath('cuda:0', case(name)[0])
-        return made[name]
-    return get
+paths = pytest.fixture(scope='module', name='paths')(make_paths)
 
 
 def dev(a, dtype=np.float32):
@@ -227,24 +202,13 @@ def test_run_decoder_is_the_composition(paths):
     snr = np.full(B, SNR_DB['builtin'][0], np.float32)
     gcx = np.float32(10.0) ** (snr / np.float32(20.0))
     y = torch.from_numpy(np.array(llr) / (-2.0 * gcx[:, None])).cuda()
-    dllr = path.bit_llr(y, torch.from_numpy(snr).cuda()).cpu().numpy()                   # what run_decoder feeds the decoder
+    dllr = path.bit_llr(y, torch.from_numpy(snr).cuda()).cpu().numpy()                   # what Decoder.run feeds the decoder
     for spec, order, span in (('min-sum:layered:iters=20:osd=1', 1, 96), ('min-sum:layered:iters=20:osd=2:span=24', 2, 24),
                               ('min-sum:layered:iters=20:osd=0', 0, 96)):
-        x, viol, iters = ldpc_eval.run_decoder(path, ldpc_eval.parse_decoder(spec), y, torch.from_numpy(snr).cuda())
+        x, viol, iters = ldpc_eval.parse_decoder(spec).run(path, y, torch.from_numpy(snr).cuda())
         wx, _, _, r = OO.bp_osd(dllr, tabs, code.layers(), H, order, span, 'min-sum', BP_ITERS)
         assert np.array_equal(x.cpu().numpy(), wx) and not viol.any().item() and np.array_equal(iters.cpu().numpy(), r['iters'])
         assert not (H.astype(np.int64) @ wx.T.astype(np.int64) % 2).any()
-
-
-class _Zero(torch.nn.Module):
-    """A stand-in model: logits 0 for every message bit (evaluate only needs a module with a parameter on the device)."""
-
-    def __init__(self):
-        super().__init__()
-        self.w = torch.nn.Parameter(torch.zeros(1))
-
-    def forward(self, node, *rest):
-        return node[:, 0, :48, 0] * self.w, None
 
 
 def test_evaluate_and_ber_curve_count_what_the_restatement_counts(paths):
@@ -254,7 +218,7 @@ def test_evaluate_and_ber_curve_count_what_the_restatement_counts(paths):
     path = paths('builtin')
     spec = 'min-sum:layered:iters=20:osd=1'
     ts = path.make_test_set(num=2, baseline=False)
-    res = ldpc_eval.evaluate(_Zero().cuda(), ts, baseline=[spec, 'min-sum:layered:iters=20'])
+    res = ldpc_eval.evaluate(ZeroLogits().cuda(), ts, baseline=[spec, 'min-sum:layered:iters=20'])
     y, gts, snr = ts['noizy_sg'].numpy(), ts['gts'].numpy(), ts['snr_dbs'].numpy()[:, 0]
     llr = path.bit_llr(ts['noizy_sg'], ts['snr_dbs'][:, 0]).cpu().numpy()
     wx = OO.bp_osd(llr, tabs, code.layers(), H, 1, 96, 'min-sum', BP_ITERS)[0]

@@ -3,16 +3,11 @@ it — in kernels that keep the next tile / sample in flight that was an HBM rou
 compiler's own resource report (`-Rpass-analysis=kernel-resource-usage`: ScratchSize) for the sources of those kernels, cross-compiled for
 gfx950 — no GPU needed."""
 import os
-import re
-import shutil
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'factor-graph-neural-network_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+from scratch_report import HIPCC, scratch
 
 # source -> the kernels (mangled-name substrings) that must have no scratch; other instances in the same source are reported, not asserted
 MUST = {
@@ -23,29 +18,13 @@ MUST = {
     'block_tail.hip': ['block_tail_kernel', 'block_head_bwd_kernel'],
     'mpconv_fwd_ws.hip': ['mpconv_fwd_ws_kernelILi64E'],          # (the 128-input instances spill at their 128-register budget: consumers only, profiles/r06/README.md)
 }
-
-
-def _scratch(src):
-    cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17',      # (the Makefile's flags)
-           '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC, '-Wno-unused-function',
-           '-Wno-pass-failed', '-fPIC'] + (['-fno-slp-vectorize'] if src == 'block_tail.hip' else []) + ['-c', '--cuda-device-only', os.path.join(CSRC, src), '-o', os.devnull,
-           '-Rpass-analysis=kernel-resource-usage']
-    err = subprocess.run(cmd, capture_output=True, text=True, timeout=1500).stderr
-    out, name = {}, None
-    for line in err.splitlines():
-        m = re.search(r'Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-        m = re.search(r'ScratchSize \[bytes/lane\]: (\d+)', line)
-        if m and name:
-            out[name] = int(m.group(1))
-    return out
+FLAGS = {'block_tail.hip': ('-fno-slp-vectorize',)}          # what the Makefile adds per source
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_benched_kernels_have_no_scratch():
     with ThreadPoolExecutor(max_workers=len(MUST)) as ex:
-        reports = dict(zip(MUST, ex.map(_scratch, MUST)))
+        reports = dict(zip(MUST, ex.map(lambda src: scratch(src, FLAGS.get(src, ())), MUST)))
     bad = []
     for src, subs in MUST.items():
         rep = reports[src]

@@ -164,8 +164,8 @@ def test_solve_bp_needs_a_device():
 
 @pytest.mark.skipif(not os.path.exists(os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')), reason='no hipcc')
 def test_bp_kernel_has_no_scratch():
-    from test_no_scratch import _scratch
-    rep = _scratch('pgm_bp.hip')
+    from scratch_report import scratch
+    rep = scratch('pgm_bp.hip')
     hits = {k: v for k, v in rep.items() if 'chain_budget_bp_kernel' in k}
     assert len(hits) == 1, rep
     assert not any(hits.values()), hits

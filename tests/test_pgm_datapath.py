@@ -4,19 +4,13 @@
   * argument validation happens before any launch, so it is testable without a device;
   * the new kernels keep everything in registers and LDS (compiler resource report, cross-compiled for gfx950)."""
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import pgm_map_oracle as PO
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'factor-graph-neural-network_amd', 'csrc')
-HIPCC = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+from scratch_report import HIPCC, scratch
 
 
 def _dyadic(rng, shape, lo, hi):
@@ -111,25 +105,9 @@ def test_philox_word_packing():
     assert len(np.unique(a)) > 0.99 * a.size
 
 
-def _scratch(src):
-    cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC,
-           '-Wno-unused-function', '-Wno-pass-failed', '-fPIC', '-c', '--cuda-device-only', os.path.join(CSRC, src), '-o',
-           os.devnull, '-Rpass-analysis=kernel-resource-usage']
-    err = subprocess.run(cmd, capture_output=True, text=True, timeout=1500).stderr
-    out, name = {}, None
-    for line in err.splitlines():
-        m = re.search(r'Function Name: (\S+)', line)
-        if m:
-            name = m.group(1)
-        m = re.search(r'ScratchSize \[bytes/lane\]: (\d+)', line)
-        if m and name:
-            out[name] = int(m.group(1))
-    return out
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='no hipcc')
 def test_pgm_kernels_have_no_scratch():
-    rep = _scratch('pgm_datapath.hip')
+    rep = scratch('pgm_datapath.hip')
     hits = {k: v for k, v in rep.items() if 'chain_budget_map_kernel' in k}
     assert len(hits) == 2, rep                                          # the solver and the sampler instance
     assert not any(hits.values()), hits

@@ -162,8 +162,8 @@ def test_solve_lp_validates_on_the_host():
 
 @pytest.mark.skipif(not os.path.exists(os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')), reason='no hipcc')
 def test_lp_kernel_has_no_scratch():
-    from test_no_scratch import _scratch
-    rep = _scratch('pgm_lp.hip')
+    from scratch_report import scratch
+    rep = scratch('pgm_lp.hip')
     hits = {k: v for k, v in rep.items() if 'chain_budget_lp_kernel' in k}
     assert len(hits) == 1, rep
     assert not any(hits.values()), hits

@@ -12,7 +12,7 @@ beside min-sum:flooding at the same iteration count (--learned_iters), with untr
 decisions) shared per iteration, per check and per edge: the weight reads are its only extra work in the loop.
 
 Ordered-statistics reprocessing (LdpcDataPath.decode_osd, csrc/ldpc_osd.hip) follows as min-sum:layered:osd=0|1|2 (order 2: the
-default span, 64), each row the whole composition ``ldpc_eval.run_decoder`` runs — the decoder with posteriors, then the reprocessing
+default span, 64), each row the whole composition ``ldpc_decoders.Decoder.run`` runs — the decoder with posteriors, then the reprocessing
 of the words it leaves with violated checks — to be read beside the plain min-sum:layered row; ``decoded`` is 1 there by construction.
 A third code, gallager(384, 3, 6, 1), sits between the two (128 threads per word).
 
@@ -27,9 +27,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'factor-graph-neural-network_amd'))
 import torch
 from fgnn_amd import _hip
-from fgnn_amd.datapath import LLR_ALGORITHMS, LLR_SCHEDULES, LdpcDataPath
+from fgnn_amd.datapath import LdpcDataPath
 from fgnn_amd.ldpc_code import LdpcCode
-from fgnn_amd.ldpc_eval import parse_decoder, run_decoder
+from fgnn_amd.ldpc_decoders import LLR_ALGORITHMS, LLR_SCHEDULES, parse_decoder
 from fgnn_amd.ldpc_nms import SHARES, LearnedMinSum
 
 
@@ -89,7 +89,7 @@ def main():
                 runs.append(('%s:%s' % (alg, sched), lambda alg=alg, sched=sched: path.decode_llr(llr, alg, sched, max_iter=50)))
         for order in (0, 1, 2):
             decoder = parse_decoder('min-sum:layered:osd=%d' % order)
-            runs.append((decoder[0], lambda decoder=decoder: run_decoder(path, decoder, y, snr)))
+            runs.append((decoder.spec, lambda decoder=decoder: decoder.run(path, y, snr)))
         n = args.learned_iters
         runs.append(('min-sum:flooding:iters=%d' % n, lambda: path.decode_llr(llr, 'min-sum', 'flooding', max_iter=n)))
         for share in SHARES:
