@@ -51,6 +51,8 @@ struct B16Params {
     int c8shift;                          // log2(nin/8)
     int et_mode;
     unsigned mkmagic;
+    int et_pad;                           // edge-type fastest: elements behind each destination's k * net (0: dense rows)
+    unsigned rowmagic;                    // ceil(2^32 / (k net)) when et_pad != 0
     int dbg;                              // FGNN_DBG ablation mask (tuning only)
     long long* prof;                      // FGNN_PROF: phase timeline of one sample of workgroup 0 (tuning only)
     int JP;                               // neighbour-list split over waves (1 = off)
@@ -140,19 +142,24 @@ __global__ __launch_bounds__(B16_THREADS) void mpconv_fwd_b16_kernel(const B16Pa
     uint4 xr[B16_XPT];
     unsigned short er[B16_EPT];
     long long ir[B16_IPT];                            // raw: clamped at the commit, so the load is not waited for here
-    const int xchunks = (nin * N) >> 3;               // 16-byte chunks of the dense sample block
+    const int xchunks = (nin * N) >> 3;               // 16-byte chunks of the sample's rows
+    const int xrow = N == 1 ? nin : (int)d.x_sn;      // elements between node rows (>= nin: a channel slice of wider rows)
     auto prefetch = [&](int b, int t) {
-        const uint4* xb = reinterpret_cast<const uint4*>(xg + (int64_t)b * d.x_sb);
+        // uint4 loads at per-lane addresses (vector global_load_dwordx4): any address, any row and sample stride -- see b16_shape
+        const unsigned short* xb = xg + (int64_t)b * d.x_sb;
 #pragma unroll
         for (int q = 0; q < B16_XPT; ++q) {
             const int f = t + q * B16_THREADS;
-            xr[q] = f < xchunks ? xb[f] : make_uint4(0, 0, 0, 0);
+            const int n = f >> p.c8shift, c8 = f - (n << p.c8shift);
+            xr[q] = f < xchunks ? *reinterpret_cast<const uint4*>(xb + n * xrow + c8 * 8) : make_uint4(0, 0, 0, 0);
         }
         const unsigned short* eb = etg + (int64_t)b * d.et_sb;
 #pragma unroll
         for (int q = 0; q < B16_EPT; ++q) {
-            const int f = t + q * B16_THREADS;
-            er[q] = f < mk * net ? eb[f] : (unsigned short)0;
+            const unsigned f = t + q * B16_THREADS;
+            // (edge-type fastest with padded destination rows: et_pad elements behind each row of k * net)
+            const unsigned at = p.et_pad ? f + __umulhi(f, p.rowmagic) * (unsigned)p.et_pad : f;
+            er[q] = (int)f < mk * net ? eb[at] : (unsigned short)0;
         }
 #pragma unroll
         for (int q = 0; q < B16_IPT; ++q) {
@@ -484,8 +491,12 @@ static int b16_shape(const fgnn_mpconv_desc* d, bool stats, B16Params* p) {
     const int ncols = d->nou * d->net;
     if (ncols % 16 != 0 || ncols > 512) return 0;
     if (d->nin != 64 && d->nin != 128) return 0;
-    // x: dense channel-fastest sample block, 16-byte aligned; y: channel-fastest
-    if (!(d->x_sc == 1 && (d->x_sn == d->nin || d->N == 1)) || (d->x_sb % 8) != 0) return 0;
+    // x: channel-fastest rows of nin channels, any row and sample stride, any address.  The kernel reads x through uint4 at
+    // PER-LANE addresses: vector global_load_dwordx4, which the hardware serves off a 16-byte boundary in the unaligned-access mode
+    // ROCm runs in.  C++ does not promise this; it rests on the x+1el / x+8B cases of tests/test_mpconv_views_gpu.py (bit equal to
+    // the aligned call on an MI355X).  A wave-UNIFORM address must never reach these loads: a scalar load drops the low address
+    // bits.  y: channel-fastest
+    if (!(d->x_sc == 1 && (d->N == 1 || (d->x_sn >= d->nin && d->x_sn <= (1 << 20))))) return 0;
     if (!(d->y_sc == 1 && (d->M == 1 || d->y_sm == d->nou))) return 0;
     const int Npad = fgnn_round_up(d->N, 16);
     const int mk = d->M * d->k;
@@ -499,8 +510,12 @@ static int b16_shape(const fgnn_mpconv_desc* d, bool stats, B16Params* p) {
         p->et_mode = 1;
     } else if ((d->et_sk == 1 || d->k == 1) && (d->et_sm == d->k || d->M == 1) && d->et_se == mk) {
         p->et_mode = 0;
-    } else if (d->et_se == 1 && d->et_sk == d->net && (d->et_sm == d->k * d->net || d->M == 1)) {
-        p->et_mode = 1;
+    } else if (d->et_se == 1 && d->et_sk == d->net && (d->M == 1 || (d->et_sm >= d->k * d->net && d->et_sm <= (1 << 20)))) {
+        p->et_mode = 1;                                  // edge-type fastest; a destination's row may be padded
+        if (d->M > 1 && d->et_sm != d->k * d->net) {
+            p->et_pad = (int)d->et_sm - d->k * d->net;
+            p->rowmagic = (unsigned)((0x100000000ULL + d->k * d->net - 1) / (d->k * d->net));
+        }
     } else {
         return 0;
     }

@@ -77,6 +77,7 @@ __global__ __launch_bounds__(512) void mpconv_fwd_fanin_kernel(const FhParams p)
     }
     const int ntile = p.Npad16 / 16;
     const int nwaves = gridDim.x * p.waves;
+    const int xrow = N == 1 ? NIN : (int)d.x_sn;      // elements between node rows (>= NIN: a channel slice of wider rows)
     for (int b = blockIdx.x * p.waves + wave; b < d.B; b += nwaves) {
         const uint16_t* xb = p.x + (int64_t)b * d.x_sb;
         // ---- P[n][o] for all nodes: B[k = c][j = n] straight from global (16 bytes per lane).  The launch gives every wave ONE
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(512) void mpconv_fwd_fanin_kernel(const FhParams p)
                 const int n = (nt0 + t) * 16 + li;
 #pragma unroll
                 for (int ks = 0; ks < KS2; ++ks)
-                    bx[t][ks] = n < N ? *reinterpret_cast<const uint4*>(xb + (int64_t)n * NIN + 32 * ks + 8 * lk) : make_uint4(0, 0, 0, 0);
+                    bx[t][ks] = n < N ? *reinterpret_cast<const uint4*>(xb + n * xrow + 32 * ks + 8 * lk) : make_uint4(0, 0, 0, 0);
             }
 #pragma unroll
             for (int t = 0; t < TB; ++t) {
@@ -204,6 +205,7 @@ __global__ __launch_bounds__(256) void mpconv_fwd_fanin_id_kernel(const FhParams
     uint8_t* carg = reinterpret_cast<uint8_t*>(reinterpret_cast<float*>(fgnn_lds_fh) + 4 * 16 * CROW) + (size_t)wave * 16 * NOU;   // [16][NOU] u8
     const int ntile = p.Npad16 / 16;
     const int nwaves = gridDim.x * 4;
+    const int xrow = N == 1 ? NIN : (int)d.x_sn;      // elements between node rows (>= NIN: a channel slice of wider rows)
     int b = blockIdx.x * 4 + wave;
     // the first sample's rows go out before the W fragments are fetched (64 strided 4-byte loads per lane: the kernel's fixed cost)
     bf16x8 aP[OT][KS2];
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(256) void mpconv_fwd_fanin_id_kernel(const FhParams
                 const bool ok = n < N;
 #pragma unroll
                 for (int ks = 0; ks < KS2; ++ks)
-                    bx[t][ks] = ok ? *reinterpret_cast<const uint4*>(xb + (int64_t)n * NIN + 32 * ks + 8 * lk) : make_uint4(0, 0, 0, 0);
+                    bx[t][ks] = ok ? *reinterpret_cast<const uint4*>(xb + n * xrow + 32 * ks + 8 * lk) : make_uint4(0, 0, 0, 0);
                 ew[t] = ok ? __uint_as_float((unsigned)eb[(int64_t)n * d.et_sk] << 16) : 0.f;
             }
 #pragma unroll
@@ -397,7 +399,12 @@ int fgnn_fwd_hyper_plan(const FgnnFwdCall& c, const FgnnSwitches& sw, FgnnPlan* 
     if (!fanin && !fanout) FGNN_REJECT("hyper-edge forward", 3);
     int waves = 8;
     if (fanin) {
-        if (!(d->x_sc == 1 && d->x_sn == d->nin && d->x_sb % 8 == 0) || ((uintptr_t)c.x & 15)) FGNN_REJECT("hyper-edge forward", 4);
+        // x: channel-fastest rows of nin channels, any row and sample stride, any address.  The kernels read x through uint4 at
+        // PER-LANE addresses: vector global_load_dwordx4, which the hardware serves off a 16-byte boundary in the unaligned-access
+        // mode ROCm runs in.  C++ does not promise this; it rests on the x+1el / x+8B cases of tests/test_mpconv_views_gpu.py (bit
+        // equal to the aligned call on an MI355X).  A wave-UNIFORM address must never reach these loads: a scalar load drops the low
+        // address bits.  (The table-driven family's LDS-DMA does need 16 bytes.)
+        if (!(d->x_sc == 1 && (d->N == 1 || (d->x_sn >= d->nin && d->x_sn <= (1 << 20))))) FGNN_REJECT("hyper-edge forward", 4);
         const int KS2 = d->nin / 32, OT = d->nou / 16;
         // the caller vouches for an identity neighbour list (FGNN_DESC_IDENTITY_LIST): the reduction stays in the MFMA accumulators
         if (!sw.no_fanin_id && (d->reserved & FGNN_DESC_IDENTITY_LIST) && d->agg == FGNN_AGG_MAX && d->k == d->N && d->N <= 128 && d->N >= 2) {

@@ -280,7 +280,9 @@ def mpconv_forward_raw(x, nn_idx, etype, filters, bias, nou, net, ext, agg, *,
         d.reserved |= _hip.DESC_IDENTITY_LIST          # (the hyper-factor's table: the fan-in kernel reduces in its accumulators)
     nbytes = int(L.fgnn_mpconv_algorithmic_bytes(ctypes.byref(d))) if TIMER is not None else 0
     npart = 0
-    if bn is not None and STATS_EPILOGUE and post_scale is None and not relu:
+    # (fgnn_mpconv_forward_stats_partials plans without pointers: the table-driven kernel it may announce wants 16-byte aligned x and
+    # etype and fails a statistics call that is not.  Such a view takes the plain forward; the BatchNorm makes its own pass.)
+    if bn is not None and STATS_EPILOGUE and post_scale is None and not relu and not ((x.data_ptr() | etype.data_ptr()) & 15):
         npart = int(L.fgnn_mpconv_forward_stats_partials(ctypes.byref(d)))
     if npart > 0:
         R = x.shape[0] * M
@@ -463,7 +465,10 @@ class _MPConv(torch.autograd.Function):
         d = _hip.make_desc(xx, nn_idx, etype, nou, net, ext, agg, False, gz)
         d.reserved = max_in_degree(nn_idx, x.shape[2])
         # shared edge weights: where the kernel sums their gradient over the batch itself, ask for that form
-        reduced = bool(want_get and ctx.shared_et and L.fgnn_mpconv_backward_reduces_getype(ctypes.byref(d)))
+        # (a pointer-free query: the kernel behind it wants 16-byte aligned x and gz and fails the reduced form on a view that is not)
+        # (as fgnn_bwd_ext_plan asks it: gz only where the channel count lets the kernel read it in 16-byte words)
+        reduced = bool(want_get and ctx.shared_et and not ((xx.data_ptr() | (gz.data_ptr() if nou % 4 == 0 else 0)) & 15)
+                       and L.fgnn_mpconv_backward_reduces_getype(ctypes.byref(d)))
         if reduced:
             d.reserved |= _hip.DESC_GETYPE_REDUCED
             get = torch.empty((1, net, M, k), device=x.device, dtype=torch.float32)
