@@ -13,11 +13,7 @@
 // check count are its functions, the carve, staging and load rule are written out in the kernel.  The weights are read from global
 // memory where they are used (one value per check update with share 0 / 1, one per edge with share 2).
 //
-// Record (train mode), per word b and iteration t three planes of M 32-bit values, plane k of check m at
-// ((b * n_iter + t - 1) * 3 + k) * M + m (a lane owns a check: the planes are read and written coalesced):
-//   plane 0  m1 (f32 bits)     plane 1  m2 (f32 bits)
-//   plane 2  bits 0..15 the signs of q_0 .. q_{L-1} (1 = q < 0), bits 16..20 i1, bits 21..25 i2 (31 = none)
-// 12 B M n_iter per word.  mag, the other-sign parity and u > 0 follow from these and the weights.
+// Record (train mode): ldpc_nms.h states it; a lane owns a check, so the planes are read and written coalesced.
 //
 // Backward layout: workgroup g of G = min(B, 512) takes the words g, g + G, ...; the same thread counts.  In LDS, ldpc_word.h's
 // state with, in the places of R, T and prior, f32 gQ [E] (the g_q of the iteration above, by edge: variable n's edges are
@@ -27,43 +23,11 @@
 // workspace.  Every partial element has one owner thread (share 1: the check's lane; share 2: the edge's check's lane; share 0:
 // thread 0, after a fixed-order wave and workgroup reduction), which adds to it word after word in the order of its words: no
 // atomics, the same bits every time.  The second launch adds the G slices in a fixed order (ldpc_nms_sum_kernel).
-#include "fgnn_hip_ldpc_nms.h"
-#include "ldpc_word.h"
-
-#define NMS_MAXIT 64
-#define NMS_BWD_GROUPS 512
-#define NMS_PARTIAL_LDS (64 * 1024)     // the backward keeps its partial in LDS while state + partial stay within this
-#define NMS_NONE 31u
-
-struct NmsFwdParams {
-    const float* llr; int64_t llr_sb;
-    const int32_t *col_ptr, *row_ptr, *row_edge, *row_var;
-    const float *alpha, *beta;
-    uint8_t* x;
-    float *post, *totals;
-    int32_t *viol, *iters;
-    uint32_t* record;
-    int64_t B;
-    int N, M, E, n_iter, share;
-};
-
-struct NmsBwdParams {
-    const float *g_totals, *llr; int64_t llr_sb;
-    const int32_t *col_ptr, *row_ptr, *row_edge, *row_var;
-    const float *alpha, *beta;
-    const uint32_t* record;
-    float *g_llr, *ws;
-    int64_t B;
-    int N, M, E, n_iter, share, W;
-};
+#include "ldpc_nms.h"     // the limits, the parameters, nms_weight, the record, the argument checks: shared with ldpc_nms_layered.hip
 
 // the state's bytes: 4 scratch ints forward, 8 floats backward
 __host__ __device__ static inline int64_t nms_state_bytes(int N, int M, int E, int backward) {
     return ldpc_word_bytes_nms(N, M, E, backward ? 32 : 16);
-}
-
-__device__ __forceinline__ float nms_weight(const float* w, int it, int W, int share, int m, int e) {
-    return w[(int64_t)(it - 1) * W + (share == 0 ? 0 : share == 1 ? m : e)];
 }
 
 template <bool TRAIN>
@@ -104,10 +68,10 @@ __global__ __launch_bounds__(256) void ldpc_nms_fwd_kernel(const NmsFwdParams p)
             const int r0 = rp[m], r1 = rp[m + 1], L = r1 - r0;
             const LdpcMinScan c = ldpc_min_scan(s, r0, r1);
             if (TRAIN) {
-                uint32_t* rec = p.record + ((b * p.n_iter + (it - 1)) * 3) * M + m;
+                uint32_t* rec = p.record + NMS_RECORD_AT(b, p.n_iter, it, M, m);
                 rec[0] = __float_as_uint(c.m1);
                 rec[M] = __float_as_uint(c.m2);
-                rec[2 * (int64_t)M] = c.signs | (c.i1 < 0 ? NMS_NONE : (uint32_t)(c.i1 - r0)) << 16 | (c.i2 < 0 ? NMS_NONE : (uint32_t)(c.i2 - r0)) << 21;
+                rec[2 * (int64_t)M] = nms_record_pack(c, r0);
             }
             float al = 0.0f, be = 0.0f;
             if (share != 2) { al = nms_weight(p.alpha, it, W, share, m, 0); be = nms_weight(p.beta, it, W, share, m, 0); }
@@ -176,7 +140,7 @@ __global__ __launch_bounds__(256) void ldpc_nms_bwd_kernel(const NmsBwdParams p)
             float sa = 0.0f, sb = 0.0f;                                         // share 0: this thread's part of the iteration's sums
             for (int m = tid; m < M; m += nt) {
                 const int r0 = rp[m], L = rp[m + 1] - r0;
-                const uint32_t* rec = p.record + ((b * n_iter + (t - 1)) * 3) * M + m;
+                const uint32_t* rec = p.record + NMS_RECORD_AT(b, n_iter, t, M, m);
                 const float m1 = __uint_as_float(rec[0]), m2 = __uint_as_float(rec[M]);
                 const uint32_t pk = rec[2 * (int64_t)M];
                 const uint32_t signs = pk & 0xffffu;
@@ -266,14 +230,6 @@ __global__ __launch_bounds__(256) void ldpc_nms_sum_kernel(const float* ws, int 
     if (i < cnt) g_alpha[i] = s; else g_beta[i - cnt] = s;
 }
 
-static int nms_check_sizes(const char* who, int64_t B, int N, int M, int E, int n_iter, int share) {
-    if (ldpc_word_check_sizes(who, N, M, E) != FGNN_OK) return FGNN_EUNSUPPORTED;
-    if (B < 0 || B > 0x7fffffffll) FGNN_FAIL(FGNN_EINVAL, "%s: batch %lld outside 0 .. 2^31-1", who, (long long)B);
-    if (n_iter < 1 || n_iter > NMS_MAXIT) FGNN_FAIL(FGNN_EINVAL, "%s: n_iter=%d outside 1..%d", who, n_iter, NMS_MAXIT);
-    if (share < 0 || share > 2) FGNN_FAIL(FGNN_EINVAL, "%s: share=%d outside 0..2", who, share);
-    return FGNN_OK;
-}
-
 extern "C" int64_t fgnn_ldpc_nms_lds_bytes(int N, int M, int E, int backward) {
     if (nms_check_sizes("ldpc_nms_lds_bytes", 0, N, M, E, 1, 0) != FGNN_OK) return -1;
     return nms_state_bytes(N, M, E, backward != 0);
@@ -281,45 +237,34 @@ extern "C" int64_t fgnn_ldpc_nms_lds_bytes(int N, int M, int E, int backward) {
 
 extern "C" int64_t fgnn_ldpc_nms_record_bytes(int64_t B, int N, int M, int E, int n_iter) {
     if (nms_check_sizes("ldpc_nms_record_bytes", B, N, M, E, n_iter, 0) != FGNN_OK) return -1;
-    return B * n_iter * 3 * (int64_t)M * 4;
+    return nms_record_bytes(B, M, n_iter);
 }
 
-extern "C" int64_t fgnn_ldpc_nms_backward_workgroups(int64_t B) { return B < 0 ? 0 : B < NMS_BWD_GROUPS ? B : NMS_BWD_GROUPS; }
+extern "C" int64_t fgnn_ldpc_nms_backward_workgroups(int64_t B) { return nms_groups(B); }
 
 extern "C" int64_t fgnn_ldpc_nms_backward_workspace_bytes(int64_t B, int N, int M, int E, int n_iter, int share) {
     if (nms_check_sizes("ldpc_nms_backward_workspace_bytes", B, N, M, E, n_iter, share) != FGNN_OK) return -1;
     const int64_t W = share == 0 ? 1 : share == 1 ? M : E;
-    return fgnn_ldpc_nms_backward_workgroups(B) * 2 * n_iter * W * 4;
+    return nms_groups(B) * 2 * n_iter * W * 4;
 }
 
 extern "C" int fgnn_ldpc_nms_forward(const float* llr, int64_t llr_sb, const int32_t* col_ptr, const int32_t* row_ptr,
                                      const int32_t* row_edge, const int32_t* row_var, const float* alpha, const float* beta, int64_t B,
                                      int N, int M, int E, int n_iter, int share, int stop_early, uint8_t* x, float* post, int32_t* viol,
                                      int32_t* iters, float* totals, void* record, int64_t record_bytes, fgnn_stream_t stream) {
-    const int rc = nms_check_sizes("ldpc_nms_forward", B, N, M, E, n_iter, share);
-    if (rc != FGNN_OK) return rc;
-    if (stop_early < 0 || stop_early > 1) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: stop_early=%d outside 0..1", stop_early);
-    if (llr_sb < 0) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: negative row stride");
-    if (stop_early && (totals || record)) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: totals and record belong to the train mode (stop_early = 0)");
-    if (B == 0) return FGNN_OK;
-    if (!llr || !col_ptr || !row_ptr || !row_edge || !row_var || !alpha || !beta) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: null input pointer");
-    if (stop_early && (!x || !viol || !iters)) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: null output pointer");
-    if (!stop_early) {
-        if (!totals || !record) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: null totals or record in train mode");
-        const int64_t need = fgnn_ldpc_nms_record_bytes(B, N, M, E, n_iter);
-        if (record_bytes < need)
-            FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_forward: a record of %lld bytes, %lld needed", (long long)record_bytes, (long long)need);
-    }
     NmsFwdParams p = {};
-    p.llr = llr; p.llr_sb = llr_sb;
-    p.col_ptr = col_ptr; p.row_ptr = row_ptr; p.row_edge = row_edge; p.row_var = row_var;
-    p.alpha = alpha; p.beta = beta;
-    p.x = x; p.post = post; p.totals = totals; p.viol = viol; p.iters = iters; p.record = (uint32_t*)record;
-    p.B = B; p.N = N; p.M = M; p.E = E; p.n_iter = n_iter; p.share = share;
+    if (int rc = nms_forward_args("ldpc_nms_forward", llr, llr_sb, col_ptr, row_ptr, row_edge, row_var, alpha, beta, B, N, M, E, n_iter,
+                                  share, stop_early, x, post, viol, iters, totals, record, record_bytes, &p))
+        return rc;
+    if (B == 0) return FGNN_OK;
     void (*kernel)(const NmsFwdParams) = stop_early ? ldpc_nms_fwd_kernel<false> : ldpc_nms_fwd_kernel<true>;
     const int threads = ldpc_word_threads(N, M), lds = (int)nms_state_bytes(N, M, E, 0);
     fgnn_note_kernel("ldpc_nms_fwd_kernel<%d>x%d", !stop_early, threads);
     return fgnn_launch("ldpc_nms_forward", kernel, dim3((unsigned)B), dim3(threads), lds, fgnn_stream(stream), p);
+}
+
+int nms_launch_sum(const char* what, const float* ws, int G, int cnt, float* g_alpha, float* g_beta, hipStream_t st) {
+    return fgnn_launch(what, ldpc_nms_sum_kernel, dim3((unsigned)((2 * cnt + 31) / 32)), dim3(256), 0, st, ws, G, cnt, g_alpha, g_beta);
 }
 
 extern "C" int fgnn_ldpc_nms_backward(const float* g_totals, const float* llr, int64_t llr_sb, const int32_t* col_ptr,
@@ -327,42 +272,18 @@ extern "C" int fgnn_ldpc_nms_backward(const float* g_totals, const float* llr, i
                                       const float* beta, const void* record, int64_t record_bytes, int64_t B, int N, int M, int E,
                                       int n_iter, int share, float* g_alpha, float* g_beta, float* g_llr, void* workspace,
                                       int64_t workspace_bytes, fgnn_stream_t stream) {
-    const int rc = nms_check_sizes("ldpc_nms_backward", B, N, M, E, n_iter, share);
-    if (rc != FGNN_OK) return rc;
-    if (llr_sb < 0) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: negative row stride");
-    const int W = share == 0 ? 1 : share == 1 ? M : E;
-    const int cnt = n_iter * W;
-    if (B == 0) {
-        if (g_alpha && g_beta) {
-            hipError_t e = hipMemsetAsync(g_alpha, 0, 4 * (size_t)cnt, fgnn_stream(stream));
-            if (e == hipSuccess) e = hipMemsetAsync(g_beta, 0, 4 * (size_t)cnt, fgnn_stream(stream));
-            if (e != hipSuccess) FGNN_FAIL(FGNN_ELAUNCH, "ldpc_nms_backward: hipMemsetAsync: %s", hipGetErrorString(e));
-        }
-        return FGNN_OK;
-    }
-    if (!g_totals || !col_ptr || !row_ptr || !row_edge || !row_var || !alpha || !beta || !record)
-        FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: null input pointer");
-    if (!g_alpha || !g_beta || !workspace) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: null output or workspace pointer");
-    if (g_llr && !llr) FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: g_llr needs llr (the load's clamp)");
-    const int64_t need_rec = fgnn_ldpc_nms_record_bytes(B, N, M, E, n_iter);
-    if (record_bytes < need_rec)
-        FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: a record of %lld bytes, %lld needed", (long long)record_bytes, (long long)need_rec);
-    const int64_t need_ws = fgnn_ldpc_nms_backward_workspace_bytes(B, N, M, E, n_iter, share);
-    if (workspace_bytes < need_ws)
-        FGNN_FAIL(FGNN_EINVAL, "ldpc_nms_backward: a workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need_ws);
     NmsBwdParams p = {};
-    p.g_totals = g_totals; p.llr = llr; p.llr_sb = llr_sb;
-    p.col_ptr = col_ptr; p.row_ptr = row_ptr; p.row_edge = row_edge; p.row_var = row_var;
-    p.alpha = alpha; p.beta = beta; p.record = (const uint32_t*)record;
-    p.g_llr = g_llr; p.ws = (float*)workspace;
-    p.B = B; p.N = N; p.M = M; p.E = E; p.n_iter = n_iter; p.share = share; p.W = W;
-    const int G = (int)fgnn_ldpc_nms_backward_workgroups(B);
+    if (int rc = nms_backward_args("ldpc_nms_backward", g_totals, llr, llr_sb, col_ptr, row_ptr, row_edge, row_var, alpha, beta, record,
+                                   record_bytes, B, N, M, E, n_iter, share, g_alpha, g_beta, g_llr, workspace, workspace_bytes, &p))
+        return rc;
+    const int cnt = n_iter * p.W;
+    if (B == 0) return nms_backward_empty("ldpc_nms_backward", g_alpha, g_beta, cnt, fgnn_stream(stream));
+    const int G = (int)nms_groups(B);
     const int64_t state = nms_state_bytes(N, M, E, 1);
     const bool part_lds = state + 8 * (int64_t)cnt <= NMS_PARTIAL_LDS;
     void (*kernel)(const NmsBwdParams) = part_lds ? ldpc_nms_bwd_kernel<true> : ldpc_nms_bwd_kernel<false>;
     const int threads = ldpc_word_threads(N, M), lds = (int)(state + (part_lds ? 8 * (int64_t)cnt : 0));
     fgnn_note_kernel("ldpc_nms_bwd_kernel<%d>x%d", part_lds, threads);
     if (int rc = fgnn_launch("ldpc_nms_backward", kernel, dim3((unsigned)G), dim3(threads), lds, fgnn_stream(stream), p)) return rc;
-    return fgnn_launch("ldpc_nms_backward sum", ldpc_nms_sum_kernel, dim3((unsigned)((2 * cnt + 31) / 32)), dim3(256), 0, fgnn_stream(stream),
-                       (const float*)workspace, G, cnt, g_alpha, g_beta);
+    return nms_launch_sum("ldpc_nms_backward sum", (const float*)workspace, G, cnt, g_alpha, g_beta, fgnn_stream(stream));
 }

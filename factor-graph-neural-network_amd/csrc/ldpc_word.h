@@ -1,4 +1,4 @@
-// ldpc_word.h — what the LLR-domain kernels (ldpc_llr.hip) and the learned min-sum kernels (ldpc_nms.hip) share: the limits, the
+// ldpc_word.h — what the LLR-domain kernels (ldpc_llr.hip) and the learned min-sum kernels (ldpc_nms.hip, ldpc_nms_layered.hip) share: the limits, the
 // per-word LDS layout and the steps every flooding iteration is made of.  Both files are built with -ffp-contract=off and each
 // function below keeps its statements in the order the restatements (tests/ldpc_llr_oracle.py, tests/ldpc_nms_oracle.py) pin.
 //

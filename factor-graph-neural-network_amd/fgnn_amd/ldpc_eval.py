@@ -254,7 +254,8 @@ def main(argv=None):
     ap.add_argument('--decoder', action='append', default=[], metavar='SPEC',
                     help='also print the table of a classical decoder; may be repeated.  mackay, or min-sum | offset-min-sum | '
                          'sum-product [:flooding | :layered] [:iters=N] [:alpha=A] [:beta=B] [:osd=W [:span=L]] (osd: ordered-'
-                         'statistics reprocessing of order W), or learned-min-sum:CHECKPOINT (python -m fgnn_amd.ldpc_nms_train)')
+                         'statistics reprocessing of order W), or learned-min-sum:CHECKPOINT (python -m fgnn_amd.ldpc_nms_train; runs the '
+                         'schedule the checkpoint was trained with, flooding or layered)')
     ap.add_argument('--curve', action='store_true', help='print a BER / WER curve of the one --decoder over --snr (no model)')
     ap.add_argument('--snr', default='0,1,2,3,4', help='--curve: SNR values in dB, comma-separated')
     ap.add_argument('--sigma_b', type=int, default=0, help='--curve: the burst level')

@@ -1,13 +1,16 @@
-"""Learned ("neural") min-sum LDPC decoding: a flooding min-sum whose normalisation weights ``alpha`` and offsets ``beta`` are trained
-(Nachmani et al.'s neural min-sum, Lugosch & Gross's neural offset min-sum) — the learned decoder FGNN's papers compare against.
+"""Learned ("neural") min-sum LDPC decoding: a flooding or layered min-sum whose normalisation weights ``alpha`` and offsets ``beta``
+are trained (Nachmani et al.'s neural min-sum, Lugosch & Gross's neural offset min-sum) — the learned decoder FGNN's papers compare
+against.
 
 The reference has no counterpart.  The decoder is defined in include/fgnn_hip_ldpc_nms.h: ``n_iter`` flooding iterations, in iteration
 t every check sends ``s * max(alpha_t[w] * mag - beta_t[w], 0)`` with ``mag`` the smallest |q| among the other edges, and the weights
 are shared per iteration, per (iteration, check) or per (iteration, edge).  Forward and backward are the two kernels of
-csrc/ldpc_nms.hip; there is no torch fallback.  It takes every code ``LdpcCode.require_llr_decoder`` takes (csrc/ldpc_word.h's
+csrc/ldpc_nms.hip; there is no torch fallback.  ``schedule='layered'`` runs the same check update layer by layer
+(``LdpcCode.layers()``), each check on the totals the earlier layers of the iteration left: include/fgnn_hip_ldpc_nms_layered.h,
+the two kernels of csrc/ldpc_nms_layered.hip.  It takes every code ``LdpcCode.require_llr_decoder`` takes (csrc/ldpc_word.h's
 limits: N, M <= 1024, degrees <= 16).
 
-    dec = LearnedMinSum(code, n_iter=5, share='edge').cuda()
+    dec = LearnedMinSum(code, n_iter=5, share='edge').cuda()          # schedule='layered': the layered decoder
     totals = dec(llr)                         # [n_iter, B, N]: every iteration's totals, differentiable in alpha, beta and llr
     multi_loss(totals, cw).backward()
     x, viol, iters = dec.decode(llr)          # early stopping, no gradient
@@ -22,7 +25,8 @@ from .ldpc_code import LdpcCode
 from .ldpc_decoders import LEARNED as KIND, check_word_batch, decode_outputs, llr_batch   # KIND: a checkpoint's decoder['kind']
 
 SHARES = {'iteration': 0, 'check': 1, 'edge': 2}       # fgnn_ldpc_nms_forward's ``share``
-MAX_ITER = 64                                          # csrc/ldpc_nms.hip's NMS_MAXIT
+MAX_ITER = 64                                          # csrc/ldpc_nms.h's NMS_MAXIT
+SCHEDULES = ('flooding', 'layered')
 
 
 def check_nms_args(llr, n_var, n_chk, n_edges, n_iter, share, alpha, beta):
@@ -58,21 +62,31 @@ def _query(name, *args):
     return r
 
 
-def nms_forward_raw(llr, tables, sizes, alpha, beta, n_iter, share):
-    """The train-mode launch: (totals [n_iter, B, N] f32, record uint8 [record bytes]).  llr [B, N] f32 on the device, unit column stride."""
+def _entry_point(which, tables, layers):
+    """(the name of the forward / backward entry point, its table arguments): ``layers`` = None for the flooding schedule, else the
+    device tensors (layer_ptr, layer_chk)."""
+    if layers is None:
+        return 'fgnn_ldpc_nms_' + which, tuple(tables)
+    return 'fgnn_ldpc_nms_layered_' + which, tuple(tables) + (layers[0], layers[1], layers[0].numel() - 1)
+
+
+def nms_forward_raw(llr, tables, sizes, alpha, beta, n_iter, share, layers=None):
+    """The train-mode launch: (totals [n_iter, B, N] f32, record uint8 [record bytes]).  llr [B, N] f32 on the device, unit column
+    stride.  ``layers``: None, or (layer_ptr, layer_chk) for the layered schedule."""
     N, M, E = sizes
     B = llr.shape[0]
     totals = torch.empty((n_iter, B, N), device=llr.device, dtype=torch.float32)
     nbytes = _query('fgnn_ldpc_nms_record_bytes', B, N, M, E, n_iter)
     record = torch.empty((nbytes,), device=llr.device, dtype=torch.uint8)
-    _hip.call('fgnn_ldpc_nms_forward', llr, llr.stride(0) if B else N, *tables, alpha, beta, B, N, M, E, n_iter, share, 0, None, None,
-              None, None, totals, record, nbytes)
+    name, tabs = _entry_point('forward', tables, layers)
+    _hip.call(name, llr, llr.stride(0) if B else N, *tabs, alpha, beta, B, N, M, E, n_iter, share, 0, None, None, None, None, totals,
+              record, nbytes)
     return totals, record
 
 
-def nms_backward_raw(g_totals, llr, tables, sizes, alpha, beta, record, n_iter, share, want_llr=True):
+def nms_backward_raw(g_totals, llr, tables, sizes, alpha, beta, record, n_iter, share, want_llr=True, layers=None):
     """The backward's two launches: (g_alpha, g_beta [n_iter, W] f32, g_llr [B, N] f32 or None).  g_totals [n_iter, B, N], any
-    strides (the kernel reads it densely: a strided one is copied)."""
+    strides (the kernel reads it densely: a strided one is copied).  ``layers`` as the forward's that wrote ``record``."""
     N, M, E = sizes
     B = llr.shape[0]
     if tuple(g_totals.shape) != (n_iter, B, N):
@@ -82,36 +96,38 @@ def nms_backward_raw(g_totals, llr, tables, sizes, alpha, beta, record, n_iter, 
     g_llr = torch.empty((B, N), device=llr.device, dtype=torch.float32) if want_llr else None
     nbytes = _query('fgnn_ldpc_nms_backward_workspace_bytes', B, N, M, E, n_iter, share)
     ws = torch.empty((max(nbytes, 16),), device=llr.device, dtype=torch.uint8)
-    _hip.call('fgnn_ldpc_nms_backward', g_totals, llr, llr.stride(0) if B else N, *tables, alpha, beta, record, record.numel(), B, N, M, E,
-              n_iter, share, g_alpha, g_beta, g_llr, ws, ws.numel())
+    name, tabs = _entry_point('backward', tables, layers)
+    _hip.call(name, g_totals, llr, llr.stride(0) if B else N, *tabs, alpha, beta, record, record.numel(), B, N, M, E, n_iter, share,
+              g_alpha, g_beta, g_llr, ws, ws.numel())
     return g_alpha, g_beta, g_llr
 
 
 class _NmsFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, llr, alpha, beta, tables, sizes, n_iter, share):
+    def forward(ctx, llr, alpha, beta, tables, sizes, n_iter, share, layers):
         alpha, beta = alpha.detach().contiguous(), beta.detach().contiguous()
-        totals, record = nms_forward_raw(llr, tables, sizes, alpha, beta, n_iter, share)
+        totals, record = nms_forward_raw(llr, tables, sizes, alpha, beta, n_iter, share, layers)
         ctx.save_for_backward(llr, alpha, beta, record)
-        ctx.nms = (tables, sizes, n_iter, share)
+        ctx.nms = (tables, sizes, n_iter, share, layers)
         return totals
 
     @staticmethod
     def backward(ctx, g_totals):
         llr, alpha, beta, record = ctx.saved_tensors
-        tables, sizes, n_iter, share = ctx.nms
+        tables, sizes, n_iter, share, layers = ctx.nms
         g_alpha, g_beta, g_llr = nms_backward_raw(g_totals, llr, tables, sizes, alpha, beta, record, n_iter, share,
-                                                  want_llr=ctx.needs_input_grad[0])
-        return g_llr, g_alpha, g_beta, None, None, None, None
+                                                  want_llr=ctx.needs_input_grad[0], layers=layers)
+        return g_llr, g_alpha, g_beta, None, None, None, None, None
 
 
 class LearnedMinSum(torch.nn.Module):
     """Min-sum with trained weights for ``code`` (an ``LdpcCode`` within ``require_llr_decoder``'s limits; None: the built-in
     96.3.963): parameters ``alpha`` and ``beta`` [n_iter, W] f32, W = 1 (``share='iteration'``), M ('check') or E ('edge', indexed by
-    the edge id e = col_ptr[n] + u), filled with the constants ``alpha`` / ``beta``.  ``state_dict()`` is these two tensors; the
-    incidence tables are buffers outside it and follow ``.to(device)``.  The module runs on a ROCm device only."""
+    the edge id e = col_ptr[n] + u), filled with the constants ``alpha`` / ``beta``.  ``schedule``: 'flooding', or 'layered' over
+    ``code.layers()``.  ``state_dict()`` is the two parameters; the incidence (and layer) tables are buffers outside it and follow
+    ``.to(device)``.  The module runs on a ROCm device only."""
 
-    def __init__(self, code=None, n_iter=5, share='edge', alpha=0.8125, beta=0.0):
+    def __init__(self, code=None, n_iter=5, share='edge', alpha=0.8125, beta=0.0, schedule='flooding'):
         super().__init__()
         code = LdpcCode.builtin() if code is None else code
         if not isinstance(code, LdpcCode):
@@ -120,20 +136,32 @@ class LearnedMinSum(torch.nn.Module):
         tabs = code.incidence_tables()
         self.N, self.M, self.E = code.n_var, code.n_chk, int(tabs[0][-1])
         W = weights_per_iteration(n_iter, share, self.M, self.E)
-        self.code, self.n_iter, self.share = code, int(n_iter), share
+        if not isinstance(schedule, str) or schedule not in SCHEDULES:
+            raise ValueError('schedule must be one of %s, got %r' % (', '.join(SCHEDULES), schedule))
+        self.code, self.n_iter, self.share, self.schedule = code, int(n_iter), share, schedule
         for name, value in (('alpha', alpha), ('beta', beta)):
             if not np.isfinite(float(value)):
                 raise ValueError('%s must be finite, got %r' % (name, value))
             self.register_parameter(name, torch.nn.Parameter(torch.full((self.n_iter, W), float(value))))
         for name, a in zip(('col_ptr', 'row_ptr', 'row_edge', 'row_var'), tabs):
             self.register_buffer(name, torch.from_numpy(a.copy()), persistent=False)
+        if schedule == 'layered':
+            for name, a in zip(('layer_ptr', 'layer_chk'), code.layers()):
+                self.register_buffer(name, torch.from_numpy(a.copy()), persistent=False)
 
     def extra_repr(self):
-        return '%r, n_iter=%d, share=%r' % (self.code, self.n_iter, self.share)
+        return '%r, n_iter=%d, share=%r%s' % (self.code, self.n_iter, self.share, ', schedule=%r' % self.schedule if self.schedule != 'flooding' else '')
 
     def decoder_entry(self):
-        """What a checkpoint carries under 'decoder'."""
-        return {'kind': KIND, 'n_iter': int(self.n_iter), 'share': self.share}
+        """What a checkpoint carries under 'decoder'; 'schedule' only where it is not flooding."""
+        entry = {'kind': KIND, 'n_iter': int(self.n_iter), 'share': self.share}
+        if self.schedule != 'flooding':
+            entry['schedule'] = self.schedule
+        return entry
+
+    def layer_tables(self):
+        """(layer_ptr, layer_chk) on the module's device for the layered schedule, None for flooding: the raw launches' ``layers``."""
+        return (self.layer_ptr, self.layer_chk) if self.schedule == 'layered' else None
 
     def _prepare(self, llr):
         B, share, _ = check_nms_args(llr, self.N, self.M, self.E, self.n_iter, self.share, self.alpha, self.beta)
@@ -143,9 +171,10 @@ class LearnedMinSum(torch.nn.Module):
 
     def forward(self, llr):
         """llr [B, N] = log P(bit = 0) / P(bit = 1) -> totals [n_iter, B, N] f32, every iteration's totals (no early stop), through
-        the train mode of ``fgnn_ldpc_nms_forward``; differentiable in ``alpha``, ``beta`` and, where it asks for it, ``llr``."""
+        the train mode of ``fgnn_ldpc_nms_forward`` (layered: ``fgnn_ldpc_nms_layered_forward``); differentiable in ``alpha``,
+        ``beta`` and, where it asks for it, ``llr``."""
         llr, _, share, tables, sizes = self._prepare(llr)
-        return _NmsFunction.apply(llr, self.alpha, self.beta, tables, sizes, int(self.n_iter), share)
+        return _NmsFunction.apply(llr, self.alpha, self.beta, tables, sizes, int(self.n_iter), share, self.layer_tables())
 
     @torch.no_grad()
     def decode(self, llr, want_posteriors=False):
@@ -153,8 +182,9 @@ class LearnedMinSum(torch.nn.Module):
         the message is x[:, :K] —, violated checks [B] int32, iterations [B] int32[, post [B, N] f32: the final totals])."""
         llr, B, share, tables, (N, M, E) = self._prepare(llr)
         x, post, viol, iters = decode_outputs(B, N, llr.device, torch.float32 if want_posteriors else None)
-        _hip.call('fgnn_ldpc_nms_forward', llr, llr.stride(0) if B else N, *tables, self.alpha.detach().contiguous(),
-                  self.beta.detach().contiguous(), B, N, M, E, int(self.n_iter), share, 1, x, post, viol, iters, None, None, 0)
+        name, tabs = _entry_point('forward', tables, self.layer_tables())
+        _hip.call(name, llr, llr.stride(0) if B else N, *tabs, self.alpha.detach().contiguous(), self.beta.detach().contiguous(), B, N, M,
+                  E, int(self.n_iter), share, 1, x, post, viol, iters, None, None, 0)
         return (x, viol, iters, post) if want_posteriors else (x, viol, iters)
 
 
@@ -175,6 +205,6 @@ def load_checkpoint(path, code=None, device='cpu'):
     if not isinstance(entry, dict) or entry.get('kind') != KIND:
         raise ValueError('%s holds no learned min-sum decoder (no \'decoder\' entry of kind %r)' % (path, KIND))
     code.check_checkpoint(ckpt, path)
-    dec = LearnedMinSum(code, int(entry['n_iter']), entry['share'])
+    dec = LearnedMinSum(code, int(entry['n_iter']), entry['share'], schedule=entry.get('schedule', 'flooding'))
     dec.load_state_dict(ckpt['model_state_dict'], strict=True)
     return dec.to(device)

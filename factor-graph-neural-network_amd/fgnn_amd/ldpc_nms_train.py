@@ -31,8 +31,9 @@ def lr_sched(epoch):
 
 
 def checkpoint_dict(model, optimizer, scheduler, epoch, gcnt):
-    """``ldpc_train``'s dict plus 'decoder' (kind, n_iter, share: what ``ldpc_nms.load_checkpoint`` rebuilds the module from); for a
-    non-default code only, plus its 'code' entry (``LdpcCode.checkpoint_entry``), by which a reader refuses another code's decoder."""
+    """``ldpc_train``'s dict plus 'decoder' (kind, n_iter, share and, where it is not flooding, schedule: what
+    ``ldpc_nms.load_checkpoint`` rebuilds the module from); for a non-default code only, plus its 'code' entry (``LdpcCode.checkpoint_entry``), by
+    which a reader refuses another code's decoder."""
     d = {'model_state_dict': model.state_dict(), 'optimizer_state_dict': optimizer.state_dict(), 'lr_sche': scheduler.state_dict(),
          'epoch': int(epoch), 'gcnt': int(gcnt), 'decoder': model.decoder_entry()}
     if not model.code.is_default:
@@ -41,13 +42,15 @@ def checkpoint_dict(model, optimizer, scheduler, epoch, gcnt):
 
 
 def checkpoint_path(out_dir, model_name, model, epoch, snr):
-    return os.path.join(out_dir, '{}_{}_{}_epoches_{}_snr_{}.pt'.format(model_name, model.share, model.n_iter, epoch, snr))
+    """``MODEL_SHARE_NITER_epoches_EPOCH_snr_SNR.pt``; a layered decoder's has ``layered_`` before the iteration count."""
+    sched = '' if model.schedule == 'flooding' else model.schedule + '_'
+    return os.path.join(out_dir, '{}_{}_{}{}_epoches_{}_snr_{}.pt'.format(model_name, model.share, sched, model.n_iter, epoch, snr))
 
 
 def train(n_epochs=10, batch_size=256, snr=None, n_iter=5, share='edge', model_path=None, model_name='LearnedMinSum', steps_per_epoch=None,
           seed=0, out_dir='.', save_every=SAVE_EVERY, log_every=LOG_EVERY, graph=True, test_set=None, lr=LR, device='cuda', code=None,
-          alpha=0.8125, beta=0.0):
-    """Train ``LearnedMinSum(code, n_iter, share, alpha, beta)`` for ``n_epochs`` epochs of ``steps_per_epoch`` batches (default:
+          alpha=0.8125, beta=0.0, schedule='flooding'):
+    """Train ``LearnedMinSum(code, n_iter, share, alpha, beta, schedule)`` for ``n_epochs`` epochs of ``steps_per_epoch`` batches (default:
     ``ldpc_train``'s ceil(10000 / batch_size)).  ``code``: an ``LdpcCode`` within ``require_llr_decoder``'s limits (None: the built-in
     96.3.963; ValueError otherwise, before anything reaches the device).  Batch number ``gcnt`` (counted from 0 over the whole run,
     resumes included) is ``sample_rng(batch_size, seed, step=gcnt, snr_db=snr)``: SNR drawn from {0..4} dB per word unless ``snr`` fixes
@@ -62,7 +65,7 @@ def train(n_epochs=10, batch_size=256, snr=None, n_iter=5, share='edge', model_p
     256 steps.
 
     Checkpoints (``checkpoint_dict``) go to ``checkpoint_path(...)``: at the top of an epoch when ``(epoch + 1) % save_every == 0`` and
-    after the last epoch with ``epoch = n_epochs``.  ``model_path`` resumes from one (its n_iter and share must be the arguments').
+    after the last epoch with ``epoch = n_epochs``.  ``model_path`` resumes from one (its n_iter, share and schedule must be the arguments').
     ``test_set`` (a path or a dict, ``ldpc_eval.load_test_set``): after the last epoch the decoder's decode mode runs on it and the
     ``ber`` / ``err_class`` of ``ldpc_eval.LdpcErrorCounts`` over the K message bits are printed and returned.
 
@@ -77,7 +80,7 @@ def train(n_epochs=10, batch_size=256, snr=None, n_iter=5, share='edge', model_p
     save_every = int(save_every)
     if n_epochs < 0 or batch_size < 1 or steps_per_epoch < 1 or save_every < 1:
         raise ValueError('n_epochs >= 0, batch_size >= 1, steps_per_epoch >= 1 and save_every >= 1 needed')
-    model = LearnedMinSum(code, n_iter, share, alpha, beta)
+    model = LearnedMinSum(code, n_iter, share, alpha, beta, schedule)
     dev = trainloop.cuda_device(device)
     from .datapath import LdpcDataPath
     from .fastpath import FastAdam
@@ -184,6 +187,8 @@ def main(argv=None):
     ap.add_argument('--snr', type=int, default=None, help='one SNR (dB) for every word; default: 0..4 dB per word')
     ap.add_argument('--n_iter', type=int, default=5, help='decoding iterations (1..64), each with weights of its own')
     ap.add_argument('--share', choices=('iteration', 'check', 'edge'), default='edge', help='one alpha / beta per iteration, per check or per edge')
+    ap.add_argument('--schedule', choices=('flooding', 'layered'), default='flooding',
+                    help='flooding, or layered: the checks layer by layer, each on the totals the earlier layers left')
     ap.add_argument('--lr', type=float, default=LR)
     ap.add_argument('--model_path', default=None, help='resume from this checkpoint')
     ap.add_argument('--model_name', default='LearnedMinSum')
@@ -200,7 +205,7 @@ def main(argv=None):
     from .ldpc_code import LdpcCode
     r = train(args.n_epochs, args.batch_size, args.snr, args.n_iter, args.share, trainloop.existing_or_none(args.model_path),
               args.model_name, args.steps_per_epoch, args.seed, args.out_dir, args.save_every, args.log_every, args.graph, args.test_path,
-              args.lr, 'cuda:0', LdpcCode.from_spec(args.code))
+              args.lr, 'cuda:0', LdpcCode.from_spec(args.code), schedule=args.schedule)
     if 'err_class' in r:                 # (an array: as lists for the JSON line; the last key either way)
         r['err_class'] = [[float(v) for v in row] for row in r['err_class']]
     trainloop.report(r, args.json)

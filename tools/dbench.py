@@ -9,7 +9,8 @@ and the decoded fraction (words that end with no violated check), and the LDS by
 
 The learned min-sum decoder (fgnn_amd.ldpc_nms.LearnedMinSum.decode, csrc/ldpc_nms.hip: the decode mode, early stopping) follows,
 beside min-sum:flooding at the same iteration count (--learned_iters), with untrained weights (alpha 0.8125, beta 0: the same
-decisions) shared per iteration, per check and per edge: the weight reads are its only extra work in the loop.
+decisions) shared per iteration, per check and per edge: the weight reads are its only extra work in the loop.  Its layered schedule
+(schedule='layered', csrc/ldpc_nms_layered.hip; rows ``learned layered ...``) follows in the same way beside min-sum:layered at that iteration count.
 
 Ordered-statistics reprocessing (LdpcDataPath.decode_osd, csrc/ldpc_osd.hip) follows as min-sum:layered:osd=0|1|2 (order 2: the
 default span, 64), each row the whole composition ``ldpc_decoders.Decoder.run`` runs — the decoder with posteriors, then the reprocessing
@@ -95,6 +96,10 @@ def main():
         for share in SHARES:
             dec = LearnedMinSum(code, n, share).to(dev)
             runs.append(('learned-min-sum %s iters=%d' % (share, n), lambda dec=dec: dec.decode(llr)))
+        runs.append(('min-sum:layered:iters=%d' % n, lambda: path.decode_llr(llr, 'min-sum', 'layered', max_iter=n)))
+        for share in SHARES:
+            dec = LearnedMinSum(code, n, share, schedule='layered').to(dev)
+            runs.append(('learned layered %s iters=%d' % (share, n), lambda dec=dec: dec.decode(llr)))
         for label, run in runs:
             med, lo, hi, (x, viol, iters) = measure(run, args.repeats)
             print('%-24s %-34s %12.0f %10.1f %10.1f %9.2f %9.4f' % (name, label, args.words / med, med * 1e6, 100 * (hi - lo) / med,
