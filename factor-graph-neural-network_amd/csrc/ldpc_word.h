@@ -1,4 +1,5 @@
-// ldpc_word.h — what the LLR-domain kernels (ldpc_llr.hip) and the learned min-sum kernels (ldpc_nms.hip, ldpc_nms_layered.hip) share: the limits, the
+// ldpc_word.h — what the LLR-domain kernels (ldpc_llr.hip), the learned min-sum kernels (ldpc_nms.hip, ldpc_nms_layered.hip) and the
+// ADMM-LP kernel (ldpc_lp.hip: R holds z, T holds x, prior holds g) share: the limits, the
 // per-word LDS layout and the steps every flooding iteration is made of.  Both files are built with -ffp-contract=off and each
 // function below keeps its statements in the order the restatements (tests/ldpc_llr_oracle.py, tests/ldpc_nms_oracle.py) pin.
 //
@@ -49,6 +50,12 @@ __host__ __device__ static inline int64_t ldpc_word_bytes_nms(int N, int M, int 
     return (4 * (2 * (int64_t)E + 2 * (int64_t)N) + scratch + 15) / 16 * 16 + (2 * ((int64_t)(M + 1) + (N + 1)) + 15) / 16 * 16;
 }
 
+// The ADMM-LP kernel's (ldpc_lp.hip): 16 scratch words, 16-bit row_ptr and col_ptr padded to a whole word, then f32 u [E].
+static inline int64_t ldpc_word_bytes_lp(int N, int M, int E) {
+    const int64_t bytes = 4 * (2 * (int64_t)E + 2 * (int64_t)N) + 4 * 16 + (2 * ((int64_t)(M + 1) + (N + 1)) + 3) / 4 * 4 + 4 * (int64_t)E;
+    return (bytes + 15) / 16 * 16;
+}
+
 // ``scratch``: the number of 32-bit scratch words.  What a kernel appends starts at cp + (N + 1).
 __device__ __forceinline__ LdpcWord ldpc_word_carve(int N, int M, int E, int scratch) {
     LdpcWord s;
@@ -95,8 +102,10 @@ __device__ __forceinline__ float ldpc_var_sum(const LdpcWord& s, int n, float in
     return sum;
 }
 
-// viol = the number of checks with an odd number of T[var] < 0: per wave, then over the waves.  Ends behind a barrier.
-__device__ __forceinline__ int ldpc_count_violated(const LdpcWord& s, int M) {
+// viol = the number of checks with an odd number of variables whose hard decision bit(T[var]) is 1: per wave, then over the waves.
+// Ends behind a barrier.
+template <class Bit>
+__device__ __forceinline__ int ldpc_count_violated_by(const LdpcWord& s, int M, Bit bit) {
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
     int cnt = 0;
     for (int m0 = wave * 64; m0 < M; m0 += nt) {
@@ -104,7 +113,7 @@ __device__ __forceinline__ int ldpc_count_violated(const LdpcWord& s, int M) {
         bool odd = false;
         if (m < M) {
             const int r1 = s.rp[m + 1];
-            for (int r = s.rp[m]; r < r1; ++r) odd ^= s.T[s.rtab[r] >> 16] < 0.0f;
+            for (int r = s.rp[m]; r < r1; ++r) odd ^= bit(s.T[s.rtab[r] >> 16]);
         }
         cnt += __popcll(__ballot(odd));
     }
@@ -113,6 +122,11 @@ __device__ __forceinline__ int ldpc_count_violated(const LdpcWord& s, int M) {
     int viol = 0;
     for (int w = 0; w < nw; ++w) viol += s.wsum[w];
     return viol;
+}
+
+// ... with the LLR-domain decision T[var] < 0
+__device__ __forceinline__ int ldpc_count_violated(const LdpcWord& s, int M) {
+    return ldpc_count_violated_by(s, M, [](float t) { return t < 0.0f; });
 }
 
 // The first sweep of a min-sum check over its edges r0 .. r1 - 1, q = T[var] - R[edge]: the two smallest |q| and their places

@@ -8,7 +8,7 @@ fails loudly (build it with ``python __graft_entry__.py`` or ``make -C csrc``).
 The header is the one place where the interface is written down: the prototypes' ctypes signatures, the list of
 exports and every mirrored constant are parsed from it when this module is imported (``signatures``, ``constants``).
 Entry points added beside it live in companion headers (``bind_header``: include/fgnn_hip_ldpc_train.h,
-include/fgnn_hip_pgm_bp.h, include/fgnn_hip_ldpc_code.h, include/fgnn_hip_ldpc_llr.h, include/fgnn_hip_ldpc_nms.h, include/fgnn_hip_ldpc_nms_layered.h, include/fgnn_hip_ldpc_osd.h, include/fgnn_hip_wgrad.h); ``SIGNATURES``,
+include/fgnn_hip_pgm_bp.h, include/fgnn_hip_ldpc_code.h, include/fgnn_hip_ldpc_llr.h, include/fgnn_hip_ldpc_nms.h, include/fgnn_hip_ldpc_nms_layered.h, include/fgnn_hip_ldpc_osd.h, include/fgnn_hip_ldpc_lp.h, include/fgnn_hip_wgrad.h); ``SIGNATURES``,
 ``EXPORTS`` and ``ABI_VERSION`` stay the main header's.
 """
 import ctypes
@@ -315,4 +315,5 @@ LDPC_LLR = bind_header('fgnn_hip_ldpc_llr.h')          # fgnn_ldpc_decode_llr, f
 LDPC_NMS = bind_header('fgnn_hip_ldpc_nms.h')          # fgnn_ldpc_nms_forward, _backward and their four size queries
 LDPC_NMS_LAYERED = bind_header('fgnn_hip_ldpc_nms_layered.h')     # fgnn_ldpc_nms_layered_forward, _backward, _lds_bytes
 LDPC_OSD = bind_header('fgnn_hip_ldpc_osd.h')          # fgnn_ldpc_osd, fgnn_ldpc_osd_lds_bytes
+LDPC_LP = bind_header('fgnn_hip_ldpc_lp.h')            # fgnn_ldpc_decode_lp, fgnn_ldpc_decode_lp_lds_bytes
 WGRAD = bind_header('fgnn_hip_wgrad.h')                # fgnn_linear_wgrad_kernel: the kernel a weight-gradient call would run

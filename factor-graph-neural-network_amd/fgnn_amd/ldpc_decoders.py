@@ -1,8 +1,9 @@
 """The classical LDPC decoders: everything on the host that drives a decoder kernel.
 
 ``LdpcDecoders``, the base class of ``datapath.LdpcDataPath``, carries the probability-domain sum-product decoder (``decode``,
-csrc/ldpc_decode.hip), the LLR-domain decoders (``decode_llr``, csrc/ldpc_llr.hip) and ordered-statistics reprocessing (``decode_osd``,
-csrc/ldpc_osd.hip) with their argument checks, mirrored limits and the one set of device tables all three read.  ``parse_decoder``
+csrc/ldpc_decode.hip), the LLR-domain decoders (``decode_llr``, csrc/ldpc_llr.hip), the ADMM linear-programming decoder (``decode_lp``,
+csrc/ldpc_lp.hip) and ordered-statistics reprocessing (``decode_osd``, csrc/ldpc_osd.hip) with their argument checks, mirrored limits
+and the one set of device tables all four read.  ``parse_decoder``
 turns a spec into a ``Decoder``, whose ``run`` decodes received words through a path.  ``ldpc_nms`` (the learned decoder) shares the
 batch check and the output buffers.
 """
@@ -17,6 +18,8 @@ from . import _hip
 LLR_ALGORITHMS = {'min-sum': 0, 'offset-min-sum': 1, 'sum-product': 2}     # fgnn_ldpc_decode_llr's ``algorithm``
 LLR_SCHEDULES = ('flooding', 'layered')
 OSD_MAX_ORDER, OSD_MAX_PAIR_SPAN = 2, 256       # fgnn_ldpc_osd's limits (csrc/ldpc_osd.hip)
+LP = 'admm-lp'                                  # the head of the ADMM-LP decoder's spec
+LP_DEFAULTS = {'max_iter': 200, 'mu': 3.0, 'penalty': 0.0, 'relax': 1.9, 'eps': 1e-5}      # ``decode_lp``'s, and the spec's
 LEARNED = 'learned-min-sum'                     # the head of the learned decoder's spec (``ldpc_nms.KIND``)
 
 # a code's incidence tables on the device (``LdpcCode.incidence_tables``) and its sizes: what every decoder kernel is given
@@ -47,6 +50,27 @@ def check_decode_llr_args(llr, n_var, algorithm, schedule, max_iter, alpha, beta
         if not (np.isfinite(float(v)) and 0 <= float(v) <= 3.0e38):
             raise ValueError('%s must be a finite float32 value >= 0, got %r' % (what, v))
     return check_word_batch('llr', llr, n_var), LLR_ALGORITHMS[algorithm]
+
+
+def check_decode_lp_args(llr, n_var, min_degree, max_iter, mu, penalty, relax, eps, stop_on_codeword):
+    """Arguments of ``LdpcDecoders.decode_lp`` (before anything reaches the device); ``min_degree``: the code's smallest positive
+    variable degree, which 2 penalty / mu must stay below (the x-update divides by degree - 2 penalty / mu).  Returns (B,
+    stop_on_codeword as 0 / 1, with None read as penalty > 0)."""
+    if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= int(max_iter) < 2 ** 31:
+        raise ValueError('max_iter must be an integer in [1, 2^31), got %r' % (max_iter,))
+    if not (np.isfinite(float(mu)) and 0 < float(mu) <= 3.0e38):
+        raise ValueError('mu must be a finite float32 value > 0, got %r' % (mu,))
+    if not (np.isfinite(float(penalty)) and 0 <= float(penalty) <= 3.0e38):
+        raise ValueError('penalty must be a finite float32 value >= 0, got %r' % (penalty,))
+    if not (np.isfinite(float(eps)) and abs(float(eps)) <= 3.0e38):
+        raise ValueError('eps must be a finite float32 value, got %r' % (eps,))
+    if not 1 <= float(np.float32(relax)) < 2:
+        raise ValueError('relax must be in [1, 2), got %r' % (relax,))
+    if stop_on_codeword not in (None, False, True, 0, 1):
+        raise ValueError('stop_on_codeword must be None, False or True, got %r' % (stop_on_codeword,))
+    if not 2 * float(np.float32(penalty)) / float(np.float32(mu)) < min_degree:
+        raise ValueError('2 penalty / mu = %g must be smaller than the smallest variable degree, %d' % (2 * float(penalty) / float(mu), min_degree))
+    return check_word_batch('llr', llr, n_var), int(float(penalty) > 0 if stop_on_codeword is None else bool(stop_on_codeword))
 
 
 def check_decode_osd_args(rel, metric, viol, n_var, order, span):
@@ -89,7 +113,7 @@ def decode_outputs(B, n_var, device, post_dtype=None):
 
 class LdpcDecoders:
     """The decoders of an ``LdpcDataPath`` (its base class; the path supplies ``device``, ``code`` and ``N``).  One set of device
-    tables per path serves all three; each decoder's limits are checked on its first call, so a code may exceed one decoder only."""
+    tables per path serves all four; each decoder's limits are checked on its first call, so a code may exceed one decoder only."""
 
     def __init__(self):
         self._tables = None             # DecoderTables, uploaded by the first decoder call
@@ -98,12 +122,15 @@ class LdpcDecoders:
         self._learned = {}              # checkpoint path -> its ``LearnedMinSum`` on the device (``learned``)
 
     def _device_tables(self, gate):
-        """The device tables for the decoder ``gate`` names ('decode', 'llr' or 'osd').  Its first call checks the code against
-        that decoder's limits (``require_decoder`` / ``require_llr_decoder``, and for 'osd' the reprocessing kernel's LDS
-        footprint); the first of any uploads ``code.incidence_tables()``."""
+        """The device tables for the decoder ``gate`` names ('decode', 'llr', 'lp' or 'osd').  Its first call checks the code against
+        that decoder's limits (``require_decoder`` / ``require_llr_decoder``, and for 'osd' and 'lp' the kernel's LDS footprint: the
+        byte query refuses what does not fit); the first of any uploads ``code.incidence_tables()``."""
         if gate not in self._gated:
             (self.code.require_decoder if gate == 'decode' else self.code.require_llr_decoder)()
             if gate == 'osd' and int(_hip.invoke('fgnn_ldpc_osd_lds_bytes', self.code.n_var, self.code.n_chk)) < 0:
+                raise ValueError(_hip.lib().fgnn_last_error().decode())
+            if gate == 'lp' and int(_hip.invoke('fgnn_ldpc_decode_lp_lds_bytes', self.code.n_var, self.code.n_chk,
+                                                int((np.asarray(self.code.nlist) >= 0).sum()))) < 0:
                 raise ValueError(_hip.lib().fgnn_last_error().decode())
             if self._tables is None:
                 tabs = self.code.incidence_tables()
@@ -165,6 +192,25 @@ class LdpcDecoders:
                   n_layers, B, N, M, E, alg, int(max_iter), float(alpha), float(beta), x, post, viol, iters)
         return (x, viol, iters, post) if want_posteriors else (x, viol, iters)
 
+    def decode_lp(self, llr, max_iter=200, mu=3.0, penalty=0.0, relax=1.9, eps=1e-5, stop_on_codeword=None, want_soft=False):
+        """The ADMM linear-programming decoder (fgnn_ldpc_decode_lp, include/fgnn_hip_ldpc_lp.h; no counterpart in the reference) for a
+        batch: llr [B, N] as ``decode_llr`` takes it.  ``mu``: the ADMM step; ``penalty``: the weight of Liu & Draper's penalty term
+        (0: the plain LP, whose integral optima are maximum-likelihood codewords); ``relax``: over-relaxation in [1, 2); a word stops
+        when its primal residual and its change of z are both at most ``eps`` (never with eps < 0), or, with ``stop_on_codeword`` (None: penalty > 0), when
+        its hard decisions satisfy every check, or after ``max_iter`` iterations.  2 penalty / mu must be smaller than the code's
+        smallest variable degree.  Returns (x [B, N] uint8 hard decisions, violated checks [B] int32, iterations [B] int32, flags [B]
+        int32: bit 0 = stopped by the residual rule, bit 1 = also integral to 1e-3, with penalty = 0 the ML certificate[, soft [B, N]
+        f32: the final x in [0, 1])."""
+        deg = (np.asarray(self.code.nlist) >= 0).sum(1)
+        B, soc = check_decode_lp_args(llr, self.N, int(deg[deg > 0].min()), max_iter, mu, penalty, relax, eps, stop_on_codeword)
+        col_ptr, row_ptr, row_edge, row_var, N, M, E = self._device_tables('lp')
+        llr = llr_batch(llr, self.device, N)
+        x, soft, viol, iters = decode_outputs(B, N, self.device, torch.float32 if want_soft else None)
+        flags = torch.empty((B,), device=self.device, dtype=torch.int32)
+        _hip.call('fgnn_ldpc_decode_lp', llr, llr.stride(0) if B else N, col_ptr, row_ptr, row_edge, row_var, B, N, M, E, int(max_iter),
+                  float(mu), float(penalty), float(relax), float(eps), soc, x, soft, viol, iters, flags)
+        return (x, viol, iters, flags, soft) if want_soft else (x, viol, iters, flags)
+
     def decode_osd(self, rel, metric=None, viol=None, order=1, span=None):
         """Ordered-statistics reprocessing (fgnn_ldpc_osd, include/fgnn_hip_ldpc_osd.h; no counterpart in the reference) for a batch:
         rel [B, N] orders the positions and gives the hard decisions (a decoder's posteriors: ``decode_llr(..., want_posteriors=True)``),
@@ -186,8 +232,8 @@ class LdpcDecoders:
 
 
 class Decoder(typing.NamedTuple):
-    """A parsed classical decoder (``parse_decoder``'s result): its canonical spec, its kind ('mackay', 'llr' or 'learned') and the
-    arguments of that kind's decoder call."""
+    """A parsed classical decoder (``parse_decoder``'s result): its canonical spec, its kind ('mackay', 'llr', 'lp' or 'learned') and
+    the arguments of that kind's decoder call."""
     spec: str
     kind: str
     args: dict
@@ -196,18 +242,37 @@ class Decoder(typing.NamedTuple):
         """Hard decisions, violated checks and iterations on received words y [B, N] at snr0 [B] dB, through ``path`` (an
         ``LdpcDataPath``).  A learned decoder's checkpoint is loaded on the first call and kept on ``path`` (once per checkpoint
         path); one trained for another code than ``path.code`` is refused (``LdpcCode.check_checkpoint``)."""
+        return self.run_flags(path, y, snr0)[:3]
+
+    @property
+    def certifies(self):
+        """Whether flag bit 1 of ``run_flags`` proves a word maximum-likelihood: the plain LP (kind 'lp', penalty 0)."""
+        return self.kind == 'lp' and self.args['penalty'] == 0
+
+    def run_flags(self, path, y, snr0):
+        """``run``'s triple and, fourth, the decoder's own flags [B] int32 (``LdpcDecoders.decode_lp``'s: before any reprocessing) for
+        kind 'lp', None for every other kind."""
         if self.kind == 'mackay':
-            return path.decode(path.bit_prior(y, snr0), **self.args)
+            return path.decode(path.bit_prior(y, snr0), **self.args) + (None,)
         llr = path.bit_llr(y, snr0)
         if self.kind == 'learned':
-            return path.learned(self.args['path']).decode(llr)
+            return tuple(path.learned(self.args['path']).decode(llr)) + (None,)
+        if self.kind == 'lp':
+            lp = dict(self.args)
+            order, span = lp.pop('osd', None), lp.pop('span', None)
+            if order is None:
+                return path.decode_lp(llr, **lp)
+            # ADMM-OSD: the words left with violated checks are reprocessed, ordered by |0.5 - x| and scored against the channel LLRs
+            _, viol, iters, flags, soft = path.decode_lp(llr, want_soft=True, **lp)
+            x = path.decode_osd(0.5 - soft, metric=llr, viol=viol, order=order, span=span)[0]
+            return x, torch.zeros_like(viol), iters, flags
         if 'osd' in self.args:  # BP-OSD: the words the decoder leaves with violated checks are reprocessed against the channel LLRs
             bp = dict(self.args)
             order, span = bp.pop('osd'), bp.pop('span', None)
             _, viol, iters, post = path.decode_llr(llr, want_posteriors=True, **bp)
             x = path.decode_osd(post, metric=llr, viol=viol, order=order, span=span)[0]
-            return x, torch.zeros_like(viol), iters
-        return path.decode_llr(llr, **self.args)
+            return x, torch.zeros_like(viol), iters, None
+        return path.decode_llr(llr, **self.args) + (None,)
 
 
 def parse_decoder(spec):
@@ -222,7 +287,11 @@ def parse_decoder(spec):
     that order.
     ``learned-min-sum:CHECKPOINT``: the trained min-sum decoder of an ``ldpc_nms_train`` checkpoint (``ldpc_nms.LearnedMinSum``), kind
     'learned', arguments {'path'}; everything behind the first colon is the path (it may hold colons), and the spec is canonical as
-    it stands.  The triple is a ``Decoder``: ``.run(path, y, snr0)`` decodes with it."""
+    it stands.
+    ``admm-lp[:iters=N][:mu=M][:penalty=A][:relax=R][:eps=E][:osd=W[:span=L]]``: the ADMM linear-programming decoder
+    (``LdpcDecoders.decode_lp``), kind 'lp', its keyword arguments max_iter, mu, penalty, relax and eps (defaults ``LP_DEFAULTS``;
+    stop_on_codeword stays at its default, penalty > 0) and 'osd' / 'span' as above (the reprocessing orders by |0.5 - x|); the
+    canonical spec lists only what differs from the defaults, in that order.  The triple is a ``Decoder``: ``.run(path, y, snr0)`` decodes with it."""
     if not isinstance(spec, str) or not spec:
         raise ValueError('a decoder spec is a non-empty string, got %r' % (spec,))
     if spec == LEARNED or spec.startswith(LEARNED + ':'):
@@ -231,6 +300,8 @@ def parse_decoder(spec):
             raise ValueError('decoder spec %r: %s:CHECKPOINT needs the path of a checkpoint' % (spec, LEARNED))
         return Decoder(spec, 'learned', {'path': ckpt})
     head, *rest = spec.split(':')
+    if head == LP:
+        return _parse_lp(spec, rest)
     opts, schedule = {}, None
     for part in rest:
         if part in LLR_SCHEDULES and schedule is None and not opts:
@@ -267,3 +338,34 @@ def parse_decoder(spec):
             kw[key] = opts[key]
             canon += ':%s=%d' % (key, opts[key])
     return Decoder(canon, 'llr', kw)
+
+
+def _parse_lp(spec, parts):
+    """``parse_decoder`` for an ``admm-lp`` spec; ``parts``: what follows the head."""
+    keys = {'iters': 'max_iter', 'mu': 'mu', 'penalty': 'penalty', 'relax': 'relax', 'eps': 'eps', 'osd': 'osd', 'span': 'span'}
+    opts = {}
+    for part in parts:
+        key, eq, val = part.partition('=')
+        if not eq or key not in keys or key in opts:
+            raise ValueError('decoder spec %r: cannot read %r (iters=N, mu=M, penalty=A, relax=R, eps=E, osd=W, span=L)' % (spec, part))
+        try:
+            opts[key] = int(val) if key in ('iters', 'osd', 'span') else float(val)
+        except ValueError:
+            raise ValueError('decoder spec %r: %s=%r is not a number' % (spec, key, val)) from None
+        v = opts[key]
+        ok = {'iters': 1 <= v < 2 ** 31, 'span': 1 <= v < 2 ** 31, 'osd': 0 <= v <= OSD_MAX_ORDER, 'mu': 0 < v <= 3.0e38,
+              'relax': 1 <= v < 2, 'eps': abs(v) <= 3.0e38}.get(key, 0 <= v <= 3.0e38)
+        if not ok:
+            raise ValueError('decoder spec %r: %s=%r is out of range' % (spec, key, val))
+    if 'span' in opts and (opts.get('osd', 0) < 1 or opts['osd'] == 2 and opts['span'] > OSD_MAX_PAIR_SPAN):
+        raise ValueError('decoder spec %r: span=L needs osd=1 or osd=2 (then L <= %d)' % (spec, OSD_MAX_PAIR_SPAN))
+    kw, canon = dict(LP_DEFAULTS), LP
+    for key in ('iters', 'mu', 'penalty', 'relax', 'eps'):
+        if key in opts and opts[key] != LP_DEFAULTS[keys[key]]:
+            kw[keys[key]] = opts[key]
+            canon += ':%s=%s' % (key, '%d' % opts[key] if key == 'iters' else repr(opts[key]))
+    for key in ('osd', 'span'):
+        if key in opts:
+            kw[key] = opts[key]
+            canon += ':%s=%d' % (key, opts[key])
+    return Decoder(canon, 'lp', kw)

@@ -120,6 +120,36 @@ class LdpcErrorCounts:
                 'counts': c}
 
 
+class MlCertificates:
+    """What only the plain LP decoder (``Decoder.certifies``) can count, accumulated on the device: ``ml_certified``, the words whose
+    flags carry the ML certificate (bit 1 of ``LdpcDecoders.decode_lp``'s), and ``certified_word_errors``, those among them that differ
+    from the sent word: each is a word on which the maximum-likelihood decoder errs too, so their number is a lower bound on its
+    word errors."""
+
+    def __init__(self, device):
+        self.counts = torch.zeros(2, dtype=torch.int64, device=device)
+
+    def add(self, x, flags, sent):
+        """x [B, N] hard decisions, flags [B], sent [B, N] the transmitted words."""
+        cert = (flags & 2) != 0
+        wrong = (x != sent.to(x.device)[:, :x.shape[1]].to(x.dtype)).any(1)
+        self.counts += torch.stack((cert.sum(), (cert & wrong).sum()))
+
+    def result(self):
+        ml_certified, certified_word_errors = self.counts.tolist()
+        return {'ml_certified': ml_certified, 'certified_word_errors': certified_word_errors}
+
+
+def run_counted(decoder, path, y, snr0, sent, certs):
+    """``decoder.run(path, y, snr0)``; a decoder that certifies also adds its flags against ``sent`` to ``certs`` (an
+    ``MlCertificates``)."""
+    if not decoder.certifies:
+        return decoder.run(path, y, snr0)
+    x, viol, iters, flags = decoder.run_flags(path, y, snr0)
+    certs.add(x, flags, sent)
+    return x, viol, iters
+
+
 def load_test_set(test_set, device, n_var=96):
     """A test set (the dict of ``make_test_set`` / the reference's generator, or a path to its ``torch.save`` file) on ``device``:
     (noizy_sg [n,96] f32, gts [n,96], snr_dbs [n,96] or [n] f32, sigma_b [n] f32); 96 reads ``n_var`` for another code."""
@@ -153,7 +183,9 @@ def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=Fal
     (``decode(bit_prior(y, snr), loops=100)``, lib/data/ldpc.py:18-24) on the same received words.  The model's training flag is
     restored afterwards.  ``baseline`` may also be a decoder spec (``parse_decoder``: 'mackay', 'min-sum:layered', ...): that decoder's
     result under 'baseline'; or a list of specs: one result each under ``res['baselines'][spec]``.  ``code``: the ``LdpcCode`` the model was built for (None: the built-in 96.3.963); the errors are counted
-    over its K message bits and the baseline runs on its ``nlist``.  ``model`` may also be a checkpoint's path (``load_model``)."""
+    over its K message bits and the baseline runs on its ``nlist``.  ``model`` may also be a checkpoint's path (``load_model``).  The
+    result of a plain LP decoder ('admm-lp' with penalty 0) also carries ``ml_certified`` and ``certified_word_errors``
+    (``MlCertificates``)."""
     if dtype not in (torch.float32, torch.bfloat16):
         raise ValueError('dtype must be float32 or bfloat16')
     if baseline is True:
@@ -173,7 +205,8 @@ def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=Fal
         raise ValueError('batch_size must be >= 1')
     dev = next(model.parameters()).device
     counts = LdpcErrorCounts(dev, snr_grid, sigma_grid)
-    decoders = [(spec, decoder, LdpcErrorCounts(dev, snr_grid, sigma_grid)) for spec, decoder in zip(specs, parsed)]
+    decoders = [(spec, decoder, LdpcErrorCounts(dev, snr_grid, sigma_grid), MlCertificates(dev)) for spec, decoder in zip(specs, parsed)]
+    result = lambda decoder, acc, certs: dict(acc.result(), **(certs.result() if decoder.certifies else {}))
     path = LdpcDataPath(dev, code)
     y, gts, snr, sb = load_test_set(test_set, dev, code.n_var)
     n = y.shape[0]
@@ -189,15 +222,15 @@ def evaluate(model, test_set, batch_size=4096, dtype=torch.float32, baseline=Fal
                                   path.nn_idx_v2f.unsqueeze(0).expand(B, -1, -1), ef_f2v, ef_v2f)
                 counts.add_logits(logits, gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
                 snr0 = snr[i:j] if snr.dim() == 1 else snr[i:j, 0]
-                for _, decoder, acc in decoders:
-                    acc.add_bits(decoder.run(path, y[i:j], snr0)[0], gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
+                for _, decoder, acc, certs in decoders:
+                    acc.add_bits(run_counted(decoder, path, y[i:j], snr0, gts[i:j], certs)[0], gts[i:j], snr[i:j], sb[i:j], nbits=code.K)
     finally:
         model.train(was)
     res = counts.result()
     if isinstance(baseline, str):
-        res['baseline'] = decoders[0][2].result()
+        res['baseline'] = result(*decoders[0][1:])
     elif decoders:
-        res['baselines'] = {spec: acc.result() for spec, _, acc in decoders}
+        res['baselines'] = {spec: result(decoder, acc, certs) for spec, decoder, acc, certs in decoders}
     return res
 
 
@@ -210,7 +243,8 @@ def ber_curve(code, decoder, snr_db, sigma_b=0, batch=4096, min_word_errors=100,
 
     Reproducible from the arguments: the j-th batch (j = 0, 1, ...) of the i-th SNR value (in the order given) is
     ``sample_rng(batch, seed=seed, step=i * 2**32 + j)``, so no two batches of a curve share their draws (at most 2**32 batches per
-    point).  Returns a list of dicts, one per SNR value: snr_db, words, bit_errors, word_errors, ber, wer, mean_iters."""
+    point).  Returns a list of dicts, one per SNR value: snr_db, words, bit_errors, word_errors, ber, wer, mean_iters, and for a plain LP
+    decoder ('admm-lp' with penalty 0) ml_certified and certified_word_errors (``MlCertificates``)."""
     code = LdpcCode.builtin() if code is None else code
     decoder = parse_decoder(decoder)
     snr_db = [float(v) for v in ([snr_db] if np.isscalar(snr_db) else snr_db)]
@@ -226,10 +260,11 @@ def ber_curve(code, decoder, snr_db, sigma_b=0, batch=4096, min_word_errors=100,
     for i, snr in enumerate(snr_db):
         acc = LdpcErrorCounts(path.device, (snr,), (sigma_b,))
         it_sum = torch.zeros((), dtype=torch.int64, device=path.device)
+        certs = MlCertificates(path.device)
         drawn = None
         for j in range(2 ** 32):
             drawn = path.sample_rng(batch, seed=seed, step=i * 2 ** 32 + j, snr_db=snr, out=drawn)
-            x, _, iters = decoder.run(path, drawn.y, drawn.snr_db)[:3]
+            x, _, iters = run_counted(decoder, path, drawn.y, drawn.snr_db, drawn.cw, certs)
             acc.add_bits(x, drawn.cw, drawn.snr_db, drawn.sigma_b, nbits=code.K)
             it_sum += iters.sum()
             tot = acc.counts[-1].tolist()
@@ -237,7 +272,7 @@ def ber_curve(code, decoder, snr_db, sigma_b=0, batch=4096, min_word_errors=100,
                 break
         bits, bit_errors, words, word_errors = tot
         out.append({'snr_db': snr, 'words': words, 'bit_errors': bit_errors, 'word_errors': word_errors, 'ber': bit_errors / bits,
-                    'wer': word_errors / words, 'mean_iters': int(it_sum) / words})
+                    'wer': word_errors / words, 'mean_iters': int(it_sum) / words, **(certs.result() if decoder.certifies else {})})
     return out
 
 
@@ -255,7 +290,9 @@ def main(argv=None):
                     help='also print the table of a classical decoder; may be repeated.  mackay, or min-sum | offset-min-sum | '
                          'sum-product [:flooding | :layered] [:iters=N] [:alpha=A] [:beta=B] [:osd=W [:span=L]] (osd: ordered-'
                          'statistics reprocessing of order W), or learned-min-sum:CHECKPOINT (python -m fgnn_amd.ldpc_nms_train; runs the '
-                         'schedule the checkpoint was trained with, flooding or layered)')
+                         'schedule the checkpoint was trained with, flooding or layered), or admm-lp [:iters=N] [:mu=M] [:penalty=A] '
+                         '[:relax=R] [:eps=E] [:osd=W [:span=L]] (the ADMM linear-programming decoder; with penalty 0 the words it '
+                         'certifies as maximum-likelihood are counted too)')
     ap.add_argument('--curve', action='store_true', help='print a BER / WER curve of the one --decoder over --snr (no model)')
     ap.add_argument('--snr', default='0,1,2,3,4', help='--curve: SNR values in dB, comma-separated')
     ap.add_argument('--sigma_b', type=int, default=0, help='--curve: the burst level')
@@ -278,10 +315,13 @@ def main(argv=None):
             ap.error('--curve takes exactly one --decoder')
         rows = ber_curve(code, args.decoder[0], [float(v) for v in args.snr.split(',')], args.sigma_b, args.batch_size,
                          args.min_word_errors, args.max_words, args.seed, dev)
-        print('%8s %10s %12s %12s %12s %12s %10s' % ('snr_db', 'words', 'bit_errors', 'word_errors', 'ber', 'wer', 'mean_iters'))
+        certifies = 'ml_certified' in rows[0]       # (the plain LP decoder: two more columns)
+        print('%8s %10s %12s %12s %12s %12s %10s' % ('snr_db', 'words', 'bit_errors', 'word_errors', 'ber', 'wer', 'mean_iters')
+              + (' %12s %10s' % ('ml_certified', 'cert_wrong') if certifies else ''))
         for r in rows:
             print('%8.3f %10d %12d %12d %12.4e %12.4e %10.3f' % (r['snr_db'], r['words'], r['bit_errors'], r['word_errors'], r['ber'],
-                                                               r['wer'], r['mean_iters']))
+                                                               r['wer'], r['mean_iters'])
+                  + (' %12d %10d' % (r['ml_certified'], r['certified_word_errors']) if certifies else ''))
         return 0
     if not args.test_path or not args.model_path:
         ap.error('give --test_path and --model_path, or --make_test_set, or --curve')
@@ -305,6 +345,10 @@ def main(argv=None):
     for spec in args.decoder:
         print(spec)
         print(torch.FloatTensor(res['baselines'][spec]['err_class']))
+        if 'ml_certified' in res['baselines'][spec]:
+            r = res['baselines'][spec]
+            print('ml_certified %d of %d words, certified_word_errors %d (a lower bound on the ML decoder\'s word errors)'
+                  % (r['ml_certified'], int(r['counts'][-1][2]), r['certified_word_errors']))
     return 0
 
 

@@ -17,6 +17,10 @@ default span, 64), each row the whole composition ``ldpc_decoders.Decoder.run`` 
 of the words it leaves with violated checks — to be read beside the plain min-sum:layered row; ``decoded`` is 1 there by construction.
 A third code, gallager(384, 3, 6, 1), sits between the two (128 threads per word).
 
+The ADMM linear-programming decoder (LdpcDataPath.decode_lp, csrc/ldpc_lp.hip) closes each code's rows as ``admm-lp`` (the plain LP:
+max_iter 200, stopped by its residual rule; one more column, the fraction of words that carry the ML certificate) and
+``admm-lp:penalty=0.8`` (the penalised decoder, stopped on a codeword), to be read beside the min-sum and sum-product rows.
+
     python tools/dbench.py [--words 4096] [--snr 2.0] [--repeats 7] [--learned_iters 5]
 """
 import argparse
@@ -100,10 +104,17 @@ def main():
         for share in SHARES:
             dec = LearnedMinSum(code, n, share, schedule='layered').to(dev)
             runs.append(('learned layered %s iters=%d' % (share, n), lambda dec=dec: dec.decode(llr)))
+        lp_bytes = _hip.invoke('fgnn_ldpc_decode_lp_lds_bytes', code.n_var, code.n_chk, E)
+        print('# %s: %d LDS bytes per word for decode_lp' % (name, lp_bytes))
+        for spec in ('admm-lp', 'admm-lp:penalty=0.8'):
+            if lp_bytes >= 0:
+                runs.append((spec, lambda kw=parse_decoder(spec).args: path.decode_lp(llr, **kw)))
         for label, run in runs:
-            med, lo, hi, (x, viol, iters) = measure(run, args.repeats)
-            print('%-24s %-34s %12.0f %10.1f %10.1f %9.2f %9.4f' % (name, label, args.words / med, med * 1e6, 100 * (hi - lo) / med,
-                                                                   iters.float().mean().item(), (viol == 0).float().mean().item()))
+            med, lo, hi, (x, viol, iters, *flags) = measure(run, args.repeats)
+            # the plain LP's last column: the fraction of words that carry the ML certificate (flag bit 1)
+            certified = '   certified %.4f' % (flags[0] & 2 != 0).float().mean().item() if label == 'admm-lp' else ''
+            print('%-24s %-34s %12.0f %10.1f %10.1f %9.2f %9.4f%s' % (name, label, args.words / med, med * 1e6, 100 * (hi - lo) / med,
+                                                                     iters.float().mean().item(), (viol == 0).float().mean().item(), certified))
 
 
 if __name__ == '__main__':
